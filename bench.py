@@ -10,6 +10,11 @@ BASELINE.json configs[2]: ViT-L/14 bf16, B=512, N=8, 1M-row bank, one GPU.
     python bench.py --gpus N --steps K --warmup W          # N > 1: starts N ranks itself
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step` = one
+timed step).  --full adds everything else the line can carry: the profile pass (roofline, per-kernel
+times), the live HBM-traffic passes, the extras (other precisions, API rates, PGD, SD, ...) and the CPU
+baselines.  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy.
+
 Multi-GPU (one process per GPU, torch.distributed backend nccl = RCCL over xGMI):
   * default: queries are data-parallel (encoders + bank replicated per GPU, no
     collective on the data path) -> "scaling": "weak";
@@ -46,12 +51,18 @@ def parse(argv=None):
     p.add_argument("--variants", type=int, default=8)
     p.add_argument("--bank-rows", type=int, default=None,
                    help="bank rows (default 1 000 000 = configs[2]; 10 000 000 with --shard-bank = configs[3])")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beyond the headline figure: the profile pass (roofline, per-kernel times), the "
+                        "live HBM-traffic passes, the extras and the CPU baselines (default: set up, warm up, time the steps, "
+                        "print the line)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step returned as DIR/<name>.npy (float32 / float64)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     p.add_argument("--cpu-seconds", type=float, default=20.0)
     p.add_argument("--no-extras", action="store_true",
-                   help="skip the extra measurements of the default N=1 run (dense-text rate, through-the-API rates, "
+                   help="--full: skip the extra measurements of the N=1 run (dense-text rate, through-the-API rates, "
                         "reference-schedule / 1-thread / configs[0] CPU baselines)")
-    p.add_argument("--no-profile-pass", action="store_true")
+    p.add_argument("--no-profile-pass", action="store_true", help="--full: skip the profile pass (roofline)")
     p.add_argument("--shard-bank", action="store_true",
                    help="BASELINE configs[3]: --bank-rows is the GLOBAL bank, row-sharded over the ranks; "
                         "partial top-k lists are exchanged with RCCL (all-gather + all-to-all) and merged on the GPU")
@@ -74,7 +85,7 @@ def parse(argv=None):
                         "kernel sees no references); default: neighbours of the text rows are planted")
     p.add_argument("--no-live-traffic", action="store_true",
                    help="do not measure roofline.traffic live (two rocprofv3 --pmc child passes of this command with --steps 1, "
-                        "run BEFORE this process touches the GPU; the default N=1 run does, ~1.5 min); fall back to the committed profile")
+                        "run BEFORE this process touches the GPU; a --full N=1 run does, ~1.5 min); fall back to the committed profile")
     p.add_argument("--sd-model", default="runwayml/stable-diffusion-v1-5",
                    help="latent-diffusion geometry of the sd_reference extra: the reference's default (src/sd_ref.py:221) or "
                         "'stabilityai/stable-diffusion-2-1-base' (src/__init__.py:110-113)")
@@ -85,6 +96,10 @@ def parse(argv=None):
                         "gloo group, run the barrier + max-over-ranks reduction and rank 0 prints a line with "
                         '"dry_run": true and value 0 -- never a measurement')
     a = p.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:
+        a.no_cpu_baseline = a.no_extras = a.no_profile_pass = a.no_live_traffic = True
     if a.bank_rows is None:
         a.bank_rows = 10_000_000 if a.shard_bank else 1_000_000
     return a
@@ -246,6 +261,23 @@ class WordReplaceVariants:
         return out
 
 
+def dump_outputs(out_dir, rec, img_idx, n_variants, lib):
+    """--dump-outputs: what the last timed step returned to its caller (rank 0's queries), split as
+    detector.unpack_records splits the records (layout: include/tvc.h); integer words as exact float64."""
+    import numpy as np
+    r = rec.numpy()
+    h, M = lib.TVC_REC_HEAD + n_variants, lib.TVC_REC_MAXREF
+    arrays = {
+        "record_scores": r[:, :h],                                                        # head words + variant similarities
+        "record_reference_indices": np.ascontiguousarray(r[:, h:h + M]).view(np.int32).astype(np.float64),
+        "record_reference_similarities": r[:, h + M:h + 2 * M],
+        "image_topk_indices": img_idx.numpy().astype(np.float64),                         # bank rows nearest each image
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(x))
+
+
 def make_captions(n, seed=3):
     import random
     rng = random.Random(seed)
@@ -258,7 +290,7 @@ def main():
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a))
 
-    # PMC passes run as child processes BEFORE anything here touches the GPU (default N=1 run of the default workload only)
+    # PMC passes run as child processes BEFORE anything here touches the GPU (--full N=1 run of the default workload only)
     live_traffic = None
     if (int(os.environ.get("WORLD_SIZE", "1")) == 1 and not a.no_live_traffic and not a.no_extras and not a.no_profile_pass
             and not a.shard_bank and not a.dry_run_launch):
@@ -452,13 +484,15 @@ def main():
         sync()
         return time.perf_counter() - t0, out
 
-    dt, (rec, _) = timed(step, a.steps, a.warmup)
+    dt, (rec, img_idx) = timed(step, a.steps, a.warmup)
     if world > 1:
         t = torch.tensor([dt], device="cpu" if a.rehearse_one_gpu else dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     if not a.shard_bank:
         eng.bank_status()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, rec, img_idx, N, pkg._lib)
     assert torch.isfinite(rec[:, :11]).all()      # words >= 12+N hold int32 bit patterns (-1 = NaN bits)
     kept_refs = float(rec[:, 8].mean())           # references kept per query by the consistency kernel
 

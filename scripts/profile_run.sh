@@ -2,10 +2,10 @@ set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/${ROUND:-r03}a
 mkdir -p $O
-python bench.py --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err
+python bench.py --full --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err
 tail -c 3000 $O/bench.json
 echo "--- kernel trace"
-rocprofv3 --kernel-trace --stats -d $O/ktrace -o kt --output-format csv -- python3 bench.py --steps 5 --warmup 2 --serial-towers --no-cpu-baseline --no-extras > $O/kt_bench.json 2> $O/kt.err
+rocprofv3 --kernel-trace --stats -d $O/ktrace -o kt --output-format csv -- python3 bench.py --full --steps 5 --warmup 2 --serial-towers --no-cpu-baseline --no-extras > $O/kt_bench.json 2> $O/kt.err
 ls $O/ktrace | head
 echo "--- pmc mfma"
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE -d $O/pmc_mfma -o m --output-format csv -- python3 bench.py --steps 1 --warmup 1 --serial-towers --no-cpu-baseline --no-extras --no-profile-pass > $O/pmc_mfma.json 2> $O/pmc_mfma.err || echo "pmc mfma failed"

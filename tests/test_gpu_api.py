@@ -334,6 +334,44 @@ def test_bench_gpus_flag_runs_two_ranks_on_one_gpu(pkg):
             assert "all_to_all_single" in out["distributed"]["data_path_collectives"]
 
 
+def test_bench_plain_run_dumps_its_outputs_and_full_adds_the_rest(pkg, tmp_path):
+    """A plain `bench.py` run times the steps and prints the line, nothing more; `--dump-outputs DIR` writes what the last
+    timed step returned, identical from run to run on the same arguments.  `--full` adds the profile pass, extras and CPU
+    baselines to the same line."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = Path(__file__).resolve().parents[1]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    base = [sys.executable, str(root / "bench.py"), "--gpus", "1", "--model", "ViT-T/16-test", "--batch", "16",
+            "--variants", "2", "--bank-rows", "4096", "--warmup", "1"]
+
+    def run(*extra):
+        r = subprocess.run(base + list(extra), capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    dumps = []
+    for tag in ("a", "b"):
+        out = run("--steps", "3", "--dump-outputs", str(tmp_path / tag))
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["higher_is_better"] is True
+        assert out["roofline"] is None and "cpu_baseline" not in out and "parity_mode" not in out
+        dumps.append({f.stem: np.load(f) for f in sorted((tmp_path / tag).glob("*.npy"))})
+    a, b = dumps
+    assert set(a) == {"record_scores", "record_reference_indices", "record_reference_similarities", "image_topk_indices"}
+    assert a["record_scores"].shape == (16, pkg._lib.TVC_REC_HEAD + 2) and a["image_topk_indices"].shape[0] == 16
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64)
+        np.testing.assert_array_equal(a[name], b[name], err_msg=name)
+    assert (a["record_reference_indices"] >= 0).any()              # planted neighbours: references were kept
+    full = run("--steps", "2", "--full", "--no-live-traffic", "--cpu-seconds", "1")
+    assert full["steps"] == 2 and full["roofline"]["achieved"] > 0
+    assert "cpu_baseline" in full and "parity_mode" in full and "pgd_inner_loop" in full
+
+
 def test_text_variant_generator_clip_filter(pkg, clip):
     """rule candidates + the CLIP semantic window + ranking
     (experiments/defenses/text_variants.py:206-284), all candidates of all texts in ONE text encode.  The
