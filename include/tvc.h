@@ -189,7 +189,15 @@ const char* tvc_last_error(tvc_handle* h);
  * residual stream, LayerNorm, softmax and QuickGELU.  Scores within 1e-4 of the reference's fp32 CPU path END TO END at
  * about a third of the bf16 mode's matrix rate (mode 1: 1/16); EOT packing and prefix sharing are kept, the pooled last
  * layer is not.  Needs tvc_set_weights_f32 first; setting the option builds the weight planes (synchronises the device).
- * Geometry limits: head_dim 64 and sequences of at most 288 tokens in modes 0 and 1 (tvc_create refuses other towers),
+ * 3 = fp16 towers: the bf16 mode's launches, tiles and workspaces with IEEE fp16 instead of bf16 -- the fp16 weights
+ * registered by tvc_set_weights_f16, fp16 LayerNorm outputs, QKV, attention output, MLP hidden and residual deltas, the
+ * products on v_mfma_f32_16x16x32_f16 (the bf16 rate) with fp32 accumulation; fp32 residual stream, LayerNorm statistics,
+ * softmax, bias and activations.  fp16 keeps 10 mantissa bits to bf16's 7 but its range ends at 65504: a value beyond it
+ * becomes +-inf (never clamped) and the embedding goes non-finite.  EOT packing, prefix sharing and the pooled last layer
+ * are kept, each with its bf16 guarantee.  The reference runs its towers in fp16 (configs/defenses/tvc.yaml: precision).
+ * Needs tvc_set_weights_f16 first (TVC_E_INVALID otherwise: without fp16 weights the handle offers no mode 3).
+ * The input-gradient entry points run the bf16 path in every mode.
+ * Geometry limits: head_dim 64 and sequences of at most 288 tokens in modes 0, 1 and 3 (tvc_create refuses other towers),
  * at most 272 tokens in mode 2 (TVC_E_INVALID when the option is set).
  * TVC_OPT_SD_ARENA_BYTES (default 48 GiB): budget of the activation arena of ONE UNet evaluation inside tvc_sd_generate.
  * The arena grows linearly with the samples of an evaluation (about 0.75 GB per image at 64 x 64 latents: both halves of
@@ -208,6 +216,11 @@ int tvc_set_option(tvc_handle* h, int32_t option, int64_t value);
  * copied: the caller keeps the buffers alive.  Geometry = the desc given to tvc_create.
  * Replaces: loading the fp32 checkpoint in the (absent) src.models CLIPModel -- src/detector.py:258-271. */
 int tvc_set_weights_f32(tvc_handle* h, const tvc_vision_weights_f32* vision, const tvc_text_weights_f32* text);
+
+/* Register IEEE fp16 tower weights for TVC_OPT_TOWER_PRECISION = 3 (either may be NULL): the structs and layout of
+ * tvc_create with every uint16_t* weight holding fp16 bits (patch_w padded to Kp columns like the bf16 one); the fp32
+ * fields may alias the bf16 set's buffers.  Referenced, not copied.  Geometry = the desc given to tvc_create. */
+int tvc_set_weights_f16(tvc_handle* h, const tvc_vision_weights* vision, const tvc_text_weights* text);
 
 /* Bytes of device workspace currently held by the handle. */
 uint64_t tvc_workspace_bytes(tvc_handle* h);
@@ -421,6 +434,17 @@ int tvc_attention(tvc_handle* h, const uint16_t* qkv_dev, uint16_t* out_dev,
 /* y bf16 [rows, d] = LayerNorm(x fp32 [rows, d]) * g + b, eps 1e-5. */
 int tvc_layernorm(tvc_handle* h, const float* x_dev, const float* g_dev, const float* b_dev,
                   uint16_t* y_dev, int32_t rows, int32_t d, void* stream);
+
+/* fp16 twins of the three blocks above (TVC_OPT_TOWER_PRECISION = 3): every 16-bit operand and output is IEEE fp16
+ * (tvc_gemm_f16: epilogues 1 / 2 store fp16, an output beyond 65504 becomes +-inf).  tvc_attention_f16 also takes
+ * starts_dev: int32 [n_seq + 1] = packed sequences of at most seq_len rows, or NULL = n_seq x seq_len dense rows. */
+int tvc_gemm_f16(tvc_handle* h, const uint16_t* a_dev, const uint16_t* b_dev,
+                 const float* bias_dev, void* out_dev, int32_t I, int32_t J, int32_t K,
+                 int64_t lda, int64_t ldb, int32_t ld_out, int32_t epilogue, void* stream);
+int tvc_attention_f16(tvc_handle* h, const uint16_t* qkv_dev, uint16_t* out_dev, const int32_t* starts_dev,
+                      int32_t n_seq, int32_t seq_len, int32_t heads, int32_t causal, void* stream);
+int tvc_layernorm_f16(tvc_handle* h, const float* x_dev, const float* g_dev, const float* b_dev,
+                      uint16_t* y_dev, int32_t rows, int32_t d, void* stream);
 
 /* Backward of tvc_attention (non-causal, fixed-length sequences, head_dim 64): qkv as the forward saw it,
  * dout bf16 [rows, width] = gradient w.r.t. the attention output, dqkv bf16 [rows, 3*width] (dq | dk | dv). */

@@ -127,6 +127,12 @@ SIGNATURES = {
     "tvc_attention_f32": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "tvc_gemm_split": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "tvc_attention_split": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    # fp16 towers: the bf16 weight structs holding fp16 bits; fp16 twins of the bf16 building blocks
+    "tvc_set_weights_f16": (C.c_int, [_P, C.POINTER(VisionWeights), C.POINTER(TextWeights)]),
+    "tvc_gemm_f16": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+                               C.c_int32, _P]),
+    "tvc_attention_f16": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "tvc_layernorm_f16": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     # latent-diffusion reference generator
     "tvc_sd_load": (C.c_int, [_P, C.POINTER(SDDesc), C.POINTER(NamedTensor), C.c_int32, _P]),
     "tvc_sd_unet": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P, _P]),

@@ -43,6 +43,8 @@ class CLIPConfig:
     tokenizer_dir: Optional[str] = None   # directory with CLIP BPE vocab.json + merges.txt
     precision: str = "bf16"               # "split": fp32-grade towers at ~1/3 of the bf16 rate (scores within 1e-4 end to end);
                                           # "fp32": the exact-f32 reference mode (~1e-6; ~15x slower)
+                                          # "fp16": IEEE fp16 towers at the bf16 rate (the reference's
+                                          # configs/defenses/tvc.yaml precision: "fp16"; overflow beyond 65504 -> inf)
 
 
 class HashTokenizer:

@@ -73,7 +73,9 @@
 #else
 #define ATT_ST_O(p_, v_) (*(p_) = (v_))
 #endif
-template <int MAXT, bool CAUSAL, int WPS, bool EXACT = false, int NW = 4>
+// F16: qkv / out are IEEE fp16 and both products run on v_mfma_f32_16x16x32_f16 (tower mode 3); the K / V images and the
+// transposed reads move 16-bit values whatever they encode.
+template <int MAXT, bool CAUSAL, int WPS, bool EXACT = false, int NW = 4, bool F16 = false>
 __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16_t* __restrict__ qkv,
                                                         uint16_t* __restrict__ out,
                                                         const int32_t* __restrict__ starts, int T_fixed,
@@ -152,8 +154,9 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
         qrow = qrow < own ? qrow : own - 1;
         return qkv + (row0 + qrow) * ld + h * ATT_DH + 8 * g;
     };
-    bf16x8_t nq0 = {}, nq1 = {};
-    if (wsub < NQ) { const uint16_t* qp = q_ptr(wsub); nq0 = ATT_LD_Q((const bf16x8_t*)qp); nq1 = ATT_LD_Q((const bf16x8_t*)(qp + 32)); }
+    typedef typename Op16<F16>::x8 x8;
+    x8 nq0 = {}, nq1 = {};
+    if (wsub < NQ) { const uint16_t* qp = q_ptr(wsub); nq0 = ATT_LD_Q((const x8*)qp); nq1 = ATT_LD_Q((const x8*)(qp + 32)); }
 
     // ---- fill K / V images (zero beyond T).  ALL global loads of the item -- both images and the first query block --
     // are issued before the first LDS write, so the workgroup pays ONE memory latency per item.  The loads are
@@ -198,18 +201,18 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
     // pointer the compiler cannot prove loop-invariant -- with all 17 pinned (what hipcc's own hoisting did) the block
     // below needs 262 registers once its running max is the three-operand form, and spills.
     constexpr int KPIN = EXACT ? (MAXT > 15 ? 15 : MAXT) : 0;
-    bf16x8_t ka[KPIN > 0 ? KPIN : 1], kb[KPIN > 0 ? KPIN : 1];
+    x8 ka[KPIN > 0 ? KPIN : 1], kb[KPIN > 0 ? KPIN : 1];
     if (EXACT) {
 #pragma unroll
         for (int t = 0; t < KPIN; ++t) {
-            ka[t] = *(const bf16x8_t*)(ldsK + (t * 16 + r16) * ATT_KROW + sw0);
-            kb[t] = *(const bf16x8_t*)(ldsK + (t * 16 + r16) * ATT_KROW + sw1);
+            ka[t] = *(const x8*)(ldsK + (t * 16 + r16) * ATT_KROW + sw0);
+            kb[t] = *(const x8*)(ldsK + (t * 16 + r16) * ATT_KROW + sw1);
         }
     }
     for (int qb = wsub; qb < NQ; qb += WPS) {
         const int qr = qb * 16 + r16;
-        const bf16x8_t bq0 = nq0, bq1 = nq1;
-        if (qb + WPS < NQ) { const uint16_t* qp = q_ptr(qb + WPS); nq0 = ATT_LD_Q((const bf16x8_t*)qp); nq1 = ATT_LD_Q((const bf16x8_t*)(qp + 32)); }
+        const x8 bq0 = nq0, bq1 = nq1;
+        if (qb + WPS < NQ) { const uint16_t* qp = q_ptr(qb + WPS); nq0 = ATT_LD_Q((const x8*)qp); nq1 = ATT_LD_Q((const x8*)(qp + 32)); }
         // absolute positions of the block's first / last query and of this lane's query
         const int qmin = pool_mode ? pool_pos : P + qb * 16;
         const int qmax = pool_mode ? pool_pos : qmin + 15;
@@ -229,13 +232,13 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
 #pragma unroll
             for (int t = 0; t < MAXT; ++t) {
                 const f32x4_t c0 = (t == MAXT - 1) ? pen_tail : f32x4_t{0.f, 0.f, 0.f, 0.f};
-                const bf16x8_t a0 = t < KPIN ? ka[t < KPIN ? t : 0] : *(const bf16x8_t*)(ldsK_i + (t * 16 + r16) * ATT_KROW + sw0);
-                s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, bq0, c0, 0, 0, 0);
+                const x8 a0 = t < KPIN ? ka[t < KPIN ? t : 0] : *(const x8*)(ldsK_i + (t * 16 + r16) * ATT_KROW + sw0);
+                s[t] = Op16<F16>::mfma(a0, bq0, c0);
             }
 #pragma unroll
             for (int t = 0; t < MAXT; ++t) {
-                const bf16x8_t a1 = t < KPIN ? kb[t < KPIN ? t : 0] : *(const bf16x8_t*)(ldsK_i + (t * 16 + r16) * ATT_KROW + sw1);
-                s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, bq1, s[t], 0, 0, 0);
+                const x8 a1 = t < KPIN ? kb[t < KPIN ? t : 0] : *(const x8*)(ldsK_i + (t * 16 + r16) * ATT_KROW + sw1);
+                s[t] = Op16<F16>::mfma(a1, bq1, s[t]);
             }
             // IEEE-754-2019 maximum (NaN-propagating): hipcc emits v_maximum3_f32 with no canonicalising copy of the
             // MFMA outputs -- 54 max instructions per block where fmaxf costs 121.  A NaN score makes the query's
@@ -259,10 +262,10 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
                         if (t * 16 + 4 * g + r > qpos) c0[r] = -INFINITY;
                 }
                 const char* kr = ldsK + (t * 16 + r16) * ATT_KROW;
-                const bf16x8_t a0 = *(const bf16x8_t*)(kr + sw0);
-                const bf16x8_t a1 = *(const bf16x8_t*)(kr + sw1);
-                c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, bq0, c0, 0, 0, 0);
-                s[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, bq1, c0, 0, 0, 0);
+                const x8 a0 = *(const x8*)(kr + sw0);
+                const x8 a1 = *(const x8*)(kr + sw1);
+                c0 = Op16<F16>::mfma(a0, bq0, c0);
+                s[t] = Op16<F16>::mfma(a1, bq1, c0);
                 mx = fmaxf(mx, fmaxf(fmaxf(s[t][0], s[t][1]), fmaxf(s[t][2], s[t][3])));
             }
         }
@@ -284,7 +287,8 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
         // and two cross-lane shuffles per query block sat on the vector issue slots that bound it).  The sum is
         // over the SAME bf16-rounded probabilities the numerator uses.
         f32x4_t osum = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        const bf16x8_t ones = __builtin_bit_cast(bf16x8_t, u32x4_t{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u});
+        constexpr uint32_t one2 = Op16<F16>::ONE2;
+        const x8 ones = __builtin_bit_cast(x8, u32x4_t{one2, one2, one2, one2});
 
         f32x4_t o[4];
 #pragma unroll
@@ -297,11 +301,11 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
                 const f32x4_t p0 = s[t0];
                 const f32x4_t p1 = (t1 < MAXT) ? s[t1 < MAXT ? t1 : 0] : f32x4_t{0.f, 0.f, 0.f, 0.f};
                 u32x4_t pk;
-                pk[0] = pack_bf16x2(p0[0], p0[1]);
-                pk[1] = pack_bf16x2(p0[2], p0[3]);
-                pk[2] = pack_bf16x2(p1[0], p1[1]);
-                pk[3] = pack_bf16x2(p1[2], p1[3]);
-                const bf16x8_t pb = __builtin_bit_cast(bf16x8_t, pk);
+                pk[0] = Op16<F16>::pack2(p0[0], p0[1]);
+                pk[1] = Op16<F16>::pack2(p0[2], p0[3]);
+                pk[2] = Op16<F16>::pack2(p1[0], p1[1]);
+                pk[3] = Op16<F16>::pack2(p1[2], p1[3]);
+                const x8 pb = __builtin_bit_cast(x8, pk);
 #pragma unroll
                 for (int md = 0; md < 4; ++md) {
                     const char* vb = ldsV + tr_off + md * 32;
@@ -312,9 +316,9 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
                     bf16x8_t a;
                     a[0] = v0[0]; a[1] = v0[1]; a[2] = v0[2]; a[3] = v0[3];
                     a[4] = v1[0]; a[5] = v1[1]; a[6] = v1[2]; a[7] = v1[3];
-                    o[md] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, pb, o[md], 0, 0, 0);
+                    o[md] = Op16<F16>::mfma(__builtin_bit_cast(x8, a), pb, o[md]);
                 }
-                osum = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pb, osum, 0, 0, 0);
+                osum = Op16<F16>::mfma(ones, pb, osum);
             }
         }
         // The NEXT block's query fragments are waited for HERE, before this block's stores are issued: vmcnt counts
@@ -333,8 +337,8 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
 #pragma unroll
         for (int mp = 0; mp < 2; ++mp) {
             const f32x4_t v0 = o[2 * mp] * inv, v1 = o[2 * mp + 1] * inv;
-            const auto r0 = __builtin_amdgcn_permlane16_swap(pack_bf16x2(v0[0], v0[1]), pack_bf16x2(v1[0], v1[1]), false, false);
-            const auto r1 = __builtin_amdgcn_permlane16_swap(pack_bf16x2(v0[2], v0[3]), pack_bf16x2(v1[2], v1[3]), false, false);
+            const auto r0 = __builtin_amdgcn_permlane16_swap(Op16<F16>::pack2(v0[0], v0[1]), Op16<F16>::pack2(v1[0], v1[1]), false, false);
+            const auto r1 = __builtin_amdgcn_permlane16_swap(Op16<F16>::pack2(v0[2], v0[3]), Op16<F16>::pack2(v1[2], v1[3]), false, false);
             ow[mp][0] = r0[0]; ow[mp][1] = r1[0]; ow[mp][2] = r0[1]; ow[mp][3] = r1[1];
         }
         if (pool_mode ? (r16 == 0) : (qr < own)) {
@@ -345,7 +349,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
     }
 }
 
-template <int MAXT, bool CAUSAL, int WPS, bool EXACT = false, int NW = 4>
+template <int MAXT, bool CAUSAL, int WPS, bool EXACT = false, int NW = 4, bool F16 = false>
 static hipError_t launch_one(const uint16_t* qkv, uint16_t* out, const int32_t* starts, int n_seq, int T,
                              int max_T, int heads, hipStream_t stream, const int32_t* pfx = nullptr,
                              int pool_mode = 0, const int32_t* pool_row = nullptr) {
@@ -359,12 +363,12 @@ static hipError_t launch_one(const uint16_t* qkv, uint16_t* out, const int32_t* 
     static std::once_flag attr_once;          // per instantiation; thread-safe
     static hipError_t attr_st = hipSuccess;
     std::call_once(attr_once, [] {
-        attr_st = hipFuncSetAttribute((const void*)attention_kernel<MAXT, CAUSAL, WPS, EXACT, NW>,
+        attr_st = hipFuncSetAttribute((const void*)attention_kernel<MAXT, CAUSAL, WPS, EXACT, NW, F16>,
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
     });
     if (attr_st != hipSuccess) return attr_st;
     const int n_items = n_seq * heads;
-    hipLaunchKernelGGL((attention_kernel<MAXT, CAUSAL, WPS, EXACT, NW>), dim3((n_items + IPW - 1) / IPW), dim3(NW * 64), lds, stream,
+    hipLaunchKernelGGL((attention_kernel<MAXT, CAUSAL, WPS, EXACT, NW, F16>), dim3((n_items + IPW - 1) / IPW), dim3(NW * 64), lds, stream,
                        qkv, out, starts, T, heads, n_items, k_bytes, region, pfx, n_seq, pool_mode, pool_row);
     return hipGetLastError();
 }
@@ -374,23 +378,31 @@ static hipError_t launch_one(const uint16_t* qkv, uint16_t* out, const int32_t* 
 // pool_mode 0: every row's output, token-major [rows, width].  1 / 2: only the pooled token of every sequence
 // (1 = its first token, 2 = its EOT token: the last packed row, or packed row pool_row[s] for dense rows), written
 // to the compact row s of `out` [n_seq, width] -- what the LAST layer of a tower needs.
-hipError_t launch_attention(const uint16_t* qkv, uint16_t* out, const int32_t* starts, int n_seq, int seq_len,
-                            int heads, int causal, hipStream_t stream, const int32_t* pfx, int pool_mode,
-                            const int32_t* pool_row) {
+template <bool F16>
+static hipError_t launch_attention_t(const uint16_t* qkv, uint16_t* out, const int32_t* starts, int n_seq, int seq_len,
+                                     int heads, int causal, hipStream_t stream, const int32_t* pfx, int pool_mode,
+                                     const int32_t* pool_row) {
     if (n_seq <= 0) return hipSuccess;
     if (seq_len < 1 || seq_len > 288 || heads < 1 || pool_mode < 0 || pool_mode > 2) return hipErrorInvalidValue;
     if (pool_mode == 2 && !starts && !pool_row) return hipErrorInvalidValue;
     const int NT = (seq_len + 15) / 16;
     if (causal) {
         if (pfx && !starts) return hipErrorInvalidValue;
-        if (NT <= 2) return launch_one<2, true, 1>(qkv, out, starts, n_seq, seq_len, seq_len, heads, stream, pfx, pool_mode, pool_row);
-        if (NT <= 6) return launch_one<6, true, 2>(qkv, out, starts, n_seq, seq_len, seq_len, heads, stream, pfx, pool_mode, pool_row);
-        return launch_one<18, true, 4>(qkv, out, starts, n_seq, seq_len, seq_len, heads, stream, pfx, pool_mode, pool_row);
+        if (NT <= 2) return launch_one<2, true, 1, false, 4, F16>(qkv, out, starts, n_seq, seq_len, seq_len, heads, stream, pfx, pool_mode, pool_row);
+        if (NT <= 6) return launch_one<6, true, 2, false, 4, F16>(qkv, out, starts, n_seq, seq_len, seq_len, heads, stream, pfx, pool_mode, pool_row);
+        return launch_one<18, true, 4, false, 4, F16>(qkv, out, starts, n_seq, seq_len, seq_len, heads, stream, pfx, pool_mode, pool_row);
     }
-    if (!starts && NT == 17) return launch_one<17, false, 4, true>(qkv, out, starts, n_seq, seq_len, seq_len, heads, stream, nullptr, pool_mode, pool_row);   // ViT-L/14: 257 tokens
-    if (!starts && NT == 4) return launch_one<4, false, 2, true>(qkv, out, starts, n_seq, seq_len, seq_len, heads, stream, nullptr, pool_mode, pool_row);     // ViT-B/32: 50 tokens
-    if (NT <= 2) return launch_one<2, false, 1>(qkv, out, starts, n_seq, seq_len, seq_len, heads, stream, nullptr, pool_mode, pool_row);
-    if (NT <= 4) return launch_one<4, false, 2>(qkv, out, starts, n_seq, seq_len, seq_len, heads, stream, nullptr, pool_mode, pool_row);
-    if (NT <= 6) return launch_one<6, false, 4>(qkv, out, starts, n_seq, seq_len, seq_len, heads, stream, nullptr, pool_mode, pool_row);
-    return launch_one<18, false, 4>(qkv, out, starts, n_seq, seq_len, seq_len, heads, stream, nullptr, pool_mode, pool_row);
+    if (!starts && NT == 17) return launch_one<17, false, 4, true, 4, F16>(qkv, out, starts, n_seq, seq_len, seq_len, heads, stream, nullptr, pool_mode, pool_row);   // ViT-L/14: 257 tokens
+    if (!starts && NT == 4) return launch_one<4, false, 2, true, 4, F16>(qkv, out, starts, n_seq, seq_len, seq_len, heads, stream, nullptr, pool_mode, pool_row);     // ViT-B/32: 50 tokens
+    if (NT <= 2) return launch_one<2, false, 1, false, 4, F16>(qkv, out, starts, n_seq, seq_len, seq_len, heads, stream, nullptr, pool_mode, pool_row);
+    if (NT <= 4) return launch_one<4, false, 2, false, 4, F16>(qkv, out, starts, n_seq, seq_len, seq_len, heads, stream, nullptr, pool_mode, pool_row);
+    if (NT <= 6) return launch_one<6, false, 4, false, 4, F16>(qkv, out, starts, n_seq, seq_len, seq_len, heads, stream, nullptr, pool_mode, pool_row);
+    return launch_one<18, false, 4, false, 4, F16>(qkv, out, starts, n_seq, seq_len, seq_len, heads, stream, nullptr, pool_mode, pool_row);
+}
+
+hipError_t launch_attention(const uint16_t* qkv, uint16_t* out, const int32_t* starts, int n_seq, int seq_len,
+                            int heads, int causal, hipStream_t stream, const int32_t* pfx, int pool_mode,
+                            const int32_t* pool_row, int f16) {
+    return f16 ? launch_attention_t<true>(qkv, out, starts, n_seq, seq_len, heads, causal, stream, pfx, pool_mode, pool_row)
+               : launch_attention_t<false>(qkv, out, starts, n_seq, seq_len, heads, causal, stream, pfx, pool_mode, pool_row);
 }

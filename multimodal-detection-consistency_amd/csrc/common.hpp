@@ -27,6 +27,52 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
     return __builtin_bit_cast(uint32_t, v);
 }
 
+// IEEE fp16 (TVC_OPT_TOWER_PRECISION = 3).  The casts round to nearest even (v_cvt_pk_f16_f32) and overflow to +-inf;
+// the round-toward-zero packer (which also saturates at 65504) is deliberately not used.
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
+
+__device__ __forceinline__ float f16_bits_to_f32(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
+__device__ __forceinline__ uint16_t f32_to_f16_bits(float f) {
+    _Float16 v = (_Float16)f;
+    return __builtin_bit_cast(uint16_t, v);
+}
+__device__ __forceinline__ uint32_t pack_f16x2(float lo, float hi) {
+    f16x2_t v;
+    v[0] = (_Float16)lo;
+    v[1] = (_Float16)hi;
+    return __builtin_bit_cast(uint32_t, v);
+}
+// the two 16-bit values of a packed pair as fp32 (lo = element 0)
+__device__ __forceinline__ float f16x2_lo(uint32_t w) { return (float)__builtin_bit_cast(f16x2_t, w)[0]; }
+__device__ __forceinline__ float f16x2_hi(uint32_t w) { return (float)__builtin_bit_cast(f16x2_t, w)[1]; }
+
+// The 16-bit operand format of the tower kernels, a compile-time parameter: bf16 (F16 = false) or IEEE fp16 (F16 = true).
+// Same bytes per element, same LDS images and fragment layouts; only the MFMA and the conversions differ.
+template <bool F16> struct Op16;
+template <> struct Op16<false> {
+    typedef bf16x8_t x8;
+    static constexpr uint32_t ONE2 = 0x3f803f80u;           // two 1.0 values
+    __device__ static __forceinline__ f32x4_t mfma(x8 a, x8 b, f32x4_t c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    }
+    __device__ static __forceinline__ uint32_t pack2(float lo, float hi) { return pack_bf16x2(lo, hi); }
+    __device__ static __forceinline__ uint16_t from_f32(float f) { return f32_to_bf16_bits(f); }
+    __device__ static __forceinline__ float lo(uint32_t w) { return __uint_as_float(w << 16); }
+    __device__ static __forceinline__ float hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+};
+template <> struct Op16<true> {
+    typedef f16x8_t x8;
+    static constexpr uint32_t ONE2 = 0x3c003c00u;
+    __device__ static __forceinline__ f32x4_t mfma(x8 a, x8 b, f32x4_t c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+    }
+    __device__ static __forceinline__ uint32_t pack2(float lo, float hi) { return pack_f16x2(lo, hi); }
+    __device__ static __forceinline__ uint16_t from_f32(float f) { return f32_to_f16_bits(f); }
+    __device__ static __forceinline__ float lo(uint32_t w) { return f16x2_lo(w); }
+    __device__ static __forceinline__ float hi(uint32_t w) { return f16x2_hi(w); }
+};
+
 // wave-level all-lane sum / max over 64 lanes
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -20,8 +20,9 @@
 // operand).  With `delta` the residual GEMMs stay store-only: the previous
 // projection's output is folded into the fp32 residual stream here, in the same
 // streaming pass that normalises it (x is written back when `write_x`).
-// d % 4 == 0, d <= 1024.
+// d % 4 == 0, d <= 1024.  F16: the deltas and y are IEEE fp16 (tower mode 3).
 // ---------------------------------------------------------------------------
+template <bool F16>
 __global__ __launch_bounds__(256) void layernorm_kernel(float* __restrict__ x, int64_t x_row_stride,
                                                         const int32_t* __restrict__ row_idx,
                                                         const uint16_t* __restrict__ delta,
@@ -59,17 +60,17 @@ __global__ __launch_bounds__(256) void layernorm_kernel(float* __restrict__ x, i
 #else
                 const u32x2_t dd = dr[c];
 #endif
-                v[i][0] += __uint_as_float(dd[0] << 16);
-                v[i][1] += __uint_as_float(dd[0] & 0xffff0000u);
-                v[i][2] += __uint_as_float(dd[1] << 16);
-                v[i][3] += __uint_as_float(dd[1] & 0xffff0000u);
+                v[i][0] += Op16<F16>::lo(dd[0]);
+                v[i][1] += Op16<F16>::hi(dd[0]);
+                v[i][2] += Op16<F16>::lo(dd[1]);
+                v[i][3] += Op16<F16>::hi(dd[1]);
             }
             if (dr2) {
                 const u32x2_t dd = dr2[c];
-                v[i][0] += __uint_as_float(dd[0] << 16);
-                v[i][1] += __uint_as_float(dd[0] & 0xffff0000u);
-                v[i][2] += __uint_as_float(dd[1] << 16);
-                v[i][3] += __uint_as_float(dd[1] & 0xffff0000u);
+                v[i][0] += Op16<F16>::lo(dd[0]);
+                v[i][1] += Op16<F16>::hi(dd[0]);
+                v[i][2] += Op16<F16>::lo(dd[1]);
+                v[i][3] += Op16<F16>::hi(dd[1]);
             }
 #if TVC_LN_NT & 2
             if (write_x && (dr || dr2)) __builtin_nontemporal_store(v[i], xr + c);
@@ -107,8 +108,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(float* __restrict__ x, i
             if (y32) ((f32x4_t*)(y32 + (int64_t)row * d))[c] = o;      // fp32 copy (hidden-state outputs)
             if (y) {
                 u32x2_t pk;
-                pk[0] = pack_bf16x2(o[0], o[1]);
-                pk[1] = pack_bf16x2(o[2], o[3]);
+                pk[0] = Op16<F16>::pack2(o[0], o[1]);
+                pk[1] = Op16<F16>::pack2(o[2], o[3]);
 #if TVC_LN_NT & 8
                 __builtin_nontemporal_store(pk, yr + c);
 #else
@@ -121,19 +122,25 @@ __global__ __launch_bounds__(256) void layernorm_kernel(float* __restrict__ x, i
 
 hipError_t launch_layernorm(float* x, int64_t x_row_stride, const int32_t* row_idx, const uint16_t* delta,
                             int write_x, const float* g, const float* b, uint16_t* y, int rows, int d,
-                            hipStream_t stream, const uint16_t* delta2, int delta_compact, float* xsum_out, float* y32) {
+                            hipStream_t stream, const uint16_t* delta2, int delta_compact, float* xsum_out, float* y32,
+                            int f16) {
     if (d % 4 != 0 || d > 1024 || rows < 0) return hipErrorInvalidValue;
     if (rows == 0) return hipSuccess;
     const int grid = (rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
-    hipLaunchKernelGGL(layernorm_kernel, dim3(grid), dim3(256), 0, stream, x, x_row_stride, row_idx, delta, delta2,
-                       write_x, g, b, y, rows, d, delta_compact, xsum_out, y32);
+    if (f16)
+        hipLaunchKernelGGL(layernorm_kernel<true>, dim3(grid), dim3(256), 0, stream, x, x_row_stride, row_idx, delta, delta2,
+                           write_x, g, b, y, rows, d, delta_compact, xsum_out, y32);
+    else
+        hipLaunchKernelGGL(layernorm_kernel<false>, dim3(grid), dim3(256), 0, stream, x, x_row_stride, row_idx, delta, delta2,
+                           write_x, g, b, y, rows, d, delta_compact, xsum_out, y32);
     return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------
 // im2col for the stride=patch conv: pix fp32 [B,3,S,S] -> bf16 [B*P, Kp],
-// column order (c, ky, kx) = the conv weight's flatten order; zero padded.
+// column order (c, ky, kx) = the conv weight's flatten order; zero padded.  F16: fp16 columns.
 // ---------------------------------------------------------------------------
+template <bool F16>
 __global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ pix,
                                                      uint16_t* __restrict__ out, int B, int S,
                                                      int patch, int Kp) {
@@ -165,7 +172,7 @@ __global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ p
                 }
                 f[h] = val;
             }
-            w[e] = pack_bf16x2(f[0], f[1]);
+            w[e] = Op16<F16>::pack2(f[0], f[1]);
         }
         *(u32x4_t*)(out + row * Kp + ch * 8) = u32x4_t{w[0], w[1], w[2], w[3]};
     }
@@ -175,6 +182,7 @@ __global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ p
 // rows (S floats contiguous: coalesced), converted and scattered into the LDS image of the g output rows, which are then
 // written as whole rows (Kp * 2 bytes contiguous).  The per-element kernel above reads 56-byte runs (patch 14) with one
 // scalar load per element: 1.75 TB/s against ~4.5 here.  S % 4 == 0 and g * Kp * 2 bytes of LDS (<= 64 KiB) required.
+template <bool F16>
 __global__ __launch_bounds__(256) void im2col_rows_kernel(const float* __restrict__ pix, uint16_t* __restrict__ out,
                                                           int S, int patch, int Kp) {
     extern __shared__ __attribute__((aligned(16))) char im_smem[];
@@ -198,7 +206,7 @@ __global__ __launch_bounds__(256) void im2col_rows_kernel(const float* __restric
         for (int e = 0; e < 4; ++e) {
             const int x = x4 * 4 + e;
             const int px = x / patch, kx = x - px * patch;
-            tile[px * Kp + c * patch * patch + ky * patch + kx] = f32_to_bf16_bits(v[e]);
+            tile[px * Kp + c * patch * patch + ky * patch + kx] = Op16<F16>::from_f32(v[e]);
         }
     }
     __syncthreads();
@@ -208,18 +216,20 @@ __global__ __launch_bounds__(256) void im2col_rows_kernel(const float* __restric
 }
 
 hipError_t launch_im2col(const float* pix, uint16_t* out, int B, int image, int patch, int Kp,
-                         hipStream_t stream) {
+                         hipStream_t stream, int f16) {
     if (B <= 0) return hipSuccess;
     const int g = image / patch;
     const size_t lds = (size_t)g * Kp * 2;
     if (image % 4 == 0 && Kp % 8 == 0 && lds <= 64 * 1024) {
-        hipLaunchKernelGGL(im2col_rows_kernel, dim3(B * g), dim3(256), lds, stream, pix, out, image, patch, Kp);
+        if (f16) hipLaunchKernelGGL(im2col_rows_kernel<true>, dim3(B * g), dim3(256), lds, stream, pix, out, image, patch, Kp);
+        else hipLaunchKernelGGL(im2col_rows_kernel<false>, dim3(B * g), dim3(256), lds, stream, pix, out, image, patch, Kp);
         return hipGetLastError();
     }
     const int64_t total = (int64_t)B * g * g * (Kp >> 3);
     int grid = (int)((total + 255) / 256);
     if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(im2col_kernel, dim3(grid), dim3(256), 0, stream, pix, out, B, image, patch, Kp);
+    if (f16) hipLaunchKernelGGL(im2col_kernel<true>, dim3(grid), dim3(256), 0, stream, pix, out, B, image, patch, Kp);
+    else hipLaunchKernelGGL(im2col_kernel<false>, dim3(grid), dim3(256), 0, stream, pix, out, B, image, patch, Kp);
     return hipGetLastError();
 }
 
@@ -491,12 +501,13 @@ hipError_t launch_l2norm_rows(float* x, int rows, int d, hipStream_t stream) {
 // multiples of 64)
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
-__global__ __launch_bounds__(256) void gelu_erf_bf16_kernel(uint16_t* __restrict__ x, int64_t n8) {
+template <bool F16>
+__global__ __launch_bounds__(256) void gelu_erf_16_kernel(uint16_t* __restrict__ x, int64_t n8) {
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n8; t += (int64_t)gridDim.x * blockDim.x) {
         u32x4_t v = ((u32x4_t*)x)[t];
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-            v[e] = pack_bf16x2(gelu_erf(__uint_as_float(v[e] << 16)), gelu_erf(__uint_as_float(v[e] & 0xffff0000u)));
+            v[e] = Op16<F16>::pack2(gelu_erf(Op16<F16>::lo(v[e])), gelu_erf(Op16<F16>::hi(v[e])));
         ((u32x4_t*)x)[t] = v;
     }
 }
@@ -508,13 +519,16 @@ __global__ __launch_bounds__(256) void gelu_erf_f32_kernel(float* __restrict__ x
         ((f32x4_t*)x)[t] = v;
     }
 }
-hipError_t launch_gelu_erf_bf16(uint16_t* x, int64_t n, hipStream_t stream) {
+template <bool F16>
+static hipError_t launch_gelu_erf_16(uint16_t* x, int64_t n, hipStream_t stream) {
     if (n % 8 != 0 || n < 0) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
     const int64_t n8 = n / 8;
-    hipLaunchKernelGGL(gelu_erf_bf16_kernel, dim3((int)((n8 + 255) / 256 < 16384 ? (n8 + 255) / 256 : 16384)), dim3(256), 0, stream, x, n8);
+    hipLaunchKernelGGL(gelu_erf_16_kernel<F16>, dim3((int)((n8 + 255) / 256 < 16384 ? (n8 + 255) / 256 : 16384)), dim3(256), 0, stream, x, n8);
     return hipGetLastError();
 }
+hipError_t launch_gelu_erf_bf16(uint16_t* x, int64_t n, hipStream_t stream) { return launch_gelu_erf_16<false>(x, n, stream); }
+hipError_t launch_gelu_erf_f16(uint16_t* x, int64_t n, hipStream_t stream) { return launch_gelu_erf_16<true>(x, n, stream); }
 hipError_t launch_gelu_erf_f32(float* x, int64_t n, hipStream_t stream) {
     if (n % 4 != 0 || n < 0) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;

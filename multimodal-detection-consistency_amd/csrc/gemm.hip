@@ -1,5 +1,7 @@
 // Dense bf16 GEMM with fused epilogues for the CLIP towers (K1/K2) and the
-// bank-search pre-pass.  See gemm_core.hpp for the tiling.
+// bank-search pre-pass.  See gemm_core.hpp for the tiling.  Every tower form also has an IEEE fp16 twin (template
+// parameter F16, GemmLaunch::f16: TVC_OPT_TOWER_PRECISION = 3): the same staging, schedule and stores with
+// v_mfma_f32_16x16x32_f16 and fp16 conversions in the 16-bit epilogues.
 #include "gemm_epilogue.hpp"
 #include "gemm_ring4.hpp"
 #include <cstdlib>
@@ -10,7 +12,7 @@
 #define TVC_PRIO_G0 1
 #define TVC_PRIO_G1 2
 
-template <int EPI>
+template <int EPI, bool F16 = false>
 __global__ __launch_bounds__(GEMM_THREADS) void gemm_bf16_kernel(GemmOperands g, GemmEpilogue e,
                                                                   int nIt, int nJt) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -20,18 +22,18 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_bf16_kernel(GemmOperands g,
 
     gemm_acc_t acc;
     gemm_zero_acc(acc);
-    gemm_mainloop(acc, g, i0, j0, smem);
+    gemm_mainloop<F16>(acc, g, i0, j0, smem);
 
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    gemm_tile_epilogue<EPI>(acc, g, e, i0, j0, wave >> 2, wave & 3, lane);
+    gemm_tile_epilogue<EPI, false, 4, false, F16>(acc, g, e, i0, j0, wave >> 2, wave & 3, lane);
 }
 
 
 // ---------------------------------------------------------------------------
 // Persistent ring-pipelined variant (gemm_ring.hpp): used for the big tower GEMMs.
 // ---------------------------------------------------------------------------
-template <int EPI>
+template <int EPI, bool F16 = false>
 __global__ __launch_bounds__(GEMM_THREADS) void gemm_ring_kernel(GemmOperands g, GemmEpilogue e, int nIt, int nJt) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
@@ -109,9 +111,10 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_ring_kernel(GemmOperands g,
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 
+    typedef typename Op16<F16>::x8 x8;
     gemm_acc_t acc;
     gemm_zero_acc(acc);
-    bf16x8_t a[8], b[4];
+    x8 a[8], b[4];
     int ct = 0, cks = 0;         // tile / k-stage of the stage the MFMAs of this wave work on
 
     auto tile_origin = [&](int t, int& i0, int& j0) {
@@ -122,9 +125,9 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_ring_kernel(GemmOperands g,
     auto load_frags = [&](int S) {
         const char* slot = smem + (S & (RING_SLOTS - 1)) * RING_SLOT_BYTES;
 #pragma unroll
-        for (int m = 0; m < 8; ++m) a[m] = *(const bf16x8_t*)(slot + a_off + m * 1024);
+        for (int m = 0; m < 8; ++m) a[m] = *(const x8*)(slot + a_off + m * 1024);
 #pragma unroll
-        for (int n = 0; n < 4; ++n) b[n] = *(const bf16x8_t*)(slot + b_off + n * 1024);
+        for (int n = 0; n < 4; ++n) b[n] = *(const x8*)(slot + b_off + n * 1024);
     };
     auto mfma_stage = [&](auto prio) {
         __builtin_amdgcn_s_setprio(decltype(prio)::value);
@@ -132,7 +135,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_ring_kernel(GemmOperands g,
         for (int m = 0; m < 8; ++m)
 #pragma unroll
             for (int n = 0; n < 4; ++n)
-                acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[m], b[n], acc[m][n], 0, 0, 0);
+                acc[m][n] = Op16<F16>::mfma(a[m], b[n], acc[m][n]);
         __builtin_amdgcn_s_setprio(0);
     };
     // after the MFMAs of stage (ct, cks): tile epilogue when it was the tile's last stage
@@ -140,7 +143,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_ring_kernel(GemmOperands g,
         if (++cks == nk) {
             int i0, j0;
             tile_origin(ct, i0, j0);
-            gemm_tile_epilogue<EPI, true>(acc, g, e, i0, j0, wm, wn, lane, smem + RING_LDS_BYTES + (ct & 1) * 1024);
+            gemm_tile_epilogue<EPI, true, 4, false, F16>(acc, g, e, i0, j0, wm, wn, lane, smem + RING_LDS_BYTES + (ct & 1) * 1024);
             gemm_zero_acc(acc);
             cks = 0; ++ct;
         }
@@ -227,7 +230,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_ring_kernel(GemmOperands g,
 //   store of its fp32 accumulators to ws[tile * S + s] in lane order (what gemm_splitk_partial_kernel writes, bit for bit:
 //   the same products in the same order), summed by gemm_splitk_finish_kernel.  A slice of a few-tile launch then runs at
 //   the ring's rate instead of the one-tile kernel's (about half of it).
-template <int EPI, bool SPLIT>
+template <int EPI, bool SPLIT, bool F16>
 __device__ __forceinline__ void gemm_ring4_body(const GemmOperands& g, const GemmEpilogue& e, int nIt, int nJt, int S, float* ws) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
@@ -315,9 +318,10 @@ __device__ __forceinline__ void gemm_ring4_body(const GemmOperands& g, const Gem
     using U_A0 = std::integral_constant<int, 0>; using U_B0 = std::integral_constant<int, 1>;
     using U_B1 = std::integral_constant<int, 2>; using U_A1 = std::integral_constant<int, 3>;
 
+    typedef typename Op16<F16>::x8 x8;
     gemm_acc_t acc;
     gemm_zero_acc(acc);
-    bf16x8_t A0f[4][2], A1f[4][2], B0f[2][2], B1f[2][2];
+    x8 A0f[4][2], A1f[4][2], B0f[2][2], B1f[2][2];
     int ct = 0;
 
     auto tile_origin = [&](int t, int& i0, int& j0) __attribute__((always_inline)) {
@@ -325,13 +329,13 @@ __device__ __forceinline__ void gemm_ring4_body(const GemmOperands& g, const Gem
         const int jt = lin / nIt;
         i0 = (lin - jt * nIt) * GEMM_BM; j0 = jt * GEMM_BN;
     };
-    typedef const __attribute__((address_space(3))) bf16x8_t* lds_frag_p;
+    typedef const __attribute__((address_space(3))) x8* lds_frag_p;
     // Fragment read addresses are loop constants (4 VGPRs; this form has ~50 to spare): a load segment is the
     // critical path of a slot, so it carries no address arithmetic beyond one add of the buffer offset per K-tile.
     const uint32_t sw_rd = (uint32_t)((((lane >> 4) ^ ((lane >> 1) & 7)) * 16));
     const uint32_t a_rd0 = smem_lds + (wm * 128 + (lane & 15)) * 128 + sw_rd, a_rd1 = a_rd0 ^ 64u;                    // k-sub-step 0 / 1
     const uint32_t b_rd0 = smem_lds + GEMM_TILE_BYTES + (wn * 64 + (lane & 15)) * 128 + sw_rd, b_rd1 = b_rd0 ^ 64u;
-    auto load_A = [&](int t, int q, bf16x8_t (&a)[4][2]) __attribute__((always_inline)) {
+    auto load_A = [&](int t, int q, x8 (&a)[4][2]) __attribute__((always_inline)) {
         const uint32_t po = (uint32_t)(t & 1) * R3_SLOT_BYTES + q * 8192;
         const uint32_t r0 = a_rd0 + po, r1 = a_rd1 + po;
 #pragma unroll
@@ -340,7 +344,7 @@ __device__ __forceinline__ void gemm_ring4_body(const GemmOperands& g, const Gem
             a[m][1] = *(lds_frag_p)(uintptr_t)(r1 + m * 2048);
         }
     };
-    auto load_B = [&](int t, int q, bf16x8_t (&b)[2][2]) __attribute__((always_inline)) {
+    auto load_B = [&](int t, int q, x8 (&b)[2][2]) __attribute__((always_inline)) {
         const uint32_t po = (uint32_t)(t & 1) * R3_SLOT_BYTES + q * 4096;
         const uint32_t r0 = b_rd0 + po, r1 = b_rd1 + po;
 #pragma unroll
@@ -355,8 +359,8 @@ __device__ __forceinline__ void gemm_ring4_body(const GemmOperands& g, const Gem
         _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                          \
             _Pragma("unroll") for (int m = 0; m < 4; ++m)                                                         \
                 _Pragma("unroll") for (int n = 0; n < 2; ++n)                                                     \
-                    acc[(QA_) * 4 + m][(QB_) * 2 + n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(                  \
-                        A_[m][ks], B_[n][ks], acc[(QA_) * 4 + m][(QB_) * 2 + n], 0, 0, 0);                        \
+                    acc[(QA_) * 4 + m][(QB_) * 2 + n] = Op16<F16>::mfma(                                          \
+                        A_[m][ks], B_[n][ks], acc[(QA_) * 4 + m][(QB_) * 2 + n]);                                  \
         __builtin_amdgcn_s_setprio(0);                                                                            \
     }
 #define RING4_BARRIER() { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); }
@@ -446,7 +450,7 @@ __device__ __forceinline__ void gemm_ring4_body(const GemmOperands& g, const Gem
             }
             int lane_e = lane;
             asm volatile("" : "+v"(lane_e));
-            gemm_tile_epilogue<EPI, true, 4, true>(acc, g, e, i0, j0, wm, wn, lane_e, smem + R3_LDS_BYTES + (ct & 1) * 1024);
+            gemm_tile_epilogue<EPI, true, 4, true, F16>(acc, g, e, i0, j0, wm, wn, lane_e, smem + R3_LDS_BYTES + (ct & 1) * 1024);
         };
         if (wm == 1) { tile_end(); }
         RING4_BARRIER()
@@ -459,14 +463,15 @@ __device__ __forceinline__ void gemm_ring4_body(const GemmOperands& g, const Gem
 #undef RING4_BARRIER
 }
 
-template <int EPI>
+template <int EPI, bool F16 = false>
 __global__ __launch_bounds__(GEMM_THREADS) void gemm_ring4_kernel(GemmOperands g, GemmEpilogue e, int nIt, int nJt) {
-    gemm_ring4_body<EPI, false>(g, e, nIt, nJt, 1, nullptr);
+    gemm_ring4_body<EPI, false, F16>(g, e, nIt, nJt, 1, nullptr);
 }
+template <bool F16 = false>
 __global__ __launch_bounds__(GEMM_THREADS) void gemm_ring4_split_kernel(GemmOperands g, float* ws, int nIt, int nJt, int S) {
     GemmEpilogue e;
     e.bias = nullptr; e.out = nullptr; e.ldo = 0;
-    gemm_ring4_body<TVC_EPI_F32, true>(g, e, nIt, nJt, S, ws);
+    gemm_ring4_body<TVC_EPI_F32, true, F16>(g, e, nIt, nJt, S, ws);
 }
 
 
@@ -478,6 +483,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_ring4_split_kernel(GemmOper
 // left-over tile is multiplied by S workgroups over 1/S of K each (fp32 partial tiles, stored in the
 // accumulator's lane order: coalesced), then summed and passed through the usual epilogue.
 // ---------------------------------------------------------------------------
+template <bool F16 = false>
 __global__ __launch_bounds__(GEMM_THREADS) void gemm_splitk_partial_kernel(GemmOperands g, float* __restrict__ ws,
                                                                            int nIt, int jt0, int S) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -487,7 +493,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_splitk_partial_kernel(GemmO
     const int b = (int)((int64_t)nk64 * split / S), e = (int)((int64_t)nk64 * (split + 1) / S);
     gemm_acc_t acc;
     gemm_zero_acc(acc);
-    if (e > b) gemm_mainloop(acc, g, it * GEMM_BM, (jt0 + jt) * GEMM_BN, smem, b, e);
+    if (e > b) gemm_mainloop<F16>(acc, g, it * GEMM_BM, (jt0 + jt) * GEMM_BN, smem, b, e);
     f32x4_t* o = (f32x4_t*)(ws + (int64_t)blockIdx.x * (GEMM_BM * GEMM_BN)) + threadIdx.x;
 #pragma unroll
     for (int m = 0; m < 8; ++m)
@@ -497,7 +503,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_splitk_partial_kernel(GemmO
 
 // One workgroup per (left-over tile, 16 x 16 sub-tile pair index m*4+n): 32 workgroups per tile, every
 // thread sums the S partial values of its 4 out-features of one token and stores them.
-template <int EPI>
+template <int EPI, bool F16 = false>
 __global__ __launch_bounds__(GEMM_THREADS) void gemm_splitk_finish_kernel(GemmOperands g, GemmEpilogue e,
                                                                           const float* __restrict__ ws, int nIt,
                                                                           int jt0, int S) {
@@ -510,47 +516,48 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_splitk_finish_kernel(GemmOp
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = it * GEMM_BM + (wave >> 2) * 128 + m * 16 + (lane >> 4) * 4;
     const int j = (jt0 + jt) * GEMM_BN + (wave & 3) * 64 + n * 16 + (lane & 15);
-    if (i < g.I && j < g.J) gemm_store4<EPI>(e, g.I, i, j, v);
+    if (i < g.I && j < g.J) gemm_store4<EPI, F16>(e, g.I, i, j, v);
 }
 
-static hipError_t set_lds_attr_impl();
-static hipError_t set_lds_attr_once() {
+template <bool F16> static hipError_t set_lds_attr_impl();
+template <bool F16> static hipError_t set_lds_attr_once() {
     // thread-safe: the Python lock is per engine, two engines may first-launch from two threads
     static std::once_flag once;
     static hipError_t st = hipSuccess;
-    std::call_once(once, [] { st = set_lds_attr_impl(); });
+    std::call_once(once, [] { st = set_lds_attr_impl<F16>(); });
     return st;
 }
-static hipError_t set_lds_attr_impl() {
+template <bool F16> static hipError_t set_lds_attr_impl() {
     hipError_t st = hipSuccess;
 #define SET_ATTR(K)                                                                              \
     if (st == hipSuccess)                                                                        \
         st = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize,     \
                                  GEMM_LDS_BYTES);
-    SET_ATTR(gemm_bf16_kernel<TVC_EPI_F32>)
-    SET_ATTR(gemm_bf16_kernel<TVC_EPI_BF16>)
-    SET_ATTR(gemm_bf16_kernel<TVC_EPI_GELU_BF16>)
-    SET_ATTR(gemm_bf16_kernel<TVC_EPI_RESID_F32>)
-    SET_ATTR(gemm_splitk_partial_kernel)
+    SET_ATTR((gemm_bf16_kernel<TVC_EPI_F32, F16>))
+    SET_ATTR((gemm_bf16_kernel<TVC_EPI_BF16, F16>))
+    SET_ATTR((gemm_bf16_kernel<TVC_EPI_GELU_BF16, F16>))
+    SET_ATTR((gemm_bf16_kernel<TVC_EPI_RESID_F32, F16>))
+    SET_ATTR(gemm_splitk_partial_kernel<F16>)
 #undef SET_ATTR
 #define SET_ATTR(K)                                                                              \
     if (st == hipSuccess)                                                                        \
         st = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize,     \
                                  RING_LDS_BYTES + 4096);
-    SET_ATTR(gemm_ring_kernel<TVC_EPI_F32>)
-    SET_ATTR(gemm_ring_kernel<TVC_EPI_BF16>)
-    SET_ATTR(gemm_ring_kernel<TVC_EPI_GELU_BF16>)
-    SET_ATTR(gemm_ring_kernel<TVC_EPI_RESID_F32>)
-    SET_ATTR(gemm_ring4_kernel<TVC_EPI_F32>)
-    SET_ATTR(gemm_ring4_kernel<TVC_EPI_BF16>)
-    SET_ATTR(gemm_ring4_kernel<TVC_EPI_GELU_BF16>)
-    SET_ATTR(gemm_ring4_split_kernel)
+    SET_ATTR((gemm_ring_kernel<TVC_EPI_F32, F16>))
+    SET_ATTR((gemm_ring_kernel<TVC_EPI_BF16, F16>))
+    SET_ATTR((gemm_ring_kernel<TVC_EPI_GELU_BF16, F16>))
+    SET_ATTR((gemm_ring_kernel<TVC_EPI_RESID_F32, F16>))
+    SET_ATTR((gemm_ring4_kernel<TVC_EPI_F32, F16>))
+    SET_ATTR((gemm_ring4_kernel<TVC_EPI_BF16, F16>))
+    SET_ATTR((gemm_ring4_kernel<TVC_EPI_GELU_BF16, F16>))
+    SET_ATTR(gemm_ring4_split_kernel<F16>)
 #undef SET_ATTR
     return st;
 }
 
-hipError_t launch_gemm_bf16(const GemmLaunch& L, hipStream_t stream) {
-    hipError_t st = set_lds_attr_once();
+template <bool F16>
+static hipError_t launch_gemm_t(const GemmLaunch& L, hipStream_t stream) {
+    hipError_t st = set_lds_attr_once<F16>();
     if (st != hipSuccess) return st;
     GemmOperands g;
     g.A = L.A; g.B = L.B; g.lda = L.lda; g.ldb = L.ldb; g.I = L.I; g.J = L.J;
@@ -590,22 +597,22 @@ hipError_t launch_gemm_bf16(const GemmLaunch& L, hipStream_t stream) {
         if (ring_split && nk64_all % S == 0 && nk64_all / S >= 4 && (L.I % GEMM_BM == 0 || L.a_rows_padded) &&
             (L.J % GEMM_BN == 0 || L.b_rows_padded) && L.lda % 64 == 0 && L.ldb % 64 == 0) {
             const dim3 rgrid(vt >= 256 ? 256 : (vt + 7) / 8 * 8);
-            hipLaunchKernelGGL(gemm_ring4_split_kernel, rgrid, block, R3_LDS_BYTES + 4096, stream, g, L.splitk_ws, nIt, nJt, S);
+            hipLaunchKernelGGL(gemm_ring4_split_kernel<F16>, rgrid, block, R3_LDS_BYTES + 4096, stream, g, L.splitk_ws, nIt, nJt, S);
         } else {
-            hipLaunchKernelGGL(gemm_splitk_partial_kernel, dim3(vt), block, GEMM_LDS_BYTES, stream, g, L.splitk_ws, nIt, 0, S);
+            hipLaunchKernelGGL(gemm_splitk_partial_kernel<F16>, dim3(vt), block, GEMM_LDS_BYTES, stream, g, L.splitk_ws, nIt, 0, S);
         }
         switch (L.epilogue) {
             case TVC_EPI_F32:
-                hipLaunchKernelGGL(gemm_splitk_finish_kernel<TVC_EPI_F32>, dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
+                hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_F32, F16>), dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
                 break;
             case TVC_EPI_BF16:
-                hipLaunchKernelGGL(gemm_splitk_finish_kernel<TVC_EPI_BF16>, dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
+                hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_BF16, F16>), dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
                 break;
             case TVC_EPI_GELU_BF16:
-                hipLaunchKernelGGL(gemm_splitk_finish_kernel<TVC_EPI_GELU_BF16>, dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
+                hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_GELU_BF16, F16>), dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
                 break;
             case TVC_EPI_RESID_F32:
-                hipLaunchKernelGGL(gemm_splitk_finish_kernel<TVC_EPI_RESID_F32>, dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
+                hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_RESID_F32, F16>), dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
                 break;
             default:
                 return hipErrorInvalidValue;
@@ -640,20 +647,20 @@ hipError_t launch_gemm_bf16(const GemmLaunch& L, hipStream_t stream) {
             M2.splitk_ws = nullptr;
             hipError_t st2 = launch_gemm_bf16(M2, stream);
             if (st2 != hipSuccess) return st2;
-            hipLaunchKernelGGL(gemm_splitk_partial_kernel, dim3(left * S), block, GEMM_LDS_BYTES, stream, g,
+            hipLaunchKernelGGL(gemm_splitk_partial_kernel<F16>, dim3(left * S), block, GEMM_LDS_BYTES, stream, g,
                                L.splitk_ws, nIt, jt_full, S);
             switch (L.epilogue) {
                 case TVC_EPI_F32:
-                    hipLaunchKernelGGL(gemm_splitk_finish_kernel<TVC_EPI_F32>, dim3(left * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt_full, S);
+                    hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_F32, F16>), dim3(left * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt_full, S);
                     break;
                 case TVC_EPI_BF16:
-                    hipLaunchKernelGGL(gemm_splitk_finish_kernel<TVC_EPI_BF16>, dim3(left * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt_full, S);
+                    hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_BF16, F16>), dim3(left * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt_full, S);
                     break;
                 case TVC_EPI_GELU_BF16:
-                    hipLaunchKernelGGL(gemm_splitk_finish_kernel<TVC_EPI_GELU_BF16>, dim3(left * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt_full, S);
+                    hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_GELU_BF16, F16>), dim3(left * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt_full, S);
                     break;
                 case TVC_EPI_RESID_F32:
-                    hipLaunchKernelGGL(gemm_splitk_finish_kernel<TVC_EPI_RESID_F32>, dim3(left * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt_full, S);
+                    hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_RESID_F32, F16>), dim3(left * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt_full, S);
                     break;
                 default:
                     return hipErrorInvalidValue;
@@ -673,13 +680,13 @@ hipError_t launch_gemm_bf16(const GemmLaunch& L, hipStream_t stream) {
             (L.J % GEMM_BN == 0 || L.b_rows_padded) && L.lda % 64 == 0 && L.ldb % 64 == 0) {
             switch (L.epilogue) {
                 case TVC_EPI_F32:
-                    hipLaunchKernelGGL(gemm_ring4_kernel<TVC_EPI_F32>, rgrid, block, R3_LDS_BYTES + 4096, stream, g, e, nIt, nJt);
+                    hipLaunchKernelGGL((gemm_ring4_kernel<TVC_EPI_F32, F16>), rgrid, block, R3_LDS_BYTES + 4096, stream, g, e, nIt, nJt);
                     break;
                 case TVC_EPI_BF16:
-                    hipLaunchKernelGGL(gemm_ring4_kernel<TVC_EPI_BF16>, rgrid, block, R3_LDS_BYTES + 4096, stream, g, e, nIt, nJt);
+                    hipLaunchKernelGGL((gemm_ring4_kernel<TVC_EPI_BF16, F16>), rgrid, block, R3_LDS_BYTES + 4096, stream, g, e, nIt, nJt);
                     break;
                 case TVC_EPI_GELU_BF16:
-                    hipLaunchKernelGGL(gemm_ring4_kernel<TVC_EPI_GELU_BF16>, rgrid, block, R3_LDS_BYTES + 4096, stream, g, e, nIt, nJt);
+                    hipLaunchKernelGGL((gemm_ring4_kernel<TVC_EPI_GELU_BF16, F16>), rgrid, block, R3_LDS_BYTES + 4096, stream, g, e, nIt, nJt);
                     break;
                 default:
                     return hipErrorInvalidValue;
@@ -688,16 +695,16 @@ hipError_t launch_gemm_bf16(const GemmLaunch& L, hipStream_t stream) {
         }
         switch (L.epilogue) {
             case TVC_EPI_F32:
-                hipLaunchKernelGGL(gemm_ring_kernel<TVC_EPI_F32>, rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
+                hipLaunchKernelGGL((gemm_ring_kernel<TVC_EPI_F32, F16>), rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
                 break;
             case TVC_EPI_BF16:
-                hipLaunchKernelGGL(gemm_ring_kernel<TVC_EPI_BF16>, rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
+                hipLaunchKernelGGL((gemm_ring_kernel<TVC_EPI_BF16, F16>), rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
                 break;
             case TVC_EPI_GELU_BF16:
-                hipLaunchKernelGGL(gemm_ring_kernel<TVC_EPI_GELU_BF16>, rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
+                hipLaunchKernelGGL((gemm_ring_kernel<TVC_EPI_GELU_BF16, F16>), rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
                 break;
             case TVC_EPI_RESID_F32:
-                hipLaunchKernelGGL(gemm_ring_kernel<TVC_EPI_RESID_F32>, rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
+                hipLaunchKernelGGL((gemm_ring_kernel<TVC_EPI_RESID_F32, F16>), rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
                 break;
             default:
                 return hipErrorInvalidValue;
@@ -719,20 +726,20 @@ hipError_t launch_gemm_bf16(const GemmLaunch& L, hipStream_t stream) {
         if (S > 16) S = 16;
         if (auto_split && (small_on || L.splitk_small) && forced < 0 && L.splitk_ws && S >= 2 &&
             (size_t)ntiles * S * GEMM_BM * GEMM_BN * 4 <= L.splitk_ws_bytes) {
-            hipLaunchKernelGGL(gemm_splitk_partial_kernel, dim3(ntiles * S), block, GEMM_LDS_BYTES, stream, g,
+            hipLaunchKernelGGL(gemm_splitk_partial_kernel<F16>, dim3(ntiles * S), block, GEMM_LDS_BYTES, stream, g,
                                L.splitk_ws, nIt, 0, S);
             switch (L.epilogue) {
                 case TVC_EPI_F32:
-                    hipLaunchKernelGGL(gemm_splitk_finish_kernel<TVC_EPI_F32>, dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
+                    hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_F32, F16>), dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
                     break;
                 case TVC_EPI_BF16:
-                    hipLaunchKernelGGL(gemm_splitk_finish_kernel<TVC_EPI_BF16>, dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
+                    hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_BF16, F16>), dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
                     break;
                 case TVC_EPI_GELU_BF16:
-                    hipLaunchKernelGGL(gemm_splitk_finish_kernel<TVC_EPI_GELU_BF16>, dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
+                    hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_GELU_BF16, F16>), dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
                     break;
                 case TVC_EPI_RESID_F32:
-                    hipLaunchKernelGGL(gemm_splitk_finish_kernel<TVC_EPI_RESID_F32>, dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
+                    hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_RESID_F32, F16>), dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
                     break;
                 default:
                     return hipErrorInvalidValue;
@@ -743,19 +750,23 @@ hipError_t launch_gemm_bf16(const GemmLaunch& L, hipStream_t stream) {
     const dim3 grid(nIt * nJt);
     switch (L.epilogue) {
         case TVC_EPI_F32:
-            hipLaunchKernelGGL(gemm_bf16_kernel<TVC_EPI_F32>, grid, block, GEMM_LDS_BYTES, stream, g, e, nIt, nJt);
+            hipLaunchKernelGGL((gemm_bf16_kernel<TVC_EPI_F32, F16>), grid, block, GEMM_LDS_BYTES, stream, g, e, nIt, nJt);
             break;
         case TVC_EPI_BF16:
-            hipLaunchKernelGGL(gemm_bf16_kernel<TVC_EPI_BF16>, grid, block, GEMM_LDS_BYTES, stream, g, e, nIt, nJt);
+            hipLaunchKernelGGL((gemm_bf16_kernel<TVC_EPI_BF16, F16>), grid, block, GEMM_LDS_BYTES, stream, g, e, nIt, nJt);
             break;
         case TVC_EPI_GELU_BF16:
-            hipLaunchKernelGGL(gemm_bf16_kernel<TVC_EPI_GELU_BF16>, grid, block, GEMM_LDS_BYTES, stream, g, e, nIt, nJt);
+            hipLaunchKernelGGL((gemm_bf16_kernel<TVC_EPI_GELU_BF16, F16>), grid, block, GEMM_LDS_BYTES, stream, g, e, nIt, nJt);
             break;
         case TVC_EPI_RESID_F32:
-            hipLaunchKernelGGL(gemm_bf16_kernel<TVC_EPI_RESID_F32>, grid, block, GEMM_LDS_BYTES, stream, g, e, nIt, nJt);
+            hipLaunchKernelGGL((gemm_bf16_kernel<TVC_EPI_RESID_F32, F16>), grid, block, GEMM_LDS_BYTES, stream, g, e, nIt, nJt);
             break;
         default:
             return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+hipError_t launch_gemm_bf16(const GemmLaunch& L, hipStream_t stream) {
+    return L.f16 ? launch_gemm_t<true>(L, stream) : launch_gemm_t<false>(L, stream);
 }

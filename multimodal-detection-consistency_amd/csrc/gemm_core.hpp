@@ -62,7 +62,8 @@ __device__ __forceinline__ void gemm_stage_tile(const uint16_t* __restrict__ bas
 
 // acc must be zero-initialised by the caller (or carry a running sum).
 // [step_begin, step_end): range of 64-deep K steps (over all planes) to multiply; the default is
-// the whole K (split-K partial tiles pass a sub-range).
+// the whole K (split-K partial tiles pass a sub-range).  F16: the operands are IEEE fp16 (common.hpp: Op16).
+template <bool F16 = false>
 __device__ __forceinline__ void gemm_mainloop(gemm_acc_t& acc, const GemmOperands& g,
                                               int i0, int j0, char* smem, int step_begin = 0, int step_end = -1) {
     const int lane = threadIdx.x & 63;
@@ -99,18 +100,19 @@ __device__ __forceinline__ void gemm_mainloop(gemm_acc_t& acc, const GemmOperand
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             const int sw = s ? sw1 : sw0;
-            bf16x8_t a[8], b[4];
+            typedef typename Op16<F16>::x8 x8;
+            x8 a[8], b[4];
 #pragma unroll
             for (int m = 0; m < 8; ++m)
-                a[m] = *(const bf16x8_t*)(ta + a_row_off + m * 2048 + sw);
+                a[m] = *(const x8*)(ta + a_row_off + m * 2048 + sw);
 #pragma unroll
             for (int n = 0; n < 4; ++n)
-                b[n] = *(const bf16x8_t*)(tb + b_row_off + n * 2048 + sw);
+                b[n] = *(const x8*)(tb + b_row_off + n * 2048 + sw);
 #pragma unroll
             for (int m = 0; m < 8; ++m)
 #pragma unroll
                 for (int n = 0; n < 4; ++n)
-                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[m], b[n], acc[m][n], 0, 0, 0);
+                    acc[m][n] = Op16<F16>::mfma(a[m], b[n], acc[m][n]);
         }
     }
     // all waves must be done with the last buffer before a caller restages

@@ -1,4 +1,5 @@
-// Fused epilogues of the bf16 GEMM kernels (bias, QuickGELU, bf16 / fp32 / residual stores).
+// Fused epilogues of the 16-bit GEMM kernels (bias, QuickGELU, bf16 / fp16 / fp32 / residual stores).  F16: the 16-bit
+// stores (TVC_EPI_BF16, TVC_EPI_GELU_BF16) write IEEE fp16 instead of bf16.
 #pragma once
 #include "gemm_ring.hpp"
 #include "kernels.hpp"
@@ -19,7 +20,7 @@ __device__ __forceinline__ float quick_gelu(float x) {
 // out[j, i..i+3] for one lane: i = 4 consecutive out-features.  The vector
 // path needs all four in range and a 4-element-aligned leading dimension;
 // ragged edges (bank samples, cosine matrices) take the scalar path.
-template <int EPI>
+template <int EPI, bool F16 = false>
 __device__ __forceinline__ void gemm_store4(const GemmEpilogue& e, int I, int i, int j, f32x4_t v) {
     const bool vec = (i + 3 < I) && ((e.ldo & 3) == 0);
     if (vec) {
@@ -36,8 +37,8 @@ __device__ __forceinline__ void gemm_store4(const GemmEpilogue& e, int I, int i,
                 for (int t = 0; t < 4; ++t) v[t] = quick_gelu(v[t]);
             }
             u32x2_t o;
-            o[0] = pack_bf16x2(v[0], v[1]);
-            o[1] = pack_bf16x2(v[2], v[3]);
+            o[0] = Op16<F16>::pack2(v[0], v[1]);
+            o[1] = Op16<F16>::pack2(v[2], v[3]);
             *(u32x2_t*)((uint16_t*)e.out + (int64_t)j * e.ldo + i) = o;
         }
         return;
@@ -51,7 +52,7 @@ __device__ __forceinline__ void gemm_store4(const GemmEpilogue& e, int I, int i,
         else if (EPI == TVC_EPI_RESID_F32) ((float*)e.out)[off] += x;
         else {
             if (EPI == TVC_EPI_GELU_BF16) x = quick_gelu(x);
-            ((uint16_t*)e.out)[off] = f32_to_bf16_bits(x);
+            ((uint16_t*)e.out)[off] = Op16<F16>::from_f32(x);
         }
     }
 }
@@ -65,7 +66,7 @@ __device__ __forceinline__ void gemm_store4(const GemmEpilogue& e, int I, int i,
 // exec-masked region and no global load that is not consumed before its end, so hipcc's
 // waitcnt pass sees nothing pending when a persistent caller loops back.
 // NT: 16-token sub-tiles per wave (4: eight-wave kernels, 8: the four-wave kernel).  BIAS_REGS: see below.
-template <int EPI, bool BIAS_LDS = false, int NT = 4, bool BIAS_REGS = false>
+template <int EPI, bool BIAS_LDS = false, int NT = 4, bool BIAS_REGS = false, bool F16 = false>
 __device__ __forceinline__ void gemm_tile_epilogue(const f32x4_t (&acc)[8][NT], const GemmOperands& g,
                                                    const GemmEpilogue& e, int i0, int j0, int wm, int wn, int lane,
                                                    const char* bias_lds = nullptr) {
@@ -130,8 +131,8 @@ __device__ __forceinline__ void gemm_tile_epilogue(const f32x4_t (&acc)[8][NT], 
 #pragma unroll
                         for (int t = 0; t < 4; ++t) { v0[t] = quick_gelu(v0[t]); v1[t] = quick_gelu(v1[t]); }
                     }
-                    const auto r0 = __builtin_amdgcn_permlane16_swap(pack_bf16x2(v0[0], v0[1]), pack_bf16x2(v1[0], v1[1]), false, false);
-                    const auto r1 = __builtin_amdgcn_permlane16_swap(pack_bf16x2(v0[2], v0[3]), pack_bf16x2(v1[2], v1[3]), false, false);
+                    const auto r0 = __builtin_amdgcn_permlane16_swap(Op16<F16>::pack2(v0[0], v0[1]), Op16<F16>::pack2(v1[0], v1[1]), false, false);
+                    const auto r1 = __builtin_amdgcn_permlane16_swap(Op16<F16>::pack2(v0[2], v0[3]), Op16<F16>::pack2(v1[2], v1[3]), false, false);
                     u32x4_t o;
                     o[0] = r0[0]; o[1] = r1[0]; o[2] = r0[1]; o[3] = r1[1];
                     // (a non-temporal store is 1-3 % faster for this kernel alone and 3.5 % slower for the
@@ -148,8 +149,8 @@ __device__ __forceinline__ void gemm_tile_epilogue(const f32x4_t (&acc)[8][NT], 
                         for (int t = 0; t < 4; ++t) v[t] = quick_gelu(v[t]);
                     }
                     u32x2_t o;
-                    o[0] = pack_bf16x2(v[0], v[1]);
-                    o[1] = pack_bf16x2(v[2], v[3]);
+                    o[0] = Op16<F16>::pack2(v[0], v[1]);
+                    o[1] = Op16<F16>::pack2(v[2], v[3]);
                     *(u32x2_t*)(p + m * 16) = o;
                 }
             }
@@ -164,7 +165,7 @@ __device__ __forceinline__ void gemm_tile_epilogue(const f32x4_t (&acc)[8][NT], 
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
             const int i = i0 + wm * 128 + m * 16 + (lane >> 4) * 4;
-            if (i < g.I) gemm_store4<EPI>(e, g.I, i, j, acc[m][n]);
+            if (i < g.I) gemm_store4<EPI, F16>(e, g.I, i, j, acc[m][n]);
         }
         if (NT > 4) __builtin_amdgcn_sched_barrier(0);
     }

@@ -92,6 +92,11 @@ struct tvc_handle {
     tvc_text_weights_f32 tw32{};
     std::vector<tvc_layer_weights_f32> vlayers32, tlayers32;
     int tower_precision = 0;   // TVC_OPT_TOWER_PRECISION
+    // fp16 towers (precision 3): the caller's IEEE fp16 weight set (tvc_set_weights_f16), referenced like the bf16 one
+    bool has_vision16 = false, has_text16 = false;
+    tvc_vision_weights vw16{};
+    tvc_text_weights tw16{};
+    std::vector<tvc_layer_weights> vlayers16, tlayers16;
     // split-bf16 mode (precision 2): planes of every GEMM weight, built from the fp32 copies when the option is set
     std::vector<SplitLayer> vsplit, tsplit;
     uint16_t* vsplit_patch = nullptr;

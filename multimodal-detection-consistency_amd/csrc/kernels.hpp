@@ -31,6 +31,7 @@ struct GemmLaunch {
     // optional scratch for the split-K tail (see launch_gemm_bf16); nullptr disables it
     float* splitk_ws = nullptr;
     size_t splitk_ws_bytes = 0;
+    bool f16 = false;              // A, B are IEEE fp16 (v_mfma_f32_16x16x32_f16) and the 16-bit epilogues store fp16 (tower mode 3)
 };
 hipError_t launch_gemm_bf16(const GemmLaunch& L, hipStream_t stream);
 
@@ -41,9 +42,10 @@ hipError_t launch_layernorm(float* x, int64_t x_row_stride, const int32_t* row_i
                             int write_x, const float* g, const float* b, uint16_t* y, int rows, int d,
                             hipStream_t stream, const uint16_t* delta2 = nullptr, int delta_compact = 0,
                             float* xsum_out = nullptr,      // xsum_out: fp32 [rows, d] receives x (+ deltas), compact
-                            float* y32 = nullptr);          // y32: fp32 copy of the output rows (y may then be nullptr)
+                            float* y32 = nullptr,           // y32: fp32 copy of the output rows (y may then be nullptr)
+                            int f16 = 0);                   // f16: y and the deltas are IEEE fp16 instead of bf16
 hipError_t launch_im2col(const float* pix, uint16_t* out, int B, int image, int patch, int Kp,
-                         hipStream_t stream);
+                         hipStream_t stream, int f16 = 0);  // f16: fp16 columns instead of bf16
 hipError_t launch_assemble_lnpre(const float* patch_out, const float* cls, const float* pos,
                                  const float* g, const float* b, float* x, int B, int T, int d,
                                  hipStream_t stream);
@@ -62,6 +64,7 @@ hipError_t launch_text_lens_scan(const int32_t* tok, int32_t* starts, int32_t* p
 hipError_t launch_l2norm_rows(float* x, int rows, int d, hipStream_t stream);
 // exact (erf) GELU in place: the activation of towers with TVC_ACT_GELU, after a store-only FC1
 hipError_t launch_gelu_erf_bf16(uint16_t* x, int64_t n, hipStream_t stream);
+hipError_t launch_gelu_erf_f16(uint16_t* x, int64_t n, hipStream_t stream);
 hipError_t launch_gelu_erf_f32(float* x, int64_t n, hipStream_t stream);
 hipError_t launch_split_planes(const float* x, uint16_t* out, int64_t rows, int d, int planes,
                                hipStream_t stream);
@@ -75,7 +78,8 @@ hipError_t launch_gather_rows(const uint16_t* bank, int64_t ld, int planes, int 
 // pool_mode 1 / 2: only the pooled token's output per sequence (first token / EOT token), compact [n_seq, width]
 hipError_t launch_attention(const uint16_t* qkv, uint16_t* out, const int32_t* starts, int n_seq,
                             int seq_len, int heads, int causal, hipStream_t stream, const int32_t* pfx = nullptr,
-                            int pool_mode = 0, const int32_t* pool_row = nullptr);
+                            int pool_mode = 0, const int32_t* pool_row = nullptr,
+                            int f16 = 0);       // f16: qkv and out are IEEE fp16, the products on the f16 MFMA
 
 // ---- bank.hip
 struct BankSearchLaunch {

@@ -56,7 +56,9 @@ struct GradSave {
 int run_layers(tvc_handle* h, const tvc_tower_arch& a, const tvc_layer_weights* lw, int n_seq, int seq_len,
                int causal, const int32_t* starts, int total_rows, int wso, hipStream_t st,
                const int32_t* pfx = nullptr, int pool_mode = 0, const int32_t* pool_row = nullptr,
-               int64_t pool_x_stride = 0, const GradSave* gs = nullptr) {
+               int64_t pool_x_stride = 0, const GradSave* gs = nullptr, bool f16 = false) {
+    // f16 (TVC_OPT_TOWER_PRECISION = 3): lw holds IEEE fp16 GEMM weights; every 16-bit activation below is fp16, the
+    // products run on the f16 MFMA.  Same launches, shapes and workspaces as the bf16 loop.
     const int d = a.width;
     const int rows = starts ? total_rows : n_seq * seq_len;
     float* X = (float*)h->ws[WS_X + wso].p;
@@ -80,7 +82,7 @@ int run_layers(tvc_handle* h, const tvc_tower_arch& a, const tvc_layer_weights* 
             // gradient mode keeps the residual stream as layer l sees it (X + the pending deltas): ln_1 writes it to the
             // kept buffer while it normalises (`xsum_out`) -- no separate device-to-device copy of X per layer
             HIP_TRY(launch_layernorm(X, d, nullptr, pending ? D1 : nullptr, 1, w.ln1_g, w.ln1_b, H, rows, d, st,
-                                     pending ? D2 : nullptr, 0, gs ? gs->x + (size_t)l * rows * d : nullptr));
+                                     pending ? D2 : nullptr, 0, gs ? gs->x + (size_t)l * rows * d : nullptr, nullptr, f16));
         }
         if (gs) {
             QKV = gs->qkv + (size_t)l * rows * 3 * d;
@@ -90,29 +92,31 @@ int run_layers(tvc_handle* h, const tvc_tower_arch& a, const tvc_layer_weights* 
         g.A = w.wqkv; g.lda = d; g.I = 3 * d; g.B = H; g.ldb = d; g.J = rows; g.K = d;
         g.bias = w.bqkv; g.out = QKV; g.ldo = 3 * d; g.epilogue = TVC_EPI_BF16; g.b_rows_padded = true;
         g.splitk_small = gs != nullptr;            // gradient mode only (see tvc_encode_image_backward)
+        g.f16 = f16;
         HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
         if (pool_mode && l == a.layers - 1) {
             const PoolBufs pb = pool_bufs(h, a, n_seq, wso);
             {
                 const double avg_len = starts ? (double)rows / n_seq : (double)seq_len;
                 ProfScope ps(h, st, TVC_PROF_ATTENTION, 4.0 * n_seq * a.heads * avg_len * 64);
-                HIP_TRY(launch_attention(QKV, pb.Hc, starts, n_seq, seq_len, a.heads, causal, st, pfx, pool_mode, pool_row));
+                HIP_TRY(launch_attention(QKV, pb.Hc, starts, n_seq, seq_len, a.heads, causal, st, pfx, pool_mode, pool_row, f16));
             }
             g = GemmLaunch();
             g.A = w.wo; g.lda = d; g.I = d; g.B = pb.Hc; g.ldb = d; g.J = n_seq; g.K = d;
-            g.bias = w.bo; g.out = pb.D1c; g.ldo = d; g.epilogue = TVC_EPI_BF16; g.b_rows_padded = true;
+            g.bias = w.bo; g.out = pb.D1c; g.ldo = d; g.epilogue = TVC_EPI_BF16; g.b_rows_padded = true; g.f16 = f16;
             HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
             HIP_TRY(launch_layernorm(X, pool_row ? d : pool_x_stride, pool_row, pb.D1c, 0, w.ln2_g, w.ln2_b, pb.H2c, n_seq, d,
-                                     st, nullptr, 1));
+                                     st, nullptr, 1, nullptr, nullptr, f16));
             g = GemmLaunch();
             g.A = w.w1; g.lda = d; g.I = a.mlp; g.B = pb.H2c; g.ldb = d; g.J = n_seq; g.K = d;
             g.bias = w.b1; g.out = pb.MLPc; g.ldo = a.mlp; g.b_rows_padded = true;
-            g.epilogue = a.act == TVC_ACT_GELU ? TVC_EPI_BF16 : TVC_EPI_GELU_BF16;
+            g.epilogue = a.act == TVC_ACT_GELU ? TVC_EPI_BF16 : TVC_EPI_GELU_BF16; g.f16 = f16;
             HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
-            if (a.act == TVC_ACT_GELU) HIP_TRY(launch_gelu_erf_bf16(pb.MLPc, (int64_t)n_seq * a.mlp, st));
+            if (a.act == TVC_ACT_GELU)
+                HIP_TRY(f16 ? launch_gelu_erf_f16(pb.MLPc, (int64_t)n_seq * a.mlp, st) : launch_gelu_erf_bf16(pb.MLPc, (int64_t)n_seq * a.mlp, st));
             g = GemmLaunch();
             g.A = w.w2; g.lda = a.mlp; g.I = d; g.B = pb.MLPc; g.ldb = a.mlp; g.J = n_seq; g.K = a.mlp;
-            g.bias = w.b2; g.out = pb.D2c; g.ldo = d; g.epilogue = TVC_EPI_BF16; g.b_rows_padded = true;
+            g.bias = w.b2; g.out = pb.D2c; g.ldo = d; g.epilogue = TVC_EPI_BF16; g.b_rows_padded = true; g.f16 = f16;
             HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
             return TVC_OK;
         }
@@ -120,21 +124,23 @@ int run_layers(tvc_handle* h, const tvc_tower_arch& a, const tvc_layer_weights* 
             const double avg_len = starts ? (double)rows / n_seq : (double)seq_len;
             const double fl = 4.0 * n_seq * a.heads * avg_len * avg_len * 64 * (causal ? 0.5 : 1.0);
             ProfScope ps(h, st, TVC_PROF_ATTENTION, fl);
-            HIP_TRY(launch_attention(QKV, H, starts, n_seq, seq_len, a.heads, causal, st, pfx));
+            HIP_TRY(launch_attention(QKV, H, starts, n_seq, seq_len, a.heads, causal, st, pfx, 0, nullptr, f16));
         }
         g = GemmLaunch();
         g.A = w.wo; g.lda = d; g.I = d; g.B = H; g.ldb = d; g.J = rows; g.K = d;
         g.bias = w.bo; g.out = D1; g.ldo = d; g.epilogue = TVC_EPI_BF16; g.b_rows_padded = true;
         g.splitk_small = gs != nullptr;
+        g.f16 = f16;
         HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
         {
             ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)rows * d * 8.0);
-            HIP_TRY(launch_layernorm(X, d, nullptr, D1, 0, w.ln2_g, w.ln2_b, H, rows, d, st));
+            HIP_TRY(launch_layernorm(X, d, nullptr, D1, 0, w.ln2_g, w.ln2_b, H, rows, d, st, nullptr, 0, nullptr, nullptr, f16));
         }
         g = GemmLaunch();
         g.A = w.w1; g.lda = d; g.I = a.mlp; g.B = H; g.ldb = d; g.J = rows; g.K = d;
         g.bias = w.b1; g.b_rows_padded = true; g.ldo = a.mlp;
         g.splitk_small = gs != nullptr;
+        g.f16 = f16;
         if (gs) {
             // keep the pre-activation (what gelu' needs); the activation is one streaming pass over it
             uint16_t* U = gs->u + (size_t)l * rows * a.mlp;
@@ -146,7 +152,7 @@ int run_layers(tvc_handle* h, const tvc_tower_arch& a, const tvc_layer_weights* 
             g.out = MLP; g.epilogue = TVC_EPI_BF16;
             HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
             ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)rows * a.mlp * 4.0);
-            HIP_TRY(launch_gelu_erf_bf16(MLP, (int64_t)rows * a.mlp, st));
+            HIP_TRY(f16 ? launch_gelu_erf_f16(MLP, (int64_t)rows * a.mlp, st) : launch_gelu_erf_bf16(MLP, (int64_t)rows * a.mlp, st));
         } else {
             g.out = MLP; g.epilogue = TVC_EPI_GELU_BF16;
             HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
@@ -155,6 +161,7 @@ int run_layers(tvc_handle* h, const tvc_tower_arch& a, const tvc_layer_weights* 
         g.A = w.w2; g.lda = a.mlp; g.I = d; g.B = MLP; g.ldb = a.mlp; g.J = rows; g.K = a.mlp;
         g.bias = w.b2; g.out = D2; g.ldo = d; g.epilogue = TVC_EPI_BF16; g.b_rows_padded = true;
         g.splitk_small = gs != nullptr;
+        g.f16 = f16;
         HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
         pending = true;
     }
@@ -263,6 +270,10 @@ int tvc_encode_image(tvc_handle* h, const float* pix_dev, int32_t B, float* out_
     if (B == 0) return TVC_OK;
     if (h->tower_precision == 1) return tvc_precise_encode_image(h, pix_dev, B, out_dev, normalize, st);
     if (h->tower_precision == 2) return tvc_split_encode_image(h, pix_dev, B, out_dev, normalize, st);
+    // precision 3: the same launches on the fp16 weight set, every 16-bit activation fp16
+    const bool f16 = h->tower_precision == 3;
+    if (f16 && !h->has_vision16) return fail(h, TVC_E_STATE, "tvc_encode_image: TVC_OPT_TOWER_PRECISION = 3 needs tvc_set_weights_f16 (vision)");
+    const tvc_vision_weights& vw = f16 ? h->vw16 : h->vw;
     int rc;
     if ((rc = ensure_tower_ws(h, a, (int64_t)chunk * T, chunk, 0))) return rc;
     if ((rc = ensure(h, WS_PATCH, ((size_t)chunk * P + 512) * Kp * 2))) return rc;      // + tile padding, as ensure_tower_ws
@@ -272,30 +283,30 @@ int tvc_encode_image(tvc_handle* h, const float* pix_dev, int32_t B, float* out_
         uint16_t* Pm = (uint16_t*)h->ws[WS_PATCH].p;
         float* patch_out = (float*)h->ws[WS_MLP].p;    // [n*P, d] fp32 fits: mlp >= 2*d
         if ((size_t)n * P * d * 4 > h->ws[WS_MLP].n) return fail(h, TVC_E_INVALID, "tvc_encode_image: mlp < 2*width unsupported");
-        HIP_TRY(launch_im2col(pix, Pm, n, m.image_size, m.patch, Kp, st));
+        HIP_TRY(launch_im2col(pix, Pm, n, m.image_size, m.patch, Kp, st, f16));
         GemmLaunch g;
-        g.A = h->vw.patch_w; g.lda = Kp; g.I = d; g.B = Pm; g.ldb = Kp; g.J = n * P; g.K = Kp;
-        g.out = patch_out; g.ldo = d; g.epilogue = TVC_EPI_F32; g.b_rows_padded = true;
+        g.A = vw.patch_w; g.lda = Kp; g.I = d; g.B = Pm; g.ldb = Kp; g.J = n * P; g.K = Kp;
+        g.out = patch_out; g.ldo = d; g.epilogue = TVC_EPI_F32; g.b_rows_padded = true; g.f16 = f16;
         HIP_TRY(timed_gemm(h, g, st, WS_SPLITK));
-        HIP_TRY(launch_assemble_lnpre(patch_out, h->vw.cls, h->vw.pos, h->vw.ln_pre_g, h->vw.ln_pre_b,
+        HIP_TRY(launch_assemble_lnpre(patch_out, vw.cls, vw.pos, vw.ln_pre_g, vw.ln_pre_b,
                                       (float*)h->ws[WS_X].p, n, T, d, st));
         const int pool = h->pooled_last ? 1 : 0;                  // only the class token (row b*T) is pooled
-        if ((rc = run_layers(h, a, h->vw.layers, n, T, 0, nullptr, 0, 0, st, nullptr, pool, nullptr, (int64_t)T * d))) return rc;
+        if ((rc = run_layers(h, a, vw.layers, n, T, 0, nullptr, 0, 0, st, nullptr, pool, nullptr, (int64_t)T * d, nullptr, f16))) return rc;
         // ln_post on the class rows, projection, L2 norm
         uint16_t* Hc = (uint16_t*)h->ws[WS_CLS].p;
         // ln_post on the class rows (row b*T), folding in the last layer's two pending deltas
         if (pool) {
             const PoolBufs pb = pool_bufs(h, a, n, 0);
-            HIP_TRY(launch_layernorm((float*)h->ws[WS_X].p, (int64_t)T * d, nullptr, pb.D1c, 0, h->vw.ln_post_g,
-                                     h->vw.ln_post_b, Hc, n, d, st, pb.D2c, 1));
+            HIP_TRY(launch_layernorm((float*)h->ws[WS_X].p, (int64_t)T * d, nullptr, pb.D1c, 0, vw.ln_post_g,
+                                     vw.ln_post_b, Hc, n, d, st, pb.D2c, 1, nullptr, nullptr, f16));
         } else {
             HIP_TRY(launch_layernorm((float*)h->ws[WS_X].p, (int64_t)T * d, nullptr,
-                                     (const uint16_t*)h->ws[WS_DELTA].p, 0, h->vw.ln_post_g, h->vw.ln_post_b, Hc, n, d, st,
-                                     (const uint16_t*)h->ws[WS_DELTA2].p));
+                                     (const uint16_t*)h->ws[WS_DELTA].p, 0, vw.ln_post_g, vw.ln_post_b, Hc, n, d, st,
+                                     (const uint16_t*)h->ws[WS_DELTA2].p, 0, nullptr, nullptr, f16));
         }
         g = GemmLaunch();
-        g.A = h->vw.proj; g.lda = d; g.I = m.embed_dim; g.B = Hc; g.ldb = d; g.J = n; g.K = d;
-        g.out = out_dev + (size_t)b0 * m.embed_dim; g.ldo = m.embed_dim; g.epilogue = TVC_EPI_F32;
+        g.A = vw.proj; g.lda = d; g.I = m.embed_dim; g.B = Hc; g.ldb = d; g.J = n; g.K = d;
+        g.out = out_dev + (size_t)b0 * m.embed_dim; g.ldo = m.embed_dim; g.epilogue = TVC_EPI_F32; g.f16 = f16;
         HIP_TRY(timed_gemm(h, g, st, WS_SPLITK));
         if (normalize) HIP_TRY(launch_l2norm_rows(out_dev + (size_t)b0 * m.embed_dim, n, m.embed_dim, st));
     }
@@ -314,6 +325,9 @@ int tvc_encode_text(tvc_handle* h, const int32_t* tok_dev, int32_t Tn, float* ou
     if (Tn == 0) return TVC_OK;
     if (h->tower_precision == 1) return tvc_precise_encode_text(h, tok_dev, Tn, out_dev, normalize, nullptr, st);
     if (h->tower_precision == 2) return tvc_split_encode_text(h, tok_dev, Tn, out_dev, normalize, nullptr, st);
+    const bool f16 = h->tower_precision == 3;
+    if (f16 && !h->has_text16) return fail(h, TVC_E_STATE, "tvc_encode_text: TVC_OPT_TOWER_PRECISION = 3 needs tvc_set_weights_f16 (text)");
+    const tvc_text_weights& tw = f16 ? h->tw16 : h->tw;
     int chunk = Tn < h->max_chunk_texts ? Tn : h->max_chunk_texts;
     // prefix sharing needs whole groups in a pass
     const int G = (h->pack_text && h->text_group >= 2 && Tn % h->text_group == 0) ? h->text_group : 0;
@@ -348,23 +362,24 @@ int tvc_encode_text(tvc_handle* h, const int32_t* tok_dev, int32_t Tn, float* ou
                 return fail(h, TVC_E_HIP, "tvc_encode_text: inconsistent sequence lengths");
             starts = sd;
         }
-        HIP_TRY(launch_text_embed(tok, h->tw.tok_emb, h->tw.pos, (float*)h->ws[WS_TX].p, eot, starts, n, ctx, d,
+        HIP_TRY(launch_text_embed(tok, tw.tok_emb, tw.pos, (float*)h->ws[WS_TX].p, eot, starts, n, ctx, d,
                                   m.vocab, st, pfx));
         const int pool = h->pooled_last ? 2 : 0;                  // only the EOT row of every text is pooled
-        if ((rc = run_layers(h, a, h->tw.layers, n, max_len, 1, starts, total_rows, WS_TOWER_N, st, pfx, pool, eot, d))) return rc;
+        if ((rc = run_layers(h, a, tw.layers, n, max_len, 1, starts, total_rows, WS_TOWER_N, st, pfx, pool, eot, d, nullptr, f16)))
+            return rc;
         uint16_t* Hc = (uint16_t*)h->ws[WS_TCLS].p;
         if (pool) {
             const PoolBufs pb = pool_bufs(h, a, n, WS_TOWER_N);
-            HIP_TRY(launch_layernorm((float*)h->ws[WS_TX].p, d, eot, pb.D1c, 0, h->tw.ln_final_g, h->tw.ln_final_b, Hc,
-                                     n, d, st, pb.D2c, 1));
+            HIP_TRY(launch_layernorm((float*)h->ws[WS_TX].p, d, eot, pb.D1c, 0, tw.ln_final_g, tw.ln_final_b, Hc,
+                                     n, d, st, pb.D2c, 1, nullptr, nullptr, f16));
         } else {
             HIP_TRY(launch_layernorm((float*)h->ws[WS_TX].p, d, eot, (const uint16_t*)h->ws[WS_TDELTA].p, 0,
-                                     h->tw.ln_final_g, h->tw.ln_final_b, Hc, n, d, st,
-                                     (const uint16_t*)h->ws[WS_TDELTA2].p));
+                                     tw.ln_final_g, tw.ln_final_b, Hc, n, d, st,
+                                     (const uint16_t*)h->ws[WS_TDELTA2].p, 0, nullptr, nullptr, f16));
         }
         GemmLaunch g;
-        g.A = h->tw.proj; g.lda = d; g.I = m.embed_dim; g.B = Hc; g.ldb = d; g.J = n; g.K = d;
-        g.out = out_dev + (size_t)t0 * m.embed_dim; g.ldo = m.embed_dim; g.epilogue = TVC_EPI_F32;
+        g.A = tw.proj; g.lda = d; g.I = m.embed_dim; g.B = Hc; g.ldb = d; g.J = n; g.K = d;
+        g.out = out_dev + (size_t)t0 * m.embed_dim; g.ldo = m.embed_dim; g.epilogue = TVC_EPI_F32; g.f16 = f16;
         HIP_TRY(timed_gemm(h, g, st, WS_TSPLITK));
         if (normalize) HIP_TRY(launch_l2norm_rows(out_dev + (size_t)t0 * m.embed_dim, n, m.embed_dim, st));
     }
@@ -382,6 +397,9 @@ int tvc_encode_text_hidden(tvc_handle* h, const int32_t* tok_dev, int32_t Tn, fl
     if (Tn == 0) return TVC_OK;
     if (h->tower_precision == 1) return tvc_precise_encode_text(h, tok_dev, Tn, nullptr, 0, out_dev, st);
     if (h->tower_precision == 2) return tvc_split_encode_text(h, tok_dev, Tn, nullptr, 0, out_dev, st);
+    const bool f16 = h->tower_precision == 3;
+    if (f16 && !h->has_text16) return fail(h, TVC_E_STATE, "tvc_encode_text_hidden: TVC_OPT_TOWER_PRECISION = 3 needs tvc_set_weights_f16 (text)");
+    const tvc_text_weights& tw = f16 ? h->tw16 : h->tw;
     const int chunk = Tn < h->max_chunk_texts ? Tn : h->max_chunk_texts;
     int rc;
     if ((rc = ensure_tower_ws(h, a, (int64_t)chunk * ctx, chunk, WS_TOWER_N))) return rc;
@@ -390,12 +408,12 @@ int tvc_encode_text_hidden(tvc_handle* h, const int32_t* tok_dev, int32_t Tn, fl
         const int n = (Tn - t0 < chunk) ? Tn - t0 : chunk;
         // every position is an output here (the conditioning sequence of a latent-diffusion UNet): dense rows, no
         // EOT packing, no pooling; the causal mask is the tower's own
-        HIP_TRY(launch_text_embed(tok_dev + (size_t)t0 * ctx, h->tw.tok_emb, h->tw.pos, (float*)h->ws[WS_TX].p,
+        HIP_TRY(launch_text_embed(tok_dev + (size_t)t0 * ctx, tw.tok_emb, tw.pos, (float*)h->ws[WS_TX].p,
                                   (int32_t*)h->ws[WS_EOT].p, nullptr, n, ctx, d, m.vocab, st, nullptr));
-        if ((rc = run_layers(h, a, h->tw.layers, n, ctx, 1, nullptr, 0, WS_TOWER_N, st))) return rc;
+        if ((rc = run_layers(h, a, tw.layers, n, ctx, 1, nullptr, 0, WS_TOWER_N, st, nullptr, 0, nullptr, 0, nullptr, f16))) return rc;
         HIP_TRY(launch_layernorm((float*)h->ws[WS_TX].p, d, nullptr, (const uint16_t*)h->ws[WS_TDELTA].p, 0,
-                                 h->tw.ln_final_g, h->tw.ln_final_b, nullptr, n * ctx, d, st,
-                                 (const uint16_t*)h->ws[WS_TDELTA2].p, 0, nullptr, out_dev + (size_t)t0 * ctx * d));
+                                 tw.ln_final_g, tw.ln_final_b, nullptr, n * ctx, d, st,
+                                 (const uint16_t*)h->ws[WS_TDELTA2].p, 0, nullptr, out_dev + (size_t)t0 * ctx * d, f16));
     }
     return TVC_OK;
 }
@@ -811,8 +829,15 @@ int tvc_set_option(tvc_handle* h, int32_t option, int64_t value) {
         case TVC_OPT_BANK_FILTER: h->bank_filter = value != 0; return TVC_OK;
         case TVC_OPT_POOLED_LAST_LAYER: h->pooled_last = value != 0; return TVC_OK;
         case TVC_OPT_TOWER_PRECISION: {
-            if (value < 0 || value > 2)
-                return fail(h, TVC_E_INVALID, "tvc_set_option: TVC_OPT_TOWER_PRECISION must be 0 (bf16), 1 (fp32) or 2 (split-bf16)");
+            if (value < 0 || value > 3)
+                return fail(h, TVC_E_INVALID, "tvc_set_option: TVC_OPT_TOWER_PRECISION must be 0 (bf16), 1 (fp32), 2 (split-bf16) or 3 (fp16)");
+            if (value == 3) {
+                // (TVC_E_INVALID, not TVC_E_STATE: before fp16 weights exist the value is outside what the handle offers,
+                // as it was before the mode existed)
+                if (!h->has_vision16 && !h->has_text16)
+                    return fail(h, TVC_E_INVALID, "tvc_set_option: TVC_OPT_TOWER_PRECISION = 3 needs tvc_set_weights_f16 first");
+                h->tower_precision = 3; return TVC_OK;
+            }
             if (value != 0 && !h->has_vision32 && !h->has_text32)
                 return fail(h, TVC_E_STATE, "tvc_set_option: TVC_OPT_TOWER_PRECISION = 1 / 2 needs tvc_set_weights_f32 first");
             if (value == 2) {
@@ -872,18 +897,21 @@ int tvc_profile_end(tvc_handle* h, double* ms, double* work, int64_t* launches, 
     return TVC_OK;
 }
 
-int tvc_gemm_bf16(tvc_handle* h, const uint16_t* a_dev, const uint16_t* b_dev, const float* bias_dev, void* out_dev,
-                  int32_t I, int32_t J, int32_t K, int64_t lda, int64_t ldb, int32_t ld_out, int32_t epilogue,
-                  void* stream) {
+}  // extern "C"
+
+namespace {
+int gemm16(tvc_handle* h, const char* name, bool f16, const uint16_t* a_dev, const uint16_t* b_dev, const float* bias_dev,
+           void* out_dev, int32_t I, int32_t J, int32_t K, int64_t lda, int64_t ldb, int32_t ld_out, int32_t epilogue,
+           void* stream) {
     if (!h) return TVC_E_INVALID;
     if (lda == 0) lda = K;
     if (ldb == 0) ldb = K;
     if (I <= 0 || J <= 0 || K <= 0 || K % 64 != 0 || !a_dev || !b_dev || !out_dev || ld_out < I ||
         epilogue < 0 || epilogue > 3 || lda < K || ldb < K || lda % 8 != 0 || ldb % 8 != 0)
-        return fail(h, TVC_E_INVALID, "tvc_gemm_bf16: need K % 64 == 0, ld_out >= I, lda / ldb >= K and multiples of 8");
+        return fail(h, TVC_E_INVALID, std::string(name) + ": need K % 64 == 0, ld_out >= I, lda / ldb >= K and multiples of 8");
     GemmLaunch g;
     g.A = a_dev; g.lda = lda; g.I = I; g.B = b_dev; g.ldb = ldb; g.J = J; g.K = K;
-    g.bias = bias_dev; g.out = out_dev; g.ldo = ld_out; g.epilogue = epilogue;
+    g.bias = bias_dev; g.out = out_dev; g.ldo = ld_out; g.epilogue = epilogue; g.f16 = f16;
     {
         int rc = ensure(h, WS_SPLITK, (size_t)256 * 256 * 256 * 4);       // split-K scratch (small or tail tiles)
         if (rc) return rc;
@@ -891,6 +919,21 @@ int tvc_gemm_bf16(tvc_handle* h, const uint16_t* a_dev, const uint16_t* b_dev, c
     }
     HIP_TRY(launch_gemm_bf16(g, (hipStream_t)stream));
     return TVC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int tvc_gemm_bf16(tvc_handle* h, const uint16_t* a_dev, const uint16_t* b_dev, const float* bias_dev, void* out_dev,
+                  int32_t I, int32_t J, int32_t K, int64_t lda, int64_t ldb, int32_t ld_out, int32_t epilogue,
+                  void* stream) {
+    return gemm16(h, "tvc_gemm_bf16", false, a_dev, b_dev, bias_dev, out_dev, I, J, K, lda, ldb, ld_out, epilogue, stream);
+}
+
+int tvc_gemm_f16(tvc_handle* h, const uint16_t* a_dev, const uint16_t* b_dev, const float* bias_dev, void* out_dev,
+                 int32_t I, int32_t J, int32_t K, int64_t lda, int64_t ldb, int32_t ld_out, int32_t epilogue,
+                 void* stream) {
+    return gemm16(h, "tvc_gemm_f16", true, a_dev, b_dev, bias_dev, out_dev, I, J, K, lda, ldb, ld_out, epilogue, stream);
 }
 
 int tvc_attention(tvc_handle* h, const uint16_t* qkv_dev, uint16_t* out_dev, int32_t n_seq, int32_t seq_len,
@@ -901,12 +944,51 @@ int tvc_attention(tvc_handle* h, const uint16_t* qkv_dev, uint16_t* out_dev, int
     return TVC_OK;
 }
 
+int tvc_attention_f16(tvc_handle* h, const uint16_t* qkv_dev, uint16_t* out_dev, const int32_t* starts_dev, int32_t n_seq,
+                      int32_t seq_len, int32_t heads, int32_t causal, void* stream) {
+    if (!h) return TVC_E_INVALID;
+    if (!qkv_dev || !out_dev) return fail(h, TVC_E_INVALID, "tvc_attention_f16: NULL buffer");
+    HIP_TRY(launch_attention(qkv_dev, out_dev, starts_dev, n_seq, seq_len, heads, causal, (hipStream_t)stream, nullptr, 0,
+                             nullptr, 1));
+    return TVC_OK;
+}
+
 int tvc_layernorm(tvc_handle* h, const float* x_dev, const float* g_dev, const float* b_dev, uint16_t* y_dev,
                   int32_t rows, int32_t d, void* stream) {
     if (!h) return TVC_E_INVALID;
     if (!x_dev || !g_dev || !b_dev || !y_dev) return fail(h, TVC_E_INVALID, "tvc_layernorm: NULL buffer");
     HIP_TRY(launch_layernorm(const_cast<float*>(x_dev), d, nullptr, nullptr, 0, g_dev, b_dev, y_dev, rows, d,
                              (hipStream_t)stream));
+    return TVC_OK;
+}
+
+int tvc_layernorm_f16(tvc_handle* h, const float* x_dev, const float* g_dev, const float* b_dev, uint16_t* y_dev,
+                      int32_t rows, int32_t d, void* stream) {
+    if (!h) return TVC_E_INVALID;
+    if (!x_dev || !g_dev || !b_dev || !y_dev) return fail(h, TVC_E_INVALID, "tvc_layernorm_f16: NULL buffer");
+    HIP_TRY(launch_layernorm(const_cast<float*>(x_dev), d, nullptr, nullptr, 0, g_dev, b_dev, y_dev, rows, d,
+                             (hipStream_t)stream, nullptr, 0, nullptr, nullptr, 1));
+    return TVC_OK;
+}
+
+int tvc_set_weights_f16(tvc_handle* h, const tvc_vision_weights* vision, const tvc_text_weights* text) {
+    if (!h) return TVC_E_INVALID;
+    if (vision) {
+        if (!h->has_vision) return fail(h, TVC_E_STATE, "tvc_set_weights_f16: handle was created without a vision tower");
+        if (!vision->layers || !vision->patch_w || !vision->proj) return fail(h, TVC_E_INVALID, "tvc_set_weights_f16: NULL vision weights");
+        h->vw16 = *vision;
+        h->vlayers16.assign(vision->layers, vision->layers + h->desc.vision.layers);
+        h->vw16.layers = h->vlayers16.data();
+        h->has_vision16 = true;
+    }
+    if (text) {
+        if (!h->has_text) return fail(h, TVC_E_STATE, "tvc_set_weights_f16: handle was created without a text tower");
+        if (!text->layers || !text->tok_emb || !text->proj) return fail(h, TVC_E_INVALID, "tvc_set_weights_f16: NULL text weights");
+        h->tw16 = *text;
+        h->tlayers16.assign(text->layers, text->layers + h->desc.text.layers);
+        h->tw16.layers = h->tlayers16.data();
+        h->has_text16 = true;
+    }
     return TVC_OK;
 }
 

@@ -92,6 +92,7 @@ class TVCEngine:
             _lib.check(None, rc)
         self._w_host = (vision_w, text_w)     # the caller's (fp32) weight dicts: the fp32-grade mode uploads them as they are
         self._has_f32 = False
+        self._has_f16 = False
         self.precision = "bf16"
         if precision != "bf16":
             self.set_precision(precision)
@@ -125,7 +126,7 @@ class TVCEngine:
                                                  C.byref(txt) if txt is not None else None))
         self._has_f32 = True
 
-    PRECISIONS = {"bf16": 0, "fp32": 1, "split": 2}
+    PRECISIONS = {"bf16": 0, "fp32": 1, "split": 2, "fp16": 3}
 
     def set_precision(self, precision: str) -> None:
         """Tower arithmetic (``TVC_OPT_TOWER_PRECISION``):
@@ -136,54 +137,74 @@ class TVCEngine:
           hi | lo bf16 planes, three MFMA products per element; scores within 1e-4 of the fp32 CPU path END TO END (the
           bar of BASELINE.json), EOT packing / prefix sharing kept;
         * ``"fp32"``: the exact reference -- every GEMM on the exact-f32 matrix instruction (1/16 of the bf16 rate),
-          fp32 attention; embeddings within ~1e-6 of the fp32 CPU path.
+          fp32 attention; embeddings within ~1e-6 of the fp32 CPU path;
+        * ``"fp16"``: the bf16 path with IEEE fp16 weights and 16-bit activations (the reference runs its towers in fp16)
+          at the bf16 rate; 3 more mantissa bits than bf16, but a value beyond 65504 becomes inf (never clamped).
 
-        ``"split"`` and ``"fp32"`` upload fp32 copies of the caller's weights.  The input-gradient entry points
+        ``"split"`` and ``"fp32"`` upload fp32 copies of the caller's weights, ``"fp16"`` fp16 copies (rounded to nearest
+        even on the host).  The input-gradient entry points
         (``encode_image_grad`` / ``encode_image_backward``: the PGD / Hubness loops) ALWAYS run the bf16 path, whatever
         this is set to."""
         if precision not in self.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(self.PRECISIONS)} (got {precision!r})")
         with self._lock, torch.cuda.device(self.device):
-            if precision != "bf16" and not self._has_f32:
+            if precision in ("fp32", "split") and not self._has_f32:
                 if self._w_host[0] is None and self._w_host[1] is None:
                     raise _lib.TVCError(_lib.TVC_E_STATE, "this engine has no towers to run in fp32")
                 self._upload_f32_weights()
+            if precision == "fp16" and not self._has_f16:
+                if self._w_host[0] is None and self._w_host[1] is None:
+                    raise _lib.TVCError(_lib.TVC_E_STATE, "this engine has no towers to run in fp16")
+                self._upload_f16_weights()
             self._check(self.lib.tvc_set_option(self.handle, _lib.TVC_OPT_TOWER_PRECISION, self.PRECISIONS[precision]))
         self.precision = precision
 
+    def _upload_f16_weights(self) -> None:
+        """IEEE fp16 copies of every GEMM weight for ``TVC_OPT_TOWER_PRECISION = 3`` (rounded on the host: ``.to(float16)``
+        is round-to-nearest-even; the fp32 tensors are uploaded as for the bf16 set)."""
+        vw, tw = self._w_host
+        vis = self._vision_struct(self.arch, vw, torch.float16) if vw is not None else None
+        txt = self._text_struct(self.arch, tw, torch.float16) if tw is not None else None
+        self._check(self.lib.tvc_set_weights_f16(self.handle, C.byref(vis) if vis is not None else None,
+                                                 C.byref(txt) if txt is not None else None))
+        self._has_f16 = True
+
     def _dev(self, t: torch.Tensor, dtype) -> torch.Tensor:
+        if dtype == torch.float16:
+            t = t.detach().cpu().float().to(torch.float16)      # round on the host (round to nearest even, overflow -> inf)
         d = t.detach().to(device=self.device, dtype=dtype).contiguous()
         self._keep.append(d)
         return d
 
-    def _layers(self, layers) -> "C.Array":
+    def _layers(self, layers, wdtype=torch.bfloat16) -> "C.Array":
         arr = (_lib.LayerWeights * len(layers))()
         for i, lw in enumerate(layers):
             for name in ("ln1_g", "ln1_b", "bqkv", "bo", "ln2_g", "ln2_b", "b1", "b2"):
                 setattr(arr[i], name, self._dev(lw[name], torch.float32).data_ptr())
             for name in ("wqkv", "wo", "w1", "w2"):
-                setattr(arr[i], name, self._dev(lw[name], torch.bfloat16).data_ptr())
+                setattr(arr[i], name, self._dev(lw[name], wdtype).data_ptr())
         self._keep.append(arr)
         return arr
 
-    def _vision_struct(self, arch: ClipArch, w: Dict) -> _lib.VisionWeights:
+    def _vision_struct(self, arch: ClipArch, w: Dict, wdtype=torch.bfloat16) -> _lib.VisionWeights:
+        """wdtype: the 16-bit type of the GEMM weights (bf16: tvc_create; fp16: tvc_set_weights_f16)."""
         s = _lib.VisionWeights()
         pw = torch.zeros((arch.vision.width, arch.patch_k_padded), dtype=torch.float32)
         pw[:, :arch.patch_k] = w['patch_w'].float().cpu()
-        s.patch_w = self._dev(pw, torch.bfloat16).data_ptr()
+        s.patch_w = self._dev(pw, wdtype).data_ptr()
         for name in ("cls", "pos", "ln_pre_g", "ln_pre_b", "ln_post_g", "ln_post_b"):
             setattr(s, name, self._dev(w[name], torch.float32).data_ptr())
-        s.proj = self._dev(w['proj'], torch.bfloat16).data_ptr()
-        s.layers = C.cast(self._layers(w['layers']), C.POINTER(_lib.LayerWeights))
+        s.proj = self._dev(w['proj'], wdtype).data_ptr()
+        s.layers = C.cast(self._layers(w['layers'], wdtype), C.POINTER(_lib.LayerWeights))
         self._keep.append(s)
         return s
 
-    def _text_struct(self, arch: ClipArch, w: Dict) -> _lib.TextWeights:
+    def _text_struct(self, arch: ClipArch, w: Dict, wdtype=torch.bfloat16) -> _lib.TextWeights:
         s = _lib.TextWeights()
         for name in ("tok_emb", "pos", "ln_final_g", "ln_final_b"):
             setattr(s, name, self._dev(w[name], torch.float32).data_ptr())
-        s.proj = self._dev(w['proj'], torch.bfloat16).data_ptr()
-        s.layers = C.cast(self._layers(w['layers']), C.POINTER(_lib.LayerWeights))
+        s.proj = self._dev(w['proj'], wdtype).data_ptr()
+        s.layers = C.cast(self._layers(w['layers'], wdtype), C.POINTER(_lib.LayerWeights))
         self._keep.append(s)
         return s
 
@@ -516,6 +537,38 @@ class TVCEngine:
                                                int(causal), _stream()))
         return out
 
+    def gemm_f16(self, a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: int = 0,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """fp16 twin of :meth:`gemm` (tower mode 3): a, b fp16 on the f16 MFMA; epilogues 1 / 2 store fp16."""
+        a = _require_cuda(a, torch.float16, "a")
+        b = _require_cuda(b, torch.float16, "b")
+        I, K = a.shape
+        J = b.shape[0]
+        if b.shape[1] != K:
+            raise ValueError("a and b must have the same number of columns")
+        if out is None:
+            out = torch.empty((J, I), dtype=torch.float32 if epilogue in (0, 3) else torch.float16, device=self.device)
+            if epilogue == 3:
+                out.zero_()
+        if bias is not None:
+            bias = _require_cuda(bias, torch.float32, "bias")
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.tvc_gemm_f16(self.handle, _ptr(a), _ptr(b), _ptr(bias), _ptr(out), I, J, K, K, K,
+                                              out.shape[1], epilogue, _stream()))
+        return out
+
+    def attention_f16(self, qkv: torch.Tensor, n_seq: int, seq_len: int, heads: int, causal: bool,
+                      starts: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """fp16 twin of :meth:`attention`; ``starts`` (int32 [n_seq + 1]): packed sequences of at most seq_len rows."""
+        qkv = _require_cuda(qkv, torch.float16, "qkv")
+        out = torch.empty((qkv.shape[0], heads * 64), dtype=torch.float16, device=self.device)
+        if starts is not None:
+            starts = _require_cuda(starts, torch.int32, "starts")
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.tvc_attention_f16(self.handle, _ptr(qkv), _ptr(out), _ptr(starts), n_seq, seq_len, heads,
+                                                   int(causal), _stream()))
+        return out
+
     def attention_backward(self, qkv: torch.Tensor, dout: torch.Tensor, n_seq: int, seq_len: int, heads: int) -> torch.Tensor:
         qkv = _require_cuda(qkv, torch.bfloat16, "qkv")
         dout = _require_cuda(dout, torch.bfloat16, "dout")
@@ -613,6 +666,16 @@ class TVCEngine:
         with self._lock, torch.cuda.device(self.device):
             self._check(self.lib.tvc_layernorm(self.handle, _ptr(x), _ptr(g), _ptr(b), _ptr(out), x.shape[0],
                                                x.shape[1], _stream()))
+        return out
+
+    def layernorm_f16(self, x: torch.Tensor, g: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+        x = _require_cuda(x, torch.float32, "x")
+        g = _require_cuda(g, torch.float32, "g")
+        b = _require_cuda(b, torch.float32, "b")
+        out = torch.empty(x.shape, dtype=torch.float16, device=self.device)
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.tvc_layernorm_f16(self.handle, _ptr(x), _ptr(g), _ptr(b), _ptr(out), x.shape[0],
+                                                   x.shape[1], _stream()))
         return out
 
     PROF_CATEGORIES = ("gemm", "attention", "bank", "rowops")

@@ -1,0 +1,129 @@
+// Host-only sanitizer driver of the fp16 tower mode (tests/test_fp16_host.py): the same build as
+// tests/host_san/driver.cpp -- tvc_abi.cpp, tvc_precise.cpp, tvc_split.cpp and tvc_sd.cpp with g++ -fsanitize=address,undefined
+// against tests/host_san's HIP stand-in, whose GEMM launcher checks every operand / output range -- walking
+// TVC_OPT_TOWER_PRECISION = 3: refused before tvc_set_weights_f16, then image / text (dense, packed, grouped, pooled on and
+// off, chunked) and hidden-state encodes on the fp16 weight set, the switch back to bf16, and a leak-free tvc_destroy.
+#include "../../include/tvc.h"
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#define CHECK(cond)                                                                              \
+    do {                                                                                         \
+        if (!(cond)) { fprintf(stderr, "driver.cpp:%d: CHECK failed: %s\n", __LINE__, #cond); return 1; } \
+    } while (0)
+#define OK(call)                                                                                           \
+    do {                                                                                                   \
+        int rc__ = (call);                                                                                 \
+        if (rc__ != TVC_OK) { fprintf(stderr, "driver.cpp:%d: %s -> %d (%s)\n", __LINE__, #call, rc__, tvc_last_error(h)); return 1; } \
+    } while (0)
+
+static void* dev(size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) abort(); return p; }
+
+int main() {
+    tvc_handle* h = nullptr;
+    // toy two-tower geometry (ViT-T/16-test): widths 256 / 128, 2 layers; the text tower uses erf GELU (the fp16 gelu pass)
+    tvc_model_desc m{};
+    m.image_size = 64; m.patch = 16; m.vocab = 49408; m.ctx = 77; m.embed_dim = 128;
+    m.vision = {256, 2, 4, 512, TVC_ACT_QUICK_GELU}; m.text = {128, 2, 2, 256, TVC_ACT_GELU};
+    const int Kp = 768;                                       // 3 * 16 * 16, already a multiple of 64
+    std::vector<void*> keep;
+    // weights are sized exactly (GEMM weight rows padded to whole 256-row tiles, as tvc_create's contract asks), so the
+    // stub's range check sees any slip in the fp16 set's addressing
+    auto buf = [&](size_t elems, size_t es) { void* p = dev(elems * es); keep.push_back(p); return p; };
+    auto rows256 = [](int r) { return (size_t)(r + 255) / 256 * 256; };
+    auto layers = [&](const tvc_tower_arch& a) {
+        std::vector<tvc_layer_weights> L(a.layers);
+        for (auto& l : L) {
+            l.ln1_g = (float*)buf(a.width, 4); l.ln1_b = (float*)buf(a.width, 4); l.ln2_g = (float*)buf(a.width, 4); l.ln2_b = (float*)buf(a.width, 4);
+            l.wqkv = (uint16_t*)buf(rows256(3 * a.width) * a.width, 2); l.bqkv = (float*)buf(3 * a.width, 4);
+            l.wo = (uint16_t*)buf(rows256(a.width) * a.width, 2); l.bo = (float*)buf(a.width, 4);
+            l.w1 = (uint16_t*)buf(rows256(a.mlp) * a.width, 2); l.b1 = (float*)buf(a.mlp, 4);
+            l.w2 = (uint16_t*)buf(rows256(a.width) * a.mlp, 2); l.b2 = (float*)buf(a.width, 4);
+        }
+        return L;
+    };
+    auto vl = layers(m.vision), tl = layers(m.text);
+    tvc_vision_weights vw{};
+    vw.patch_w = (uint16_t*)buf(rows256(256) * Kp, 2); vw.cls = (float*)buf(256, 4); vw.pos = (float*)buf(17 * 256, 4);
+    vw.ln_pre_g = (float*)buf(256, 4); vw.ln_pre_b = (float*)buf(256, 4); vw.ln_post_g = (float*)buf(256, 4); vw.ln_post_b = (float*)buf(256, 4);
+    vw.proj = (uint16_t*)buf(rows256(128) * 256, 2); vw.layers = vl.data();
+    tvc_text_weights tw{};
+    tw.tok_emb = (float*)buf((size_t)49408 * 128, 4); tw.pos = (float*)buf(77 * 128, 4); tw.ln_final_g = (float*)buf(128, 4);
+    tw.ln_final_b = (float*)buf(128, 4); tw.proj = (uint16_t*)buf(rows256(128) * 128, 2); tw.layers = tl.data();
+    CHECK(tvc_create(&m, &vw, &tw, &h) == TVC_OK && h);
+    // ---- mode 3 is refused until fp16 weights are registered; the refusal leaves the handle in bf16
+    CHECK(tvc_set_option(h, TVC_OPT_TOWER_PRECISION, 3) == TVC_E_INVALID && strstr(tvc_last_error(h), "tvc_set_weights_f16"));
+    CHECK(tvc_set_option(h, TVC_OPT_TOWER_PRECISION, 4) == TVC_E_INVALID);
+    const int B = 5, N = 3;
+    float* pix = (float*)buf((size_t)B * 3 * 64 * 64, 4);
+    int32_t* tok = (int32_t*)buf((size_t)B * (N + 1) * 77, 4);
+    memset(tok, 0, (size_t)B * (N + 1) * 77 * 4);
+    float* fi = (float*)buf(B * 128, 4); float* ft = (float*)buf(B * (N + 1) * 128, 4);
+    float* hid = (float*)buf((size_t)B * 77 * 128, 4);
+    OK(tvc_encode_image(h, pix, B, fi, 1, nullptr));
+    // ---- the fp16 weight set: its own GEMM weights, fp32 tensors aliasing the bf16 set's
+    auto vl16 = layers(m.vision), tl16 = layers(m.text);
+    for (int l = 0; l < m.vision.layers; ++l) {
+        vl16[l].ln1_g = vl[l].ln1_g; vl16[l].ln1_b = vl[l].ln1_b; vl16[l].bqkv = vl[l].bqkv; vl16[l].b2 = vl[l].b2;
+    }
+    tvc_vision_weights vw16 = vw;
+    vw16.patch_w = (uint16_t*)buf(rows256(256) * Kp, 2); vw16.proj = (uint16_t*)buf(rows256(128) * 256, 2); vw16.layers = vl16.data();
+    tvc_text_weights tw16 = tw;
+    tw16.proj = (uint16_t*)buf(rows256(128) * 128, 2); tw16.layers = tl16.data();
+    {
+        tvc_vision_weights bad = vw16; bad.layers = nullptr;
+        CHECK(tvc_set_weights_f16(h, &bad, nullptr) == TVC_E_INVALID);
+        CHECK(tvc_set_weights_f16(nullptr, &vw16, &tw16) == TVC_E_INVALID);
+    }
+    // only the vision set: the text tower refuses mode 3 instead of reading missing weights
+    OK(tvc_set_weights_f16(h, &vw16, nullptr));
+    OK(tvc_set_option(h, TVC_OPT_TOWER_PRECISION, 3));
+    OK(tvc_encode_image(h, pix, B, fi, 1, nullptr));
+    CHECK(tvc_encode_text(h, tok, B * (N + 1), ft, 1, nullptr) == TVC_E_STATE);
+    CHECK(tvc_encode_text_hidden(h, tok, B, hid, nullptr) == TVC_E_STATE);
+    OK(tvc_set_weights_f16(h, nullptr, &tw16));
+    // ---- fp16 towers: dense, packed, grouped, pooled on / off, chunked, hidden states
+    for (int pooled = 0; pooled < 2; ++pooled)
+        for (int pack = 0; pack < 2; ++pack) {
+            OK(tvc_set_option(h, TVC_OPT_POOLED_LAST_LAYER, pooled));
+            OK(tvc_set_option(h, TVC_OPT_TEXT_PACKING, pack));
+            OK(tvc_set_option(h, TVC_OPT_TEXT_GROUP, pack ? N + 1 : 0));
+            OK(tvc_encode_image(h, pix, B, fi, 1, nullptr));
+            OK(tvc_encode_text(h, tok, B * (N + 1), ft, 1, nullptr));
+        }
+    OK(tvc_set_option(h, TVC_OPT_MAX_CHUNK_IMAGES, 2)); OK(tvc_set_option(h, TVC_OPT_MAX_CHUNK_TEXTS, 7));
+    OK(tvc_encode_image(h, pix, B, fi, 0, nullptr)); OK(tvc_encode_text(h, tok, B * (N + 1), ft, 0, nullptr));
+    OK(tvc_encode_text_hidden(h, tok, B, hid, nullptr));
+    OK(tvc_set_option(h, TVC_OPT_MAX_CHUNK_IMAGES, 512)); OK(tvc_set_option(h, TVC_OPT_MAX_CHUNK_TEXTS, 4608));
+    OK(tvc_encode_text_hidden(h, tok, B, hid, nullptr));
+    // the input-gradient path keeps running bf16 in mode 3
+    float* gout = (float*)buf(B * 128, 4); float* gpix = (float*)buf((size_t)B * 3 * 64 * 64, 4);
+    OK(tvc_encode_image_grad(h, pix, B, fi, 1, nullptr)); OK(tvc_encode_image_backward(h, gout, gpix, nullptr));
+    // ---- parity building blocks (argument checks; the stub checks the GEMM ranges)
+    uint16_t* a16 = (uint16_t*)buf(256 * 128, 2); uint16_t* b16 = (uint16_t*)buf(300 * 128, 2); float* o32 = (float*)buf(300 * 256, 4);
+    OK(tvc_gemm_f16(h, a16, b16, nullptr, o32, 256, 300, 128, 0, 0, 256, 0, nullptr));
+    OK(tvc_gemm_f16(h, a16, b16, nullptr, o32, 256, 300, 128, 0, 0, 256, 1, nullptr));
+    CHECK(tvc_gemm_f16(h, a16, b16, nullptr, o32, 256, 300, 100, 0, 0, 256, 0, nullptr) == TVC_E_INVALID);
+    uint16_t* qkv = (uint16_t*)buf((size_t)2 * 77 * 3 * 128, 2); uint16_t* ao = (uint16_t*)buf((size_t)2 * 77 * 128, 2);
+    OK(tvc_attention_f16(h, qkv, ao, nullptr, 2, 77, 2, 1, nullptr));
+    CHECK(tvc_attention_f16(h, nullptr, ao, nullptr, 2, 77, 2, 1, nullptr) == TVC_E_INVALID);
+    OK(tvc_layernorm_f16(h, o32, vw.ln_pre_g, vw.ln_pre_b, ao, 2, 128, nullptr));
+    // ---- profiling bracket in mode 3, then back to bf16
+    double ms[TVC_PROF_NCAT], work[TVC_PROF_NCAT], big[3]; int64_t launches[TVC_PROF_NCAT];
+    OK(tvc_profile_begin(h)); OK(tvc_encode_image(h, pix, B, fi, 1, nullptr)); OK(tvc_profile_end(h, ms, work, launches, big));
+    CHECK(launches[TVC_PROF_GEMM] > 0);
+    OK(tvc_set_option(h, TVC_OPT_TOWER_PRECISION, 0));
+    OK(tvc_encode_image(h, pix, B, fi, 1, nullptr)); OK(tvc_encode_text(h, tok, B * (N + 1), ft, 1, nullptr));
+    OK(tvc_set_option(h, TVC_OPT_TOWER_PRECISION, 3));           // registered weights stay registered
+    OK(tvc_encode_text(h, tok, B * (N + 1), ft, 1, nullptr));
+    OK(tvc_set_option(h, TVC_OPT_TOWER_PRECISION, 0));
+    tvc_destroy(h);
+    for (void* p : keep) (void)hipFree(p);
+    CHECK(hip_stub_blocks().empty());                               // every handle-owned device block was released
+    printf("HOST_SAN_F16_OK\n");
+    return 0;
+}
