@@ -1,6 +1,7 @@
 // Internal: the handle behind include/tvc.h, its workspace slots and the launch helpers shared by the translation
-// units that implement the C-ABI (tvc_abi.cpp: CLIP towers, bank, consistency; tvc_precise.cpp: fp32-grade towers;
-// tvc_sd.cpp: latent-diffusion reference generator).
+// units that implement the C-ABI (tvc_abi.cpp: the CLIP tower encode drivers of every precision mode and the bf16 /
+// fp16 towers, bank, consistency; tvc_precise.cpp: the fp32-grade towers' stem, layer loop and head; tvc_split.cpp: the
+// split-bf16 towers' stem, layer loop, head and weight planes; tvc_sd.cpp: latent-diffusion reference generator).
 #pragma once
 #include "../../include/tvc.h"
 #include "kernels.hpp"
@@ -25,7 +26,7 @@ enum Slot {
     WS_GSAVE, WS_GOUT, WS_GXL, WS_GDX, WS_G16, WS_GMLP2, WS_GDQKV, WS_GSTATS, WS_GSMALL, WS_GPATCH,
     // fp32-grade towers (TVC_OPT_TOWER_PRECISION = 1): vision set, then the text set (+ WS_P_N)
     WS_PX, WS_PH, WS_PQKV, WS_PMLP, WS_PCLS, WS_P_N_END,
-    WS_PTX = WS_P_N_END, WS_PTH, WS_PTQKV, WS_PTMLP, WS_PTCLS, WS_PEOT,
+    WS_PTX = WS_P_N_END, WS_PTH, WS_PTQKV, WS_PTMLP, WS_PTCLS,
     // split-bf16 towers (TVC_OPT_TOWER_PRECISION = 2, tvc_split.cpp): vision set, then the text set (+ WS_S_N)
     WS_SX, WS_SH, WS_SQKV, WS_SU, WS_SM, WS_SDELTA1, WS_SDELTA2, WS_SCLS, WS_S_END,
     WS_STX = WS_S_END, WS_STH, WS_STQKV, WS_STU, WS_STM, WS_STDELTA1, WS_STDELTA2, WS_STCLS,
@@ -48,6 +49,7 @@ struct BankSlot {
     float* bounds = nullptr;          // device [2]: max row norms of the bank planes
 };
 
+constexpr int WS_P_N = WS_P_N_END - WS_PX;    // offset from a vision fp32-grade slot to its text twin
 constexpr int WS_S_N = WS_S_END - WS_SX;      // offset from a vision split slot to its text twin
 
 // hi | lo bf16 planes [round_up(out, 256), 2 * in] of one layer's GEMM weights (split-bf16 mode), handle-owned
@@ -61,12 +63,26 @@ struct ProfRec {
     int gI = 0, gJ = 0, gK = 0, gP = 0, gS = 0;     // GEMM launches: shape, planes, fixed K split (TVC_PROF_DUMP)
 };
 
+// One registered weight set of a tower: the caller's struct with its layer array copied (the caller's array may go away
+// after the call; the tensors themselves are referenced, not copied)
+template <class W, class L>
+struct TowerWeights {
+    W w{};
+    std::vector<L> layers;
+    bool set = false;
+    void assign(const W& src, int n_layers) {
+        w = src;
+        layers.assign(src.layers, src.layers + n_layers);
+        w.layers = layers.data();
+        set = true;
+    }
+};
+
 struct tvc_handle {
     tvc_model_desc desc{};
-    bool has_vision = false, has_text = false;
-    tvc_vision_weights vw{};
-    tvc_text_weights tw{};
-    std::vector<tvc_layer_weights> vlayers, tlayers;
+    // bf16 weights (tvc_create): precision 0 and the input-gradient path; `set` = the handle has that tower
+    TowerWeights<tvc_vision_weights, tvc_layer_weights> vision;
+    TowerWeights<tvc_text_weights, tvc_layer_weights> text;
     // banks: TVC_MAX_BANKS independent slots (retriever index, reference bank, defense references ...
     // registered by different owners on one engine); tvc_bank_select picks the one the bank calls address
     BankSlot banks[TVC_MAX_BANKS];
@@ -86,17 +102,13 @@ struct tvc_handle {
     const float* grad_pix = nullptr;
     bool prof = false;
     std::vector<ProfRec> prof_recs;
-    // fp32-grade towers: fp32 copies of every weight (tvc_set_weights_f32) and the switch
-    bool has_vision32 = false, has_text32 = false;
-    tvc_vision_weights_f32 vw32{};
-    tvc_text_weights_f32 tw32{};
-    std::vector<tvc_layer_weights_f32> vlayers32, tlayers32;
+    // fp32 copies of every weight (tvc_set_weights_f32): precision 1, and the source of precision 2's planes
+    TowerWeights<tvc_vision_weights_f32, tvc_layer_weights_f32> vision32;
+    TowerWeights<tvc_text_weights_f32, tvc_layer_weights_f32> text32;
     int tower_precision = 0;   // TVC_OPT_TOWER_PRECISION
-    // fp16 towers (precision 3): the caller's IEEE fp16 weight set (tvc_set_weights_f16), referenced like the bf16 one
-    bool has_vision16 = false, has_text16 = false;
-    tvc_vision_weights vw16{};
-    tvc_text_weights tw16{};
-    std::vector<tvc_layer_weights> vlayers16, tlayers16;
+    // fp16 towers (precision 3): the caller's IEEE fp16 weight set (tvc_set_weights_f16)
+    TowerWeights<tvc_vision_weights, tvc_layer_weights> vision16;
+    TowerWeights<tvc_text_weights, tvc_layer_weights> text16;
     // split-bf16 mode (precision 2): planes of every GEMM weight, built from the fp32 copies when the option is set
     std::vector<SplitLayer> vsplit, tsplit;
     uint16_t* vsplit_patch = nullptr;
@@ -112,6 +124,25 @@ struct tvc_handle {
 void tvc_sd_free(tvc_handle* h);    // tvc_sd.cpp
 void tvc_split_free(tvc_handle* h); // tvc_split.cpp
 int tvc_split_prepare(tvc_handle* h);
+
+// What precisions 1 (tvc_precise.cpp) and 2 (tvc_split.cpp) supply to the tower encode drivers of tvc_abi.cpp, which
+// own everything else (checks, chunking, text packing, embeddings, L2 normalisation); `text` picks the tower.
+//   *_ensure: the workspace of passes of up to n_seq sequences; X = the fp32 residual stream the embeddings go to
+//   *_stem:   im2col + patch GEMM of n images -> patch_out fp32 [n * P, d]
+//   *_layers: n_seq sequences of seq_len dense rows, or (starts) total_rows packed rows
+//   *_head:   final LayerNorm of `rows` rows of X (x_stride, row_idx as launch_layernorm), then the projection to out
+//             [rows, embed_dim]; hidden: the LayerNorm's fp32 rows to out instead
+int precise_ensure(tvc_handle* h, bool text, int n_seq, float** X);
+int precise_stem(tvc_handle* h, const float* pix, int n, const float** patch_out, hipStream_t st);
+int precise_layers(tvc_handle* h, bool text, int n_seq, int seq_len, hipStream_t st);
+int precise_head(tvc_handle* h, bool text, int64_t x_stride, const int32_t* row_idx, int rows, float* out, bool hidden,
+                 hipStream_t st);
+int split_ensure(tvc_handle* h, bool text, int n_seq, float** X);
+int split_stem(tvc_handle* h, const float* pix, int n, const float** patch_out, hipStream_t st);
+int split_layers(tvc_handle* h, bool text, int n_seq, int seq_len, const int32_t* starts, int total_rows,
+                 const int32_t* pfx, hipStream_t st);
+int split_head(tvc_handle* h, bool text, int64_t x_stride, const int32_t* row_idx, int rows, float* out, bool hidden,
+               hipStream_t st);
 
 inline int fail(tvc_handle* h, int code, const std::string& msg) {
     if (h) h->err = msg; else g_create_error = msg;
@@ -193,4 +224,12 @@ inline hipError_t timed_gemm(tvc_handle* h, const GemmLaunch& g, hipStream_t st,
         return launch_gemm_bf16(g2, st);
     }
     return launch_gemm_bf16(g, st);
+}
+
+// exact-f32 GEMM (precise.hip): out[j, i] (op)= sum_k X[j, k] W[i, k] + bias[i], epi as launch_gemm_f32
+inline int timed_gemm_f32(tvc_handle* h, const float* W, int I, int K, const float* X, int64_t J, const float* bias, float* out,
+                          int64_t ldo, int epi, hipStream_t st) {
+    ProfScope ps(h, st, TVC_PROF_GEMM, 2.0 * I * (double)J * K);
+    HIP_TRY(launch_gemm_f32(W, K, X, K, bias, out, ldo, I, (int)J, K, epi, st));
+    return TVC_OK;
 }

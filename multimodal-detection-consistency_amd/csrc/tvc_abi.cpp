@@ -6,16 +6,6 @@
 
 #include <cstdlib>
 
-// tvc_precise.cpp
-int tvc_precise_encode_image(tvc_handle* h, const float* pix_dev, int32_t B, float* out_dev, int32_t normalize, hipStream_t st);
-int tvc_precise_encode_text(tvc_handle* h, const int32_t* tok_dev, int32_t Tn, float* out_dev, int32_t normalize,
-                            float* hidden_out, hipStream_t st);
-
-// tvc_split.cpp
-int tvc_split_encode_image(tvc_handle* h, const float* pix_dev, int32_t B, float* out_dev, int32_t normalize, hipStream_t st);
-int tvc_split_encode_text(tvc_handle* h, const int32_t* tok_dev, int32_t Tn, float* out_dev, int32_t normalize, float* hidden_out,
-                          hipStream_t st);
-
 namespace {
 
 bool tower_ok(const tvc_tower_arch& a) {
@@ -187,6 +177,162 @@ int ensure_tower_ws(tvc_handle* h, const tvc_tower_arch& a, int64_t rows, int n_
     return TVC_OK;
 }
 
+// The bf16 / fp16 stem: im2col + patch GEMM of n images -> patch_out fp32 [n * P, d] (fn names the caller in errors)
+int patch_stem(tvc_handle* h, const char* fn, const float* pix, int n, bool f16, const float** patch_out, hipStream_t st) {
+    const tvc_model_desc& m = h->desc;
+    const int gside = m.image_size / m.patch, P = gside * gside, d = m.vision.width;
+    const int Kp = (3 * m.patch * m.patch + 63) / 64 * 64;
+    uint16_t* Pm = (uint16_t*)h->ws[WS_PATCH].p;
+    float* po = (float*)h->ws[WS_MLP].p;    // [n*P, d] fp32 fits: mlp >= 2*d
+    if ((size_t)n * P * d * 4 > h->ws[WS_MLP].n) return fail(h, TVC_E_INVALID, std::string(fn) + ": mlp < 2*width unsupported");
+    HIP_TRY(launch_im2col(pix, Pm, n, m.image_size, m.patch, Kp, st, f16));
+    GemmLaunch g;
+    g.A = (f16 ? h->vision16 : h->vision).w.patch_w; g.lda = Kp; g.I = d; g.B = Pm; g.ldb = Kp; g.J = n * P; g.K = Kp;
+    g.out = po; g.ldo = d; g.epilogue = TVC_EPI_F32; g.b_rows_padded = true; g.f16 = f16;
+    HIP_TRY(timed_gemm(h, g, st, WS_SPLITK));
+    *patch_out = po;
+    return TVC_OK;
+}
+
+// ---- what the tower encode drivers ask of the precision mode (TVC_OPT_TOWER_PRECISION): its weights, stem, layer loop
+// and head -- 0 (bf16) and 3 (the same launches on the fp16 weight set) here, 1 in tvc_precise.cpp, 2 in tvc_split.cpp.
+// Mode 1 runs dense; mode 2 packs text rows but has no pooled last layer.
+
+// TVC_E_STATE unless the mode's weights of the tower are registered; then sizes the mode's workspace for passes of up to
+// n_seq sequences.  X: the fp32 residual stream the embeddings go to.
+int tower_begin(tvc_handle* h, bool text, const char* fn, int n_seq, float** X) {
+    const int mode = h->tower_precision;
+    auto missing = [&](const char* tail) {      // modes 1 and 2 name the tower's encode call, mode 3 the entry point
+        return fail(h, TVC_E_STATE, std::string(mode == 3 ? fn : text ? "tvc_encode_text" : "tvc_encode_image") +
+                                        ": TVC_OPT_TOWER_PRECISION = " + std::to_string(mode) + " needs tvc_set_weights_f" +
+                                        (mode == 3 ? "16" : "32") + (text ? " (text)" : " (vision)") + tail);
+    };
+    const bool has32 = text ? h->text32.set : h->vision32.set;
+    if (mode == 1) return has32 ? precise_ensure(h, text, n_seq, X) : missing("");
+    if (mode == 2) {
+        if (!has32 || !h->split_ready || (text ? h->tsplit : h->vsplit).empty()) return missing(" before the option is set");
+        return split_ensure(h, text, n_seq, X);
+    }
+    if (mode == 3 && !(text ? h->text16.set : h->vision16.set)) return missing("");
+    const tvc_model_desc& m = h->desc;
+    const int gside = m.image_size / m.patch, P = gside * gside, T = P + 1;
+    const int Kp = (3 * m.patch * m.patch + 63) / 64 * 64;
+    int rc;
+    if (text) {
+        if ((rc = ensure_tower_ws(h, m.text, (int64_t)n_seq * m.ctx, n_seq, WS_TOWER_N))) return rc;
+    } else {
+        if ((rc = ensure_tower_ws(h, m.vision, (int64_t)n_seq * T, n_seq, 0))) return rc;
+        if ((rc = ensure(h, WS_PATCH, ((size_t)n_seq * P + 512) * Kp * 2))) return rc;      // + tile padding, as ensure_tower_ws
+    }
+    *X = (float*)h->ws[WS_X + (text ? WS_TOWER_N : 0)].p;
+    return TVC_OK;
+}
+
+// pool (modes 0, 3): the last layer computes only the pooled row of every sequence, at X + row_idx[s] * x_stride (text:
+// the EOT rows) or X + s * x_stride (vision: the class rows)
+int tower_layers(tvc_handle* h, bool text, int n_seq, int seq_len, const int32_t* starts, int total_rows, const int32_t* pfx,
+                 bool pool, int64_t x_stride, const int32_t* row_idx, hipStream_t st) {
+    if (h->tower_precision == 1) return precise_layers(h, text, n_seq, seq_len, st);
+    if (h->tower_precision == 2) return split_layers(h, text, n_seq, seq_len, starts, total_rows, pfx, st);
+    const bool f16 = h->tower_precision == 3;
+    const tvc_layer_weights* lw = text ? (f16 ? h->text16 : h->text).w.layers : (f16 ? h->vision16 : h->vision).w.layers;
+    return run_layers(h, text ? h->desc.text : h->desc.vision, lw, n_seq, seq_len, text ? 1 : 0, starts, total_rows,
+                      text ? WS_TOWER_N : 0, st, pfx, pool ? (text ? 2 : 1) : 0, row_idx, x_stride, nullptr, f16);
+}
+
+// final LayerNorm (ln_post / ln_final) of `rows` rows of X, folding in the last layer's two pending deltas, then the
+// projection to out [rows, embed_dim]; hidden: the LayerNorm's fp32 rows to out instead
+int tower_head(tvc_handle* h, bool text, int64_t x_stride, const int32_t* row_idx, int rows, bool pool, float* out, bool hidden,
+               hipStream_t st) {
+    if (h->tower_precision == 1) return precise_head(h, text, x_stride, row_idx, rows, out, hidden, st);
+    if (h->tower_precision == 2) return split_head(h, text, x_stride, row_idx, rows, out, hidden, st);
+    const bool f16 = h->tower_precision == 3;
+    const tvc_model_desc& m = h->desc;
+    const tvc_tower_arch& a = text ? m.text : m.vision;
+    const int d = a.width, wso = text ? WS_TOWER_N : 0;
+    const tvc_vision_weights& vw = (f16 ? h->vision16 : h->vision).w;
+    const tvc_text_weights& tw = (f16 ? h->text16 : h->text).w;
+    const PoolBufs pb = pool ? pool_bufs(h, a, rows, wso) : PoolBufs{};    // a pooled last layer's deltas: compact, output row order
+    uint16_t* Hc = hidden ? nullptr : (uint16_t*)h->ws[WS_CLS + wso].p;
+    HIP_TRY(launch_layernorm((float*)h->ws[WS_X + wso].p, x_stride, row_idx, pool ? pb.D1c : (const uint16_t*)h->ws[WS_DELTA + wso].p,
+                             0, text ? tw.ln_final_g : vw.ln_post_g, text ? tw.ln_final_b : vw.ln_post_b, Hc, rows, d, st,
+                             pool ? pb.D2c : (const uint16_t*)h->ws[WS_DELTA2 + wso].p, pool ? 1 : 0, nullptr,
+                             hidden ? out : nullptr, f16));
+    if (hidden) return TVC_OK;
+    GemmLaunch g;
+    g.A = text ? tw.proj : vw.proj; g.lda = d; g.I = m.embed_dim; g.B = Hc; g.ldb = d; g.J = rows; g.K = d;
+    g.out = out; g.ldo = m.embed_dim; g.epilogue = TVC_EPI_F32; g.f16 = f16;
+    HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
+    return TVC_OK;
+}
+
+// tvc_encode_text (pooled embeddings to out_dev) and, hidden, tvc_encode_text_hidden (ln_final at every position of the
+// dense rows -> out_dev [Tn, ctx, width])
+int encode_text(tvc_handle* h, const char* fn, const int32_t* tok_dev, int32_t Tn, float* out_dev, int32_t normalize, bool hidden,
+                void* stream) {
+    if (!h) return TVC_E_INVALID;
+    if (!h->text.set) return fail(h, TVC_E_STATE, std::string(fn) + ": handle has no text tower");
+    if (Tn < 0 || (Tn > 0 && (!tok_dev || !out_dev))) return fail(h, TVC_E_INVALID, std::string(fn) + ": bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    const tvc_model_desc& m = h->desc;
+    const int d = m.text.width, ctx = m.ctx;
+    if (Tn == 0) return TVC_OK;
+    int chunk = Tn < h->max_chunk_texts ? Tn : h->max_chunk_texts;
+    const int mode = h->tower_precision;
+    // every position is an output of a hidden-state call (the conditioning sequence of a latent-diffusion UNet): dense
+    // rows, no EOT packing, no pooling; the causal mask is the tower's own
+    const bool pack = h->pack_text && !hidden && mode != 1;
+    const bool pool = h->pooled_last && !hidden && (mode == 0 || mode == 3);      // only the EOT row of every text is pooled
+    // prefix sharing needs whole groups in a pass
+    const int G = (pack && h->text_group >= 2 && Tn % h->text_group == 0) ? h->text_group : 0;
+    if (G && chunk >= G) chunk = chunk / G * G;
+    const bool share = G && chunk % G == 0;
+    float* X;
+    int rc;
+    if ((rc = tower_begin(h, true, fn, chunk, &X))) return rc;
+    if (share && (rc = ensure(h, WS_PFX, (size_t)chunk * 2 * 4))) return rc;
+    if ((rc = ensure(h, WS_EOT, (size_t)chunk * 4))) return rc;
+    if (pack && (rc = ensure(h, WS_STARTS, (size_t)(chunk + 2) * 4))) return rc;
+    if (pack && (rc = ensure(h, WS_LENS, (size_t)chunk * 4))) return rc;
+    int32_t* eot = (int32_t*)h->ws[WS_EOT].p;
+    for (int t0 = 0; t0 < Tn; t0 += chunk) {
+        const int n = (Tn - t0 < chunk) ? Tn - t0 : chunk;
+        const int32_t* tok = tok_dev + (size_t)t0 * ctx;
+        const int32_t* starts = nullptr;
+        const int32_t* pfx = nullptr;
+        int total_rows = n * ctx, max_len = ctx;
+        if (pack) {
+            // Keep only the tokens up to and including EOT: under the causal mask the later
+            // positions cannot reach the pooled (EOT) row, so the result is bit-identical.
+            // The row count sizes the GEMM grids, hence ONE 8-byte read-back per call.
+            int32_t* sd = (int32_t*)h->ws[WS_STARTS].p;
+            int32_t* pd = share ? (int32_t*)h->ws[WS_PFX].p : nullptr;
+            HIP_TRY(launch_text_lens_scan(tok, sd, pd, n, ctx, G, st, (int32_t*)h->ws[WS_LENS].p));
+            pfx = pd;
+            int32_t tail[2] = {0, 0};
+            HIP_TRY(hipMemcpyAsync(tail, sd + n, sizeof tail, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            total_rows = tail[0]; max_len = tail[1];
+            if (total_rows < (share ? n / G : n) || total_rows > n * ctx || max_len < 1 || max_len > ctx)
+                return fail(h, TVC_E_HIP, "tvc_encode_text: inconsistent sequence lengths");
+            starts = sd;
+        }
+        auto embed = [&](const auto& w) {
+            return launch_text_embed(tok, w.tok_emb, w.pos, X, eot, starts, n, ctx, d, m.vocab, st, pfx);
+        };
+        HIP_TRY(mode == 1 || mode == 2 ? embed(h->text32.w) : embed((mode == 3 ? h->text16 : h->text).w));
+        if ((rc = tower_layers(h, true, n, max_len, starts, total_rows, pfx, pool, d, eot, st))) return rc;
+        if (hidden) {
+            if ((rc = tower_head(h, true, d, nullptr, n * ctx, false, out_dev + (size_t)t0 * ctx * d, true, st))) return rc;
+            continue;
+        }
+        float* out = out_dev + (size_t)t0 * m.embed_dim;
+        if ((rc = tower_head(h, true, d, eot, n, pool, out, false, st))) return rc;
+        if (normalize) HIP_TRY(launch_l2norm_rows(out, n, m.embed_dim, st));
+    }
+    return TVC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -216,10 +362,7 @@ int tvc_create(const tvc_model_desc* desc, const tvc_vision_weights* vision, con
         }
         const int T = (d.image_size / d.patch) * (d.image_size / d.patch) + 1;
         if (T > 288) { delete nh; return fail(h, TVC_E_INVALID, "tvc_create: vision sequence longer than 288 tokens"); }
-        nh->vw = *vision;
-        nh->vlayers.assign(vision->layers, vision->layers + d.vision.layers);
-        nh->vw.layers = nh->vlayers.data();
-        nh->has_vision = true;
+        nh->vision.assign(*vision, d.vision.layers);
     }
     if (text) {
         const tvc_model_desc& d = *desc;
@@ -227,10 +370,7 @@ int tvc_create(const tvc_model_desc* desc, const tvc_vision_weights* vision, con
             delete nh;
             return fail(h, TVC_E_INVALID, "tvc_create: unsupported text geometry");
         }
-        nh->tw = *text;
-        nh->tlayers.assign(text->layers, text->layers + d.text.layers);
-        nh->tw.layers = nh->tlayers.data();
-        nh->has_text = true;
+        nh->text.assign(*text, d.text.layers);
     }
     *out = nh;
     return TVC_OK;
@@ -259,163 +399,44 @@ uint64_t tvc_workspace_bytes(tvc_handle* h) {
 int tvc_encode_image(tvc_handle* h, const float* pix_dev, int32_t B, float* out_dev, int32_t normalize,
                      void* stream) {
     if (!h) return TVC_E_INVALID;
-    if (!h->has_vision) return fail(h, TVC_E_STATE, "tvc_encode_image: handle has no vision tower");
+    if (!h->vision.set) return fail(h, TVC_E_STATE, "tvc_encode_image: handle has no vision tower");
     if (B < 0 || (B > 0 && (!pix_dev || !out_dev))) return fail(h, TVC_E_INVALID, "tvc_encode_image: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     const tvc_model_desc& m = h->desc;
-    const tvc_tower_arch& a = m.vision;
-    const int gside = m.image_size / m.patch, P = gside * gside, T = P + 1, d = a.width;
-    const int Kp = (3 * m.patch * m.patch + 63) / 64 * 64;
+    const int gside = m.image_size / m.patch, T = gside * gside + 1, d = m.vision.width;
     const int chunk = B < h->max_chunk_images ? B : h->max_chunk_images;
     if (B == 0) return TVC_OK;
-    if (h->tower_precision == 1) return tvc_precise_encode_image(h, pix_dev, B, out_dev, normalize, st);
-    if (h->tower_precision == 2) return tvc_split_encode_image(h, pix_dev, B, out_dev, normalize, st);
-    // precision 3: the same launches on the fp16 weight set, every 16-bit activation fp16
-    const bool f16 = h->tower_precision == 3;
-    if (f16 && !h->has_vision16) return fail(h, TVC_E_STATE, "tvc_encode_image: TVC_OPT_TOWER_PRECISION = 3 needs tvc_set_weights_f16 (vision)");
-    const tvc_vision_weights& vw = f16 ? h->vw16 : h->vw;
+    const int mode = h->tower_precision;
+    const bool pool = h->pooled_last && (mode == 0 || mode == 3);      // only the class token (row b*T) is pooled
+    float* X;
     int rc;
-    if ((rc = ensure_tower_ws(h, a, (int64_t)chunk * T, chunk, 0))) return rc;
-    if ((rc = ensure(h, WS_PATCH, ((size_t)chunk * P + 512) * Kp * 2))) return rc;      // + tile padding, as ensure_tower_ws
+    if ((rc = tower_begin(h, false, "tvc_encode_image", chunk, &X))) return rc;
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int n = (B - b0 < chunk) ? B - b0 : chunk;
         const float* pix = pix_dev + (size_t)b0 * 3 * m.image_size * m.image_size;
-        uint16_t* Pm = (uint16_t*)h->ws[WS_PATCH].p;
-        float* patch_out = (float*)h->ws[WS_MLP].p;    // [n*P, d] fp32 fits: mlp >= 2*d
-        if ((size_t)n * P * d * 4 > h->ws[WS_MLP].n) return fail(h, TVC_E_INVALID, "tvc_encode_image: mlp < 2*width unsupported");
-        HIP_TRY(launch_im2col(pix, Pm, n, m.image_size, m.patch, Kp, st, f16));
-        GemmLaunch g;
-        g.A = vw.patch_w; g.lda = Kp; g.I = d; g.B = Pm; g.ldb = Kp; g.J = n * P; g.K = Kp;
-        g.out = patch_out; g.ldo = d; g.epilogue = TVC_EPI_F32; g.b_rows_padded = true; g.f16 = f16;
-        HIP_TRY(timed_gemm(h, g, st, WS_SPLITK));
-        HIP_TRY(launch_assemble_lnpre(patch_out, vw.cls, vw.pos, vw.ln_pre_g, vw.ln_pre_b,
-                                      (float*)h->ws[WS_X].p, n, T, d, st));
-        const int pool = h->pooled_last ? 1 : 0;                  // only the class token (row b*T) is pooled
-        if ((rc = run_layers(h, a, vw.layers, n, T, 0, nullptr, 0, 0, st, nullptr, pool, nullptr, (int64_t)T * d, nullptr, f16))) return rc;
-        // ln_post on the class rows, projection, L2 norm
-        uint16_t* Hc = (uint16_t*)h->ws[WS_CLS].p;
-        // ln_post on the class rows (row b*T), folding in the last layer's two pending deltas
-        if (pool) {
-            const PoolBufs pb = pool_bufs(h, a, n, 0);
-            HIP_TRY(launch_layernorm((float*)h->ws[WS_X].p, (int64_t)T * d, nullptr, pb.D1c, 0, vw.ln_post_g,
-                                     vw.ln_post_b, Hc, n, d, st, pb.D2c, 1, nullptr, nullptr, f16));
-        } else {
-            HIP_TRY(launch_layernorm((float*)h->ws[WS_X].p, (int64_t)T * d, nullptr,
-                                     (const uint16_t*)h->ws[WS_DELTA].p, 0, vw.ln_post_g, vw.ln_post_b, Hc, n, d, st,
-                                     (const uint16_t*)h->ws[WS_DELTA2].p, 0, nullptr, nullptr, f16));
-        }
-        g = GemmLaunch();
-        g.A = vw.proj; g.lda = d; g.I = m.embed_dim; g.B = Hc; g.ldb = d; g.J = n; g.K = d;
-        g.out = out_dev + (size_t)b0 * m.embed_dim; g.ldo = m.embed_dim; g.epilogue = TVC_EPI_F32; g.f16 = f16;
-        HIP_TRY(timed_gemm(h, g, st, WS_SPLITK));
-        if (normalize) HIP_TRY(launch_l2norm_rows(out_dev + (size_t)b0 * m.embed_dim, n, m.embed_dim, st));
+        const float* patch_out;
+        rc = mode == 1 ? precise_stem(h, pix, n, &patch_out, st) : mode == 2 ? split_stem(h, pix, n, &patch_out, st)
+                       : patch_stem(h, "tvc_encode_image", pix, n, mode == 3, &patch_out, st);
+        if (rc) return rc;
+        auto assemble = [&](const auto& w) {
+            return launch_assemble_lnpre(patch_out, w.cls, w.pos, w.ln_pre_g, w.ln_pre_b, X, n, T, d, st);
+        };
+        HIP_TRY(mode == 1 || mode == 2 ? assemble(h->vision32.w) : assemble((mode == 3 ? h->vision16 : h->vision).w));
+        if ((rc = tower_layers(h, false, n, T, nullptr, 0, nullptr, pool, (int64_t)T * d, nullptr, st))) return rc;
+        float* out = out_dev + (size_t)b0 * m.embed_dim;
+        if ((rc = tower_head(h, false, (int64_t)T * d, nullptr, n, pool, out, false, st))) return rc;
+        if (normalize) HIP_TRY(launch_l2norm_rows(out, n, m.embed_dim, st));
     }
     return TVC_OK;
 }
 
 int tvc_encode_text(tvc_handle* h, const int32_t* tok_dev, int32_t Tn, float* out_dev, int32_t normalize,
                     void* stream) {
-    if (!h) return TVC_E_INVALID;
-    if (!h->has_text) return fail(h, TVC_E_STATE, "tvc_encode_text: handle has no text tower");
-    if (Tn < 0 || (Tn > 0 && (!tok_dev || !out_dev))) return fail(h, TVC_E_INVALID, "tvc_encode_text: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    const tvc_model_desc& m = h->desc;
-    const tvc_tower_arch& a = m.text;
-    const int d = a.width, ctx = m.ctx;
-    if (Tn == 0) return TVC_OK;
-    if (h->tower_precision == 1) return tvc_precise_encode_text(h, tok_dev, Tn, out_dev, normalize, nullptr, st);
-    if (h->tower_precision == 2) return tvc_split_encode_text(h, tok_dev, Tn, out_dev, normalize, nullptr, st);
-    const bool f16 = h->tower_precision == 3;
-    if (f16 && !h->has_text16) return fail(h, TVC_E_STATE, "tvc_encode_text: TVC_OPT_TOWER_PRECISION = 3 needs tvc_set_weights_f16 (text)");
-    const tvc_text_weights& tw = f16 ? h->tw16 : h->tw;
-    int chunk = Tn < h->max_chunk_texts ? Tn : h->max_chunk_texts;
-    // prefix sharing needs whole groups in a pass
-    const int G = (h->pack_text && h->text_group >= 2 && Tn % h->text_group == 0) ? h->text_group : 0;
-    if (G && chunk >= G) chunk = chunk / G * G;
-    const bool share = G && chunk % G == 0;
-    int rc;
-    if ((rc = ensure_tower_ws(h, a, (int64_t)chunk * ctx, chunk, WS_TOWER_N))) return rc;
-    if (share && (rc = ensure(h, WS_PFX, (size_t)chunk * 2 * 4))) return rc;
-    if ((rc = ensure(h, WS_EOT, (size_t)chunk * 4))) return rc;
-    if ((rc = ensure(h, WS_STARTS, (size_t)(chunk + 2) * 4))) return rc;
-    if ((rc = ensure(h, WS_LENS, (size_t)chunk * 4))) return rc;
-    for (int t0 = 0; t0 < Tn; t0 += chunk) {
-        const int n = (Tn - t0 < chunk) ? Tn - t0 : chunk;
-        int32_t* eot = (int32_t*)h->ws[WS_EOT].p;
-        const int32_t* tok = tok_dev + (size_t)t0 * ctx;
-        const int32_t* starts = nullptr;
-        const int32_t* pfx = nullptr;
-        int total_rows = n * ctx, max_len = ctx;
-        if (h->pack_text) {
-            // Keep only the tokens up to and including EOT: under the causal mask the later
-            // positions cannot reach the pooled (EOT) row, so the result is bit-identical.
-            // The row count sizes the GEMM grids, hence ONE 8-byte read-back per call.
-            int32_t* sd = (int32_t*)h->ws[WS_STARTS].p;
-            int32_t* pd = share ? (int32_t*)h->ws[WS_PFX].p : nullptr;
-            HIP_TRY(launch_text_lens_scan(tok, sd, pd, n, ctx, G, st, (int32_t*)h->ws[WS_LENS].p));
-            pfx = pd;
-            int32_t tail[2] = {0, 0};
-            HIP_TRY(hipMemcpyAsync(tail, sd + n, sizeof tail, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            total_rows = tail[0]; max_len = tail[1];
-            if (total_rows < (share ? n / G : n) || total_rows > n * ctx || max_len < 1 || max_len > ctx)
-                return fail(h, TVC_E_HIP, "tvc_encode_text: inconsistent sequence lengths");
-            starts = sd;
-        }
-        HIP_TRY(launch_text_embed(tok, tw.tok_emb, tw.pos, (float*)h->ws[WS_TX].p, eot, starts, n, ctx, d,
-                                  m.vocab, st, pfx));
-        const int pool = h->pooled_last ? 2 : 0;                  // only the EOT row of every text is pooled
-        if ((rc = run_layers(h, a, tw.layers, n, max_len, 1, starts, total_rows, WS_TOWER_N, st, pfx, pool, eot, d, nullptr, f16)))
-            return rc;
-        uint16_t* Hc = (uint16_t*)h->ws[WS_TCLS].p;
-        if (pool) {
-            const PoolBufs pb = pool_bufs(h, a, n, WS_TOWER_N);
-            HIP_TRY(launch_layernorm((float*)h->ws[WS_TX].p, d, eot, pb.D1c, 0, tw.ln_final_g, tw.ln_final_b, Hc,
-                                     n, d, st, pb.D2c, 1, nullptr, nullptr, f16));
-        } else {
-            HIP_TRY(launch_layernorm((float*)h->ws[WS_TX].p, d, eot, (const uint16_t*)h->ws[WS_TDELTA].p, 0,
-                                     tw.ln_final_g, tw.ln_final_b, Hc, n, d, st,
-                                     (const uint16_t*)h->ws[WS_TDELTA2].p, 0, nullptr, nullptr, f16));
-        }
-        GemmLaunch g;
-        g.A = tw.proj; g.lda = d; g.I = m.embed_dim; g.B = Hc; g.ldb = d; g.J = n; g.K = d;
-        g.out = out_dev + (size_t)t0 * m.embed_dim; g.ldo = m.embed_dim; g.epilogue = TVC_EPI_F32; g.f16 = f16;
-        HIP_TRY(timed_gemm(h, g, st, WS_TSPLITK));
-        if (normalize) HIP_TRY(launch_l2norm_rows(out_dev + (size_t)t0 * m.embed_dim, n, m.embed_dim, st));
-    }
-    return TVC_OK;
+    return encode_text(h, "tvc_encode_text", tok_dev, Tn, out_dev, normalize, false, stream);
 }
 
 int tvc_encode_text_hidden(tvc_handle* h, const int32_t* tok_dev, int32_t Tn, float* out_dev, void* stream) {
-    if (!h) return TVC_E_INVALID;
-    if (!h->has_text) return fail(h, TVC_E_STATE, "tvc_encode_text_hidden: handle has no text tower");
-    if (Tn < 0 || (Tn > 0 && (!tok_dev || !out_dev))) return fail(h, TVC_E_INVALID, "tvc_encode_text_hidden: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    const tvc_model_desc& m = h->desc;
-    const tvc_tower_arch& a = m.text;
-    const int d = a.width, ctx = m.ctx;
-    if (Tn == 0) return TVC_OK;
-    if (h->tower_precision == 1) return tvc_precise_encode_text(h, tok_dev, Tn, nullptr, 0, out_dev, st);
-    if (h->tower_precision == 2) return tvc_split_encode_text(h, tok_dev, Tn, nullptr, 0, out_dev, st);
-    const bool f16 = h->tower_precision == 3;
-    if (f16 && !h->has_text16) return fail(h, TVC_E_STATE, "tvc_encode_text_hidden: TVC_OPT_TOWER_PRECISION = 3 needs tvc_set_weights_f16 (text)");
-    const tvc_text_weights& tw = f16 ? h->tw16 : h->tw;
-    const int chunk = Tn < h->max_chunk_texts ? Tn : h->max_chunk_texts;
-    int rc;
-    if ((rc = ensure_tower_ws(h, a, (int64_t)chunk * ctx, chunk, WS_TOWER_N))) return rc;
-    if ((rc = ensure(h, WS_EOT, (size_t)chunk * 4))) return rc;
-    for (int t0 = 0; t0 < Tn; t0 += chunk) {
-        const int n = (Tn - t0 < chunk) ? Tn - t0 : chunk;
-        // every position is an output here (the conditioning sequence of a latent-diffusion UNet): dense rows, no
-        // EOT packing, no pooling; the causal mask is the tower's own
-        HIP_TRY(launch_text_embed(tok_dev + (size_t)t0 * ctx, tw.tok_emb, tw.pos, (float*)h->ws[WS_TX].p,
-                                  (int32_t*)h->ws[WS_EOT].p, nullptr, n, ctx, d, m.vocab, st, nullptr));
-        if ((rc = run_layers(h, a, tw.layers, n, ctx, 1, nullptr, 0, WS_TOWER_N, st, nullptr, 0, nullptr, 0, nullptr, f16))) return rc;
-        HIP_TRY(launch_layernorm((float*)h->ws[WS_TX].p, d, nullptr, (const uint16_t*)h->ws[WS_TDELTA].p, 0,
-                                 tw.ln_final_g, tw.ln_final_b, nullptr, n * ctx, d, st,
-                                 (const uint16_t*)h->ws[WS_TDELTA2].p, 0, nullptr, out_dev + (size_t)t0 * ctx * d, f16));
-    }
-    return TVC_OK;
+    return encode_text(h, "tvc_encode_text_hidden", tok_dev, Tn, out_dev, 0, true, stream);
 }
 
 int tvc_bank_set(tvc_handle* h, const void* bank_dev, int64_t R, int32_t D, int32_t dtype, void* stream) {
@@ -642,14 +663,14 @@ int build_transposed_weights(tvc_handle* h, hipStream_t st) {
     std::vector<void*> t((size_t)a.layers * 4 + 2, nullptr);
     int rc = TVC_OK;
     for (int l = 0; l < a.layers && !rc; ++l) {
-        const tvc_layer_weights& w = h->vw.layers[l];
+        const tvc_layer_weights& w = h->vision.w.layers[l];
         if ((rc = tr(w.wqkv, 3 * d, d, &t[l * 4 + 0]))) break;      // [3d, d] -> [d, 3d]
         if ((rc = tr(w.wo, d, d, &t[l * 4 + 1]))) break;
         if ((rc = tr(w.w1, a.mlp, d, &t[l * 4 + 2]))) break;        // [mlp, d] -> [d, mlp]
         if ((rc = tr(w.w2, d, a.mlp, &t[l * 4 + 3]))) break;        // [d, mlp] -> [mlp, d]
     }
-    if (!rc) rc = tr(h->vw.proj, m.embed_dim, d, &t[(size_t)a.layers * 4]);           // [D, d] -> [d, D]
-    if (!rc) rc = tr(h->vw.patch_w, d, Kp, &t[(size_t)a.layers * 4 + 1]);             // [d, Kp] -> [Kp, d]
+    if (!rc) rc = tr(h->vision.w.proj, m.embed_dim, d, &t[(size_t)a.layers * 4]);           // [D, d] -> [d, D]
+    if (!rc) rc = tr(h->vision.w.patch_w, d, Kp, &t[(size_t)a.layers * 4 + 1]);             // [d, Kp] -> [Kp, d]
     if (rc) { for (void* p : t) if (p) (void)hipFree(p); return rc; }
     h->wT = t;
     return TVC_OK;
@@ -658,7 +679,7 @@ int build_transposed_weights(tvc_handle* h, hipStream_t st) {
 
 int tvc_encode_image_grad(tvc_handle* h, const float* pix_dev, int32_t B, float* out_dev, int32_t normalize, void* stream) {
     if (!h) return TVC_E_INVALID;
-    if (!h->has_vision) return fail(h, TVC_E_STATE, "tvc_encode_image_grad: handle has no vision tower");
+    if (!h->vision.set) return fail(h, TVC_E_STATE, "tvc_encode_image_grad: handle has no vision tower");
     if (B < 1 || !pix_dev || !out_dev) return fail(h, TVC_E_INVALID, "tvc_encode_image_grad: bad arguments");
     if (B > h->max_chunk_images) return fail(h, TVC_E_INVALID, "tvc_encode_image_grad: B exceeds TVC_OPT_MAX_CHUNK_IMAGES (one pass only)");
     if (h->desc.vision.act != TVC_ACT_QUICK_GELU) return fail(h, TVC_E_INVALID, "tvc_encode_image_grad: only QuickGELU towers have a backward pass");
@@ -680,22 +701,17 @@ int tvc_encode_image_grad(tvc_handle* h, const float* pix_dev, int32_t B, float*
     gs.u = gs.d1 + (size_t)a.layers * rows * d;
     if ((rc = ensure(h, WS_GOUT, (size_t)B * m.embed_dim * 4))) return rc;
     if ((rc = ensure(h, WS_GXL, (size_t)B * d * 4))) return rc;
-    uint16_t* Pm = (uint16_t*)h->ws[WS_PATCH].p;
-    float* patch_out = (float*)h->ws[WS_MLP].p;
-    if ((size_t)B * P * d * 4 > h->ws[WS_MLP].n) return fail(h, TVC_E_INVALID, "tvc_encode_image_grad: mlp < 2*width unsupported");
-    HIP_TRY(launch_im2col(pix_dev, Pm, B, m.image_size, m.patch, Kp, st));
-    GemmLaunch g;
-    g.A = h->vw.patch_w; g.lda = Kp; g.I = d; g.B = Pm; g.ldb = Kp; g.J = B * P; g.K = Kp;
-    g.out = patch_out; g.ldo = d; g.epilogue = TVC_EPI_F32; g.b_rows_padded = true;
-    HIP_TRY(timed_gemm(h, g, st, WS_SPLITK));
-    HIP_TRY(launch_assemble_lnpre(patch_out, h->vw.cls, h->vw.pos, h->vw.ln_pre_g, h->vw.ln_pre_b, (float*)h->ws[WS_X].p, B, T, d, st));
-    if ((rc = run_layers(h, a, h->vw.layers, B, T, 0, nullptr, 0, 0, st, nullptr, 0, nullptr, 0, &gs))) return rc;
+    const float* patch_out;
+    if ((rc = patch_stem(h, "tvc_encode_image_grad", pix_dev, B, false, &patch_out, st))) return rc;
+    const tvc_vision_weights& vw = h->vision.w;
+    HIP_TRY(launch_assemble_lnpre(patch_out, vw.cls, vw.pos, vw.ln_pre_g, vw.ln_pre_b, (float*)h->ws[WS_X].p, B, T, d, st));
+    if ((rc = run_layers(h, a, vw.layers, B, T, 0, nullptr, 0, 0, st, nullptr, 0, nullptr, 0, &gs))) return rc;
     uint16_t* Hc = (uint16_t*)h->ws[WS_CLS].p;
     HIP_TRY(launch_layernorm((float*)h->ws[WS_X].p, (int64_t)T * d, nullptr, gs.d1 + (size_t)(a.layers - 1) * rows * d, 0,
-                             h->vw.ln_post_g, h->vw.ln_post_b, Hc, B, d, st, (const uint16_t*)h->ws[WS_DELTA2].p, 0,
+                             vw.ln_post_g, vw.ln_post_b, Hc, B, d, st, (const uint16_t*)h->ws[WS_DELTA2].p, 0,
                              (float*)h->ws[WS_GXL].p));
-    g = GemmLaunch();
-    g.A = h->vw.proj; g.lda = d; g.I = m.embed_dim; g.B = Hc; g.ldb = d; g.J = B; g.K = d;
+    GemmLaunch g;
+    g.A = vw.proj; g.lda = d; g.I = m.embed_dim; g.B = Hc; g.ldb = d; g.J = B; g.K = d;
     g.out = h->ws[WS_GOUT].p; g.ldo = m.embed_dim; g.epilogue = TVC_EPI_F32;
     HIP_TRY(timed_gemm(h, g, st, WS_SPLITK));
     HIP_TRY(hipMemcpyAsync(out_dev, h->ws[WS_GOUT].p, (size_t)B * m.embed_dim * 4, hipMemcpyDeviceToDevice, st));
@@ -706,7 +722,7 @@ int tvc_encode_image_grad(tvc_handle* h, const float* pix_dev, int32_t B, float*
 
 int tvc_encode_image_backward(tvc_handle* h, const float* grad_out_dev, float* grad_pix_dev, void* stream) {
     if (!h) return TVC_E_INVALID;
-    if (!h->has_vision || h->grad_B < 1) return fail(h, TVC_E_STATE, "tvc_encode_image_backward: call tvc_encode_image_grad first");
+    if (!h->vision.set || h->grad_B < 1) return fail(h, TVC_E_STATE, "tvc_encode_image_backward: call tvc_encode_image_grad first");
     if (!grad_out_dev || !grad_pix_dev) return fail(h, TVC_E_INVALID, "tvc_encode_image_backward: NULL buffer");
     hipStream_t st = (hipStream_t)stream;
     const tvc_model_desc& m = h->desc;
@@ -748,7 +764,7 @@ int tvc_encode_image_backward(tvc_handle* h, const float* grad_out_dev, float* g
     if ((rc = gemm(h->wT[(size_t)a.layers * 4], D, d, dP16, D, B, D, dHc, d, TVC_EPI_BF16))) return rc;
     HIP_TRY(hipMemsetAsync(dX, 0, (size_t)rows * d * 4, st));
     HIP_TRY(hipMemsetAsync(G16, 0, (size_t)rows * d * 2, st));
-    HIP_TRY(launch_layernorm_bwd((const float*)h->ws[WS_GXL].p, d, nullptr, dHc, 0, h->vw.ln_post_g, nullptr, dX, G16, B, d,
+    HIP_TRY(launch_layernorm_bwd((const float*)h->ws[WS_GXL].p, d, nullptr, dHc, 0, h->vision.w.ln_post_g, nullptr, dX, G16, B, d,
                                  (int64_t)T * d, st));
     // ---- layers, last to first, on what the forward kept (GradSave)
     const float* sx = (const float*)h->ws[WS_GSAVE].p;
@@ -756,7 +772,7 @@ int tvc_encode_image_backward(tvc_handle* h, const float* grad_out_dev, float* g
     const uint16_t* sd1 = sqkv + (size_t)a.layers * rows * 3 * d;
     const uint16_t* su = sd1 + (size_t)a.layers * rows * d;
     for (int l = a.layers - 1; l >= 0; --l) {
-        const tvc_layer_weights& w = h->vw.layers[l];
+        const tvc_layer_weights& w = h->vision.w.layers[l];
         void* const* wt = &h->wT[(size_t)l * 4];
         const float* X = sx + (size_t)l * rows * d;
         const uint16_t* QKV = sqkv + (size_t)l * rows * 3 * d;
@@ -777,9 +793,9 @@ int tvc_encode_image_backward(tvc_handle* h, const float* grad_out_dev, float* g
     uint16_t* Pm = (uint16_t*)h->ws[WS_PATCH].p;
     float* patch_out = (float*)h->ws[WS_GPATCH].p;                  // fp32 [B*P, d], then reused as dcols [B*P, Kp]
     HIP_TRY(launch_im2col(h->grad_pix, Pm, B, m.image_size, m.patch, Kp, st));
-    if ((rc = gemm(h->vw.patch_w, Kp, d, Pm, Kp, B * P, Kp, patch_out, d, TVC_EPI_F32))) return rc;
+    if ((rc = gemm(h->vision.w.patch_w, Kp, d, Pm, Kp, B * P, Kp, patch_out, d, TVC_EPI_F32))) return rc;
     uint16_t* dpatch = (uint16_t*)h->ws[WS_GDQKV].p;               // bf16 [B*P, d]
-    HIP_TRY(launch_lnpre_bwd(patch_out, h->vw.pos, h->vw.ln_pre_g, dX, dpatch, B, T, d, st));
+    HIP_TRY(launch_lnpre_bwd(patch_out, h->vision.w.pos, h->vision.w.ln_pre_g, dX, dpatch, B, T, d, st));
     if ((rc = gemm(h->wT[(size_t)a.layers * 4 + 1], d, Kp, dpatch, d, B * P, d, patch_out, Kp, TVC_EPI_F32))) return rc;
     HIP_TRY(launch_col2im(patch_out, grad_pix_dev, B, m.image_size, m.patch, Kp, st));
     return TVC_OK;
@@ -834,11 +850,11 @@ int tvc_set_option(tvc_handle* h, int32_t option, int64_t value) {
             if (value == 3) {
                 // (TVC_E_INVALID, not TVC_E_STATE: before fp16 weights exist the value is outside what the handle offers,
                 // as it was before the mode existed)
-                if (!h->has_vision16 && !h->has_text16)
+                if (!h->vision16.set && !h->text16.set)
                     return fail(h, TVC_E_INVALID, "tvc_set_option: TVC_OPT_TOWER_PRECISION = 3 needs tvc_set_weights_f16 first");
                 h->tower_precision = 3; return TVC_OK;
             }
-            if (value != 0 && !h->has_vision32 && !h->has_text32)
+            if (value != 0 && !h->vision32.set && !h->text32.set)
                 return fail(h, TVC_E_STATE, "tvc_set_option: TVC_OPT_TOWER_PRECISION = 1 / 2 needs tvc_set_weights_f32 first");
             if (value == 2) {
                 const int rc = tvc_split_prepare(h);        // builds the weight planes once (synchronises the device)
@@ -974,20 +990,14 @@ int tvc_layernorm_f16(tvc_handle* h, const float* x_dev, const float* g_dev, con
 int tvc_set_weights_f16(tvc_handle* h, const tvc_vision_weights* vision, const tvc_text_weights* text) {
     if (!h) return TVC_E_INVALID;
     if (vision) {
-        if (!h->has_vision) return fail(h, TVC_E_STATE, "tvc_set_weights_f16: handle was created without a vision tower");
+        if (!h->vision.set) return fail(h, TVC_E_STATE, "tvc_set_weights_f16: handle was created without a vision tower");
         if (!vision->layers || !vision->patch_w || !vision->proj) return fail(h, TVC_E_INVALID, "tvc_set_weights_f16: NULL vision weights");
-        h->vw16 = *vision;
-        h->vlayers16.assign(vision->layers, vision->layers + h->desc.vision.layers);
-        h->vw16.layers = h->vlayers16.data();
-        h->has_vision16 = true;
+        h->vision16.assign(*vision, h->desc.vision.layers);
     }
     if (text) {
-        if (!h->has_text) return fail(h, TVC_E_STATE, "tvc_set_weights_f16: handle was created without a text tower");
+        if (!h->text.set) return fail(h, TVC_E_STATE, "tvc_set_weights_f16: handle was created without a text tower");
         if (!text->layers || !text->tok_emb || !text->proj) return fail(h, TVC_E_INVALID, "tvc_set_weights_f16: NULL text weights");
-        h->tw16 = *text;
-        h->tlayers16.assign(text->layers, text->layers + h->desc.text.layers);
-        h->tw16.layers = h->tlayers16.data();
-        h->has_text16 = true;
+        h->text16.assign(*text, h->desc.text.layers);
     }
     return TVC_OK;
 }
