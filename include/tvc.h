@@ -420,8 +420,10 @@ int tvc_profile_end(tvc_handle* h, double* ms, double* work, int64_t* launches, 
 
 /* out[j, i] = sum_k a[i, k] * b[j, k]  (+ bias[i]); a bf16 [I, lda] ("weights"),
  * b bf16 [J, ldb] ("tokens"); K % 64 == 0; lda / ldb = row strides in elements (0 = K, i.e. dense rows;
- * otherwise >= K and a multiple of 8).  epilogue: 0 = fp32 store, 1 = bf16 store, 2 = bf16 quick-GELU,
- * 3 = fp32 residual add (out += ...). */
+ * otherwise >= K, a multiple of 8 and below 2^23); only the first K columns of a row are read.  out [J, ld_out],
+ * ld_out >= I (any value): only out[j, i] for j < J, i < I is written (read too by epilogue 3).  a_dev, b_dev, out_dev
+ * and a non-NULL bias_dev must be 16-byte aligned.  A call that breaks any of these returns TVC_E_INVALID and launches
+ * nothing.  epilogue: 0 = fp32 store, 1 = bf16 store, 2 = bf16 quick-GELU, 3 = fp32 residual add (out += ...). */
 int tvc_gemm_bf16(tvc_handle* h, const uint16_t* a_dev, const uint16_t* b_dev,
                   const float* bias_dev, void* out_dev, int32_t I, int32_t J, int32_t K,
                   int64_t lda, int64_t ldb, int32_t ld_out, int32_t epilogue, void* stream);
@@ -436,7 +438,8 @@ int tvc_layernorm(tvc_handle* h, const float* x_dev, const float* g_dev, const f
                   uint16_t* y_dev, int32_t rows, int32_t d, void* stream);
 
 /* fp16 twins of the three blocks above (TVC_OPT_TOWER_PRECISION = 3): every 16-bit operand and output is IEEE fp16
- * (tvc_gemm_f16: epilogues 1 / 2 store fp16, an output beyond 65504 becomes +-inf).  tvc_attention_f16 also takes
+ * (tvc_gemm_f16: the arguments and preconditions of tvc_gemm_bf16; epilogues 1 / 2 store fp16, an output beyond 65504
+ * becomes +-inf).  tvc_attention_f16 also takes
  * starts_dev: int32 [n_seq + 1] = packed sequences of at most seq_len rows, or NULL = n_seq x seq_len dense rows. */
 int tvc_gemm_f16(tvc_handle* h, const uint16_t* a_dev, const uint16_t* b_dev,
                  const float* bias_dev, void* out_dev, int32_t I, int32_t J, int32_t K,

@@ -555,6 +555,61 @@ template <bool F16> static hipError_t set_lds_attr_impl() {
     return st;
 }
 
+// The env switches of the dispatch, read once per process (the values host_plan.hpp's gemm_form receives).
+static const GemmFormEnv& gemm_form_env() {
+    static const GemmFormEnv env = [] {
+        GemmFormEnv v;
+        // variant: 0 = one tile per workgroup (gemm_core.hpp), 1 = persistent ring (gemm_ring.hpp / gemm_ring4.hpp)
+        if (const char* x = getenv("TVC_GEMM_VARIANT")) v.variant = atoi(x);
+        // (the ring's deep LDS-DMA pipeline also beats the one-tile kernel's wait-per-K-tile loop on launches of fewer
+        // tiles than CUs, one tile per workgroup: TVC_GEMM_RING_MIN_TILES, default 8 -- 64 until the latent-diffusion model's
+        // guidance halves went to two streams: a half's 16 x 16-level launches are 30-60 tiles, and 8 / 16 / 32 / 64 gave
+        // 17.2 / 17.1 / 17.15 / 16.85 images/s with the same bits, profiles/r04_sd_ring_min_tiles.log)
+        if (const char* x = getenv("TVC_GEMM_RING_MIN_TILES")) v.ring_min_tiles = atoi(x);
+        // TVC_GEMM_RING_FORM=1 forces ring form 1.  (Forms 2 and 3 and the four-wave gemm_solo kernel of rounds 1-2 measured
+        // no faster than forms 1 and 4 and were removed in round 3; DESIGN.md 4.1 keeps their numbers.)
+        if (const char* x = getenv("TVC_GEMM_RING_FORM")) v.ring_form = atoi(x);
+        // split-K tail: whole rounds to the ring kernel, the left-over tile columns split over K.
+        // Opt-in (TVC_GEMM_SPLITK_TAIL=1): it shortens the GEMM launches themselves by 1.4 % (89.7 vs 91.0 ms
+        // per step) but the step does not get faster when the two towers run on two streams - the other
+        // tower's kernels already fill the idle CUs of a last round - and it adds two launches per GEMM.
+        if (const char* x = getenv("TVC_GEMM_SPLITK_TAIL")) v.splitk_tail = atoi(x) != 0;
+        // Opt-in (TVC_GEMM_SPLITK_SMALL=1, a latency mode: one query 7.5 -> 5.3 ms): the fp32 sums are taken
+        // in a different order than in the one-pass kernels, so a query's embedding would depend (in the
+        // last bits) on the size of the batch it arrives in; by default it does not
+        // (tests/test_gpu_configs.py::test_config1_scale_properties, batch-split invariance).
+        if (const char* x = getenv("TVC_GEMM_SPLITK_SMALL")) v.splitk_small = atoi(x) != 0;
+        // fixed-split slices of equal depth on whole-row operands run in the ring kernel (virtual tiles)
+        if (const char* x = getenv("TVC_GEMM_RING_SPLIT")) v.ring_split = atoi(x) != 0;
+        return v;
+    }();
+    return env;
+}
+
+// split-K partial + finish kernels for the tiles from tile column jt0 on (S-way K split; ws holds their fp32 partial tiles)
+template <bool F16>
+static hipError_t launch_splitk_finish(const GemmLaunch& L, const GemmOperands& g, const GemmEpilogue& e, int tiles, int nIt,
+                                       int jt0, int S, hipStream_t stream) {
+    const dim3 block(GEMM_THREADS);
+    switch (L.epilogue) {
+        case TVC_EPI_F32:
+            hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_F32, F16>), dim3(tiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt0, S);
+            break;
+        case TVC_EPI_BF16:
+            hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_BF16, F16>), dim3(tiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt0, S);
+            break;
+        case TVC_EPI_GELU_BF16:
+            hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_GELU_BF16, F16>), dim3(tiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt0, S);
+            break;
+        case TVC_EPI_RESID_F32:
+            hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_RESID_F32, F16>), dim3(tiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt0, S);
+            break;
+        default:
+            return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 template <bool F16>
 static hipError_t launch_gemm_t(const GemmLaunch& L, hipStream_t stream) {
     hipError_t st = set_lds_attr_once<F16>();
@@ -568,116 +623,58 @@ static hipError_t launch_gemm_t(const GemmLaunch& L, hipStream_t stream) {
     GemmEpilogue e;
     e.bias = L.bias; e.out = L.out; e.ldo = L.ldo;
     const int nIt = (L.I + GEMM_BM - 1) / GEMM_BM, nJt = (L.J + GEMM_BN - 1) / GEMM_BN;
-    const dim3 block(GEMM_THREADS);
-    // variant: 0 = one tile per workgroup (gemm_core.hpp), 1 = persistent ring (gemm_ring.hpp / gemm_ring4.hpp).
-    // The ring needs enough tiles to keep 256 persistent workgroups busy.
-    static const int forced = [] { const char* v = getenv("TVC_GEMM_VARIANT"); return v ? atoi(v) : -1; }();
     const int ntiles = nIt * nJt;
-    const bool deep = (int64_t)L.K * L.planes >= 256;      // >= 8 ring stages per tile
-    // (the ring's deep LDS-DMA pipeline also beats the one-tile kernel's wait-per-K-tile loop on launches of fewer
-    // tiles than CUs, one tile per workgroup: TVC_GEMM_RING_MIN_TILES, default 8 -- 64 until the latent-diffusion model's
-    // guidance halves went to two streams: a half's 16 x 16-level launches are 30-60 tiles, and 8 / 16 / 32 / 64 gave
-    // 17.2 / 17.1 / 17.15 / 16.85 images/s with the same bits, profiles/r04_sd_ring_min_tiles.log)
-    static const int ring_min_env = [] { const char* v = getenv("TVC_GEMM_RING_MIN_TILES"); return v ? atoi(v) : 8; }();
-    // launches that may split K over idle CUs (`splitk_small`: the input-gradient path at small batches) keep the old bound:
-    // below 64 tiles they split
-    const int ring_min = (L.splitk_small && ring_min_env < 64) ? 64 : ring_min_env;
-    // Launches that opted into split-K (`splitk_small`: the latent-diffusion model, whose results carry no batch-position
-    // invariance to protect) and have 64..128 tiles of a DEEP K (a 3 x 3 convolution at 16 x 16 latents: 120 tiles x 180
-    // K-tiles) also take the split-K kernels below instead of one tile per workgroup on half the chip.
-    const int nk64_all = (int)((int64_t)L.K * L.planes / GEMM_BK);
-    const bool auto_split = L.splitk_fixed == 0;       // splitk_fixed: the caller fixed the K split (kernels.hpp)
-    if (L.splitk_fixed >= 2) {
-        int S = L.splitk_fixed;
-        if (S > nk64_all) S = nk64_all;
-        if (!L.splitk_ws || (size_t)ntiles * S * GEMM_BM * GEMM_BN * 4 > L.splitk_ws_bytes) return hipErrorInvalidValue;
-        // slices of equal depth on whole-row operands run in the ring kernel (virtual tiles); anything else in the one-tile loop
-        static const bool ring_split = [] { const char* v = getenv("TVC_GEMM_RING_SPLIT"); return !v || atoi(v) != 0; }();
-        const int vt = ntiles * S;
-        if (ring_split && nk64_all % S == 0 && nk64_all / S >= 4 && (L.I % GEMM_BM == 0 || L.a_rows_padded) &&
-            (L.J % GEMM_BN == 0 || L.b_rows_padded) && L.lda % 64 == 0 && L.ldb % 64 == 0) {
-            const dim3 rgrid(vt >= 256 ? 256 : (vt + 7) / 8 * 8);
-            hipLaunchKernelGGL(gemm_ring4_split_kernel<F16>, rgrid, block, R3_LDS_BYTES + 4096, stream, g, L.splitk_ws, nIt, nJt, S);
-        } else {
-            hipLaunchKernelGGL(gemm_splitk_partial_kernel<F16>, dim3(vt), block, GEMM_LDS_BYTES, stream, g, L.splitk_ws, nIt, 0, S);
+    const dim3 block(GEMM_THREADS);
+    // The form (host_plan.hpp, gemm_form): the ring kernels need >= 8 ring stages per tile (K * planes >= 256) and enough
+    // tiles to keep the persistent workgroups busy; launches of fewer tiles than CUs may split K over the idle CUs
+    // (`splitk_small`: the input-gradient path at small batches and the latent-diffusion model, whose results carry no
+    // batch-position invariance to protect -- 64..128 tiles of a DEEP K, a 3 x 3 convolution at 16 x 16 latents: 120 tiles
+    // x 180 K-tiles, take the split-K kernels too instead of one tile per workgroup on half the chip); `splitk_fixed`: the
+    // caller fixed the K split (kernels.hpp).
+    GemmFormArgs fa;
+    fa.I = L.I; fa.J = L.J; fa.K = L.K; fa.planes = L.planes; fa.lda = L.lda; fa.ldb = L.ldb; fa.epilogue = L.epilogue;
+    fa.splitk_small = L.splitk_small; fa.splitk_fixed = L.splitk_fixed; fa.has_ws = L.splitk_ws != nullptr;
+    fa.ws_bytes = L.splitk_ws_bytes; fa.a_rows_padded = L.a_rows_padded; fa.b_rows_padded = L.b_rows_padded;
+    const GemmPlan plan = gemm_form(fa, gemm_form_env());
+    const int S = plan.S;
+    switch (plan.form) {
+        case GEMM_FORM_SPLITK_FIXED: {
+            if (!L.splitk_ws || (size_t)ntiles * S * GEMM_BM * GEMM_BN * 4 > L.splitk_ws_bytes) return hipErrorInvalidValue;
+            const int vt = ntiles * S;
+            if (plan.ring_split) {
+                const dim3 rgrid(vt >= 256 ? 256 : (vt + 7) / 8 * 8);
+                hipLaunchKernelGGL(gemm_ring4_split_kernel<F16>, rgrid, block, R3_LDS_BYTES + 4096, stream, g, L.splitk_ws, nIt, nJt, S);
+            } else {
+                hipLaunchKernelGGL(gemm_splitk_partial_kernel<F16>, dim3(vt), block, GEMM_LDS_BYTES, stream, g, L.splitk_ws, nIt, 0, S);
+            }
+            return launch_splitk_finish<F16>(L, g, e, ntiles, nIt, 0, S, stream);
         }
-        switch (L.epilogue) {
-            case TVC_EPI_F32:
-                hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_F32, F16>), dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
-                break;
-            case TVC_EPI_BF16:
-                hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_BF16, F16>), dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
-                break;
-            case TVC_EPI_GELU_BF16:
-                hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_GELU_BF16, F16>), dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
-                break;
-            case TVC_EPI_RESID_F32:
-                hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_RESID_F32, F16>), dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
-                break;
-            default:
-                return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    const bool mid_split = auto_split && L.splitk_small && L.splitk_ws && forced < 0 && ntiles >= ring_min && ntiles <= 128 && nk64_all >= 32 &&
-                           (size_t)ntiles * (256 / ntiles) * GEMM_BM * GEMM_BN * 4 <= L.splitk_ws_bytes;
-    const bool ring = deep && !mid_split && (forced >= 0 ? (forced >= 1 && ntiles >= 8) : (ntiles >= ring_min));
-    if (ring) {
-        // ---- split-K tail: whole rounds to the ring kernel, the left-over tile columns split over K
-        // Opt-in (TVC_GEMM_SPLITK_TAIL=1): it shortens the GEMM launches themselves by 1.4 % (89.7 vs 91.0 ms
-        // per step) but the step does not get faster when the two towers run on two streams - the other
-        // tower's kernels already fill the idle CUs of a last round - and it adds two launches per GEMM.
-        static const bool tail_on = [] { const char* v = getenv("TVC_GEMM_SPLITK_TAIL"); return v && atoi(v) != 0; }();
-        // (`splitk_small` launches take it too, with whole tile COLUMNS for the ring kernel even when the tile rows do not
-        // divide 256: 96 token columns x 3 feature rows = 288 tiles -> 85 columns = 255 tiles in one round + 33 tiles split 7-way)
-        const int full_tiles = ntiles / 256 * 256;
-        const int jt_full = full_tiles / nIt;                 // tile columns the ring kernel keeps
-        const int left = ntiles - jt_full * nIt;              // tiles of the left-over columns
-        const int nk64 = (int)((int64_t)L.K * L.planes / GEMM_BK);
-        int S = left > 0 ? 256 / left : 0;
-        if (S > nk64 / 4) S = nk64 / 4;
-        if (S > 16) S = 16;
-        const bool whole_rounds = (jt_full * nIt) % 256 == 0;
-        const bool tail = auto_split && forced < 0 && L.splitk_ws && jt_full >= 1 && left >= 1 && S >= 2 &&
-                          ((tail_on && whole_rounds && left <= 64) || (L.splitk_small && left <= 128)) &&
-                          (size_t)left * S * GEMM_BM * GEMM_BN * 4 <= L.splitk_ws_bytes;
-        if (tail) {
+        case GEMM_FORM_SPLITK_TAIL: {
+            // (`splitk_small` launches take it too, with whole tile COLUMNS for the ring kernel even when the tile rows do not
+            // divide 256: 96 token columns x 3 feature rows = 288 tiles -> 85 columns = 255 tiles in one round + 33 tiles split 7-way)
             GemmLaunch M2 = L;
-            M2.J = jt_full * GEMM_BN;
+            M2.J = plan.jt_full * GEMM_BN;
             M2.splitk_ws = nullptr;
             hipError_t st2 = launch_gemm_bf16(M2, stream);
             if (st2 != hipSuccess) return st2;
-            hipLaunchKernelGGL(gemm_splitk_partial_kernel<F16>, dim3(left * S), block, GEMM_LDS_BYTES, stream, g,
-                               L.splitk_ws, nIt, jt_full, S);
-            switch (L.epilogue) {
-                case TVC_EPI_F32:
-                    hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_F32, F16>), dim3(left * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt_full, S);
-                    break;
-                case TVC_EPI_BF16:
-                    hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_BF16, F16>), dim3(left * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt_full, S);
-                    break;
-                case TVC_EPI_GELU_BF16:
-                    hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_GELU_BF16, F16>), dim3(left * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt_full, S);
-                    break;
-                case TVC_EPI_RESID_F32:
-                    hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_RESID_F32, F16>), dim3(left * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt_full, S);
-                    break;
-                default:
-                    return hipErrorInvalidValue;
-            }
-            return hipGetLastError();
+            hipLaunchKernelGGL(gemm_splitk_partial_kernel<F16>, dim3(plan.left * S), block, GEMM_LDS_BYTES, stream, g,
+                               L.splitk_ws, nIt, plan.jt_full, S);
+            return launch_splitk_finish<F16>(L, g, e, plan.left, nIt, plan.jt_full, S, stream);
         }
-        const dim3 rgrid(ntiles >= 256 ? 256 : (ntiles + 7) / 8 * 8);   // a workgroup without a tile returns at once
-        // ring form: 4 (barrier-staggered ping-pong in 16-MFMA phases over 64-deep whole-line K-tiles) where its
-        // preconditions hold, else 1 (32-deep stages, clamped rows: any shape); TVC_GEMM_RING_FORM=1 forces form 1.
-        // (Forms 2 and 3 and the four-wave gemm_solo kernel of rounds 1-2 measured no faster than these two and were
-        // removed in round 3; DESIGN.md 4.1 keeps their numbers.)
-        static const int ring_form = [] { const char* v = getenv("TVC_GEMM_RING_FORM"); return v ? atoi(v) : 4; }();
-        // form 4 reads whole rows without clamping: out-feature rows must fill whole tiles, B must have readable
-        // rows up to the next multiple of 256 (J % 256 == 0, or a padded workspace: GemmLaunch::b_rows_padded), and
-        // the row pitches must be multiples of 128 bytes (its source swizzle flips address bit 6)
-        if (ring_form == 4 && L.epilogue != TVC_EPI_RESID_F32 && (L.I % GEMM_BM == 0 || L.a_rows_padded) &&
-            (L.J % GEMM_BN == 0 || L.b_rows_padded) && L.lda % 64 == 0 && L.ldb % 64 == 0) {
+        case GEMM_FORM_SPLITK_SMALL:
+        case GEMM_FORM_MID_SPLIT:
+            // few tiles, deep K (small batches): one tile per workgroup would leave most of the 256 CUs idle and run K
+            // serially (FC2 at one image: 8 workgroups x 64 K-steps).  Split K over S workgroups per tile (fp32 partial
+            // tiles + the finish kernel of the split-K tail).
+            hipLaunchKernelGGL(gemm_splitk_partial_kernel<F16>, dim3(ntiles * S), block, GEMM_LDS_BYTES, stream, g,
+                               L.splitk_ws, nIt, 0, S);
+            return launch_splitk_finish<F16>(L, g, e, ntiles, nIt, 0, S, stream);
+        case GEMM_FORM_RING4: {
+            // barrier-staggered ping-pong in 16-MFMA phases over 64-deep whole-line K-tiles.  It reads whole rows without
+            // clamping: out-feature rows must fill whole tiles, B must have readable rows up to the next multiple of 256
+            // (J % 256 == 0, or a padded workspace: GemmLaunch::b_rows_padded), and the row pitches must be multiples of
+            // 128 bytes (its source swizzle flips address bit 6)
+            const dim3 rgrid(ntiles >= 256 ? 256 : (ntiles + 7) / 8 * 8);   // a workgroup without a tile returns at once
             switch (L.epilogue) {
                 case TVC_EPI_F32:
                     hipLaunchKernelGGL((gemm_ring4_kernel<TVC_EPI_F32, F16>), rgrid, block, R3_LDS_BYTES + 4096, stream, g, e, nIt, nJt);
@@ -693,59 +690,29 @@ static hipError_t launch_gemm_t(const GemmLaunch& L, hipStream_t stream) {
             }
             return hipGetLastError();
         }
-        switch (L.epilogue) {
-            case TVC_EPI_F32:
-                hipLaunchKernelGGL((gemm_ring_kernel<TVC_EPI_F32, F16>), rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
-                break;
-            case TVC_EPI_BF16:
-                hipLaunchKernelGGL((gemm_ring_kernel<TVC_EPI_BF16, F16>), rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
-                break;
-            case TVC_EPI_GELU_BF16:
-                hipLaunchKernelGGL((gemm_ring_kernel<TVC_EPI_GELU_BF16, F16>), rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
-                break;
-            case TVC_EPI_RESID_F32:
-                hipLaunchKernelGGL((gemm_ring_kernel<TVC_EPI_RESID_F32, F16>), rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
-                break;
-            default:
-                return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    // ---- few tiles, deep K (small batches): one tile per workgroup would leave most of the 256 CUs idle
-    // and run K serially (FC2 at one image: 8 workgroups x 64 K-steps).  Split K over S workgroups per
-    // tile (fp32 partial tiles + the finish kernel of the split-K tail above).
-    {
-        // Opt-in (TVC_GEMM_SPLITK_SMALL=1, a latency mode: one query 7.5 -> 5.3 ms): the fp32 sums are taken
-        // in a different order than in the one-pass kernels, so a query's embedding would depend (in the
-        // last bits) on the size of the batch it arrives in; by default it does not
-        // (tests/test_gpu_configs.py::test_config1_scale_properties, batch-split invariance).
-        static const bool small_on = [] { const char* v = getenv("TVC_GEMM_SPLITK_SMALL"); return v && atoi(v) != 0; }();
-        const int nk64 = (int)((int64_t)L.K * L.planes / GEMM_BK);
-        int S = ntiles > 0 ? 256 / ntiles : 0;
-        if (S > nk64 / 2) S = nk64 / 2;
-        if (S > 16) S = 16;
-        if (auto_split && (small_on || L.splitk_small) && forced < 0 && L.splitk_ws && S >= 2 &&
-            (size_t)ntiles * S * GEMM_BM * GEMM_BN * 4 <= L.splitk_ws_bytes) {
-            hipLaunchKernelGGL(gemm_splitk_partial_kernel<F16>, dim3(ntiles * S), block, GEMM_LDS_BYTES, stream, g,
-                               L.splitk_ws, nIt, 0, S);
+        case GEMM_FORM_RING1: {
+            // 32-deep stages, clamped rows: any shape
+            const dim3 rgrid(ntiles >= 256 ? 256 : (ntiles + 7) / 8 * 8);
             switch (L.epilogue) {
                 case TVC_EPI_F32:
-                    hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_F32, F16>), dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
+                    hipLaunchKernelGGL((gemm_ring_kernel<TVC_EPI_F32, F16>), rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
                     break;
                 case TVC_EPI_BF16:
-                    hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_BF16, F16>), dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
+                    hipLaunchKernelGGL((gemm_ring_kernel<TVC_EPI_BF16, F16>), rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
                     break;
                 case TVC_EPI_GELU_BF16:
-                    hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_GELU_BF16, F16>), dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
+                    hipLaunchKernelGGL((gemm_ring_kernel<TVC_EPI_GELU_BF16, F16>), rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
                     break;
                 case TVC_EPI_RESID_F32:
-                    hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_RESID_F32, F16>), dim3(ntiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, 0, S);
+                    hipLaunchKernelGGL((gemm_ring_kernel<TVC_EPI_RESID_F32, F16>), rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
                     break;
                 default:
                     return hipErrorInvalidValue;
             }
             return hipGetLastError();
         }
+        case GEMM_FORM_ONE_TILE:
+            break;
     }
     const dim3 grid(nIt * nJt);
     switch (L.epilogue) {

@@ -63,3 +63,96 @@ inline size_t sd_groupnorm_ws_floats(int n, int HW, int groups) {
     const int nslab = (HW + slab - 1) / slab;
     return (size_t)n * nslab * groups * 2 + (size_t)n * groups * 2;
 }
+
+// ---- the form of a 16-bit GEMM launch (tvc_gemm_bf16 / tvc_gemm_f16 and every internal caller of launch_gemm_bf16):
+// launch_gemm_bf16 (gemm.hip) dispatches on exactly this plan, so a test can name the kernel a shape reaches without a GPU
+enum GemmForm {
+    GEMM_FORM_ONE_TILE = 0,     // gemm_bf16_kernel: one 256 x 256 tile per workgroup
+    GEMM_FORM_RING1,            // gemm_ring_kernel: persistent ring, clamped rows (any shape)
+    GEMM_FORM_RING4,            // gemm_ring4_kernel: persistent ring over whole-line K-tiles (whole row tiles, 128-byte pitches)
+    GEMM_FORM_SPLITK_SMALL,     // few tiles, deep K: K split over the idle CUs (partial + finish kernels)
+    GEMM_FORM_SPLITK_TAIL,      // ring launch of whole rounds + split-K partial / finish kernels for the left-over tile columns
+    GEMM_FORM_SPLITK_FIXED,     // the caller fixed the K split (GemmLaunch::splitk_fixed >= 2)
+    GEMM_FORM_MID_SPLIT,        // `splitk_small` launches of 64..128 tiles of a deep K: the split-K kernels of SPLITK_SMALL
+};
+
+// the env switches gemm.hip reads once per process, as values (the defaults = unset)
+struct GemmFormEnv {
+    int variant = -1;           // TVC_GEMM_VARIANT: 0 = one tile per workgroup everywhere, >= 1 = the ring from 8 tiles on
+    int ring_min_tiles = 8;     // TVC_GEMM_RING_MIN_TILES
+    int ring_form = 4;          // TVC_GEMM_RING_FORM: 1 forces ring form 1
+    bool splitk_tail = false;   // TVC_GEMM_SPLITK_TAIL
+    bool splitk_small = false;  // TVC_GEMM_SPLITK_SMALL
+    bool ring_split = true;     // TVC_GEMM_RING_SPLIT
+};
+
+// the sizes and flags of a launch that the dispatch reads (a GemmLaunch without its pointers)
+struct GemmFormArgs {
+    int I = 0, J = 0, K = 0, planes = 1;
+    int64_t lda = 0, ldb = 0;
+    int epilogue = 0;           // TVC_EPI_*: 3 = the fp32 residual add, which ring form 4 does not carry
+    bool splitk_small = false;
+    int splitk_fixed = 0;
+    bool has_ws = false;        // a split-K workspace was passed
+    size_t ws_bytes = 0;
+    bool a_rows_padded = false, b_rows_padded = false;
+};
+
+struct GemmPlan {
+    GemmForm form = GEMM_FORM_ONE_TILE;
+    int S = 0;                  // the K split of the split forms
+    int jt_full = 0;            // SPLITK_TAIL: tile columns of the ring launch; the rest are split over K
+    int left = 0;               // SPLITK_TAIL: tiles of the left-over columns
+    bool ring_split = false;    // SPLITK_FIXED: the slices run in the ring kernel (else the one-tile partial loop)
+};
+
+inline GemmPlan gemm_form(const GemmFormArgs& a, const GemmFormEnv& env) {
+    const int BM = HOST_PLAN_GEMM_BM, BN = HOST_PLAN_GEMM_BN;
+    const size_t tile_bytes = (size_t)BM * BN * 4;      // one fp32 partial tile of the split-K workspace
+    const int nIt = (a.I + BM - 1) / BM, nJt = (a.J + BN - 1) / BN;
+    const int ntiles = nIt * nJt;
+    const bool deep = (int64_t)a.K * a.planes >= 256;   // >= 8 ring stages per tile
+    const int ring_min = (a.splitk_small && env.ring_min_tiles < 64) ? 64 : env.ring_min_tiles;
+    const int nk64 = (int)((int64_t)a.K * a.planes / 64);
+    const bool auto_split = a.splitk_fixed == 0;
+    const int forced = env.variant;
+    GemmPlan p;
+    if (a.splitk_fixed >= 2) {
+        p.form = GEMM_FORM_SPLITK_FIXED;
+        p.S = a.splitk_fixed > nk64 ? nk64 : a.splitk_fixed;
+        p.ring_split = env.ring_split && nk64 % p.S == 0 && nk64 / p.S >= 4 && (a.I % BM == 0 || a.a_rows_padded) &&
+                       (a.J % BN == 0 || a.b_rows_padded) && a.lda % 64 == 0 && a.ldb % 64 == 0;
+        return p;
+    }
+    const bool mid_split = auto_split && a.splitk_small && a.has_ws && forced < 0 && ntiles >= ring_min && ntiles <= 128 &&
+                           nk64 >= 32 && (size_t)ntiles * (256 / ntiles) * tile_bytes <= a.ws_bytes;
+    const bool ring = deep && !mid_split && (forced >= 0 ? (forced >= 1 && ntiles >= 8) : (ntiles >= ring_min));
+    if (ring) {
+        const int full_tiles = ntiles / 256 * 256;
+        const int jt_full = full_tiles / nIt;
+        const int left = ntiles - jt_full * nIt;
+        int S = left > 0 ? 256 / left : 0;
+        if (S > nk64 / 4) S = nk64 / 4;
+        if (S > 16) S = 16;
+        const bool whole_rounds = (jt_full * nIt) % 256 == 0;
+        if (auto_split && forced < 0 && a.has_ws && jt_full >= 1 && left >= 1 && S >= 2 &&
+            ((env.splitk_tail && whole_rounds && left <= 64) || (a.splitk_small && left <= 128)) &&
+            (size_t)left * S * tile_bytes <= a.ws_bytes) {
+            p.form = GEMM_FORM_SPLITK_TAIL; p.S = S; p.jt_full = jt_full; p.left = left;
+            return p;
+        }
+        const bool form4 = env.ring_form == 4 && a.epilogue != 3 && (a.I % BM == 0 || a.a_rows_padded) &&
+                           (a.J % BN == 0 || a.b_rows_padded) && a.lda % 64 == 0 && a.ldb % 64 == 0;
+        p.form = form4 ? GEMM_FORM_RING4 : GEMM_FORM_RING1;
+        return p;
+    }
+    int S = ntiles > 0 ? 256 / ntiles : 0;
+    if (S > nk64 / 2) S = nk64 / 2;
+    if (S > 16) S = 16;
+    if (auto_split && (env.splitk_small || a.splitk_small) && forced < 0 && a.has_ws && S >= 2 &&
+        (size_t)ntiles * S * tile_bytes <= a.ws_bytes) {
+        p.form = mid_split ? GEMM_FORM_MID_SPLIT : GEMM_FORM_SPLITK_SMALL;
+        p.S = S;
+    }
+    return p;
+}

@@ -925,6 +925,13 @@ int gemm16(tvc_handle* h, const char* name, bool f16, const uint16_t* a_dev, con
     if (I <= 0 || J <= 0 || K <= 0 || K % 64 != 0 || !a_dev || !b_dev || !out_dev || ld_out < I ||
         epilogue < 0 || epilogue > 3 || lda < K || ldb < K || lda % 8 != 0 || ldb % 8 != 0)
         return fail(h, TVC_E_INVALID, std::string(name) + ": need K % 64 == 0, ld_out >= I, lda / ldb >= K and multiples of 8");
+    // the kernels load and store 16 bytes per lane from the buffers' bases, and the ring forms compute a lane's row offset
+    // (row * pitch, in elements) in 32 bits
+    auto misaligned = [](const void* p) { return ((uintptr_t)p & 15) != 0; };
+    if (misaligned(a_dev) || misaligned(b_dev) || misaligned(out_dev) || (bias_dev && misaligned(bias_dev)))
+        return fail(h, TVC_E_INVALID, std::string(name) + ": a, b, out and bias must be 16-byte aligned");
+    if (lda >= ((int64_t)1 << 23) || ldb >= ((int64_t)1 << 23))
+        return fail(h, TVC_E_INVALID, std::string(name) + ": lda / ldb must be below 2^23");
     GemmLaunch g;
     g.A = a_dev; g.lda = lda; g.I = I; g.B = b_dev; g.ldb = ldb; g.J = J; g.K = K;
     g.bias = bias_dev; g.out = out_dev; g.ldo = ld_out; g.epilogue = epilogue; g.f16 = f16;

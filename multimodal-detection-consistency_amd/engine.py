@@ -57,6 +57,19 @@ def _require_cuda(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
     return t.contiguous()
 
 
+def _check_out(out: torch.Tensor, J: int, I: int, dtype, name: str = "out") -> int:
+    """The row pitch of a GEMM output: ``out`` must be a [J, >= I] matrix of unit column stride and of the epilogue's
+    dtype on the GPU (a column view of a wider buffer is fine: its row stride becomes ``ld_out``)."""
+    if not out.is_cuda:
+        raise ValueError(f"{name} must live on the GPU (got {out.device})")
+    if out.dtype != dtype:
+        raise ValueError(f"{name} must be {dtype} for this epilogue (got {out.dtype})")
+    if out.dim() != 2 or out.shape[0] != J or out.shape[1] < I or out.stride(1) != 1 or (J > 1 and out.stride(0) < I):
+        raise ValueError(f"{name} must be [{J}, >= {I}] with unit column stride (got shape {tuple(out.shape)}, "
+                         f"strides {tuple(out.stride())})")
+    return out.stride(0)
+
+
 class TVCEngine:
     """Owns a ``tvc_handle`` and the device copies of the tower weights."""
 
@@ -518,15 +531,17 @@ class TVCEngine:
         K = k if k is not None else lda
         if k is None and lda != ldb:
             raise ValueError("a and b must have the same number of columns (or pass k)")
+        odt = torch.float32 if epilogue in (0, 3) else torch.bfloat16
         if out is None:
-            out = torch.empty((J, I), dtype=torch.float32 if epilogue in (0, 3) else torch.bfloat16, device=self.device)
+            out = torch.empty((J, I), dtype=odt, device=self.device)
             if epilogue == 3:
                 out.zero_()
+        ld_out = _check_out(out, J, I, odt)
         if bias is not None:
             bias = _require_cuda(bias, torch.float32, "bias")
         with self._lock, torch.cuda.device(self.device):
             self._check(self.lib.tvc_gemm_bf16(self.handle, _ptr(a), _ptr(b), _ptr(bias), _ptr(out), I, J, K, lda, ldb,
-                                               out.shape[1], epilogue, _stream()))
+                                               ld_out, epilogue, _stream()))
         return out
 
     def attention(self, qkv: torch.Tensor, n_seq: int, seq_len: int, heads: int, causal: bool) -> torch.Tensor:
@@ -538,23 +553,26 @@ class TVCEngine:
         return out
 
     def gemm_f16(self, a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: int = 0,
-                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 out: Optional[torch.Tensor] = None, k: Optional[int] = None) -> torch.Tensor:
         """fp16 twin of :meth:`gemm` (tower mode 3): a, b fp16 on the f16 MFMA; epilogues 1 / 2 store fp16."""
         a = _require_cuda(a, torch.float16, "a")
         b = _require_cuda(b, torch.float16, "b")
-        I, K = a.shape
-        J = b.shape[0]
-        if b.shape[1] != K:
-            raise ValueError("a and b must have the same number of columns")
+        I, lda = a.shape
+        J, ldb = b.shape
+        K = k if k is not None else lda
+        if k is None and lda != ldb:
+            raise ValueError("a and b must have the same number of columns (or pass k)")
+        odt = torch.float32 if epilogue in (0, 3) else torch.float16
         if out is None:
-            out = torch.empty((J, I), dtype=torch.float32 if epilogue in (0, 3) else torch.float16, device=self.device)
+            out = torch.empty((J, I), dtype=odt, device=self.device)
             if epilogue == 3:
                 out.zero_()
+        ld_out = _check_out(out, J, I, odt)
         if bias is not None:
             bias = _require_cuda(bias, torch.float32, "bias")
         with self._lock, torch.cuda.device(self.device):
-            self._check(self.lib.tvc_gemm_f16(self.handle, _ptr(a), _ptr(b), _ptr(bias), _ptr(out), I, J, K, K, K,
-                                              out.shape[1], epilogue, _stream()))
+            self._check(self.lib.tvc_gemm_f16(self.handle, _ptr(a), _ptr(b), _ptr(bias), _ptr(out), I, J, K, lda, ldb,
+                                              ld_out, epilogue, _stream()))
         return out
 
     def attention_f16(self, qkv: torch.Tensor, n_seq: int, seq_len: int, heads: int, causal: bool,
@@ -615,11 +633,12 @@ class TVCEngine:
             raise ValueError("w [I, K] and x [J, K] expected")
         if out is None:
             out = torch.zeros((x.shape[0], w.shape[0]), dtype=torch.float32, device=self.device)
+        ld_out = _check_out(out, x.shape[0], w.shape[0], torch.float32)
         if bias is not None:
             bias = _require_cuda(bias, torch.float32, "bias")
         with self._lock, torch.cuda.device(self.device):
             self._check(self.lib.tvc_gemm_f32(self.handle, _ptr(w), _ptr(x), _ptr(bias), _ptr(out), w.shape[0], x.shape[0],
-                                              w.shape[1], out.shape[1], epilogue, _stream()))
+                                              w.shape[1], ld_out, epilogue, _stream()))
         return out
 
     def attention_f32(self, qkv: torch.Tensor, n_seq: int, seq_len: int, heads: int, causal: bool) -> torch.Tensor:

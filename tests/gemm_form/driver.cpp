@@ -1,0 +1,37 @@
+// Host-only driver of the 16-bit GEMM dispatch (tests/test_gemm_form.py): reads one launch per line on stdin --
+//   I J K planes lda ldb epilogue splitk_small splitk_fixed has_ws ws_bytes a_rows_padded b_rows_padded
+//   TVC_GEMM_VARIANT TVC_GEMM_RING_MIN_TILES TVC_GEMM_RING_FORM TVC_GEMM_SPLITK_TAIL TVC_GEMM_SPLITK_SMALL TVC_GEMM_RING_SPLIT
+// -- and prints the form csrc/host_plan.hpp's gemm_form gives it (the one launch_gemm_bf16 takes) and its K split.
+#include "host_plan.hpp"
+
+#include <cstdio>
+
+static const char* form_name(GemmForm f) {
+    switch (f) {
+        case GEMM_FORM_ONE_TILE: return "ONE_TILE";
+        case GEMM_FORM_RING1: return "RING1";
+        case GEMM_FORM_RING4: return "RING4";
+        case GEMM_FORM_SPLITK_SMALL: return "SPLITK_SMALL";
+        case GEMM_FORM_SPLITK_TAIL: return "SPLITK_TAIL";
+        case GEMM_FORM_SPLITK_FIXED: return "SPLITK_FIXED";
+        case GEMM_FORM_MID_SPLIT: return "MID_SPLIT";
+    }
+    return "?";
+}
+
+int main() {
+    long long v[19];
+    for (;;) {
+        for (int i = 0; i < 19; ++i)
+            if (scanf("%lld", &v[i]) != 1) return i == 0 ? 0 : 1;
+        GemmFormArgs a;
+        a.I = (int)v[0]; a.J = (int)v[1]; a.K = (int)v[2]; a.planes = (int)v[3]; a.lda = v[4]; a.ldb = v[5];
+        a.epilogue = (int)v[6]; a.splitk_small = v[7] != 0; a.splitk_fixed = (int)v[8]; a.has_ws = v[9] != 0;
+        a.ws_bytes = (size_t)v[10]; a.a_rows_padded = v[11] != 0; a.b_rows_padded = v[12] != 0;
+        GemmFormEnv e;
+        e.variant = (int)v[13]; e.ring_min_tiles = (int)v[14]; e.ring_form = (int)v[15]; e.splitk_tail = v[16] != 0;
+        e.splitk_small = v[17] != 0; e.ring_split = v[18] != 0;
+        const GemmPlan p = gemm_form(a, e);
+        printf("%s %d\n", form_name(p.form), p.S);
+    }
+}

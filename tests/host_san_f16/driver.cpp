@@ -108,6 +108,35 @@ int main() {
     OK(tvc_gemm_f16(h, a16, b16, nullptr, o32, 256, 300, 128, 0, 0, 256, 0, nullptr));
     OK(tvc_gemm_f16(h, a16, b16, nullptr, o32, 256, 300, 128, 0, 0, 256, 1, nullptr));
     CHECK(tvc_gemm_f16(h, a16, b16, nullptr, o32, 256, 300, 100, 0, 0, 256, 0, nullptr) == TVC_E_INVALID);
+    // ---- the 16-bit GEMM contract (include/tvc.h): padded operand rows, output pitches beyond I, a ragged I, every epilogue;
+    // the stub checks each launch's A, B, bias and output ranges against these exactly sized blocks.  Misaligned pointers
+    // and pitches of 2^23 or more are refused before any launch.
+    {
+        const int gI = 301, gJ = 300, gK = 128, ldo = gI + 4;
+        const int64_t lda = gK + 8, ldb = gK + 64;
+        std::vector<void*> blocks;
+        auto exact = [&](size_t bytes) { void* p = dev(bytes); blocks.push_back(p); return p; };
+        uint16_t* ga = (uint16_t*)exact(((size_t)(gI - 1) * lda + gK) * 2);
+        uint16_t* gb = (uint16_t*)exact(((size_t)(gJ - 1) * ldb + gK) * 2);
+        float* gbias = (float*)exact((size_t)gI * 4);
+        char* go = (char*)exact(((size_t)(gJ - 1) * ldo + gI) * 4);
+        for (int epi = 0; epi < 4; ++epi) {
+            OK(tvc_gemm_f16(h, ga, gb, gbias, go, gI, gJ, gK, lda, ldb, ldo, epi, nullptr));
+            OK(tvc_gemm_f16(h, ga, gb, nullptr, go, gI, gJ, gK, lda, ldb, gI + 1, epi, nullptr));
+        }
+        OK(tvc_gemm_f16(h, ga, gb, gbias, go, gI, gJ, gK, gK, ldb, gI, 1, nullptr));
+        OK(tvc_gemm_f16(h, ga, gb, gbias, go, 1, gJ, gK, ((int64_t)1 << 23) - 8, ldb, ldo, 0, nullptr));   // one row: any pitch below 2^23
+        const int64_t big = (int64_t)1 << 23;
+        CHECK(tvc_gemm_f16(h, ga, gb, gbias, go, 1, gJ, gK, big, ldb, ldo, 0, nullptr) == TVC_E_INVALID && strlen(tvc_last_error(h)) > 0);
+        CHECK(tvc_gemm_f16(h, ga, gb, gbias, go, gI, 1, gK, lda, big + 64, ldo, 0, nullptr) == TVC_E_INVALID);
+        CHECK(tvc_gemm_f16(h, ga + 1, gb, gbias, go, gI, gJ, gK, lda, ldb, ldo, 0, nullptr) == TVC_E_INVALID);
+        CHECK(tvc_gemm_f16(h, ga, gb + 4, gbias, go, gI, gJ, gK, lda, ldb, ldo, 0, nullptr) == TVC_E_INVALID);
+        CHECK(tvc_gemm_f16(h, ga, gb, gbias + 1, go, gI, gJ, gK, lda, ldb, ldo, 0, nullptr) == TVC_E_INVALID);
+        CHECK(tvc_gemm_f16(h, ga, gb, gbias, go + 8, gI, gJ, gK, lda, ldb, ldo, 1, nullptr) == TVC_E_INVALID);
+        CHECK(tvc_gemm_f16(h, ga, gb, gbias, go, gI, gJ, gK, gK + 4, ldb, ldo, 0, nullptr) == TVC_E_INVALID);   // not a multiple of 8
+        CHECK(tvc_gemm_f16(h, ga, gb, gbias, go, gI, gJ, gK, lda, ldb, gI - 1, 0, nullptr) == TVC_E_INVALID);   // ld_out < I
+        for (void* p : blocks) (void)hipFree(p);
+    }
     uint16_t* qkv = (uint16_t*)buf((size_t)2 * 77 * 3 * 128, 2); uint16_t* ao = (uint16_t*)buf((size_t)2 * 77 * 128, 2);
     OK(tvc_attention_f16(h, qkv, ao, nullptr, 2, 77, 2, 1, nullptr));
     CHECK(tvc_attention_f16(h, nullptr, ao, nullptr, 2, 77, 2, 1, nullptr) == TVC_E_INVALID);

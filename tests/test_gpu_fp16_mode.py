@@ -114,12 +114,25 @@ def _child(code, env):
     return [ln for ln in r.stdout.splitlines() if ln.startswith("checksum")]
 
 
+# The shapes of _FORMS and the form each reaches per child (csrc/host_plan.hpp gemm_form; tests/test_gemm_form.py asserts
+# these labels).  Ring forms 4 and 1 meet on four shapes; (3072, 300) has ragged token rows and runs ring form 1 in both
+# processes, (1024, 131072, 64) and (768, 7) the one-tile kernel in both: for those three the bit comparison shows
+# determinism only.  Split-K runs on (768, 7) under TVC_GEMM_SPLITK_SMALL=1, the split-K tail on (4096, 33024) under
+# TVC_GEMM_SPLITK_TAIL=1.
+_FORM_SHAPES = ((1024, 131072, 1024, 1), (4096, 33024, 1024, 2), (1024, 131072, 64, 1), (512, 65536, 640, 0),
+                (768, 7, 768, 1), (3072, 300, 1024, 2), (1024, 2304, 4096, 1))
+_FORM_LABELS = {
+    "": ("RING4", "RING4", "ONE_TILE", "RING4", "ONE_TILE", "RING1", "RING4"),
+    "TVC_GEMM_RING_FORM=1": ("RING1", "RING1", "ONE_TILE", "RING1", "ONE_TILE", "RING1", "RING1"),
+    "TVC_GEMM_SPLITK_SMALL=1": ("RING4", "RING4", "ONE_TILE", "RING4", "SPLITK_SMALL", "RING1", "RING4"),
+    "TVC_GEMM_SPLITK_TAIL=1": ("RING4", "SPLITK_TAIL", "ONE_TILE", "RING4", "ONE_TILE", "RING1", "RING4"),
+    "TVC_GEMM_VARIANT=0": ("ONE_TILE",) * 7,
+}
 _FORMS = r'''
 import torch, tvc_amd as pkg
 eng = pkg.TVCEngine()
 g = torch.Generator(device="cuda:0").manual_seed(11)
-for I, J, K, epi in ((1024, 131072, 1024, 1), (4096, 33024, 1024, 2), (1024, 131072, 64, 1), (512, 65536, 640, 0),
-                     (768, 7, 768, 1), (3072, 300, 1024, 2), (1024, 2304, 4096, 1)):
+for I, J, K, epi in ''' + repr(_FORM_SHAPES) + r''':
     a = (torch.randn(I, K, device="cuda:0", generator=g) * K ** -0.5).half()
     b = torch.randn(J, K, device="cuda:0", generator=g).half()
     bias = torch.randn(I, device="cuda:0", generator=g) * 3.0
@@ -137,9 +150,10 @@ print("CHILD_OK")
 
 
 def test_gemm_f16_forms_bit_identical_and_variants_correct():
-    """Ring forms 1 and 4 (TVC_GEMM_RING_FORM, read once per process) return the same fp16 BITS, as in bf16; the split-K
-    forms (TVC_GEMM_SPLITK_SMALL / TVC_GEMM_SPLITK_TAIL) and the one-tile kernel everywhere (TVC_GEMM_VARIANT=0) are correct
-    in fp16 too."""
+    """Ring forms 1 and 4 (TVC_GEMM_RING_FORM, read once per process) return the same fp16 BITS, as in bf16 (four of the
+    seven shapes compare form 4 with form 1; see _FORM_LABELS for what each shape reaches); split-K small
+    (TVC_GEMM_SPLITK_SMALL, on the 768 x 7 shape) and the one-tile kernel everywhere (TVC_GEMM_VARIANT=0) are correct in
+    fp16 too, and so is the split-K tail (TVC_GEMM_SPLITK_TAIL, on the 4096 x 33024 shape)."""
     s4 = _child(_FORMS, {})
     s1 = _child(_FORMS, {"TVC_GEMM_RING_FORM": "1"})
     assert len(s4) == 7 and s1 == s4

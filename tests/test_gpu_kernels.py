@@ -77,11 +77,18 @@ def test_gemm_tile_counts_just_above_a_round(gpu_engine, I, J, K, epi):
         assert (out[lo:hi] - ref).abs().max().item() < tol
 
 
-@pytest.mark.parametrize("I,J,K,epi", [(1024, 20000, 64, 1), (512, 40000, 128, 0), (768, 30000, 192, 2)])
+# what each shape reaches (csrc/host_plan.hpp gemm_form; tests/test_gemm_form.py asserts these labels)
+_SHORT_K_FORMS = {(1024, 20000, 64, 1): "ONE_TILE", (512, 40000, 128, 0): "ONE_TILE", (768, 30000, 192, 2): "ONE_TILE",
+                  (1024, 20480, 256, 1): "RING4", (768, 30000, 256, 0): "RING1"}
+
+
+@pytest.mark.parametrize("I,J,K,epi", [(1024, 20000, 64, 1), (512, 40000, 128, 0), (768, 30000, 192, 2),
+                                       (1024, 20480, 256, 1), (768, 30000, 256, 0)])
 def test_gemm_persistent_without_bias_and_short_k(gpu_engine, I, J, K, epi):
-    """The persistent kernel with bias = nullptr (its epilogue keeps the bias vectors in registers: zeros here) and with
-    one to three K-tiles per output tile (every K-tile is then a tile's FIRST one, whose counted waits let the previous
-    epilogue's stores pass: 16 of them for bf16 outputs, 32 for fp32)."""
+    """bias = nullptr with short K.  K = 64 / 128 / 192 (one to three K-tiles per output tile) are below the ring's
+    8-stage minimum (K >= 256) and run the ONE-TILE kernel (_SHORT_K_FORMS); K = 256 reaches the persistent kernels,
+    ring form 4 (whole tiles) and ring form 1 (ragged token rows), whose epilogue keeps the bias vectors in registers
+    (zeros here) and whose first K-tile of a tile lets the previous epilogue's stores pass in its counted waits."""
     g = torch.Generator(device="cuda:0").manual_seed(13)
     a = (torch.randn(I, K, device="cuda:0", generator=g) * K ** -0.5).to(torch.bfloat16)
     b = torch.randn(J, K, device="cuda:0", generator=g).to(torch.bfloat16)
@@ -240,9 +247,11 @@ print("SOLO_OK")
 
 def test_ring_forms_are_bit_identical():
     """every ring form sums each output element over K in the same order and runs the same epilogue
-    arithmetic, so forms 1 and 4 (the default) return the same BITS on tower-sized launches (incl. QuickGELU, a
-    ragged number of tile rounds, K = 64 and the fp32 epilogue).  scripts/gemm_form_check.py prints a checksum of the
-    raw output bits per shape; the env switch is read once per process, hence the subprocesses."""
+    arithmetic, so forms 1 and 4 (the default) return the same BITS on tower-sized launches (incl. QuickGELU and a
+    ragged number of tile rounds): six shapes of scripts/gemm_form_check.py compare form 4 with form 1.  Its K = 64 and
+    K = 128 shapes (the latter with the fp32 epilogue) take the one-tile kernel in both processes and show determinism
+    only (gemm_form_check.SHAPES labels each shape).  The script prints a checksum of the raw output bits per shape; the
+    env switch is read once per process, hence the subprocesses."""
     import os
     import subprocess
     import sys
