@@ -40,7 +40,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
-#include <mutex>
+#include "launch.hpp"
 
 #define ATT_DH 64
 #define ATT_KROW 128     // K image: 64 bf16 per row
@@ -360,17 +360,10 @@ static hipError_t launch_one(const uint16_t* qkv, uint16_t* out, const int32_t* 
     const int region = k_bytes + (EXACT ? NT * 16 : NP * 32) * ATT_VROW;
     constexpr int IPW = NW / WPS;
     const size_t lds = (size_t)region * IPW;
-    static std::once_flag attr_once;          // per instantiation; thread-safe
-    static hipError_t attr_st = hipSuccess;
-    std::call_once(attr_once, [] {
-        attr_st = hipFuncSetAttribute((const void*)attention_kernel<MAXT, CAUSAL, WPS, EXACT, NW, F16>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    });
-    if (attr_st != hipSuccess) return attr_st;
     const int n_items = n_seq * heads;
-    hipLaunchKernelGGL((attention_kernel<MAXT, CAUSAL, WPS, EXACT, NW, F16>), dim3((n_items + IPW - 1) / IPW), dim3(NW * 64), lds, stream,
-                       qkv, out, starts, T, heads, n_items, k_bytes, region, pfx, n_seq, pool_mode, pool_row);
-    return hipGetLastError();
+    return launch<attention_kernel<MAXT, CAUSAL, WPS, EXACT, NW, F16>, 128 * 1024>(
+        dim3((n_items + IPW - 1) / IPW), dim3(NW * 64), lds, stream, qkv, out, starts, T, heads, n_items, k_bytes, region, pfx, n_seq,
+        pool_mode, pool_row);
 }
 
 // starts == nullptr: n_seq sequences of seq_len rows each; otherwise sequence s owns rows
@@ -403,6 +396,7 @@ static hipError_t launch_attention_t(const uint16_t* qkv, uint16_t* out, const i
 hipError_t launch_attention(const uint16_t* qkv, uint16_t* out, const int32_t* starts, int n_seq, int seq_len,
                             int heads, int causal, hipStream_t stream, const int32_t* pfx, int pool_mode,
                             const int32_t* pool_row, int f16) {
-    return f16 ? launch_attention_t<true>(qkv, out, starts, n_seq, seq_len, heads, causal, stream, pfx, pool_mode, pool_row)
-               : launch_attention_t<false>(qkv, out, starts, n_seq, seq_len, heads, causal, stream, pfx, pool_mode, pool_row);
+    return dispatch<true, false>(f16 != 0, [&](auto h) {
+        return launch_attention_t<h.value>(qkv, out, starts, n_seq, seq_len, heads, causal, stream, pfx, pool_mode, pool_row);
+    });
 }

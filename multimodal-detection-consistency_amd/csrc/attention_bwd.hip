@@ -14,7 +14,7 @@
 // by 32 dwords, the 16 lanes a ds_read_b128 services together hit 16 distinct 16-byte slots).
 #include "common.hpp"
 #include "kernels.hpp"
-#include <mutex>
+#include "launch.hpp"
 
 #define ATT_DH 64
 #define ATT_ROW 160
@@ -325,26 +325,12 @@ hipError_t launch_attention_bwd(const uint16_t* qkv, const uint16_t* dao, uint16
     const int NT = (T + 15) / 16, NP = (NT + 1) / 2;
     const size_t lds_a = (size_t)NT * 16 * ATT_ROW + (size_t)NT * 16 * 128;
     const size_t lds_b = (size_t)2 * NP * 32 * ATT_ROW + (size_t)NP * 32 * 16;
-    static std::once_flag once;
-    static hipError_t st = hipSuccess;
-    std::call_once(once, [] {
-        st = hipFuncSetAttribute((const void*)attention_bwd_dq_kernel<18>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (st == hipSuccess)
-            st = hipFuncSetAttribute((const void*)attention_bwd_dq_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (st == hipSuccess)
-            st = hipFuncSetAttribute((const void*)attention_bwd_dkv_kernel<18, 4, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (st == hipSuccess)
-            st = hipFuncSetAttribute((const void*)attention_bwd_dkv_kernel<18, DKV_NW, 9>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    });
-    if (st != hipSuccess) return st;
+    constexpr size_t MAX_LDS = 150 * 1024;
     const dim3 grid(n_seq * heads), block(256);
-    if (NT <= 4)
-        hipLaunchKernelGGL(attention_bwd_dq_kernel<4>, grid, block, lds_a, stream, qkv, dao, dqkv, stats_ws, T, heads);
-    else
-        hipLaunchKernelGGL(attention_bwd_dq_kernel<18>, grid, block, lds_a, stream, qkv, dao, dqkv, stats_ws, T, heads);
-    if (NP == 9)        // 257 tokens (ViT-L/14): straight-line pair loop
-        hipLaunchKernelGGL((attention_bwd_dkv_kernel<18, DKV_NW, 9>), grid, dim3(DKV_NW * 64), lds_b, stream, qkv, dao, dqkv, stats_ws, T, heads);
-    else
-        hipLaunchKernelGGL((attention_bwd_dkv_kernel<18, 4, 0>), grid, block, lds_b, stream, qkv, dao, dqkv, stats_ws, T, heads);
-    return hipGetLastError();
+    const hipError_t st = NT > 4 ? launch<attention_bwd_dq_kernel<18>, MAX_LDS>(grid, block, lds_a, stream, qkv, dao, dqkv, stats_ws, T, heads)
+                                 : launch<attention_bwd_dq_kernel<4>, MAX_LDS>(grid, block, lds_a, stream, qkv, dao, dqkv, stats_ws, T, heads);
+    if (st != hipSuccess) return st;
+    if (NP != 9) return launch<attention_bwd_dkv_kernel<18, 4, 0>, MAX_LDS>(grid, block, lds_b, stream, qkv, dao, dqkv, stats_ws, T, heads);
+    // 257 tokens (ViT-L/14): straight-line pair loop
+    return launch<attention_bwd_dkv_kernel<18, DKV_NW, 9>, MAX_LDS>(grid, dim3(DKV_NW * 64), lds_b, stream, qkv, dao, dqkv, stats_ws, T, heads);
 }

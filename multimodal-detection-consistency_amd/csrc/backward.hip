@@ -4,6 +4,7 @@
 // HBM-bound, one 64-lane wave per row, 16-byte accesses, shuffle reductions -- the layout of elementwise.hip.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "launch.hpp"
 
 #define LN_EPS 1e-5f
 #define ROWS_PER_BLOCK 4
@@ -98,13 +99,10 @@ hipError_t launch_layernorm_bwd(const float* x, int64_t x_row_stride, const uint
     if (d % 4 != 0 || d > 1024 || rows < 0) return hipErrorInvalidValue;
     if (rows == 0) return hipSuccess;
     const int grid = (rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
-    if (dy_fp32)
-        hipLaunchKernelGGL(layernorm_bwd_kernel<true>, dim3(grid), dim3(256), 0, stream, x, x_row_stride, delta, dy, gamma,
-                           dres, dx, dx16, rows, d, out_row_stride);
-    else
-        hipLaunchKernelGGL(layernorm_bwd_kernel<false>, dim3(grid), dim3(256), 0, stream, x, x_row_stride, delta, dy, gamma,
-                           dres, dx, dx16, rows, d, out_row_stride);
-    return hipGetLastError();
+    return dispatch<true, false>(dy_fp32 != 0, [&](auto f32) {
+        return launch<layernorm_bwd_kernel<f32.value>>(dim3(grid), dim3(256), 0, stream, x, x_row_stride, delta, dy, gamma, dres, dx, dx16,
+                                                       rows, d, out_row_stride);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -175,9 +173,8 @@ hipError_t launch_lnpre_bwd(const float* patch_out, const float* pos, const floa
     if (d % 4 != 0 || d > 1024) return hipErrorInvalidValue;
     const int64_t rows = (int64_t)B * (T - 1);
     if (rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(lnpre_bwd_kernel, dim3((int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)), dim3(256), 0, stream,
-                       patch_out, pos, gamma, dy, dpatch, B, T, d);
-    return hipGetLastError();
+    return launch<lnpre_bwd_kernel>(dim3((int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)), dim3(256), 0, stream, patch_out, pos,
+                                    gamma, dy, dpatch, B, T, d);
 }
 
 // ---------------------------------------------------------------------------
@@ -208,8 +205,7 @@ hipError_t launch_gelu_bwd(uint16_t* dm, const uint16_t* u, int64_t n, hipStream
     if (n == 0) return hipSuccess;
     int64_t grid = (n / 8 + 255) / 256;
     if (grid > 16384) grid = 16384;
-    hipLaunchKernelGGL(gelu_bwd_kernel, dim3((int)grid), dim3(256), 0, stream, dm, u, n / 8);
-    return hipGetLastError();
+    return launch<gelu_bwd_kernel>(dim3((int)grid), dim3(256), 0, stream, dm, u, n / 8);
 }
 
 // quick-GELU forward on a bf16 buffer (the grad-mode forward stores the pre-activation and applies this)
@@ -232,8 +228,7 @@ hipError_t launch_gelu_fwd(const uint16_t* u, uint16_t* out, int64_t n, hipStrea
     if (n == 0) return hipSuccess;
     int64_t grid = (n / 8 + 255) / 256;
     if (grid > 16384) grid = 16384;
-    hipLaunchKernelGGL(gelu_fwd_kernel, dim3((int)grid), dim3(256), 0, stream, u, out, n / 8);
-    return hipGetLastError();
+    return launch<gelu_fwd_kernel>(dim3((int)grid), dim3(256), 0, stream, u, out, n / 8);
 }
 
 // ---------------------------------------------------------------------------
@@ -262,9 +257,8 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict
 
 hipError_t launch_l2norm_bwd(const float* x, const float* dy, uint16_t* dx16, int rows, int d, int normalize, hipStream_t stream) {
     if (rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(l2norm_bwd_kernel, dim3((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(256), 0, stream, x, dy, dx16,
-                       rows, d, normalize);
-    return hipGetLastError();
+    return launch<l2norm_bwd_kernel>(dim3((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(256), 0, stream, x, dy, dx16, rows, d,
+                                     normalize);
 }
 
 // ---------------------------------------------------------------------------
@@ -290,8 +284,7 @@ hipError_t launch_col2im(const float* dcols, float* dpix, int B, int S, int patc
     if (total == 0) return hipSuccess;
     int64_t grid = (total + 255) / 256;
     if (grid > 16384) grid = 16384;
-    hipLaunchKernelGGL(col2im_kernel, dim3((int)grid), dim3(256), 0, stream, dcols, dpix, B, S, patch, Kp);
-    return hipGetLastError();
+    return launch<col2im_kernel>(dim3((int)grid), dim3(256), 0, stream, dcols, dpix, B, S, patch, Kp);
 }
 
 // ---------------------------------------------------------------------------
@@ -310,8 +303,7 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(const uint16_t* __r
 
 hipError_t launch_transpose_bf16(const uint16_t* in, uint16_t* out, int R, int C, hipStream_t stream) {
     if (R <= 0 || C <= 0) return hipSuccess;
-    hipLaunchKernelGGL(transpose_bf16_kernel, dim3((C + 31) / 32, (R + 31) / 32), dim3(256), 0, stream, in, out, R, C);
-    return hipGetLastError();
+    return launch<transpose_bf16_kernel>(dim3((C + 31) / 32, (R + 31) / 32), dim3(256), 0, stream, in, out, R, C);
 }
 
 // ---------------------------------------------------------------------------
@@ -392,14 +384,12 @@ __global__ __launch_bounds__(1024) void l2_step_kernel(float* __restrict__ adv, 
 hipError_t launch_l2_step(float* adv, const float* clean, const float* grad, int B, int64_t n, float eps, float step, float lo,
                           float hi, int descent, hipStream_t stream) {
     if (B <= 0 || n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(l2_step_kernel, dim3(B), dim3(1024), 0, stream, adv, clean, grad, n, eps, step, lo, hi, descent ? -1.0f : 1.0f);
-    return hipGetLastError();
+    return launch<l2_step_kernel>(dim3(B), dim3(1024), 0, stream, adv, clean, grad, n, eps, step, lo, hi, descent ? -1.0f : 1.0f);
 }
 
 hipError_t launch_pgd_step(float* adv, const float* clean, const float* grad, float* mom, int B, int64_t n, float eps,
                            float alpha, float mu, float lo, float hi, int targeted, hipStream_t stream) {
     if (B <= 0 || n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(pgd_step_kernel, dim3(B), dim3(1024), 0, stream, adv, clean, grad, mom, n, eps, alpha, mu, lo, hi,
-                       targeted ? -1.0f : 1.0f);
-    return hipGetLastError();
+    return launch<pgd_step_kernel>(dim3(B), dim3(1024), 0, stream, adv, clean, grad, mom, n, eps, alpha, mu, lo, hi,
+                                   targeted ? -1.0f : 1.0f);
 }

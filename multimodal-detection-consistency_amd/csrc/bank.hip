@@ -37,8 +37,8 @@
 #include "gemm_core.hpp"
 #include "gemm_ring4.hpp"
 #include "kernels.hpp"
+#include "launch.hpp"
 #include <cstdlib>
-#include <mutex>
 
 #define BANK_POOL 6144
 #define BANK_MAX_RESCORE_D 2048   // fp32 query row staged in LDS by the re-scoring select
@@ -185,10 +185,9 @@ hipError_t launch_bank_bounds(const uint16_t* bank, int64_t ld, int planes, int 
     if (st != hipSuccess || R == 0) return st;
     int64_t grid = (R + 3) / 4;
     if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(bank_bounds_kernel, dim3((int)grid), dim3(256), 0, stream, bank, ld, planes, D, R,
-                       (uint32_t*)bounds);
-    hipLaunchKernelGGL(bank_bounds_finish_kernel, dim3(1), dim3(1), 0, stream, bounds);
-    return hipGetLastError();
+    st = launch<bank_bounds_kernel>(dim3((int)grid), dim3(256), 0, stream, bank, ld, planes, D, R, (uint32_t*)bounds);
+    if (st != hipSuccess) return st;
+    return launch<bank_bounds_finish_kernel>(dim3(1), dim3(1), 0, stream, bounds);
 }
 
 struct BankEpilogue {
@@ -559,28 +558,12 @@ static hipError_t launch_skinny_kb(const uint16_t* bank, int64_t ldb, const uint
                                    int rows_per_chunk, hipStream_t stream) {
     const int nqt = (e.M + 15) / 16;
     const size_t lds = (size_t)nqt * 16 * (KB * 128 + 16) + 64 * 4 + 64;
-#define SKINNY_CASE(N)                                                                                                        \
-    case N: {                                                                                                                 \
-        static std::once_flag once;                                                                                           \
-        static hipError_t ast = hipSuccess;                                                                                   \
-        std::call_once(once, [] {                                                                                             \
-            ast = hipFuncSetAttribute((const void*)bank_filter_skinny_kernel<KB, N>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                      4 * 16 * (KB * 128 + 16) + 64 * 4 + 64);                                                \
-        });                                                                                                                   \
-        if (ast != hipSuccess) return ast;                                                                                    \
-        hipLaunchKernelGGL((bank_filter_skinny_kernel<KB, N>), dim3(S), dim3(512), lds, stream, bank, ldb, qplanes, e,        \
-                           rows_per_chunk);                                                                                   \
-        break;                                                                                                                \
-    }
-    switch (nqt) {
-        SKINNY_CASE(1)
-        SKINNY_CASE(2)
-        SKINNY_CASE(3)
-        SKINNY_CASE(4)
-        default: return hipErrorInvalidValue;
-    }
-#undef SKINNY_CASE
-    return hipGetLastError();
+    // every NQT is registered with the LDS of NQT = 4
+    constexpr size_t max_lds = 4 * 16 * (KB * 128 + 16) + 64 * 4 + 64;
+    return dispatch<1, 2, 3, 4>(nqt, [&](auto n) {
+        return launch<bank_filter_skinny_kernel<KB, n.value>, max_lds>(dim3(S), dim3(512), lds, stream, bank, ldb, qplanes, e,
+                                                                       rows_per_chunk);
+    });
 }
 
 // D in {128, 512, 768} (two register sets of D / 64 x 2 sixteen-byte pieces: D = 1024 would spill) and M <= 64; false = shape
@@ -588,12 +571,9 @@ static hipError_t launch_skinny_kb(const uint16_t* bank, int64_t ldb, const uint
 static bool skinny_covers(int D, int M) { return M >= 1 && M <= 64 && (D == 128 || D == 512 || D == 768); }
 static hipError_t launch_bank_filter_skinny(const uint16_t* bank, int64_t ldb, int D, const uint16_t* qplanes, const BankEpilogue& e,
                                             int S, int rows_per_chunk, hipStream_t stream) {
-    switch (D) {
-        case 128: return launch_skinny_kb<2>(bank, ldb, qplanes, e, S, rows_per_chunk, stream);
-        case 512: return launch_skinny_kb<8>(bank, ldb, qplanes, e, S, rows_per_chunk, stream);
-        case 768: return launch_skinny_kb<12>(bank, ldb, qplanes, e, S, rows_per_chunk, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch<128, 512, 768>(D, [&](auto d) {
+        return launch_skinny_kb<d.value / 64>(bank, ldb, qplanes, e, S, rows_per_chunk, stream);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -716,40 +696,17 @@ static hipError_t launch_sample_skinny_kb(const uint16_t* bank, int64_t ldb, con
     const int per = (n_sample + 255) / 256;
     const dim3 grid(256, (M + nqt * 16 - 1) / (nqt * 16));
     const size_t lds = (size_t)nqt * 16 * (KB * 256 + 16) + 8 * nqt * 16 * 4;
-    static std::once_flag once;
-    static hipError_t ast = hipSuccess;
-    std::call_once(once, [] {
-        ast = hipFuncSetAttribute((const void*)bank_sample_skinny_kernel<KB, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  16 * (KB * 256 + 16) + 8 * 16 * 4);
-        if (ast == hipSuccess)
-            ast = hipFuncSetAttribute((const void*)bank_sample_skinny_kernel<KB, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      32 * (KB * 256 + 16) + 8 * 32 * 4);
-        if (ast == hipSuccess)
-            ast = hipFuncSetAttribute((const void*)bank_sample_skinny_kernel<KB, 3>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      48 * (KB * 256 + 16) + 8 * 48 * 4);
+    return dispatch<1, 2, 3>(nqt, [&](auto n) {
+        constexpr size_t max_lds = n.value * 16 * (KB * 256 + 16) + 8 * n.value * 16 * 4;
+        return launch<bank_sample_skinny_kernel<KB, n.value>, max_lds>(grid, dim3(512), lds, stream, bank, ldb, qplanes, M, n_sample,
+                                                                       sample_stride, per, gmax);
     });
-    if (ast != hipSuccess) return ast;
-#define SAMPLE_CASE(N)                                                                                                          \
-    case N:                                                                                                                     \
-        hipLaunchKernelGGL((bank_sample_skinny_kernel<KB, N>), grid, dim3(512), lds, stream, bank, ldb, qplanes, M, n_sample,   \
-                           sample_stride, per, gmax);                                                                           \
-        break;
-    switch (nqt) {
-        SAMPLE_CASE(1)
-        SAMPLE_CASE(2)
-        SAMPLE_CASE(3)
-    }
-#undef SAMPLE_CASE
-    return hipGetLastError();
 }
 static hipError_t launch_bank_sample_skinny(const uint16_t* bank, int64_t ldb, int D, const uint16_t* qplanes, int M, int n_sample,
                                             int sample_stride, float* gmax, hipStream_t stream) {
-    switch (D) {
-        case 128: return launch_sample_skinny_kb<2>(bank, ldb, qplanes, M, n_sample, sample_stride, gmax, stream);
-        case 512: return launch_sample_skinny_kb<8>(bank, ldb, qplanes, M, n_sample, sample_stride, gmax, stream);
-        case 768: return launch_sample_skinny_kb<12>(bank, ldb, qplanes, M, n_sample, sample_stride, gmax, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch<128, 512, 768>(D, [&](auto d) {
+        return launch_sample_skinny_kb<d.value / 64>(bank, ldb, qplanes, M, n_sample, sample_stride, gmax, stream);
+    });
 }
 
 // (v desc, idx asc) ordering
@@ -1010,49 +967,25 @@ __global__ __launch_bounds__(1024) void row_topk_kernel(float* __restrict__ sims
 
 hipError_t launch_bank_search_dense(const BankSearchLaunch& L, float* sims_ws, int block_rows, hipStream_t stream) {
     const int D = L.D;
-    const int planes = (L.bank_planes == 2) ? 3 : 2;
-    const int a_off[4] = {0, 0, D, 0};
-    const int b_off[4] = {0, D, 0, 0};
     for (int m0 = 0; m0 < L.M; m0 += block_rows) {
         const int m = (L.M - m0 < block_rows) ? L.M - m0 : block_rows;
-        GemmLaunch G;
-        G.A = L.bank; G.lda = L.ldb; G.I = (int)L.R;
-        G.B = L.qplanes + (int64_t)m0 * 2 * D; G.ldb = 2 * (int64_t)D; G.J = m; G.K = D; G.planes = planes;
-        for (int p = 0; p < 4; ++p) { G.a_plane_off[p] = a_off[p]; G.b_plane_off[p] = b_off[p]; }
-        G.out = sims_ws; G.ldo = L.R; G.epilogue = TVC_EPI_F32;
+        const GemmLaunch G = gemm_launch_planes(L.bank, L.ldb, (int)L.R, L.bank_planes, L.qplanes + (int64_t)m0 * 2 * D, m, D,
+                                                sims_ws, L.R);
         hipError_t st = launch_gemm_bf16(G, stream);
         if (st != hipSuccess) return st;
-        hipLaunchKernelGGL(row_topk_kernel, dim3(m), dim3(1024), 0, stream, sims_ws, L.R, L.k, L.count_thr,
-                           L.idx_offset, L.topk_idx + (int64_t)m0 * L.k, L.topk_sim + (int64_t)m0 * L.k,
-                           L.moments ? L.moments + (int64_t)m0 * 4 : nullptr);
-        st = hipGetLastError();
+        st = launch<row_topk_kernel>(dim3(m), dim3(1024), 0, stream, sims_ws, L.R, L.k, L.count_thr, L.idx_offset,
+                                     L.topk_idx + (int64_t)m0 * L.k, L.topk_sim + (int64_t)m0 * L.k,
+                                     L.moments ? L.moments + (int64_t)m0 * 4 : nullptr);
         if (st != hipSuccess) return st;
     }
     return hipSuccess;
 }
 
 hipError_t launch_bank_search(const BankSearchLaunch& L, hipStream_t stream) {
-    // thread-safe one-time setup (two engines may launch their first search from two threads)
-    static std::once_flag attr_once;
-    static hipError_t attr_st = hipSuccess;
-    std::call_once(attr_once, [] {
-        attr_st = hipFuncSetAttribute((const void*)bank_search_kernel<false>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, BANK_LDS_BYTES);
-        if (attr_st == hipSuccess)
-            attr_st = hipFuncSetAttribute((const void*)bank_search_kernel<true>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, BANK_LDS_BYTES);
-        if (attr_st == hipSuccess)
-            attr_st = hipFuncSetAttribute((const void*)bank_filter_ring_kernel,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, BANK_LDS_BYTES);
-    });
-    if (attr_st != hipSuccess) return attr_st;
     const int D = L.D;
     // products: (bank plane, query plane) pairs accumulated into one tile
     //   bf16 bank : b.qhi + b.qlo
     //   fp32 bank : bhi.qhi + bhi.qlo + blo.qhi
-    const int planes = (L.bank_planes == 2) ? 3 : 2;
-    const int a_off[4] = {0, 0, D, 0};          // bank plane offsets
-    const int b_off[4] = {0, D, 0, 0};          // query plane offsets
     // fast form: one-product filter + exact re-scoring (needs no per-row moments)
     const bool filter = (L.moments == nullptr) && L.bank_bounds && L.rows && D <= BANK_MAX_RESCORE_D && L.allow_filter;
 
@@ -1068,32 +1001,26 @@ hipError_t launch_bank_search(const BankSearchLaunch& L, hipStream_t stream) {
         // s0 holds >= M * n_sample floats, n_sample >= 256 or the whole bank: the first [M, 256] of it take the group maxima
         st = launch_bank_sample_skinny(L.bank, L.ldb, D, L.qplanes, L.M, L.n_sample, L.sample_stride, L.gmax, stream);
         if (st != hipSuccess) return st;
-        hipLaunchKernelGGL(kth_groups_kernel, dim3(L.M), dim3(256), 0, stream, L.gmax, L.k, L.tau, L.qplanes, D, L.bank_bounds,
-                           L.overflow);
-        st = hipGetLastError();
+        st = launch<kth_groups_kernel>(dim3(L.M), dim3(256), 0, stream, L.gmax, L.k, L.tau, L.qplanes, D, L.bank_bounds, L.overflow);
         if (st != hipSuccess) return st;
     } else {
-        GemmLaunch G;
-        G.A = L.bank; G.lda = L.ldb * (int64_t)L.sample_stride; G.I = L.n_sample;
-        G.B = L.qplanes; G.ldb = 2 * (int64_t)D; G.J = L.M; G.K = D; G.planes = planes;
-        for (int p = 0; p < 4; ++p) { G.a_plane_off[p] = a_off[p]; G.b_plane_off[p] = b_off[p]; }
-        G.out = L.s0; G.ldo = L.n_sample; G.epilogue = TVC_EPI_F32;
+        const GemmLaunch G = gemm_launch_planes(L.bank, L.ldb * (int64_t)L.sample_stride, L.n_sample, L.bank_planes, L.qplanes, L.M, D,
+                                                L.s0, L.n_sample);
         st = launch_gemm_bf16(G, stream);
         if (st != hipSuccess) return st;
-        hipLaunchKernelGGL(kth_bound_kernel, dim3(L.M), dim3(1024), 0, stream, L.s0, L.n_sample, L.k, L.tau,
-                           filter ? L.qplanes : nullptr, D, L.bank_bounds);
-        st = hipGetLastError();
+        st = launch<kth_bound_kernel>(dim3(L.M), dim3(1024), 0, stream, L.s0, L.n_sample, L.k, L.tau, filter ? L.qplanes : nullptr, D,
+                                      L.bank_bounds);
         if (st != hipSuccess) return st;
         st = hipMemsetAsync(L.overflow, 0, sizeof(int32_t), stream);
         if (st != hipSuccess) return st;
     }
 
     // ---- pass 1: fused GEMM + filter ---------------------------------------
-    GemmOperands g;
+    GemmOperands g = {};
     g.A = L.bank; g.lda = L.ldb; g.I = (int)L.R;
     g.B = L.qplanes; g.ldb = 2 * (int64_t)D; g.J = L.M;
-    g.ksteps_per_plane = D / GEMM_BK; g.planes = filter ? 1 : planes;
-    for (int p = 0; p < 4; ++p) { g.a_plane_off[p] = a_off[p]; g.b_plane_off[p] = b_off[p]; }
+    g.ksteps_per_plane = D / GEMM_BK; g.planes = filter ? 1 : (L.bank_planes == 2 ? 3 : 2);
+    g.b_plane_off[1] = D; g.a_plane_off[2] = D;     // as gemm_launch_planes (kernels.hpp)
     BankEpilogue e;
     e.tau = L.tau; e.cand = (Cand*)L.cand; e.cand_cnt = L.cand_cnt; e.mom_part = L.mom_part;
     e.overflow = L.overflow; e.R = L.R; e.idx_offset = L.idx_offset; e.M = L.M; e.count_thr = L.count_thr;
@@ -1104,26 +1031,21 @@ hipError_t launch_bank_search(const BankSearchLaunch& L, hipStream_t stream) {
     // the one-tile-at-a-time loop, for A/B runs); the ragged last bank tile is handled inside the kernel
     static const bool ring_on = [] { const char* v = getenv("TVC_BANK_RING"); return !v || atoi(v) != 0; }();
     const bool ring = filter && ring_on && L.q_rows_padded && (g.lda % 64 == 0) && (g.ldb % 64 == 0) && L.R >= GEMM_BM;
-    if (skinny) {
+    const dim3 grid(nQt * L.S), block(GEMM_THREADS);
+    if (skinny)
         st = launch_bank_filter_skinny(L.bank, L.ldb, D, L.qplanes, e, L.S, tpc * GEMM_BM, stream);
-        if (st != hipSuccess) return st;
-    } else if (ring)
-        hipLaunchKernelGGL(bank_filter_ring_kernel, dim3(nQt * L.S), dim3(GEMM_THREADS), BANK_LDS_BYTES, stream,
-                           g, e, nQt, L.S, tpc, nbt);
-    else if (filter)
-        hipLaunchKernelGGL(bank_search_kernel<true>, dim3(nQt * L.S), dim3(GEMM_THREADS), BANK_LDS_BYTES, stream,
-                           g, e, nQt, L.S, tpc, nbt);
+    else if (ring)
+        st = launch<bank_filter_ring_kernel, BANK_LDS_BYTES>(grid, block, BANK_LDS_BYTES, stream, g, e, nQt, L.S, tpc, nbt);
     else
-        hipLaunchKernelGGL(bank_search_kernel<false>, dim3(nQt * L.S), dim3(GEMM_THREADS), BANK_LDS_BYTES, stream,
-                           g, e, nQt, L.S, tpc, nbt);
-    st = hipGetLastError();
+        st = dispatch<false, true>(filter, [&](auto f) {
+            return launch<bank_search_kernel<f.value>, BANK_LDS_BYTES>(grid, block, BANK_LDS_BYTES, stream, g, e, nQt, L.S, tpc, nbt);
+        });
     if (st != hipSuccess) return st;
 
     // ---- pass 2: select -----------------------------------------------------
-    hipLaunchKernelGGL(bank_select_kernel, dim3(L.M), dim3(SEL_T), 0, stream, (const Cand*)L.cand,
-                       L.cand_cnt, L.mom_part, L.S, L.M, L.k, L.topk_idx, L.topk_sim, L.moments, L.overflow,
-                       filter ? L.bank : nullptr, L.ldb, L.bank_planes, D, L.rows, L.idx_offset);
-    return hipGetLastError();
+    return launch<bank_select_kernel>(dim3(L.M), dim3(SEL_T), 0, stream, (const Cand*)L.cand, L.cand_cnt, L.mom_part, L.S, L.M, L.k,
+                                      L.topk_idx, L.topk_sim, L.moments, L.overflow, filter ? L.bank : nullptr, L.ldb,
+                                      L.bank_planes, D, L.rows, L.idx_offset);
 }
 
 // ---------------------------------------------------------------------------
@@ -1209,7 +1131,6 @@ hipError_t launch_topk_merge(const int32_t* idx_parts, const float* sim_parts, c
                              hipStream_t stream) {
     if (M == 0) return hipSuccess;
     if (W < 1 || k < 1 || k > 128 || W * k > 256 || kf < 0 || kf > k || kf > 32) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(topk_merge_kernel, dim3(M), dim3(256), 0, stream, idx_parts, sim_parts, feat_parts,
-                       mom_parts, W, M, k, kf, D, idx_out, sim_out, feat_out, mom_out);
-    return hipGetLastError();
+    return launch<topk_merge_kernel>(dim3(M), dim3(256), 0, stream, idx_parts, sim_parts, feat_parts, mom_parts, W, M, k, kf, D,
+                                     idx_out, sim_out, feat_out, mom_out);
 }

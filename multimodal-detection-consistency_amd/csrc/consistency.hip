@@ -6,6 +6,7 @@
 // (reference: src/detector.py:461-471, experiments/defenses/detector.py:244-266).
 #include "common.hpp"
 #include "kernels.hpp"
+#include "launch.hpp"
 
 #define CONS_MAX_TEXT 40      // N + 1 <= 40
 #define CONS_MAX_CAND 320     // (N + 1) * reference_count
@@ -178,7 +179,6 @@ hipError_t launch_consistency(const float* img, const float* txt, int B, int N, 
                               hipStream_t stream) {
     if (B == 0) return hipSuccess;
     if (N < 0 || N + 1 > CONS_MAX_TEXT || (N + 1) * p.reference_count > CONS_MAX_CAND) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(consistency_kernel, dim3(B), dim3(256), 0, stream, img, txt, B, N, D, ref_idx, ref_sim,
-                       ref_feat, ks, kf, p, rec, rec_stride);
-    return hipGetLastError();
+    return launch<consistency_kernel>(dim3(B), dim3(256), 0, stream, img, txt, B, N, D, ref_idx, ref_sim, ref_feat, ks, kf, p, rec,
+                                      rec_stride);
 }

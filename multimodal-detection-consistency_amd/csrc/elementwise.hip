@@ -4,6 +4,7 @@
 // wave-shuffle reductions (no LDS).
 #include "common.hpp"
 #include "kernels.hpp"
+#include "launch.hpp"
 
 #define LN_EPS 1e-5f
 // Non-temporal hints of the LayerNorm pass (bit mask: 1 = x loads, 2 = x stores, 4 = delta loads, 8 = y stores).  The
@@ -127,13 +128,10 @@ hipError_t launch_layernorm(float* x, int64_t x_row_stride, const int32_t* row_i
     if (d % 4 != 0 || d > 1024 || rows < 0) return hipErrorInvalidValue;
     if (rows == 0) return hipSuccess;
     const int grid = (rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
-    if (f16)
-        hipLaunchKernelGGL(layernorm_kernel<true>, dim3(grid), dim3(256), 0, stream, x, x_row_stride, row_idx, delta, delta2,
-                           write_x, g, b, y, rows, d, delta_compact, xsum_out, y32);
-    else
-        hipLaunchKernelGGL(layernorm_kernel<false>, dim3(grid), dim3(256), 0, stream, x, x_row_stride, row_idx, delta, delta2,
-                           write_x, g, b, y, rows, d, delta_compact, xsum_out, y32);
-    return hipGetLastError();
+    return dispatch<true, false>(f16 != 0, [&](auto h) {
+        return launch<layernorm_kernel<h.value>>(dim3(grid), dim3(256), 0, stream, x, x_row_stride, row_idx, delta, delta2, write_x, g, b,
+                                                 y, rows, d, delta_compact, xsum_out, y32);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -220,17 +218,16 @@ hipError_t launch_im2col(const float* pix, uint16_t* out, int B, int image, int 
     if (B <= 0) return hipSuccess;
     const int g = image / patch;
     const size_t lds = (size_t)g * Kp * 2;
-    if (image % 4 == 0 && Kp % 8 == 0 && lds <= 64 * 1024) {
-        if (f16) hipLaunchKernelGGL(im2col_rows_kernel<true>, dim3(B * g), dim3(256), lds, stream, pix, out, image, patch, Kp);
-        else hipLaunchKernelGGL(im2col_rows_kernel<false>, dim3(B * g), dim3(256), lds, stream, pix, out, image, patch, Kp);
-        return hipGetLastError();
-    }
+    if (image % 4 == 0 && Kp % 8 == 0 && lds <= 64 * 1024)
+        return dispatch<true, false>(f16 != 0, [&](auto h) {
+            return launch<im2col_rows_kernel<h.value>>(dim3(B * g), dim3(256), lds, stream, pix, out, image, patch, Kp);
+        });
     const int64_t total = (int64_t)B * g * g * (Kp >> 3);
     int grid = (int)((total + 255) / 256);
     if (grid > 8192) grid = 8192;
-    if (f16) hipLaunchKernelGGL(im2col_kernel<true>, dim3(grid), dim3(256), 0, stream, pix, out, B, image, patch, Kp);
-    else hipLaunchKernelGGL(im2col_kernel<false>, dim3(grid), dim3(256), 0, stream, pix, out, B, image, patch, Kp);
-    return hipGetLastError();
+    return dispatch<true, false>(f16 != 0, [&](auto h) {
+        return launch<im2col_kernel<h.value>>(dim3(grid), dim3(256), 0, stream, pix, out, B, image, patch, Kp);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -298,8 +295,7 @@ hipError_t launch_assemble_lnpre(const float* patch_out, const float* cls, const
     const int64_t rows = (int64_t)B * T;
     if (rows == 0) return hipSuccess;
     const int grid = (int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
-    hipLaunchKernelGGL(assemble_lnpre_kernel, dim3(grid), dim3(256), 0, stream, patch_out, cls, pos, g, b, x, B, T, d);
-    return hipGetLastError();
+    return launch<assemble_lnpre_kernel>(dim3(grid), dim3(256), 0, stream, patch_out, cls, pos, g, b, x, B, T, d);
 }
 
 // ---------------------------------------------------------------------------
@@ -405,10 +401,9 @@ hipError_t launch_text_lens_scan(const int32_t* tok, int32_t* starts, int32_t* p
     if (pfx && G < 2) return hipErrorInvalidValue;
     int32_t* lens = pfx ? pfx + n_text : lens_ws;
     if (!lens) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(text_lens_kernel, dim3((n_text + 3) / 4), dim3(256), 0, stream, tok, starts, pfx, lens, n_text,
-                       ctx, G);
-    hipLaunchKernelGGL(text_scan_kernel, dim3(1), dim3(1024), 0, stream, starts, pfx, lens, n_text, G);
-    return hipGetLastError();
+    const hipError_t st = launch<text_lens_kernel>(dim3((n_text + 3) / 4), dim3(256), 0, stream, tok, starts, pfx, lens, n_text, ctx, G);
+    if (st != hipSuccess) return st;
+    return launch<text_scan_kernel>(dim3(1), dim3(1024), 0, stream, starts, pfx, lens, n_text, G);
 }
 
 // ---------------------------------------------------------------------------
@@ -469,9 +464,7 @@ hipError_t launch_text_embed(const int32_t* tok, const float* tok_emb, const flo
     const int64_t rows = (int64_t)n_text * ctx;
     if (rows == 0) return hipSuccess;
     const int grid = (int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
-    hipLaunchKernelGGL(text_embed_kernel, dim3(grid), dim3(256), 0, stream, tok, tok_emb, pos, x, eot_row, starts,
-                       pfx, n_text, ctx, d, vocab);
-    return hipGetLastError();
+    return launch<text_embed_kernel>(dim3(grid), dim3(256), 0, stream, tok, tok_emb, pos, x, eot_row, starts, pfx, n_text, ctx, d, vocab);
 }
 
 // ---------------------------------------------------------------------------
@@ -492,8 +485,7 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(float* __restrict__ x,
 hipError_t launch_l2norm_rows(float* x, int rows, int d, hipStream_t stream) {
     if (rows == 0) return hipSuccess;
     const int grid = (rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
-    hipLaunchKernelGGL(l2norm_rows_kernel, dim3(grid), dim3(256), 0, stream, x, rows, d);
-    return hipGetLastError();
+    return launch<l2norm_rows_kernel>(dim3(grid), dim3(256), 0, stream, x, rows, d);
 }
 
 // ---------------------------------------------------------------------------
@@ -524,8 +516,7 @@ static hipError_t launch_gelu_erf_16(uint16_t* x, int64_t n, hipStream_t stream)
     if (n % 8 != 0 || n < 0) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
     const int64_t n8 = n / 8;
-    hipLaunchKernelGGL(gelu_erf_16_kernel<F16>, dim3((int)((n8 + 255) / 256 < 16384 ? (n8 + 255) / 256 : 16384)), dim3(256), 0, stream, x, n8);
-    return hipGetLastError();
+    return launch<gelu_erf_16_kernel<F16>>(dim3((int)((n8 + 255) / 256 < 16384 ? (n8 + 255) / 256 : 16384)), dim3(256), 0, stream, x, n8);
 }
 hipError_t launch_gelu_erf_bf16(uint16_t* x, int64_t n, hipStream_t stream) { return launch_gelu_erf_16<false>(x, n, stream); }
 hipError_t launch_gelu_erf_f16(uint16_t* x, int64_t n, hipStream_t stream) { return launch_gelu_erf_16<true>(x, n, stream); }
@@ -533,8 +524,7 @@ hipError_t launch_gelu_erf_f32(float* x, int64_t n, hipStream_t stream) {
     if (n % 4 != 0 || n < 0) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
     const int64_t n4 = n / 4;
-    hipLaunchKernelGGL(gelu_erf_f32_kernel, dim3((int)((n4 + 255) / 256 < 16384 ? (n4 + 255) / 256 : 16384)), dim3(256), 0, stream, x, n4);
-    return hipGetLastError();
+    return launch<gelu_erf_f32_kernel>(dim3((int)((n4 + 255) / 256 < 16384 ? (n4 + 255) / 256 : 16384)), dim3(256), 0, stream, x, n4);
 }
 
 // ---------------------------------------------------------------------------
@@ -570,8 +560,7 @@ hipError_t launch_split_planes(const float* x, uint16_t* out, int64_t rows, int 
     const int64_t total = rows * (d >> 2);
     int grid = (int)((total + 255) / 256);
     if (grid > 16384) grid = 16384;
-    hipLaunchKernelGGL(split_planes_kernel, dim3(grid), dim3(256), 0, stream, x, out, rows, d, planes);
-    return hipGetLastError();
+    return launch<split_planes_kernel>(dim3(grid), dim3(256), 0, stream, x, out, rows, d, planes);
 }
 
 // ---------------------------------------------------------------------------
@@ -604,6 +593,5 @@ hipError_t launch_gather_rows(const uint16_t* bank, int64_t ld, int planes, int 
                               hipStream_t stream) {
     if (n == 0) return hipSuccess;
     const int grid = (n + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(grid), dim3(256), 0, stream, bank, ld, planes, D, R, idx, idx_offset, n, out);
-    return hipGetLastError();
+    return launch<gather_rows_kernel>(dim3(grid), dim3(256), 0, stream, bank, ld, planes, D, R, idx, idx_offset, n, out);
 }

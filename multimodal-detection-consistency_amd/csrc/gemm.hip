@@ -4,9 +4,8 @@
 // v_mfma_f32_16x16x32_f16 and fp16 conversions in the 16-bit epilogues.
 #include "gemm_epilogue.hpp"
 #include "gemm_ring4.hpp"
+#include "launch.hpp"
 #include <cstdlib>
-#include <mutex>
-#include <type_traits>
 
 // s_setprio levels of the MFMA phases of the two wave groups of the ring kernel (see gemm_ring_kernel)
 #define TVC_PRIO_G0 1
@@ -519,42 +518,6 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_splitk_finish_kernel(GemmOp
     if (i < g.I && j < g.J) gemm_store4<EPI, F16>(e, g.I, i, j, v);
 }
 
-template <bool F16> static hipError_t set_lds_attr_impl();
-template <bool F16> static hipError_t set_lds_attr_once() {
-    // thread-safe: the Python lock is per engine, two engines may first-launch from two threads
-    static std::once_flag once;
-    static hipError_t st = hipSuccess;
-    std::call_once(once, [] { st = set_lds_attr_impl<F16>(); });
-    return st;
-}
-template <bool F16> static hipError_t set_lds_attr_impl() {
-    hipError_t st = hipSuccess;
-#define SET_ATTR(K)                                                                              \
-    if (st == hipSuccess)                                                                        \
-        st = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                                 GEMM_LDS_BYTES);
-    SET_ATTR((gemm_bf16_kernel<TVC_EPI_F32, F16>))
-    SET_ATTR((gemm_bf16_kernel<TVC_EPI_BF16, F16>))
-    SET_ATTR((gemm_bf16_kernel<TVC_EPI_GELU_BF16, F16>))
-    SET_ATTR((gemm_bf16_kernel<TVC_EPI_RESID_F32, F16>))
-    SET_ATTR(gemm_splitk_partial_kernel<F16>)
-#undef SET_ATTR
-#define SET_ATTR(K)                                                                              \
-    if (st == hipSuccess)                                                                        \
-        st = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                                 RING_LDS_BYTES + 4096);
-    SET_ATTR((gemm_ring_kernel<TVC_EPI_F32, F16>))
-    SET_ATTR((gemm_ring_kernel<TVC_EPI_BF16, F16>))
-    SET_ATTR((gemm_ring_kernel<TVC_EPI_GELU_BF16, F16>))
-    SET_ATTR((gemm_ring_kernel<TVC_EPI_RESID_F32, F16>))
-    SET_ATTR((gemm_ring4_kernel<TVC_EPI_F32, F16>))
-    SET_ATTR((gemm_ring4_kernel<TVC_EPI_BF16, F16>))
-    SET_ATTR((gemm_ring4_kernel<TVC_EPI_GELU_BF16, F16>))
-    SET_ATTR(gemm_ring4_split_kernel<F16>)
-#undef SET_ATTR
-    return st;
-}
-
 // The env switches of the dispatch, read once per process (the values host_plan.hpp's gemm_form receives).
 static const GemmFormEnv& gemm_form_env() {
     static const GemmFormEnv env = [] {
@@ -586,34 +549,35 @@ static const GemmFormEnv& gemm_form_env() {
     return env;
 }
 
-// split-K partial + finish kernels for the tiles from tile column jt0 on (S-way K split; ws holds their fp32 partial tiles)
+// the LDS each kernel family is registered with at its first launch (launch.hpp)
+constexpr size_t RING_MAX_LDS = RING_LDS_BYTES + 4096;
+static_assert(GEMM_BM == HOST_PLAN_GEMM_BM && GEMM_BN == HOST_PLAN_GEMM_BN, "gemm_form() plans in the kernels' tiles");
+
+// f(integral_constant epilogue) for any of the four epilogues
+template <class F>
+static hipError_t dispatch_epilogue(int epilogue, F&& f) {
+    return dispatch<TVC_EPI_F32, TVC_EPI_BF16, TVC_EPI_GELU_BF16, TVC_EPI_RESID_F32>(epilogue, f);
+}
+
+// split-K partial kernel for the tiles from tile column jt0 on (S-way K split; ws receives their fp32 partial tiles)
+template <bool F16>
+static hipError_t launch_splitk_partial(const GemmLaunch& L, const GemmOperands& g, int tiles, int nIt, int jt0, int S,
+                                        hipStream_t stream) {
+    return launch<gemm_splitk_partial_kernel<F16>, GEMM_LDS_BYTES>(dim3(tiles * S), dim3(GEMM_THREADS), GEMM_LDS_BYTES, stream, g,
+                                                                   L.splitk_ws, nIt, jt0, S);
+}
+// ... and the finish kernel that sums them into the epilogue
 template <bool F16>
 static hipError_t launch_splitk_finish(const GemmLaunch& L, const GemmOperands& g, const GemmEpilogue& e, int tiles, int nIt,
                                        int jt0, int S, hipStream_t stream) {
-    const dim3 block(GEMM_THREADS);
-    switch (L.epilogue) {
-        case TVC_EPI_F32:
-            hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_F32, F16>), dim3(tiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt0, S);
-            break;
-        case TVC_EPI_BF16:
-            hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_BF16, F16>), dim3(tiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt0, S);
-            break;
-        case TVC_EPI_GELU_BF16:
-            hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_GELU_BF16, F16>), dim3(tiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt0, S);
-            break;
-        case TVC_EPI_RESID_F32:
-            hipLaunchKernelGGL((gemm_splitk_finish_kernel<TVC_EPI_RESID_F32, F16>), dim3(tiles * 32), block, 0, stream, g, e, L.splitk_ws, nIt, jt0, S);
-            break;
-        default:
-            return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_epilogue(L.epilogue, [&](auto epi) {
+        return launch<gemm_splitk_finish_kernel<epi.value, F16>>(dim3(tiles * 32), dim3(GEMM_THREADS), 0, stream, g, e, L.splitk_ws,
+                                                                 nIt, jt0, S);
+    });
 }
 
 template <bool F16>
 static hipError_t launch_gemm_t(const GemmLaunch& L, hipStream_t stream) {
-    hipError_t st = set_lds_attr_once<F16>();
-    if (st != hipSuccess) return st;
     GemmOperands g;
     g.A = L.A; g.B = L.B; g.lda = L.lda; g.ldb = L.ldb; g.I = L.I; g.J = L.J;
     g.ksteps_per_plane = L.K / GEMM_BK;
@@ -631,22 +595,20 @@ static hipError_t launch_gemm_t(const GemmLaunch& L, hipStream_t stream) {
     // batch-position invariance to protect -- 64..128 tiles of a DEEP K, a 3 x 3 convolution at 16 x 16 latents: 120 tiles
     // x 180 K-tiles, take the split-K kernels too instead of one tile per workgroup on half the chip); `splitk_fixed`: the
     // caller fixed the K split (kernels.hpp).
-    GemmFormArgs fa;
-    fa.I = L.I; fa.J = L.J; fa.K = L.K; fa.planes = L.planes; fa.lda = L.lda; fa.ldb = L.ldb; fa.epilogue = L.epilogue;
-    fa.splitk_small = L.splitk_small; fa.splitk_fixed = L.splitk_fixed; fa.has_ws = L.splitk_ws != nullptr;
-    fa.ws_bytes = L.splitk_ws_bytes; fa.a_rows_padded = L.a_rows_padded; fa.b_rows_padded = L.b_rows_padded;
-    const GemmPlan plan = gemm_form(fa, gemm_form_env());
+    const GemmPlan plan = gemm_form(form_args(L), gemm_form_env());
     const int S = plan.S;
+    const dim3 rgrid(ntiles >= 256 ? 256 : (ntiles + 7) / 8 * 8);   // the rings: a workgroup without a tile returns at once
+    hipError_t st;
     switch (plan.form) {
         case GEMM_FORM_SPLITK_FIXED: {
             if (!L.splitk_ws || (size_t)ntiles * S * GEMM_BM * GEMM_BN * 4 > L.splitk_ws_bytes) return hipErrorInvalidValue;
             const int vt = ntiles * S;
-            if (plan.ring_split) {
-                const dim3 rgrid(vt >= 256 ? 256 : (vt + 7) / 8 * 8);
-                hipLaunchKernelGGL(gemm_ring4_split_kernel<F16>, rgrid, block, R3_LDS_BYTES + 4096, stream, g, L.splitk_ws, nIt, nJt, S);
-            } else {
-                hipLaunchKernelGGL(gemm_splitk_partial_kernel<F16>, dim3(vt), block, GEMM_LDS_BYTES, stream, g, L.splitk_ws, nIt, 0, S);
-            }
+            if (plan.ring_split)
+                st = launch<gemm_ring4_split_kernel<F16>, RING_MAX_LDS>(dim3(vt >= 256 ? 256 : (vt + 7) / 8 * 8), block,
+                                                                        R3_LDS_BYTES + 4096, stream, g, L.splitk_ws, nIt, nJt, S);
+            else
+                st = launch_splitk_partial<F16>(L, g, ntiles, nIt, 0, S, stream);
+            if (st != hipSuccess) return st;
             return launch_splitk_finish<F16>(L, g, e, ntiles, nIt, 0, S, stream);
         }
         case GEMM_FORM_SPLITK_TAIL: {
@@ -655,10 +617,9 @@ static hipError_t launch_gemm_t(const GemmLaunch& L, hipStream_t stream) {
             GemmLaunch M2 = L;
             M2.J = plan.jt_full * GEMM_BN;
             M2.splitk_ws = nullptr;
-            hipError_t st2 = launch_gemm_bf16(M2, stream);
-            if (st2 != hipSuccess) return st2;
-            hipLaunchKernelGGL(gemm_splitk_partial_kernel<F16>, dim3(plan.left * S), block, GEMM_LDS_BYTES, stream, g,
-                               L.splitk_ws, nIt, plan.jt_full, S);
+            st = launch_gemm_bf16(M2, stream);
+            if (st == hipSuccess) st = launch_splitk_partial<F16>(L, g, plan.left, nIt, plan.jt_full, S, stream);
+            if (st != hipSuccess) return st;
             return launch_splitk_finish<F16>(L, g, e, plan.left, nIt, plan.jt_full, S, stream);
         }
         case GEMM_FORM_SPLITK_SMALL:
@@ -666,72 +627,28 @@ static hipError_t launch_gemm_t(const GemmLaunch& L, hipStream_t stream) {
             // few tiles, deep K (small batches): one tile per workgroup would leave most of the 256 CUs idle and run K
             // serially (FC2 at one image: 8 workgroups x 64 K-steps).  Split K over S workgroups per tile (fp32 partial
             // tiles + the finish kernel of the split-K tail).
-            hipLaunchKernelGGL(gemm_splitk_partial_kernel<F16>, dim3(ntiles * S), block, GEMM_LDS_BYTES, stream, g,
-                               L.splitk_ws, nIt, 0, S);
+            st = launch_splitk_partial<F16>(L, g, ntiles, nIt, 0, S, stream);
+            if (st != hipSuccess) return st;
             return launch_splitk_finish<F16>(L, g, e, ntiles, nIt, 0, S, stream);
-        case GEMM_FORM_RING4: {
+        case GEMM_FORM_RING4:
             // barrier-staggered ping-pong in 16-MFMA phases over 64-deep whole-line K-tiles.  It reads whole rows without
             // clamping: out-feature rows must fill whole tiles, B must have readable rows up to the next multiple of 256
             // (J % 256 == 0, or a padded workspace: GemmLaunch::b_rows_padded), and the row pitches must be multiples of
-            // 128 bytes (its source swizzle flips address bit 6)
-            const dim3 rgrid(ntiles >= 256 ? 256 : (ntiles + 7) / 8 * 8);   // a workgroup without a tile returns at once
-            switch (L.epilogue) {
-                case TVC_EPI_F32:
-                    hipLaunchKernelGGL((gemm_ring4_kernel<TVC_EPI_F32, F16>), rgrid, block, R3_LDS_BYTES + 4096, stream, g, e, nIt, nJt);
-                    break;
-                case TVC_EPI_BF16:
-                    hipLaunchKernelGGL((gemm_ring4_kernel<TVC_EPI_BF16, F16>), rgrid, block, R3_LDS_BYTES + 4096, stream, g, e, nIt, nJt);
-                    break;
-                case TVC_EPI_GELU_BF16:
-                    hipLaunchKernelGGL((gemm_ring4_kernel<TVC_EPI_GELU_BF16, F16>), rgrid, block, R3_LDS_BYTES + 4096, stream, g, e, nIt, nJt);
-                    break;
-                default:
-                    return hipErrorInvalidValue;
-            }
-            return hipGetLastError();
-        }
-        case GEMM_FORM_RING1: {
+            // 128 bytes (its source swizzle flips address bit 6).  It carries no residual epilogue.
+            return dispatch<TVC_EPI_F32, TVC_EPI_BF16, TVC_EPI_GELU_BF16>(L.epilogue, [&](auto epi) {
+                return launch<gemm_ring4_kernel<epi.value, F16>, RING_MAX_LDS>(rgrid, block, R3_LDS_BYTES + 4096, stream, g, e, nIt, nJt);
+            });
+        case GEMM_FORM_RING1:
             // 32-deep stages, clamped rows: any shape
-            const dim3 rgrid(ntiles >= 256 ? 256 : (ntiles + 7) / 8 * 8);
-            switch (L.epilogue) {
-                case TVC_EPI_F32:
-                    hipLaunchKernelGGL((gemm_ring_kernel<TVC_EPI_F32, F16>), rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
-                    break;
-                case TVC_EPI_BF16:
-                    hipLaunchKernelGGL((gemm_ring_kernel<TVC_EPI_BF16, F16>), rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
-                    break;
-                case TVC_EPI_GELU_BF16:
-                    hipLaunchKernelGGL((gemm_ring_kernel<TVC_EPI_GELU_BF16, F16>), rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
-                    break;
-                case TVC_EPI_RESID_F32:
-                    hipLaunchKernelGGL((gemm_ring_kernel<TVC_EPI_RESID_F32, F16>), rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
-                    break;
-                default:
-                    return hipErrorInvalidValue;
-            }
-            return hipGetLastError();
-        }
+            return dispatch_epilogue(L.epilogue, [&](auto epi) {
+                return launch<gemm_ring_kernel<epi.value, F16>, RING_MAX_LDS>(rgrid, block, RING_LDS_BYTES + 2048, stream, g, e, nIt, nJt);
+            });
         case GEMM_FORM_ONE_TILE:
             break;
     }
-    const dim3 grid(nIt * nJt);
-    switch (L.epilogue) {
-        case TVC_EPI_F32:
-            hipLaunchKernelGGL((gemm_bf16_kernel<TVC_EPI_F32, F16>), grid, block, GEMM_LDS_BYTES, stream, g, e, nIt, nJt);
-            break;
-        case TVC_EPI_BF16:
-            hipLaunchKernelGGL((gemm_bf16_kernel<TVC_EPI_BF16, F16>), grid, block, GEMM_LDS_BYTES, stream, g, e, nIt, nJt);
-            break;
-        case TVC_EPI_GELU_BF16:
-            hipLaunchKernelGGL((gemm_bf16_kernel<TVC_EPI_GELU_BF16, F16>), grid, block, GEMM_LDS_BYTES, stream, g, e, nIt, nJt);
-            break;
-        case TVC_EPI_RESID_F32:
-            hipLaunchKernelGGL((gemm_bf16_kernel<TVC_EPI_RESID_F32, F16>), grid, block, GEMM_LDS_BYTES, stream, g, e, nIt, nJt);
-            break;
-        default:
-            return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_epilogue(L.epilogue, [&](auto epi) {
+        return launch<gemm_bf16_kernel<epi.value, F16>, GEMM_LDS_BYTES>(dim3(ntiles), block, GEMM_LDS_BYTES, stream, g, e, nIt, nJt);
+    });
 }
 
 hipError_t launch_gemm_bf16(const GemmLaunch& L, hipStream_t stream) {

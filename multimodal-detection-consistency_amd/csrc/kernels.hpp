@@ -26,7 +26,6 @@ struct GemmLaunch {
     void* out = nullptr;           // [J, ldo]
     int64_t ldo = 0;
     int epilogue = TVC_EPI_F32;
-    bool no_solo = false;          // internal: remainder launch of a split GEMM
     bool b_rows_padded = false;    // B has readable (garbage) rows up to the next multiple of 256 beyond J
     // optional scratch for the split-K tail (see launch_gemm_bf16); nullptr disables it
     float* splitk_ws = nullptr;
@@ -34,6 +33,32 @@ struct GemmLaunch {
     bool f16 = false;              // A, B are IEEE fp16 (v_mfma_f32_16x16x32_f16) and the 16-bit epilogues store fp16 (tower mode 3)
 };
 hipError_t launch_gemm_bf16(const GemmLaunch& L, hipStream_t stream);
+// the plain one-plane product out[J, ldo] = epilogue(B[J, ldb] * A[I, lda]^T + bias); callers set the odd flags afterwards
+inline GemmLaunch gemm_launch(const uint16_t* A, int64_t lda, int I, const uint16_t* B, int64_t ldb, int J, int K,
+                              const float* bias, void* out, int64_t ldo, int epilogue) {
+    GemmLaunch g;
+    g.A = A; g.lda = lda; g.I = I; g.B = B; g.ldb = ldb; g.J = J; g.K = K;
+    g.bias = bias; g.out = out; g.ldo = ldo; g.epilogue = epilogue;
+    return g;
+}
+// the bank's (hi | lo) plane products, fp32 out: rows of A and B hold D-wide planes side by side, B always (hi | lo).
+// bank_planes 1: hi * hi + hi * lo; 2: + lo * hi from A's second plane (the lo * lo term is below fp32)
+inline GemmLaunch gemm_launch_planes(const uint16_t* A, int64_t lda, int I, int bank_planes, const uint16_t* B, int J, int D,
+                                     float* out, int64_t ldo) {
+    GemmLaunch g = gemm_launch(A, lda, I, B, 2 * (int64_t)D, J, D, nullptr, out, ldo, TVC_EPI_F32);
+    g.planes = bank_planes == 2 ? 3 : 2;
+    g.b_plane_off[1] = D;
+    g.a_plane_off[2] = D;
+    return g;
+}
+// what gemm_form() reads of a launch
+inline GemmFormArgs form_args(const GemmLaunch& L) {
+    GemmFormArgs a;
+    a.I = L.I; a.J = L.J; a.K = L.K; a.planes = L.planes; a.lda = L.lda; a.ldb = L.ldb; a.epilogue = L.epilogue;
+    a.splitk_small = L.splitk_small; a.splitk_fixed = L.splitk_fixed; a.has_ws = L.splitk_ws != nullptr;
+    a.ws_bytes = L.splitk_ws_bytes; a.a_rows_padded = L.a_rows_padded; a.b_rows_padded = L.b_rows_padded;
+    return a;
+}
 
 // ---- elementwise.hip
 // y = LN(x [+ delta [+ delta2]]); with a delta and write_x the sum is written back to x (residual stream)

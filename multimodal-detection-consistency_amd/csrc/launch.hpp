@@ -1,0 +1,32 @@
+// The one place a kernel is started (included by the .hip files only; kernels.hpp and handle.hpp stay free of it).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <mutex>
+#include <type_traits>
+
+// Starts Kernel and returns hipGetLastError().  MaxLds > 0: the kernel takes more than 64 KiB of dynamic LDS, so its first
+// launch registers MaxLds bytes with the runtime (once per kernel, thread-safe: the Python lock is per engine, two engines
+// may first-launch from two threads); a failed registration or lds > MaxLds is returned without launching.
+template <auto Kernel, size_t MaxLds = 0, class... Args>
+hipError_t launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    if constexpr (MaxLds > 0) {
+        static std::once_flag once;
+        static hipError_t attr = hipSuccess;
+        std::call_once(once, [] {
+            attr = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MaxLds);
+        });
+        if (attr != hipSuccess) return attr;
+        if (lds > MaxLds) return hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+    return hipGetLastError();
+}
+
+// Runtime value -> template argument: calls f(std::integral_constant<.., V>{}) for the V of Vs that equals v and returns its
+// result; hipErrorInvalidValue when v is none of them.  Only the listed values are instantiated (a left fold: in list order).
+template <auto... Vs, class T, class F>
+hipError_t dispatch(T v, F&& f) {
+    hipError_t st = hipErrorInvalidValue;
+    (void)(... || (v == Vs && ((st = f(std::integral_constant<decltype(Vs), Vs>{})), true)));
+    return st;
+}

@@ -7,7 +7,7 @@
 // slower than the bf16 towers and is not the benchmarked path).
 #include "common.hpp"
 #include "kernels.hpp"
-#include <mutex>
+#include "launch.hpp"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
@@ -216,8 +216,7 @@ hipError_t launch_gemm_f32(const float* W, int64_t ldw, const float* X, int64_t 
     const int64_t gy = ((int64_t)J + PG_BM - 1) / PG_BM;
     if (gy > 65535) return hipErrorInvalidValue;
     dim3 grid((I + PG_BN - 1) / PG_BN, (unsigned)gy);
-    hipLaunchKernelGGL(gemm_f32_kernel, grid, dim3(256), 0, stream, W, ldw, X, ldx, bias, out, ldo, I, J, K, epi);
-    return hipGetLastError();
+    return launch<gemm_f32_kernel>(grid, dim3(256), 0, stream, W, ldw, X, ldx, bias, out, ldo, I, J, K, epi);
 }
 
 hipError_t launch_attention_f32(const float* qkv, float* out, int n_seq, int T, int heads, int causal,
@@ -225,14 +224,7 @@ hipError_t launch_attention_f32(const float* qkv, float* out, int n_seq, int T, 
     if (n_seq <= 0) return hipSuccess;
     if (T <= 0 || T > 288 || heads <= 0) return hipErrorInvalidValue;
     const size_t lds = (size_t)T * 64 * 4 * 2;
-    static std::once_flag attr_once;          // thread-safe: two engines may first-launch from two threads
-    static hipError_t attr_st = hipSuccess;
-    std::call_once(attr_once, [] {
-        attr_st = hipFuncSetAttribute((const void*)attention_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
-    });
-    if (attr_st != hipSuccess) return attr_st;
-    hipLaunchKernelGGL(attention_f32_kernel, dim3(n_seq * heads), dim3(256), lds, stream, qkv, out, T, heads, causal);
-    return hipGetLastError();
+    return launch<attention_f32_kernel, 160 * 1024 - 512>(dim3(n_seq * heads), dim3(256), lds, stream, qkv, out, T, heads, causal);
 }
 
 hipError_t launch_im2col_f32(const float* pix, float* out, int B, int image, int patch, hipStream_t stream) {
@@ -240,8 +232,7 @@ hipError_t launch_im2col_f32(const float* pix, float* out, int B, int image, int
     const int g = image / patch;
     const int64_t total = (int64_t)B * g * g * 3 * patch * patch;
     int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    hipLaunchKernelGGL(im2col_f32_kernel, dim3(grid), dim3(256), 0, stream, pix, out, B, image, patch);
-    return hipGetLastError();
+    return launch<im2col_f32_kernel>(dim3(grid), dim3(256), 0, stream, pix, out, B, image, patch);
 }
 
 hipError_t launch_gather_f32_rows(const float* x, int64_t ld, const int32_t* idx, int64_t idx_mul, float* out, int n,
@@ -250,6 +241,5 @@ hipError_t launch_gather_f32_rows(const float* x, int64_t ld, const int32_t* idx
     if (d % 4 != 0) return hipErrorInvalidValue;
     const int64_t total = (int64_t)n * (d >> 2);
     int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(gather_f32_rows_kernel, dim3(grid), dim3(256), 0, stream, x, ld, idx, idx_mul, out, n, d);
-    return hipGetLastError();
+    return launch<gather_f32_rows_kernel>(dim3(grid), dim3(256), 0, stream, x, ld, idx, idx_mul, out, n, d);
 }

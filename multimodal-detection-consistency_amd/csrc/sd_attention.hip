@@ -20,6 +20,7 @@
 // scores exists only in that last tile.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "launch.hpp"
 #include <cstdlib>
 
 namespace {
@@ -293,9 +294,8 @@ hipError_t launch_fa(const uint16_t* Q, int64_t ldq, const uint16_t* K, int64_t 
     const float scale_log2 = 1.4426950408889634f / sqrtf((float)DH);
     const int nqb = (Tq + NW * 16 * QB - 1) / (NW * 16 * QB);
     dim3 grid((unsigned)((int64_t)nqb * heads * n));
-    hipLaunchKernelGGL((sd_flash_attention_kernel<DH, QB, NW>), grid, dim3(NW * 64), 0, st, Q, ldq, K, ldk, V, ldv, O, ldo, Tq, Tk,
-                       scale_log2, heads, nqb);
-    return hipGetLastError();
+    return launch<sd_flash_attention_kernel<DH, QB, NW>>(grid, dim3(NW * 64), 0, st, Q, ldq, K, ldk, V, ldv, O, ldo, Tq, Tk, scale_log2,
+                                                         heads, nqb);
 }
 
 }  // namespace
@@ -316,17 +316,12 @@ hipError_t sd_flash_attention(const uint16_t* Q, int64_t ldq, const uint16_t* K,
     if (items * ((Tq + 127) / 128) >= 512) shape = 2;        // 2: 4 waves x 2 blocks (128 queries)
     if (items * ((Tq + 255) / 256) >= 512) shape = 3;        // 3: 8 waves x 2 blocks (256 queries)
     if (shape_env) shape = shape_env;
-#define FA_CASE(DH_, MAXSHAPE_)                                                                                          \
-    case DH_: {                                                                                                         \
-        const int sh = shape < MAXSHAPE_ ? shape : MAXSHAPE_;                                                           \
-        if (sh == 3) return launch_fa<DH_, (MAXSHAPE_ >= 3 ? 2 : 1), (MAXSHAPE_ >= 3 ? 8 : 4)>(Q, ldq, K, ldk, V, ldv, O, ldo, n, heads, Tq, Tk, st); \
-        if (sh == 2) return launch_fa<DH_, (MAXSHAPE_ >= 2 ? 2 : 1), 4>(Q, ldq, K, ldk, V, ldv, O, ldo, n, heads, Tq, Tk, st);      \
-        return launch_fa<DH_, 1, 4>(Q, ldq, K, ldk, V, ldv, O, ldo, n, heads, Tq, Tk, st);                             \
-    }
-    switch (dh) {
-        FA_CASE(8, 3) FA_CASE(16, 3) FA_CASE(24, 3) FA_CASE(32, 3) FA_CASE(40, 3) FA_CASE(48, 3) FA_CASE(56, 3) FA_CASE(64, 3)
-        FA_CASE(80, 3) FA_CASE(96, 1) FA_CASE(128, 1) FA_CASE(160, 1)
-        default: return hipErrorInvalidValue;       // head_dim not instantiated
-    }
-#undef FA_CASE
+    // head dims up to 80 have all three shapes, the wider ones shape 1 only; any other head_dim is not instantiated
+    return dispatch<8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 128, 160>(dh, [&](auto d) {
+        constexpr int DH = d.value, MAXSHAPE = DH <= 80 ? 3 : 1;
+        const int sh = shape < MAXSHAPE ? shape : MAXSHAPE;
+        if (sh == 3) return launch_fa<DH, (MAXSHAPE >= 3 ? 2 : 1), (MAXSHAPE >= 3 ? 8 : 4)>(Q, ldq, K, ldk, V, ldv, O, ldo, n, heads, Tq, Tk, st);
+        if (sh == 2) return launch_fa<DH, (MAXSHAPE >= 2 ? 2 : 1), 4>(Q, ldq, K, ldk, V, ldv, O, ldo, n, heads, Tq, Tk, st);
+        return launch_fa<DH, 1, 4>(Q, ldq, K, ldk, V, ldv, O, ldo, n, heads, Tq, Tk, st);
+    });
 }

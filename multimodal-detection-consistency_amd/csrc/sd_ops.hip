@@ -4,6 +4,7 @@
 // themselves) and every normalisation is a streaming pass; statistics and arithmetic are fp32.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -542,14 +543,12 @@ hipError_t sd_im2col3x3(const uint16_t* in, uint16_t* out, int n, int Hi, int Wi
     const int Hs = up ? 2 * Hi : Hi, Ws = up ? 2 * Wi : Wi;
     const int Ho = (Hs - 1) / stride + 1, Wo = (Ws - 1) / stride + 1;       // padding 1, kernel 3
     const int64_t total = (int64_t)n * Ho * Wo * 9 * (C >> 3);
-    hipLaunchKernelGGL(im2col3x3_kernel, dim3(grid_for(total)), dim3(256), 0, st, in, out, n, Hi, Wi, C, Ho, Wo, stride, up);
-    return hipGetLastError();
+    return launch<im2col3x3_kernel>(dim3(grid_for(total)), dim3(256), 0, st, in, out, n, Hi, Wi, C, Ho, Wo, stride, up);
 }
 
 hipError_t sd_im2col_in(const float* in, uint16_t* out, int n, int Cin, int H, int W, int Kp, float scale, hipStream_t st) {
     if (9 * Cin > Kp) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(im2col_in_kernel, dim3(grid_for((int64_t)n * H * W * Kp)), dim3(256), 0, st, in, out, n, Cin, H, W, Kp, scale);
-    return hipGetLastError();
+    return launch<im2col_in_kernel>(dim3(grid_for((int64_t)n * H * W * Kp)), dim3(256), 0, st, in, out, n, Cin, H, W, Kp, scale);
 }
 
 // ws: >= n * nslab * groups * 2 + n * groups * 2 floats (sd_groupnorm_ws_floats)
@@ -568,102 +567,87 @@ hipError_t sd_groupnorm(const uint16_t* x, const float* tadd, int64_t ld_t, cons
     float* part = ws;
     const int cv = C >> 3, Wv = cv < 256 ? cv : 256, lanes = 256 / Wv;
     const size_t lds = (size_t)lanes * C * 2 * 4;
-    hipLaunchKernelGGL(gn_partial_kernel, dim3(n * nslab), dim3(256), lds, st, x, tadd, ld_t, part, H, W, C, groups, slab, nslab, in_pad);
-    hipLaunchKernelGGL(gn_apply_kernel, dim3(n * (out_pad ? H + 2 : H)), dim3(256), 0, st, x, tadd, ld_t, part, nslab,
-                       (double)HW * (C / groups), eps, gamma, beta, y, n, H, W, C, groups, silu, in_pad, out_pad);
-    return hipGetLastError();
+    const hipError_t e = launch<gn_partial_kernel>(dim3(n * nslab), dim3(256), lds, st, x, tadd, ld_t, part, H, W, C, groups, slab, nslab,
+                                                   in_pad);
+    if (e != hipSuccess) return e;
+    return launch<gn_apply_kernel>(dim3(n * (out_pad ? H + 2 : H)), dim3(256), 0, st, x, tadd, ld_t, part, nslab,
+                                   (double)HW * (C / groups), eps, gamma, beta, y, n, H, W, C, groups, silu, in_pad, out_pad);
 }
 
 // H, W: the OUTPUT's extent (up: the input is (H / 2) x (W / 2))
 hipError_t sd_relayout(const uint16_t* in, uint16_t* out, int n, int H, int W, int C, int in_pad, int out_pad, int up, hipStream_t st) {
     if (C % 8 != 0 || (up && ((H | W) & 1))) return hipErrorInvalidValue;
     const int64_t rows = out_pad ? (int64_t)n * (H + 2) * (W + 2) : (int64_t)n * H * W;
-    hipLaunchKernelGGL(relayout_kernel, dim3(grid_for(rows * (C >> 3))), dim3(256), 0, st, in, out, n, H, W, C, in_pad, out_pad, up);
-    return hipGetLastError();
+    return launch<relayout_kernel>(dim3(grid_for(rows * (C >> 3))), dim3(256), 0, st, in, out, n, H, W, C, in_pad, out_pad, up);
 }
 
 hipError_t sd_add_padded(const uint16_t* a, const uint16_t* b_padded, uint16_t* out, int n, int H, int W, int C, hipStream_t st) {
     if (C % 8 != 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(add_padded_kernel, dim3(grid_for((int64_t)n * H * W * (C >> 3))), dim3(256), 0, st, a, b_padded, out, n, H, W, C);
-    return hipGetLastError();
+    return launch<add_padded_kernel>(dim3(grid_for((int64_t)n * H * W * (C >> 3))), dim3(256), 0, st, a, b_padded, out, n, H, W, C);
 }
 
 hipError_t sd_layernorm_bf16(const uint16_t* x, const float* g, const float* b, uint16_t* y, int64_t rows, int C, float eps,
                              hipStream_t st, const uint16_t* add, uint16_t* sum_out) {
     if (C % 8 != 0 || C > 1536 || ((add != nullptr) != (sum_out != nullptr))) return hipErrorInvalidValue;
     if (rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(ln_bf16_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, g, b, y, rows, C, eps, add, sum_out);
-    return hipGetLastError();
+    return launch<ln_bf16_kernel>(dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, g, b, y, rows, C, eps, add, sum_out);
 }
 
 hipError_t sd_geglu(const uint16_t* in, uint16_t* out, int64_t rows, int Ch, hipStream_t st) {
     if (Ch % 8 != 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(geglu_kernel, dim3(grid_for(rows * (Ch >> 3))), dim3(256), 0, st, in, out, rows, Ch);
-    return hipGetLastError();
+    return launch<geglu_kernel>(dim3(grid_for(rows * (Ch >> 3))), dim3(256), 0, st, in, out, rows, Ch);
 }
 
 hipError_t sd_add_bf16(const uint16_t* a, const uint16_t* b, uint16_t* out, int64_t n, hipStream_t st) {
     if (n % 8 != 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(add_bf16_kernel, dim3(grid_for(n >> 3)), dim3(256), 0, st, a, b, out, n >> 3);
-    return hipGetLastError();
+    return launch<add_bf16_kernel>(dim3(grid_for(n >> 3)), dim3(256), 0, st, a, b, out, n >> 3);
 }
 
 hipError_t sd_concat(const uint16_t* a, int Ca, const uint16_t* b, int Cb, uint16_t* out, int64_t tokens, hipStream_t st) {
     if (Ca % 8 != 0 || Cb % 8 != 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(concat_kernel, dim3(grid_for(tokens * ((Ca + Cb) >> 3))), dim3(256), 0, st, a, Ca, b, Cb, out, tokens);
-    return hipGetLastError();
+    return launch<concat_kernel>(dim3(grid_for(tokens * ((Ca + Cb) >> 3))), dim3(256), 0, st, a, Ca, b, Cb, out, tokens);
 }
 
 hipError_t sd_cast_silu(const float* in, uint16_t* out, int64_t n, int silu, hipStream_t st) {
-    hipLaunchKernelGGL(cast_silu_kernel, dim3(grid_for(n)), dim3(256), 0, st, in, out, n, silu);
-    return hipGetLastError();
+    return launch<cast_silu_kernel>(dim3(grid_for(n)), dim3(256), 0, st, in, out, n, silu);
 }
 
 hipError_t sd_tokens_to_nchw(const float* in, int64_t ld, float* out, int n, int C, int H, int W, float mul, float add, int clamp01,
                              int in_pad, hipStream_t st) {
-    hipLaunchKernelGGL(tokens_to_nchw_kernel, dim3(grid_for((int64_t)n * C * H * W)), dim3(256), 0, st, in, ld, out, n, C, H, W, mul,
-                       add, clamp01, in_pad);
-    return hipGetLastError();
+    return launch<tokens_to_nchw_kernel>(dim3(grid_for((int64_t)n * C * H * W)), dim3(256), 0, st, in, ld, out, n, C, H, W, mul, add,
+                                         clamp01, in_pad);
 }
 
 hipError_t sd_pointwise_small(const float* in, const float* w, const float* bias, float* out, int n, int C, int HW, float in_scale,
                               hipStream_t st) {
     if (C > 8) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(pointwise_small_kernel, dim3(grid_for((int64_t)n * C * HW)), dim3(256), 0, st, in, w, bias, out, n, C, HW,
-                       in_scale);
-    return hipGetLastError();
+    return launch<pointwise_small_kernel>(dim3(grid_for((int64_t)n * C * HW)), dim3(256), 0, st, in, w, bias, out, n, C, HW, in_scale);
 }
 
 hipError_t sd_cfg(const float* e, float* out, int64_t n, float g, hipStream_t st) {
-    hipLaunchKernelGGL(cfg_kernel, dim3(grid_for(n)), dim3(256), 0, st, e, out, n, g);
-    return hipGetLastError();
+    return launch<cfg_kernel>(dim3(grid_for(n)), dim3(256), 0, st, e, out, n, g);
 }
 
 hipError_t sd_lincomb(float* out, const float* sample, float cs, float ce, const float* e0, float c0, const float* e1, float c1,
                       const float* e2, float c2, const float* e3, float c3, int64_t n, hipStream_t st) {
-    hipLaunchKernelGGL(lincomb_kernel, dim3(grid_for(n)), dim3(256), 0, st, out, sample, cs, ce, e0, c0, e1, c1, e2, c2, e3, c3, n);
-    return hipGetLastError();
+    return launch<lincomb_kernel>(dim3(grid_for(n)), dim3(256), 0, st, out, sample, cs, ce, e0, c0, e1, c1, e2, c2, e3, c3, n);
 }
 
 hipError_t sd_softmax_rows(const float* s, uint16_t* p, int64_t rows, int T, float scale, hipStream_t st) {
     if (rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)rows), dim3(256), 0, st, s, p, T, scale);
-    return hipGetLastError();
+    return launch<softmax_rows_kernel>(dim3((unsigned)rows), dim3(256), 0, st, s, p, T, scale);
 }
 
 hipError_t sd_nchw_to_tokens(const float* in, uint16_t* out, int n, int C, int HW, hipStream_t st) {
-    hipLaunchKernelGGL(nchw_to_tokens_kernel, dim3(grid_for((int64_t)n * C * HW)), dim3(256), 0, st, in, out, n, C, HW);
-    return hipGetLastError();
+    return launch<nchw_to_tokens_kernel>(dim3(grid_for((int64_t)n * C * HW)), dim3(256), 0, st, in, out, n, C, HW);
 }
 
 hipError_t sd_tokens_bf16_to_nchw(const uint16_t* in, float* out, int n, int C, int HW, hipStream_t st) {
-    hipLaunchKernelGGL(tokens_bf16_to_nchw_kernel, dim3(grid_for((int64_t)n * C * HW)), dim3(256), 0, st, in, out, n, C, HW);
-    return hipGetLastError();
+    return launch<tokens_bf16_to_nchw_kernel>(dim3(grid_for((int64_t)n * C * HW)), dim3(256), 0, st, in, out, n, C, HW);
 }
 
 hipError_t sd_timestep_embed(uint16_t* out, int n, int dim, float t, hipStream_t st) {
-    hipLaunchKernelGGL(timestep_embed_kernel, dim3(grid_for((int64_t)n * dim)), dim3(256), 0, st, out, n, dim, t);
-    return hipGetLastError();
+    return launch<timestep_embed_kernel>(dim3(grid_for((int64_t)n * dim)), dim3(256), 0, st, out, n, dim, t);
 }
 
 // in fp32 [n, 3, H, W] -> out fp32 [n, 3, S, S]: resize to (Hr, Wr), crop at (oy, ox), (v - mean) / std; cubic: bicubic else bilinear
@@ -672,11 +656,8 @@ hipError_t sd_resize_norm(const float* in, float* out, int n, int H, int W, int 
     if (n <= 0) return hipSuccess;
     if (H < 1 || W < 1 || Hr < S || Wr < S || oy < 0 || ox < 0 || oy + S > Hr || ox + S > Wr) return hipErrorInvalidValue;
     const int64_t total = (int64_t)n * 3 * S * S;
-    if (cubic)
-        hipLaunchKernelGGL(resize_norm_kernel<1>, dim3(grid_for(total)), dim3(256), 0, st, in, out, n, H, W, Hr, Wr, oy, ox, S, mean[0],
-                           mean[1], mean[2], sd[0], sd[1], sd[2]);
-    else
-        hipLaunchKernelGGL(resize_norm_kernel<0>, dim3(grid_for(total)), dim3(256), 0, st, in, out, n, H, W, Hr, Wr, oy, ox, S, mean[0],
-                           mean[1], mean[2], sd[0], sd[1], sd[2]);
-    return hipGetLastError();
+    return dispatch<1, 0>(cubic ? 1 : 0, [&](auto c) {
+        return launch<resize_norm_kernel<c.value>>(dim3(grid_for(total)), dim3(256), 0, st, in, out, n, H, W, Hr, Wr, oy, ox, S, mean[0],
+                                                   mean[1], mean[2], sd[0], sd[1], sd[2]);
+    });
 }

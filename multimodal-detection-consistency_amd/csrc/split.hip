@@ -9,7 +9,7 @@
 // ring kernel as the bf16 mode with planes = 3.
 #include "common.hpp"
 #include "kernels.hpp"
-#include <mutex>
+#include "launch.hpp"
 
 namespace {
 
@@ -301,18 +301,9 @@ hipError_t launch_split_one(const float* qkv, uint16_t* out, const int32_t* star
                             hipStream_t stream, const int32_t* pfx) {
     const int kt = (T + 15) / 16 * 16;
     const size_t lds = (size_t)kt * (2 * SA_KROW + 2 * SA_VROW);
-    static std::once_flag once;
-    static hipError_t attr_st = hipSuccess;
-    std::call_once(once, [] {
-        attr_st = hipFuncSetAttribute((const void*)attention_split_kernel<MAXT, CAUSAL>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      160 * 1024);
-    });
-    if (attr_st != hipSuccess) return attr_st;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
     const int n_items = n_seq * heads;
-    hipLaunchKernelGGL((attention_split_kernel<MAXT, CAUSAL>), dim3(n_items), dim3(256), lds, stream, qkv, out, starts, T, heads,
-                       n_items, kt, pfx, n_seq);
-    return hipGetLastError();
+    return launch<attention_split_kernel<MAXT, CAUSAL>, 160 * 1024>(dim3(n_items), dim3(256), lds, stream, qkv, out, starts, T, heads,
+                                                                    n_items, kt, pfx, n_seq);
 }
 
 }  // namespace
@@ -321,9 +312,8 @@ hipError_t launch_ln_split(float* x, int64_t x_row_stride, const int32_t* row_id
                            const float* g, const float* b, uint16_t* planes, float* y32, int rows, int d, hipStream_t stream) {
     if (d % 4 != 0 || d > 1024 || rows < 0 || (!planes && !y32)) return hipErrorInvalidValue;
     if (rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(ln_split_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, x, x_row_stride, row_idx, d1, d2, write_x, g, b,
-                       planes, y32, rows, d);
-    return hipGetLastError();
+    return launch<ln_split_kernel>(dim3((rows + 3) / 4), dim3(256), 0, stream, x, x_row_stride, row_idx, d1, d2, write_x, g, b, planes,
+                                   y32, rows, d);
 }
 
 hipError_t launch_rows_split(const float* x, int64_t ld_in, uint16_t* out, int64_t rows, int K, int Kp, int gelu, hipStream_t stream) {
@@ -331,8 +321,7 @@ hipError_t launch_rows_split(const float* x, int64_t ld_in, uint16_t* out, int64
     if (rows == 0) return hipSuccess;
     const int64_t total = rows * (Kp >> 2);
     int grid = (int)((total + 255) / 256 < 32768 ? (total + 255) / 256 : 32768);
-    hipLaunchKernelGGL(rows_split_kernel, dim3(grid), dim3(256), 0, stream, x, ld_in, out, rows, K, Kp, gelu);
-    return hipGetLastError();
+    return launch<rows_split_kernel>(dim3(grid), dim3(256), 0, stream, x, ld_in, out, rows, K, Kp, gelu);
 }
 
 // starts == nullptr: n_seq sequences of seq_len rows; else packed rows (+ pfx: shared prefixes), seq_len = the maximum

@@ -78,11 +78,9 @@ int run_layers(tvc_handle* h, const tvc_tower_arch& a, const tvc_layer_weights* 
             QKV = gs->qkv + (size_t)l * rows * 3 * d;
             D1 = gs->d1 + (size_t)l * rows * d;
         }
-        GemmLaunch g;
-        g.A = w.wqkv; g.lda = d; g.I = 3 * d; g.B = H; g.ldb = d; g.J = rows; g.K = d;
-        g.bias = w.bqkv; g.out = QKV; g.ldo = 3 * d; g.epilogue = TVC_EPI_BF16; g.b_rows_padded = true;
+        GemmLaunch g = gemm_launch(w.wqkv, d, 3 * d, H, d, rows, d, w.bqkv, QKV, 3 * d, TVC_EPI_BF16);
+        g.b_rows_padded = true; g.f16 = f16;
         g.splitk_small = gs != nullptr;            // gradient mode only (see tvc_encode_image_backward)
-        g.f16 = f16;
         HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
         if (pool_mode && l == a.layers - 1) {
             const PoolBufs pb = pool_bufs(h, a, n_seq, wso);
@@ -91,22 +89,19 @@ int run_layers(tvc_handle* h, const tvc_tower_arch& a, const tvc_layer_weights* 
                 ProfScope ps(h, st, TVC_PROF_ATTENTION, 4.0 * n_seq * a.heads * avg_len * 64);
                 HIP_TRY(launch_attention(QKV, pb.Hc, starts, n_seq, seq_len, a.heads, causal, st, pfx, pool_mode, pool_row, f16));
             }
-            g = GemmLaunch();
-            g.A = w.wo; g.lda = d; g.I = d; g.B = pb.Hc; g.ldb = d; g.J = n_seq; g.K = d;
-            g.bias = w.bo; g.out = pb.D1c; g.ldo = d; g.epilogue = TVC_EPI_BF16; g.b_rows_padded = true; g.f16 = f16;
+            g = gemm_launch(w.wo, d, d, pb.Hc, d, n_seq, d, w.bo, pb.D1c, d, TVC_EPI_BF16);
+            g.b_rows_padded = true; g.f16 = f16;
             HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
             HIP_TRY(launch_layernorm(X, pool_row ? d : pool_x_stride, pool_row, pb.D1c, 0, w.ln2_g, w.ln2_b, pb.H2c, n_seq, d,
                                      st, nullptr, 1, nullptr, nullptr, f16));
-            g = GemmLaunch();
-            g.A = w.w1; g.lda = d; g.I = a.mlp; g.B = pb.H2c; g.ldb = d; g.J = n_seq; g.K = d;
-            g.bias = w.b1; g.out = pb.MLPc; g.ldo = a.mlp; g.b_rows_padded = true;
-            g.epilogue = a.act == TVC_ACT_GELU ? TVC_EPI_BF16 : TVC_EPI_GELU_BF16; g.f16 = f16;
+            g = gemm_launch(w.w1, d, a.mlp, pb.H2c, d, n_seq, d, w.b1, pb.MLPc, a.mlp,
+                            a.act == TVC_ACT_GELU ? TVC_EPI_BF16 : TVC_EPI_GELU_BF16);
+            g.b_rows_padded = true; g.f16 = f16;
             HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
             if (a.act == TVC_ACT_GELU)
                 HIP_TRY(f16 ? launch_gelu_erf_f16(pb.MLPc, (int64_t)n_seq * a.mlp, st) : launch_gelu_erf_bf16(pb.MLPc, (int64_t)n_seq * a.mlp, st));
-            g = GemmLaunch();
-            g.A = w.w2; g.lda = a.mlp; g.I = d; g.B = pb.MLPc; g.ldb = a.mlp; g.J = n_seq; g.K = a.mlp;
-            g.bias = w.b2; g.out = pb.D2c; g.ldo = d; g.epilogue = TVC_EPI_BF16; g.b_rows_padded = true; g.f16 = f16;
+            g = gemm_launch(w.w2, a.mlp, d, pb.MLPc, a.mlp, n_seq, a.mlp, w.b2, pb.D2c, d, TVC_EPI_BF16);
+            g.b_rows_padded = true; g.f16 = f16;
             HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
             return TVC_OK;
         }
@@ -116,42 +111,27 @@ int run_layers(tvc_handle* h, const tvc_tower_arch& a, const tvc_layer_weights* 
             ProfScope ps(h, st, TVC_PROF_ATTENTION, fl);
             HIP_TRY(launch_attention(QKV, H, starts, n_seq, seq_len, a.heads, causal, st, pfx, 0, nullptr, f16));
         }
-        g = GemmLaunch();
-        g.A = w.wo; g.lda = d; g.I = d; g.B = H; g.ldb = d; g.J = rows; g.K = d;
-        g.bias = w.bo; g.out = D1; g.ldo = d; g.epilogue = TVC_EPI_BF16; g.b_rows_padded = true;
-        g.splitk_small = gs != nullptr;
-        g.f16 = f16;
+        g = gemm_launch(w.wo, d, d, H, d, rows, d, w.bo, D1, d, TVC_EPI_BF16);
+        g.b_rows_padded = true; g.f16 = f16; g.splitk_small = gs != nullptr;
         HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
         {
             ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)rows * d * 8.0);
             HIP_TRY(launch_layernorm(X, d, nullptr, D1, 0, w.ln2_g, w.ln2_b, H, rows, d, st, nullptr, 0, nullptr, nullptr, f16));
         }
-        g = GemmLaunch();
-        g.A = w.w1; g.lda = d; g.I = a.mlp; g.B = H; g.ldb = d; g.J = rows; g.K = d;
-        g.bias = w.b1; g.b_rows_padded = true; g.ldo = a.mlp;
-        g.splitk_small = gs != nullptr;
-        g.f16 = f16;
+        // FC1 fuses QuickGELU into its epilogue.  Gradient mode keeps the pre-activation U (what gelu' needs) and erf GELU (the
+        // SD-2.x text encoder) has no fused form: both store only, the activation is one streaming pass after the GEMM
+        uint16_t* U = gs ? gs->u + (size_t)l * rows * a.mlp : MLP;
+        g = gemm_launch(w.w1, d, a.mlp, H, d, rows, d, w.b1, U, a.mlp, gs || a.act == TVC_ACT_GELU ? TVC_EPI_BF16 : TVC_EPI_GELU_BF16);
+        g.b_rows_padded = true; g.f16 = f16; g.splitk_small = gs != nullptr;
+        HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
         if (gs) {
-            // keep the pre-activation (what gelu' needs); the activation is one streaming pass over it
-            uint16_t* U = gs->u + (size_t)l * rows * a.mlp;
-            g.out = U; g.epilogue = TVC_EPI_BF16;
-            HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
             HIP_TRY(launch_gelu_fwd(U, MLP, (int64_t)rows * a.mlp, st));
         } else if (a.act == TVC_ACT_GELU) {
-            // erf GELU (the SD-2.x text encoder): store-only FC1, the activation as a streaming pass in place
-            g.out = MLP; g.epilogue = TVC_EPI_BF16;
-            HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
             ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)rows * a.mlp * 4.0);
             HIP_TRY(f16 ? launch_gelu_erf_f16(MLP, (int64_t)rows * a.mlp, st) : launch_gelu_erf_bf16(MLP, (int64_t)rows * a.mlp, st));
-        } else {
-            g.out = MLP; g.epilogue = TVC_EPI_GELU_BF16;
-            HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
         }
-        g = GemmLaunch();
-        g.A = w.w2; g.lda = a.mlp; g.I = d; g.B = MLP; g.ldb = a.mlp; g.J = rows; g.K = a.mlp;
-        g.bias = w.b2; g.out = D2; g.ldo = d; g.epilogue = TVC_EPI_BF16; g.b_rows_padded = true;
-        g.splitk_small = gs != nullptr;
-        g.f16 = f16;
+        g = gemm_launch(w.w2, a.mlp, d, MLP, a.mlp, rows, a.mlp, w.b2, D2, d, TVC_EPI_BF16);
+        g.b_rows_padded = true; g.f16 = f16; g.splitk_small = gs != nullptr;
         HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
         pending = true;
     }
@@ -186,9 +166,8 @@ int patch_stem(tvc_handle* h, const char* fn, const float* pix, int n, bool f16,
     float* po = (float*)h->ws[WS_MLP].p;    // [n*P, d] fp32 fits: mlp >= 2*d
     if ((size_t)n * P * d * 4 > h->ws[WS_MLP].n) return fail(h, TVC_E_INVALID, std::string(fn) + ": mlp < 2*width unsupported");
     HIP_TRY(launch_im2col(pix, Pm, n, m.image_size, m.patch, Kp, st, f16));
-    GemmLaunch g;
-    g.A = (f16 ? h->vision16 : h->vision).w.patch_w; g.lda = Kp; g.I = d; g.B = Pm; g.ldb = Kp; g.J = n * P; g.K = Kp;
-    g.out = po; g.ldo = d; g.epilogue = TVC_EPI_F32; g.b_rows_padded = true; g.f16 = f16;
+    GemmLaunch g = gemm_launch((f16 ? h->vision16 : h->vision).w.patch_w, Kp, d, Pm, Kp, n * P, Kp, nullptr, po, d, TVC_EPI_F32);
+    g.b_rows_padded = true; g.f16 = f16;
     HIP_TRY(timed_gemm(h, g, st, WS_SPLITK));
     *patch_out = po;
     return TVC_OK;
@@ -259,9 +238,8 @@ int tower_head(tvc_handle* h, bool text, int64_t x_stride, const int32_t* row_id
                              pool ? pb.D2c : (const uint16_t*)h->ws[WS_DELTA2 + wso].p, pool ? 1 : 0, nullptr,
                              hidden ? out : nullptr, f16));
     if (hidden) return TVC_OK;
-    GemmLaunch g;
-    g.A = text ? tw.proj : vw.proj; g.lda = d; g.I = m.embed_dim; g.B = Hc; g.ldb = d; g.J = rows; g.K = d;
-    g.out = out; g.ldo = m.embed_dim; g.epilogue = TVC_EPI_F32; g.f16 = f16;
+    GemmLaunch g = gemm_launch(text ? tw.proj : vw.proj, d, m.embed_dim, Hc, d, rows, d, nullptr, out, m.embed_dim, TVC_EPI_F32);
+    g.f16 = f16;
     HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
     return TVC_OK;
 }
@@ -614,12 +592,7 @@ int tvc_cosine_matrix(tvc_handle* h, const float* x_dev, int32_t N, const float*
     HIP_TRY(launch_split_planes(xn, xp, N, D, 2, st));
     HIP_TRY(launch_split_planes(yn, yp, M, D, 2, st));
     // out[n, m]: "A rows" (fast output dim) = y, "B rows" = x; hi.hi + hi.lo + lo.hi
-    GemmLaunch g;
-    g.A = yp; g.lda = 2 * (int64_t)D; g.I = M; g.B = xp; g.ldb = 2 * (int64_t)D; g.J = N; g.K = D; g.planes = 3;
-    g.a_plane_off[0] = 0; g.a_plane_off[1] = 0; g.a_plane_off[2] = D;
-    g.b_plane_off[0] = 0; g.b_plane_off[1] = D; g.b_plane_off[2] = 0;
-    g.out = out_dev; g.ldo = M; g.epilogue = TVC_EPI_F32;
-    HIP_TRY(timed_gemm(h, g, st));
+    HIP_TRY(timed_gemm(h, gemm_launch_planes(yp, 2 * (int64_t)D, M, 2, xp, N, D, out_dev, M), st));
     return TVC_OK;
 }
 
@@ -710,10 +683,8 @@ int tvc_encode_image_grad(tvc_handle* h, const float* pix_dev, int32_t B, float*
     HIP_TRY(launch_layernorm((float*)h->ws[WS_X].p, (int64_t)T * d, nullptr, gs.d1 + (size_t)(a.layers - 1) * rows * d, 0,
                              vw.ln_post_g, vw.ln_post_b, Hc, B, d, st, (const uint16_t*)h->ws[WS_DELTA2].p, 0,
                              (float*)h->ws[WS_GXL].p));
-    GemmLaunch g;
-    g.A = vw.proj; g.lda = d; g.I = m.embed_dim; g.B = Hc; g.ldb = d; g.J = B; g.K = d;
-    g.out = h->ws[WS_GOUT].p; g.ldo = m.embed_dim; g.epilogue = TVC_EPI_F32;
-    HIP_TRY(timed_gemm(h, g, st, WS_SPLITK));
+    HIP_TRY(timed_gemm(h, gemm_launch(vw.proj, d, m.embed_dim, Hc, d, B, d, nullptr, h->ws[WS_GOUT].p, m.embed_dim, TVC_EPI_F32), st,
+                       WS_SPLITK));
     HIP_TRY(hipMemcpyAsync(out_dev, h->ws[WS_GOUT].p, (size_t)B * m.embed_dim * 4, hipMemcpyDeviceToDevice, st));
     if (normalize) HIP_TRY(launch_l2norm_rows(out_dev, B, m.embed_dim, st));
     h->grad_B = B; h->grad_normalize = normalize; h->grad_pix = pix_dev;
@@ -748,9 +719,8 @@ int tvc_encode_image_backward(tvc_handle* h, const float* grad_out_dev, float* g
     uint16_t* dQKV = (uint16_t*)h->ws[WS_GDQKV].p;
     auto gemm = [&](const void* A, int64_t lda, int I, const uint16_t* Bm, int64_t ldb, int J, int K, void* out, int64_t ldo,
                     int epi) -> int {
-        GemmLaunch g;
-        g.A = (const uint16_t*)A; g.lda = lda; g.I = I; g.B = Bm; g.ldb = ldb; g.J = J; g.K = K;
-        g.out = out; g.ldo = ldo; g.epilogue = epi; g.b_rows_padded = true;
+        GemmLaunch g = gemm_launch((const uint16_t*)A, lda, I, Bm, ldb, J, K, nullptr, out, ldo, epi);
+        g.b_rows_padded = true;
         // the gradient path promises no batch-position invariance of its last bits: a partial last round of tiles (FC1-shaped
         // GEMMs at 32 images: 528 tiles = 2 rounds + 16 tiles) is split over K instead of taking a third round
         g.splitk_small = true;
@@ -932,9 +902,8 @@ int gemm16(tvc_handle* h, const char* name, bool f16, const uint16_t* a_dev, con
         return fail(h, TVC_E_INVALID, std::string(name) + ": a, b, out and bias must be 16-byte aligned");
     if (lda >= ((int64_t)1 << 23) || ldb >= ((int64_t)1 << 23))
         return fail(h, TVC_E_INVALID, std::string(name) + ": lda / ldb must be below 2^23");
-    GemmLaunch g;
-    g.A = a_dev; g.lda = lda; g.I = I; g.B = b_dev; g.ldb = ldb; g.J = J; g.K = K;
-    g.bias = bias_dev; g.out = out_dev; g.ldo = ld_out; g.epilogue = epilogue; g.f16 = f16;
+    GemmLaunch g = gemm_launch(a_dev, lda, I, b_dev, ldb, J, K, bias_dev, out_dev, ld_out, epilogue);
+    g.f16 = f16;
     {
         int rc = ensure(h, WS_SPLITK, (size_t)256 * 256 * 256 * 4);       // split-K scratch (small or tail tiles)
         if (rc) return rc;

@@ -163,9 +163,8 @@ struct Run {
     // rows_per_sample: B rows of ONE sample (what the K split is chosen from)
     void gemm(const void* A, int I, int K, const uint16_t* B, int64_t J, const float* bias, void* out, int64_t ldo, int epi,
               int64_t rows_per_sample) {
-        GemmLaunch g;
-        g.A = (const uint16_t*)A; g.lda = K; g.I = I; g.B = B; g.ldb = K; g.J = (int)J; g.K = K;
-        g.bias = bias; g.out = out; g.ldo = ldo; g.epilogue = epi; g.b_rows_padded = true;
+        GemmLaunch g = gemm_launch((const uint16_t*)A, K, I, B, K, (int)J, K, bias, out, ldo, epi);
+        g.b_rows_padded = true;
         g.a_rows_padded = true;            // tvc_sd_load's contract: GEMM weights are readable to the next multiple of 256 rows
         // the 16 x 16 / 8 x 8 levels and the time / text projections are a few tiles with a long K: split it over the idle CUs
         launch_fixed(g, rows_per_sample, "sd gemm");
@@ -188,13 +187,13 @@ struct Run {
         const void* w = W(prefix + "weight");
         const float* b = (const float*)W(prefix + "bias");
         const int Wp = xp.W + 2;
-        GemmLaunch g;
-        g.A = (const uint16_t*)w; g.lda = 9 * (int64_t)xp.C; g.I = Cout; g.B = xp.p; g.ldb = xp.C;
-        g.J = (int)(xp.rows() - 2 * (Wp + 1)); g.K = xp.C; g.planes = 9;
+        char* base = out_f32 ? (char*)of : (char*)y.p;          // nullptr in a dry pass
+        void* out = base ? base + (size_t)(Wp + 1) * Cout * (out_f32 ? 4 : 2) : nullptr;
+        GemmLaunch g = gemm_launch((const uint16_t*)w, 9 * (int64_t)xp.C, Cout, xp.p, xp.C, (int)(xp.rows() - 2 * (Wp + 1)), xp.C, b, out,
+                                   Cout, out_f32 ? TVC_EPI_F32 : TVC_EPI_BF16);
+        g.planes = 9;
         for (int t = 0; t < 9; ++t) { g.a_plane_off[t] = t * xp.C; g.b_plane_off[t] = ((t / 3) * Wp + t % 3) * xp.C; }
-        g.bias = b; g.ldo = Cout; g.b_rows_padded = true; g.a_rows_padded = true;
-        if (out_f32) { g.out = of ? of + (size_t)(Wp + 1) * Cout : nullptr; g.epilogue = TVC_EPI_F32; }
-        else { g.out = y.p ? y.p + (size_t)(Wp + 1) * Cout : nullptr; g.epilogue = TVC_EPI_BF16; }
+        g.b_rows_padded = true; g.a_rows_padded = true;
         launch_fixed(g, (int64_t)(xp.H + 2) * Wp, "sd conv gemm");
         return y;
     }

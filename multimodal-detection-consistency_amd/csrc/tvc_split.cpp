@@ -36,13 +36,11 @@ SBufs split_bufs(tvc_handle* h, bool text) {
 // out fp32 [J, ldo] = (W_hi + W_lo)[I, K] x (B_hi + B_lo)[J, K]^T + bias, without the lo x lo term
 int gemm3(tvc_handle* h, const uint16_t* Ws, int I, int K, const uint16_t* Bs, int64_t J, const float* bias, float* out, int64_t ldo,
           hipStream_t st) {
-    GemmLaunch g;
-    g.A = Ws; g.lda = 2 * (int64_t)K; g.I = I; g.B = Bs; g.ldb = 2 * (int64_t)K; g.J = (int)J; g.K = K;
+    GemmLaunch g = gemm_launch(Ws, 2 * (int64_t)K, I, Bs, 2 * (int64_t)K, (int)J, K, bias, out, ldo, TVC_EPI_F32);
     g.planes = 3;                                       // small terms first, the hi x hi products last
     g.a_plane_off[0] = 0; g.b_plane_off[0] = K;         // A_hi x B_lo
     g.a_plane_off[1] = K; g.b_plane_off[1] = 0;         // A_lo x B_hi
     g.a_plane_off[2] = 0; g.b_plane_off[2] = 0;         // A_hi x B_hi
-    g.bias = bias; g.out = out; g.ldo = ldo; g.epilogue = TVC_EPI_F32;
     g.a_rows_padded = true; g.b_rows_padded = true;     // split weights / workspaces are allocated to whole tiles
     HIP_TRY(timed_gemm(h, g, st));
     return TVC_OK;

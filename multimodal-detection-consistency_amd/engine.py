@@ -520,72 +520,53 @@ class TVCEngine:
         return self.consistency(img, txt, cfg)
 
     # ---- building blocks (parity tests / profiling) ----------------------
+    def _gemm16(self, dt: torch.dtype, fn, a, b, bias, epilogue, out, k) -> torch.Tensor:
+        a = _require_cuda(a, dt, "a")
+        b = _require_cuda(b, dt, "b")
+        I, lda = a.shape
+        J, ldb = b.shape
+        K = k if k is not None else lda
+        if k is None and lda != ldb:
+            raise ValueError("a and b must have the same number of columns (or pass k)")
+        odt = torch.float32 if epilogue in (0, 3) else dt
+        if out is None:
+            out = torch.empty((J, I), dtype=odt, device=self.device)
+            if epilogue == 3:
+                out.zero_()
+        ld_out = _check_out(out, J, I, odt)
+        if bias is not None:
+            bias = _require_cuda(bias, torch.float32, "bias")
+        with self._lock, torch.cuda.device(self.device):
+            self._check(fn(self.handle, _ptr(a), _ptr(b), _ptr(bias), _ptr(out), I, J, K, lda, ldb, ld_out, epilogue, _stream()))
+        return out
+
     def gemm(self, a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: int = 0,
              out: Optional[torch.Tensor] = None, k: Optional[int] = None) -> torch.Tensor:
         """out[j, i] = sum_k a[i, k] b[j, k] (+ bias[i]); a, b bf16.  ``k``: multiply only the first k columns
         (the operands' row strides stay their full widths: padded leading dimensions)."""
-        a = _require_cuda(a, torch.bfloat16, "a")
-        b = _require_cuda(b, torch.bfloat16, "b")
-        I, lda = a.shape
-        J, ldb = b.shape
-        K = k if k is not None else lda
-        if k is None and lda != ldb:
-            raise ValueError("a and b must have the same number of columns (or pass k)")
-        odt = torch.float32 if epilogue in (0, 3) else torch.bfloat16
-        if out is None:
-            out = torch.empty((J, I), dtype=odt, device=self.device)
-            if epilogue == 3:
-                out.zero_()
-        ld_out = _check_out(out, J, I, odt)
-        if bias is not None:
-            bias = _require_cuda(bias, torch.float32, "bias")
-        with self._lock, torch.cuda.device(self.device):
-            self._check(self.lib.tvc_gemm_bf16(self.handle, _ptr(a), _ptr(b), _ptr(bias), _ptr(out), I, J, K, lda, ldb,
-                                               ld_out, epilogue, _stream()))
-        return out
-
-    def attention(self, qkv: torch.Tensor, n_seq: int, seq_len: int, heads: int, causal: bool) -> torch.Tensor:
-        qkv = _require_cuda(qkv, torch.bfloat16, "qkv")
-        out = torch.empty((qkv.shape[0], heads * 64), dtype=torch.bfloat16, device=self.device)
-        with self._lock, torch.cuda.device(self.device):
-            self._check(self.lib.tvc_attention(self.handle, _ptr(qkv), _ptr(out), n_seq, seq_len, heads,
-                                               int(causal), _stream()))
-        return out
+        return self._gemm16(torch.bfloat16, self.lib.tvc_gemm_bf16, a, b, bias, epilogue, out, k)
 
     def gemm_f16(self, a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: int = 0,
                  out: Optional[torch.Tensor] = None, k: Optional[int] = None) -> torch.Tensor:
         """fp16 twin of :meth:`gemm` (tower mode 3): a, b fp16 on the f16 MFMA; epilogues 1 / 2 store fp16."""
-        a = _require_cuda(a, torch.float16, "a")
-        b = _require_cuda(b, torch.float16, "b")
-        I, lda = a.shape
-        J, ldb = b.shape
-        K = k if k is not None else lda
-        if k is None and lda != ldb:
-            raise ValueError("a and b must have the same number of columns (or pass k)")
-        odt = torch.float32 if epilogue in (0, 3) else torch.float16
-        if out is None:
-            out = torch.empty((J, I), dtype=odt, device=self.device)
-            if epilogue == 3:
-                out.zero_()
-        ld_out = _check_out(out, J, I, odt)
-        if bias is not None:
-            bias = _require_cuda(bias, torch.float32, "bias")
+        return self._gemm16(torch.float16, self.lib.tvc_gemm_f16, a, b, bias, epilogue, out, k)
+
+    def _attention16(self, dt: torch.dtype, fn, qkv, n_seq, seq_len, heads, causal, *starts) -> torch.Tensor:
+        # starts: given (a tensor or None) only for an entry point that takes the argument
+        qkv = _require_cuda(qkv, dt, "qkv")
+        out = torch.empty((qkv.shape[0], heads * 64), dtype=dt, device=self.device)
+        starts = [s if s is None else _require_cuda(s, torch.int32, "starts") for s in starts]
         with self._lock, torch.cuda.device(self.device):
-            self._check(self.lib.tvc_gemm_f16(self.handle, _ptr(a), _ptr(b), _ptr(bias), _ptr(out), I, J, K, lda, ldb,
-                                              ld_out, epilogue, _stream()))
+            self._check(fn(self.handle, _ptr(qkv), _ptr(out), *map(_ptr, starts), n_seq, seq_len, heads, int(causal), _stream()))
         return out
+
+    def attention(self, qkv: torch.Tensor, n_seq: int, seq_len: int, heads: int, causal: bool) -> torch.Tensor:
+        return self._attention16(torch.bfloat16, self.lib.tvc_attention, qkv, n_seq, seq_len, heads, causal)
 
     def attention_f16(self, qkv: torch.Tensor, n_seq: int, seq_len: int, heads: int, causal: bool,
                       starts: Optional[torch.Tensor] = None) -> torch.Tensor:
         """fp16 twin of :meth:`attention`; ``starts`` (int32 [n_seq + 1]): packed sequences of at most seq_len rows."""
-        qkv = _require_cuda(qkv, torch.float16, "qkv")
-        out = torch.empty((qkv.shape[0], heads * 64), dtype=torch.float16, device=self.device)
-        if starts is not None:
-            starts = _require_cuda(starts, torch.int32, "starts")
-        with self._lock, torch.cuda.device(self.device):
-            self._check(self.lib.tvc_attention_f16(self.handle, _ptr(qkv), _ptr(out), _ptr(starts), n_seq, seq_len, heads,
-                                                   int(causal), _stream()))
-        return out
+        return self._attention16(torch.float16, self.lib.tvc_attention_f16, qkv, n_seq, seq_len, heads, causal, starts)
 
     def attention_backward(self, qkv: torch.Tensor, dout: torch.Tensor, n_seq: int, seq_len: int, heads: int) -> torch.Tensor:
         qkv = _require_cuda(qkv, torch.bfloat16, "qkv")
@@ -677,25 +658,20 @@ class TVCEngine:
                                                      int(causal), _stream()))
         return planes[:, :w].float() + planes[:, w:].float()
 
-    def layernorm(self, x: torch.Tensor, g: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    def _layernorm16(self, dt: torch.dtype, fn, x, g, b) -> torch.Tensor:
         x = _require_cuda(x, torch.float32, "x")
         g = _require_cuda(g, torch.float32, "g")
         b = _require_cuda(b, torch.float32, "b")
-        out = torch.empty(x.shape, dtype=torch.bfloat16, device=self.device)
+        out = torch.empty(x.shape, dtype=dt, device=self.device)
         with self._lock, torch.cuda.device(self.device):
-            self._check(self.lib.tvc_layernorm(self.handle, _ptr(x), _ptr(g), _ptr(b), _ptr(out), x.shape[0],
-                                               x.shape[1], _stream()))
+            self._check(fn(self.handle, _ptr(x), _ptr(g), _ptr(b), _ptr(out), x.shape[0], x.shape[1], _stream()))
         return out
 
+    def layernorm(self, x: torch.Tensor, g: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+        return self._layernorm16(torch.bfloat16, self.lib.tvc_layernorm, x, g, b)
+
     def layernorm_f16(self, x: torch.Tensor, g: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-        x = _require_cuda(x, torch.float32, "x")
-        g = _require_cuda(g, torch.float32, "g")
-        b = _require_cuda(b, torch.float32, "b")
-        out = torch.empty(x.shape, dtype=torch.float16, device=self.device)
-        with self._lock, torch.cuda.device(self.device):
-            self._check(self.lib.tvc_layernorm_f16(self.handle, _ptr(x), _ptr(g), _ptr(b), _ptr(out), x.shape[0],
-                                                   x.shape[1], _stream()))
-        return out
+        return self._layernorm16(torch.float16, self.lib.tvc_layernorm_f16, x, g, b)
 
     PROF_CATEGORIES = ("gemm", "attention", "bank", "rowops")
 
