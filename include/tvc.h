@@ -392,6 +392,15 @@ static inline int32_t tvc_rec_stride(int32_t N) { return TVC_REC_HEAD + N + 2 * 
  * ref_idx/ref_sim [B*(N+1), ks] = bank search results of the text rows
  * (global indices), ref_feat fp32 [B*(N+1), kf, D] = rows of the first kf
  * (>= reference_count) results; pass ks = 0 / NULLs for "no bank".
+ * To reproduce the reference's sort / filter / slice (retrieval_ref.py:206-216)
+ * each ref_sim row must be non-increasing over its entries with ref_idx >= 0,
+ * as tvc_bank_search and tvc_topk_merge return it.  The kernel does not sort: it
+ * looks at the first min(reference_count, ks, kf) entries of each row, in order,
+ * and keeps those with ref_idx >= 0 and ref_sim >= similarity_threshold; later
+ * entries are never read, whatever their similarity.
+ * Limits (TVC_E_INVALID otherwise, nothing is launched): N + 1 <= 40,
+ * (N + 1) * reference_count <= 320, 0 <= retrieval_top_k <= 16, and ks > 0
+ * needs all three ref_* buffers and kf >= 1.
  * rec_dev fp32 [B, tvc_rec_stride(N)].
  * Replaces src/detector.py:461-485,573-579,643-682 and
  * experiments/defenses/detector.py:184-204,228-300,302-325. */
