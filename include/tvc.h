@@ -458,6 +458,20 @@ int tvc_attention_f16(tvc_handle* h, const uint16_t* qkv_dev, uint16_t* out_dev,
 int tvc_layernorm_f16(tvc_handle* h, const float* x_dev, const float* g_dev, const float* b_dev,
                       uint16_t* y_dev, int32_t rows, int32_t d, void* stream);
 
+/* The tower attention kernel with every launch option (parity tests): qkv / out bf16, or IEEE fp16 when f16 != 0.
+ * starts_dev: int32 [n_seq + 1] = packed sequences of at most seq_len rows, or NULL = n_seq x seq_len dense rows.
+ * pfx_dev (optional, causal packed rows only), int32 [2 * n_seq]: sequence s = pfx[s] rows starting at packed row
+ * pfx[n_seq + s] (shared prefix, keys only) followed by its own rows [starts[s], starts[s+1]) (keys + queries); pfx[s] is
+ * the prefix length, pfx[n_seq + s] the packed row of the prefix's position 0, and seq_len bounds prefix + own rows.
+ * pool_mode 0: out [rows, width], every own row's output.  1 / 2: only the pooled token's output per sequence (1 = its
+ * first token, 2 = its EOT token: the last packed row, or packed row pool_row_dev[s] (int32 [n_seq]) for dense rows),
+ * written to the compact row s of out [n_seq, width].
+ * Returns TVC_E_INVALID and launches nothing for: pfx without starts or without causal, pool_mode 2 on dense rows without
+ * pool_row, pool_mode outside 0..2, seq_len outside 1..288, heads < 1, NULL qkv / out. */
+int tvc_attention_ex(tvc_handle* h, const uint16_t* qkv_dev, uint16_t* out_dev, const int32_t* starts_dev,
+                     const int32_t* pfx_dev, int32_t n_seq, int32_t seq_len, int32_t heads, int32_t causal,
+                     int32_t pool_mode, const int32_t* pool_row_dev, int32_t f16, void* stream);
+
 /* Backward of tvc_attention (non-causal, fixed-length sequences, head_dim 64): qkv as the forward saw it,
  * dout bf16 [rows, width] = gradient w.r.t. the attention output, dqkv bf16 [rows, 3*width] (dq | dk | dv). */
 int tvc_attention_backward(tvc_handle* h, const uint16_t* qkv_dev, const uint16_t* dout_dev, uint16_t* dqkv_dev,
@@ -539,6 +553,13 @@ int tvc_sd_block(tvc_handle* h, int32_t kind, const char* prefix, const float* x
 /* Streaming attention of the UNet (parity tests): q [n * Tq, heads * dh], k / v [n * Tk, heads * dh], out like q; bf16. */
 int tvc_sd_attention(tvc_handle* h, const uint16_t* q_dev, const uint16_t* k_dev, const uint16_t* v_dev, uint16_t* out_dev,
                      int32_t n, int32_t heads, int32_t Tq, int32_t Tk, int32_t dh, void* stream);
+/* The same with one row stride (in elements) per operand, as the model's fused projections pass them: head h of a row
+ * occupies its columns [h * dh, (h + 1) * dh), columns beyond heads * dh are neither read nor written.  ldq / ldk / ldv
+ * multiples of 8, ldo a multiple of 4, each >= heads * dh, q / k / v 16-byte and out 8-byte aligned; anything else
+ * returns TVC_E_INVALID and launches nothing. */
+int tvc_sd_attention_ex(tvc_handle* h, const uint16_t* q_dev, int64_t ldq, const uint16_t* k_dev, int64_t ldk,
+                        const uint16_t* v_dev, int64_t ldv, uint16_t* out_dev, int64_t ldo, int32_t n, int32_t heads,
+                        int32_t Tq, int32_t Tk, int32_t dh, void* stream);
 
 /* Image preprocessing on the device: images fp32 [n, 3, H, W] with values in [0, 1] -> out fp32 [n, 3, S, S]:
  * antialiased resize of the short side to S (filter 0 = bilinear: torchvision Resize as in
@@ -567,6 +588,12 @@ int tvc_gemm_split(tvc_handle* h, const float* w_dev, const float* x_dev, const 
                    int32_t I, int32_t J, int32_t K, int32_t ld_out, void* stream);
 int tvc_attention_split(tvc_handle* h, const float* qkv_dev, uint16_t* out_planes_dev, const int32_t* starts_dev,
                         int32_t n_seq, int32_t seq_len, int32_t heads, int32_t causal, void* stream);
+/* tvc_attention_split plus prefix sharing: pfx_dev (optional, causal packed rows only), int32 [2 * n_seq], as in
+ * tvc_attention_ex -- pfx[s] is the prefix length, pfx[n_seq + s] the packed row of the prefix's position 0, and seq_len
+ * (<= 272) bounds prefix + own rows.  pfx without starts or without causal returns TVC_E_INVALID and launches nothing. */
+int tvc_attention_split_ex(tvc_handle* h, const float* qkv_dev, uint16_t* out_planes_dev, const int32_t* starts_dev,
+                           const int32_t* pfx_dev, int32_t n_seq, int32_t seq_len, int32_t heads, int32_t causal,
+                           void* stream);
 
 #ifdef __cplusplus
 }

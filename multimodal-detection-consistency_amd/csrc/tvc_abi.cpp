@@ -945,6 +945,24 @@ int tvc_attention_f16(tvc_handle* h, const uint16_t* qkv_dev, uint16_t* out_dev,
     return TVC_OK;
 }
 
+int tvc_attention_ex(tvc_handle* h, const uint16_t* qkv_dev, uint16_t* out_dev, const int32_t* starts_dev, const int32_t* pfx_dev,
+                     int32_t n_seq, int32_t seq_len, int32_t heads, int32_t causal, int32_t pool_mode, const int32_t* pool_row_dev,
+                     int32_t f16, void* stream) {
+    if (!h) return TVC_E_INVALID;
+    if (!qkv_dev || !out_dev) return fail(h, TVC_E_INVALID, "tvc_attention_ex: NULL buffer");
+    // what launch_attention refuses (or, for a prefix on a non-causal launch, would silently drop), checked here so that a
+    // refused call launches nothing whatever the launcher does
+    if (n_seq < 0 || seq_len < 1 || seq_len > 288 || heads < 1 || pool_mode < 0 || pool_mode > 2)
+        return fail(h, TVC_E_INVALID, "tvc_attention_ex: need n_seq >= 0, 1 <= seq_len <= 288, heads >= 1 and pool_mode 0 / 1 / 2");
+    if (pfx_dev && (!starts_dev || !causal))
+        return fail(h, TVC_E_INVALID, "tvc_attention_ex: pfx needs packed rows (starts) and the causal mask");
+    if (pool_mode == 2 && !starts_dev && !pool_row_dev)
+        return fail(h, TVC_E_INVALID, "tvc_attention_ex: pool_mode 2 on dense rows needs pool_row");
+    HIP_TRY(launch_attention(qkv_dev, out_dev, starts_dev, n_seq, seq_len, heads, causal, (hipStream_t)stream, pfx_dev, pool_mode,
+                             pool_row_dev, f16 != 0));
+    return TVC_OK;
+}
+
 int tvc_layernorm(tvc_handle* h, const float* x_dev, const float* g_dev, const float* b_dev, uint16_t* y_dev,
                   int32_t rows, int32_t d, void* stream) {
     if (!h) return TVC_E_INVALID;

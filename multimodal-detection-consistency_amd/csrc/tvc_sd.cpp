@@ -914,4 +914,20 @@ int tvc_sd_attention(tvc_handle* h, const uint16_t* q_dev, const uint16_t* k_dev
     return TVC_OK;
 }
 
+int tvc_sd_attention_ex(tvc_handle* h, const uint16_t* q_dev, int64_t ldq, const uint16_t* k_dev, int64_t ldk, const uint16_t* v_dev,
+                        int64_t ldv, uint16_t* out_dev, int64_t ldo, int32_t n, int32_t heads, int32_t Tq, int32_t Tk, int32_t dh,
+                        void* stream) {
+    if (!h) return TVC_E_INVALID;
+    if (!q_dev || !k_dev || !v_dev || !out_dev || n < 1 || heads < 1 || Tq < 1 || Tk < 1 || dh < 8 || dh > 160 || dh % 8)
+        return fail(h, TVC_E_INVALID, "tvc_sd_attention_ex: need head_dim % 8 == 0 and <= 160, non-NULL buffers");
+    // the alignment rule of sd_flash_attention (16-byte loads of q / k / v pieces, 8-byte stores) and rows that hold all heads
+    const int64_t w = (int64_t)heads * dh;
+    if (ldq < w || ldk < w || ldv < w || ldo < w || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 ||
+        ((uintptr_t)q_dev & 15) || ((uintptr_t)k_dev & 15) || ((uintptr_t)v_dev & 15) || ((uintptr_t)out_dev & 7))
+        return fail(h, TVC_E_INVALID, "tvc_sd_attention_ex: need ldq / ldk / ldv % 8 == 0, ldo % 4 == 0, every stride >= heads * dh, "
+                                      "q / k / v 16-byte and out 8-byte aligned");
+    HIP_TRY(sd_flash_attention(q_dev, ldq, k_dev, ldk, v_dev, ldv, out_dev, ldo, n, heads, Tq, Tk, dh, (hipStream_t)stream));
+    return TVC_OK;
+}
+
 }  // extern "C"

@@ -226,3 +226,15 @@ extern "C" int tvc_attention_split(tvc_handle* h, const float* qkv_dev, uint16_t
     HIP_TRY(launch_attention_split(qkv_dev, out_planes_dev, starts_dev, n_seq, seq_len, heads, causal, (hipStream_t)stream, nullptr));
     return TVC_OK;
 }
+
+extern "C" int tvc_attention_split_ex(tvc_handle* h, const float* qkv_dev, uint16_t* out_planes_dev, const int32_t* starts_dev,
+                                      const int32_t* pfx_dev, int32_t n_seq, int32_t seq_len, int32_t heads, int32_t causal,
+                                      void* stream) {
+    if (!h) return TVC_E_INVALID;
+    if (!qkv_dev || !out_planes_dev || seq_len < 1 || seq_len > 272 || heads < 1 || n_seq < 0)
+        return fail(h, TVC_E_INVALID, "tvc_attention_split_ex: need 1 <= seq_len <= 272 and non-NULL buffers");
+    if (pfx_dev && (!starts_dev || !causal))
+        return fail(h, TVC_E_INVALID, "tvc_attention_split_ex: pfx needs packed rows (starts) and the causal mask");
+    HIP_TRY(launch_attention_split(qkv_dev, out_planes_dev, starts_dev, n_seq, seq_len, heads, causal, (hipStream_t)stream, pfx_dev));
+    return TVC_OK;
+}

@@ -568,6 +568,27 @@ class TVCEngine:
         """fp16 twin of :meth:`attention`; ``starts`` (int32 [n_seq + 1]): packed sequences of at most seq_len rows."""
         return self._attention16(torch.float16, self.lib.tvc_attention_f16, qkv, n_seq, seq_len, heads, causal, starts)
 
+    def attention_ex(self, qkv: torch.Tensor, n_seq: int, seq_len: int, heads: int, causal: bool,
+                     starts: Optional[torch.Tensor] = None, pfx: Optional[torch.Tensor] = None, pool_mode: int = 0,
+                     pool_row: Optional[torch.Tensor] = None, f16: bool = False,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The tower attention kernel with every launch option (``tvc_attention_ex``, include/tvc.h): qkv bf16 (fp16 with
+        ``f16``); ``starts`` int32 [n_seq + 1], ``pfx`` int32 [2 * n_seq], ``pool_row`` int32 [n_seq].  Returns
+        [rows, width], or the compact [n_seq, width] when ``pool_mode`` is 1 / 2; ``out`` (optional) is written in place."""
+        dt = torch.float16 if f16 else torch.bfloat16
+        qkv = _require_cuda(qkv, dt, "qkv")
+        shape = (n_seq if pool_mode else qkv.shape[0], heads * 64)
+        if out is None:
+            out = torch.empty(shape, dtype=dt, device=self.device)
+        elif not out.is_cuda or out.dtype != dt or out.shape != shape or not out.is_contiguous():
+            raise ValueError(f"attention_ex: out must be a contiguous {dt} tensor of shape {shape} on the GPU")
+        starts, pfx, pool_row = (t if t is None else _require_cuda(t, torch.int32, name)
+                                 for t, name in ((starts, "starts"), (pfx, "pfx"), (pool_row, "pool_row")))
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.tvc_attention_ex(self.handle, _ptr(qkv), _ptr(out), _ptr(starts), _ptr(pfx), n_seq, seq_len,
+                                                  heads, int(causal), pool_mode, _ptr(pool_row), int(f16), _stream()))
+        return out
+
     def attention_backward(self, qkv: torch.Tensor, dout: torch.Tensor, n_seq: int, seq_len: int, heads: int) -> torch.Tensor:
         qkv = _require_cuda(qkv, torch.bfloat16, "qkv")
         dout = _require_cuda(dout, torch.bfloat16, "dout")
@@ -656,6 +677,19 @@ class TVCEngine:
         with self._lock, torch.cuda.device(self.device):
             self._check(self.lib.tvc_attention_split(self.handle, _ptr(qkv), _ptr(planes), _ptr(starts), n_seq, seq_len, heads,
                                                      int(causal), _stream()))
+        return planes[:, :w].float() + planes[:, w:].float()
+
+    def attention_split_ex(self, qkv: torch.Tensor, n_seq: int, seq_len: int, heads: int, causal: bool,
+                           starts: Optional[torch.Tensor] = None, pfx: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """:meth:`attention_split` plus prefix sharing (``tvc_attention_split_ex``): ``pfx`` int32 [2 * n_seq] as in
+        :meth:`attention_ex`.  Rows the kernel does not write come back as zeros."""
+        qkv = _require_cuda(qkv, torch.float32, "qkv")
+        w = heads * 64
+        planes = torch.zeros((qkv.shape[0], 2 * w), dtype=torch.bfloat16, device=self.device)
+        starts, pfx = (t if t is None else _require_cuda(t, torch.int32, name) for t, name in ((starts, "starts"), (pfx, "pfx")))
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.tvc_attention_split_ex(self.handle, _ptr(qkv), _ptr(planes), _ptr(starts), _ptr(pfx), n_seq,
+                                                        seq_len, heads, int(causal), _stream()))
         return planes[:, :w].float() + planes[:, w:].float()
 
     def _layernorm16(self, dt: torch.dtype, fn, x, g, b) -> torch.Tensor:

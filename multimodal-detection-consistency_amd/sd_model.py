@@ -185,16 +185,41 @@ class SDKernels:
                                         int(vae), _ptr(out), _stream()))
         return out
 
-    def attention(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, n: int, heads: int) -> torch.Tensor:
+    def attention(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, n: int, heads: int, ld=None,
+                  dh: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """q [n * Tq, heads * dh], k / v [n * Tk, heads * dh] bf16 -> [n * Tq, heads * dh] bf16."""
-        e = self.engine
-        q, k, v = (t.to(e.device, torch.bfloat16).contiguous() for t in (q, k, v))
+        return streaming_attention(self.engine, q, k, v, n, heads, ld=ld, dh=dh, out=out)
+
+
+def streaming_attention(engine: TVCEngine, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, n: int, heads: int, ld=None,
+                        dh: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The UNet's streaming attention kernel on its own (needs no loaded model): q [n * Tq, heads * dh], k / v
+    [n * Tk, heads * dh] bf16 -> [n * Tq, heads * dh] bf16.
+
+    ``ld = (ldq, ldk, ldv, ldo)``: one row stride (in elements) per operand, as the model's fused projections pass them
+    (``tvc_sd_attention_ex``).  q / k / v / out are then [rows, ld*] tensors whose first ``heads * dh`` columns are the
+    heads, ``dh`` must be given, and ``out`` (optional, [n * Tq, ldo]) is written in place -- columns beyond
+    ``heads * dh`` are neither read nor written."""
+    e = engine
+    q, k, v = (t.to(e.device, torch.bfloat16).contiguous() for t in (q, k, v))
+    if ld is None:
         dh = q.shape[1] // heads
         out = torch.empty_like(q)
         with e._lock, torch.cuda.device(e.device):
             e._check(e.lib.tvc_sd_attention(e.handle, _ptr(q), _ptr(k), _ptr(v), _ptr(out), n, heads, q.shape[0] // n,
                                             k.shape[0] // n, dh, _stream()))
         return out
+    ldq, ldk, ldv, ldo = (int(x) for x in ld)
+    if dh is None or (q.shape[1], k.shape[1], v.shape[1]) != (ldq, ldk, ldv) or k.shape[0] != v.shape[0]:
+        raise ValueError("streaming_attention: with ld, pass dh and q / k / v as [rows, ldq / ldk / ldv] tensors")
+    if out is None:
+        out = torch.zeros((q.shape[0], ldo), dtype=torch.bfloat16, device=e.device)
+    elif out.shape != (q.shape[0], ldo) or out.dtype != torch.bfloat16 or not out.is_contiguous() or out.device != q.device:
+        raise ValueError("streaming_attention: out must be a contiguous bf16 [n * Tq, ldo] tensor on the engine's device")
+    with e._lock, torch.cuda.device(e.device):
+        e._check(e.lib.tvc_sd_attention_ex(e.handle, _ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(out), ldo, n, heads,
+                                           q.shape[0] // n, k.shape[0] // n, dh, _stream()))
+    return out
 
 
 @dataclass

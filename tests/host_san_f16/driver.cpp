@@ -141,6 +141,43 @@ int main() {
     OK(tvc_attention_f16(h, qkv, ao, nullptr, 2, 77, 2, 1, nullptr));
     CHECK(tvc_attention_f16(h, nullptr, ao, nullptr, 2, 77, 2, 1, nullptr) == TVC_E_INVALID);
     OK(tvc_layernorm_f16(h, o32, vw.ln_pre_g, vw.ln_pre_b, ao, 2, 128, nullptr));
+    // ---- the attention entry points with every launch option: the stub launchers accept anything, so TVC_E_INVALID here
+    // means the call was refused before any launch
+    {
+        int32_t* st = (int32_t*)buf(3, 4); int32_t* pf = (int32_t*)buf(4, 4); int32_t* pr = (int32_t*)buf(2, 4);
+        float* q32 = (float*)buf((size_t)2 * 77 * 3 * 128, 4); uint16_t* pl = (uint16_t*)buf((size_t)2 * 77 * 2 * 128, 2);
+        for (int f16 = 0; f16 < 2; ++f16) {
+            OK(tvc_attention_ex(h, qkv, ao, nullptr, nullptr, 2, 77, 2, 1, 0, nullptr, f16, nullptr));
+            OK(tvc_attention_ex(h, qkv, ao, st, pf, 2, 77, 2, 1, 2, nullptr, f16, nullptr));
+            OK(tvc_attention_ex(h, qkv, ao, nullptr, nullptr, 2, 77, 2, 0, 2, pr, f16, nullptr));
+            OK(tvc_attention_ex(h, qkv, ao, nullptr, nullptr, 2, 288, 2, 0, 1, nullptr, f16, nullptr));
+            CHECK(tvc_attention_ex(h, qkv, ao, nullptr, pf, 2, 77, 2, 1, 0, nullptr, f16, nullptr) == TVC_E_INVALID);   // pfx without starts
+            CHECK(tvc_attention_ex(h, qkv, ao, st, pf, 2, 77, 2, 0, 0, nullptr, f16, nullptr) == TVC_E_INVALID);        // pfx without causal
+            CHECK(tvc_attention_ex(h, qkv, ao, nullptr, nullptr, 2, 77, 2, 1, 2, nullptr, f16, nullptr) == TVC_E_INVALID && strlen(tvc_last_error(h)) > 0);
+            CHECK(tvc_attention_ex(h, qkv, ao, nullptr, nullptr, 2, 77, 2, 1, 3, nullptr, f16, nullptr) == TVC_E_INVALID);
+            CHECK(tvc_attention_ex(h, qkv, ao, nullptr, nullptr, 2, 0, 2, 1, 0, nullptr, f16, nullptr) == TVC_E_INVALID);
+            CHECK(tvc_attention_ex(h, qkv, ao, nullptr, nullptr, 2, 289, 2, 1, 0, nullptr, f16, nullptr) == TVC_E_INVALID);
+            CHECK(tvc_attention_ex(h, qkv, ao, nullptr, nullptr, 2, 77, 0, 1, 0, nullptr, f16, nullptr) == TVC_E_INVALID);
+            CHECK(tvc_attention_ex(h, nullptr, ao, nullptr, nullptr, 2, 77, 2, 1, 0, nullptr, f16, nullptr) == TVC_E_INVALID);
+        }
+        OK(tvc_attention_split_ex(h, q32, pl, st, pf, 2, 77, 2, 1, nullptr));
+        OK(tvc_attention_split_ex(h, q32, pl, nullptr, nullptr, 2, 272, 2, 0, nullptr));
+        CHECK(tvc_attention_split_ex(h, q32, pl, nullptr, pf, 2, 77, 2, 1, nullptr) == TVC_E_INVALID);
+        CHECK(tvc_attention_split_ex(h, q32, pl, st, pf, 2, 77, 2, 0, nullptr) == TVC_E_INVALID);
+        CHECK(tvc_attention_split_ex(h, q32, pl, st, nullptr, 2, 273, 2, 1, nullptr) == TVC_E_INVALID);
+        CHECK(tvc_attention_split_ex(h, q32, pl, st, nullptr, 2, 0, 2, 1, nullptr) == TVC_E_INVALID);
+        CHECK(tvc_attention_split_ex(h, q32, nullptr, st, nullptr, 2, 77, 2, 1, nullptr) == TVC_E_INVALID);
+        // streaming attention: 2 heads of 24 in rows of 56 / 64 / 72 / 52 elements
+        OK(tvc_sd_attention_ex(h, qkv, 56, qkv, 64, qkv, 72, ao, 52, 2, 2, 5, 7, 24, nullptr));
+        CHECK(tvc_sd_attention_ex(h, qkv, 52, qkv, 64, qkv, 72, ao, 52, 2, 2, 5, 7, 24, nullptr) == TVC_E_INVALID);     // ldq % 8
+        CHECK(tvc_sd_attention_ex(h, qkv, 56, qkv, 68, qkv, 72, ao, 52, 2, 2, 5, 7, 24, nullptr) == TVC_E_INVALID);     // ldk % 8
+        CHECK(tvc_sd_attention_ex(h, qkv, 56, qkv, 64, qkv, 76, ao, 52, 2, 2, 5, 7, 24, nullptr) == TVC_E_INVALID);     // ldv % 8
+        CHECK(tvc_sd_attention_ex(h, qkv, 56, qkv, 64, qkv, 72, ao, 50, 2, 2, 5, 7, 24, nullptr) == TVC_E_INVALID);     // ldo % 4
+        CHECK(tvc_sd_attention_ex(h, qkv, 40, qkv, 64, qkv, 72, ao, 52, 2, 2, 5, 7, 24, nullptr) == TVC_E_INVALID);     // ldq < heads * dh
+        CHECK(tvc_sd_attention_ex(h, qkv + 4, 56, qkv, 64, qkv, 72, ao, 52, 2, 2, 5, 7, 24, nullptr) == TVC_E_INVALID); // q not 16-byte aligned
+        CHECK(tvc_sd_attention_ex(h, qkv, 56, qkv, 64, qkv, 72, ao + 2, 52, 2, 2, 5, 7, 24, nullptr) == TVC_E_INVALID); // out not 8-byte aligned
+        CHECK(tvc_sd_attention_ex(h, qkv, 56, qkv, 64, qkv, 72, ao, 52, 2, 2, 5, 7, 20, nullptr) == TVC_E_INVALID);     // head_dim % 8
+    }
     // ---- profiling bracket in mode 3, then back to bf16
     double ms[TVC_PROF_NCAT], work[TVC_PROF_NCAT], big[3]; int64_t launches[TVC_PROF_NCAT];
     OK(tvc_profile_begin(h)); OK(tvc_encode_image(h, pix, B, fi, 1, nullptr)); OK(tvc_profile_end(h, ms, work, launches, big));
