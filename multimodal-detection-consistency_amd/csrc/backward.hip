@@ -2,12 +2,11 @@
 // `encode_image_tensor(x, requires_grad=True)` (reference: src/attacks/pgd_attack.py:456-486,
 // src/attacks/hubness_attack.py:269-424).  No weight gradients.
 // HBM-bound, one 64-lane wave per row, 16-byte accesses, shuffle reductions -- the layout of elementwise.hip.
+// The row shape, the LayerNorm statistics and backward tail, QuickGELU and the bf16 unpack / pack come from rows.hpp.
 #include "common.hpp"
 #include "kernels.hpp"
 #include "launch.hpp"
-
-#define LN_EPS 1e-5f
-#define ROWS_PER_BLOCK 4
+#include "rows.hpp"
 
 // ---------------------------------------------------------------------------
 // LayerNorm backward with the residual path folded in:
@@ -24,73 +23,32 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
                                                             const void* __restrict__ dy, const float* __restrict__ gamma,
                                                             const float* dres, float* dx, uint16_t* __restrict__ dx16,
                                                             int rows, int d, int64_t out_row_stride) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    const int lane = row_lane();
+    const int row = wave_row();
     if (row >= rows) return;
     const f32x4_t* xr = (const f32x4_t*)(x + (int64_t)row * x_row_stride);
     const u32x2_t* dr = delta ? (const u32x2_t*)(delta + (int64_t)row * x_row_stride) : nullptr;
     const int nv = d >> 2;
-    f32x4_t v[4], g[4];
+    f32x4_t v[4] = {}, g[4] = {};
     float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + i * 64;
-        v[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        g[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        if (c < nv) {
-            v[i] = xr[c];
-            if (dr) {
-                const u32x2_t dd = dr[c];
-                v[i][0] += __uint_as_float(dd[0] << 16); v[i][1] += __uint_as_float(dd[0] & 0xffff0000u);
-                v[i][2] += __uint_as_float(dd[1] << 16); v[i][3] += __uint_as_float(dd[1] & 0xffff0000u);
-            }
-            s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-            const f32x4_t gm = ((const f32x4_t*)gamma)[c];
-            if (DY32) {
-                g[i] = ((const f32x4_t*)((const float*)dy + (int64_t)row * d))[c] * gm;
-            } else {
-                const u32x2_t yy = ((const u32x2_t*)((const uint16_t*)dy + (int64_t)row * d))[c];
-                g[i][0] = __uint_as_float(yy[0] << 16) * gm[0]; g[i][1] = __uint_as_float(yy[0] & 0xffff0000u) * gm[1];
-                g[i][2] = __uint_as_float(yy[1] << 16) * gm[2]; g[i][3] = __uint_as_float(yy[1] & 0xffff0000u) * gm[3];
-            }
-        }
-    }
-    const float mean = wave_sum(s) / (float)d;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + i * 64;
-        if (c < nv) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) { v[i][t] -= mean; q += v[i][t] * v[i][t]; }
-        }
-    }
-    const float rstd = rsqrtf(wave_sum(q) / (float)d + LN_EPS);
-    float sg = 0.f, sgx = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + i * 64;
-        if (c < nv) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) { v[i][t] *= rstd; sg += g[i][t]; sgx = fmaf(g[i][t], v[i][t], sgx); }
-        }
-    }
-    const float c1 = wave_sum(sg) / (float)d, c2 = wave_sum(sgx) / (float)d;
+    for_pieces(lane, nv, [&](int i, int c) {
+        v[i] = xr[c];
+        if (dr) v[i] += unpack4(dr[c]);
+        s += piece_sum(v[i]);
+        const f32x4_t gm = ((const f32x4_t*)gamma)[c];
+        if (DY32) g[i] = ((const f32x4_t*)((const float*)dy + (int64_t)row * d))[c] * gm;
+        else g[i] = unpack4(((const u32x2_t*)((const uint16_t*)dy + (int64_t)row * d))[c]) * gm;
+    });
+    const float mean = row_mean(s, d);
+    const float rstd = row_rstd(v, mean, lane, nv, d);
     const f32x4_t* rr = dres ? (const f32x4_t*)(dres + (int64_t)row * out_row_stride) : nullptr;
     f32x4_t* ox = (f32x4_t*)(dx + (int64_t)row * out_row_stride);
     u32x2_t* o16 = dx16 ? (u32x2_t*)(dx16 + (int64_t)row * out_row_stride) : nullptr;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + i * 64;
-        if (c < nv) {
-            f32x4_t o;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) o[t] = rstd * (g[i][t] - c1 - v[i][t] * c2);
-            if (rr) o += rr[c];
-            ox[c] = o;
-            if (o16) o16[c] = u32x2_t{pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])};
-        }
-    }
+    ln_bwd_tail(v, g, mean, rstd, lane, nv, d, [&](int c, f32x4_t o) {
+        if (rr) o += rr[c];
+        ox[c] = o;
+        if (o16) o16[c] = pack4(o);
+    });
 }
 
 hipError_t launch_layernorm_bwd(const float* x, int64_t x_row_stride, const uint16_t* delta, const void* dy, int dy_fp32,
@@ -98,9 +56,8 @@ hipError_t launch_layernorm_bwd(const float* x, int64_t x_row_stride, const uint
                                 int64_t out_row_stride, hipStream_t stream) {
     if (d % 4 != 0 || d > 1024 || rows < 0) return hipErrorInvalidValue;
     if (rows == 0) return hipSuccess;
-    const int grid = (rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
     return dispatch<true, false>(dy_fp32 != 0, [&](auto f32) {
-        return launch<layernorm_bwd_kernel<f32.value>>(dim3(grid), dim3(256), 0, stream, x, x_row_stride, delta, dy, gamma, dres, dx, dx16,
+        return launch<layernorm_bwd_kernel<f32.value>>(row_grid(rows), dim3(256), 0, stream, x, x_row_stride, delta, dy, gamma, dres, dx, dx16,
                                                        rows, d, out_row_stride);
     });
 }
@@ -113,8 +70,8 @@ hipError_t launch_layernorm_bwd(const float* x, int64_t x_row_stride, const uint
 __global__ __launch_bounds__(256) void lnpre_bwd_kernel(const float* __restrict__ patch_out, const float* __restrict__ pos,
                                                         const float* __restrict__ gamma, const float* __restrict__ dy,
                                                         uint16_t* __restrict__ dpatch, int B, int T, int d) {
-    const int lane = threadIdx.x & 63;
-    const int64_t prow = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);     // row of patch_out
+    const int lane = row_lane();
+    const int64_t prow = wave_row<int64_t>();     // row of patch_out
     if (prow >= (int64_t)B * (T - 1)) return;
     const int64_t b = prow / (T - 1);
     const int t = (int)(prow - b * (T - 1)) + 1;
@@ -122,50 +79,17 @@ __global__ __launch_bounds__(256) void lnpre_bwd_kernel(const float* __restrict_
     const f32x4_t* pr = (const f32x4_t*)(pos + (int64_t)t * d);
     const f32x4_t* gy = (const f32x4_t*)(dy + (b * T + t) * d);
     const int nv = d >> 2;
-    f32x4_t v[4], g[4];
+    f32x4_t v[4] = {}, g[4] = {};
     float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + i * 64;
-        v[i] = f32x4_t{0.f, 0.f, 0.f, 0.f}; g[i] = v[i];
-        if (c < nv) {
-            v[i] = src[c] + pr[c];
-            s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-            g[i] = gy[c] * ((const f32x4_t*)gamma)[c];
-        }
-    }
-    const float mean = wave_sum(s) / (float)d;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + i * 64;
-        if (c < nv) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { v[i][e] -= mean; q += v[i][e] * v[i][e]; }
-        }
-    }
-    const float rstd = rsqrtf(wave_sum(q) / (float)d + LN_EPS);
-    float sg = 0.f, sgx = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + i * 64;
-        if (c < nv) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { v[i][e] *= rstd; sg += g[i][e]; sgx = fmaf(g[i][e], v[i][e], sgx); }
-        }
-    }
-    const float c1 = wave_sum(sg) / (float)d, c2 = wave_sum(sgx) / (float)d;
+    for_pieces(lane, nv, [&](int i, int c) {
+        v[i] = src[c] + pr[c];
+        s += piece_sum(v[i]);
+        g[i] = gy[c] * ((const f32x4_t*)gamma)[c];
+    });
+    const float mean = row_mean(s, d);
+    const float rstd = row_rstd(v, mean, lane, nv, d);
     u32x2_t* o = (u32x2_t*)(dpatch + prow * d);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + i * 64;
-        if (c < nv) {
-            f32x4_t r;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) r[e] = rstd * (g[i][e] - c1 - v[i][e] * c2);
-            o[c] = u32x2_t{pack_bf16x2(r[0], r[1]), pack_bf16x2(r[2], r[3])};
-        }
-    }
+    ln_bwd_tail(v, g, mean, rstd, lane, nv, d, [&](int c, f32x4_t r) { o[c] = pack4(r); });
 }
 
 hipError_t launch_lnpre_bwd(const float* patch_out, const float* pos, const float* gamma, const float* dy,
@@ -173,7 +97,7 @@ hipError_t launch_lnpre_bwd(const float* patch_out, const float* pos, const floa
     if (d % 4 != 0 || d > 1024) return hipErrorInvalidValue;
     const int64_t rows = (int64_t)B * (T - 1);
     if (rows == 0) return hipSuccess;
-    return launch<lnpre_bwd_kernel>(dim3((int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)), dim3(256), 0, stream, patch_out, pos,
+    return launch<lnpre_bwd_kernel>(row_grid(rows), dim3(256), 0, stream, patch_out, pos,
                                     gamma, dy, dpatch, B, T, d);
 }
 
@@ -182,53 +106,36 @@ hipError_t launch_lnpre_bwd(const float* patch_out, const float* pos, const floa
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gelu_bwd_kernel(uint16_t* __restrict__ dm, const uint16_t* __restrict__ u, int64_t n8) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
-        const u32x4_t a = ((const u32x4_t*)dm)[i], b = ((const u32x4_t*)u)[i];
-        u32x4_t o;
+        float g[8], x[8];
+        unpack8(((const u32x4_t*)dm)[i], g);
+        unpack8(((const u32x4_t*)u)[i], x);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float r[2];
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                const float g = hh ? __uint_as_float(a[e] & 0xffff0000u) : __uint_as_float(a[e] << 16);
-                const float x = hh ? __uint_as_float(b[e] & 0xffff0000u) : __uint_as_float(b[e] << 16);
-                const float sg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.4554670f * x));
-                r[hh] = g * (sg + 1.702f * x * sg * (1.0f - sg));
-            }
-            o[e] = pack_bf16x2(r[0], r[1]);
-        }
-        ((u32x4_t*)dm)[i] = o;
+        for (int e = 0; e < 8; ++e) g[e] *= quick_gelu_grad(x[e]);
+        ((u32x4_t*)dm)[i] = pack8(g);
     }
 }
 
 hipError_t launch_gelu_bwd(uint16_t* dm, const uint16_t* u, int64_t n, hipStream_t stream) {
     if (n % 8 != 0) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
-    int64_t grid = (n / 8 + 255) / 256;
-    if (grid > 16384) grid = 16384;
-    return launch<gelu_bwd_kernel>(dim3((int)grid), dim3(256), 0, stream, dm, u, n / 8);
+    return launch<gelu_bwd_kernel>(stride_grid(n / 8, 16384), dim3(256), 0, stream, dm, u, n / 8);
 }
 
 // quick-GELU forward on a bf16 buffer (the grad-mode forward stores the pre-activation and applies this)
 __global__ __launch_bounds__(256) void gelu_fwd_kernel(const uint16_t* __restrict__ u, uint16_t* __restrict__ out, int64_t n8) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
-        const u32x4_t b = ((const u32x4_t*)u)[i];
-        u32x4_t o;
+        float x[8];
+        unpack8(((const u32x4_t*)u)[i], x);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float x0 = __uint_as_float(b[e] << 16), x1 = __uint_as_float(b[e] & 0xffff0000u);
-            o[e] = pack_bf16x2(x0 * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.4554670f * x0)),
-                               x1 * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.4554670f * x1)));
-        }
-        ((u32x4_t*)out)[i] = o;
+        for (int e = 0; e < 8; ++e) x[e] = quick_gelu(x[e]);
+        ((u32x4_t*)out)[i] = pack8(x);
     }
 }
 
 hipError_t launch_gelu_fwd(const uint16_t* u, uint16_t* out, int64_t n, hipStream_t stream) {
     if (n % 8 != 0) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
-    int64_t grid = (n / 8 + 255) / 256;
-    if (grid > 16384) grid = 16384;
-    return launch<gelu_fwd_kernel>(dim3((int)grid), dim3(256), 0, stream, u, out, n / 8);
+    return launch<gelu_fwd_kernel>(stride_grid(n / 8, 16384), dim3(256), 0, stream, u, out, n / 8);
 }
 
 // ---------------------------------------------------------------------------
@@ -237,8 +144,8 @@ hipError_t launch_gelu_fwd(const uint16_t* u, uint16_t* out, int64_t n, hipStrea
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                          uint16_t* __restrict__ dx16, int rows, int d, int normalize) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    const int lane = row_lane();
+    const int row = wave_row();
     if (row >= rows) return;
     const float* xr = x + (int64_t)row * d;
     const float* gr = dy + (int64_t)row * d;
@@ -257,7 +164,7 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict
 
 hipError_t launch_l2norm_bwd(const float* x, const float* dy, uint16_t* dx16, int rows, int d, int normalize, hipStream_t stream) {
     if (rows == 0) return hipSuccess;
-    return launch<l2norm_bwd_kernel>(dim3((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(256), 0, stream, x, dy, dx16, rows, d,
+    return launch<l2norm_bwd_kernel>(row_grid(rows), dim3(256), 0, stream, x, dy, dx16, rows, d,
                                      normalize);
 }
 
@@ -282,9 +189,7 @@ __global__ __launch_bounds__(256) void col2im_kernel(const float* __restrict__ d
 hipError_t launch_col2im(const float* dcols, float* dpix, int B, int S, int patch, int Kp, hipStream_t stream) {
     const int64_t total = (int64_t)B * 3 * S * S;
     if (total == 0) return hipSuccess;
-    int64_t grid = (total + 255) / 256;
-    if (grid > 16384) grid = 16384;
-    return launch<col2im_kernel>(dim3((int)grid), dim3(256), 0, stream, dcols, dpix, B, S, patch, Kp);
+    return launch<col2im_kernel>(stride_grid(total, 16384), dim3(256), 0, stream, dcols, dpix, B, S, patch, Kp);
 }
 
 // ---------------------------------------------------------------------------

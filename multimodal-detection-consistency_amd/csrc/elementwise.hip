@@ -1,12 +1,12 @@
 // HBM-bound row kernels of the CLIP towers and the bank path: LayerNorm,
 // patch im2col, token assembly, embedding gather, L2 normalise, split-bf16
 // planes, bank row gather.  One 64-lane wave per row, 16-byte accesses,
-// wave-shuffle reductions (no LDS).
+// wave-shuffle reductions (no LDS).  The row shape, the LayerNorm statistics and the GELU forms come from rows.hpp.
 #include "common.hpp"
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "rows.hpp"
 
-#define LN_EPS 1e-5f
 // Non-temporal hints of the LayerNorm pass (bit mask: 1 = x loads, 2 = x stores, 4 = delta loads, 8 = y stores).  The
 // residual stream and the projection output are read ONCE here and re-read only after the next GEMMs have streamed
 // > 256 MB through the caches, so they are marked streaming: 7 measured 14.0 -> 12.6 ms of LayerNorm per step against 0
@@ -14,7 +14,6 @@
 #ifndef TVC_LN_NT
 #define TVC_LN_NT 7
 #endif
-#define ROWS_PER_BLOCK 4   // 256 threads = 4 waves = 4 rows
 
 // ---------------------------------------------------------------------------
 // (residual add +) LayerNorm: x fp32 row (+ delta bf16 row) -> bf16 row (GEMM
@@ -33,8 +32,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(float* __restrict__ x, i
                                                         uint16_t* __restrict__ y, int rows, int d,
                                                         int delta_compact, float* __restrict__ xsum_out,
                                                         float* __restrict__ y32) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    const int lane = row_lane();
+    const int row = wave_row();
     if (row >= rows) return;
     const int64_t src_row = row_idx ? (int64_t)row_idx[row] : (int64_t)row;
     f32x4_t* xr = (f32x4_t*)(x + src_row * x_row_stride);
@@ -43,82 +42,44 @@ __global__ __launch_bounds__(256) void layernorm_kernel(float* __restrict__ x, i
     const u32x2_t* dr = delta ? (const u32x2_t*)(delta + doff) : nullptr;
     const u32x2_t* dr2 = delta2 ? (const u32x2_t*)(delta2 + doff) : nullptr;
     const int nv = d >> 2;
-    f32x4_t v[4];
+    f32x4_t v[4] = {};
     float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + i * 64;
-        v[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        if (c < nv) {
+    for_pieces(lane, nv, [&](int i, int c) {
 #if TVC_LN_NT & 1
-            v[i] = __builtin_nontemporal_load(xr + c);
+        v[i] = __builtin_nontemporal_load(xr + c);
 #else
-            v[i] = xr[c];
+        v[i] = xr[c];
 #endif
-            if (dr) {
+        if (dr) {
 #if TVC_LN_NT & 4
-                const u32x2_t dd = __builtin_nontemporal_load(dr + c);
+            v[i] += unpack4<F16>(__builtin_nontemporal_load(dr + c));
 #else
-                const u32x2_t dd = dr[c];
+            v[i] += unpack4<F16>(dr[c]);
 #endif
-                v[i][0] += Op16<F16>::lo(dd[0]);
-                v[i][1] += Op16<F16>::hi(dd[0]);
-                v[i][2] += Op16<F16>::lo(dd[1]);
-                v[i][3] += Op16<F16>::hi(dd[1]);
-            }
-            if (dr2) {
-                const u32x2_t dd = dr2[c];
-                v[i][0] += Op16<F16>::lo(dd[0]);
-                v[i][1] += Op16<F16>::hi(dd[0]);
-                v[i][2] += Op16<F16>::lo(dd[1]);
-                v[i][3] += Op16<F16>::hi(dd[1]);
-            }
+        }
+        if (dr2) v[i] += unpack4<F16>(dr2[c]);
 #if TVC_LN_NT & 2
-            if (write_x && (dr || dr2)) __builtin_nontemporal_store(v[i], xr + c);
+        if (write_x && (dr || dr2)) __builtin_nontemporal_store(v[i], xr + c);
 #else
-            if (write_x && (dr || dr2)) xr[c] = v[i];
+        if (write_x && (dr || dr2)) xr[c] = v[i];
 #endif
-            if (xsum_out) ((f32x4_t*)(xsum_out + (int64_t)row * d))[c] = v[i];
-            s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-        }
-    }
-    const float mean = wave_sum(s) / (float)d;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + i * 64;
-        if (c < nv) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const float dlt = v[i][t] - mean;
-                q += dlt * dlt;
-            }
-        }
-    }
-    const float rstd = rsqrtf(wave_sum(q) / (float)d + LN_EPS);
+        if (xsum_out) ((f32x4_t*)(xsum_out + (int64_t)row * d))[c] = v[i];
+        s += piece_sum(v[i]);
+    });
+    const float mean = row_mean(s, d);
+    const float rstd = row_rstd(v, mean, lane, nv, d);
     u32x2_t* yr = (u32x2_t*)(y + (int64_t)row * d);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + i * 64;
-        if (c < nv) {
-            const f32x4_t gg = ((const f32x4_t*)g)[c];
-            const f32x4_t bb = ((const f32x4_t*)b)[c];
-            f32x4_t o;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) o[t] = (v[i][t] - mean) * rstd * gg[t] + bb[t];
-            if (y32) ((f32x4_t*)(y32 + (int64_t)row * d))[c] = o;      // fp32 copy (hidden-state outputs)
-            if (y) {
-                u32x2_t pk;
-                pk[0] = Op16<F16>::pack2(o[0], o[1]);
-                pk[1] = Op16<F16>::pack2(o[2], o[3]);
+    for_pieces(lane, nv, [&](int i, int c) {
+        const f32x4_t o = ln_affine(v[i], mean, rstd, g, b, c);
+        if (y32) ((f32x4_t*)(y32 + (int64_t)row * d))[c] = o;      // fp32 copy (hidden-state outputs)
+        if (y) {
 #if TVC_LN_NT & 8
-                __builtin_nontemporal_store(pk, yr + c);
+            __builtin_nontemporal_store(pack4<F16>(o), yr + c);
 #else
-                yr[c] = pk;
+            yr[c] = pack4<F16>(o);
 #endif
-            }
         }
-    }
+    });
 }
 
 hipError_t launch_layernorm(float* x, int64_t x_row_stride, const int32_t* row_idx, const uint16_t* delta,
@@ -127,9 +88,8 @@ hipError_t launch_layernorm(float* x, int64_t x_row_stride, const int32_t* row_i
                             int f16) {
     if (d % 4 != 0 || d > 1024 || rows < 0) return hipErrorInvalidValue;
     if (rows == 0) return hipSuccess;
-    const int grid = (rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
     return dispatch<true, false>(f16 != 0, [&](auto h) {
-        return launch<layernorm_kernel<h.value>>(dim3(grid), dim3(256), 0, stream, x, x_row_stride, row_idx, delta, delta2, write_x, g, b,
+        return launch<layernorm_kernel<h.value>>(row_grid(rows), dim3(256), 0, stream, x, x_row_stride, row_idx, delta, delta2, write_x, g, b,
                                                  y, rows, d, delta_compact, xsum_out, y32);
     });
 }
@@ -223,10 +183,8 @@ hipError_t launch_im2col(const float* pix, uint16_t* out, int B, int image, int 
             return launch<im2col_rows_kernel<h.value>>(dim3(B * g), dim3(256), lds, stream, pix, out, image, patch, Kp);
         });
     const int64_t total = (int64_t)B * g * g * (Kp >> 3);
-    int grid = (int)((total + 255) / 256);
-    if (grid > 8192) grid = 8192;
     return dispatch<true, false>(f16 != 0, [&](auto h) {
-        return launch<im2col_kernel<h.value>>(dim3(grid), dim3(256), 0, stream, pix, out, B, image, patch, Kp);
+        return launch<im2col_kernel<h.value>>(stride_grid(total, 8192), dim3(256), 0, stream, pix, out, B, image, patch, Kp);
     });
 }
 
@@ -239,8 +197,8 @@ __global__ __launch_bounds__(256) void assemble_lnpre_kernel(const float* __rest
                                                              const float* __restrict__ g,
                                                              const float* __restrict__ b,
                                                              float* __restrict__ x, int B, int T, int d) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    const int lane = row_lane();
+    const int64_t row = wave_row<int64_t>();
     if (row >= (int64_t)B * T) return;
     const int t = (int)(row % T);
     const int64_t bimg = row / T;
@@ -248,44 +206,16 @@ __global__ __launch_bounds__(256) void assemble_lnpre_kernel(const float* __rest
                                   : (const f32x4_t*)(patch_out + (bimg * (T - 1) + (t - 1)) * d);
     const f32x4_t* pr = (const f32x4_t*)(pos + (int64_t)t * d);
     const int nv = d >> 2;
-    f32x4_t v[4];
+    f32x4_t v[4] = {};
     float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + i * 64;
-        v[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        if (c < nv) {
-            v[i] = src[c] + pr[c];
-            s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-        }
-    }
-    const float mean = wave_sum(s) / (float)d;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + i * 64;
-        if (c < nv) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float dl = v[i][e] - mean;
-                q += dl * dl;
-            }
-        }
-    }
-    const float rstd = rsqrtf(wave_sum(q) / (float)d + LN_EPS);
+    for_pieces(lane, nv, [&](int i, int c) {
+        v[i] = src[c] + pr[c];
+        s += piece_sum(v[i]);
+    });
+    const float mean = row_mean(s, d);
+    const float rstd = row_rstd(v, mean, lane, nv, d);
     f32x4_t* xr = (f32x4_t*)(x + row * d);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + i * 64;
-        if (c < nv) {
-            const f32x4_t gg = ((const f32x4_t*)g)[c];
-            const f32x4_t bb = ((const f32x4_t*)b)[c];
-            f32x4_t o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (v[i][e] - mean) * rstd * gg[e] + bb[e];
-            xr[c] = o;
-        }
-    }
+    for_pieces(lane, nv, [&](int i, int c) { xr[c] = ln_affine(v[i], mean, rstd, g, b, c); });
 }
 
 hipError_t launch_assemble_lnpre(const float* patch_out, const float* cls, const float* pos,
@@ -294,8 +224,7 @@ hipError_t launch_assemble_lnpre(const float* patch_out, const float* cls, const
     if (d % 4 != 0 || d > 1024) return hipErrorInvalidValue;
     const int64_t rows = (int64_t)B * T;
     if (rows == 0) return hipSuccess;
-    const int grid = (int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
-    return launch<assemble_lnpre_kernel>(dim3(grid), dim3(256), 0, stream, patch_out, cls, pos, g, b, x, B, T, d);
+    return launch<assemble_lnpre_kernel>(row_grid(rows), dim3(256), 0, stream, patch_out, cls, pos, g, b, x, B, T, d);
 }
 
 // ---------------------------------------------------------------------------
@@ -313,16 +242,11 @@ hipError_t launch_assemble_lnpre(const float* patch_out, const float* cls, const
 // workgroups) parks own[n] in starts[n] and len[n] in lens[n] (= pfx[n_text + n] when sharing);
 // `text_scan_kernel` (one workgroup) turns them into the exclusive scan, the maximum length and the
 // base rows.  (One workgroup doing both spent 0.8 ms per step waiting on its own token reads.)
-__global__ __launch_bounds__(256) void text_lens_kernel(const int32_t* __restrict__ tok, int32_t* __restrict__ starts,
-                                                        int32_t* __restrict__ pfx, int32_t* __restrict__ lens,
-                                                        int n_text, int ctx, int G) {
-    const int lane = threadIdx.x & 63;
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= n_text) return;
-    // len = position of the first maximum id + 1
+// position of the first maximum of tok[0 .. ctx) (ties -> lowest position, as torch.argmax), in every lane of the wave
+__device__ __forceinline__ int first_max_pos(const int32_t* __restrict__ tok, int ctx, int lane) {
     int best = -1, best_t = 0;
     for (int tt = lane; tt < ctx; tt += 64) {
-        const int v = tok[(int64_t)n * ctx + tt];
+        const int v = tok[tt];
         if (v > best) { best = v; best_t = tt; }
     }
 #pragma unroll
@@ -331,7 +255,17 @@ __global__ __launch_bounds__(256) void text_lens_kernel(const int32_t* __restric
         const int ot = __shfl_xor(best_t, o, 64);
         if (ov > best || (ov == best && ot < best_t)) { best = ov; best_t = ot; }
     }
-    int len = best_t + 1, p = 0;
+    return best_t;
+}
+
+__global__ __launch_bounds__(256) void text_lens_kernel(const int32_t* __restrict__ tok, int32_t* __restrict__ starts,
+                                                        int32_t* __restrict__ pfx, int32_t* __restrict__ lens,
+                                                        int n_text, int ctx, int G) {
+    const int lane = row_lane();
+    const int n = wave_row();
+    if (n >= n_text) return;
+    // len = position of the first maximum id + 1
+    int len = first_max_pos(tok + (int64_t)n * ctx, ctx, lane) + 1, p = 0;
     if (pfx) {
         const int bn = n / G * G;
         if (bn != n) {
@@ -401,7 +335,7 @@ hipError_t launch_text_lens_scan(const int32_t* tok, int32_t* starts, int32_t* p
     if (pfx && G < 2) return hipErrorInvalidValue;
     int32_t* lens = pfx ? pfx + n_text : lens_ws;
     if (!lens) return hipErrorInvalidValue;
-    const hipError_t st = launch<text_lens_kernel>(dim3((n_text + 3) / 4), dim3(256), 0, stream, tok, starts, pfx, lens, n_text, ctx, G);
+    const hipError_t st = launch<text_lens_kernel>(row_grid(n_text), dim3(256), 0, stream, tok, starts, pfx, lens, n_text, ctx, G);
     if (st != hipSuccess) return st;
     return launch<text_scan_kernel>(dim3(1), dim3(1024), 0, stream, starts, pfx, lens, n_text, G);
 }
@@ -420,8 +354,8 @@ __global__ __launch_bounds__(256) void text_embed_kernel(const int32_t* __restri
                                                          const int32_t* __restrict__ starts,
                                                          const int32_t* __restrict__ pfx, int n_text,
                                                          int ctx, int d, int vocab) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    const int lane = row_lane();
+    const int64_t row = wave_row<int64_t>();
     if (row >= (int64_t)n_text * ctx) return;
     const int t = (int)(row % ctx);
     const int64_t n = row / ctx;
@@ -441,18 +375,7 @@ __global__ __launch_bounds__(256) void text_embed_kernel(const int32_t* __restri
     f32x4_t* xr = (f32x4_t*)(x + out_row * d);
     for (int c = lane; c < (d >> 2); c += 64) xr[c] = er[c] + pr[c];
     if (t == 0 && !starts) {
-        // arg-max over the ctx ids of text n; ties -> lowest position
-        int best = -1, best_t = 0;
-        for (int tt = lane; tt < ctx; tt += 64) {
-            const int v = tok[n * ctx + tt];
-            if (v > best) { best = v; best_t = tt; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const int ov = __shfl_xor(best, o, 64);
-            const int ot = __shfl_xor(best_t, o, 64);
-            if (ov > best || (ov == best && ot < best_t)) { best = ov; best_t = ot; }
-        }
+        const int best_t = first_max_pos(tok + n * ctx, ctx, lane);
         if (lane == 0) eot_row[n] = (int32_t)(n * ctx + best_t);
     }
 }
@@ -463,8 +386,7 @@ hipError_t launch_text_embed(const int32_t* tok, const float* tok_emb, const flo
     if (d % 4 != 0) return hipErrorInvalidValue;
     const int64_t rows = (int64_t)n_text * ctx;
     if (rows == 0) return hipSuccess;
-    const int grid = (int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
-    return launch<text_embed_kernel>(dim3(grid), dim3(256), 0, stream, tok, tok_emb, pos, x, eot_row, starts, pfx, n_text, ctx, d, vocab);
+    return launch<text_embed_kernel>(row_grid(rows), dim3(256), 0, stream, tok, tok_emb, pos, x, eot_row, starts, pfx, n_text, ctx, d, vocab);
 }
 
 // ---------------------------------------------------------------------------
@@ -472,8 +394,8 @@ hipError_t launch_text_embed(const int32_t* tok, const float* tok_emb, const flo
 // `x / x.norm(dim=-1, keepdim=True)` -- retrieval_ref.py:243)
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void l2norm_rows_kernel(float* __restrict__ x, int rows, int d) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    const int lane = row_lane();
+    const int row = wave_row();
     if (row >= rows) return;
     float* xr = x + (int64_t)row * d;
     float s = 0.f;
@@ -484,15 +406,13 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(float* __restrict__ x,
 
 hipError_t launch_l2norm_rows(float* x, int rows, int d, hipStream_t stream) {
     if (rows == 0) return hipSuccess;
-    const int grid = (rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
-    return launch<l2norm_rows_kernel>(dim3(grid), dim3(256), 0, stream, x, rows, d);
+    return launch<l2norm_rows_kernel>(row_grid(rows), dim3(256), 0, stream, x, rows, d);
 }
 
 // ---------------------------------------------------------------------------
 // exact GELU 0.5 x (1 + erf(x / sqrt 2)) in place (towers with TVC_ACT_GELU: n % 8 == 0 / n % 4 == 0 -- widths are
 // multiples of 64)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 template <bool F16>
 __global__ __launch_bounds__(256) void gelu_erf_16_kernel(uint16_t* __restrict__ x, int64_t n8) {
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n8; t += (int64_t)gridDim.x * blockDim.x) {
@@ -511,20 +431,19 @@ __global__ __launch_bounds__(256) void gelu_erf_f32_kernel(float* __restrict__ x
         ((f32x4_t*)x)[t] = v;
     }
 }
-template <bool F16>
-static hipError_t launch_gelu_erf_16(uint16_t* x, int64_t n, hipStream_t stream) {
+hipError_t launch_gelu_erf_16(uint16_t* x, int64_t n, int f16, hipStream_t stream) {
     if (n % 8 != 0 || n < 0) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
     const int64_t n8 = n / 8;
-    return launch<gelu_erf_16_kernel<F16>>(dim3((int)((n8 + 255) / 256 < 16384 ? (n8 + 255) / 256 : 16384)), dim3(256), 0, stream, x, n8);
+    return dispatch<true, false>(f16 != 0, [&](auto h) {
+        return launch<gelu_erf_16_kernel<h.value>>(stride_grid(n8, 16384), dim3(256), 0, stream, x, n8);
+    });
 }
-hipError_t launch_gelu_erf_bf16(uint16_t* x, int64_t n, hipStream_t stream) { return launch_gelu_erf_16<false>(x, n, stream); }
-hipError_t launch_gelu_erf_f16(uint16_t* x, int64_t n, hipStream_t stream) { return launch_gelu_erf_16<true>(x, n, stream); }
 hipError_t launch_gelu_erf_f32(float* x, int64_t n, hipStream_t stream) {
     if (n % 4 != 0 || n < 0) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
     const int64_t n4 = n / 4;
-    return launch<gelu_erf_f32_kernel>(dim3((int)((n4 + 255) / 256 < 16384 ? (n4 + 255) / 256 : 16384)), dim3(256), 0, stream, x, n4);
+    return launch<gelu_erf_f32_kernel>(stride_grid(n4, 16384), dim3(256), 0, stream, x, n4);
 }
 
 // ---------------------------------------------------------------------------
@@ -557,10 +476,7 @@ hipError_t launch_split_planes(const float* x, uint16_t* out, int64_t rows, int 
                                hipStream_t stream) {
     if (d % 4 != 0 || planes < 1 || planes > 2) return hipErrorInvalidValue;
     if (rows == 0) return hipSuccess;
-    const int64_t total = rows * (d >> 2);
-    int grid = (int)((total + 255) / 256);
-    if (grid > 16384) grid = 16384;
-    return launch<split_planes_kernel>(dim3(grid), dim3(256), 0, stream, x, out, rows, d, planes);
+    return launch<split_planes_kernel>(stride_grid(rows * (d >> 2), 16384), dim3(256), 0, stream, x, out, rows, d, planes);
 }
 
 // ---------------------------------------------------------------------------
@@ -571,8 +487,8 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const uint16_t* __rest
                                                           const int32_t* __restrict__ idx,
                                                           int64_t idx_offset, int n,
                                                           float* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    const int lane = row_lane();
+    const int row = wave_row();
     if (row >= n) return;
     const int64_t src = (int64_t)idx[row] - idx_offset;
     float* o = out + (int64_t)row * D;
@@ -592,6 +508,5 @@ hipError_t launch_gather_rows(const uint16_t* bank, int64_t ld, int planes, int 
                               const int32_t* idx, int64_t idx_offset, int n, float* out,
                               hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    const int grid = (n + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
-    return launch<gather_rows_kernel>(dim3(grid), dim3(256), 0, stream, bank, ld, planes, D, R, idx, idx_offset, n, out);
+    return launch<gather_rows_kernel>(row_grid(n), dim3(256), 0, stream, bank, ld, planes, D, R, idx, idx_offset, n, out);
 }

@@ -3,19 +3,13 @@
 #pragma once
 #include "gemm_ring.hpp"
 #include "kernels.hpp"
+#include "rows.hpp"      // quick_gelu
 
 struct GemmEpilogue {
     const float* bias;     // [I] or nullptr
     void* out;             // [J, ldo]
     int64_t ldo;
 };
-
-__device__ __forceinline__ float quick_gelu(float x) {
-    // x * sigmoid(1.702 x) = x / (1 + 2^(-1.702 log2(e) x)): v_exp_f32 + v_rcp_f32 (1 ulp each; the
-    // result is rounded to bf16 anyway) instead of an IEEE division.  x -> -inf: 2^(+inf) = inf,
-    // rcp(inf) = 0, x * 0 = -0.
-    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.4554670f * x));
-}
 
 // out[j, i..i+3] for one lane: i = 4 consecutive out-features.  The vector
 // path needs all four in range and a 4-element-aligned leading dimension;

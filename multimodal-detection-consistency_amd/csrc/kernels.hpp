@@ -88,8 +88,7 @@ hipError_t launch_text_lens_scan(const int32_t* tok, int32_t* starts, int32_t* p
                                  hipStream_t stream, int32_t* lens_ws);
 hipError_t launch_l2norm_rows(float* x, int rows, int d, hipStream_t stream);
 // exact (erf) GELU in place: the activation of towers with TVC_ACT_GELU, after a store-only FC1
-hipError_t launch_gelu_erf_bf16(uint16_t* x, int64_t n, hipStream_t stream);
-hipError_t launch_gelu_erf_f16(uint16_t* x, int64_t n, hipStream_t stream);
+hipError_t launch_gelu_erf_16(uint16_t* x, int64_t n, int f16, hipStream_t stream);      // bf16, or IEEE fp16 with f16
 hipError_t launch_gelu_erf_f32(float* x, int64_t n, hipStream_t stream);
 hipError_t launch_split_planes(const float* x, uint16_t* out, int64_t rows, int d, int planes,
                                hipStream_t stream);

@@ -1,8 +1,10 @@
-// The one place a kernel is started (included by the .hip files only; kernels.hpp and handle.hpp stay free of it).
+// The one place a kernel is started, and the grids of the two common kernel shapes (included by the .hip files only;
+// kernels.hpp and handle.hpp stay free of it).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <type_traits>
+#include "rows.hpp"      // ROWS_PER_BLOCK
 
 // Starts Kernel and returns hipGetLastError().  MaxLds > 0: the kernel takes more than 64 KiB of dynamic LDS, so its first
 // launch registers MaxLds bytes with the runtime (once per kernel, thread-safe: the Python lock is per engine, two engines
@@ -29,4 +31,12 @@ hipError_t dispatch(T v, F&& f) {
     hipError_t st = hipErrorInvalidValue;
     (void)(... || (v == Vs && ((st = f(std::integral_constant<decltype(Vs), Vs>{})), true)));
     return st;
+}
+
+// Grid of a wave-per-row kernel: ROWS_PER_BLOCK rows per 256-thread workgroup.
+inline dim3 row_grid(int64_t rows) { return dim3((unsigned)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)); }
+// Grid of a grid-stride kernel over `total` items on 256 threads, at most `cap` workgroups (each kernel keeps its own cap).
+inline dim3 stride_grid(int64_t total, int64_t cap) {
+    const int64_t g = (total + 255) / 256;
+    return dim3((unsigned)(g < cap ? g : cap));
 }

@@ -8,6 +8,7 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "rows.hpp"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
@@ -17,8 +18,6 @@ constexpr int PG_BM = 128;      // tokens per workgroup tile
 constexpr int PG_BN = 128;      // out-features per workgroup tile
 constexpr int PG_BK = 32;       // k per LDS stage (128 B of a row)
 constexpr int PG_LD = 36;       // LDS row stride in floats: 16-byte aligned rows, conflict-free b128 fragment reads
-
-__device__ __forceinline__ float quick_gelu_f32(float v) { return v / (1.0f + expf(-1.702f * v)); }
 
 // out[j, i] (op)= sum_k X[j, k] * W[i, k] + bias[i]
 //   epi 0: store      1: QuickGELU, store      2: out += (residual add in place)
@@ -106,7 +105,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
                 if (j >= J) continue;
                 float v = acc[tm][tn][r] + bv;
                 float* o = out + j * ldo + f;
-                if (epi == 1) v = quick_gelu_f32(v);
+                if (epi == 1) v = quick_gelu_exact(v);
                 if (epi == 2) v += *o;
                 *o = v;
             }
@@ -231,8 +230,7 @@ hipError_t launch_im2col_f32(const float* pix, float* out, int B, int image, int
     if (B <= 0) return hipSuccess;
     const int g = image / patch;
     const int64_t total = (int64_t)B * g * g * 3 * patch * patch;
-    int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    return launch<im2col_f32_kernel>(dim3(grid), dim3(256), 0, stream, pix, out, B, image, patch);
+    return launch<im2col_f32_kernel>(stride_grid(total, 16384), dim3(256), 0, stream, pix, out, B, image, patch);
 }
 
 hipError_t launch_gather_f32_rows(const float* x, int64_t ld, const int32_t* idx, int64_t idx_mul, float* out, int n,
@@ -240,6 +238,5 @@ hipError_t launch_gather_f32_rows(const float* x, int64_t ld, const int32_t* idx
     if (n <= 0) return hipSuccess;
     if (d % 4 != 0) return hipErrorInvalidValue;
     const int64_t total = (int64_t)n * (d >> 2);
-    int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    return launch<gather_f32_rows_kernel>(dim3(grid), dim3(256), 0, stream, x, ld, idx, idx_mul, out, n, d);
+    return launch<gather_f32_rows_kernel>(stride_grid(total, 8192), dim3(256), 0, stream, x, ld, idx, idx_mul, out, n, d);
 }

@@ -1,23 +1,15 @@
 // Row / elementwise kernels of the latent-diffusion reference generator (tvc_sd.cpp): everything between the GEMMs of
 // the UNet and the VAE decoder.  Activations are bf16 NHWC -- [n * H * W tokens, C channels], channels contiguous -- so
 // that every convolution is a GEMM over K-contiguous token rows (3x3: rows gathered by im2col3x3_kernel; 1x1: the rows
-// themselves) and every normalisation is a streaming pass; statistics and arithmetic are fp32.
+// themselves) and every normalisation is a streaming pass; statistics and arithmetic are fp32.  The 8-wide bf16
+// unpack / pack, the row decode and the erf GELU come from rows.hpp.
 #include "common.hpp"
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "rows.hpp"
 
 namespace {
 
-__device__ __forceinline__ void unpack8(const u32x4_t v, float* f) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __uint_as_float(v[i] << 16);
-        f[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
-    }
-}
-__device__ __forceinline__ u32x4_t pack8(const float* f) {
-    return u32x4_t{pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7])};
-}
 __device__ __forceinline__ float silu_f(float v) { return v / (1.0f + __expf(-v)); }
 
 // Token row of pixel t (= y * W + x) of image img.  Dense layout: img * HW + t.  PADDED layout (the operands and the
@@ -223,8 +215,8 @@ __global__ __launch_bounds__(256) void ln_bf16_kernel(const uint16_t* __restrict
                                                       const float* __restrict__ b, uint16_t* __restrict__ y, int64_t rows,
                                                       int C, float eps, const uint16_t* __restrict__ add,
                                                       uint16_t* __restrict__ sum_out) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = row_lane();
+    const int64_t row = wave_row<int64_t>();
     if (row >= rows) return;
     const int cv = C >> 3;
     const u32x4_t* xr = (const u32x4_t*)(x + row * C);
@@ -284,7 +276,7 @@ __global__ __launch_bounds__(256) void geglu_kernel(const uint16_t* __restrict__
         unpack8(*(const u32x4_t*)(in + r * 2 * Ch + c * 8), a);
         unpack8(*(const u32x4_t*)(in + r * 2 * Ch + Ch + c * 8), g);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) a[i] *= 0.5f * g[i] * (1.0f + erff(g[i] * 0.70710678118654752f));
+        for (int i = 0; i < 8; ++i) a[i] *= gelu_erf(g[i]);
         *(u32x4_t*)(out + r * Ch + c * 8) = pack8(a);
     }
 }
@@ -531,10 +523,8 @@ __global__ __launch_bounds__(256) void resize_norm_kernel(const float* __restric
     }
 }
 
-inline int grid_for(int64_t total) {
-    const int64_t g = (total + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
-}
+// never empty: the entry points below launch for total == 0 too
+inline dim3 grid_for(int64_t total) { return stride_grid(total > 0 ? total : 1, 65536); }
 
 }  // namespace
 
@@ -543,12 +533,12 @@ hipError_t sd_im2col3x3(const uint16_t* in, uint16_t* out, int n, int Hi, int Wi
     const int Hs = up ? 2 * Hi : Hi, Ws = up ? 2 * Wi : Wi;
     const int Ho = (Hs - 1) / stride + 1, Wo = (Ws - 1) / stride + 1;       // padding 1, kernel 3
     const int64_t total = (int64_t)n * Ho * Wo * 9 * (C >> 3);
-    return launch<im2col3x3_kernel>(dim3(grid_for(total)), dim3(256), 0, st, in, out, n, Hi, Wi, C, Ho, Wo, stride, up);
+    return launch<im2col3x3_kernel>(grid_for(total), dim3(256), 0, st, in, out, n, Hi, Wi, C, Ho, Wo, stride, up);
 }
 
 hipError_t sd_im2col_in(const float* in, uint16_t* out, int n, int Cin, int H, int W, int Kp, float scale, hipStream_t st) {
     if (9 * Cin > Kp) return hipErrorInvalidValue;
-    return launch<im2col_in_kernel>(dim3(grid_for((int64_t)n * H * W * Kp)), dim3(256), 0, st, in, out, n, Cin, H, W, Kp, scale);
+    return launch<im2col_in_kernel>(grid_for((int64_t)n * H * W * Kp), dim3(256), 0, st, in, out, n, Cin, H, W, Kp, scale);
 }
 
 // ws: >= n * nslab * groups * 2 + n * groups * 2 floats (sd_groupnorm_ws_floats)
@@ -578,59 +568,59 @@ hipError_t sd_groupnorm(const uint16_t* x, const float* tadd, int64_t ld_t, cons
 hipError_t sd_relayout(const uint16_t* in, uint16_t* out, int n, int H, int W, int C, int in_pad, int out_pad, int up, hipStream_t st) {
     if (C % 8 != 0 || (up && ((H | W) & 1))) return hipErrorInvalidValue;
     const int64_t rows = out_pad ? (int64_t)n * (H + 2) * (W + 2) : (int64_t)n * H * W;
-    return launch<relayout_kernel>(dim3(grid_for(rows * (C >> 3))), dim3(256), 0, st, in, out, n, H, W, C, in_pad, out_pad, up);
+    return launch<relayout_kernel>(grid_for(rows * (C >> 3)), dim3(256), 0, st, in, out, n, H, W, C, in_pad, out_pad, up);
 }
 
 hipError_t sd_add_padded(const uint16_t* a, const uint16_t* b_padded, uint16_t* out, int n, int H, int W, int C, hipStream_t st) {
     if (C % 8 != 0) return hipErrorInvalidValue;
-    return launch<add_padded_kernel>(dim3(grid_for((int64_t)n * H * W * (C >> 3))), dim3(256), 0, st, a, b_padded, out, n, H, W, C);
+    return launch<add_padded_kernel>(grid_for((int64_t)n * H * W * (C >> 3)), dim3(256), 0, st, a, b_padded, out, n, H, W, C);
 }
 
 hipError_t sd_layernorm_bf16(const uint16_t* x, const float* g, const float* b, uint16_t* y, int64_t rows, int C, float eps,
                              hipStream_t st, const uint16_t* add, uint16_t* sum_out) {
     if (C % 8 != 0 || C > 1536 || ((add != nullptr) != (sum_out != nullptr))) return hipErrorInvalidValue;
     if (rows <= 0) return hipSuccess;
-    return launch<ln_bf16_kernel>(dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, g, b, y, rows, C, eps, add, sum_out);
+    return launch<ln_bf16_kernel>(row_grid(rows), dim3(256), 0, st, x, g, b, y, rows, C, eps, add, sum_out);
 }
 
 hipError_t sd_geglu(const uint16_t* in, uint16_t* out, int64_t rows, int Ch, hipStream_t st) {
     if (Ch % 8 != 0) return hipErrorInvalidValue;
-    return launch<geglu_kernel>(dim3(grid_for(rows * (Ch >> 3))), dim3(256), 0, st, in, out, rows, Ch);
+    return launch<geglu_kernel>(grid_for(rows * (Ch >> 3)), dim3(256), 0, st, in, out, rows, Ch);
 }
 
 hipError_t sd_add_bf16(const uint16_t* a, const uint16_t* b, uint16_t* out, int64_t n, hipStream_t st) {
     if (n % 8 != 0) return hipErrorInvalidValue;
-    return launch<add_bf16_kernel>(dim3(grid_for(n >> 3)), dim3(256), 0, st, a, b, out, n >> 3);
+    return launch<add_bf16_kernel>(grid_for(n >> 3), dim3(256), 0, st, a, b, out, n >> 3);
 }
 
 hipError_t sd_concat(const uint16_t* a, int Ca, const uint16_t* b, int Cb, uint16_t* out, int64_t tokens, hipStream_t st) {
     if (Ca % 8 != 0 || Cb % 8 != 0) return hipErrorInvalidValue;
-    return launch<concat_kernel>(dim3(grid_for(tokens * ((Ca + Cb) >> 3))), dim3(256), 0, st, a, Ca, b, Cb, out, tokens);
+    return launch<concat_kernel>(grid_for(tokens * ((Ca + Cb) >> 3)), dim3(256), 0, st, a, Ca, b, Cb, out, tokens);
 }
 
 hipError_t sd_cast_silu(const float* in, uint16_t* out, int64_t n, int silu, hipStream_t st) {
-    return launch<cast_silu_kernel>(dim3(grid_for(n)), dim3(256), 0, st, in, out, n, silu);
+    return launch<cast_silu_kernel>(grid_for(n), dim3(256), 0, st, in, out, n, silu);
 }
 
 hipError_t sd_tokens_to_nchw(const float* in, int64_t ld, float* out, int n, int C, int H, int W, float mul, float add, int clamp01,
                              int in_pad, hipStream_t st) {
-    return launch<tokens_to_nchw_kernel>(dim3(grid_for((int64_t)n * C * H * W)), dim3(256), 0, st, in, ld, out, n, C, H, W, mul, add,
+    return launch<tokens_to_nchw_kernel>(grid_for((int64_t)n * C * H * W), dim3(256), 0, st, in, ld, out, n, C, H, W, mul, add,
                                          clamp01, in_pad);
 }
 
 hipError_t sd_pointwise_small(const float* in, const float* w, const float* bias, float* out, int n, int C, int HW, float in_scale,
                               hipStream_t st) {
     if (C > 8) return hipErrorInvalidValue;
-    return launch<pointwise_small_kernel>(dim3(grid_for((int64_t)n * C * HW)), dim3(256), 0, st, in, w, bias, out, n, C, HW, in_scale);
+    return launch<pointwise_small_kernel>(grid_for((int64_t)n * C * HW), dim3(256), 0, st, in, w, bias, out, n, C, HW, in_scale);
 }
 
 hipError_t sd_cfg(const float* e, float* out, int64_t n, float g, hipStream_t st) {
-    return launch<cfg_kernel>(dim3(grid_for(n)), dim3(256), 0, st, e, out, n, g);
+    return launch<cfg_kernel>(grid_for(n), dim3(256), 0, st, e, out, n, g);
 }
 
 hipError_t sd_lincomb(float* out, const float* sample, float cs, float ce, const float* e0, float c0, const float* e1, float c1,
                       const float* e2, float c2, const float* e3, float c3, int64_t n, hipStream_t st) {
-    return launch<lincomb_kernel>(dim3(grid_for(n)), dim3(256), 0, st, out, sample, cs, ce, e0, c0, e1, c1, e2, c2, e3, c3, n);
+    return launch<lincomb_kernel>(grid_for(n), dim3(256), 0, st, out, sample, cs, ce, e0, c0, e1, c1, e2, c2, e3, c3, n);
 }
 
 hipError_t sd_softmax_rows(const float* s, uint16_t* p, int64_t rows, int T, float scale, hipStream_t st) {
@@ -639,15 +629,15 @@ hipError_t sd_softmax_rows(const float* s, uint16_t* p, int64_t rows, int T, flo
 }
 
 hipError_t sd_nchw_to_tokens(const float* in, uint16_t* out, int n, int C, int HW, hipStream_t st) {
-    return launch<nchw_to_tokens_kernel>(dim3(grid_for((int64_t)n * C * HW)), dim3(256), 0, st, in, out, n, C, HW);
+    return launch<nchw_to_tokens_kernel>(grid_for((int64_t)n * C * HW), dim3(256), 0, st, in, out, n, C, HW);
 }
 
 hipError_t sd_tokens_bf16_to_nchw(const uint16_t* in, float* out, int n, int C, int HW, hipStream_t st) {
-    return launch<tokens_bf16_to_nchw_kernel>(dim3(grid_for((int64_t)n * C * HW)), dim3(256), 0, st, in, out, n, C, HW);
+    return launch<tokens_bf16_to_nchw_kernel>(grid_for((int64_t)n * C * HW), dim3(256), 0, st, in, out, n, C, HW);
 }
 
 hipError_t sd_timestep_embed(uint16_t* out, int n, int dim, float t, hipStream_t st) {
-    return launch<timestep_embed_kernel>(dim3(grid_for((int64_t)n * dim)), dim3(256), 0, st, out, n, dim, t);
+    return launch<timestep_embed_kernel>(grid_for((int64_t)n * dim), dim3(256), 0, st, out, n, dim, t);
 }
 
 // in fp32 [n, 3, H, W] -> out fp32 [n, 3, S, S]: resize to (Hr, Wr), crop at (oy, ox), (v - mean) / std; cubic: bicubic else bilinear
@@ -657,7 +647,7 @@ hipError_t sd_resize_norm(const float* in, float* out, int n, int H, int W, int 
     if (H < 1 || W < 1 || Hr < S || Wr < S || oy < 0 || ox < 0 || oy + S > Hr || ox + S > Wr) return hipErrorInvalidValue;
     const int64_t total = (int64_t)n * 3 * S * S;
     return dispatch<1, 0>(cubic ? 1 : 0, [&](auto c) {
-        return launch<resize_norm_kernel<c.value>>(dim3(grid_for(total)), dim3(256), 0, st, in, out, n, H, W, Hr, Wr, oy, ox, S, mean[0],
+        return launch<resize_norm_kernel<c.value>>(grid_for(total), dim3(256), 0, st, in, out, n, H, W, Hr, Wr, oy, ox, S, mean[0],
                                                    mean[1], mean[2], sd[0], sd[1], sd[2]);
     });
 }

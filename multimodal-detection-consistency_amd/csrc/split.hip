@@ -6,10 +6,11 @@
 //
 // Plane layout of a GEMM operand: [rows, 2 * K] bf16, hi plane in columns 0 .. K-1, lo plane in K .. 2K-1 -- the
 // GEMM's "planes" mechanism (gemm_core.hpp) addresses them as column offsets, so the tower GEMMs run on the same
-// ring kernel as the bf16 mode with planes = 3.
+// ring kernel as the bf16 mode with planes = 3.  The row shape, the LayerNorm statistics and the GELU forms come from rows.hpp.
 #include "common.hpp"
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "rows.hpp"
 
 namespace {
 
@@ -36,58 +37,37 @@ __global__ __launch_bounds__(256) void ln_split_kernel(float* __restrict__ x, in
                                                        const float* __restrict__ d1, const float* __restrict__ d2, int write_x,
                                                        const float* __restrict__ g, const float* __restrict__ b,
                                                        uint16_t* __restrict__ planes, float* __restrict__ y32, int rows, int d) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = row_lane();
+    const int row = wave_row();
     if (row >= rows) return;
     const int64_t src = row_idx ? (int64_t)row_idx[row] : (int64_t)row;
     f32x4_t* xr = (f32x4_t*)(x + src * x_row_stride);
     const f32x4_t* p1 = d1 ? (const f32x4_t*)(d1 + src * x_row_stride) : nullptr;
     const f32x4_t* p2 = d2 ? (const f32x4_t*)(d2 + src * x_row_stride) : nullptr;
     const int nv = d >> 2;
-    f32x4_t v[4];
+    f32x4_t v[4] = {};
     float s = 0.f;
+    for_pieces(lane, nv, [&](int i, int c) {
+        v[i] = xr[c];
+        if (p1) v[i] += p1[c];
+        if (p2) v[i] += p2[c];
+        if (write_x && (p1 || p2)) xr[c] = v[i];
+        s += piece_sum(v[i]);
+    });
+    const float mean = row_mean(s, d);
+    const float rstd = row_rstd<true>(v, mean, lane, nv, d);      // IEEE sqrt and division: this mode's bits are under contract
+    for_pieces(lane, nv, [&](int i, int c) {
+        const f32x4_t o = ln_affine(v[i], mean, rstd, g, b, c);
+        if (y32) ((f32x4_t*)(y32 + (int64_t)row * d))[c] = o;
+        if (planes) {
+            float h[4], l[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + i * 64;
-        v[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        if (c < nv) {
-            v[i] = xr[c];
-            if (p1) v[i] += p1[c];
-            if (p2) v[i] += p2[c];
-            if (write_x && (p1 || p2)) xr[c] = v[i];
-            s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+            for (int t = 0; t < 4; ++t) split2(o[t], h[t], l[t]);
+            uint16_t* pr = planes + (int64_t)row * 2 * d + c * 4;
+            *(u32x2_t*)pr = u32x2_t{pack_bf16x2(h[0], h[1]), pack_bf16x2(h[2], h[3])};
+            *(u32x2_t*)(pr + d) = u32x2_t{pack_bf16x2(l[0], l[1]), pack_bf16x2(l[2], l[3])};
         }
-    }
-    const float mean = wave_sum(s) / (float)d;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + i * 64;
-        if (c < nv) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) { const float dl = v[i][t] - mean; q += dl * dl; }
-        }
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)d + 1e-5f);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + i * 64;
-        if (c < nv) {
-            const f32x4_t gg = ((const f32x4_t*)g)[c], bb = ((const f32x4_t*)b)[c];
-            f32x4_t o;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) o[t] = (v[i][t] - mean) * rstd * gg[t] + bb[t];
-            if (y32) ((f32x4_t*)(y32 + (int64_t)row * d))[c] = o;
-            if (planes) {
-                float h[4], l[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) split2(o[t], h[t], l[t]);
-                uint16_t* pr = planes + (int64_t)row * 2 * d + c * 4;
-                *(u32x2_t*)pr = u32x2_t{pack_bf16x2(h[0], h[1]), pack_bf16x2(h[2], h[3])};
-                *(u32x2_t*)(pr + d) = u32x2_t{pack_bf16x2(l[0], l[1]), pack_bf16x2(l[2], l[3])};
-            }
-        }
-    }
+    });
 }
 
 // fp32 rows [rows, ld_in] (first K columns used) -> planes [rows, 2 * Kp], zero padded from K to Kp; gelu 1 applies
@@ -106,8 +86,8 @@ __global__ __launch_bounds__(256) void rows_split_kernel(const float* __restrict
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float u = v[e];
-            if (gelu == 1) u = u / (1.0f + expf(-1.702f * u));
-            else if (gelu == 2) u = 0.5f * u * (1.0f + erff(u * 0.70710678118654752f));
+            if (gelu == 1) u = quick_gelu_exact(u);
+            else if (gelu == 2) u = gelu_erf(u);
             split2(u, h[e], l[e]);
         }
         uint16_t* o = out + r * (int64_t)(2 * Kp) + c * 4;
@@ -312,16 +292,14 @@ hipError_t launch_ln_split(float* x, int64_t x_row_stride, const int32_t* row_id
                            const float* g, const float* b, uint16_t* planes, float* y32, int rows, int d, hipStream_t stream) {
     if (d % 4 != 0 || d > 1024 || rows < 0 || (!planes && !y32)) return hipErrorInvalidValue;
     if (rows == 0) return hipSuccess;
-    return launch<ln_split_kernel>(dim3((rows + 3) / 4), dim3(256), 0, stream, x, x_row_stride, row_idx, d1, d2, write_x, g, b, planes,
+    return launch<ln_split_kernel>(row_grid(rows), dim3(256), 0, stream, x, x_row_stride, row_idx, d1, d2, write_x, g, b, planes,
                                    y32, rows, d);
 }
 
 hipError_t launch_rows_split(const float* x, int64_t ld_in, uint16_t* out, int64_t rows, int K, int Kp, int gelu, hipStream_t stream) {
     if (K % 4 != 0 || Kp % 4 != 0 || Kp < K || rows < 0) return hipErrorInvalidValue;
     if (rows == 0) return hipSuccess;
-    const int64_t total = rows * (Kp >> 2);
-    int grid = (int)((total + 255) / 256 < 32768 ? (total + 255) / 256 : 32768);
-    return launch<rows_split_kernel>(dim3(grid), dim3(256), 0, stream, x, ld_in, out, rows, K, Kp, gelu);
+    return launch<rows_split_kernel>(stride_grid(rows * (Kp >> 2), 32768), dim3(256), 0, stream, x, ld_in, out, rows, K, Kp, gelu);
 }
 
 // starts == nullptr: n_seq sequences of seq_len rows; else packed rows (+ pfx: shared prefixes), seq_len = the maximum

@@ -99,7 +99,7 @@ int run_layers(tvc_handle* h, const tvc_tower_arch& a, const tvc_layer_weights* 
             g.b_rows_padded = true; g.f16 = f16;
             HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
             if (a.act == TVC_ACT_GELU)
-                HIP_TRY(f16 ? launch_gelu_erf_f16(pb.MLPc, (int64_t)n_seq * a.mlp, st) : launch_gelu_erf_bf16(pb.MLPc, (int64_t)n_seq * a.mlp, st));
+                HIP_TRY(launch_gelu_erf_16(pb.MLPc, (int64_t)n_seq * a.mlp, f16, st));
             g = gemm_launch(w.w2, a.mlp, d, pb.MLPc, a.mlp, n_seq, a.mlp, w.b2, pb.D2c, d, TVC_EPI_BF16);
             g.b_rows_padded = true; g.f16 = f16;
             HIP_TRY(timed_gemm(h, g, st, WS_SPLITK + wso));
@@ -128,7 +128,7 @@ int run_layers(tvc_handle* h, const tvc_tower_arch& a, const tvc_layer_weights* 
             HIP_TRY(launch_gelu_fwd(U, MLP, (int64_t)rows * a.mlp, st));
         } else if (a.act == TVC_ACT_GELU) {
             ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)rows * a.mlp * 4.0);
-            HIP_TRY(f16 ? launch_gelu_erf_f16(MLP, (int64_t)rows * a.mlp, st) : launch_gelu_erf_bf16(MLP, (int64_t)rows * a.mlp, st));
+            HIP_TRY(launch_gelu_erf_16(MLP, (int64_t)rows * a.mlp, f16, st));
         }
         g = gemm_launch(w.w2, a.mlp, d, MLP, a.mlp, rows, a.mlp, w.b2, D2, d, TVC_EPI_BF16);
         g.b_rows_padded = true; g.f16 = f16; g.splitk_small = gs != nullptr;

@@ -1,0 +1,138 @@
+"""Bit-identity of two builds of libtvc_hip.so (a refactor against its parent commit):
+
+    python scripts/lib_ab.py OLD.so NEW.so [--timeout 240] [--keep DIR]
+
+One fresh child process per library (selected with TVC_LIB_PATH, each child under its own ``timeout -k 10``; the second starts
+only if the first exited 0).  A child runs seed-fixed inputs through the library and writes one .npy file per result; the
+parent compares the two sets byte for byte and prints one line per array and one JSON summary line.  Exit status 0 = every
+array identical.
+
+Covered: the towers at the toy CLIP geometry of the GPU tests with seeded random weights -- encode_image (B = 3), encode_text
+with group = 3 over 6 texts of different lengths (packing and prefix sharing on), encode_text_hidden -- in all four
+precisions, each with TVC_OPT_POOLED_LAST_LAYER on and off; the gradient path (encode_image_grad + encode_image_backward,
+B = 2); the kernel entries layernorm, layernorm_f16 and layernorm_backward (with and without dres) on the piece-loop edge
+shapes; one latent-diffusion transformer block and one resnet block at 8 x 8 (ln_bf16_kernel with and without `add`, GEGLU,
+the adds).
+"""
+import argparse
+import importlib
+import json
+import os
+import subprocess
+import sys
+import tempfile
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parents[1]
+LN_SHAPES = ((1, 64), (5, 260), (7, 1024))
+TEXT_LENS = (19, 12, 9, 17, 15, 5)      # ids between SOT and EOT of the 6 texts
+
+
+def child(out_dir: Path) -> None:
+    import torch
+    sys.path.insert(0, str(ROOT))
+    pkg = importlib.import_module("multimodal-detection-consistency_amd")
+    L = pkg._lib
+
+    def save(name: str, t) -> None:
+        t = t.detach().cpu().contiguous()
+        if t.dtype in (torch.bfloat16, torch.float16):
+            t = t.view(torch.int16)
+        np.save(out_dir / (name + ".npy"), t.numpy())
+
+    arch = pkg.get_arch("ViT-T/16-test")
+    vw, tw = pkg.synth.make_clip_weights(arch, seed=0)
+    eng = pkg.TVCEngine(arch, vw, tw)
+    imgs = pkg.synth.make_images(3, arch.image_size, seed=1).cuda()
+    # 2 groups of (original, 2 variants), each text cut to a length of its own
+    toks = pkg.synth.make_tokens(2, 2, arch.ctx, seed=2, min_len=TEXT_LENS[0], max_len=TEXT_LENS[0]).view(-1, arch.ctx)
+    for j, n in enumerate(TEXT_LENS):
+        toks[j, 1 + n] = pkg.synth.EOT
+        toks[j, 2 + n:] = 0
+    toks = toks.cuda()
+    for prec in ("bf16", "fp16", "split", "fp32"):
+        eng.set_precision(prec)
+        for pooled in (1, 0):
+            eng.set_option(L.TVC_OPT_POOLED_LAST_LAYER, pooled)
+            tag = f"{prec}_pooled{pooled}"
+            save(f"image_{tag}", eng.encode_image(imgs))
+            save(f"text_{tag}", eng.encode_text(toks, group=3))
+            save(f"hidden_{tag}", eng.encode_text_hidden(toks))
+    eng.set_precision("bf16")
+    eng.set_option(L.TVC_OPT_POOLED_LAST_LAYER, 1)
+    g = torch.Generator().manual_seed(3)
+    px = imgs[:2].contiguous()
+    save("grad_fwd", eng.encode_image_grad(px))
+    save("grad_bwd", eng.encode_image_backward(torch.randn((2, arch.embed_dim), generator=g).cuda()))
+    for rows, d in LN_SHAPES:
+        x = (torch.randn((rows, d), generator=g) * 3 + 1).cuda()
+        gam, bet = torch.randn(d, generator=g).cuda(), torch.randn(d, generator=g).cuda()
+        dy = torch.randn((rows, d), generator=g).to(torch.bfloat16).cuda()
+        dres = torch.randn((rows, d), generator=g).cuda()
+        save(f"ln_{rows}x{d}", eng.layernorm(x, gam, bet))
+        save(f"ln_f16_{rows}x{d}", eng.layernorm_f16(x, gam, bet))
+        save(f"ln_bwd_{rows}x{d}", eng.layernorm_backward(x, dy, gam, None))
+        save(f"ln_bwd_dres_{rows}x{d}", eng.layernorm_backward(x, dy, gam, dres))
+    eng.close()
+
+    sarch = pkg.SDArch(block_out_channels=(64, 128), down_block_attn=(True, False), layers_per_block=1, heads=8,
+                       cross_attention_dim=128, vae_block_out_channels=(64, 128), vae_layers_per_block=1, sample_size=16)
+    uw, _ = pkg.make_sd_weights(sarch, seed=3, which="unet")
+    eng = pkg.TVCEngine()
+    k = pkg.SDKernels(eng, sarch, uw, None)
+    x = torch.randn((2, 64, 8, 8), generator=g)
+    ctx = torch.randn((2, sarch.ctx, sarch.cross_attention_dim), generator=g)
+    temb = torch.randn((2, sarch.time_dim), generator=g)
+    save("sd_transformer", k.block(1, "down_blocks.0.attentions.0.", x, 64, ctx=ctx))
+    save("sd_resnet", k.block(0, "down_blocks.0.resnets.0.", x, 64, temb=temb))
+    torch.cuda.synchronize()
+    eng.close()
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("old")
+    ap.add_argument("new")
+    ap.add_argument("--timeout", type=int, default=240, help="seconds per child")
+    ap.add_argument("--keep", default=None, help="directory that keeps the .npy files (default: a temporary one)")
+    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child:
+        child(Path(a.child))
+        return 0
+    with tempfile.TemporaryDirectory() as tmp:
+        base = Path(a.keep) if a.keep else Path(tmp)
+        dirs = []
+        for tag, lib in (("old", a.old), ("new", a.new)):
+            d = base / tag
+            d.mkdir(parents=True, exist_ok=True)
+            dirs.append(d)
+            env = dict(os.environ, TVC_LIB_PATH=str(Path(lib).resolve()))
+            rc = subprocess.run(["timeout", "-k", "10", str(a.timeout), sys.executable, __file__, a.old, a.new, "--child", str(d)],
+                                env=env).returncode
+            if rc != 0:
+                print(json.dumps({"lib_ab": "child failed", "library": lib, "exit": rc}), flush=True)
+                return 2
+        names = sorted(p.name for p in dirs[0].glob("*.npy"))
+        missing = sorted(set(names) ^ {p.name for p in dirs[1].glob("*.npy")})
+        differ = []
+        for n in names:
+            if n in missing:
+                continue
+            same = (dirs[0] / n).read_bytes() == (dirs[1] / n).read_bytes()
+            line = f"{n[:-4]:28s} {'identical' if same else 'DIFFERS'}"
+            if not same:
+                o, w = np.load(dirs[0] / n), np.load(dirs[1] / n)
+                line += f"  {int((o != w).sum())} of {o.size} elements"
+                differ.append(n[:-4])
+            print(line)
+        ok = bool(names) and not differ and not missing
+        print(json.dumps({"lib_ab": "identical" if ok else "DIFFERENT", "arrays": len(names), "differ": differ, "missing": missing}),
+              flush=True)
+        return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

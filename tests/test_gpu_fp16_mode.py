@@ -196,7 +196,7 @@ def test_attention_f16_vs_fp64(pkg, n_seq, T, heads, causal):
     eng.close()
 
 
-@pytest.mark.parametrize("rows,d", [(300, 768), (77, 1024), (5, 128)])
+@pytest.mark.parametrize("rows,d", [(300, 768), (77, 1024), (5, 128), (1, 64), (5, 260), (7, 1024)])      # + piece-loop edges
 def test_layernorm_f16_vs_fp64(pkg, rows, d):
     eng = pkg.TVCEngine()
     g = torch.Generator().manual_seed(rows + d)

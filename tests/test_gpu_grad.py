@@ -23,7 +23,7 @@ def _bf(x):
 def test_layernorm_backward_vs_autograd(gpu_engine):
     eng = gpu_engine
     g0 = torch.Generator().manual_seed(0)
-    for rows, d in ((7, 768), (200, 1024), (33, 192)):
+    for rows, d in ((7, 768), (200, 1024), (33, 192), (1, 64), (5, 260), (7, 1024)):      # the last three: piece-loop edges
         x = torch.randn(rows, d, generator=g0) * 2 + 0.3
         gam = torch.rand(d, generator=g0) + 0.5
         bet = torch.randn(d, generator=g0)

@@ -110,7 +110,9 @@ def test_gemm_identity_asymmetric(gpu_engine):
     assert torch.equal(out, b.float())
 
 
-@pytest.mark.parametrize("rows,d", [(5, 128), (1000, 256), (257, 768), (514, 1024)])
+# the last three: the edges of the four-piece row loop (one piece on 16 lanes, one row of a four-row block; nv = 65, a second
+# piece with a single active lane and a ragged last block; all four pieces full)
+@pytest.mark.parametrize("rows,d", [(5, 128), (1000, 256), (257, 768), (514, 1024), (1, 64), (5, 260), (7, 1024)])
 def test_layernorm(gpu_engine, rows, d):
     x = _rand((rows, d), 5, 3.0) + 0.5
     g = 1 + _rand((d,), 6, 0.1)
