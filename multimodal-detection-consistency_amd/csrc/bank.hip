@@ -34,6 +34,15 @@
 // the products are exact and the result is the fp32-accumulated cosine of the
 // stored values (|err| ~ 1e-6); an fp32 bank is split the same way and uses the
 // three products hi.hi + lo.hi + hi.lo.
+//
+// Written once, ahead of the kernels that use them:
+//   cand_better / argmax_reduce<W>    the (v desc, idx asc) order and its shuffle reduction (select; row_topk: cand_better)
+//   Moments / combine / mom_lanes<>   the (sum, sumsq, max, count) 4-tuple and its reductions (search, select, merge)
+//   cand_append / cand_count_out      the listing rule of all four filter kernels: slot, cap, overflow flag
+//   bank_item / bank_lane_setup       item order and lane set-up of bank_search_kernel<FILTER> and bank_filter_ring_kernel
+//   bank_tile_epilogue<FULL, FILTER>  a 256 x 256 tile of similarities -> lists (+ moments)
+//   skinny_load_group / skinny_mfma / skinny_walk
+//                                     the stream of bank_filter_skinny_kernel and bank_sample_skinny_kernel
 #include "gemm_core.hpp"
 #include "gemm_ring4.hpp"
 #include "kernels.hpp"
@@ -48,6 +57,49 @@ struct Cand {
     float v;
     int32_t idx;
 };
+// (v desc, idx asc) ordering
+__device__ __forceinline__ bool cand_better(float v, int idx, float ov, int oidx) {
+    return (v > ov) || (v == ov && idx < oidx);
+}
+// all-lane arg-max of (v, idx) in that order over groups of W lanes; pos < 0 = this lane brings no candidate
+template <int W>
+__device__ __forceinline__ void argmax_reduce(float& v, int& idx, int& pos) {
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(v, o, 64);
+        const int oi = __shfl_xor(idx, o, 64);
+        const int op = __shfl_xor(pos, o, 64);
+        if (op >= 0 && (pos < 0 || cand_better(ov, oi, v, idx))) { v = ov; idx = oi; pos = op; }
+    }
+}
+
+// A query's moments over a set of bank rows, [sum, sum of squares, max, count >= count_thr] as stored in mom_part / moments.
+// Every reduction over lanes, waves, chunks and shards is a chain of combine() calls in a fixed order.
+struct Moments {
+    float sum = 0.f, sq = 0.f, mx = -INFINITY, cnt = 0.f;
+};
+__device__ __forceinline__ Moments combine(const Moments a, const Moments b) {
+    Moments r;
+    r.sum = a.sum + b.sum; r.sq = a.sq + b.sq; r.mx = fmaxf(a.mx, b.mx); r.cnt = a.cnt + b.cnt;
+    return r;
+}
+__device__ __forceinline__ Moments mom_load(const float* p) {
+    Moments r;
+    r.sum = p[0]; r.sq = p[1]; r.mx = p[2]; r.cnt = p[3];
+    return r;
+}
+__device__ __forceinline__ void mom_store(float* p, const Moments m) { p[0] = m.sum; p[1] = m.sq; p[2] = m.mx; p[3] = m.cnt; }
+// combine() with the lanes at the xor distances Os, taken in that order, all lanes; written field by field (the sums, then
+// the maximum: the order wave_sum / wave_max calls gave) -- distance by distance through combine() is the same arithmetic,
+// but hipcc then allocates bank_search_kernel<false>'s tile loop differently (EXPERIMENTS.md)
+template <int... Os>
+__device__ __forceinline__ Moments mom_lanes(Moments m) {
+    ((m.sum += __shfl_xor(m.sum, Os, 64)), ...);
+    ((m.sq += __shfl_xor(m.sq, Os, 64)), ...);
+    ((m.cnt += __shfl_xor(m.cnt, Os, 64)), ...);
+    ((m.mx = fmaxf(m.mx, __shfl_xor(m.mx, Os, 64))), ...);
+    return m;
+}
 
 // (bank_plan: host_plan.hpp)
 
@@ -154,14 +206,14 @@ __global__ __launch_bounds__(256) void bank_bounds_kernel(const uint16_t* __rest
             const u32x4_t h = *(const u32x4_t*)(br + c);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float a = __uint_as_float(h[e] << 16), b = __uint_as_float(h[e] & 0xffff0000u);
+                const float a = Op16<false>::lo(h[e]), b = Op16<false>::hi(h[e]);
                 h2 = fmaf(a, a, fmaf(b, b, h2));
             }
             if (planes > 1) {
                 const u32x4_t l = *(const u32x4_t*)(br + D + c);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float a = __uint_as_float(l[e] << 16), b = __uint_as_float(l[e] & 0xffff0000u);
+                    const float a = Op16<false>::lo(l[e]), b = Op16<false>::hi(l[e]);
                     l2 = fmaf(a, a, fmaf(b, b, l2));
                 }
             }
@@ -202,84 +254,36 @@ struct BankEpilogue {
     float count_thr;
 };
 
-template <bool FULL, bool FILTER>
-__device__ __forceinline__ void bank_tile_epilogue(const gemm_acc_t& acc, const BankEpilogue& e,
-                                                   int64_t tile_row0, int chunk, int j0, int wm, int wn,
-                                                   int lane, const float (&tau)[4], float (&sum)[4],
-                                                   float (&sq)[4], float (&mx)[4], float (&cn)[4],
-                                                   int* lds_cnt) {
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-        const int ql = wn * 64 + n * 16 + (lane & 15);
-        const int q = j0 + ql;
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const int64_t row = tile_row0 + wm * 128 + m * 16 + (lane >> 4) * 4;
-            f32x4_t v = acc[m][n];
-            if (!FULL) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (row + r >= e.R) v[r] = -INFINITY;
-            }
-            const float m4 = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
-            if (!FILTER) {
-                if (FULL) {
-                    sum[n] += (v[0] + v[1]) + (v[2] + v[3]);
-                    sq[n] = fmaf(v[0], v[0], fmaf(v[1], v[1], fmaf(v[2], v[2], fmaf(v[3], v[3], sq[n]))));
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (row + r < e.R) { sum[n] += v[r]; sq[n] = fmaf(v[r], v[r], sq[n]); }
-                }
-                mx[n] = fmaxf(mx[n], m4);
-                if (m4 >= e.count_thr) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) cn[n] += (v[r] >= e.count_thr) ? 1.f : 0.f;
-                }
-            }
-            // NaN similarities (zero-norm query row, NaN bank row) are never listed: every comparison
-            // with a NaN is false, and fmaxf drops NaN operands; tau itself is never NaN (kth_bound_kernel)
-            if (m4 > tau[n]) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if (v[r] > tau[n] && (FULL || row + r < e.R)) {
-                        // rare path (a few survivors per lane per bank chunk): keep
-                        // its address arithmetic inside the branch, not hoisted into
-                        // registers that stay live across the main loop
-                        int qlo = ql;
-                        asm volatile("" : "+v"(qlo));
-                        // padded query lanes (q >= M) re-read the last query row with tau = +inf and never get
-                        // here; the guard keeps a stray append out of the lists of (chunk + 1, q - M)
-                        if (j0 + qlo < e.M) {
-                            const int slot = atomicAdd(&lds_cnt[qlo], 1);
-                            if (slot < BANK_CAP) {
-                                Cand c;
-                                c.v = v[r];
-                                c.idx = (int32_t)(row + r + e.idx_offset);
-                                e.cand[((int64_t)chunk * e.M + (j0 + qlo)) * BANK_CAP + slot] = c;
-                            }
-                        }
-                    }
-                }
-            }
+// ---- the listing rule of the four filter kernels: one definition each of the append and of the count write-out
+// Bank row `row` survived query q0 + ql's filter with value v: append it to the list of (chunk, q0 + ql); ql = the query's
+// counter in lds_cnt.  A rare path (a few survivors per lane per bank chunk): the pin keeps its address arithmetic inside
+// the caller's branch, not hoisted into registers that stay live across the main loop.  Padded query lanes (q0 + ql >= M)
+// carry tau = +inf and never get here; the guard keeps a stray append out of the lists of (chunk + 1, q - M).  Slots past
+// the cap are counted, not stored (cand_count_out reports them).
+__device__ __forceinline__ void cand_append(const BankEpilogue& e, int* lds_cnt, int chunk, int q0, int ql, float v, int64_t row) {
+    asm volatile("" : "+v"(ql));
+    if (q0 + ql < e.M) {
+        const int slot = atomicAdd(&lds_cnt[ql], 1);
+        if (slot < BANK_CAP) {
+            Cand c;
+            c.v = v;
+            c.idx = (int32_t)(row + e.idx_offset);
+            e.cand[((int64_t)chunk * e.M + (q0 + ql)) * BANK_CAP + slot] = c;
         }
     }
 }
+// the list length of (chunk, q < M) from its counter c (read after a barrier); a counter past the cap sets the overflow flag
+__device__ __forceinline__ void cand_count_out(const BankEpilogue& e, int chunk, int q, int c) {
+    if (c > BANK_CAP) { c = BANK_CAP; atomicOr(e.overflow, 1); }
+    e.cand_cnt[(int64_t)chunk * e.M + q] = c;
+}
 
-template <bool FILTER>
-__global__ __launch_bounds__(GEMM_THREADS) void bank_search_kernel(GemmOperands g, BankEpilogue e,
-                                                                   int nQt, int S, int tiles_per_chunk,
-                                                                   int n_bank_tiles) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    int* lds_cnt = (int*)(smem + GEMM_LDS_BYTES);
-    float* lds_mom = (float*)(smem + GEMM_LDS_BYTES + 256 * 4);
-    // Order of the (query tile, bank chunk) items inside an XCD (consecutive `lin` = concurrently
-    // resident workgroups): blocks of 4 query tiles x 8 chunks, so the 32 workgroups of a block keep
-    // 4 query tiles (1.6 MB of planes) in the XCD's L2 AND read every bank tile four times from L2 for
-    // one HBM read (query-tile-slowest order streamed the whole bank once per query tile: 30 GB per
-    // launch at cfg 2).  Ragged counts fall back to query tile slowest.
+// Order of the (query tile, bank chunk) items inside an XCD (consecutive `lin` = concurrently resident workgroups): blocks
+// of 4 query tiles x 8 chunks, so the 32 workgroups of a block keep 4 query tiles (1.6 MB of planes) in the XCD's L2 AND
+// read every bank tile four times from L2 for one HBM read (query-tile-slowest order streamed the whole bank once per
+// query tile: 30 GB per launch at cfg 2).  Ragged counts fall back to query tile slowest.
+__device__ __forceinline__ void bank_item(int nQt, int S, int& qt, int& chunk) {
     const int lin = xcd_contiguous(blockIdx.x, nQt * S);
-    int qt, chunk;
     if ((nQt & 3) == 0 && (S & 7) == 0) {
         const int blk = lin >> 5, r = lin & 31;
         const int ncg = S >> 3;
@@ -289,71 +293,118 @@ __global__ __launch_bounds__(GEMM_THREADS) void bank_search_kernel(GemmOperands 
     } else {
         qt = lin / S; chunk = lin - qt * S;
     }
-    const int j0 = qt * GEMM_BN;
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int wm = wave >> 2, wn = wave & 3;
+}
 
+// What a lane of the 256-query-tile kernels knows before its first tile: its item, its place in the 2 x 4 wave grid and
+// the item's bank tiles [bt0, bt1) ...
+struct BankLane {
+    int chunk, j0, lane, wm, wn, bt0, bt1;
+};
+// ... and the taus of its four queries (+inf for padded query rows: never listed); clears the item's list counters and ends
+// with a barrier.  (tau is an array of the kernel's own and the tile epilogue takes the BankLane by value: with tau inside
+// the struct, or the struct by reference, hipcc allocates the same kernels differently -- EXPERIMENTS.md.)
+__device__ __forceinline__ BankLane bank_lane_setup(const BankEpilogue& e, int nQt, int S, int tiles_per_chunk, int n_bank_tiles,
+                                                    int* lds_cnt, float (&tau)[4]) {
+    BankLane L;
+    int qt;
+    bank_item(nQt, S, qt, L.chunk);
+    L.j0 = qt * GEMM_BN;
+    L.lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    L.wm = wave >> 2; L.wn = wave & 3;
     if (threadIdx.x < 256) lds_cnt[threadIdx.x] = 0;
-    float tau[4], sum[4], sq[4], mx[4], cn[4];
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
-        const int q = j0 + wn * 64 + n * 16 + (lane & 15);
+        const int q = L.j0 + L.wn * 64 + n * 16 + (L.lane & 15);
         tau[n] = (q < e.M) ? e.tau[q] : INFINITY;
-        sum[n] = 0.f; sq[n] = 0.f; mx[n] = -INFINITY; cn[n] = 0.f;
     }
     __syncthreads();
+    L.bt0 = L.chunk * tiles_per_chunk;
+    L.bt1 = L.bt0 + tiles_per_chunk;
+    if (L.bt1 > n_bank_tiles) L.bt1 = n_bank_tiles;
+    return L;
+}
 
-    const int bt0 = chunk * tiles_per_chunk;
-    int bt1 = bt0 + tiles_per_chunk;
-    if (bt1 > n_bank_tiles) bt1 = n_bank_tiles;
-    for (int bt = bt0; bt < bt1; ++bt) {
+// One 256 x 256 tile of similarities: survivors to the lists; !FILTER: also into the lane's moments mom[4] (FILTER: unused, may be null)
+template <bool FULL, bool FILTER>
+__device__ __forceinline__ void bank_tile_epilogue(const gemm_acc_t& acc, const BankEpilogue& e, int64_t tile_row0, const BankLane L,
+                                                   const float (&tau)[4], Moments* mom, int* lds_cnt) {
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        const int ql = L.wn * 64 + n * 16 + (L.lane & 15);
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            const int64_t row = tile_row0 + L.wm * 128 + m * 16 + (L.lane >> 4) * 4;
+            f32x4_t v = acc[m][n];
+            if (!FULL) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (row + r >= e.R) v[r] = -INFINITY;
+            }
+            const float m4 = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+            if (!FILTER) {
+                if (FULL) {
+                    mom[n].sum += (v[0] + v[1]) + (v[2] + v[3]);
+                    mom[n].sq = fmaf(v[0], v[0], fmaf(v[1], v[1], fmaf(v[2], v[2], fmaf(v[3], v[3], mom[n].sq))));
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (row + r < e.R) { mom[n].sum += v[r]; mom[n].sq = fmaf(v[r], v[r], mom[n].sq); }
+                }
+                mom[n].mx = fmaxf(mom[n].mx, m4);
+                if (m4 >= e.count_thr) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) mom[n].cnt += (v[r] >= e.count_thr) ? 1.f : 0.f;
+                }
+            }
+            // NaN similarities (zero-norm query row, NaN bank row) are never listed: every comparison
+            // with a NaN is false, and fmaxf drops NaN operands; tau itself is never NaN (kth_bound_kernel)
+            if (m4 > tau[n]) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (v[r] > tau[n] && (FULL || row + r < e.R)) cand_append(e, lds_cnt, L.chunk, L.j0, ql, v[r], row + r);
+            }
+        }
+    }
+}
+template <bool FILTER>
+__global__ __launch_bounds__(GEMM_THREADS) void bank_search_kernel(GemmOperands g, BankEpilogue e,
+                                                                   int nQt, int S, int tiles_per_chunk,
+                                                                   int n_bank_tiles) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int* lds_cnt = (int*)(smem + GEMM_LDS_BYTES);
+    float* lds_mom = (float*)(smem + GEMM_LDS_BYTES + 256 * 4);
+    float tau[4];
+    const BankLane L = bank_lane_setup(e, nQt, S, tiles_per_chunk, n_bank_tiles, lds_cnt, tau);
+    Moments mom_regs[4];
+    Moments* const mom = FILTER ? nullptr : mom_regs;      // the filter form carries no moments
+    for (int bt = L.bt0; bt < L.bt1; ++bt) {
         gemm_acc_t acc;
         gemm_zero_acc(acc);
         const int64_t tile_row0 = (int64_t)bt * GEMM_BM;
-        gemm_mainloop(acc, g, (int)tile_row0, j0, smem);
+        gemm_mainloop(acc, g, (int)tile_row0, L.j0, smem);
         if (tile_row0 + GEMM_BM <= e.R)
-            bank_tile_epilogue<true, FILTER>(acc, e, tile_row0, chunk, j0, wm, wn, lane, tau, sum, sq, mx, cn, lds_cnt);
+            bank_tile_epilogue<true, FILTER>(acc, e, tile_row0, L, tau, mom, lds_cnt);
         else
-            bank_tile_epilogue<false, FILTER>(acc, e, tile_row0, chunk, j0, wm, wn, lane, tau, sum, sq, mx, cn, lds_cnt);
+            bank_tile_epilogue<false, FILTER>(acc, e, tile_row0, L, tau, mom, lds_cnt);
     }
 
-    if (FILTER) {
-        __syncthreads();
-        if (threadIdx.x < 256) {
-            const int q = j0 + threadIdx.x;
-            if (q < e.M) {
-                int c = lds_cnt[threadIdx.x];
-                if (c > BANK_CAP) { c = BANK_CAP; atomicOr(e.overflow, 1); }
-                e.cand_cnt[(int64_t)chunk * e.M + q] = c;
-            }
-        }
-        return;
-    }
-    // moments: the 4 lane groups of a wave and the 2 wm-waves share a query
+    if (!FILTER) {
+        // moments: the 4 lane groups of a wave and the 2 wm-waves share a query
 #pragma unroll
-    for (int n = 0; n < 4; ++n) {
-        float s = sum[n], s2 = sq[n], m = mx[n], c = cn[n];
-        s += __shfl_xor(s, 16, 64);  s += __shfl_xor(s, 32, 64);
-        s2 += __shfl_xor(s2, 16, 64); s2 += __shfl_xor(s2, 32, 64);
-        c += __shfl_xor(c, 16, 64);  c += __shfl_xor(c, 32, 64);
-        m = fmaxf(m, __shfl_xor(m, 16, 64)); m = fmaxf(m, __shfl_xor(m, 32, 64));
-        if ((lane >> 4) == 0) {
-            float* p = lds_mom + ((wm * 256) + wn * 64 + n * 16 + (lane & 15)) * 4;
-            p[0] = s; p[1] = s2; p[2] = m; p[3] = c;
+        for (int n = 0; n < 4; ++n) {
+            const Moments m = mom_lanes<16, 32>(mom[n]);
+            if ((L.lane >> 4) == 0) mom_store(lds_mom + ((L.wm * 256) + L.wn * 64 + n * 16 + (L.lane & 15)) * 4, m);
         }
     }
     __syncthreads();
     if (threadIdx.x < 256) {
-        const int q = j0 + threadIdx.x;
+        const int q = L.j0 + threadIdx.x;
         if (q < e.M) {
-            const float* a = lds_mom + threadIdx.x * 4;
-            const float* b = lds_mom + (256 + threadIdx.x) * 4;
-            float* o = e.mom_part + ((int64_t)chunk * e.M + q) * 4;
-            o[0] = a[0] + b[0]; o[1] = a[1] + b[1]; o[2] = fmaxf(a[2], b[2]); o[3] = a[3] + b[3];
-            int c = lds_cnt[threadIdx.x];
-            if (c > BANK_CAP) { c = BANK_CAP; atomicOr(e.overflow, 1); }
-            e.cand_cnt[(int64_t)chunk * e.M + q] = c;
+            if (!FILTER)
+                mom_store(e.mom_part + ((int64_t)L.chunk * e.M + q) * 4,
+                          combine(mom_load(lds_mom + threadIdx.x * 4), mom_load(lds_mom + (256 + threadIdx.x) * 4)));
+            cand_count_out(e, L.chunk, q, lds_cnt[threadIdx.x]);
         }
     }
 }
@@ -370,80 +421,102 @@ __global__ __launch_bounds__(GEMM_THREADS) void bank_filter_ring_kernel(GemmOper
                                                                         int tiles_per_chunk, int n_bank_tiles) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int* lds_cnt = (int*)(smem + GEMM_LDS_BYTES);
-    const int lin = xcd_contiguous(blockIdx.x, nQt * S);
-    int qt, chunk;
-    if ((nQt & 3) == 0 && (S & 7) == 0) {       // (the item order of bank_search_kernel)
-        const int blk = lin >> 5, r = lin & 31;
-        const int ncg = S >> 3;
-        const int qg = blk / ncg, cg = blk - qg * ncg;
-        qt = qg * 4 + (r & 3);
-        chunk = cg * 8 + (r >> 2);
-    } else {
-        qt = lin / S; chunk = lin - qt * S;
-    }
-    const int j0 = qt * GEMM_BN;
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int wm = wave >> 2, wn = wave & 3;
-
-    if (threadIdx.x < 256) lds_cnt[threadIdx.x] = 0;
-    float tau[4], sum[4], sq[4], mx[4], cn[4];      // (only tau is live in the filter form)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-        const int q = j0 + wn * 64 + n * 16 + (lane & 15);
-        tau[n] = (q < e.M) ? e.tau[q] : INFINITY;
-        sum[n] = 0.f; sq[n] = 0.f; mx[n] = -INFINITY; cn[n] = 0.f;
-    }
-    __syncthreads();
-
-    const int bt0 = chunk * tiles_per_chunk;
-    int bt1 = bt0 + tiles_per_chunk;
-    if (bt1 > n_bank_tiles) bt1 = n_bank_tiles;
+    float tau[4];
+    const BankLane L = bank_lane_setup(e, nQt, S, tiles_per_chunk, n_bank_tiles, lds_cnt, tau);
     const int n_full = (int)(e.R / GEMM_BM);
-    const int bt_ring_end = bt1 < n_full ? bt1 : n_full;
+    const int bt_ring_end = L.bt1 < n_full ? L.bt1 : n_full;
     ring4_stream(
-        g, smem, bt_ring_end - bt0,
-        [&](int n, int& i0, int& jj0) __attribute__((always_inline)) { i0 = (bt0 + n) * GEMM_BM; jj0 = j0; },
+        g, smem, bt_ring_end - L.bt0,
+        [&](int n, int& i0, int& jj0) __attribute__((always_inline)) { i0 = (L.bt0 + n) * GEMM_BM; jj0 = L.j0; },
         [&](int n, const gemm_acc_t& acc) __attribute__((always_inline)) {
-            bank_tile_epilogue<true, true>(acc, e, (int64_t)(bt0 + n) * GEMM_BM, chunk, j0, wm, wn, lane, tau, sum, sq, mx,
-                                           cn, lds_cnt);
+            bank_tile_epilogue<true, true>(acc, e, (int64_t)(L.bt0 + n) * GEMM_BM, L, tau, nullptr, lds_cnt);
         });
-    for (int bt = (bt_ring_end > bt0 ? bt_ring_end : bt0); bt < bt1; ++bt) {      // the ragged last bank tile
+    for (int bt = (bt_ring_end > L.bt0 ? bt_ring_end : L.bt0); bt < L.bt1; ++bt) {      // the ragged last bank tile
         gemm_acc_t acc;
         gemm_zero_acc(acc);
         const int64_t tile_row0 = (int64_t)bt * GEMM_BM;
-        gemm_mainloop(acc, g, (int)tile_row0, j0, smem);
-        bank_tile_epilogue<false, true>(acc, e, tile_row0, chunk, j0, wm, wn, lane, tau, sum, sq, mx, cn, lds_cnt);
+        gemm_mainloop(acc, g, (int)tile_row0, L.j0, smem);
+        bank_tile_epilogue<false, true>(acc, e, tile_row0, L, tau, nullptr, lds_cnt);
     }
     __syncthreads();
-    if (threadIdx.x < 256) {
-        const int q = j0 + threadIdx.x;
-        if (q < e.M) {
-            int c = lds_cnt[threadIdx.x];
-            if (c > BANK_CAP) { c = BANK_CAP; atomicOr(e.overflow, 1); }
-            e.cand_cnt[(int64_t)chunk * e.M + q] = c;
-        }
-    }
+    if (threadIdx.x < 256 && L.j0 + threadIdx.x < e.M) cand_count_out(e, L.chunk, L.j0 + threadIdx.x, lds_cnt[threadIdx.x]);
 }
 
 
 // ---------------------------------------------------------------------------------------------------------------
-// The filter pass for SMALL query batches (M <= 64: the reference searches ONE query at a time, src/retrieval.py:636-680;
-// BASELINE configs[0] has 48 rows) -- the HBM-bound regime of SURVEY.md 8(d).  The 256-query tile of the kernels above
-// multiplies 256 query columns whatever M is (R x 256 x D x 2 FLOP: 0.28 ms at R = 1 M even at the matrix peak) and
-// re-reads the bank through the L2 5 x; here the bank is streamed ONCE, straight from HBM into MFMA operand registers,
-// and multiplied with 16 * NQT query columns held in LDS:
-//   * a workgroup (8 waves, one per CU) owns a contiguous chunk of bank rows; each wave walks its own 16-row groups:
-//     all D / 64 x 2 sixteen-byte pieces of a group are requested before the previous group is multiplied (two register
-//     sets: ~50 KB of loads in flight per wave, 400 KB per CU -- latency is covered by bytes, not by occupancy);
-//   * a lane (row r = lane & 15, k-group g = lane >> 4) loads the 32 contiguous bytes [g * 32, g * 32 + 32) of every
+// The skinny stream, shared by bank_filter_skinny_kernel and bank_sample_skinny_kernel below (M <= 64): bank rows go
+// ONCE from memory into MFMA operand registers and are multiplied with 16 * NQT query columns held in LDS.
+//   * each of a workgroup's 8 waves walks its own 16-row groups (grp = wave, wave + 8, ...): all D / 64 x 2 sixteen-byte
+//     pieces of a group are requested before the previous group is multiplied (two register sets: ~50 KB of loads in
+//     flight per wave, 400 KB per CU -- latency is covered by bytes, not by occupancy);
+//   * a lane (row r16 = lane & 15, k-group g = lane >> 4) loads the 32 contiguous bytes [g * 32, g * 32 + 32) of every
 //     128-byte line of its row: the two MFMAs of a 64-deep block take k = 64 kb + 16 g + {0..7} and {8..15} -- any
 //     k permutation is a valid inner product as long as the query fragments use the same one (they do: the LDS image of
 //     the queries is read with the same offsets);
-//   * queries: hi planes [16 NQT, D] bf16 in LDS, row pitch D * 2 + 16 bytes (16 lanes of a ds_read_b128 group hit 16
-//     distinct 16-byte bank groups: conflict-free);
+//   * queries: QP planes (hi, or hi | lo) of 16 * NQT rows, [D * QP] bf16 per row in LDS, row pitch D * 2 * QP + 16 bytes
+//     (16 lanes of a ds_read_b128 group hit 16 distinct 16-byte bank groups: conflict-free); rows >= M are zeros.
+// The kernels supply the row address of a group, what is done with its accumulators, and their own copy of the queries to
+// LDS (a rolled loop in the filter kernel, six pieces deep in the latency-bound sample kernel: EXPERIMENTS.md).
+// ---------------------------------------------------------------------------------------------------------------
+// the lane's 2 * KB pieces of one row; src = the row + g * 16 elements.  NT: non-temporal (a row that is read once)
+template <int KB, bool NT>
+__device__ __forceinline__ void skinny_load_group(const uint16_t* src, u32x4_t (&a)[2 * KB]) {
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+        if (NT) {
+            a[2 * kb] = __builtin_nontemporal_load((const u32x4_t*)(src + kb * 64));
+            a[2 * kb + 1] = __builtin_nontemporal_load((const u32x4_t*)(src + kb * 64 + 8));
+        } else {
+            a[2 * kb] = *(const u32x4_t*)(src + kb * 64);
+            a[2 * kb + 1] = *(const u32x4_t*)(src + kb * 64 + 8);
+        }
+    }
+}
+// acc[n] = the group's 16 rows x the queries n * 16 .. n * 16 + 15, the products of the QP planes summed into one accumulator;
+// qbase = the LDS image + r16 * pitch + g * 32.  FENCE: a scheduling barrier per 64-deep block
+template <int KB, int NQT, int QP, bool FENCE>
+__device__ __forceinline__ void skinny_mfma(const u32x4_t (&a)[2 * KB], const char* qbase, f32x4_t (&acc)[NQT]) {
+    constexpr int D = KB * 64, QPITCH = D * 2 * QP + 16;
+#pragma unroll
+    for (int n = 0; n < NQT; ++n) acc[n] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+            const bf16x8_t af = __builtin_bit_cast(bf16x8_t, a[2 * kb + hf]);
+#pragma unroll
+            for (int n = 0; n < NQT; ++n) {
+                const char* qp = qbase + n * 16 * QPITCH + kb * 128 + hf * 16;
+#pragma unroll
+                for (int p = 0; p < QP; ++p)
+                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, *(const bf16x8_t*)(qp + p * 2 * D), acc[n], 0, 0, 0);
+            }
+        }
+        if (FENCE) __builtin_amdgcn_sched_barrier(0);
+    }
+}
+// the walk of a wave over its groups from `grp` on, whose pieces are already requested into a0: group i + 8 is in flight
+// while group i is multiplied
+template <int N, class Load, class Compute>
+__device__ __forceinline__ void skinny_walk(int grp, int n_groups, u32x4_t (&a0)[N], u32x4_t (&a1)[N], Load&& load, Compute&& compute) {
+    while (grp < n_groups) {
+        if (grp + 8 < n_groups) load(grp + 8, a1);
+        compute(grp, a0);
+        grp += 8;
+        if (grp >= n_groups) break;
+        if (grp + 8 < n_groups) load(grp + 8, a0);
+        compute(grp, a1);
+        grp += 8;
+    }
+}
+// ---------------------------------------------------------------------------------------------------------------
+// The filter pass for SMALL query batches (M <= 64: the reference searches ONE query at a time, src/retrieval.py:636-680;
+// BASELINE configs[0] has 48 rows) -- the HBM-bound regime of SURVEY.md 8(d).  The 256-query tile of the kernels above
+// multiplies 256 query columns whatever M is (R x 256 x D x 2 FLOP: 0.28 ms at R = 1 M even at the matrix peak) and
+// re-reads the bank through the L2 5 x; here the bank is streamed ONCE, straight from HBM (non-temporal loads), against
+// the queries' hi planes: a workgroup (8 waves, one per CU) owns a contiguous chunk of bank rows.
 //   * epilogue: as bank_tile_epilogue<FILTER> -- every lane compares its 4 rows x NQT queries with its queries' tau and
-//     appends survivors to the per-(chunk, query) lists (LDS slot counters, no global atomics).  The products are summed
+//     appends survivors to the per-(chunk, query) lists (cand_append).  The products are summed
 //     in another k order than in the ring kernel (fp32: ~1e-7), which the margin of kth_bound_kernel covers; the select
 //     pass re-scores the listed rows exactly, so the top-k set and values are the same.
 // ---------------------------------------------------------------------------------------------------------------
@@ -481,32 +554,14 @@ __global__ __launch_bounds__(512) void bank_filter_skinny_kernel(const uint16_t*
     const int n_groups = row_hi > row_lo ? (int)((row_hi - row_lo + 15) >> 4) : 0;
     const char* qbase = smem + r16 * QPITCH + g * 32;
 
-    auto load_group = [&](int grp, u32x4_t (&a)[2 * KB]) {
+    auto load_group = [&](int grp, u32x4_t (&a)[2 * KB]) __attribute__((always_inline)) {
         int64_t row = row_lo + (int64_t)grp * 16 + r16;
         if (row >= e.R) row = e.R - 1;                        // clamped: masked in the epilogue
-        const uint16_t* src = bank + row * ldb + g * 16;
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb) {
-            a[2 * kb] = __builtin_nontemporal_load((const u32x4_t*)(src + kb * 64));
-            a[2 * kb + 1] = __builtin_nontemporal_load((const u32x4_t*)(src + kb * 64 + 8));
-        }
+        skinny_load_group<KB, true>(bank + row * ldb + g * 16, a);
     };
-    auto compute_group = [&](int grp, const u32x4_t (&a)[2 * KB]) {
+    auto compute_group = [&](int grp, const u32x4_t (&a)[2 * KB]) __attribute__((always_inline)) {
         f32x4_t acc[NQT];
-#pragma unroll
-        for (int n = 0; n < NQT; ++n) acc[n] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb) {
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf) {
-                const bf16x8_t af = __builtin_bit_cast(bf16x8_t, a[2 * kb + hf]);
-#pragma unroll
-                for (int n = 0; n < NQT; ++n) {
-                    const bf16x8_t bfr = *(const bf16x8_t*)(qbase + n * 16 * QPITCH + kb * 128 + hf * 16);
-                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfr, acc[n], 0, 0, 0);
-                }
-            }
-        }
+        skinny_mfma<KB, NQT, 1, false>(a, qbase, acc);
         const int64_t row0 = row_lo + (int64_t)grp * 16 + 4 * g;
 #pragma unroll
         for (int n = 0; n < NQT; ++n) {
@@ -514,43 +569,16 @@ __global__ __launch_bounds__(512) void bank_filter_skinny_kernel(const uint16_t*
             const float m4 = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
             if (m4 > tau[n]) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if (v[r] > tau[n] && row0 + r < row_hi) {
-                        int q = n * 16 + r16;
-                        asm volatile("" : "+v"(q));
-                        if (q < e.M) {
-                            const int slot = atomicAdd(&lds_cnt[q], 1);
-                            if (slot < BANK_CAP) {
-                                Cand c;
-                                c.v = v[r];
-                                c.idx = (int32_t)(row0 + r + e.idx_offset);
-                                e.cand[((int64_t)chunk * e.M + q) * BANK_CAP + slot] = c;
-                            }
-                        }
-                    }
-                }
+                for (int r = 0; r < 4; ++r)
+                    if (v[r] > tau[n] && row0 + r < row_hi) cand_append(e, lds_cnt, chunk, 0, n * 16 + r16, v[r], row0 + r);
             }
         }
     };
-    // two register sets: group i + 8 is in flight while group i is multiplied
     u32x4_t a0[2 * KB], a1[2 * KB];
-    int grp = wave;
-    if (grp < n_groups) load_group(grp, a0);
-    while (grp < n_groups) {
-        if (grp + 8 < n_groups) load_group(grp + 8, a1);
-        compute_group(grp, a0);
-        grp += 8;
-        if (grp >= n_groups) break;
-        if (grp + 8 < n_groups) load_group(grp + 8, a0);
-        compute_group(grp, a1);
-        grp += 8;
-    }
+    if (wave < n_groups) load_group(wave, a0);
+    skinny_walk(wave, n_groups, a0, a1, load_group, compute_group);
     __syncthreads();
-    if (tid < NQT * 16 && tid < e.M) {
-        int c = lds_cnt[tid];
-        if (c > BANK_CAP) { c = BANK_CAP; atomicOr(e.overflow, 1); }
-        e.cand_cnt[(int64_t)chunk * e.M + tid] = c;
-    }
+    if (tid < NQT * 16 && tid < e.M) cand_count_out(e, chunk, tid, lds_cnt[tid]);
 }
 
 template <int KB>
@@ -609,34 +637,15 @@ __global__ __launch_bounds__(512) void bank_sample_skinny_kernel(const uint16_t*
 #pragma unroll
     for (int n = 0; n < NQT; ++n) mx[n] = -INFINITY;
 
-    auto load_group = [&](int grp, u32x4_t (&a)[2 * KB]) {
+    auto load_group = [&](int grp, u32x4_t (&a)[2 * KB]) __attribute__((always_inline)) {
         int i = i_lo + grp * 16 + r16;
         if (i >= i_hi) i = i_hi - 1;
-        const uint16_t* src = bank + (int64_t)i * sample_stride * ldb + g * 16;
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb) {
-            a[2 * kb] = *(const u32x4_t*)(src + kb * 64);
-            a[2 * kb + 1] = *(const u32x4_t*)(src + kb * 64 + 8);
-        }
+        skinny_load_group<KB, false>(bank + (int64_t)i * sample_stride * ldb + g * 16, a);
     };
-    auto compute_group = [&](int grp, const u32x4_t (&a)[2 * KB]) {
+    auto compute_group = [&](int grp, const u32x4_t (&a)[2 * KB]) __attribute__((always_inline)) {
         f32x4_t acc[NQT];
-#pragma unroll
-        for (int n = 0; n < NQT; ++n) acc[n] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb) {
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf) {
-                const bf16x8_t af = __builtin_bit_cast(bf16x8_t, a[2 * kb + hf]);
-#pragma unroll
-                for (int n = 0; n < NQT; ++n) {
-                    const char* qp = qbase + n * 16 * QPITCH + kb * 128 + hf * 16;
-                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, *(const bf16x8_t*)qp, acc[n], 0, 0, 0);
-                    acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, *(const bf16x8_t*)(qp + 2 * D), acc[n], 0, 0, 0);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);       // keeps hipcc from hoisting every fragment read of the group (154 spills)
-        }
+        // the fence keeps hipcc from hoisting every fragment read of the group (154 spills)
+        skinny_mfma<KB, NQT, 2, true>(a, qbase, acc);
         const int i0 = i_lo + grp * 16 + 4 * g;
 #pragma unroll
         for (int n = 0; n < NQT; ++n)
@@ -644,12 +653,11 @@ __global__ __launch_bounds__(512) void bank_sample_skinny_kernel(const uint16_t*
             for (int r = 0; r < 4; ++r)
                 if (i0 + r < i_hi) mx[n] = fmaxf(mx[n], acc[n][r]);
     };
-    // two register sets: a wave has two or three groups (n_sample / 256 rows per workgroup), both requested up front -- and
-    // before the queries' planes are copied to LDS (NQT * 16 * D / 4 sixteen-byte pieces, 3 per thread and query at D = 768,
+    // a wave has two or three groups (n_sample / 256 rows per workgroup), both requested up front -- and the first before
+    // the queries' planes are copied to LDS (NQT * 16 * D / 4 sixteen-byte pieces, 3 per thread and query at D = 768,
     // unrolled so that a thread's pieces are in flight together): the launch is latency-bound, the two latencies overlap
     u32x4_t a0[2 * KB], a1[2 * KB];
-    int grp = wave;
-    if (grp < n_groups) load_group(grp, a0);
+    if (wave < n_groups) load_group(wave, a0);
     {
         constexpr int PIECES = NQT * 16 * (D / 4);
         constexpr int ROUNDS = (PIECES + 511) / 512;
@@ -663,15 +671,7 @@ __global__ __launch_bounds__(512) void bank_sample_skinny_kernel(const uint16_t*
         }
     }
     __syncthreads();
-    while (grp < n_groups) {
-        if (grp + 8 < n_groups) load_group(grp + 8, a1);
-        compute_group(grp, a0);
-        grp += 8;
-        if (grp >= n_groups) break;
-        if (grp + 8 < n_groups) load_group(grp + 8, a0);
-        compute_group(grp, a1);
-        grp += 8;
-    }
+    skinny_walk(wave, n_groups, a0, a1, load_group, compute_group);
 #pragma unroll
     for (int n = 0; n < NQT; ++n) {
         float v = mx[n];
@@ -707,11 +707,6 @@ static hipError_t launch_bank_sample_skinny(const uint16_t* bank, int64_t ldb, i
     return dispatch<128, 512, 768>(D, [&](auto d) {
         return launch_sample_skinny_kb<d.value / 64>(bank, ldb, qplanes, M, n_sample, sample_stride, gmax, stream);
     });
-}
-
-// (v desc, idx asc) ordering
-__device__ __forceinline__ bool cand_better(float v, int idx, float ov, int oidx) {
-    return (v > ov) || (v == ov && idx < oidx);
 }
 
 // One workgroup of SEL_T threads per query.  Round 4: 1 024 threads (16 waves x 4 rows in flight in the re-scoring: the
@@ -826,10 +821,10 @@ __global__ __launch_bounds__(SEL_T) void bank_select_kernel(const Cand* __restri
                 for (int u = 0; u < 4; ++u) {
 #pragma unroll
                     for (int e2 = 0; e2 < 4; ++e2) {
-                        float a = __uint_as_float(h[u][e2] << 16), b = __uint_as_float(h[u][e2] & 0xffff0000u);
+                        float a = Op16<false>::lo(h[u][e2]), b = Op16<false>::hi(h[u][e2]);
                         if (rs_planes > 1) {
-                            a += __uint_as_float(l[u][e2] << 16);
-                            b += __uint_as_float(l[u][e2] & 0xffff0000u);
+                            a += Op16<false>::lo(l[u][e2]);
+                            b += Op16<false>::hi(l[u][e2]);
                         }
                         const float qa = e2 < 2 ? q0[e2 * 2] : q1[e2 * 2 - 4];
                         const float qb = e2 < 2 ? q0[e2 * 2 + 1] : q1[e2 * 2 - 3];
@@ -857,25 +852,13 @@ __global__ __launch_bounds__(SEL_T) void bank_select_kernel(const Cand* __restri
             const Cand c = pool[i];
             if (c.idx >= 0 && cand_better(c.v, c.idx, bv, bi)) { bv = c.v; bi = c.idx; bp = i; }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            const int op = __shfl_xor(bp, o, 64);
-            if (op >= 0 && (bp < 0 || cand_better(ov, oi, bv, bi))) { bv = ov; bi = oi; bp = op; }
-        }
+        argmax_reduce<64>(bv, bi, bp);
         const int par = r & 1;
         if (lane == 0) { red_v[par][wave] = bv; red_i[par][wave] = bi; red_p[par][wave] = bp; }
         __syncthreads();
         float fv = red_v[par][lane & (SEL_W - 1)];
         int fi = red_i[par][lane & (SEL_W - 1)], fp = red_p[par][lane & (SEL_W - 1)];
-#pragma unroll
-        for (int o = SEL_W / 2; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(fv, o, 64);
-            const int oi = __shfl_xor(fi, o, 64);
-            const int op = __shfl_xor(fp, o, 64);
-            if (op >= 0 && (fp < 0 || cand_better(ov, oi, fv, fi))) { fv = ov; fi = oi; fp = op; }
-        }
+        argmax_reduce<SEL_W>(fv, fi, fp);
         if (t == 0) {
             topk_idx[(int64_t)q * k + r] = fp >= 0 ? fi : -1;
             topk_sim[(int64_t)q * k + r] = fp >= 0 ? fv : -INFINITY;
@@ -884,19 +867,15 @@ __global__ __launch_bounds__(SEL_T) void bank_select_kernel(const Cand* __restri
     }
 
     if (moments) {
-        float s = 0.f, s2 = 0.f, m = -INFINITY, c = 0.f;
-        for (int ch = t; ch < S; ch += SEL_T) {
-            const float* p = mom_part + ((int64_t)ch * M + q) * 4;
-            s += p[0]; s2 += p[1]; m = fmaxf(m, p[2]); c += p[3];
-        }
-        s = wave_sum(s); s2 = wave_sum(s2); c = wave_sum(c); m = wave_max(m);
-        if (lane == 0) { mom_red[wave][0] = s; mom_red[wave][1] = s2; mom_red[wave][2] = m; mom_red[wave][3] = c; }
+        Moments m;
+        for (int ch = t; ch < S; ch += SEL_T) m = combine(m, mom_load(mom_part + ((int64_t)ch * M + q) * 4));
+        m = mom_lanes<32, 16, 8, 4, 2, 1>(m);
+        if (lane == 0) mom_store(mom_red[wave], m);
         __syncthreads();
         if (t == 0) {
-            float* o = moments + (int64_t)q * 4;
-            float s0 = 0.f, s1 = 0.f, m2 = -INFINITY, s3 = 0.f;
-            for (int w = 0; w < SEL_W; ++w) { s0 += mom_red[w][0]; s1 += mom_red[w][1]; m2 = fmaxf(m2, mom_red[w][2]); s3 += mom_red[w][3]; }
-            o[0] = s0; o[1] = s1; o[2] = m2; o[3] = s3;
+            Moments o;
+            for (int w = 0; w < SEL_W; ++w) o = combine(o, mom_load(mom_red[w]));
+            mom_store(moments + (int64_t)q * 4, o);
         }
     }
 }
@@ -917,6 +896,7 @@ __global__ __launch_bounds__(1024) void row_topk_kernel(float* __restrict__ sims
     const int q = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     float* row = sims + (int64_t)q * R;
     if (moments) {
+        // three sums, not a Moments: the maximum is the first arg-max round's
         float s = 0.f, s2 = 0.f, c = 0.f;
         for (int64_t i = t; i < R; i += 1024) { const float v = row[i]; s += v; s2 = fmaf(v, v, s2); c += (v >= count_thr) ? 1.f : 0.f; }
         s = wave_sum(s); s2 = wave_sum(s2); c = wave_sum(c);
@@ -936,20 +916,20 @@ __global__ __launch_bounds__(1024) void row_topk_kernel(float* __restrict__ sims
         for (int64_t i = t; i < R; i += 1024) {
             const float v = row[i];
             // NaN similarities (NaN bank rows / zero-norm queries) are never returned
-            if (v == v && v != -INFINITY && (!has || v > bv || (v == bv && (int)i < bi))) { bv = v; bi = (int)i; has = true; }
+            if (v == v && v != -INFINITY && (!has || cand_better(v, (int)i, bv, bi))) { bv = v; bi = (int)i; has = true; }
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const float ov = __shfl_xor(bv, o, 64);
             const int oi = __shfl_xor(bi, o, 64);
-            if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+            if (oi != 0x7fffffff && (bi == 0x7fffffff || cand_better(ov, oi, bv, bi))) { bv = ov; bi = oi; }
         }
         if (lane == 0) { rv[wave] = bv; ri[wave] = bi; }
         __syncthreads();
         if (t == 0) {
             float fv = rv[0]; int fi = ri[0];
             for (int w = 1; w < 16; ++w)
-                if (ri[w] != 0x7fffffff && (fi == 0x7fffffff || rv[w] > fv || (rv[w] == fv && ri[w] < fi))) { fv = rv[w]; fi = ri[w]; }
+                if (ri[w] != 0x7fffffff && (fi == 0x7fffffff || cand_better(rv[w], ri[w], fv, fi))) { fv = rv[w]; fi = ri[w]; }
             if (fi != 0x7fffffff) {
                 topk_idx[(int64_t)q * k + r] = (int32_t)(fi + idx_offset);
                 topk_sim[(int64_t)q * k + r] = fv;
@@ -981,6 +961,12 @@ hipError_t launch_bank_search_dense(const BankSearchLaunch& L, float* sims_ws, i
     return hipSuccess;
 }
 
+// an on / off switch of the A/B runs: on unless the variable is set to 0 (callers read it once per process)
+static bool env_flag(const char* name) {
+    const char* v = getenv(name);
+    return !v || atoi(v) != 0;
+}
+
 hipError_t launch_bank_search(const BankSearchLaunch& L, hipStream_t stream) {
     const int D = L.D;
     // products: (bank plane, query plane) pairs accumulated into one tile
@@ -990,10 +976,10 @@ hipError_t launch_bank_search(const BankSearchLaunch& L, hipStream_t stream) {
     const bool filter = (L.moments == nullptr) && L.bank_bounds && L.rows && D <= BANK_MAX_RESCORE_D && L.allow_filter;
 
     // small query batches: the bank streamed once from HBM against <= 64 query columns (TVC_BANK_SKINNY=0: off, for A/B runs)
-    static const bool skinny_on = [] { const char* v = getenv("TVC_BANK_SKINNY"); return !v || atoi(v) != 0; }();
+    static const bool skinny_on = env_flag("TVC_BANK_SKINNY");
     const bool skinny = filter && skinny_on && skinny_covers(D, L.M) && L.ldb % 8 == 0;
     // ... and, over a bf16 bank, the sample's group maxima by the same route (TVC_BANK_SKINNY_SAMPLE=0: the dense sample GEMM)
-    static const bool skinny_sample_on = [] { const char* v = getenv("TVC_BANK_SKINNY_SAMPLE"); return !v || atoi(v) != 0; }();
+    static const bool skinny_sample_on = env_flag("TVC_BANK_SKINNY_SAMPLE");
 
     // ---- pass 0: sample GEMM + tau ----------------------------------------
     hipError_t st;
@@ -1016,11 +1002,8 @@ hipError_t launch_bank_search(const BankSearchLaunch& L, hipStream_t stream) {
     }
 
     // ---- pass 1: fused GEMM + filter ---------------------------------------
-    GemmOperands g = {};
-    g.A = L.bank; g.lda = L.ldb; g.I = (int)L.R;
-    g.B = L.qplanes; g.ldb = 2 * (int64_t)D; g.J = L.M;
-    g.ksteps_per_plane = D / GEMM_BK; g.planes = filter ? 1 : (L.bank_planes == 2 ? 3 : 2);
-    g.b_plane_off[1] = D; g.a_plane_off[2] = D;     // as gemm_launch_planes (kernels.hpp)
+    GemmOperands g = gemm_operands(gemm_launch_planes(L.bank, L.ldb, (int)L.R, L.bank_planes, L.qplanes, L.M, D, nullptr, 0));
+    if (filter) g.planes = 1;       // the first product alone: bank hi x query hi
     BankEpilogue e;
     e.tau = L.tau; e.cand = (Cand*)L.cand; e.cand_cnt = L.cand_cnt; e.mom_part = L.mom_part;
     e.overflow = L.overflow; e.R = L.R; e.idx_offset = L.idx_offset; e.M = L.M; e.count_thr = L.count_thr;
@@ -1029,7 +1012,7 @@ hipError_t launch_bank_search(const BankSearchLaunch& L, hipStream_t stream) {
     const int tpc = (nbt + L.S - 1) / L.S;
     // the filter pass streams its bank tiles through GEMM form 4 where that form's preconditions hold (TVC_BANK_RING=0:
     // the one-tile-at-a-time loop, for A/B runs); the ragged last bank tile is handled inside the kernel
-    static const bool ring_on = [] { const char* v = getenv("TVC_BANK_RING"); return !v || atoi(v) != 0; }();
+    static const bool ring_on = env_flag("TVC_BANK_RING");
     const bool ring = filter && ring_on && L.q_rows_padded && (g.lda % 64 == 0) && (g.ldb % 64 == 0) && L.R >= GEMM_BM;
     const dim3 grid(nQt * L.S), block(GEMM_THREADS);
     if (skinny)
@@ -1115,13 +1098,9 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const int32_t* __restri
         }
     }
     if (mom_out && mom_parts && t == 0) {
-        float s = 0.f, s2 = 0.f, m = -INFINITY, c = 0.f;
-        for (int w = 0; w < W; ++w) {
-            const float* p = mom_parts + ((int64_t)w * M + q) * 4;
-            s += p[0]; s2 += p[1]; m = fmaxf(m, p[2]); c += p[3];
-        }
-        float* o = mom_out + (int64_t)q * 4;
-        o[0] = s; o[1] = s2; o[2] = m; o[3] = c;
+        Moments m;
+        for (int w = 0; w < W; ++w) m = combine(m, mom_load(mom_parts + ((int64_t)w * M + q) * 4));
+        mom_store(mom_out + (int64_t)q * 4, m);
     }
 }
 

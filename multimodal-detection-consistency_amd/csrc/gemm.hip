@@ -578,12 +578,8 @@ static hipError_t launch_splitk_finish(const GemmLaunch& L, const GemmOperands& 
 
 template <bool F16>
 static hipError_t launch_gemm_t(const GemmLaunch& L, hipStream_t stream) {
-    GemmOperands g;
-    g.A = L.A; g.B = L.B; g.lda = L.lda; g.ldb = L.ldb; g.I = L.I; g.J = L.J;
-    g.ksteps_per_plane = L.K / GEMM_BK;
-    g.planes = L.planes;
     if (L.planes < 1 || L.planes > GEMM_MAX_PLANES) return hipErrorInvalidValue;
-    for (int p = 0; p < GEMM_MAX_PLANES; ++p) { g.a_plane_off[p] = L.a_plane_off[p]; g.b_plane_off[p] = L.b_plane_off[p]; }
+    const GemmOperands g = gemm_operands(L);
     GemmEpilogue e;
     e.bias = L.bias; e.out = L.out; e.ldo = L.ldo;
     const int nIt = (L.I + GEMM_BM - 1) / GEMM_BM, nJt = (L.J + GEMM_BN - 1) / GEMM_BN;

@@ -22,6 +22,7 @@
 // b_plane_off[p] + k, all accumulated into the same tile.
 #pragma once
 #include "common.hpp"
+#include "kernels.hpp"
 
 #define GEMM_BM 256          // I rows per workgroup
 #define GEMM_BN 256          // J rows per workgroup
@@ -41,6 +42,16 @@ struct GemmOperands {
     int a_plane_off[GEMM_MAX_PLANES];
     int b_plane_off[GEMM_MAX_PLANES];
 };
+
+// the operand half of a host-side launch (kernels.hpp) as the kernels take it
+inline GemmOperands gemm_operands(const GemmLaunch& L) {
+    GemmOperands g;
+    g.A = L.A; g.B = L.B; g.lda = L.lda; g.ldb = L.ldb; g.I = L.I; g.J = L.J;
+    g.ksteps_per_plane = L.K / GEMM_BK;
+    g.planes = L.planes;
+    for (int p = 0; p < GEMM_MAX_PLANES; ++p) { g.a_plane_off[p] = L.a_plane_off[p]; g.b_plane_off[p] = L.b_plane_off[p]; }
+    return g;
+}
 
 typedef f32x4_t gemm_acc_t[8][4];
 

@@ -5,7 +5,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import torch
 import tvc_amd as pkg
 D, k = 768, 10
-for (R, M) in ((1_000_000, 5120), (125_000, 40960), (1_250_000, 40960), (10_000_000, 5120)):
+SHAPES = ((1_000_000, 5120), (125_000, 40960), (1_250_000, 40960), (10_000_000, 5120))
+for (R, M) in SHAPES[:int(sys.argv[1]) if len(sys.argv) > 1 else None]:      # optional argument: only the first N shapes
     eng = pkg.TVCEngine()
     bank = pkg.synth.make_bank(R, D, seed=7, device="cuda:0", dtype=torch.bfloat16)
     g = torch.Generator(device="cuda:0").manual_seed(0)

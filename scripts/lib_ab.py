@@ -12,7 +12,9 @@ with group = 3 over 6 texts of different lengths (packing and prefix sharing on)
 precisions, each with TVC_OPT_POOLED_LAST_LAYER on and off; the gradient path (encode_image_grad + encode_image_backward,
 B = 2); the kernel entries layernorm, layernorm_f16 and layernorm_backward (with and without dres) on the piece-loop edge
 shapes; one latent-diffusion transformer block and one resnet block at 8 x 8 (ln_bf16_kernel with and without `add`, GEGLU,
-the adds).
+the adds); the bank search (bank_cases below: every filter kernel, both tau kernels, the select, the dense fallback and the
+shard merge; the children inherit TVC_BANK_RING / TVC_BANK_SKINNY / TVC_BANK_SKINNY_SAMPLE, so a run with all three at 0
+reaches bank_search_kernel<true> and the dense sample for small M).
 """
 import argparse
 import importlib
@@ -28,6 +30,68 @@ import numpy as np
 ROOT = Path(__file__).resolve().parents[1]
 LN_SHAPES = ((1, 64), (5, 260), (7, 1024))
 TEXT_LENS = (19, 12, 9, 17, 15, 5)      # ids between SOT and EOT of the 6 texts
+
+
+def bank_cases(pkg, save) -> None:
+    """topk_idx, topk_sim and (where requested) the moments of seeded searches; bank.hip names the kernels."""
+    import ctypes as C
+    import torch
+    L = pkg._lib
+
+    def unit(shape, seed):
+        return torch.nn.functional.normalize(torch.randn(shape, generator=torch.Generator().manual_seed(seed)), dim=-1)
+
+    eng = pkg.TVCEngine()
+
+    def search(tag, q, k, **kw):
+        idx, sim, mom = eng.bank_search(q, k, **kw)
+        eng.bank_status()
+        save(f"bank_{tag}_idx", idx)
+        save(f"bank_{tag}_sim", sim)
+        if mom is not None:
+            save(f"bank_{tag}_mom", mom)
+
+    # skinny filter + skinny sample + kth_groups_kernel
+    eng.set_bank(unit((1000, 512), 11).to(torch.bfloat16).cuda())
+    search("1000x48", unit((48, 512), 12).cuda(), 5, want_moments=False)
+    # skinny filter over two planes + the dense sample + kth_bound_kernel
+    eng.set_bank(unit((4097, 128), 13).cuda())
+    search("4097x17", unit((17, 128), 14).cuda(), 7, want_moments=False)
+    # the 256-query-tile kernels in the blocked item order: all products (moments), the ring filter, the filter switched off
+    q770 = unit((770, 64), 15).cuda()
+    for R, dt, seed in ((4000, torch.float32, 16), (90001, torch.bfloat16, 17)):
+        eng.set_bank(unit((R, 64), seed).to(dt).cuda())
+        search(f"{R}x770_mom", q770, 5, count_thr=0.05)
+        search(f"{R}x770_filter", q770, 5, want_moments=False)
+        eng.set_option(L.TVC_OPT_BANK_FILTER, 0)
+        search(f"{R}x770_nofilter", q770, 5, want_moments=False)
+        eng.set_option(L.TVC_OPT_BANK_FILTER, 1)
+        if R == 4000:
+            search("4000x770_offset", q770, 5, idx_offset=123456, want_moments=False)
+            # row_topk_kernel with moments: the dense fallback on 70 query rows
+            q = q770[:70].contiguous()
+            i2 = torch.empty((70, 5), dtype=torch.int32, device="cuda:0")
+            s2 = torch.empty((70, 5), dtype=torch.float32, device="cuda:0")
+            m2 = torch.empty((70, 4), dtype=torch.float32, device="cuda:0")
+            rc = eng.lib.tvc_bank_search_dense(eng.handle, C.c_void_p(q.data_ptr()), 70, 5, 0.05, 0, C.c_void_p(i2.data_ptr()),
+                                               C.c_void_p(s2.data_ptr()), C.c_void_p(m2.data_ptr()),
+                                               C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            assert rc == 0, rc
+            save("bank_dense_idx", i2)
+            save("bank_dense_sim", s2)
+            save("bank_dense_mom", m2)
+    # topk_merge_kernel on the inputs of tests/test_gpu_api.py::test_topk_merge_kernel
+    W, M, k, kf, D = 4, 37, 8, 3, 128
+    g = torch.Generator().manual_seed(0)
+    sim = torch.rand((W, M, k), generator=g).sort(dim=-1, descending=True).values
+    idx = torch.stack([torch.randperm(1000, generator=g)[:k] + 1000 * w for w in range(W) for _ in range(M)]).view(W, M, k).int()
+    idx[3, :, 5:] = -1
+    feat = torch.randn((W, M, kf, D), generator=g)
+    mom = torch.rand((W, M, 4), generator=g)
+    for name, t in zip(("idx", "sim", "feat", "mom"), eng.topk_merge(idx.cuda(), sim.cuda(), feat.cuda(), mom.cuda())):
+        save(f"merge_{name}", t)
+    torch.cuda.synchronize()
+    eng.close()
 
 
 def child(out_dir: Path) -> None:
@@ -89,6 +153,7 @@ def child(out_dir: Path) -> None:
     save("sd_resnet", k.block(0, "down_blocks.0.resnets.0.", x, 64, temb=temb))
     torch.cuda.synchronize()
     eng.close()
+    bank_cases(pkg, save)
 
 
 def main() -> int:

@@ -2,9 +2,12 @@
 //   I J K planes lda ldb epilogue splitk_small splitk_fixed has_ws ws_bytes a_rows_padded b_rows_padded
 //   TVC_GEMM_VARIANT TVC_GEMM_RING_MIN_TILES TVC_GEMM_RING_FORM TVC_GEMM_SPLITK_TAIL TVC_GEMM_SPLITK_SMALL TVC_GEMM_RING_SPLIT
 // -- and prints the form csrc/host_plan.hpp's gemm_form gives it (the one launch_gemm_bf16 takes) and its K split.
+// With the arguments `bank_plan R M k` it prints bank_plan's cut of that search instead.
 #include "host_plan.hpp"
 
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 
 static const char* form_name(GemmForm f) {
     switch (f) {
@@ -19,7 +22,19 @@ static const char* form_name(GemmForm f) {
     return "?";
 }
 
-int main() {
+// `driver bank_plan R M k`: csrc/host_plan.hpp's bank_plan for that search and what pass 1 (bank.hip) makes of it
+static int print_bank_plan(long long R, int M, int k) {
+    int n_sample, stride, S, cap;
+    bank_plan(R, M, k, &n_sample, &stride, &S, &cap);
+    const int nQt = (M + HOST_PLAN_GEMM_BN - 1) / HOST_PLAN_GEMM_BN;
+    const int nbt = (int)((R + HOST_PLAN_GEMM_BM - 1) / HOST_PLAN_GEMM_BM);
+    printf("n_sample=%d stride=%d S=%d nQt=%d bank_tiles=%d tiles_per_chunk=%d blocked=%d\n", n_sample, stride, S, nQt, nbt,
+           (nbt + S - 1) / S, (int)(nQt % 4 == 0 && S % 8 == 0));
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc == 5 && !strcmp(argv[1], "bank_plan")) return print_bank_plan(atoll(argv[2]), atoi(argv[3]), atoi(argv[4]));
     long long v[19];
     for (;;) {
         for (int i = 0; i < 19; ++i)

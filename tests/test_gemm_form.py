@@ -45,7 +45,21 @@ def gemm_form(tmp_path_factory):
         assert len(out) == len(queries)
         return [(f, int(s)) for f, s in out]
 
+    many.exe = exe
     return many
+
+
+def test_bank_plan_of_the_blocked_item_order_shapes(gemm_form):
+    """tests/test_gpu_path.py::test_bank_search_blocked_item_order and the last two shapes of
+    tests/test_gpu_kernels.py::test_bank_filter_ring_and_one_tile_loops_agree claim the blocked (query tile, chunk) order of
+    pass 1 (nQt % 4 == 0 and S % 8 == 0), a ragged last bank tile, and one / two bank tiles per chunk: bank_plan says so."""
+    want = {(4000, 770, 5): "n_sample=4000 stride=1 S=16 nQt=4 bank_tiles=16 tiles_per_chunk=1 blocked=1",
+            (90001, 770, 5): "n_sample=5632 stride=15 S=176 nQt=4 bank_tiles=352 tiles_per_chunk=2 blocked=1"}
+    for (R, M, k), line in want.items():
+        r = subprocess.run([str(gemm_form.exe), "bank_plan", str(R), str(M), str(k)], capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert r.stdout.strip() == line
+        assert R % 256 != 0 and M % 256 != 0
 
 
 def test_contract_cases_reach_their_labelled_forms(gemm_form):

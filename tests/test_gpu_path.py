@@ -16,11 +16,14 @@ def _unit(shape, seed):
     return x / x.norm(dim=-1, keepdim=True)
 
 
-def _check_topk(idx, sim, S, k, tol):
-    """idx/sim: GPU result [M, k]; S: exact fp64 similarity matrix [M, R]."""
+def _check_topk(idx, sim, S, k, tol, order=None):
+    """idx/sim: GPU result [M, k]; S: exact fp64 similarity matrix [M, R]; order: the stable descending argsort of S's
+    rows (its first min(k, R) columns), for callers that check several results against one S."""
     M, R = S.shape
     kk = min(k, R)
-    order = np.argsort(-S, axis=1, kind="stable")[:, :kk]
+    if order is None:
+        order = np.argsort(-S, axis=1, kind="stable")
+    order = order[:, :kk]
     ref_sim = np.take_along_axis(S, order, 1)
     assert np.abs(sim[:, :kk] - ref_sim).max() < tol
     if kk < k:
@@ -60,6 +63,34 @@ def test_bank_search(gpu_engine, R, M, D, k, dtype):
     near = np.abs(S - 0.05) < 1e-5
     cnt = (S >= 0.05).sum(1)
     assert (np.abs(mom[:, 3] - cnt) <= near.sum(1)).all()
+
+
+# (tests/test_gemm_form.py::test_bank_plan_of_the_blocked_item_order_shapes pins what these two shapes reach)
+@pytest.mark.parametrize("R,M,D,k,dtype", [(4000, 770, 64, 5, torch.float32), (90001, 770, 64, 5, torch.bfloat16)])
+def test_bank_search_blocked_item_order(gpu_engine, R, M, D, k, dtype):
+    """M = 770 is four query tiles and bank_plan cuts these banks into 16 / 176 chunks, so the (query tile, chunk) items
+    of pass 1 take the blocked order (4 query tiles x 8 chunks; bank.hip, bank_item) that otherwise only the workload's own
+    sizes reach -- with a ragged last bank tile, a ragged fourth query tile, one and two bank tiles per chunk.  With moments
+    (all products, bank_search_kernel<false>) and without (the ring filter); ~16 / ~256 rows per query pass the filter."""
+    bank = _unit((R, D), 100 + R).to(dtype)
+    q = _unit((M, D), 200 + M)
+    gpu_engine.set_bank(bank.cuda())
+    S = (q.double().cuda() @ bank.double().cuda().t()).cpu().numpy()       # the reference, once for both searches
+    order = np.argsort(-S, axis=1, kind="stable")[:, :k]
+    idx, sim, mom = gpu_engine.bank_search(q.cuda(), k, count_thr=0.05)
+    gpu_engine.bank_status()
+    _check_topk(idx.cpu().numpy(), sim.cpu().numpy().astype(np.float64), S, k, 1e-5, order)
+    mom = mom.cpu().numpy().astype(np.float64)
+    assert np.abs(mom[:, 0] - S.sum(1)).max() < 1e-3 * max(1.0, np.sqrt(R))
+    assert np.abs(mom[:, 1] - (S * S).sum(1)).max() < 1e-3 * max(1.0, R / D)
+    assert np.abs(mom[:, 2] - S.max(1)).max() < 1e-5
+    near = np.abs(S - 0.05) < 1e-5
+    cnt = (S >= 0.05).sum(1)
+    assert (np.abs(mom[:, 3] - cnt) <= near.sum(1)).all()
+    idx, sim, mom = gpu_engine.bank_search(q.cuda(), k, want_moments=False)
+    gpu_engine.bank_status()
+    assert mom is None
+    _check_topk(idx.cpu().numpy(), sim.cpu().numpy().astype(np.float64), S, k, 1e-5, order)
 
 
 @pytest.mark.parametrize("R,M,D,k,dtype,scale", [
