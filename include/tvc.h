@@ -206,10 +206,21 @@ const char* tvc_last_error(tvc_handle* h);
  * TVC_OPT_SD_STREAMS (default 2; 1 = off): inside tvc_sd_generate the unconditional and the conditional half of a UNet
  * evaluation run on two HIP streams (the caller's and one the handle owns, forked / joined by events), each in its own
  * half of the arena: a launch of one half fills the compute units the other half's partial tile round leaves idle.  Every
- * sample's arithmetic is independent of its batch mates, so the images are bit-identical with 1 and 2. */
+ * sample's arithmetic is independent of its batch mates, so the images are bit-identical with 1 and 2.
+ * TVC_OPT_SD_PRECISION (default 0): the 16-bit format of the latent-diffusion model.  0 = bf16.  1 = IEEE fp16, the dtype the
+ * reference runs Stable Diffusion in (src/sd_ref.py:222 torch_dtype "float16"): every 16-bit tensor given to tvc_sd_load holds
+ * fp16 bits, every 16-bit activation between kernels is fp16, the products run on v_mfma_f32_16x16x32_f16 (the bf16 rate) with
+ * fp32 accumulation; the same launches, tiles, arena, K splits, streams and chunking as mode 0, each with its bit-identity
+ * guarantee.  fp32 as in mode 0: GroupNorm / LayerNorm statistics, softmax, SiLU, GEGLU, biases, the time embedding's sin / cos,
+ * classifier-free guidance, the scheduler arithmetic; latents, text states and images cross the ABI as fp32 in both modes.
+ * fp16 keeps 10 mantissa bits to bf16's 7 but its range ends at 65504: a weight or an activation beyond it becomes +-inf (never
+ * clamped) and the output goes non-finite.  tvc_sd_attention / _ex read their operands in the handle's format.
+ * Any other value: TVC_E_INVALID.  The tensors registered by tvc_sd_load are one format, so a DIFFERENT value while a model is
+ * loaded on the handle returns TVC_E_STATE (set it before tvc_sd_load; the value it already has is always accepted).
+ * Independent of TVC_OPT_TOWER_PRECISION: the text states arrive as fp32 whatever mode the towers ran in. */
 enum { TVC_OPT_TEXT_PACKING = 1, TVC_OPT_MAX_CHUNK_IMAGES = 2, TVC_OPT_MAX_CHUNK_TEXTS = 3,
        TVC_OPT_BANK_FILTER = 4, TVC_OPT_TEXT_GROUP = 5, TVC_OPT_POOLED_LAST_LAYER = 6, TVC_OPT_TOWER_PRECISION = 7,
-       TVC_OPT_SD_ARENA_BYTES = 8, TVC_OPT_SD_STREAMS = 9 };
+       TVC_OPT_SD_ARENA_BYTES = 8, TVC_OPT_SD_STREAMS = 9, TVC_OPT_SD_PRECISION = 10 };
 int tvc_set_option(tvc_handle* h, int32_t option, int64_t value);
 
 /* Register fp32 copies of the tower weights for TVC_OPT_TOWER_PRECISION = 1 (either may be NULL).  Referenced, not
@@ -490,7 +501,8 @@ int tvc_layernorm_backward(tvc_handle* h, const float* x_dev, const uint16_t* dy
  * Stable Diffusion 2.x (src/__init__.py:110-113 lists stable-diffusion-2-1): per-level head counts, linear proj_in /
  * proj_out ([C, C] weights -- a 1 x 1 convolution on token rows is the same GEMM), cross-attention width 1024,
  * optionally v-prediction.
- * Activations are bf16 token-major (NHWC) between GEMMs, statistics / softmax / scheduler arithmetic fp32. */
+ * Activations are 16-bit token-major (NHWC) between GEMMs -- bf16, or IEEE fp16 with TVC_OPT_SD_PRECISION = 1 --, statistics /
+ * softmax / scheduler arithmetic fp32. */
 typedef struct {
     int32_t in_channels, out_channels;           /* 4, 4                                            */
     int32_t n_blocks;                            /* 4                                               */
@@ -524,6 +536,8 @@ typedef struct { const char* name; const void* ptr; } tvc_named_tensor;
  *   biases, norm gains / offsets, post_quant_conv.weight [4, 4]  -> fp32
  *   every bf16 matrix must be READABLE up to the next multiple of 256 rows (zero rows appended by the host): the GEMM
  *   stages whole 256-row tiles of it even where Co (320, 640, 4 ...) is not a multiple of 256
+ * With TVC_OPT_SD_PRECISION = 1 (set BEFORE this call) every tensor listed as bf16 above holds IEEE fp16 bits instead, same
+ * shapes and padding; a weight beyond 65504 is +-inf in that format (never clamped) and the outputs go non-finite.
  * Referenced, not copied (the caller keeps them alive), except the resnets' time projections, which are gathered into
  * one matrix inside the handle.  Either half may be absent (UNet-only / VAE-only handles). */
 int tvc_sd_load(tvc_handle* h, const tvc_sd_desc* desc, const tvc_named_tensor* tensors, int32_t n_tensors, void* stream);
@@ -550,13 +564,15 @@ int tvc_sd_generate(tvc_handle* h, const float* cond_dev, const float* uncond_de
 int tvc_sd_block(tvc_handle* h, int32_t kind, const char* prefix, const float* x_dev, int32_t n, int32_t Cin, int32_t H,
                  int32_t W, const float* temb_dev, const float* ctx_dev, int32_t Cout, int32_t vae, float* out_dev, void* stream);
 
-/* Streaming attention of the UNet (parity tests): q [n * Tq, heads * dh], k / v [n * Tk, heads * dh], out like q; bf16. */
+/* Streaming attention of the UNet (parity tests): q [n * Tq, heads * dh], k / v [n * Tk, heads * dh], out like q; 16-bit in
+ * the handle's SD format: bf16, or IEEE fp16 after TVC_OPT_SD_PRECISION = 1 (products on the f16 MFMA, fp16 probabilities and
+ * outputs; an operand beyond 65504 is +-inf, never clamped, and its rows come out non-finite). */
 int tvc_sd_attention(tvc_handle* h, const uint16_t* q_dev, const uint16_t* k_dev, const uint16_t* v_dev, uint16_t* out_dev,
                      int32_t n, int32_t heads, int32_t Tq, int32_t Tk, int32_t dh, void* stream);
 /* The same with one row stride (in elements) per operand, as the model's fused projections pass them: head h of a row
  * occupies its columns [h * dh, (h + 1) * dh), columns beyond heads * dh are neither read nor written.  ldq / ldk / ldv
  * multiples of 8, ldo a multiple of 4, each >= heads * dh, q / k / v 16-byte and out 8-byte aligned; anything else
- * returns TVC_E_INVALID and launches nothing. */
+ * returns TVC_E_INVALID and launches nothing.  The operands are in the handle's SD format, as for tvc_sd_attention. */
 int tvc_sd_attention_ex(tvc_handle* h, const uint16_t* q_dev, int64_t ldq, const uint16_t* k_dev, int64_t ldk,
                         const uint16_t* v_dev, int64_t ldv, uint16_t* out_dev, int64_t ldo, int32_t n, int32_t heads,
                         int32_t Tq, int32_t Tk, int32_t dh, void* stream);

@@ -25,6 +25,7 @@ TVC_OPT_POOLED_LAST_LAYER = 6
 TVC_OPT_TOWER_PRECISION = 7
 TVC_OPT_SD_ARENA_BYTES = 8
 TVC_OPT_SD_STREAMS = 9
+TVC_OPT_SD_PRECISION = 10
 
 
 class TVCError(RuntimeError):

@@ -115,6 +115,7 @@ struct tvc_handle {
     std::vector<void*> split_owned;
     bool split_ready = false;
     struct SdState* sd = nullptr;   // latent-diffusion model (tvc_sd.cpp), owned
+    int sd_precision = 0;           // TVC_OPT_SD_PRECISION: 0 = bf16, 1 = IEEE fp16; fixed while a model is loaded (its tensors are one format)
     size_t sd_arena_bytes = (size_t)48 << 30;   // TVC_OPT_SD_ARENA_BYTES: activation arena of one UNet evaluation
     // TVC_OPT_SD_STREAMS: the two classifier-free-guidance halves of a UNet evaluation on two HIP streams (tvc_sd.cpp)
     int sd_streams = 2;

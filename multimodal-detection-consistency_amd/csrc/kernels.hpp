@@ -196,32 +196,36 @@ hipError_t launch_rows_split(const float* x, int64_t ld_in, uint16_t* out, int64
 hipError_t launch_attention_split(const float* qkv, uint16_t* out, const int32_t* starts, int n_seq, int seq_len, int heads,
                                   int causal, hipStream_t stream, const int32_t* pfx = nullptr);
 
-// ---- sd_ops.hip / sd_attention.hip: latent-diffusion reference generator (bf16 token-major activations)
+// ---- sd_ops.hip / sd_attention.hip: latent-diffusion reference generator (16-bit token-major activations)
+// f16 (TVC_OPT_SD_PRECISION = 1): every 16-bit tensor a launcher reads or writes is IEEE fp16 instead of bf16.  The launchers
+// without the flag (im2col3x3, relayout, concat; launch_transpose_bf16) only move 16-bit words: one instantiation serves both.
 hipError_t sd_im2col3x3(const uint16_t* in, uint16_t* out, int n, int Hi, int Wi, int C, int stride, int up, hipStream_t st);
-hipError_t sd_im2col_in(const float* in, uint16_t* out, int n, int Cin, int H, int W, int Kp, float scale, hipStream_t st);
+hipError_t sd_im2col_in(const float* in, uint16_t* out, int n, int Cin, int H, int W, int Kp, float scale, hipStream_t st, int f16 = 0);
 hipError_t sd_groupnorm(const uint16_t* x, const float* tadd, int64_t ld_t, const float* gamma, const float* beta, uint16_t* y,
                         int n, int H, int W, int C, int groups, float eps, int silu, int in_pad, int out_pad, float* ws,
-                        hipStream_t st);
+                        hipStream_t st, int f16 = 0);
 hipError_t sd_relayout(const uint16_t* in, uint16_t* out, int n, int H, int W, int C, int in_pad, int out_pad, int up, hipStream_t st);
-hipError_t sd_add_padded(const uint16_t* a, const uint16_t* b_padded, uint16_t* out, int n, int H, int W, int C, hipStream_t st);
+hipError_t sd_add_padded(const uint16_t* a, const uint16_t* b_padded, uint16_t* out, int n, int H, int W, int C, hipStream_t st,
+                         int f16 = 0);
+// add: y = LN(r16(x + add)), the 16-bit sum also to sum_out
 hipError_t sd_layernorm_bf16(const uint16_t* x, const float* g, const float* b, uint16_t* y, int64_t rows, int C, float eps, hipStream_t st,
-                             const uint16_t* add = nullptr, uint16_t* sum_out = nullptr);     // add: y = LN(bf16(x + add)), the sum also to sum_out
-hipError_t sd_geglu(const uint16_t* in, uint16_t* out, int64_t rows, int Ch, hipStream_t st);
-hipError_t sd_add_bf16(const uint16_t* a, const uint16_t* b, uint16_t* out, int64_t n, hipStream_t st);
+                             const uint16_t* add = nullptr, uint16_t* sum_out = nullptr, int f16 = 0);
+hipError_t sd_geglu(const uint16_t* in, uint16_t* out, int64_t rows, int Ch, hipStream_t st, int f16 = 0);
+hipError_t sd_add_bf16(const uint16_t* a, const uint16_t* b, uint16_t* out, int64_t n, hipStream_t st, int f16 = 0);
 hipError_t sd_concat(const uint16_t* a, int Ca, const uint16_t* b, int Cb, uint16_t* out, int64_t tokens, hipStream_t st);
-hipError_t sd_cast_silu(const float* in, uint16_t* out, int64_t n, int silu, hipStream_t st);
+hipError_t sd_cast_silu(const float* in, uint16_t* out, int64_t n, int silu, hipStream_t st, int f16 = 0);
 hipError_t sd_tokens_to_nchw(const float* in, int64_t ld, float* out, int n, int C, int H, int W, float mul, float add, int clamp01,
                              int in_pad, hipStream_t st);
 hipError_t sd_pointwise_small(const float* in, const float* w, const float* bias, float* out, int n, int C, int HW, float in_scale, hipStream_t st);
 hipError_t sd_cfg(const float* e, float* out, int64_t n, float g, hipStream_t st);
 hipError_t sd_lincomb(float* out, const float* sample, float cs, float ce, const float* e0, float c0, const float* e1, float c1,
                       const float* e2, float c2, const float* e3, float c3, int64_t n, hipStream_t st);
-hipError_t sd_softmax_rows(const float* s, uint16_t* p, int64_t rows, int T, float scale, hipStream_t st);
-hipError_t sd_nchw_to_tokens(const float* in, uint16_t* out, int n, int C, int HW, hipStream_t st);
-hipError_t sd_tokens_bf16_to_nchw(const uint16_t* in, float* out, int n, int C, int HW, hipStream_t st);
-hipError_t sd_timestep_embed(uint16_t* out, int n, int dim, float t, hipStream_t st);
-// Q [n * Tq, ldq], K / V [n * Tk, ldk / ldv], O [n * Tq, ldo] bf16; head h = columns [h * dh, (h + 1) * dh); dh % 8 == 0, <= 160
+hipError_t sd_softmax_rows(const float* s, uint16_t* p, int64_t rows, int T, float scale, hipStream_t st, int f16 = 0);
+hipError_t sd_nchw_to_tokens(const float* in, uint16_t* out, int n, int C, int HW, hipStream_t st, int f16 = 0);
+hipError_t sd_tokens_bf16_to_nchw(const uint16_t* in, float* out, int n, int C, int HW, hipStream_t st, int f16 = 0);
+hipError_t sd_timestep_embed(uint16_t* out, int n, int dim, float t, hipStream_t st, int f16 = 0);
+// Q [n * Tq, ldq], K / V [n * Tk, ldk / ldv], O [n * Tq, ldo] bf16 (fp16 with f16); head h = columns [h * dh, (h + 1) * dh); dh % 8 == 0, <= 160
 hipError_t sd_flash_attention(const uint16_t* Q, int64_t ldq, const uint16_t* K, int64_t ldk, const uint16_t* V, int64_t ldv,
-                              uint16_t* O, int64_t ldo, int n, int heads, int Tq, int Tk, int dh, hipStream_t st);
+                              uint16_t* O, int64_t ldo, int n, int heads, int Tq, int Tk, int dh, hipStream_t st, int f16 = 0);
 hipError_t sd_resize_norm(const float* in, float* out, int n, int H, int W, int Hr, int Wr, int oy, int ox, int S, int cubic,
                           const float* mean, const float* sd, hipStream_t st);

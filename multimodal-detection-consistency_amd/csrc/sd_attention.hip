@@ -18,6 +18,12 @@
 // parameter (piece -> (row, chunk) is a compile-time division), full tiles are loaded unguarded through per-thread
 // pointers, the ragged last tile clamps its row index instead of masking, and the "key >= Tk" initialisation of the
 // scores exists only in that last tile.
+//
+// F16 (TVC_OPT_SD_PRECISION = 1): Q, K, V and O hold IEEE fp16 instead of bf16 -- the same bytes, LDS images, fragment layouts
+// and launch shapes; the three products (scores, P.V, the ones.P row sum) run on v_mfma_f32_16x16x32_f16 and the
+// probabilities / outputs are rounded to fp16.  The lazy maximum keeps the probabilities <= 2^8, far inside fp16's range;
+// a probability below fp16's subnormal floor (2^-24 of the row's reference maximum) becomes 0, where bf16 would keep it with
+// 8 bits: it is below half an ulp of the row sum either way.  Inputs beyond 65504 are the caller's +-inf (never clamped).
 #include "common.hpp"
 #include "kernels.hpp"
 #include "launch.hpp"
@@ -26,6 +32,18 @@
 namespace {
 
 __device__ __forceinline__ float mx3(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+
+// Two transposed 8-byte LDS reads (ds_read_b64_tr_b16) -> one MFMA A fragment of 8.  The instruction moves 16-bit words, so
+// both formats read through the bf16-typed builtin and the fragment is bit-cast to the format's x8 (as attention.hip does).
+template <bool F16>
+__device__ __forceinline__ typename Op16<F16>::x8 read_tr16_pair(const char* p0, const char* p1) {
+    const bf16x4_t v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)p0);
+    const bf16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)p1);
+    bf16x8_t a;
+    a[0] = v0[0]; a[1] = v0[1]; a[2] = v0[2]; a[3] = v0[3];
+    a[4] = v1[0]; a[5] = v1[1]; a[6] = v1[2]; a[7] = v1[3];
+    return __builtin_bit_cast(typename Op16<F16>::x8, a);
+}
 
 template <int DH, int QB, int NW>
 struct FaCfg {
@@ -53,13 +71,14 @@ struct FaCfg {
     static constexpr int NSETS = OCC2 ? 1 : 2;
 };
 
-template <int DH, int QB, int NW>
+template <int DH, int QB, int NW, bool F16>
 __global__ __launch_bounds__(NW * 64, (NW == 8 && DH <= 48) ? 4 : 1)    /* = FaCfg::OCC2 */ void sd_flash_attention_kernel(const uint16_t* __restrict__ Q, int64_t ldq,
                                                                  const uint16_t* __restrict__ K, int64_t ldk,
                                                                  const uint16_t* __restrict__ V, int64_t ldv,
                                                                  uint16_t* __restrict__ O, int64_t ldo, int Tq, int Tk,
                                                                  float scale_log2, int heads, int nqb) {
     using C = FaCfg<DH, QB, NW>;
+    using x8 = typename Op16<F16>::x8;
     constexpr int KS = C::KS, DV = C::DV, NT = C::NT;
     __shared__ __attribute__((aligned(16))) char smem[C::KBYTES + C::VBYTES];
     char* ldsK = smem;
@@ -88,7 +107,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && DH <= 48) ? 4 : 1)    /* = FaC
         }
 
     // ---- Q fragments (registers, whole kernel): lane holds Q[q][32 s + 8 g .. + 7] of its QB query blocks
-    bf16x8_t bq[QB][KS];
+    x8 bq[QB][KS];
 #pragma unroll
     for (int u = 0; u < QB; ++u) {
         int qrow = q0 + u * 16 + r16;
@@ -99,7 +118,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && DH <= 48) ? 4 : 1)    /* = FaC
             const int c = 4 * s + g;
             u32x4_t v = u32x4_t{0u, 0u, 0u, 0u};
             if (c < C::DCH) v = *(const u32x4_t*)(qp + c * 8);
-            bq[u][s] = __builtin_bit_cast(bf16x8_t, v);
+            bq[u][s] = __builtin_bit_cast(x8, v);
         }
     }
 
@@ -168,7 +187,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && DH <= 48) ? 4 : 1)    /* = FaC
     //    block and tile are skipped by a wave-uniform branch.
     f32x4_t o[QB][DV], osum[QB];
     float m_run[QB];
-    const bf16x8_t ones = __builtin_bit_cast(bf16x8_t, u32x4_t{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u});
+    const x8 ones = __builtin_bit_cast(x8, u32x4_t{Op16<F16>::ONE2, Op16<F16>::ONE2, Op16<F16>::ONE2, Op16<F16>::ONE2});
 #pragma unroll
     for (int u = 0; u < QB; ++u) {
         m_run[u] = -INFINITY;
@@ -201,12 +220,12 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && DH <= 48) ? 4 : 1)    /* = FaC
             const char* kr = ldsK + (t * 16 + r16) * C::KROW + g * 16;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                const bf16x8_t a = *(const bf16x8_t*)(kr + ks * 64);
+                const x8 a = *(const x8*)(kr + ks * 64);
 #pragma unroll
-                for (int u = 0; u < QB; ++u) s[u][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bq[u][ks], s[u][t], 0, 0, 0);
+                for (int u = 0; u < QB; ++u) s[u][t] = Op16<F16>::mfma(a, bq[u][ks], s[u][t]);
             }
         }
-        bf16x8_t pb[QB][2];
+        x8 pb[QB][2];
 #pragma unroll
         for (int u = 0; u < QB; ++u) {
             // IEEE-754-2019 maximum (v_maximum3_f32, NaN-propagating: no canonicalising copies of the MFMA outputs)
@@ -234,8 +253,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && DH <= 48) ? 4 : 1)    /* = FaC
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
                 const f32x4_t p0 = s[u][2 * kk], p1 = s[u][2 * kk + 1];
-                pb[u][kk] = __builtin_bit_cast(bf16x8_t, u32x4_t{pack_bf16x2(p0[0], p0[1]), pack_bf16x2(p0[2], p0[3]),
-                                                                  pack_bf16x2(p1[0], p1[1]), pack_bf16x2(p1[2], p1[3])});
+                pb[u][kk] = __builtin_bit_cast(x8, u32x4_t{Op16<F16>::pack2(p0[0], p0[1]), Op16<F16>::pack2(p0[2], p0[3]),
+                                                            Op16<F16>::pack2(p1[0], p1[1]), Op16<F16>::pack2(p1[2], p1[3])});
             }
         }
         // ---- O^T += V^T . P^T, two k-steps of 32 keys; a V^T fragment feeds all QB blocks
@@ -244,18 +263,12 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && DH <= 48) ? 4 : 1)    /* = FaC
 #pragma unroll
             for (int md = 0; md < DV; ++md) {
                 const char* vb = ldsV + tr_off + md * 32;
-                const bf16x4_t v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                    (__attribute__((address_space(3))) bf16x4_t*)(vb + (2 * kk) * 16 * C::VROW));
-                const bf16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                    (__attribute__((address_space(3))) bf16x4_t*)(vb + (2 * kk + 1) * 16 * C::VROW));
-                bf16x8_t a;
-                a[0] = v0[0]; a[1] = v0[1]; a[2] = v0[2]; a[3] = v0[3];
-                a[4] = v1[0]; a[5] = v1[1]; a[6] = v1[2]; a[7] = v1[3];
+                const x8 a = read_tr16_pair<F16>(vb + (2 * kk) * 16 * C::VROW, vb + (2 * kk + 1) * 16 * C::VROW);
 #pragma unroll
-                for (int u = 0; u < QB; ++u) o[u][md] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, pb[u][kk], o[u][md], 0, 0, 0);
+                for (int u = 0; u < QB; ++u) o[u][md] = Op16<F16>::mfma(a, pb[u][kk], o[u][md]);
             }
 #pragma unroll
-            for (int u = 0; u < QB; ++u) osum[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pb[u][kk], osum[u], 0, 0, 0);
+            for (int u = 0; u < QB; ++u) osum[u] = Op16<F16>::mfma(ones, pb[u][kk], osum[u]);
         }
     };
     if (C::NSETS == 1) {
@@ -279,8 +292,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && DH <= 48) ? 4 : 1)    /* = FaC
                 const int d = md * 16 + 4 * g;
                 if (d < DH) {
                     u32x2_t w;
-                    w[0] = pack_bf16x2(o[u][md][0] * inv, o[u][md][1] * inv);
-                    w[1] = pack_bf16x2(o[u][md][2] * inv, o[u][md][3] * inv);
+                    w[0] = Op16<F16>::pack2(o[u][md][0] * inv, o[u][md][1] * inv);
+                    w[1] = Op16<F16>::pack2(o[u][md][2] * inv, o[u][md][3] * inv);
                     *(u32x2_t*)(op + d) = w;
                 }
             }
@@ -288,13 +301,13 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && DH <= 48) ? 4 : 1)    /* = FaC
     }
 }
 
-template <int DH, int QB, int NW>
+template <int DH, int QB, int NW, bool F16>
 hipError_t launch_fa(const uint16_t* Q, int64_t ldq, const uint16_t* K, int64_t ldk, const uint16_t* V, int64_t ldv,
                      uint16_t* O, int64_t ldo, int n, int heads, int Tq, int Tk, hipStream_t st) {
     const float scale_log2 = 1.4426950408889634f / sqrtf((float)DH);
     const int nqb = (Tq + NW * 16 * QB - 1) / (NW * 16 * QB);
     dim3 grid((unsigned)((int64_t)nqb * heads * n));
-    return launch<sd_flash_attention_kernel<DH, QB, NW>>(grid, dim3(NW * 64), 0, st, Q, ldq, K, ldk, V, ldv, O, ldo, Tq, Tk, scale_log2,
+    return launch<sd_flash_attention_kernel<DH, QB, NW, F16>>(grid, dim3(NW * 64), 0, st, Q, ldq, K, ldk, V, ldv, O, ldo, Tq, Tk, scale_log2,
                                                          heads, nqb);
 }
 
@@ -302,7 +315,7 @@ hipError_t launch_fa(const uint16_t* Q, int64_t ldq, const uint16_t* K, int64_t 
 
 // Q [n * Tq, ldq], K / V [n * Tk, ldk / ldv], O [n * Tq, ldo]; head h occupies columns [h * dh, (h + 1) * dh)
 hipError_t sd_flash_attention(const uint16_t* Q, int64_t ldq, const uint16_t* K, int64_t ldk, const uint16_t* V, int64_t ldv,
-                              uint16_t* O, int64_t ldo, int n, int heads, int Tq, int Tk, int dh, hipStream_t st) {
+                              uint16_t* O, int64_t ldo, int n, int heads, int Tq, int Tk, int dh, hipStream_t st, int f16) {
     if (n <= 0 || Tq <= 0) return hipSuccess;
     if (Tk <= 0 || heads < 1 || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 || (int64_t)n * heads * ((Tq + 63) / 64) > 0x7fffffffLL)
         return hipErrorInvalidValue;
@@ -317,11 +330,15 @@ hipError_t sd_flash_attention(const uint16_t* Q, int64_t ldq, const uint16_t* K,
     if (items * ((Tq + 255) / 256) >= 512) shape = 3;        // 3: 8 waves x 2 blocks (256 queries)
     if (shape_env) shape = shape_env;
     // head dims up to 80 have all three shapes, the wider ones shape 1 only; any other head_dim is not instantiated
-    return dispatch<8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 128, 160>(dh, [&](auto d) {
-        constexpr int DH = d.value, MAXSHAPE = DH <= 80 ? 3 : 1;
-        const int sh = shape < MAXSHAPE ? shape : MAXSHAPE;
-        if (sh == 3) return launch_fa<DH, (MAXSHAPE >= 3 ? 2 : 1), (MAXSHAPE >= 3 ? 8 : 4)>(Q, ldq, K, ldk, V, ldv, O, ldo, n, heads, Tq, Tk, st);
-        if (sh == 2) return launch_fa<DH, (MAXSHAPE >= 2 ? 2 : 1), 4>(Q, ldq, K, ldk, V, ldv, O, ldo, n, heads, Tq, Tk, st);
-        return launch_fa<DH, 1, 4>(Q, ldq, K, ldk, V, ldv, O, ldo, n, heads, Tq, Tk, st);
+    return dispatch<true, false>(f16 != 0, [&](auto h16) {
+        constexpr bool F16 = h16.value;
+        return dispatch<8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 128, 160>(dh, [&](auto d) {
+            constexpr int DH = d.value, MAXSHAPE = DH <= 80 ? 3 : 1;
+            const int sh = shape < MAXSHAPE ? shape : MAXSHAPE;
+            if (sh == 3)
+                return launch_fa<DH, (MAXSHAPE >= 3 ? 2 : 1), (MAXSHAPE >= 3 ? 8 : 4), F16>(Q, ldq, K, ldk, V, ldv, O, ldo, n, heads, Tq, Tk, st);
+            if (sh == 2) return launch_fa<DH, (MAXSHAPE >= 2 ? 2 : 1), 4, F16>(Q, ldq, K, ldk, V, ldv, O, ldo, n, heads, Tq, Tk, st);
+            return launch_fa<DH, 1, 4, F16>(Q, ldq, K, ldk, V, ldv, O, ldo, n, heads, Tq, Tk, st);
+        });
     });
 }

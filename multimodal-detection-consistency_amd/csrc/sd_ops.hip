@@ -50,6 +50,7 @@ __global__ __launch_bounds__(256) void im2col3x3_kernel(const uint16_t* __restri
 
 // fp32 NCHW [n, Cin, H, W] (Cin * 9 <= Kp) -> bf16 rows [n * H * W, Kp], column tap * Cin + ci, zero padded;
 // the input is multiplied by `scale` (the VAE's 1 / scaling_factor)
+template <bool F16>
 __global__ __launch_bounds__(256) void im2col_in_kernel(const float* __restrict__ in, uint16_t* __restrict__ out, int n,
                                                         int Cin, int H, int W, int Kp, float scale) {
     const int64_t total = (int64_t)n * H * W * Kp;
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(256) void im2col_in_kernel(const float* __restrict_
             const int yy = y + tap / 3 - 1, xx = x + tap % 3 - 1;
             if (yy >= 0 && yy < H && xx >= 0 && xx < W) v = in[((img * Cin + ci) * H + yy) * W + xx] * scale;
         }
-        out[t] = f32_to_bf16_bits(v);
+        out[t] = Op16<F16>::from_f32(v);
     }
 }
 
@@ -74,6 +75,7 @@ __global__ __launch_bounds__(256) void im2col_in_kernel(const float* __restrict_
 // with 16-byte loads (a wave reads whole rows) and keeps per-channel sums in registers; the per-channel sums of all token
 // lanes meet in LDS, thread g then adds its group's channels in a fixed order: part[n][slab][group] = {sum, sumsq}.
 // x' = x + tadd[n, c] (the resnet's time projection, fp32 [n, ld_t]) when given.  C % 8 == 0, C <= 4096.
+template <bool F16>
 __global__ __launch_bounds__(256) void gn_partial_kernel(const uint16_t* __restrict__ x, const float* __restrict__ tadd,
                                                          int64_t ld_t, float* __restrict__ part, int H, int W, int C, int groups,
                                                          int slab_tokens, int nslab, int in_pad) {
@@ -95,8 +97,8 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const uint16_t* __restr
                 const u32x4_t r0 = *(const u32x4_t*)(x + tok_row(img, t, H, W, in_pad) * C + v * 8);
                 const u32x4_t r1 = *(const u32x4_t*)(x + tok_row(img, t + lanes, H, W, in_pad) * C + v * 8);
                 float f[8], h8[8];
-                unpack8(r0, f);
-                unpack8(r1, h8);
+                unpack8<F16>(r0, f);
+                unpack8<F16>(r1, h8);
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     const float a = f[i] + ta[i], b2 = h8[i] + ta[i];
@@ -105,7 +107,7 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const uint16_t* __restr
             }
             for (; t < t1; t += lanes) {
                 float f[8];
-                unpack8(*(const u32x4_t*)(x + tok_row(img, t, H, W, in_pad) * C + v * 8), f);
+                unpack8<F16>(*(const u32x4_t*)(x + tok_row(img, t, H, W, in_pad) * C + v * 8), f);
 #pragma unroll
                 for (int i = 0; i < 8; ++i) { const float a = f[i] + ta[i]; s[i] += a; q[i] += a * a; }
             }
@@ -135,6 +137,7 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const uint16_t* __restr
 // The image's {mean, rstd} per group come first: every workgroup sums the slabs' partials of ITS image in fp64 (thread = (group,
 // one of 8 slab lanes), then the 8 lanes in a fixed order) -- a few KB out of L2 per workgroup instead of a third kernel
 // between the statistics pass and this one.
+template <bool F16>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const uint16_t* __restrict__ x, const float* __restrict__ tadd,
                                                        int64_t ld_t, const float* __restrict__ part, int nslab, double count,
                                                        float eps, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -194,13 +197,13 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const uint16_t* __restric
             u32x4_t o = u32x4_t{0u, 0u, 0u, 0u};
             if (xx >= 0 && xx < W) {
                 float f[8];
-                unpack8(*(const u32x4_t*)(xrow + (int64_t)xx * C + v * 8), f);
+                unpack8<F16>(*(const u32x4_t*)(xrow + (int64_t)xx * C + v * 8), f);
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     const float val = fmaf(f[i], sc[i], sh[i]);
                     f[i] = silu ? silu_f(val) : val;
                 }
-                o = pack8(f);
+                o = pack8<F16>(f);
             }
             *(u32x4_t*)(yrow + (int64_t)xo * C + v * 8) = o;
         }
@@ -211,6 +214,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const uint16_t* __restric
 // With `add` the row is first replaced by bf16(x + add), which is also written to `sum_out` (the residual stream a
 // transformer block carries on): the residual add and the LayerNorm that follows it in ONE pass, bit-identical to
 // add_bf16_kernel followed by this kernel (the sum is rounded to bf16 before it is normalised, as the stored one is).
+template <bool F16>
 __global__ __launch_bounds__(256) void ln_bf16_kernel(const uint16_t* __restrict__ x, const float* __restrict__ g,
                                                       const float* __restrict__ b, uint16_t* __restrict__ y, int64_t rows,
                                                       int C, float eps, const uint16_t* __restrict__ add,
@@ -226,15 +230,15 @@ __global__ __launch_bounds__(256) void ln_bf16_kernel(const uint16_t* __restrict
     for (int i = 0; i < 3; ++i) {
         const int v = lane + i * 64;
         if (v < cv) {
-            unpack8(xr[v], f[i]);
+            unpack8<F16>(xr[v], f[i]);
             if (add) {
                 float a8[8];
-                unpack8(((const u32x4_t*)(add + row * C))[v], a8);
+                unpack8<F16>(((const u32x4_t*)(add + row * C))[v], a8);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) a8[e] += f[i][e];
-                const u32x4_t pk = pack8(a8);
+                const u32x4_t pk = pack8<F16>(a8);
                 ((u32x4_t*)(sum_out + row * C))[v] = pk;
-                unpack8(pk, f[i]);
+                unpack8<F16>(pk, f[i]);
             }
 #pragma unroll
             for (int e = 0; e < 8; ++e) s += f[i][e];
@@ -259,12 +263,13 @@ __global__ __launch_bounds__(256) void ln_bf16_kernel(const uint16_t* __restrict
             float o[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = (f[i][e] - mean) * rstd * g[v * 8 + e] + b[v * 8 + e];
-            yr[v] = pack8(o);
+            yr[v] = pack8<F16>(o);
         }
     }
 }
 
 // ---- GEGLU: in [rows, 2 * Ch] (value | gate) -> out [rows, Ch] = value * gelu(gate), exact (erf) GELU
+template <bool F16>
 __global__ __launch_bounds__(256) void geglu_kernel(const uint16_t* __restrict__ in, uint16_t* __restrict__ out, int64_t rows,
                                                     int Ch) {
     const int cv = Ch >> 3;
@@ -273,28 +278,30 @@ __global__ __launch_bounds__(256) void geglu_kernel(const uint16_t* __restrict__
         const int c = (int)(t % cv);
         const int64_t r = t / cv;
         float a[8], g[8];
-        unpack8(*(const u32x4_t*)(in + r * 2 * Ch + c * 8), a);
-        unpack8(*(const u32x4_t*)(in + r * 2 * Ch + Ch + c * 8), g);
+        unpack8<F16>(*(const u32x4_t*)(in + r * 2 * Ch + c * 8), a);
+        unpack8<F16>(*(const u32x4_t*)(in + r * 2 * Ch + Ch + c * 8), g);
 #pragma unroll
         for (int i = 0; i < 8; ++i) a[i] *= gelu_erf(g[i]);
-        *(u32x4_t*)(out + r * Ch + c * 8) = pack8(a);
+        *(u32x4_t*)(out + r * Ch + c * 8) = pack8<F16>(a);
     }
 }
 
 // ---- out = a + b (bf16, n8 pieces of 8)
+template <bool F16>
 __global__ __launch_bounds__(256) void add_bf16_kernel(const uint16_t* __restrict__ a, const uint16_t* __restrict__ b,
                                                        uint16_t* __restrict__ out, int64_t n8) {
     for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n8; t += (int64_t)gridDim.x * 256) {
         float x[8], y[8];
-        unpack8(((const u32x4_t*)a)[t], x);
-        unpack8(((const u32x4_t*)b)[t], y);
+        unpack8<F16>(((const u32x4_t*)a)[t], x);
+        unpack8<F16>(((const u32x4_t*)b)[t], y);
 #pragma unroll
         for (int i = 0; i < 8; ++i) x[i] += y[i];
-        ((u32x4_t*)out)[t] = pack8(x);
+        ((u32x4_t*)out)[t] = pack8<F16>(x);
     }
 }
 
 // ---- out[dense] = a[dense] + b[PADDED layout] (the residual add behind a resnet's second convolution)
+template <bool F16>
 __global__ __launch_bounds__(256) void add_padded_kernel(const uint16_t* __restrict__ a, const uint16_t* __restrict__ b,
                                                          uint16_t* __restrict__ out, int n, int H, int W, int C) {
     const int cv = C >> 3;
@@ -305,11 +312,11 @@ __global__ __launch_bounds__(256) void add_padded_kernel(const uint16_t* __restr
         const int img = (int)(tok / ((int64_t)H * W));
         const int p = (int)(tok - (int64_t)img * H * W);
         float x[8], y[8];
-        unpack8(((const u32x4_t*)a)[t], x);
-        unpack8(*(const u32x4_t*)(b + tok_row(img, p, H, W, 1) * C + c * 8), y);
+        unpack8<F16>(((const u32x4_t*)a)[t], x);
+        unpack8<F16>(*(const u32x4_t*)(b + tok_row(img, p, H, W, 1) * C + c * 8), y);
 #pragma unroll
         for (int i = 0; i < 8; ++i) x[i] += y[i];
-        ((u32x4_t*)out)[t] = pack8(x);
+        ((u32x4_t*)out)[t] = pack8<F16>(x);
     }
 }
 
@@ -350,11 +357,12 @@ __global__ __launch_bounds__(256) void concat_kernel(const uint16_t* __restrict_
 }
 
 // ---- fp32 -> bf16 with optional SiLU (time-embedding MLP)
+template <bool F16>
 __global__ __launch_bounds__(256) void cast_silu_kernel(const float* __restrict__ in, uint16_t* __restrict__ out, int64_t n,
                                                         int silu) {
     for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) {
         const float v = in[t];
-        out[t] = f32_to_bf16_bits(silu ? silu_f(v) : v);
+        out[t] = Op16<F16>::from_f32(silu ? silu_f(v) : v);
     }
 }
 
@@ -414,6 +422,7 @@ __global__ __launch_bounds__(256) void lincomb_kernel(float* __restrict__ out, c
 }
 
 // ---- row softmax of fp32 scores (already scaled) -> bf16 probabilities; one workgroup per row, T <= 16384
+template <bool F16>
 __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restrict__ s, uint16_t* __restrict__ p, int T, float scale) {
     __shared__ float red[4];
     const float* sr = s + (int64_t)blockIdx.x * T;
@@ -431,10 +440,11 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
     __syncthreads();
     const float inv = 1.0f / ((red[0] + red[1]) + (red[2] + red[3]));
-    for (int i = threadIdx.x; i < T; i += 256) pr[i] = f32_to_bf16_bits(__expf(sr[i] * scale - mx) * inv);
+    for (int i = threadIdx.x; i < T; i += 256) pr[i] = Op16<F16>::from_f32(__expf(sr[i] * scale - mx) * inv);
 }
 
 // ---- layout converters of the block-level entry points: fp32 NCHW <-> bf16 token-major
+template <bool F16>
 __global__ __launch_bounds__(256) void nchw_to_tokens_kernel(const float* __restrict__ in, uint16_t* __restrict__ out, int n, int C,
                                                              int HW) {
     const int64_t total = (int64_t)n * HW * C;
@@ -443,9 +453,10 @@ __global__ __launch_bounds__(256) void nchw_to_tokens_kernel(const float* __rest
         int64_t r = t / C;
         const int p = (int)(r % HW);
         const int64_t img = r / HW;
-        out[t] = f32_to_bf16_bits(in[(img * C + c) * HW + p]);
+        out[t] = Op16<F16>::from_f32(in[(img * C + c) * HW + p]);
     }
 }
+template <bool F16>
 __global__ __launch_bounds__(256) void tokens_bf16_to_nchw_kernel(const uint16_t* __restrict__ in, float* __restrict__ out, int n,
                                                                   int C, int HW) {
     const int64_t total = (int64_t)n * C * HW;
@@ -454,18 +465,19 @@ __global__ __launch_bounds__(256) void tokens_bf16_to_nchw_kernel(const uint16_t
         int64_t r = t / HW;
         const int c = (int)(r % C);
         const int64_t img = r / C;
-        out[t] = bf16_bits_to_f32(in[(img * HW + p) * C + c]);
+        out[t] = Op16<F16>::lo(in[(img * HW + p) * C + c]);
     }
 }
 
 // ---- sinusoidal timestep embedding (flip_sin_to_cos, freq_shift 0): out bf16 [n, dim] = [cos | sin](t * 10000^(-i / half))
+template <bool F16>
 __global__ __launch_bounds__(256) void timestep_embed_kernel(uint16_t* __restrict__ out, int n, int dim, float t) {
     const int half = dim >> 1;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n * dim; i += gridDim.x * 256) {
         const int k = i % dim;
         const int j = k < half ? k : k - half;
         const float ang = t * expf(-9.210340371976184f * (float)j / (float)half);
-        out[i] = f32_to_bf16_bits(k < half ? cosf(ang) : sinf(ang));
+        out[i] = Op16<F16>::from_f32(k < half ? cosf(ang) : sinf(ang));
     }
 }
 
@@ -536,9 +548,11 @@ hipError_t sd_im2col3x3(const uint16_t* in, uint16_t* out, int n, int Hi, int Wi
     return launch<im2col3x3_kernel>(grid_for(total), dim3(256), 0, st, in, out, n, Hi, Wi, C, Ho, Wo, stride, up);
 }
 
-hipError_t sd_im2col_in(const float* in, uint16_t* out, int n, int Cin, int H, int W, int Kp, float scale, hipStream_t st) {
+hipError_t sd_im2col_in(const float* in, uint16_t* out, int n, int Cin, int H, int W, int Kp, float scale, hipStream_t st, int f16) {
     if (9 * Cin > Kp) return hipErrorInvalidValue;
-    return launch<im2col_in_kernel>(grid_for((int64_t)n * H * W * Kp), dim3(256), 0, st, in, out, n, Cin, H, W, Kp, scale);
+    return dispatch<true, false>(f16 != 0, [&](auto h) {
+        return launch<im2col_in_kernel<h.value>>(grid_for((int64_t)n * H * W * Kp), dim3(256), 0, st, in, out, n, Cin, H, W, Kp, scale);
+    });
 }
 
 // ws: >= n * nslab * groups * 2 + n * groups * 2 floats (sd_groupnorm_ws_floats)
@@ -550,18 +564,20 @@ hipError_t sd_im2col_in(const float* in, uint16_t* out, int n, int Cin, int H, i
 
 hipError_t sd_groupnorm(const uint16_t* x, const float* tadd, int64_t ld_t, const float* gamma, const float* beta, uint16_t* y,
                         int n, int H, int W, int C, int groups, float eps, int silu, int in_pad, int out_pad, float* ws,
-                        hipStream_t st) {
+                        hipStream_t st, int f16) {
     if (groups > 32 || C % groups != 0 || C % 8 != 0 || C > 4096) return hipErrorInvalidValue;
     const int HW = H * W, slab = gn_slab_tokens(HW);
     const int nslab = (HW + slab - 1) / slab;
     float* part = ws;
     const int cv = C >> 3, Wv = cv < 256 ? cv : 256, lanes = 256 / Wv;
     const size_t lds = (size_t)lanes * C * 2 * 4;
-    const hipError_t e = launch<gn_partial_kernel>(dim3(n * nslab), dim3(256), lds, st, x, tadd, ld_t, part, H, W, C, groups, slab, nslab,
-                                                   in_pad);
-    if (e != hipSuccess) return e;
-    return launch<gn_apply_kernel>(dim3(n * (out_pad ? H + 2 : H)), dim3(256), 0, st, x, tadd, ld_t, part, nslab,
-                                   (double)HW * (C / groups), eps, gamma, beta, y, n, H, W, C, groups, silu, in_pad, out_pad);
+    return dispatch<true, false>(f16 != 0, [&](auto h) {
+        const hipError_t e = launch<gn_partial_kernel<h.value>>(dim3(n * nslab), dim3(256), lds, st, x, tadd, ld_t, part, H, W, C, groups,
+                                                                slab, nslab, in_pad);
+        if (e != hipSuccess) return e;
+        return launch<gn_apply_kernel<h.value>>(dim3(n * (out_pad ? H + 2 : H)), dim3(256), 0, st, x, tadd, ld_t, part, nslab,
+                                                (double)HW * (C / groups), eps, gamma, beta, y, n, H, W, C, groups, silu, in_pad, out_pad);
+    });
 }
 
 // H, W: the OUTPUT's extent (up: the input is (H / 2) x (W / 2))
@@ -571,26 +587,35 @@ hipError_t sd_relayout(const uint16_t* in, uint16_t* out, int n, int H, int W, i
     return launch<relayout_kernel>(grid_for(rows * (C >> 3)), dim3(256), 0, st, in, out, n, H, W, C, in_pad, out_pad, up);
 }
 
-hipError_t sd_add_padded(const uint16_t* a, const uint16_t* b_padded, uint16_t* out, int n, int H, int W, int C, hipStream_t st) {
+hipError_t sd_add_padded(const uint16_t* a, const uint16_t* b_padded, uint16_t* out, int n, int H, int W, int C, hipStream_t st,
+                         int f16) {
     if (C % 8 != 0) return hipErrorInvalidValue;
-    return launch<add_padded_kernel>(grid_for((int64_t)n * H * W * (C >> 3)), dim3(256), 0, st, a, b_padded, out, n, H, W, C);
+    return dispatch<true, false>(f16 != 0, [&](auto h) {
+        return launch<add_padded_kernel<h.value>>(grid_for((int64_t)n * H * W * (C >> 3)), dim3(256), 0, st, a, b_padded, out, n, H, W, C);
+    });
 }
 
 hipError_t sd_layernorm_bf16(const uint16_t* x, const float* g, const float* b, uint16_t* y, int64_t rows, int C, float eps,
-                             hipStream_t st, const uint16_t* add, uint16_t* sum_out) {
+                             hipStream_t st, const uint16_t* add, uint16_t* sum_out, int f16) {
     if (C % 8 != 0 || C > 1536 || ((add != nullptr) != (sum_out != nullptr))) return hipErrorInvalidValue;
     if (rows <= 0) return hipSuccess;
-    return launch<ln_bf16_kernel>(row_grid(rows), dim3(256), 0, st, x, g, b, y, rows, C, eps, add, sum_out);
+    return dispatch<true, false>(f16 != 0, [&](auto h) {
+        return launch<ln_bf16_kernel<h.value>>(row_grid(rows), dim3(256), 0, st, x, g, b, y, rows, C, eps, add, sum_out);
+    });
 }
 
-hipError_t sd_geglu(const uint16_t* in, uint16_t* out, int64_t rows, int Ch, hipStream_t st) {
+hipError_t sd_geglu(const uint16_t* in, uint16_t* out, int64_t rows, int Ch, hipStream_t st, int f16) {
     if (Ch % 8 != 0) return hipErrorInvalidValue;
-    return launch<geglu_kernel>(grid_for(rows * (Ch >> 3)), dim3(256), 0, st, in, out, rows, Ch);
+    return dispatch<true, false>(f16 != 0, [&](auto h) {
+        return launch<geglu_kernel<h.value>>(grid_for(rows * (Ch >> 3)), dim3(256), 0, st, in, out, rows, Ch);
+    });
 }
 
-hipError_t sd_add_bf16(const uint16_t* a, const uint16_t* b, uint16_t* out, int64_t n, hipStream_t st) {
+hipError_t sd_add_bf16(const uint16_t* a, const uint16_t* b, uint16_t* out, int64_t n, hipStream_t st, int f16) {
     if (n % 8 != 0) return hipErrorInvalidValue;
-    return launch<add_bf16_kernel>(grid_for(n >> 3), dim3(256), 0, st, a, b, out, n >> 3);
+    return dispatch<true, false>(f16 != 0, [&](auto h) {
+        return launch<add_bf16_kernel<h.value>>(grid_for(n >> 3), dim3(256), 0, st, a, b, out, n >> 3);
+    });
 }
 
 hipError_t sd_concat(const uint16_t* a, int Ca, const uint16_t* b, int Cb, uint16_t* out, int64_t tokens, hipStream_t st) {
@@ -598,8 +623,10 @@ hipError_t sd_concat(const uint16_t* a, int Ca, const uint16_t* b, int Cb, uint1
     return launch<concat_kernel>(grid_for(tokens * ((Ca + Cb) >> 3)), dim3(256), 0, st, a, Ca, b, Cb, out, tokens);
 }
 
-hipError_t sd_cast_silu(const float* in, uint16_t* out, int64_t n, int silu, hipStream_t st) {
-    return launch<cast_silu_kernel>(grid_for(n), dim3(256), 0, st, in, out, n, silu);
+hipError_t sd_cast_silu(const float* in, uint16_t* out, int64_t n, int silu, hipStream_t st, int f16) {
+    return dispatch<true, false>(f16 != 0, [&](auto h) {
+        return launch<cast_silu_kernel<h.value>>(grid_for(n), dim3(256), 0, st, in, out, n, silu);
+    });
 }
 
 hipError_t sd_tokens_to_nchw(const float* in, int64_t ld, float* out, int n, int C, int H, int W, float mul, float add, int clamp01,
@@ -623,21 +650,29 @@ hipError_t sd_lincomb(float* out, const float* sample, float cs, float ce, const
     return launch<lincomb_kernel>(grid_for(n), dim3(256), 0, st, out, sample, cs, ce, e0, c0, e1, c1, e2, c2, e3, c3, n);
 }
 
-hipError_t sd_softmax_rows(const float* s, uint16_t* p, int64_t rows, int T, float scale, hipStream_t st) {
+hipError_t sd_softmax_rows(const float* s, uint16_t* p, int64_t rows, int T, float scale, hipStream_t st, int f16) {
     if (rows <= 0) return hipSuccess;
-    return launch<softmax_rows_kernel>(dim3((unsigned)rows), dim3(256), 0, st, s, p, T, scale);
+    return dispatch<true, false>(f16 != 0, [&](auto h) {
+        return launch<softmax_rows_kernel<h.value>>(dim3((unsigned)rows), dim3(256), 0, st, s, p, T, scale);
+    });
 }
 
-hipError_t sd_nchw_to_tokens(const float* in, uint16_t* out, int n, int C, int HW, hipStream_t st) {
-    return launch<nchw_to_tokens_kernel>(grid_for((int64_t)n * C * HW), dim3(256), 0, st, in, out, n, C, HW);
+hipError_t sd_nchw_to_tokens(const float* in, uint16_t* out, int n, int C, int HW, hipStream_t st, int f16) {
+    return dispatch<true, false>(f16 != 0, [&](auto h) {
+        return launch<nchw_to_tokens_kernel<h.value>>(grid_for((int64_t)n * C * HW), dim3(256), 0, st, in, out, n, C, HW);
+    });
 }
 
-hipError_t sd_tokens_bf16_to_nchw(const uint16_t* in, float* out, int n, int C, int HW, hipStream_t st) {
-    return launch<tokens_bf16_to_nchw_kernel>(grid_for((int64_t)n * C * HW), dim3(256), 0, st, in, out, n, C, HW);
+hipError_t sd_tokens_bf16_to_nchw(const uint16_t* in, float* out, int n, int C, int HW, hipStream_t st, int f16) {
+    return dispatch<true, false>(f16 != 0, [&](auto h) {
+        return launch<tokens_bf16_to_nchw_kernel<h.value>>(grid_for((int64_t)n * C * HW), dim3(256), 0, st, in, out, n, C, HW);
+    });
 }
 
-hipError_t sd_timestep_embed(uint16_t* out, int n, int dim, float t, hipStream_t st) {
-    return launch<timestep_embed_kernel>(grid_for((int64_t)n * dim), dim3(256), 0, st, out, n, dim, t);
+hipError_t sd_timestep_embed(uint16_t* out, int n, int dim, float t, hipStream_t st, int f16) {
+    return dispatch<true, false>(f16 != 0, [&](auto h) {
+        return launch<timestep_embed_kernel<h.value>>(grid_for((int64_t)n * dim), dim3(256), 0, st, out, n, dim, t);
+    });
 }
 
 // in fp32 [n, 3, H, W] -> out fp32 [n, 3, S, S]: resize to (Hr, Wr), crop at (oy, ox), (v - mean) / std; cubic: bicubic else bilinear

@@ -847,6 +847,12 @@ int tvc_set_option(tvc_handle* h, int32_t option, int64_t value) {
         case TVC_OPT_SD_STREAMS:
             if (value < 1 || value > 2) return fail(h, TVC_E_INVALID, "tvc_set_option: TVC_OPT_SD_STREAMS must be 1 or 2");
             h->sd_streams = (int)value; return TVC_OK;
+        case TVC_OPT_SD_PRECISION:
+            if (value < 0 || value > 1) return fail(h, TVC_E_INVALID, "tvc_set_option: TVC_OPT_SD_PRECISION must be 0 (bf16) or 1 (fp16)");
+            // the tensors registered by tvc_sd_load are one format: the option moves only while no model is loaded
+            if (h->sd && (int)value != h->sd_precision)
+                return fail(h, TVC_E_STATE, "tvc_set_option: TVC_OPT_SD_PRECISION cannot change while a latent-diffusion model is loaded");
+            h->sd_precision = (int)value; return TVC_OK;
         default: return fail(h, TVC_E_INVALID, "tvc_set_option: unknown option");
     }
 }

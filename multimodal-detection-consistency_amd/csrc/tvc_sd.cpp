@@ -4,7 +4,8 @@
 // diffusers.StableDiffusionPipeline.  Geometry from the config.json files the reference holds
 // (cache/sd/models--runwayml--stable-diffusion-v1-5/snapshots/*/{unet,vae,scheduler}).
 //
-// Layout: activations are bf16 token-major [n * H * W, C] (NHWC); every convolution and linear layer is ONE call of
+// Layout: activations are 16-bit token-major -- bf16, or IEEE fp16 with TVC_OPT_SD_PRECISION = 1 (Run::f16: the same launches,
+// shapes and arena; the flag picks the GEMMs' MFMA and the row kernels' conversions) -- [n * H * W, C] (NHWC); every convolution and linear layer is ONE call of
 // the tower GEMM (gemm.hip; 3x3 convolutions gather their rows with sd_im2col3x3 -- stride-2 and nearest-2x-upsample
 // forms included --, 1x1 convolutions read the rows as they are); GroupNorm / LayerNorm / GEGLU / residual adds are
 // streaming row kernels (sd_ops.hip); attention is the streaming kernel of sd_attention.hip (VAE: one 512-wide head,
@@ -20,7 +21,7 @@ struct SdState {
     tvc_sd_desc d{};
     std::unordered_map<std::string, const void*> w;
     bool has_unet = false, has_vae = false;
-    void* temb_w = nullptr;      // bf16 [temb_total, time_dim]: every resnet's time_emb_proj.weight, gathered
+    void* temb_w = nullptr;      // 16-bit [temb_total, time_dim] (a byte copy: the handle's SD format): every resnet's time_emb_proj.weight, gathered
     void* temb_b = nullptr;      // fp32 [temb_total]
     int temb_total = 0;
     std::unordered_map<std::string, int> temb_off;
@@ -41,7 +42,7 @@ void tvc_sd_free(tvc_handle* h) {
 
 namespace {
 
-struct Act {             // bf16 token-major activation
+struct Act {             // 16-bit token-major activation (bf16, or fp16 with Run::f16)
     uint16_t* p = nullptr;
     int n = 0, H = 0, W = 0, C = 0;
     bool pad = false;    // PADDED layout (sd_ops.hip, tok_row): (H + 2) x (W + 2) rows per image -- what the 9-plane conv GEMM reads / writes
@@ -55,6 +56,10 @@ struct Run {
     SdState* S;
     hipStream_t st;
     bool dry;                 // sizing pass: allocate, launch nothing
+    // TVC_OPT_SD_PRECISION = 1: every registered 16-bit tensor and every 16-bit activation is IEEE fp16, the products run on
+    // the f16 MFMA.  Passed to every GEMM and to every row kernel that converts; sizes, splits, streams and chunking do not see it
+    // (TVC_EPI_BF16 below reads "the 16-bit epilogue", as in the towers' fp16 mode).
+    bool f16 = h->sd_precision == 1;
     char* base = nullptr;
     size_t off = 0, high = 0;
     size_t cap = 0;           // bytes behind `base` (the real pass): an allocation beyond it is an error, never a wild pointer
@@ -115,6 +120,7 @@ struct Run {
             g.splitk_ws_bytes = tiles * S * 256 * 256 * 4;
             g.splitk_ws = (float*)alloc(g.splitk_ws_bytes);
         }
+        g.f16 = f16;
         if (live()) hip(timed_gemm(h, g, st), what);
         off = mark;
     }
@@ -249,7 +255,7 @@ struct Run {
         const float* b = (const float*)W(prefix + "bias");
         if (live()) {
             ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)x.tok() * x.C * 6.0);
-            hip(sd_groupnorm(x.p, tadd, ld_t, g, b, y.p, x.n, x.H, x.W, x.C, S->d.norm_groups, eps, silu, x.pad, out_pad, ws, st),
+            hip(sd_groupnorm(x.p, tadd, ld_t, g, b, y.p, x.n, x.H, x.W, x.C, S->d.norm_groups, eps, silu, x.pad, out_pad, ws, st, f16),
                 "sd_groupnorm");
         }
         off = mark;
@@ -261,7 +267,7 @@ struct Run {
         const float* b = (const float*)W(prefix + "bias");
         if (live()) {
             ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)x.tok() * x.C * 4.0);
-            hip(sd_layernorm_bf16(x.p, g, b, y.p, x.tok(), x.C, 1e-5f, st), "sd_layernorm");
+            hip(sd_layernorm_bf16(x.p, g, b, y.p, x.tok(), x.C, 1e-5f, st, nullptr, nullptr, f16), "sd_layernorm");
         }
         return y;
     }
@@ -273,7 +279,7 @@ struct Run {
         const float* bb = (const float*)W(prefix + "bias");
         if (live()) {
             ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)a.tok() * a.C * 8.0);
-            hip(sd_layernorm_bf16(a.p, g, bb, y.p, a.tok(), a.C, 1e-5f, st, b.p, sum.p), "sd_add_layernorm");
+            hip(sd_layernorm_bf16(a.p, g, bb, y.p, a.tok(), a.C, 1e-5f, st, b.p, sum.p, f16), "sd_add_layernorm");
         }
         return y;
     }
@@ -281,7 +287,7 @@ struct Run {
         Act y = act(a.n, a.H, a.W, a.C);
         if (live()) {
             ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)a.tok() * a.C * 6.0);
-            hip(sd_add_bf16(a.p, b.p, y.p, a.tok() * a.C, st), "sd_add");
+            hip(sd_add_bf16(a.p, b.p, y.p, a.tok() * a.C, st, f16), "sd_add");
         }
         return y;
     }
@@ -289,7 +295,7 @@ struct Run {
                    int64_t ldo, int n, int heads, int Tq, int Tk, int dh) {
         if (!live()) return;
         ProfScope ps(h, st, TVC_PROF_ATTENTION, 4.0 * n * heads * (double)Tq * Tk * dh);
-        hip(sd_flash_attention(q, ldq, k, ldk, v, ldv, o, ldo, n, heads, Tq, Tk, dh, st), "sd_flash_attention");
+        hip(sd_flash_attention(q, ldq, k, ldk, v, ldv, o, ldo, n, heads, Tq, Tk, dh, st, f16), "sd_flash_attention");
     }
 
     // ResnetBlock2D: x + conv2(silu(gn2(conv1(silu(gn1(x))) + time projection))), 1x1 shortcut when the widths differ
@@ -310,7 +316,7 @@ struct Run {
         if (x.C != Cout) sc = linear(x, p + "conv_shortcut.weight", p + "conv_shortcut.bias", Cout);
         if (live()) {
             ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)x.tok() * Cout * 6.0);
-            hip(sd_add_padded(sc.p, h4.p, out.p, x.n, x.H, x.W, Cout, st), "sd_add_padded");
+            hip(sd_add_padded(sc.p, h4.p, out.p, x.n, x.H, x.W, Cout, st, f16), "sd_add_padded");
         }
         off = mark;
         return out;
@@ -352,13 +358,13 @@ struct Run {
             Act ge = act(n, x.H, x.W, 4 * C);
             if (live()) {
                 ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)x.tok() * C * 24.0);
-                hip(sd_geglu(gg.p, ge.p, gg.tok(), 4 * C, st), "sd_geglu");
+                hip(sd_geglu(gg.p, ge.p, gg.tok(), 4 * C, st, f16), "sd_geglu");
             }
             Act o = linear(ge, t + "ff.net.2.weight", t + "ff.net.2.bias", C);
             hs = add(hs, o);
         }
         Act po = linear(hs, p + "proj_out.weight", p + "proj_out.bias", C);
-        if (live()) hip(sd_add_bf16(x.p, po.p, out.p, out.tok() * C, st), "sd_add");
+        if (live()) hip(sd_add_bf16(x.p, po.p, out.p, out.tok() * C, st, f16), "sd_add");
         off = mark;
         return out;
     }
@@ -385,15 +391,15 @@ struct Run {
                 hip(hipMemcpy2DAsync(qc, (size_t)C * 2, rows, (size_t)3 * C * 2, (size_t)C * 2, T, hipMemcpyDeviceToDevice, st), "copy q");
                 hip(hipMemcpy2DAsync(kc, (size_t)C * 2, rows + C, (size_t)3 * C * 2, (size_t)C * 2, T, hipMemcpyDeviceToDevice, st), "copy k");
                 hip(hipMemcpy2DAsync(pr, (size_t)C * 2, rows + 2 * C, (size_t)3 * C * 2, (size_t)C * 2, T, hipMemcpyDeviceToDevice, st), "copy v");
-                hip(launch_transpose_bf16(pr, vT, T, C, st), "transpose v");
+                hip(launch_transpose_bf16(pr, vT, T, C, st), "transpose v");      // moves 16-bit words: either format
             }
             // scores[q, key] = q . k  (A = keys, B = queries), probabilities, out[q, c] = sum_key P[q, key] V^T[c, key]
             gemm(kc, T, C, qc, T, nullptr, sc, T, TVC_EPI_F32, T);
-            if (live()) hip(sd_softmax_rows(sc, pr, T, T, 1.0f / sqrtf((float)C), st), "sd_softmax_rows");
+            if (live()) hip(sd_softmax_rows(sc, pr, T, T, 1.0f / sqrtf((float)C), st, f16), "sd_softmax_rows");
             gemm(vT, C, T, pr, T, nullptr, a.p + (int64_t)i * T * C, C, TVC_EPI_BF16, T);
         }
         Act o = linear(a, p + "proj_attn.weight", p + "proj_attn.bias", C);
-        if (live()) hip(sd_add_bf16(x.p, o.p, out.p, out.tok() * C, st), "sd_add");
+        if (live()) hip(sd_add_bf16(x.p, o.p, out.p, out.tok() * C, st, f16), "sd_add");
         off = mark;
         return out;
     }
@@ -406,9 +412,9 @@ void unet_forward(Run& R, const float* latents, int n, int H, int W, float times
     SdState* S = R.S;
     const tvc_sd_desc& d = S->d;
     const int nb = d.n_blocks, c0 = d.block_out_channels[0], Tdim = 4 * c0;
-    // text states -> bf16 rows
+    // text states -> 16-bit rows
     uint16_t* ctx16 = (uint16_t*)R.alloc_keep((size_t)pad_rows((int64_t)n * d.ctx) * d.cross_attention_dim * 2);
-    if (R.live() && R.keep_fill()) R.hip(sd_cast_silu(ctx, ctx16, (int64_t)n * d.ctx * d.cross_attention_dim, 0, R.st), "ctx cast");
+    if (R.live() && R.keep_fill()) R.hip(sd_cast_silu(ctx, ctx16, (int64_t)n * d.ctx * d.cross_attention_dim, 0, R.st, R.f16), "ctx cast");
     // time embedding MLP, then every resnet's time projection in one GEMM: tadd fp32 [n, temb_total]
     uint16_t* te = (uint16_t*)R.alloc((size_t)pad_rows(n) * c0 * 2);
     float* t1 = (float*)R.alloc((size_t)n * Tdim * 4);
@@ -418,11 +424,11 @@ void unet_forward(Run& R, const float* latents, int n, int H, int W, float times
     float* tadd = (float*)R.alloc((size_t)n * S->temb_total * 4);
     const void* w1 = R.W("time_embedding.linear_1.weight"); const float* b1 = (const float*)R.W("time_embedding.linear_1.bias");
     const void* w2 = R.W("time_embedding.linear_2.weight"); const float* b2 = (const float*)R.W("time_embedding.linear_2.bias");
-    if (R.live()) R.hip(sd_timestep_embed(te, n, c0, timestep, R.st), "timestep embed");
+    if (R.live()) R.hip(sd_timestep_embed(te, n, c0, timestep, R.st, R.f16), "timestep embed");
     R.gemm(w1, Tdim, c0, te, n, b1, t1, Tdim, TVC_EPI_F32, 1);
-    if (R.live()) R.hip(sd_cast_silu(t1, t1b, (int64_t)n * Tdim, 1, R.st), "silu");
+    if (R.live()) R.hip(sd_cast_silu(t1, t1b, (int64_t)n * Tdim, 1, R.st, R.f16), "silu");
     R.gemm(w2, Tdim, Tdim, t1b, n, b2, t2, Tdim, TVC_EPI_F32, 1);
-    if (R.live()) R.hip(sd_cast_silu(t2, t2b, (int64_t)n * Tdim, 1, R.st), "silu");       // resnets apply SiLU to temb first
+    if (R.live()) R.hip(sd_cast_silu(t2, t2b, (int64_t)n * Tdim, 1, R.st, R.f16), "silu");       // resnets apply SiLU to temb first
     R.gemm(S->temb_w, S->temb_total, Tdim, t2b, n, (const float*)S->temb_b, tadd, S->temb_total, TVC_EPI_F32, 1);
 
     // conv_in on the fp32 NCHW latents
@@ -430,7 +436,7 @@ void unet_forward(Run& R, const float* latents, int n, int H, int W, float times
     {
         const size_t mark = R.off;
         uint16_t* col = (uint16_t*)R.alloc((size_t)pad_rows((int64_t)n * H * W) * 64 * 2);
-        if (R.live()) R.hip(sd_im2col_in(latents, col, n, d.in_channels, H, W, 64, 1.0f, R.st), "im2col_in");
+        if (R.live()) R.hip(sd_im2col_in(latents, col, n, d.in_channels, H, W, 64, 1.0f, R.st, R.f16), "im2col_in");
         R.gemm(R.W("conv_in.weight"), c0, 64, col, (int64_t)n * H * W, (const float*)R.W("conv_in.bias"), x.p, c0, TVC_EPI_BF16,
                (int64_t)H * W);
         R.off = mark;
@@ -492,7 +498,7 @@ void vae_forward(Run& R, const float* latents, int n, int H, int W, float* image
     {
         const size_t mark = R.off;
         uint16_t* col = (uint16_t*)R.alloc((size_t)pad_rows((int64_t)n * H * W) * 64 * 2);
-        if (R.live()) R.hip(sd_im2col_in(z, col, n, L, H, W, 64, 1.0f, R.st), "im2col_in");
+        if (R.live()) R.hip(sd_im2col_in(z, col, n, L, H, W, 64, 1.0f, R.st, R.f16), "im2col_in");
         R.gemm(R.W("decoder.conv_in.weight"), top, 64, col, (int64_t)n * H * W, (const float*)R.W("decoder.conv_in.bias"), x.p, top,
                TVC_EPI_BF16, (int64_t)H * W);
         R.off = mark;
@@ -855,7 +861,7 @@ int tvc_sd_block(tvc_handle* h, int32_t kind, const char* prefix, const float* x
     const std::string p(prefix);
     return with_arena(h, (hipStream_t)stream, WS_SD0, [&](Run& R) {
         Act x = R.act(n, H, W, Cin);
-        if (R.live()) R.hip(sd_nchw_to_tokens(x_dev, x.p, n, Cin, H * W, R.st), "nchw_to_tokens");
+        if (R.live()) R.hip(sd_nchw_to_tokens(x_dev, x.p, n, Cin, H * W, R.st, R.f16), "nchw_to_tokens");
         Act y;
         if (kind == 0) {
             // the block's own time projection: tadd[n, Cout] = silu(temb) W^T + b, laid out as one slice of temb_total
@@ -864,14 +870,14 @@ int tvc_sd_block(tvc_handle* h, int32_t kind, const char* prefix, const float* x
                 const int Tdim = 4 * d.block_out_channels[0];
                 uint16_t* tb = (uint16_t*)R.alloc((size_t)pad_rows(n) * Tdim * 2);
                 float* tadd = (float*)R.alloc((size_t)n * S->temb_total * 4);
-                if (R.live()) R.hip(sd_cast_silu(temb_dev, tb, (int64_t)n * Tdim, 1, R.st), "silu");
+                if (R.live()) R.hip(sd_cast_silu(temb_dev, tb, (int64_t)n * Tdim, 1, R.st, R.f16), "silu");
                 R.gemm(S->temb_w, S->temb_total, Tdim, tb, n, (const float*)S->temb_b, tadd, S->temb_total, TVC_EPI_F32, 1);
                 tadd_all = tadd;
             }
             y = R.resnet(x, p, Cout, tadd_all, vae ? 1e-6f : d.norm_eps);
         } else if (kind == 1) {
             uint16_t* ctx16 = (uint16_t*)R.alloc((size_t)pad_rows((int64_t)n * d.ctx) * d.cross_attention_dim * 2);
-            if (R.live()) R.hip(sd_cast_silu(ctx_dev, ctx16, (int64_t)n * d.ctx * d.cross_attention_dim, 0, R.st), "ctx cast");
+            if (R.live()) R.hip(sd_cast_silu(ctx_dev, ctx16, (int64_t)n * d.ctx * d.cross_attention_dim, 0, R.st, R.f16), "ctx cast");
             y = R.transformer(x, p, ctx16, block_heads(d, p));
         } else if (kind == 2) {
             y = R.vae_attention(x, p);
@@ -885,7 +891,7 @@ int tvc_sd_block(tvc_handle* h, int32_t kind, const char* prefix, const float* x
         } else {
             y = kind == 5 ? R.upsample_conv(x, p, Cout) : R.conv3x3(x, p, Cout, 2, 0);
         }
-        if (R.live()) R.hip(sd_tokens_bf16_to_nchw(y.p, out_dev, y.n, y.C, y.H * y.W, R.st), "tokens_to_nchw");
+        if (R.live()) R.hip(sd_tokens_bf16_to_nchw(y.p, out_dev, y.n, y.C, y.H * y.W, R.st, R.f16), "tokens_to_nchw");
     });
 }
 
@@ -910,7 +916,7 @@ int tvc_sd_attention(tvc_handle* h, const uint16_t* q_dev, const uint16_t* k_dev
     if (!q_dev || !k_dev || !v_dev || !out_dev || n < 1 || heads < 1 || Tq < 1 || Tk < 1 || dh < 8 || dh > 160 || dh % 8)
         return fail(h, TVC_E_INVALID, "tvc_sd_attention: need head_dim % 8 == 0 and <= 160, non-NULL buffers");
     const int64_t ld = (int64_t)heads * dh;
-    HIP_TRY(sd_flash_attention(q_dev, ld, k_dev, ld, v_dev, ld, out_dev, ld, n, heads, Tq, Tk, dh, (hipStream_t)stream));
+    HIP_TRY(sd_flash_attention(q_dev, ld, k_dev, ld, v_dev, ld, out_dev, ld, n, heads, Tq, Tk, dh, (hipStream_t)stream, h->sd_precision == 1));
     return TVC_OK;
 }
 
@@ -926,7 +932,8 @@ int tvc_sd_attention_ex(tvc_handle* h, const uint16_t* q_dev, int64_t ldq, const
         ((uintptr_t)q_dev & 15) || ((uintptr_t)k_dev & 15) || ((uintptr_t)v_dev & 15) || ((uintptr_t)out_dev & 7))
         return fail(h, TVC_E_INVALID, "tvc_sd_attention_ex: need ldq / ldk / ldv % 8 == 0, ldo % 4 == 0, every stride >= heads * dh, "
                                       "q / k / v 16-byte and out 8-byte aligned");
-    HIP_TRY(sd_flash_attention(q_dev, ldq, k_dev, ldk, v_dev, ldv, out_dev, ldo, n, heads, Tq, Tk, dh, (hipStream_t)stream));
+    HIP_TRY(sd_flash_attention(q_dev, ldq, k_dev, ldk, v_dev, ldv, out_dev, ldo, n, heads, Tq, Tk, dh, (hipStream_t)stream,
+                               h->sd_precision == 1));
     return TVC_OK;
 }
 

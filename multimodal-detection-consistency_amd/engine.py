@@ -107,6 +107,7 @@ class TVCEngine:
         self._has_f32 = False
         self._has_f16 = False
         self.precision = "bf16"
+        self.sd_precision = "bf16"            # TVC_OPT_SD_PRECISION (set_sd_precision): the latent-diffusion model's 16-bit format
         if precision != "bf16":
             self.set_precision(precision)
 
@@ -728,6 +729,19 @@ class TVCEngine:
     def set_option(self, option: int, value: int) -> None:
         """``_lib.TVC_OPT_*`` (e.g. text packing on / off)."""
         self._check(self.lib.tvc_set_option(self.handle, option, value))
+        if option == _lib.TVC_OPT_SD_PRECISION:
+            self.sd_precision = "fp16" if value else "bf16"
+
+    SD_PRECISIONS = {"bf16": 0, "fp16": 1}
+
+    def set_sd_precision(self, precision: str) -> None:
+        """The 16-bit format of the latent-diffusion model on this handle (``TVC_OPT_SD_PRECISION``): ``"bf16"`` (default) or
+        ``"fp16"`` -- the tensors given to ``tvc_sd_load`` and the operands of ``tvc_sd_attention`` are then IEEE fp16.
+        Independent of the towers' ``set_precision``.  Changing it while a model is loaded raises ``TVCError`` (TVC_E_STATE)."""
+        if precision not in self.SD_PRECISIONS:
+            raise ValueError(f"SD precision must be one of {sorted(self.SD_PRECISIONS)} (got {precision!r})")
+        with self._lock:
+            self.set_option(_lib.TVC_OPT_SD_PRECISION, self.SD_PRECISIONS[precision])
 
     def workspace_bytes(self) -> int:
         return int(self.lib.tvc_workspace_bytes(self.handle))

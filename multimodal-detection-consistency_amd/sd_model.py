@@ -45,15 +45,22 @@ def _conv3x3_rows(w: torch.Tensor, pad_to: int = 0) -> torch.Tensor:
     return r
 
 
+SD_DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16}      # precision name -> the 16-bit dtype of TVC_OPT_SD_PRECISION 0 / 1
+
+
 def prepare_sd_tensors(unet_w: Optional[Dict[str, torch.Tensor]], vae_w: Optional[Dict[str, torch.Tensor]],
-                       device: torch.device) -> Dict[str, torch.Tensor]:
-    """diffusers state dicts -> the device tensors ``tvc_sd_load`` documents (include/tvc.h): GEMM operands bf16 with
-    3x3 kernels flattened tap-major, q/k/v fused, everything else fp32."""
+                       device: torch.device, dtype: torch.dtype = torch.bfloat16) -> Dict[str, torch.Tensor]:
+    """diffusers state dicts -> the device tensors ``tvc_sd_load`` documents (include/tvc.h): GEMM operands in the 16-bit
+    ``dtype`` (bf16, or float16 for ``TVC_OPT_SD_PRECISION = 1``) with 3x3 kernels flattened tap-major, q/k/v fused,
+    everything else fp32."""
+    if dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"prepare_sd_tensors: dtype must be torch.bfloat16 or torch.float16 (got {dtype})")
     out: Dict[str, torch.Tensor] = {}
+    w16 = dtype
 
     def put(name: str, t: torch.Tensor, dtype) -> None:
         t = t.detach().to(dtype=dtype)
-        if dtype == torch.bfloat16 and t.dim() == 2 and t.shape[0] % 256:
+        if dtype == w16 and t.dim() == 2 and t.shape[0] % 256:
             # tvc_sd_load's contract: GEMM weights are readable up to the next multiple of 256 rows (zero rows), so the
             # fast GEMM form stages whole 256-row tiles even where the width (320, 640, 4 ...) is not a multiple of 256
             t = torch.cat([t, t.new_zeros((256 - t.shape[0] % 256, t.shape[1]))])
@@ -74,23 +81,23 @@ def prepare_sd_tensors(unet_w: Optional[Dict[str, torch.Tensor]], vae_w: Optiona
             elif name == "post_quant_conv.weight":
                 put(name, t.reshape(t.shape[0], t.shape[1]), torch.float32)
             elif t.dim() == 4 and t.shape[-1] == 3:
-                put(name, _conv3x3_rows(t.float(), 64 if t.shape[1] * 9 < 64 else 0), torch.bfloat16)
+                put(name, _conv3x3_rows(t.float(), 64 if t.shape[1] * 9 < 64 else 0), w16)
             elif t.dim() == 4:
-                put(name, t.reshape(t.shape[0], t.shape[1]), torch.bfloat16)
+                put(name, t.reshape(t.shape[0], t.shape[1]), w16)
             elif name.endswith(("attn1.to_q.weight", "attn1.to_k.weight", "attn1.to_v.weight")):
                 p = name.rsplit(".", 2)[0] + "."
-                put(p + "to_qkv.weight", torch.cat([w[p + "to_q.weight"], w[p + "to_k.weight"], w[p + "to_v.weight"]]), torch.bfloat16)
+                put(p + "to_qkv.weight", torch.cat([w[p + "to_q.weight"], w[p + "to_k.weight"], w[p + "to_v.weight"]]), w16)
                 fused.update({p + "to_q.weight", p + "to_k.weight", p + "to_v.weight"})
             elif name.endswith(("attn2.to_k.weight", "attn2.to_v.weight")):
                 p = name.rsplit(".", 2)[0] + "."
-                put(p + "to_kv.weight", torch.cat([w[p + "to_k.weight"], w[p + "to_v.weight"]]), torch.bfloat16)
+                put(p + "to_kv.weight", torch.cat([w[p + "to_k.weight"], w[p + "to_v.weight"]]), w16)
                 fused.update({p + "to_k.weight", p + "to_v.weight"})
             elif name.endswith((".query.weight", ".key.weight", ".value.weight")):
                 p = name.rsplit(".", 2)[0] + "."
-                put(p + "to_qkv.weight", torch.cat([w[p + "query.weight"], w[p + "key.weight"], w[p + "value.weight"]]), torch.bfloat16)
+                put(p + "to_qkv.weight", torch.cat([w[p + "query.weight"], w[p + "key.weight"], w[p + "value.weight"]]), w16)
                 fused.update({p + "query.weight", p + "key.weight", p + "value.weight"})
             else:
-                put(name, t, torch.bfloat16)
+                put(name, t, w16)
     return out
 
 
@@ -119,9 +126,17 @@ def sd_desc(a: SDArch) -> "_lib.SDDesc":
 class SDKernels:
     """The ``tvc_sd_*`` entry points on one engine (handle)."""
 
-    def __init__(self, engine: TVCEngine, arch: SDArch, unet_w: Optional[Dict] = None, vae_w: Optional[Dict] = None):
-        self.engine, self.arch = engine, arch
-        self.tensors = prepare_sd_tensors(unet_w, vae_w, engine.device)
+    def __init__(self, engine: TVCEngine, arch: SDArch, unet_w: Optional[Dict] = None, vae_w: Optional[Dict] = None,
+                 precision: str = "bf16"):
+        """``precision``: ``"bf16"`` (default) or ``"fp16"`` -- the model's 16-bit format (``TVC_OPT_SD_PRECISION``, set on
+        the engine before the load; the weights are prepared in the matching dtype).  fp16 is the dtype the reference runs
+        Stable Diffusion in; its range ends at 65504 (beyond: +-inf, never clamped)."""
+        if precision not in SD_DTYPES:
+            raise ValueError(f"SDKernels: precision must be 'bf16' or 'fp16' (got {precision!r})")
+        self.engine, self.arch, self.precision = engine, arch, precision
+        with torch.cuda.device(engine.device):
+            engine.set_sd_precision(precision)      # TVC_E_STATE if the handle holds a model of the other format
+        self.tensors = prepare_sd_tensors(unet_w, vae_w, engine.device, SD_DTYPES[precision])
         names = sorted(self.tensors)
         arr = (_lib.NamedTensor * len(names))()
         self._names = [n.encode() for n in names]
@@ -187,21 +202,27 @@ class SDKernels:
 
     def attention(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, n: int, heads: int, ld=None,
                   dh: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """q [n * Tq, heads * dh], k / v [n * Tk, heads * dh] bf16 -> [n * Tq, heads * dh] bf16."""
+        """q [n * Tq, heads * dh], k / v [n * Tk, heads * dh] -> [n * Tq, heads * dh], all in this model's 16-bit dtype."""
         return streaming_attention(self.engine, q, k, v, n, heads, ld=ld, dh=dh, out=out)
 
 
 def streaming_attention(engine: TVCEngine, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, n: int, heads: int, ld=None,
                         dh: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The UNet's streaming attention kernel on its own (needs no loaded model): q [n * Tq, heads * dh], k / v
-    [n * Tk, heads * dh] bf16 -> [n * Tq, heads * dh] bf16.
+    [n * Tk, heads * dh] -> [n * Tq, heads * dh], all in the engine's SD format: ``torch.bfloat16``, or ``torch.float16``
+    after ``engine.set_sd_precision("fp16")``.  Operands of the other 16-bit dtype raise ``ValueError`` before any launch
+    (their bits would be read as the wrong format); other dtypes are converted.
 
     ``ld = (ldq, ldk, ldv, ldo)``: one row stride (in elements) per operand, as the model's fused projections pass them
     (``tvc_sd_attention_ex``).  q / k / v / out are then [rows, ld*] tensors whose first ``heads * dh`` columns are the
     heads, ``dh`` must be given, and ``out`` (optional, [n * Tq, ldo]) is written in place -- columns beyond
     ``heads * dh`` are neither read nor written."""
     e = engine
-    q, k, v = (t.to(e.device, torch.bfloat16).contiguous() for t in (q, k, v))
+    dt = SD_DTYPES[e.sd_precision]
+    other = torch.float16 if dt == torch.bfloat16 else torch.bfloat16
+    if any(t is not None and t.dtype == other for t in (q, k, v, out)):
+        raise ValueError(f"streaming_attention: this engine's SD precision is {e.sd_precision!r}: pass {dt} operands, not {other}")
+    q, k, v = (t.to(e.device, dt).contiguous() for t in (q, k, v))
     if ld is None:
         dh = q.shape[1] // heads
         out = torch.empty_like(q)
@@ -213,9 +234,9 @@ def streaming_attention(engine: TVCEngine, q: torch.Tensor, k: torch.Tensor, v: 
     if dh is None or (q.shape[1], k.shape[1], v.shape[1]) != (ldq, ldk, ldv) or k.shape[0] != v.shape[0]:
         raise ValueError("streaming_attention: with ld, pass dh and q / k / v as [rows, ldq / ldk / ldv] tensors")
     if out is None:
-        out = torch.zeros((q.shape[0], ldo), dtype=torch.bfloat16, device=e.device)
-    elif out.shape != (q.shape[0], ldo) or out.dtype != torch.bfloat16 or not out.is_contiguous() or out.device != q.device:
-        raise ValueError("streaming_attention: out must be a contiguous bf16 [n * Tq, ldo] tensor on the engine's device")
+        out = torch.zeros((q.shape[0], ldo), dtype=dt, device=e.device)
+    elif out.shape != (q.shape[0], ldo) or out.dtype != dt or not out.is_contiguous() or out.device != q.device:
+        raise ValueError(f"streaming_attention: out must be a contiguous {dt} [n * Tq, ldo] tensor on the engine's device")
     with e._lock, torch.cuda.device(e.device):
         e._check(e.lib.tvc_sd_attention_ex(e.handle, _ptr(q), ldq, _ptr(k), ldk, _ptr(v), ldv, _ptr(out), ldo, n, heads,
                                            q.shape[0] // n, k.shape[0] // n, dh, _stream()))
@@ -233,6 +254,7 @@ class SDModelConfig:
     text_model: Optional[str] = None                        # conditioning tower; None = the architecture's (SDArch.text_arch:
                                                             # CLIP ViT-L/14 for SD 1.x, "SD2-text" = OpenCLIP ViT-H/14 for SD 2.x)
     tokenizer_dir: Optional[str] = None
+    precision: str = "bf16"                                 # UNet / VAE 16-bit format: "bf16", or "fp16" (the reference's torch_dtype)
 
 
 class StableDiffusionModel:
@@ -281,7 +303,7 @@ class StableDiffusionModel:
                 logger.warning("latent-diffusion model '%s': seeded RANDOM UNet / VAE weights (random_init=True) -- its images "
                                "are noise; for benchmarks and parity tests only", self.config.model_name)
                 weights = make_sd_weights(self.arch, self.config.seed, device=str(self.device))
-        self.kernels = SDKernels(self.text_engine, self.arch, weights[0], weights[1])
+        self.kernels = SDKernels(self.text_engine, self.arch, weights[0], weights[1], precision=self.config.precision)
         self.generation_count = 0
 
     # ---- conditioning --------------------------------------------------------------------------------------

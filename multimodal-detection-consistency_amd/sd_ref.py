@@ -130,7 +130,8 @@ class SDReferenceConfig:
     """:217-255 (same names and defaults)."""
     sd_model: str = "runwayml/stable-diffusion-v1-5"
     device: str = "cuda"
-    torch_dtype: str = "float16"
+    torch_dtype: str = "float16"          # compatibility field (the reference's name and default): selects NOTHING here -- the
+                                         # default generator runs bf16; `precision="fp16"` below is the reference's dtype
     num_images_per_prompt: int = 3
     num_inference_steps: int = 50
     guidance_scale: float = 7.5
@@ -153,6 +154,9 @@ class SDReferenceConfig:
     unet_weights: Optional[str] = None
     vae_weights: Optional[str] = None
     random_init: bool = False
+    # not in the reference: the in-tree model's 16-bit format, "bf16" (default) or "fp16" (IEEE fp16 weights, activations and
+    # MFMA: what the reference's torch_dtype "float16" means; SDModelConfig.precision)
+    precision: str = "bf16"
 
     def __post_init__(self):
         if self.variant_methods is None:
@@ -174,7 +178,8 @@ class SDReferenceGenerator:
                 sd_model = StableDiffusionModel(SDModelConfig(model_name=self.config.sd_model, device=self.config.device,
                                                               unet_weights=self.config.unet_weights,
                                                               vae_weights=self.config.vae_weights,
-                                                              random_init=self.config.random_init), clip_model=clip_model)
+                                                              random_init=self.config.random_init,
+                                                              precision=self.config.precision), clip_model=clip_model)
             except Exception as e:                                 # noqa: BLE001
                 logger.error("could not build the latent-diffusion model: %s", e)
                 sd_model = None
