@@ -577,6 +577,53 @@ int tvc_sd_attention_ex(tvc_handle* h, const uint16_t* q_dev, int64_t ldq, const
                         const uint16_t* v_dev, int64_t ldv, uint16_t* out_dev, int64_t ldo, int32_t n, int32_t heads,
                         int32_t Tq, int32_t Tk, int32_t dh, void* stream);
 
+/* One row kernel of the generator on the caller's device buffers (parity tests): everything between its GEMMs.  Each op is
+ * exactly ONE kernel launcher, with no copy and no relayout in between; no model needs to be loaded; the 16-bit format
+ * ("16" below) is the handle's SD format, as for tvc_sd_attention.  Layouts: "tokens" = [n * H * W, C] rows (NHWC, dense);
+ * "padded" = every image an (H + 2) x (W + 2) grid of rows, pixel (y, x) at row (y + 1) * (W + 2) + (x + 1), whose border
+ * rows a convolution reads as its zero padding (a padded OUTPUT has its borders written as zeros, the borders of a padded
+ * INPUT are never read).  Slots of tvc_sd_op_args per op (unused slots are ignored; flags are 0 / 1):
+ *   GROUPNORM        in0 x 16, in1 tadd fp32 [n, ld_t] or NULL (x + tadd[img, c] is what is normalised), in2 gamma, in3 beta
+ *                    fp32 [C]; out0 y 16; i = n, H, W, C, groups, silu, in_pad, out_pad, ld_t; f0 = eps.  C % 8 == 0,
+ *                    C <= 4096, groups <= 32, C % groups == 0.  Its statistics scratch is the handle's.
+ *   LAYERNORM        in0 x 16 [rows, C], in1 g, in2 b fp32 [C], in3 add 16 or NULL; out0 y, out1 sum_out 16 (given exactly
+ *                    when add is: sum_out = x + add, y = LayerNorm(sum_out)); i = rows (0 is allowed: nothing is written),
+ *                    C; f0 = eps.  C % 8 == 0, C <= 1536.
+ *   GEGLU            in0 16 [rows, 2 * Ch] (value | gate); out0 16 [rows, Ch] = value * gelu_erf(gate); i = rows, Ch (% 8).
+ *   ADD              in0, in1 16 [n]; out0 16 = in0 + in1; i = n (% 8).
+ *   ADD_PADDED       in0 16 tokens, in1 16 padded; out0 16 tokens; i = n, H, W, C (% 8).
+ *   RELAYOUT         in0 16; out0 16; i = n, H, W (the OUTPUT's extent), C (% 8), in_pad, out_pad, up (the input is
+ *                    (H / 2) x (W / 2), nearest-2x upsampled; H, W even).
+ *   IM2COL3X3        in0 16 tokens [n, Hi, Wi, C]; out0 16 [n * Ho * Wo, 9 * C], column (ky * 3 + kx) * C + c, padding 1,
+ *                    Ho = (Hs - 1) / stride + 1 with Hs = Hi (2 * Hi with up); i = n, Hi, Wi, C (% 8), stride (1, 2), up (stride 1).
+ *   IM2COL_IN        in0 fp32 NCHW [n, Cin, H, W]; out0 16 [n * H * W, Kp], column tap * Cin + ci of in0 * scale, zeros from
+ *                    column 9 * Cin on; i = n, Cin, H, W, Kp (>= 9 * Cin); f0 = scale.
+ *   CONCAT           in0 16 [tokens, Ca], in1 16 [tokens, Cb]; out0 16 [tokens, Ca + Cb]; i = Ca, Cb (% 8), tokens.
+ *   CAST_SILU        in0 fp32 [n]; out0 16 [n]; i = n, silu.
+ *   TOKENS_TO_NCHW   in0 fp32 rows of pitch ld (first C columns; dense, or padded with in_pad); out0 fp32 NCHW
+ *                    = in0 * mul + add, clamped to [0, 1] with clamp; i = n, C, H, W, ld, clamp, in_pad; f0 = mul, f1 = add.
+ *   POINTWISE_SMALL  in0 fp32 NCHW [n, C, HW], in1 w fp32 [C, C], in2 bias fp32 [C]; out0 fp32 NCHW
+ *                    = bias[c] + sum_ci w[c, ci] * (in0[n, ci, p] * in_scale); i = n, C (<= 8), HW; f0 = in_scale.
+ *   CFG              in0 fp32 [2 * n] (unconditional | conditional); out0 fp32 [n] = eu + g * (ec - eu); i = n; f0 = g.
+ *   LINCOMB          in0 sample fp32 [n], in1 .. in4 e0 .. e3 fp32 [n] (e1 .. e3 may be NULL); out0 fp32 [n] (may be in0)
+ *                    = cs * sample - ce * (c0 e0 + c1 e1 + c2 e2 + c3 e3); i = n; f = cs, ce, c0, c1, c2, c3.
+ *   SOFTMAX_ROWS     in0 fp32 [rows, T]; out0 16 [rows, T] = softmax(in0 * scale) per row; i = rows, T; f0 = scale (> 0).
+ *   NCHW_TO_TOKENS   in0 fp32 NCHW [n, C, HW]; out0 16 tokens; i = n, C, HW.
+ *   TOKENS16_TO_NCHW in0 16 tokens; out0 fp32 NCHW; i = n, C, HW.
+ *   TIMESTEP_EMBED   out0 16 [n, dim] = [cos | sin](t * 10000^(-j / (dim / 2))), every row the same; i = n, dim (even); f0 = t.
+ *   TRANSPOSE        in0 16 [R, C]; out0 16 [C, R]; i = R, C.
+ * A NULL args or required pointer, a pointer the kernel's vector accesses need aligned (16 bytes for 16-bit tensors read or
+ * written in pieces of 8, 4 for fp32) and is not, an extent that is not positive, extents whose product leaves int32, an
+ * unknown op: TVC_E_INVALID; an argument the launcher rejects: TVC_E_HIP.  Either way
+ * nothing is launched. */
+enum { TVC_SD_OP_GROUPNORM = 0, TVC_SD_OP_LAYERNORM = 1, TVC_SD_OP_GEGLU = 2, TVC_SD_OP_ADD = 3, TVC_SD_OP_ADD_PADDED = 4,
+       TVC_SD_OP_RELAYOUT = 5, TVC_SD_OP_IM2COL3X3 = 6, TVC_SD_OP_IM2COL_IN = 7, TVC_SD_OP_CONCAT = 8, TVC_SD_OP_CAST_SILU = 9,
+       TVC_SD_OP_TOKENS_TO_NCHW = 10, TVC_SD_OP_POINTWISE_SMALL = 11, TVC_SD_OP_CFG = 12, TVC_SD_OP_LINCOMB = 13,
+       TVC_SD_OP_SOFTMAX_ROWS = 14, TVC_SD_OP_NCHW_TO_TOKENS = 15, TVC_SD_OP_TOKENS16_TO_NCHW = 16,
+       TVC_SD_OP_TIMESTEP_EMBED = 17, TVC_SD_OP_TRANSPOSE = 18, TVC_SD_OP_COUNT = 19 };
+typedef struct { const void* in[6]; void* out[2]; int64_t i[12]; float f[12]; } tvc_sd_op_args;
+int tvc_sd_op(tvc_handle* h, int32_t op, const tvc_sd_op_args* a, void* stream);
+
 /* Image preprocessing on the device: images fp32 [n, 3, H, W] with values in [0, 1] -> out fp32 [n, 3, S, S]:
  * antialiased resize of the short side to S (filter 0 = bilinear: torchvision Resize as in
  * experiments/defenses/generative_ref.py:55-59 -- which resizes BOTH sides to S; 1 = bicubic: the CLIP preprocess of

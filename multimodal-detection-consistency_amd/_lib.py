@@ -87,6 +87,18 @@ class NamedTensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("ptr", C.c_void_p)]
 
 
+class SDOpArgs(C.Structure):
+    """``tvc_sd_op_args`` (include/tvc.h)."""
+    _fields_ = [("inp", C.c_void_p * 6), ("out", C.c_void_p * 2), ("i", C.c_int64 * 12), ("f", C.c_float * 12)]
+
+
+# TVC_SD_OP_* (include/tvc.h): the row kernels of the latent-diffusion generator behind tvc_sd_op
+SD_OPS = {name: code for code, name in enumerate((
+    "groupnorm", "layernorm", "geglu", "add", "add_padded", "relayout", "im2col3x3", "im2col_in", "concat", "cast_silu",
+    "tokens_to_nchw", "pointwise_small", "cfg", "lincomb", "softmax_rows", "nchw_to_tokens", "tokens16_to_nchw",
+    "timestep_embed", "transpose"))}
+
+
 # name -> (restype, argtypes); must list every symbol include/tvc.h declares
 SIGNATURES = {
     "tvc_abi_version": (C.c_uint32, []),
@@ -149,6 +161,7 @@ SIGNATURES = {
     "tvc_sd_attention": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "tvc_sd_attention_ex": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, _P]),
+    "tvc_sd_op": (C.c_int, [_P, C.c_int32, C.POINTER(SDOpArgs), _P]),
 }
 
 _lib = None

@@ -243,6 +243,26 @@ def streaming_attention(engine: TVCEngine, q: torch.Tensor, k: torch.Tensor, v: 
     return out
 
 
+def sd_op(engine: TVCEngine, op: str, ins: Sequence[Optional[torch.Tensor]] = (), outs: Sequence[Optional[torch.Tensor]] = (),
+          i: Sequence[int] = (), f: Sequence[float] = ()) -> None:
+    """One row kernel of the generator on the caller's tensors (``tvc_sd_op``; needs no loaded model).  ``op`` is a key of
+    ``_lib.SD_OPS``; ``ins`` / ``outs`` / ``i`` / ``f`` fill the slots include/tvc.h lists for it (``None`` = NULL).
+    Nothing is converted, copied or checked here: the tensors' data pointers are passed as they are (16-bit ones in the
+    engine's SD format), a view inside a larger buffer included.  Raises ``TVCError`` where the C-ABI refuses the call."""
+    e = engine
+    a = _lib.SDOpArgs()
+    for k, t in enumerate(ins):
+        a.inp[k] = None if t is None else t.data_ptr()
+    for k, t in enumerate(outs):
+        a.out[k] = None if t is None else t.data_ptr()
+    for k, v in enumerate(i):
+        a.i[k] = int(v)
+    for k, v in enumerate(f):
+        a.f[k] = float(v)
+    with e._lock, torch.cuda.device(e.device):
+        e._check(e.lib.tvc_sd_op(e.handle, _lib.SD_OPS[op], C.byref(a), _stream()))
+
+
 @dataclass
 class SDModelConfig:
     model_name: str = "runwayml/stable-diffusion-v1-5"      # src/sd_ref.py:220

@@ -236,6 +236,40 @@ int main(int argc, char** argv) {
     CHECK(tvc_sd_block(h, 0, "no_such_block.", x, 2, 64, 16, 16, temb, nullptr, 64, 0, y, nullptr) != TVC_OK);
     CHECK(tvc_sd_block(h, 1, "down_blocks.0.attentions.0.", x, 2, 64, 16, 16, nullptr, nullptr, 64, 0, y, nullptr) == TVC_E_INVALID);
     CHECK(tvc_sd_block(h, 7, "x.", x, 2, 64, 16, 16, nullptr, nullptr, 64, 0, y, nullptr) == TVC_E_INVALID);
+    // tvc_sd_op: every op's slot decoding with valid arguments (the launchers are stubs), then what the entry itself refuses
+    {
+        uint16_t* a16 = (uint16_t*)buf((size_t)1 << 16, 2); uint16_t* o16 = (uint16_t*)buf((size_t)1 << 16, 2);
+        float* a32 = (float*)buf((size_t)1 << 14, 4); float* o32 = (float*)buf((size_t)1 << 14, 4);
+        for (int op = 0; op < TVC_SD_OP_COUNT; ++op) {
+            tvc_sd_op_args s{};
+            const bool in32 = op == TVC_SD_OP_IM2COL_IN || (op >= TVC_SD_OP_CAST_SILU && op <= TVC_SD_OP_NCHW_TO_TOKENS);
+            s.in[0] = in32 ? (const void*)a32 : (const void*)a16;
+            s.in[1] = op == TVC_SD_OP_LAYERNORM || op == TVC_SD_OP_POINTWISE_SMALL || op == TVC_SD_OP_LINCOMB ? (const void*)a32 : (const void*)a16;
+            if (op == TVC_SD_OP_GROUPNORM) s.in[1] = nullptr;
+            s.in[2] = a32; s.in[3] = op == TVC_SD_OP_LAYERNORM ? nullptr : (const void*)a32;
+            const bool out32 = op == TVC_SD_OP_TOKENS_TO_NCHW || op == TVC_SD_OP_POINTWISE_SMALL || op == TVC_SD_OP_CFG ||
+                               op == TVC_SD_OP_LINCOMB || op == TVC_SD_OP_TOKENS16_TO_NCHW;
+            s.out[0] = out32 ? (void*)o32 : (void*)o16;
+            for (int k = 0; k < 4; ++k) s.i[k] = 8;
+            if (op == TVC_SD_OP_GROUPNORM) s.i[4] = 4;                       // groups
+            if (op == TVC_SD_OP_IM2COL3X3) s.i[4] = 1;                       // stride
+            if (op == TVC_SD_OP_IM2COL_IN) s.i[4] = 72;                      // Kp
+            if (op == TVC_SD_OP_TOKENS_TO_NCHW) s.i[4] = 8;                  // ld
+            if (op == TVC_SD_OP_LAYERNORM || op == TVC_SD_OP_GEGLU || op == TVC_SD_OP_CAST_SILU) s.i[1] = op == TVC_SD_OP_CAST_SILU ? 1 : 8;
+            s.f[0] = 1.f;
+            OK(tvc_sd_op(h, op, &s, nullptr));
+            s.out[0] = nullptr;
+            CHECK(tvc_sd_op(h, op, &s, nullptr) == TVC_E_INVALID);           // NULL output
+            s.out[0] = out32 ? (void*)o32 : (void*)o16;
+            s.i[0] = 0;
+            if (op != TVC_SD_OP_LAYERNORM) CHECK(tvc_sd_op(h, op, &s, nullptr) == TVC_E_INVALID);      // an extent of 0
+            s.i[0] = (int64_t)1 << 40;
+            CHECK(tvc_sd_op(h, op, &s, nullptr) == TVC_E_INVALID);           // an extent beyond int32
+        }
+        tvc_sd_op_args s{};
+        CHECK(tvc_sd_op(h, TVC_SD_OP_COUNT, &s, nullptr) == TVC_E_INVALID && tvc_sd_op(h, -1, &s, nullptr) == TVC_E_INVALID);
+        CHECK(tvc_sd_op(h, 0, nullptr, nullptr) == TVC_E_INVALID && tvc_sd_op(nullptr, 0, &s, nullptr) == TVC_E_INVALID);
+    }
     // an allocation the "device" cannot serve is reported as TVC_E_NOMEM, and the handle stays usable
     hip_stub_limit() = (size_t)64 << 20;
     CHECK(tvc_sd_unet(h, lat, 6, 64, 64, 1.f, ctx, eps, nullptr) == TVC_E_NOMEM || tvc_sd_unet(h, lat, 6, 64, 64, 1.f, ctx, eps, nullptr) == TVC_E_INVALID ||
