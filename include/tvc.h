@@ -624,6 +624,80 @@ enum { TVC_SD_OP_GROUPNORM = 0, TVC_SD_OP_LAYERNORM = 1, TVC_SD_OP_GEGLU = 2, TV
 typedef struct { const void* in[6]; void* out[2]; int64_t i[12]; float f[12]; } tvc_sd_op_args;
 int tvc_sd_op(tvc_handle* h, int32_t op, const tvc_sd_op_args* a, void* stream);
 
+/* One row kernel of the CLIP towers on the caller's device buffers (parity tests): the LayerNorm family forward and
+ * backward, the stem's gathers, the activations, the split-mode plane kernels, the row gathers and the text length / embedding
+ * kernels.  Each op is exactly ONE kernel launcher, with no copy in between; no weights are needed and no handle state is
+ * read.  "16" = a 16-bit tensor: bf16, or IEEE fp16 where the op has an f16 flag and it is 1.  Strides are in elements.
+ * Slots of tvc_tower_op_args per op (unused slots are ignored; flags are 0 / 1; "or NULL" marks the optional pointers):
+ *   LAYERNORM        in0 x fp32 (row r at in0 + src(r) * x_row_stride, src(r) = row_idx[r], or r without row_idx; WRITTEN
+ *                    with write_x and a delta), in1 row_idx int32 [rows] or NULL, in2 delta, in3 delta2 16 or NULL (row r at
+ *                    src(r) * x_row_stride -- x's layout --, or at r * d with delta_compact), in4 g, in5 b fp32 [d];
+ *                    out0 y 16 [rows, d] or NULL, out1 y32 fp32 [rows, d] or NULL (one of the two is required; y is the
+ *                    rounding of y32), out2 xsum fp32 [rows, d] or NULL = (x + delta) + delta2 in fp32, which is also what
+ *                    write_x stores to x and what is normalised; i = rows, d, x_row_stride (>= d, % 4), write_x,
+ *                    delta_compact, f16.  d % 4 == 0, d <= 1024.
+ *   LAYERNORM_BWD    in0 x fp32 (row r at r * x_row_stride), in1 delta bf16 or NULL (row r at r * x_row_stride: x's layout),
+ *                    in2 dy [rows, d] dense, bf16 or fp32 with dy_fp32, in3 gamma fp32 [d], in4 dres fp32 or NULL (row r at
+ *                    r * out_row_stride; may be out0: in place); out0 dx fp32, out1 dx16 bf16 or NULL = bf16(dx) (rows at
+ *                    r * out_row_stride both; elements between the rows are not written);
+ *                    dx = rstd * (g - mean(g) - xhat * mean(g * xhat)) + dres with g = dy * gamma and xhat of x + delta;
+ *                    i = rows, d, x_row_stride, out_row_stride (>= d, % 4), dy_fp32.  d % 4 == 0, d <= 1024.
+ *   LNPRE_BWD        in0 patch_out fp32 [B * (T - 1), d], in1 pos fp32 [T, d], in2 gamma fp32 [d], in3 dy fp32 [B * T, d] (its
+ *                    class rows t = 0 are not read); out0 bf16 [B * (T - 1), d] = LayerNorm backward at patch_out + pos[t];
+ *                    i = B, T (>= 2), d.
+ *   ASSEMBLE_LNPRE   in0 patch_out fp32 [B * (T - 1), d] (NULL allowed with T = 1), in1 cls fp32 [d], in2 pos fp32 [T, d], in3 g,
+ *                    in4 b fp32 [d]; out0 x fp32 [B * T, d] = LayerNorm((t == 0 ? cls : patch_out[b, t - 1]) + pos[t]); i = B, T, d.
+ *   IM2COL           in0 pix fp32 [B, 3, image, image]; out0 16 [B * P, Kp], P = (image / patch)^2, column (c, ky, kx), zeros
+ *                    from column 3 * patch^2 on; i = B, image, patch, Kp (>= 3 * patch^2, % 8), f16.  in0 16-byte aligned
+ *                    when image % 4 == 0.
+ *   IM2COL_F32       in0 pix fp32; out0 fp32 [B * P, 3 * patch^2]; i = B, image, patch.
+ *   COL2IM           in0 dcols fp32 [B * P, Kp] (columns from 3 * patch^2 on are not read); out0 dpix fp32 [B, 3, S, S];
+ *                    i = B, S, patch, Kp.
+ *   GELU_FWD         in0 u bf16 [n]; out0 bf16 [n] = u * sigmoid(1.702 u) (fast exponential and reciprocal); i = n (% 8).
+ *   GELU_BWD         in0 u bf16 [n]; out0 dm bf16 [n], in place: dm *= s + 1.702 u s (1 - s), s = sigmoid(1.702 u); i = n (% 8).
+ *   GELU_ERF_16      out0 x 16 [n], in place: 0.5 x (1 + erf(x / sqrt 2)); i = n (% 8), f16.
+ *   GELU_ERF_F32     out0 x fp32 [n], in place; i = n (% 4).
+ *   L2NORM_ROWS      out0 x fp32 [rows, d], in place: x / |x| (no epsilon); i = rows, d.
+ *   L2NORM_BWD       in0 x fp32 [rows, d] (not read, may be NULL, with normalize 0), in1 dy fp32 [rows, d]; out0 bf16 [rows, d]
+ *                    = (dy - y (y . dy)) / |x| with y = x / |x|, or bf16(dy) with normalize 0; i = rows, d, normalize.
+ *   LN_SPLIT         in0 x fp32, in1 row_idx, in4 g, in5 b as LAYERNORM; in2 d1, in3 d2 fp32 or NULL (always x's layout);
+ *                    out0 planes bf16 [rows, 2 * d] or NULL (hi = bf16(y32) | lo = bf16(y32 - hi)), out1 y32 fp32 [rows, d] or
+ *                    NULL (one of the two is required); i = rows, d, x_row_stride, write_x.
+ *   ROWS_SPLIT       in0 x fp32 [rows, ld_in]; out0 bf16 [rows, 2 * Kp]: hi | lo planes of act(x[:, :K]), zeros in columns
+ *                    K .. Kp of both; i = rows, K, Kp (>= K; both % 4), ld_in (>= K, % 4), gelu (0 none, 1 QuickGELU with expf and
+ *                    an IEEE division, 2 erf GELU).
+ *   SPLIT_PLANES     in0 x fp32 [rows, d]; out0 bf16 [rows, planes * d]; i = rows, d (% 4), planes (1: hi only, 2).
+ *   GATHER_ROWS      in0 bank bf16 [R, ld], in1 idx int32 [n]; out0 fp32 [n, D] = bank[idx - idx_offset, :D] (+ [D : 2 D] with
+ *                    planes 2), zeros where idx < 0 or idx - idx_offset is outside [0, R); i = n, D, R, ld (>= planes * D),
+ *                    planes (1, 2), idx_offset (>= 0).
+ *   GATHER_F32_ROWS  in0 x fp32 rows of pitch ld, in1 idx int32 [n] or NULL; out0 fp32 [n, d] = x[idx[r]] or, without idx,
+ *                    x[r * idx_mul]; i = n, d (% 4), ld (>= d, % 4), idx_mul (>= 0).
+ *   TEXT_LENS_SCAN   in0 tok int32 [n_text, ctx]; out0 starts int32 [n_text + 2], out1 pfx int32 [2 * n_text] or NULL, out2
+ *                    scratch int32 [n_text] (required without pfx); len = position of the first maximum id + 1; with pfx
+ *                    (groups of G consecutive texts, the first is the base) pfx[n] = min(first mismatch with the base, len,
+ *                    the base's len), 0 for a base, and pfx[n_text + n] = starts[base]; starts = exclusive scan of len - pfx,
+ *                    starts[n_text] = total, starts[n_text + 1] = the largest len; i = n_text, ctx, G (>= 2 with pfx).
+ *   TEXT_EMBED       in0 tok int32 [n_text, ctx], in1 tok_emb fp32 [vocab, d], in2 pos fp32 [ctx, d], in3 starts or NULL, in4 pfx
+ *                    or NULL (needs starts), both as TEXT_LENS_SCAN writes them; out0 x fp32 rows of d = tok_emb[clamp(id, 0,
+ *                    vocab - 1)] + pos[t] at row n * ctx + t (dense) or starts[n] + t - pfx[n] for the text's own positions
+ *                    (packed; other rows are not written), out1 eot_row int32 [n_text] = the row of the first maximum id
+ *                    (a text with no own rows: its base's row pfx[n_text + n] + pfx[n] - 1); i = n_text, ctx, d (% 4), vocab.
+ * A NULL args or required pointer; a pointer or a row stride that is not aligned for the kernel's vector accesses (16 bytes
+ * for fp32 rows read or written as 4-vectors and for 16-bit tensors in pieces of 8, 8 bytes for 16-bit rows in pieces of 4,
+ * the element size for the scalar kernels: the im2col / col2im fp32 forms, the L2 kernels, GATHER_ROWS, the text kernels' int32);
+ * a stride below the row's width; an extent that is not positive; extents whose product leaves int32; image % patch != 0; a flag
+ * that is neither 0 nor 1; planes or gelu outside the values listed; an unknown op: TVC_E_INVALID.  What a launcher rejects
+ * (d % 4, d > 1024, n % 8, Kp < K, G < 2 with pfx): TVC_E_HIP.  Either way nothing is launched. */
+enum { TVC_TOWER_OP_LAYERNORM = 0, TVC_TOWER_OP_LAYERNORM_BWD = 1, TVC_TOWER_OP_LNPRE_BWD = 2, TVC_TOWER_OP_ASSEMBLE_LNPRE = 3,
+       TVC_TOWER_OP_IM2COL = 4, TVC_TOWER_OP_IM2COL_F32 = 5, TVC_TOWER_OP_COL2IM = 6, TVC_TOWER_OP_GELU_FWD = 7,
+       TVC_TOWER_OP_GELU_BWD = 8, TVC_TOWER_OP_GELU_ERF_16 = 9, TVC_TOWER_OP_GELU_ERF_F32 = 10, TVC_TOWER_OP_L2NORM_ROWS = 11,
+       TVC_TOWER_OP_L2NORM_BWD = 12, TVC_TOWER_OP_LN_SPLIT = 13, TVC_TOWER_OP_ROWS_SPLIT = 14, TVC_TOWER_OP_SPLIT_PLANES = 15,
+       TVC_TOWER_OP_GATHER_ROWS = 16, TVC_TOWER_OP_GATHER_F32_ROWS = 17, TVC_TOWER_OP_TEXT_LENS_SCAN = 18,
+       TVC_TOWER_OP_TEXT_EMBED = 19, TVC_TOWER_OP_COUNT = 20 };
+/* as tvc_sd_op_args with four output slots: LAYERNORM has three outputs */
+typedef struct { const void* in[6]; void* out[4]; int64_t i[12]; float f[12]; } tvc_tower_op_args;
+int tvc_tower_op(tvc_handle* h, int32_t op, const tvc_tower_op_args* a, void* stream);
+
 /* Image preprocessing on the device: images fp32 [n, 3, H, W] with values in [0, 1] -> out fp32 [n, 3, S, S]:
  * antialiased resize of the short side to S (filter 0 = bilinear: torchvision Resize as in
  * experiments/defenses/generative_ref.py:55-59 -- which resizes BOTH sides to S; 1 = bicubic: the CLIP preprocess of

@@ -99,6 +99,18 @@ SD_OPS = {name: code for code, name in enumerate((
     "timestep_embed", "transpose"))}
 
 
+class TowerOpArgs(C.Structure):
+    """``tvc_tower_op_args`` (include/tvc.h)."""
+    _fields_ = [("inp", C.c_void_p * 6), ("out", C.c_void_p * 4), ("i", C.c_int64 * 12), ("f", C.c_float * 12)]
+
+
+# TVC_TOWER_OP_* (include/tvc.h): the row kernels of the CLIP towers behind tvc_tower_op
+TOWER_OPS = {name: code for code, name in enumerate((
+    "layernorm", "layernorm_bwd", "lnpre_bwd", "assemble_lnpre", "im2col", "im2col_f32", "col2im", "gelu_fwd", "gelu_bwd",
+    "gelu_erf_16", "gelu_erf_f32", "l2norm_rows", "l2norm_bwd", "ln_split", "rows_split", "split_planes", "gather_rows",
+    "gather_f32_rows", "text_lens_scan", "text_embed"))}
+
+
 # name -> (restype, argtypes); must list every symbol include/tvc.h declares
 SIGNATURES = {
     "tvc_abi_version": (C.c_uint32, []),
@@ -162,6 +174,7 @@ SIGNATURES = {
     "tvc_sd_attention_ex": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_int32, _P]),
     "tvc_sd_op": (C.c_int, [_P, C.c_int32, C.POINTER(SDOpArgs), _P]),
+    "tvc_tower_op": (C.c_int, [_P, C.c_int32, C.POINTER(TowerOpArgs), _P]),
 }
 
 _lib = None

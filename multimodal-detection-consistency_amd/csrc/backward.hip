@@ -14,8 +14,9 @@
 //   g     = dy * gamma             dy: gradient w.r.t. the LN output (bf16, or fp32 when DY32)
 //   dx    = rstd * (g - mean(g) - xhat * mean(g * xhat)) (+ dres)
 // dres / dx are fp32 [*, d] rows of the residual-stream gradient (may alias: in place); dx16 (optional) receives
-// the bf16 copy that the next GEMM reads.  Row addressing: x rows at `x_row_stride` (elements) with optional
-// row_idx; dy / delta / dres / dx compact [rows, d] unless *_strided says they share x's row layout.
+// the bf16 copy that the next GEMM reads.  Row addressing (elements; pinned by tests/test_gpu_tower_ops.py): x AND delta
+// row r at r * x_row_stride -- delta shares x's layout, as in the forward --; dy dense [rows, d]; dres, dx and dx16 row r at
+// r * out_row_stride (ln_post scatters into the class rows of a zeroed [B * T, d] buffer: what lies between the rows is not written).
 // ---------------------------------------------------------------------------
 template <bool DY32>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ x, int64_t x_row_stride,

@@ -94,10 +94,13 @@ __device__ __forceinline__ float quick_gelu_sigmoid(float x) {
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.4554670f * x));
 }
 __device__ __forceinline__ float quick_gelu(float x) { return x * quick_gelu_sigmoid(x); }
-// d quick_gelu / dx = s + 1.702 x s (1 - s)
+// d quick_gelu / dx = s + 1.702 x s (1 - s).  The product runs on x clamped to +-1e38: beyond it s is exactly 0 or 1 and the
+// second term is 0, but 1.702 x itself overflows from |x| = 2e38 on and inf * 0 made the gradient NaN at the ends of the bf16
+// range.  Inside the clamp the expression and its bits are what they were.
 __device__ __forceinline__ float quick_gelu_grad(float x) {
     const float s = quick_gelu_sigmoid(x);
-    return s + 1.702f * x * s * (1.0f - s);
+    const float xc = fminf(fmaxf(x, -1e38f), 1e38f);
+    return s + 1.702f * xc * s * (1.0f - s);
 }
 // the expf / division form of the fp32-grade modes (as the fp32 CPU path)
 __device__ __forceinline__ float quick_gelu_exact(float x) { return x / (1.0f + expf(-1.702f * x)); }

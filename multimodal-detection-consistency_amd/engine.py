@@ -708,6 +708,21 @@ class TVCEngine:
     def layernorm_f16(self, x: torch.Tensor, g: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
         return self._layernorm16(torch.float16, self.lib.tvc_layernorm_f16, x, g, b)
 
+    def tower_op(self, op: str, ins=(), outs=(), i=()) -> None:
+        """One row kernel of the towers on the caller's tensors (``tvc_tower_op``; needs no weights).  ``op`` is a key of
+        ``_lib.TOWER_OPS``; ``ins`` / ``outs`` / ``i`` fill the slots include/tvc.h lists for it (``None`` = NULL).  Nothing is
+        converted, copied or checked here: the tensors' data pointers are passed as they are, a view inside a larger buffer
+        included.  Raises ``TVCError`` where the C-ABI refuses the call."""
+        a = _lib.TowerOpArgs()
+        for k, t in enumerate(ins):
+            a.inp[k] = None if t is None else t.data_ptr()
+        for k, t in enumerate(outs):
+            a.out[k] = None if t is None else t.data_ptr()
+        for k, v in enumerate(i):
+            a.i[k] = int(v)
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.tvc_tower_op(self.handle, _lib.TOWER_OPS[op], C.byref(a), _stream()))
+
     PROF_CATEGORIES = ("gemm", "attention", "bank", "rowops")
 
     def profile_begin(self) -> None:

@@ -270,6 +270,88 @@ int main(int argc, char** argv) {
         CHECK(tvc_sd_op(h, TVC_SD_OP_COUNT, &s, nullptr) == TVC_E_INVALID && tvc_sd_op(h, -1, &s, nullptr) == TVC_E_INVALID);
         CHECK(tvc_sd_op(h, 0, nullptr, nullptr) == TVC_E_INVALID && tvc_sd_op(nullptr, 0, &s, nullptr) == TVC_E_INVALID);
     }
+    // tvc_tower_op: the same walk -- every op's slot decoding with valid arguments, then what the entry itself refuses
+    {
+        uint16_t* a16 = (uint16_t*)buf((size_t)1 << 16, 2); uint16_t* o16 = (uint16_t*)buf((size_t)1 << 16, 2);
+        float* a32 = (float*)buf((size_t)1 << 14, 4); float* o32 = (float*)buf((size_t)1 << 14, 4);
+        int32_t* i32 = (int32_t*)buf(1 << 10, 4); int32_t* oi32 = (int32_t*)buf(1 << 10, 4);
+        auto valid = [&](int op) {
+            tvc_tower_op_args s{};
+            switch (op) {
+            case TVC_TOWER_OP_LAYERNORM:
+                s.in[0] = a32; s.in[1] = i32; s.in[2] = a16; s.in[3] = a16; s.in[4] = a32; s.in[5] = a32;
+                s.out[0] = o16; s.out[1] = o32; s.out[2] = o32; s.i[0] = 4; s.i[1] = 8; s.i[2] = 24; s.i[3] = 1; s.i[4] = 1; s.i[5] = 1; break;
+            case TVC_TOWER_OP_LAYERNORM_BWD:
+                s.in[0] = a32; s.in[1] = a16; s.in[2] = a32; s.in[3] = a32; s.in[4] = o32;
+                s.out[0] = o32; s.out[1] = o16; s.i[0] = 4; s.i[1] = 8; s.i[2] = 24; s.i[3] = 16; s.i[4] = 1; break;
+            case TVC_TOWER_OP_LNPRE_BWD:
+                s.in[0] = a32; s.in[1] = a32; s.in[2] = a32; s.in[3] = a32; s.out[0] = o16; s.i[0] = 2; s.i[1] = 3; s.i[2] = 8; break;
+            case TVC_TOWER_OP_ASSEMBLE_LNPRE:
+                s.in[0] = a32; s.in[1] = a32; s.in[2] = a32; s.in[3] = a32; s.in[4] = a32; s.out[0] = o32; s.i[0] = 2; s.i[1] = 3; s.i[2] = 8; break;
+            case TVC_TOWER_OP_IM2COL:
+                s.in[0] = a32; s.out[0] = o16; s.i[0] = 2; s.i[1] = 8; s.i[2] = 4; s.i[3] = 64; s.i[4] = 1; break;
+            case TVC_TOWER_OP_IM2COL_F32:
+                s.in[0] = a32; s.out[0] = o32; s.i[0] = 2; s.i[1] = 8; s.i[2] = 4; break;
+            case TVC_TOWER_OP_COL2IM:
+                s.in[0] = a32; s.out[0] = o32; s.i[0] = 2; s.i[1] = 8; s.i[2] = 4; s.i[3] = 64; break;
+            case TVC_TOWER_OP_GELU_FWD: case TVC_TOWER_OP_GELU_BWD: case TVC_TOWER_OP_GELU_ERF_16:
+                s.in[0] = a16; s.out[0] = o16; s.i[0] = 16; break;
+            case TVC_TOWER_OP_GELU_ERF_F32:
+                s.out[0] = o32; s.i[0] = 16; break;
+            case TVC_TOWER_OP_L2NORM_ROWS:
+                s.out[0] = o32; s.i[0] = 4; s.i[1] = 10; break;
+            case TVC_TOWER_OP_L2NORM_BWD:
+                s.in[0] = a32; s.in[1] = a32; s.out[0] = o16; s.i[0] = 4; s.i[1] = 10; s.i[2] = 1; break;
+            case TVC_TOWER_OP_LN_SPLIT:
+                s.in[0] = a32; s.in[1] = i32; s.in[2] = a32; s.in[3] = a32; s.in[4] = a32; s.in[5] = a32;
+                s.out[0] = o16; s.out[1] = o32; s.i[0] = 4; s.i[1] = 8; s.i[2] = 24; s.i[3] = 1; break;
+            case TVC_TOWER_OP_ROWS_SPLIT:
+                s.in[0] = a32; s.out[0] = o16; s.i[0] = 4; s.i[1] = 8; s.i[2] = 16; s.i[3] = 12; s.i[4] = 2; break;
+            case TVC_TOWER_OP_SPLIT_PLANES:
+                s.in[0] = a32; s.out[0] = o16; s.i[0] = 4; s.i[1] = 8; s.i[2] = 2; break;
+            case TVC_TOWER_OP_GATHER_ROWS:
+                s.in[0] = a16; s.in[1] = i32; s.out[0] = o32; s.i[0] = 4; s.i[1] = 10; s.i[2] = 6; s.i[3] = 24; s.i[4] = 2; s.i[5] = 3; break;
+            case TVC_TOWER_OP_GATHER_F32_ROWS:
+                s.in[0] = a32; s.out[0] = o32; s.i[0] = 4; s.i[1] = 8; s.i[2] = 12; s.i[3] = 5; break;
+            case TVC_TOWER_OP_TEXT_LENS_SCAN:
+                s.in[0] = i32; s.out[0] = oi32; s.out[1] = oi32 + 64; s.i[0] = 5; s.i[1] = 7; s.i[2] = 2; break;
+            case TVC_TOWER_OP_TEXT_EMBED:
+                s.in[0] = i32; s.in[1] = a32; s.in[2] = a32; s.in[3] = i32; s.in[4] = i32; s.out[0] = o32; s.out[1] = oi32;
+                s.i[0] = 5; s.i[1] = 7; s.i[2] = 8; s.i[3] = 11; break;
+            }
+            return s;
+        };
+        for (int op = 0; op < TVC_TOWER_OP_COUNT; ++op) {
+            tvc_tower_op_args s = valid(op);
+            OK(tvc_tower_op(h, op, &s, nullptr));
+            s.out[0] = nullptr; s.out[1] = nullptr;
+            CHECK(tvc_tower_op(h, op, &s, nullptr) == TVC_E_INVALID);        // NULL output
+            s = valid(op); s.out[0] = (char*)s.out[0] + 1;
+            CHECK(tvc_tower_op(h, op, &s, nullptr) == TVC_E_INVALID);        // an output no access of the kernel is aligned for
+            s = valid(op); s.i[0] = 0;
+            CHECK(tvc_tower_op(h, op, &s, nullptr) == TVC_E_INVALID);        // an extent of 0
+            s.i[0] = (int64_t)1 << 40;
+            CHECK(tvc_tower_op(h, op, &s, nullptr) == TVC_E_INVALID);        // an extent beyond int32
+        }
+        tvc_tower_op_args s = valid(TVC_TOWER_OP_LAYERNORM);
+        s.i[2] = 6;  CHECK(tvc_tower_op(h, TVC_TOWER_OP_LAYERNORM, &s, nullptr) == TVC_E_INVALID);      // x_row_stride < d
+        s.i[2] = 10; CHECK(tvc_tower_op(h, TVC_TOWER_OP_LAYERNORM, &s, nullptr) == TVC_E_INVALID);      // x_row_stride % 4
+        s.i[2] = 24; s.in[2] = a16 + 2; CHECK(tvc_tower_op(h, TVC_TOWER_OP_LAYERNORM, &s, nullptr) == TVC_E_INVALID);   // delta at 4 bytes
+        s = valid(TVC_TOWER_OP_LAYERNORM); s.i[1] = 6; s.i[2] = 8;
+        CHECK(tvc_tower_op(h, TVC_TOWER_OP_LAYERNORM, &s, nullptr) == TVC_OK);      // d % 4: the launcher's (a stub here), not the entry's
+        s = valid(TVC_TOWER_OP_IM2COL); s.i[2] = 3;
+        CHECK(tvc_tower_op(h, TVC_TOWER_OP_IM2COL, &s, nullptr) == TVC_E_INVALID);  // image % patch
+        s = valid(TVC_TOWER_OP_IM2COL); s.i[3] = 40;
+        CHECK(tvc_tower_op(h, TVC_TOWER_OP_IM2COL, &s, nullptr) == TVC_E_INVALID);  // Kp < 3 * patch^2
+        s = valid(TVC_TOWER_OP_TEXT_LENS_SCAN); s.out[1] = nullptr;
+        CHECK(tvc_tower_op(h, TVC_TOWER_OP_TEXT_LENS_SCAN, &s, nullptr) == TVC_E_INVALID);               // neither pfx nor the scratch
+        s = valid(TVC_TOWER_OP_TEXT_EMBED); s.in[3] = nullptr;
+        CHECK(tvc_tower_op(h, TVC_TOWER_OP_TEXT_EMBED, &s, nullptr) == TVC_E_INVALID);                   // pfx without starts
+        s = valid(TVC_TOWER_OP_GATHER_ROWS); s.i[4] = 3;
+        CHECK(tvc_tower_op(h, TVC_TOWER_OP_GATHER_ROWS, &s, nullptr) == TVC_E_INVALID);                  // planes
+        CHECK(tvc_tower_op(h, TVC_TOWER_OP_COUNT, &s, nullptr) == TVC_E_INVALID && tvc_tower_op(h, -1, &s, nullptr) == TVC_E_INVALID);
+        CHECK(tvc_tower_op(h, 0, nullptr, nullptr) == TVC_E_INVALID && tvc_tower_op(nullptr, 0, &s, nullptr) == TVC_E_INVALID);
+    }
     // an allocation the "device" cannot serve is reported as TVC_E_NOMEM, and the handle stays usable
     hip_stub_limit() = (size_t)64 << 20;
     CHECK(tvc_sd_unet(h, lat, 6, 64, 64, 1.f, ctx, eps, nullptr) == TVC_E_NOMEM || tvc_sd_unet(h, lat, 6, 64, 64, 1.f, ctx, eps, nullptr) == TVC_E_INVALID ||

@@ -97,6 +97,69 @@ def test_pgd_step_kernel_matches_formula(gpu_engine):
             assert diff[~unsure].max().item() < 1e-6
 
 
+@pytest.mark.parametrize("n", [1, 1023, 1025])
+def test_pgd_and_l2_step_small_and_ragged_images(gpu_engine, n):
+    """One element, one short of the 1024 threads, one more than them (a second trip for thread 0 only).  Image 0 stays inside
+    the eps ball (nothing is shrunk or clipped), image 1 starts outside it, image 2 (l2_step) has an all-zero gradient: the 1e-8
+    guard makes its step 0 and adv is only projected.
+    pgd_step without momentum is additions, min and max of fp32 numbers (the sign step is an exact product): bit patterns of the
+    same chain in fp32 on the CPU.  A block sum here is at most 2 terms per thread, 6 shuffle levels
+    and 16 partial sums: under 24 roundings of 2^-24, so below 2^-19 relative in the worst case.  With momentum: |mom - ref64| <=
+    2^-19 (|mu mom| + |grad| / |grad|_1) (the L1 sum, its reciprocal, a product-sum).  l2_step: |adv - ref64| <= 2^-19 (|clean| +
+    |adv| + |step| + |d|): two such sums, each halved by its square root, and the result passes through both."""
+    eng = gpu_engine
+    g0 = torch.Generator().manual_seed(40 + n)
+    B = 3
+    clean = torch.rand((B, n), generator=g0) * 0.5 + 0.25
+    grad = torch.randn((B, n), generator=g0) * 1e-3
+    eps, alpha, mu = 8 / 255, 2 / 255, 0.9
+    adv = clean + (torch.rand((B, n), generator=g0) - 0.5) * 0.01          # |adv + step - clean| < eps
+    adv[1] = clean[1] + 0.05 * torch.where(torch.rand(n, generator=g0) < 0.5, -1.0, 1.0)      # beyond eps: clipped back
+    for targeted in (False, True):
+        a = adv.clone().cuda()
+        eng.pgd_step(a, clean.cuda(), grad.cuda(), None, eps, alpha, mu, 0.0, 1.0, targeted)
+        w = adv + torch.tensor(-alpha if targeted else alpha, dtype=torch.float32) * grad.sign()
+        dl = torch.minimum(torch.maximum(w - clean, torch.tensor(-eps, dtype=torch.float32)), torch.tensor(eps, dtype=torch.float32))
+        want = (clean + dl).clamp(0.0, 1.0)
+        assert torch.equal(a.cpu().view(torch.int32), want.view(torch.int32)), f"pgd_step n={n} targeted={targeted}"
+        assert ((want[0] - clean[0]).abs() < eps * 0.999).all() and ((want[1] - clean[1]).abs() > eps * 0.999).all()
+    mom = torch.randn((B, n), generator=g0) * 1e-2
+    a, m = adv.clone().cuda(), mom.clone().cuda()
+    eng.pgd_step(a, clean.cuda(), grad.cuda(), m, eps, alpha, mu, 0.0, 1.0, False)
+    l1 = grad.double().abs().sum(1, keepdim=True)
+    wm = float(torch.tensor(mu, dtype=torch.float32)) * mom.double() + grad.double() / l1
+    S = 2.0 ** -19 * ((mu * mom.double()).abs() + grad.double().abs() / l1)
+    assert ((m.cpu().double() - wm).abs() <= S).all(), f"pgd_step momentum n={n}"
+    sure = wm.abs() > S
+    w = adv.double() + alpha * wm.sign()
+    want = (clean.double() + (w - clean.double()).clamp(-eps, eps)).clamp(0, 1)
+    assert ((a.cpu().double() - want).abs()[sure] <= 2.0 ** -23).all()
+    # ---- l2_step
+    eps2, step = 0.02 * n ** 0.5, 0.004 * n ** 0.5
+    adv2 = clean + (torch.rand((B, n), generator=g0) - 0.5) * 0.01         # |d|_2 < eps2 after the step: not shrunk
+    adv2[1] = clean[1] + 0.05 * torch.where(torch.rand(n, generator=g0) < 0.5, -1.0, 1.0)     # |d|_2 = 0.05 sqrt(n) > eps2
+    adv2[2] = clean[2] + 0.03 * torch.where(torch.rand(n, generator=g0) < 0.5, -1.0, 1.0)
+    grad2 = grad.clone()
+    grad2[2] = 0.0
+    worst = 0.0
+    for descent in (True, False):
+        a = adv2.clone().cuda()
+        eng.l2_step(a, clean.cuda(), grad2.cuda(), eps2, step, 0.0, 1.0, descent)
+        c64, g64 = clean.double(), grad2.double()
+        stepv = (-1 if descent else 1) * step * g64 / (g64.norm(dim=1, keepdim=True) + float(torch.tensor(1e-8, dtype=torch.float32)))
+        d = adv2.double() + stepv - c64
+        dn = d.norm(dim=1, keepdim=True)
+        scale = torch.clamp(dn, max=eps2) / (dn + float(torch.tensor(1e-8, dtype=torch.float32)))
+        want = (c64 + d * scale).clamp(0, 1)
+        S = 2.0 ** -19 * (c64.abs() + adv2.double().abs() + stepv.abs() + d.abs())
+        err = (a.cpu().double() - want).abs()
+        assert (err <= S).all(), f"l2_step n={n} descent={descent}: {(err - S).max().item():.3e} over"
+        worst = max(worst, (err / S).max().item())
+        assert dn[0].item() < eps2 < dn[1].item() and scale[0].item() > 0.999 and stepv[2].abs().max().item() == 0.0
+        assert ((want[2] - c64[2]).norm() - eps2).abs().item() < 1e-6        # the zero-gradient image: projected, not moved
+    print(f"[measured] pgd_step / l2_step n={n}: pgd bit-equal; l2 worst |got - ref| = {worst:.3f} of S = 2^-19 M")
+
+
 def _oracle_grad(vw, x, t_unit, heads, patch):
     xr = x.clone().requires_grad_(True)
     f = clip_oracle.vision_forward(vw, xr, heads, patch)
