@@ -319,6 +319,44 @@ int tvc_topk_merge(tvc_handle* h, const int32_t* idx_parts_dev, const float* sim
                    int32_t* idx_out_dev, float* sim_out_dev, float* feat_out_dev,
                    float* mom_out_dev, void* stream);
 
+/* ---- k-means over a bank slot ------------------------------------------ */
+
+/* Both entries work on the rows of the currently selected bank slot (tvc_bank_select / tvc_bank_set): any [R, D]
+ * matrix, bf16 used in place or fp32 held as (hi | lo) bf16 planes.  The rows need not be unit length: the
+ * clustering is Euclidean.  One Lloyd iteration is one assign and one update; the driver loop, the initialisation
+ * and the stop rule are the caller's.  Together they replace KMeans(n_clusters, random_state = 42, n_init = 10)
+ * .fit_predict(vectors) of src/ref_bank.py:294-300 and the training half of faiss.IndexIVFFlat
+ * (src/retrieval.py:101-103,124-126, retrieval_ref.py:141-160, scripts/build_faiss_indices.py:139-142).
+ * Both return TVC_E_STATE when the slot holds no bank or R == 0, and TVC_E_INVALID for K < 1, K > R, K > 65536
+ * or a NULL required buffer; nothing is launched then. */
+
+/* Assign: for every bank row x, labels[r] = argmax_j (x . c_j - |c_j|^2 / 2), the Euclidean nearest centre.
+ *   centroids_dev  fp32 [K, D]
+ *   labels_dev     int32 [R]; ties go to the lowest centre index (equality of the fp32 scores); NaN scores never
+ *                  win, a row whose scores are all NaN gets -1
+ *   score_dev      fp32 [R] or NULL: the winning score (-inf for label -1)
+ *   dist2_dev      fp32 [R] or NULL: max(0, |x|^2 - 2 score), the squared distance to the centre (0 for label -1)
+ * The [R, K] score matrix is never written: it lives in MFMA accumulators tile by tile.  Products in the bank
+ * search's split-bf16 form: exact bf16 products against (hi | lo) centre planes for a bf16 bank, hi.hi + lo.hi +
+ * hi.lo for an fp32 bank; |c|^2 / 2 is taken from the fp32 centres. */
+int tvc_kmeans_assign(tvc_handle* h, const float* centroids_dev, int32_t K,
+                      int32_t* labels_dev, float* score_dev, float* dist2_dev, void* stream);
+
+/* Update: centroids_out[j] = the mean of the bank rows labelled j (hi + lo of an fp32 bank), fp32 sums in a fixed
+ * order -- a counting sort of the row indices by label, stable, then one workgroup per cluster.  No floating-point
+ * atomics: the result is a pure function of the bank and the labels, bit for bit.
+ *   labels_dev         int32 [R]; labels outside [0, K) (the -1 of assign) belong to no cluster
+ *   centroids_in_dev   fp32 [K, D]: a cluster with no member copies its row unchanged
+ *   centroids_out_dev  fp32 [K, D] (must not alias centroids_in_dev)
+ *   counts_dev         int32 [K]
+ *   offsets_dev        int32 [K + 1] or NULL: exclusive scan of counts
+ *   order_dev          int32 [R] or NULL: row indices grouped by cluster, ascending inside each cluster; entries
+ *                      [offsets[j], offsets[j + 1]) are cluster j's members (the inverted-list layout), entries
+ *                      from offsets[K] on are not written */
+int tvc_kmeans_update(tvc_handle* h, const int32_t* labels_dev, const float* centroids_in_dev, int32_t K,
+                      float* centroids_out_dev, int32_t* counts_dev, int32_t* offsets_dev, int32_t* order_dev,
+                      void* stream);
+
 /* All-pairs cosine matrix out[n, m] = cos(x[n], y[m]), fp32-grade (both sides
  * L2-normalised on device, split into bf16 (hi, lo) planes, three MFMA products).
  * x fp32 [N, D], y fp32 [M, D], out fp32 [N, M]; D % 64 == 0.

@@ -57,10 +57,7 @@ struct Cand {
     float v;
     int32_t idx;
 };
-// (v desc, idx asc) ordering
-__device__ __forceinline__ bool cand_better(float v, int idx, float ov, int oidx) {
-    return (v > ov) || (v == ov && idx < oidx);
-}
+// (cand_better, the (v desc, idx asc) ordering: common.hpp -- kmeans.hip orders its centres by it too)
 // all-lane arg-max of (v, idx) in that order over groups of W lanes; pos < 0 = this lane brings no candidate
 template <int W>
 __device__ __forceinline__ void argmax_reduce(float& v, int& idx, int& pos) {

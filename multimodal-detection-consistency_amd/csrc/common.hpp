@@ -85,6 +85,11 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// (v desc, idx asc): the order of the bank search's candidates and of k-means' centres; false whenever v is NaN
+__device__ __forceinline__ bool cand_better(float v, int idx, float ov, int oidx) {
+    return (v > ov) || (v == ov && idx < oidx);
+}
+
 // 16-byte async global->LDS copy (global_load_lds_dwordx4).  `lds_wave_base`
 // must be wave-uniform: the hardware writes lane L at lds_wave_base + 16*L.
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {

@@ -1,7 +1,8 @@
 // Internal: the handle behind include/tvc.h, its workspace slots and the launch helpers shared by the translation
 // units that implement the C-ABI (tvc_abi.cpp: the CLIP tower encode drivers of every precision mode and the bf16 /
 // fp16 towers, bank, consistency; tvc_precise.cpp: the fp32-grade towers' stem, layer loop and head; tvc_split.cpp: the
-// split-bf16 towers' stem, layer loop, head and weight planes; tvc_sd.cpp: latent-diffusion reference generator).
+// split-bf16 towers' stem, layer loop, head and weight planes; tvc_sd.cpp: latent-diffusion reference generator;
+// tvc_kmeans.cpp: k-means over a bank slot).
 #pragma once
 #include "../../include/tvc.h"
 #include "kernels.hpp"
@@ -32,6 +33,9 @@ enum Slot {
     WS_STX = WS_S_END, WS_STH, WS_STQKV, WS_STU, WS_STM, WS_STDELTA1, WS_STDELTA2, WS_STCLS,
     // latent-diffusion reference generator (tvc_sd.cpp)
     WS_SD0, WS_SD1, WS_SD2, WS_SD3, WS_SD4, WS_SD5, WS_SD6, WS_SD7,
+    // k-means over a bank slot (tvc_kmeans.cpp): centre planes, half norms, counting-sort counters, offsets / order when the
+    // caller does not ask for them
+    WS_KM_CPLANES, WS_KM_HALFNORM, WS_KM_BLKCNT, WS_KM_OFFSETS, WS_KM_ORDER,
     WS_COUNT
 };
 

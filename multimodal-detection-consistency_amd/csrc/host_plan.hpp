@@ -55,6 +55,21 @@ inline void bank_plan(int64_t R, int M, int k, int* n_sample, int* sample_stride
     *cap = BANK_CAP;
 }
 
+// k-means update (kmeans.hip): the counting sort cuts the R rows into nblocks runs of rows_per_block rows (a multiple of the
+// 256-row chunk of the stable scatter); the [nblocks, K] counter matrix stays under 16 MiB and nblocks under 1 024 (the
+// column scan walks the blocks one after the other)
+#define KMEANS_MAX_K 65536
+inline void kmeans_update_plan(int64_t R, int K, int* nblocks, int* rows_per_block) {
+    int64_t nb = ((int64_t)4 << 20) / (K > 0 ? K : 1);
+    if (nb > 1024) nb = 1024;
+    const int64_t chunks = (R + 255) / 256;
+    if (nb > chunks) nb = chunks;
+    if (nb < 1) nb = 1;
+    const int64_t rpb = ((R + nb - 1) / nb + 255) / 256 * 256;
+    *rows_per_block = (int)(rpb > 0 ? rpb : 256);
+    *nblocks = (int)((R + *rows_per_block - 1) / *rows_per_block > 0 ? (R + *rows_per_block - 1) / *rows_per_block : 1);
+}
+
 // GroupNorm statistics slabs: small slabs = many workgroups (the pass is latency-bound on few), at most 1024 slabs per image
 inline int gn_slab_tokens(int HW) { int s = 64; while ((HW + s - 1) / s > 1024) s *= 2; return s; }
 // ws: >= n * nslab * groups * 2 + n * groups * 2 floats

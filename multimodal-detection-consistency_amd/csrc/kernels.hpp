@@ -145,6 +145,40 @@ hipError_t launch_topk_merge(const int32_t* idx_parts, const float* sim_parts, c
                              int32_t* idx_out, float* sim_out, float* feat_out, float* mom_out,
                              hipStream_t stream);
 
+// ---- kmeans.hip: k-means over a bank slot (assign: nearest centre per bank row; update: deterministic cluster means)
+struct KmeansAssignLaunch {
+    const uint16_t* bank = nullptr;   // [R, ldb] bf16 planes, as BankSearchLaunch
+    int64_t ldb = 0;
+    int64_t R = 0;
+    int D = 0;
+    int bank_planes = 1;
+    const float* centroids = nullptr; // [K, D] fp32
+    const uint16_t* cplanes = nullptr;// [K, 2 * D] bf16 (hi | lo) planes of the centres
+    int K = 0;
+    float* halfnorm = nullptr;        // workspace [round_up(K, 256)]: |c|^2 / 2, NaN in the padding
+    int32_t* labels = nullptr;        // [R]: arg-max of x.c - |c|^2 / 2, lowest centre on ties, -1 when every score is NaN
+    float* score = nullptr;           // [R] or nullptr: the winning score
+    float* dist2 = nullptr;           // [R] or nullptr: max(0, |x|^2 - 2 score); 0 for label -1
+};
+hipError_t launch_kmeans_assign(const KmeansAssignLaunch& L, hipStream_t stream);
+struct KmeansUpdateLaunch {
+    const uint16_t* bank = nullptr;
+    int64_t ldb = 0;
+    int64_t R = 0;
+    int D = 0;
+    int bank_planes = 1;
+    const int32_t* labels = nullptr;  // [R]; labels outside [0, K) belong to no cluster
+    const float* centroids_in = nullptr;   // [K, D]: the row an empty cluster keeps
+    int K = 0;
+    int nblocks = 0, rows_per_block = 0;   // kmeans_update_plan
+    int32_t* blk_cnt = nullptr;       // workspace [nblocks, K]
+    float* centroids_out = nullptr;   // [K, D]
+    int32_t* counts = nullptr;        // [K]
+    int32_t* offsets = nullptr;       // [K + 1]
+    int32_t* order = nullptr;         // [R]: row indices grouped by cluster, ascending inside a cluster
+};
+hipError_t launch_kmeans_update(const KmeansUpdateLaunch& L, hipStream_t stream);
+
 // ---- consistency.hip
 struct ConsistencyParams {
     int reference_count;

@@ -1,0 +1,321 @@
+// K-means over a registered bank slot (src/ref_bank.py:259-339; the training half of an IVF index): one Lloyd iteration is
+// an ASSIGN pass (nearest centre of every bank row) and an UPDATE pass (the mean of every cluster's rows).
+//
+//   assign  `kmeans_assign_kernel`: a workgroup owns 256 bank rows and walks the centre tiles.  Per 256 x 256 tile it runs
+//           the GEMM main loop with the CENTRES on the MFMA row dimension and the BANK ROWS on the lane dimension -- a lane
+//           holds 32 centres of one bank row per (m, n) block, so the running (best score, centre) of a row is four register
+//           pairs per lane and no score ever leaves the accumulators.  score = x.c - |c|^2 / 2 (arg-max = Euclidean nearest),
+//           the half norms come from an fp32 [K] vector padded to whole tiles with NaN: a padded centre can never win.
+//           The (score desc, centre asc) order is cand_better; NaN scores lose every comparison, a row whose scores are all
+//           NaN keeps the "none" index and gets label -1.  The four lane groups of a wave and the two wave rows that share
+//           a bank row are reduced once, after the last centre tile.
+//           Products as in the bank search: centres are split into (hi | lo) bf16 planes; a bf16 bank multiplies both
+//           (exact products), an fp32 bank's planes take hi.hi + lo.hi + hi.lo.
+//   update  a counting sort -- per-block label histogram (integer atomics into the block's own counter row), a column
+//           scan over the blocks, an exclusive scan over the clusters, a STABLE scatter (rank inside a 256-row chunk by
+//           comparison, chunks in order) -- gives the member lists in ascending row order; one workgroup per cluster then
+//           sums its members in a fixed order in fp32.  No floating-point atomics: the centres are a pure function of
+//           (bank, labels).
+#include "gemm_core.hpp"
+#include "kernels.hpp"
+#include "launch.hpp"
+
+#define KM_NONE 0x7fffffff
+#define KM_LDS_BYTES (GEMM_LDS_BYTES + 256 * 8)
+
+// ---- assign ------------------------------------------------------------------------------------------------------
+// halfnorm[k] = |c_k|^2 / 2 from the fp32 centres, k < K; NaN for the padding up to Kpad (a multiple of 256)
+__global__ __launch_bounds__(256) void kmeans_halfnorm_kernel(const float* __restrict__ c, int D, int K, int Kpad,
+                                                              float* __restrict__ halfnorm) {
+    const int lane = threadIdx.x & 63;
+    const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (k >= Kpad) return;
+    float s = __builtin_nanf("");
+    if (k < K) {
+        const float* row = c + (int64_t)k * D;
+        s = 0.f;
+        for (int i = lane * 4; i < D; i += 256) {
+            const f32x4_t v = *(const f32x4_t*)(row + i);
+            s = fmaf(v[0], v[0], fmaf(v[1], v[1], fmaf(v[2], v[2], fmaf(v[3], v[3], s))));
+        }
+        s = 0.5f * wave_sum(s);
+    }
+    if (lane == 0) halfnorm[k] = s;
+}
+
+// out[r] = |x_r|^2 of the stored row (hi + lo of an fp32 bank), one wave per row
+__global__ __launch_bounds__(256) void kmeans_rownorm_kernel(const uint16_t* __restrict__ bank, int64_t ld, int planes, int D,
+                                                             int64_t R, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < R; r += (int64_t)gridDim.x * 4) {
+        const uint16_t* br = bank + r * ld;
+        float s = 0.f;
+        for (int c = lane * 8; c < D; c += 512) {
+            const u32x4_t h = *(const u32x4_t*)(br + c);
+            u32x4_t l = u32x4_t{0u, 0u, 0u, 0u};
+            if (planes > 1) l = *(const u32x4_t*)(br + D + c);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float a = Op16<false>::lo(h[e]) + Op16<false>::lo(l[e]), b = Op16<false>::hi(h[e]) + Op16<false>::hi(l[e]);
+                s = fmaf(a, a, fmaf(b, b, s));
+            }
+        }
+        s = wave_sum(s);
+        if (lane == 0) out[r] = s;
+    }
+}
+
+struct KmeansAssignArgs {
+    const float* halfnorm;     // [n_ctiles * 256], NaN beyond K
+    int32_t* labels;           // [R]
+    float* score;              // [R] or null
+    float* dist2;              // [R] or null; holds |x|^2 on entry
+    int R;
+};
+
+__global__ __launch_bounds__(GEMM_THREADS) void kmeans_assign_kernel(GemmOperands g, KmeansAssignArgs e, int n_ctiles) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* red_v = (float*)(smem + GEMM_LDS_BYTES);        // the bests of wave row 1, per bank row of the tile
+    int* red_i = (int*)(red_v + 256);
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int wm = wave >> 2, wn = wave & 3;
+    const int j0 = blockIdx.x * GEMM_BN;
+    float bv[4];
+    int bi[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) { bv[n] = -INFINITY; bi[n] = KM_NONE; }
+    for (int ct = 0; ct < n_ctiles; ++ct) {
+        gemm_acc_t acc;
+        gemm_zero_acc(acc);
+        gemm_mainloop(acc, g, ct * GEMM_BM, j0, smem);
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            const int c0 = ct * GEMM_BM + wm * 128 + m * 16 + (lane >> 4) * 4;
+            const f32x4_t hn = *(const f32x4_t*)(e.halfnorm + c0);
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float s = acc[m][n][r] - hn[r];
+                    if (cand_better(s, c0 + r, bv[n], bi[n])) { bv[n] = s; bi[n] = c0 + r; }
+                }
+            }
+        }
+    }
+    // the 4 lane groups of a wave, then the 2 wave rows, share a bank row
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+#pragma unroll
+        for (int o = 16; o <= 32; o <<= 1) {
+            const float ov = __shfl_xor(bv[n], o, 64);
+            const int oi = __shfl_xor(bi[n], o, 64);
+            if (cand_better(ov, oi, bv[n], bi[n])) { bv[n] = ov; bi[n] = oi; }
+        }
+        const int jl = wn * 64 + n * 16 + (lane & 15);
+        if (wm == 1 && (lane >> 4) == 0) { red_v[jl] = bv[n]; red_i[jl] = bi[n]; }
+    }
+    __syncthreads();
+    if (wm == 0 && (lane >> 4) == 0) {
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            const int jl = wn * 64 + n * 16 + (lane & 15);
+            const int row = j0 + jl;
+            if (row >= e.R) continue;
+            float v = bv[n];
+            int i = bi[n];
+            if (cand_better(red_v[jl], red_i[jl], v, i)) { v = red_v[jl]; i = red_i[jl]; }
+            const bool none = i == KM_NONE;
+            e.labels[row] = none ? -1 : i;
+            if (e.score) e.score[row] = v;
+            if (e.dist2) e.dist2[row] = none ? 0.f : fmaxf(0.f, e.dist2[row] - 2.f * v);
+        }
+    }
+}
+
+hipError_t launch_kmeans_assign(const KmeansAssignLaunch& L, hipStream_t stream) {
+    if (L.R < 1 || L.R > 0x7fffffffLL || L.K < 1 || L.D < 64 || L.D % 64 != 0 || L.bank_planes < 1 || L.bank_planes > 2)
+        return hipErrorInvalidValue;
+    const int n_ctiles = (L.K + GEMM_BM - 1) / GEMM_BM;
+    const int Kpad = n_ctiles * GEMM_BM;
+    hipError_t st = launch<kmeans_halfnorm_kernel>(dim3(Kpad / 4), dim3(256), 0, stream, L.centroids, L.D, L.K, Kpad, L.halfnorm);
+    if (st != hipSuccess) return st;
+    if (L.dist2) {
+        int64_t grid = (L.R + 3) / 4;
+        if (grid > 16384) grid = 16384;
+        st = launch<kmeans_rownorm_kernel>(dim3((int)grid), dim3(256), 0, stream, L.bank, L.ldb, L.bank_planes, L.D, L.R, L.dist2);
+        if (st != hipSuccess) return st;
+    }
+    // centres on the MFMA row dimension (A), bank rows on the lane dimension (B)
+    //   bf16 bank : chi.b + clo.b
+    //   fp32 bank : chi.bhi + chi.blo + clo.bhi
+    GemmOperands g;
+    g.A = L.cplanes; g.lda = 2 * (int64_t)L.D; g.I = L.K;
+    g.B = L.bank; g.ldb = L.ldb; g.J = (int)L.R;
+    g.ksteps_per_plane = L.D / GEMM_BK;
+    for (int p = 0; p < GEMM_MAX_PLANES; ++p) { g.a_plane_off[p] = 0; g.b_plane_off[p] = 0; }
+    if (L.bank_planes == 2) {
+        g.planes = 3;
+        g.b_plane_off[1] = L.D;
+        g.a_plane_off[2] = L.D;
+    } else {
+        g.planes = 2;
+        g.a_plane_off[1] = L.D;
+    }
+    KmeansAssignArgs e;
+    e.halfnorm = L.halfnorm; e.labels = L.labels; e.score = L.score; e.dist2 = L.dist2; e.R = (int)L.R;
+    const int64_t n_btiles = (L.R + GEMM_BN - 1) / GEMM_BN;
+    return launch<kmeans_assign_kernel, KM_LDS_BYTES>(dim3((unsigned)n_btiles), dim3(GEMM_THREADS), KM_LDS_BYTES, stream, g, e, n_ctiles);
+}
+
+// ---- update ------------------------------------------------------------------------------------------------------
+// Block b of the counting sort owns the rows [b * rpb, (b + 1) * rpb) and row b of the [nblocks, K] counter matrix.
+__global__ __launch_bounds__(256) void kmeans_hist_kernel(const int32_t* __restrict__ labels, int64_t R, int K, int rpb,
+                                                          int32_t* __restrict__ blk_cnt) {
+    const int64_t beg = (int64_t)blockIdx.x * rpb;
+    const int64_t end = beg + rpb < R ? beg + rpb : R;
+    int32_t* cnt = blk_cnt + (int64_t)blockIdx.x * K;
+    for (int64_t i = beg + threadIdx.x; i < end; i += 256) {
+        const int l = labels[i];
+        if ((unsigned)l < (unsigned)K) atomicAdd(&cnt[l], 1);       // integer: the counts do not depend on the order
+    }
+}
+// per cluster: the counters of the blocks become exclusive prefixes over the blocks; counts[j] = the total
+__global__ __launch_bounds__(256) void kmeans_colscan_kernel(int32_t* __restrict__ blk_cnt, int nblocks, int K,
+                                                             int32_t* __restrict__ counts) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= K) return;
+    int run = 0;
+    for (int b = 0; b < nblocks; ++b) {
+        const int t = blk_cnt[(int64_t)b * K + j];
+        blk_cnt[(int64_t)b * K + j] = run;
+        run += t;
+    }
+    counts[j] = run;
+}
+// offsets[0 .. K] = exclusive scan of counts; one workgroup, thread t owns the clusters [t * per, (t + 1) * per)
+__global__ __launch_bounds__(1024) void kmeans_offsets_kernel(const int32_t* __restrict__ counts, int K, int per,
+                                                              int32_t* __restrict__ offsets) {
+    __shared__ int wsum[16];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int j0 = t * per, j1 = (j0 + per < K) ? j0 + per : K;
+    int mine = 0;
+    for (int j = j0; j < j1; ++j) mine += counts[j];
+    int incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += v;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int base = incl - mine, total = 0;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) {
+        const int v = wsum[w];
+        if (w < wave) base += v;
+        total += v;
+    }
+    for (int j = j0; j < j1; ++j) { offsets[j] = base; base += counts[j]; }
+    if (t == 0) offsets[K] = total;
+}
+// stable scatter: a block walks its rows in chunks of 256; inside a chunk a row's rank among the rows of its label is
+// counted by comparison, between chunks the block's running position per label is its entry of the counter matrix
+__global__ __launch_bounds__(256) void kmeans_scatter_kernel(const int32_t* __restrict__ labels, int64_t R, int K, int rpb,
+                                                             int32_t* blk_cnt, const int32_t* __restrict__ offsets,
+                                                             int32_t* __restrict__ order) {
+    __shared__ int lab[256];
+    const int t = threadIdx.x;
+    const int64_t beg = (int64_t)blockIdx.x * rpb;
+    const int64_t end = beg + rpb < R ? beg + rpb : R;
+    int32_t* cnt = blk_cnt + (int64_t)blockIdx.x * K;
+    for (int64_t base = beg; base < end; base += 256) {
+        const int64_t i = base + t;
+        int l = i < end ? labels[i] : -1;
+        if ((unsigned)l >= (unsigned)K) l = -1;
+        lab[t] = l;
+        __syncthreads();
+        int rank = 0, total = 0;
+        if (l >= 0) {
+            for (int u = 0; u < 256; ++u) {
+                const int same = lab[u] == l;
+                rank += same & (u < t);
+                total += same;
+            }
+            const int64_t pos = (int64_t)offsets[l] + cnt[l] + rank;
+            if (pos < R) order[pos] = (int32_t)i;      // always true for the labels the histogram saw
+        }
+        __syncthreads();
+        if (l >= 0 && rank == total - 1) cnt[l] += total;
+        __syncthreads();
+    }
+}
+// one workgroup per cluster: thread (g, p) sums the 8 columns of piece p over the members g, g + G, ... in list order, the G
+// partial sums are added in the order of g; an empty cluster copies its input row
+__global__ __launch_bounds__(256) void kmeans_centroid_kernel(const uint16_t* __restrict__ bank, int64_t ld, int planes, int D,
+                                                              const int32_t* __restrict__ order, const int32_t* __restrict__ offsets,
+                                                              const float* __restrict__ cin, float* __restrict__ cout) {
+    __shared__ float red[256 * 8];
+    const int k = blockIdx.x, t = threadIdx.x;
+    const int beg = offsets[k], n = offsets[k + 1] - beg;
+    if (n <= 0) {
+        for (int c = t; c < D; c += 256) cout[(int64_t)k * D + c] = cin[(int64_t)k * D + c];
+        return;
+    }
+    const int pieces = D / 8;
+    const int P = pieces < 256 ? pieces : 256;
+    const int G = 256 / P;
+    const int g = t / P, p = t - g * P;
+    for (int p0 = 0; p0 < pieces; p0 += P) {
+        const bool live = g < G && p0 + p < pieces;
+        const int c = (p0 + p) * 8;
+        float s[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] = 0.f;
+        if (live) {
+#pragma unroll 4
+            for (int i = g; i < n; i += G) {
+                const uint16_t* br = bank + (int64_t)order[beg + i] * ld + c;
+                const u32x4_t h = *(const u32x4_t*)br;
+                u32x4_t l = u32x4_t{0u, 0u, 0u, 0u};
+                if (planes > 1) l = *(const u32x4_t*)(br + D);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    s[2 * e] += Op16<false>::lo(h[e]) + Op16<false>::lo(l[e]);
+                    s[2 * e + 1] += Op16<false>::hi(h[e]) + Op16<false>::hi(l[e]);
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) red[(g * P + p) * 8 + e] = s[e];
+        }
+        __syncthreads();
+        if (live && g == 0) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                float v = s[e];
+                for (int gg = 1; gg < G; ++gg) v += red[(gg * P + p) * 8 + e];
+                cout[(int64_t)k * D + c + e] = v / (float)n;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+hipError_t launch_kmeans_update(const KmeansUpdateLaunch& L, hipStream_t stream) {
+    if (L.R < 1 || L.R > 0x7fffffffLL || L.K < 1 || L.D < 64 || L.D % 64 != 0 || L.bank_planes < 1 || L.bank_planes > 2 ||
+        L.nblocks < 1 || L.rows_per_block < 1 || (int64_t)L.nblocks * L.rows_per_block < L.R)
+        return hipErrorInvalidValue;
+    hipError_t st = hipMemsetAsync(L.blk_cnt, 0, (size_t)L.nblocks * L.K * 4, stream);
+    if (st != hipSuccess) return st;
+    st = launch<kmeans_hist_kernel>(dim3(L.nblocks), dim3(256), 0, stream, L.labels, L.R, L.K, L.rows_per_block, L.blk_cnt);
+    if (st != hipSuccess) return st;
+    st = launch<kmeans_colscan_kernel>(dim3((L.K + 255) / 256), dim3(256), 0, stream, L.blk_cnt, L.nblocks, L.K, L.counts);
+    if (st != hipSuccess) return st;
+    st = launch<kmeans_offsets_kernel>(dim3(1), dim3(1024), 0, stream, (const int32_t*)L.counts, L.K, (L.K + 1023) / 1024, L.offsets);
+    if (st != hipSuccess) return st;
+    st = launch<kmeans_scatter_kernel>(dim3(L.nblocks), dim3(256), 0, stream, L.labels, L.R, L.K, L.rows_per_block, L.blk_cnt,
+                                       (const int32_t*)L.offsets, L.order);
+    if (st != hipSuccess) return st;
+    return launch<kmeans_centroid_kernel>(dim3(L.K), dim3(256), 0, stream, L.bank, L.ldb, L.bank_planes, L.D, (const int32_t*)L.order,
+                                          (const int32_t*)L.offsets, L.centroids_in, L.centroids_out);
+}

@@ -461,6 +461,132 @@ class TVCEngine:
             self._check(self.lib.tvc_bank_gather(self.handle, _ptr(idx), n, idx_offset, _ptr(out), _stream()))
         return out.view(*idx.shape, b["dim"])
 
+    # ---- k-means over a bank slot ----------------------------------------
+    def kmeans_assign(self, centroids: torch.Tensor, bank: str = DEFAULT_BANK):
+        """centroids fp32 [K, D] -> (labels int32 [R], score fp32 [R], dist2 fp32 [R]) over the rows of ``bank``:
+        the Euclidean nearest centre of every row (ties: lowest centre index; -1 when every score is NaN), its score
+        x.c - |c|^2 / 2 and the squared distance max(0, |x|^2 - 2 score)."""
+        centroids = _require_cuda(centroids, torch.float32, "centroids")
+        with self._lock, torch.cuda.device(self.device):
+            b = self._select(bank)
+            if centroids.dim() != 2 or centroids.shape[1] != b["dim"]:
+                raise ValueError(f"centroids must be [K, {b['dim']}] (got {tuple(centroids.shape)})")
+            R = b["rows"]
+            labels = torch.empty(R, dtype=torch.int32, device=self.device)
+            score = torch.empty(R, dtype=torch.float32, device=self.device)
+            dist2 = torch.empty(R, dtype=torch.float32, device=self.device)
+            self._check(self.lib.tvc_kmeans_assign(self.handle, _ptr(centroids), centroids.shape[0], _ptr(labels), _ptr(score),
+                                                   _ptr(dist2), _stream()))
+        return labels, score, dist2
+
+    def kmeans_update(self, labels: torch.Tensor, centroids: torch.Tensor, bank: str = DEFAULT_BANK, want_lists: bool = False):
+        """labels int32 [R], centroids fp32 [K, D] -> (centres fp32 [K, D], counts int32 [K], offsets int32 [K + 1] | None,
+        order int32 [R] | None): the mean of every cluster's rows (an empty cluster keeps its row of ``centroids``),
+        bit-reproducible.  ``want_lists``: also the member lists -- ``order[offsets[j]:offsets[j + 1]]`` are cluster j's
+        rows in ascending order; entries of ``order`` from ``offsets[K]`` on are -1 (rows labelled -1 are in no list)."""
+        labels = _require_cuda(labels, torch.int32, "labels")
+        centroids = _require_cuda(centroids, torch.float32, "centroids")
+        with self._lock, torch.cuda.device(self.device):
+            b = self._select(bank)
+            if labels.shape != (b["rows"],):
+                raise ValueError(f"labels must be [{b['rows']}] (got {tuple(labels.shape)})")
+            if centroids.dim() != 2 or centroids.shape[1] != b["dim"]:
+                raise ValueError(f"centroids must be [K, {b['dim']}] (got {tuple(centroids.shape)})")
+            K = centroids.shape[0]
+            out = torch.empty_like(centroids)
+            counts = torch.empty(K, dtype=torch.int32, device=self.device)
+            offsets = torch.empty(K + 1, dtype=torch.int32, device=self.device) if want_lists else None
+            order = torch.full((b["rows"],), -1, dtype=torch.int32, device=self.device) if want_lists else None
+            self._check(self.lib.tvc_kmeans_update(self.handle, _ptr(labels), _ptr(centroids), K, _ptr(out), _ptr(counts),
+                                                   _ptr(offsets), _ptr(order), _stream()))
+        return out, counts, offsets, order
+
+    def _kmeans_init(self, K: int, bank: str, init, rng) -> torch.Tensor:
+        """The K starting centres of one restart; every random number comes from ``rng`` (a seeded CPU generator), drawn
+        before the first kernel runs."""
+        import numpy as np
+        R = self.bank_size(bank)
+        if init == "random":
+            rows = rng.choice(R, K, replace=False)
+            return self.bank_gather(torch.from_numpy(rows.astype(np.int32)).to(self.device), bank=bank)
+        if init != "k-means++":
+            raise ValueError(f"init must be 'k-means++', 'random' or a [K, D] tensor (got {init!r})")
+        # D^2 sampling (Arthur & Vassilvitskii): centre j is row searchsorted(cumsum(d2), u[j] * sum(d2)), d2 = the squared
+        # distance to the nearest centre chosen so far -- one K = 1 assign per centre
+        u = rng.random(K)
+        first = min(int(u[0] * R), R - 1)
+        centres = [self.bank_gather(torch.tensor([first], dtype=torch.int32, device=self.device), bank=bank)]
+        d2 = None
+        for j in range(1, K):
+            _, _, d = self.kmeans_assign(centres[-1], bank=bank)
+            d2 = d if d2 is None else torch.minimum(d2, d)
+            cum = torch.cumsum(d2.double(), 0)
+            target = (cum[-1] * float(u[j])).reshape(1)
+            row = torch.searchsorted(cum, target, right=True).clamp_(max=R - 1).to(torch.int32)
+            centres.append(self.bank_gather(row, bank=bank))
+        return torch.cat(centres, 0)
+
+    def kmeans(self, K: int, bank: str = DEFAULT_BANK, init="k-means++", n_init: int = 10, max_iter: int = 300,
+               tol: float = 1e-4, seed=42, n_features: Optional[int] = None):
+        """Lloyd's k-means over the rows of ``bank`` -> (centres fp32 [K, D], labels int32 [R], inertia float, n_iter int,
+        order int32 [R], offsets int32 [K + 1]) of the best of ``n_init`` restarts (lowest inertia, the earliest restart
+        on equality).  ``KMeans(n_clusters=K, n_init=n_init, max_iter=max_iter, tol=tol)`` of src/ref_bank.py:298 with the
+        arithmetic in ``tvc_kmeans_assign`` / ``tvc_kmeans_update``; this loop is Python, as the PGD loop is.
+
+        * init: ``"k-means++"`` (D^2 sampling), ``"random"`` (K distinct rows) or a tensor [K, D] (one restart).  Restart
+          i draws from ``numpy.random.default_rng(seed + i)`` (``seed`` may also be a sequence of ``n_init`` seeds), so a
+          run is reproducible; the starting centres of the returned restart are kept in ``self.kmeans_last_init``.
+        * stop rule (sklearn's): the labels did not change, or sum |c_new - c_old|^2 <= tol * the mean over the
+          ``n_features`` features (default: the bank's D) of the data's variance; then one final assign, so the returned
+          labels, inertia (``dist2.double().sum()``), ``order`` and ``offsets`` belong to the returned centres.
+        * empty clusters: after an update the e empty clusters take the e rows with the largest ``dist2`` (ties: the lower
+          row index), handed out in that order to the empty clusters in ascending id, and the loop goes on.  This is
+          sklearn's ``_relocate_empty_clusters`` WITHOUT the subtraction: the donor clusters' centres are not adjusted
+          for the row they gave away (the next update recomputes them anyway)."""
+        import numpy as np
+        R = self.bank_size(bank)
+        if not 1 <= K <= R:
+            raise ValueError(f"need 1 <= K <= R = {R} (got K = {K})")
+        fixed = isinstance(init, torch.Tensor)
+        if fixed:
+            init = _require_cuda(init, torch.float32, "init")
+            n_init = 1
+        seeds = [int(s) for s in seed] if isinstance(seed, (list, tuple)) else [int(seed) + i for i in range(n_init)]
+        if len(seeds) != n_init:
+            raise ValueError(f"seed must be an int or a sequence of n_init = {n_init} ints")
+        # the data's variance from the kernels themselves: the K = 1 update is the mean row, its assign the squared deviations
+        zero = torch.zeros(R, dtype=torch.int32, device=self.device)
+        mean, _, _, _ = self.kmeans_update(zero, torch.zeros((1, self._banks[bank]["dim"]), device=self.device), bank=bank)
+        _, _, dev2 = self.kmeans_assign(mean, bank=bank)
+        tol_abs = tol * dev2.double().sum().item() / (R * (n_features or self._banks[bank]["dim"]))
+        best = None
+        for s in seeds:
+            C0 = init if fixed else self._kmeans_init(K, bank, init, np.random.default_rng(s))
+            Cc, prev, n_iter = C0, None, 0
+            for it in range(max_iter):
+                labels, _, d2 = self.kmeans_assign(Cc, bank=bank)
+                Cn, counts, _, _ = self.kmeans_update(labels, Cc, bank=bank)
+                empty = (counts == 0).nonzero().flatten()
+                if empty.numel():
+                    far = torch.sort(d2, descending=True, stable=True).indices[:empty.numel()].to(torch.int32)
+                    Cn[empty] = self.bank_gather(far, bank=bank)
+                n_iter = it + 1
+                shift = (Cn - Cc).double().pow(2).sum().item()
+                Cc = Cn
+                if prev is not None and torch.equal(labels, prev):
+                    break
+                if shift <= tol_abs:
+                    break
+                prev = labels
+            labels, _, d2 = self.kmeans_assign(Cc, bank=bank)
+            inertia = d2.double().sum().item()
+            if best is None or inertia < best[2]:
+                best = (Cc, labels, inertia, n_iter, C0)
+        Cc, labels, inertia, n_iter, C0 = best
+        self.kmeans_last_init = C0
+        _, _, offsets, order = self.kmeans_update(labels, Cc, bank=bank, want_lists=True)
+        return Cc, labels, inertia, n_iter, order, offsets
+
     def topk_merge(self, idx_parts, sim_parts, feat_parts=None, mom_parts=None):
         """parts [W, M, k] (+ feat [W, M, kf, D], mom [W, M, 4]) -> merged (idx, sim, feat, mom)."""
         idx_parts = _require_cuda(idx_parts, torch.int32, "idx_parts")

@@ -6,11 +6,20 @@ a device matrix of L2-normalised rows (re-registered lazily after additions) and
 ``query_similar`` is one ``tvc_bank_search`` call (fp32 bank -> split-bf16
 planes, fp32-grade cosines).  In scope: ``add_reference`` (admission check
 included), ``query_similar``, ``_compute_similarities``, size / FIFO-LRU-random
-eviction bookkeeping.  Out of scope (host bookkeeping off the q/s path,
-SURVEY.md 2.1 #4): KMeans / DBSCAN clustering and JSON persistence.
+eviction bookkeeping, and the KMeans clustering (``perform_clustering``,
+``query_by_cluster``, ``get_cluster_centers``, the ``auto_clustering`` hook and the
+cluster bookkeeping on eviction, ``src/ref_bank.py:226-339,429-450``): the raw
+vectors are registered under a second, temporary bank slot and clustered by
+``TVCEngine.kmeans`` (``tvc_kmeans_assign`` / ``tvc_kmeans_update``) with the
+reference's ``n_init=10``, seed 42.  The restarts draw their starting centres from
+numpy's generator, not sklearn's, so the clusters are a k-means optimum of the same
+data but not sklearn's own labelling.  Out of scope: DBSCAN clustering (the method
+is accepted by the config and fails as the reference's own ``except`` does: an
+error is logged and ``perform_clustering`` returns False) and JSON persistence.
 """
 from __future__ import annotations
 
+import logging
 import time
 from collections import deque
 from dataclasses import dataclass, field
@@ -21,6 +30,8 @@ import numpy as np
 import torch
 
 from .engine import TVCEngine
+
+logger = logging.getLogger(__name__)
 
 
 @dataclass
@@ -38,6 +49,8 @@ class ReferenceBankConfig:
     feature_dim: int = 512
 
     def __post_init__(self):
+        if self.clustering_method not in ("kmeans", "dbscan", "none"):
+            raise ValueError(f"unsupported clustering method: {self.clustering_method}")
         if self.update_strategy not in ("fifo", "lru", "random", "similarity"):
             raise ValueError(f"unsupported update strategy: {self.update_strategy}")
 
@@ -59,12 +72,16 @@ class ReferenceBank:
         self.config = config or ReferenceBankConfig()
         self.engine = engine or TVCEngine()
         self.references: List[ReferenceItem] = []
+        self.clusters: Dict[int, List[int]] = {}            # cluster id -> reference indices (src/ref_bank.py:98)
+        self.cluster_centers: Optional[np.ndarray] = None
+        self.cluster_init: Optional[np.ndarray] = None      # the starting centres of the restart the last clustering kept
         self.access_order: deque = deque()
         self._lock = Lock()
         self._dirty = True
         self._rng = rng or np.random.default_rng()
         self.bank_name = f"ref_bank:{id(self):x}"       # own bank slot on the (possibly shared) engine
-        self.stats = {"total_added": 0, "total_removed": 0, "total_queries": 0}
+        self.stats = {"total_added": 0, "total_removed": 0, "total_queries": 0, "clustering_count": 0,
+                      "last_clustering_time": None}
 
     def __len__(self) -> int:
         return len(self.references)
@@ -131,6 +148,8 @@ class ReferenceBank:
             self.references.append(ReferenceItem(np.array(vector, dtype=np.float64), dict(metadata), time.time()))
             self.stats["total_added"] += 1
             self._dirty = True
+            if self.config.auto_clustering and len(self.references) % self.config.clustering_interval == 0:   # :156-159
+                self._perform_clustering()
             return True
 
     def add_references(self, vectors: np.ndarray, metadatas: Optional[List[Dict[str, Any]]] = None) -> None:
@@ -154,9 +173,83 @@ class ReferenceBank:
         elif s == "random":
             idx = int(self._rng.integers(len(self.references)))
         self.references.pop(idx)
-        self.access_order = deque(i if i < idx else i - 1 for i in self.access_order if i != idx)
+        self._update_clusters_after_removal(idx)
         self.stats["total_removed"] += 1
         self._dirty = True
+
+    def _update_clusters_after_removal(self, removed_idx: int) -> None:
+        """src/ref_bank.py:429-460: indices above the removed one shift down, the removed one leaves its cluster, a
+        cluster left without members leaves the dict; the same for the LRU order."""
+        new_clusters = {}
+        for cluster_id, indices in self.clusters.items():
+            kept = [i if i < removed_idx else i - 1 for i in indices if i != removed_idx]
+            if kept:
+                new_clusters[cluster_id] = kept
+        self.clusters = new_clusters
+        self.access_order = deque(i if i < removed_idx else i - 1 for i in self.access_order if i != removed_idx)
+
+    # -- clustering -------------------------------------------------------------
+    def query_by_cluster(self, cluster_id: int, top_k: int = 10) -> List[ReferenceItem]:
+        """src/ref_bank.py:226-247: the first ``top_k`` members of a cluster in index order; [] for an unknown id."""
+        with self._lock:
+            if cluster_id not in self.clusters:
+                return []
+            return [self.references[i] for i in self.clusters[cluster_id][:top_k]]
+
+    def get_cluster_centers(self) -> Optional[np.ndarray]:
+        """src/ref_bank.py:249-257: a copy."""
+        with self._lock:
+            return self.cluster_centers.copy() if self.cluster_centers is not None else None
+
+    def perform_clustering(self, force: bool = False) -> bool:
+        """src/ref_bank.py:259-274: True when the references were clustered; failures are logged, never raised."""
+        try:
+            with self._lock:
+                return self._perform_clustering(force)
+        except Exception as e:
+            logger.error(f"clustering failed: {e}")
+            return False
+
+    def _perform_clustering(self, force: bool = False) -> bool:
+        """src/ref_bank.py:276-339 (lock held).  KMeans(n_clusters, random_state=42, n_init=10) over the RAW vectors
+        (:294, not the unit rows of the cosine search) becomes ``engine.kmeans`` over a temporary bank slot that holds
+        them zero-padded to the 64 multiple; its starting centres stay in ``self.cluster_init`` (fp64 [n_clusters, D])."""
+        if len(self.references) < 2:
+            return False
+        method = self.config.clustering_method
+        if method == "none":                 # without force :289-290; with force the method falls through to :317-318
+            return False
+        try:
+            if method != "kmeans":
+                raise NotImplementedError(f"clustering method {method!r} is not built on the GPU path")
+            D, Dp = self.config.feature_dim, self._padded_dim()
+            V = np.zeros((len(self.references), Dp), dtype=np.float32)
+            for i, r in enumerate(self.references):
+                V[i, :D] = r.vector
+            n_clusters = min(self.config.num_clusters, len(self.references))
+            name = self.bank_name + ":raw"
+            try:
+                self.engine.set_bank(torch.from_numpy(V).to(self.engine.device), name=name)
+                centres, labels, _, _, order, offsets = self.engine.kmeans(n_clusters, bank=name, n_init=10, seed=42, n_features=D)
+                init = self.engine.kmeans_last_init
+            finally:
+                self.engine.release_bank(name)
+            self.cluster_centers = centres[:, :D].double().cpu().numpy()
+            self.cluster_init = init[:, :D].double().cpu().numpy()
+            labels, order, offsets = labels.cpu().numpy(), order.cpu().numpy(), offsets.cpu().numpy()
+            self.clusters.clear()
+            for j in range(n_clusters):       # the member lists come grouped and ascending from the counting sort
+                if offsets[j + 1] > offsets[j]:
+                    self.clusters[j] = order[offsets[j]:offsets[j + 1]].tolist()
+            for i, r in enumerate(self.references):
+                r.cluster_id = int(labels[i]) if labels[i] >= 0 else None
+            self.stats["clustering_count"] += 1
+            self.stats["last_clustering_time"] = time.time()
+            logger.info(f"clustering done: {len(self.clusters)} clusters")
+            return True
+        except Exception as e:               # the reference's failure contract (:337-339)
+            logger.error(f"clustering failed: {e}")
+            return False
 
     def query_similar(self, query_vector: np.ndarray, top_k: int = 10,
                       similarity_threshold: Optional[float] = None) -> List[Tuple[ReferenceItem, float]]:
