@@ -16,6 +16,9 @@ A mask is a yes / no property, so it is read back exactly instead of being infer
                        decodes to it; a forbidden target (the nearest INVISIBLE rows) must leave the output equal to
                        ``model``, which never sees it.
 * ``sd_*``             the same two witnesses for the streaming kernel (separate q / k / v, n samples, any head dim).
+                       The needle does NOT check the streaming kernel's softmax VALUES: its 12-nat margin makes
+                       everything accumulated before a move of the reference e^-12 of the result, so a wrong rescale
+                       passes it.  That is tests/sd_attn_ref.py and tests/test_gpu_sd_attention_values.py.
 
 ``kernel`` arguments are callables ``qkv fp32 [rows, 3 * width] -> out [output rows, width]`` (any float dtype); every
 probe value is exact in bf16 and fp16.
