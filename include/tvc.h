@@ -357,6 +357,57 @@ int tvc_kmeans_update(tvc_handle* h, const int32_t* labels_dev, const float* cen
                       float* centroids_out_dev, int32_t* counts_dev, int32_t* offsets_dev, int32_t* order_dev,
                       void* stream);
 
+/* ---- IVF search: probe + list scan over a bank slot ------------------------------------------------ */
+
+/* An IVF index over R rows is four things:
+ *   centroids     fp32 [nlist, D]
+ *   the rows      stored IN LIST ORDER in a bank slot (tvc_bank_set of bank[order]; bf16 or fp32)
+ *   list_offsets  int32 [nlist + 1]: list l = the stored rows [list_offsets[l], list_offsets[l + 1]); empty lists are legal
+ *   row_ids       int32 [R]: the original index of every stored row, ascending inside a list (the `order` of
+ *                 tvc_kmeans_update's stable counting sort); NULL = identity
+ * Probe: the nprobe lists of a query are the nprobe largest q . c - |c|^2 / 2, ties to the lower list id, NaN scores never
+ * win -- the score and order of tvc_kmeans_assign, so a row sits in the list this rule ranks first for it.
+ * Scan: the exact top-k by inner product of the query with the rows of its probed lists, in tvc_bank_search's contract:
+ * global index = row_ids[pos] + idx_offset, order (similarity desc, index asc by ORIGINAL index), -1 / -inf padded when the
+ * probed lists hold fewer than k rows, NaN similarities never returned.  No moments: they are defined over all R rows.
+ * Together they replace faiss.IndexIVFFlat.search (src/retrieval.py:101-103,496-498, retrieval_ref.py:141-160,
+ * scripts/build_faiss_indices.py:139-142).  DIFFERENCE from the reference: it builds IndexIVFFlat(IndexFlatIP(d), d, nlist)
+ * without a metric argument, so its in-list distances are squared L2, ascending, which its callers read as similarities.  On
+ * unit rows the ranking is the same (d^2 = 2 - 2 cos); this library returns the cosines, as the flat search does, so the
+ * callers' thresholds keep their meaning.
+ * Both calls enqueue and return (no host synchronisation); a refusal launches nothing and allocates nothing. */
+
+/* The nprobe best lists of every query row; needs no bank.
+ *   rows_dev       fp32 [M, D], D % 64 == 0
+ *   centroids_dev  fp32 [nlist, D]
+ *   lists_dev      int32 [M, nprobe]: list ids, best first.  nprobe is clamped to nlist as faiss does: the ranks from nlist
+ *                  on (and the ranks a query with NaN scores cannot fill) are -1, which tvc_ivf_scan skips
+ *   score_dev      fp32 [M, nprobe] or NULL: the scores (-inf where lists_dev is -1)
+ * TVC_E_INVALID: nprobe outside 1..TVC_MAX_TOPK, nlist outside 1..65536, D <= 0 or D % 64 != 0, M < 0, a NULL required buffer. */
+int tvc_ivf_probe(tvc_handle* h, const float* rows_dev, int32_t M, int32_t D,
+                  const float* centroids_dev, int32_t nlist, int32_t nprobe,
+                  int32_t* lists_dev, float* score_dev, void* stream);
+
+/* Exact top-k over the probed lists of the SELECTED slot, whose rows are stored in list order.
+ *   rows_dev        fp32 [M, D], D = the slot's
+ *   probes_dev      int32 [M, nprobe]: list ids, -1 (any id outside [0, nlist)) = skip; a list named twice in one row is
+ *                   the caller's error
+ *   max_list_rows   the longest list, known to whoever built the index.  A probed list that is longer is read up to its
+ *                   first max_list_rows rows AND raises the overflow word: tvc_bank_status then reports TVC_E_OVERFLOW
+ *                   (never a silent truncation)
+ *   topk_idx_dev    int32 [M, k], topk_sim_dev fp32 [M, k]
+ *   topk_pos_dev    int32 [M, k] or NULL: the stored position of each result (what tvc_bank_gather takes), -1 in the padding
+ * The similarities of a chunk of queries with their probed lists go through a score workspace of at most 256 MiB
+ * (nprobe x round_up(max_list_rows, 16) floats per query); the queries are chunked to fit.
+ * TVC_E_STATE: the selected slot holds no bank rows.  TVC_E_INVALID: k or nprobe outside 1..TVC_MAX_TOPK, nlist outside
+ * 1..65536, max_list_rows < 1, M < 0, a NULL required buffer, a slot whose D is not one of {128, 512, 768} (the widths the
+ * row stream covers), or nprobe x round_up(max_list_rows, 16) x 4 bytes above the 256 MiB workspace. */
+int tvc_ivf_scan(tvc_handle* h, const float* rows_dev, int32_t M, int32_t k,
+                 const int32_t* probes_dev, int32_t nprobe,
+                 const int32_t* list_offsets_dev, int32_t nlist, int32_t max_list_rows,
+                 const int32_t* row_ids_dev, int64_t idx_offset,
+                 int32_t* topk_idx_dev, float* topk_sim_dev, int32_t* topk_pos_dev, void* stream);
+
 /* All-pairs cosine matrix out[n, m] = cos(x[n], y[m]), fp32-grade (both sides
  * L2-normalised on device, split into bf16 (hi, lo) planes, three MFMA products).
  * x fp32 [N, D], y fp32 [M, D], out fp32 [N, M]; D % 64 == 0.

@@ -15,7 +15,7 @@ from .arch import ARCHS, ClipArch, Tower, get_arch
 from .clip import CLIPConfig, CLIPModel
 from .detector import (AdversarialDetector, ConsistencyChecker, DetectionConfig, DetectorConfig,
                        MultiModalDefenseDetector, aggregate_scores, create_adversarial_detector, unpack_records)
-from .engine import ConsistencyConfig, TVCEngine
+from .engine import ConsistencyConfig, IVFIndex, TVCEngine
 from .metrics import DetectionEvaluator, DetectionMetrics, SimilarityCalculator
 from .pipeline import (DefensePipeline, MultiModalDetectionPipeline, PipelineConfig, PipelineProfiler,
                        PipelineResult, create_defense_pipeline, create_detection_pipeline)

@@ -129,6 +129,8 @@ SIGNATURES = {
     "tvc_bank_gather": (C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, _P]),
     "tvc_kmeans_assign": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P]),
     "tvc_kmeans_update": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    "tvc_ivf_probe": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P]),
+    "tvc_ivf_scan": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P, _P]),
     "tvc_topk_merge": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                  _P, _P, _P, _P, _P]),
     "tvc_cosine_matrix": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),

@@ -2,7 +2,7 @@
 // units that implement the C-ABI (tvc_abi.cpp: the CLIP tower encode drivers of every precision mode and the bf16 /
 // fp16 towers, bank, consistency; tvc_precise.cpp: the fp32-grade towers' stem, layer loop and head; tvc_split.cpp: the
 // split-bf16 towers' stem, layer loop, head and weight planes; tvc_sd.cpp: latent-diffusion reference generator;
-// tvc_kmeans.cpp: k-means over a bank slot).
+// tvc_kmeans.cpp: k-means over a bank slot; tvc_ivf.cpp: IVF probe and list scan).
 #pragma once
 #include "../../include/tvc.h"
 #include "kernels.hpp"
@@ -36,6 +36,10 @@ enum Slot {
     // k-means over a bank slot (tvc_kmeans.cpp): centre planes, half norms, counting-sort counters, offsets / order when the
     // caller does not ask for them
     WS_KM_CPLANES, WS_KM_HALFNORM, WS_KM_BLKCNT, WS_KM_OFFSETS, WS_KM_ORDER,
+    // IVF search (tvc_ivf.cpp): the probe's centroid / query planes, half norms and score rows; the scan's query planes, the
+    // counting sort of its (query, probe) pairs and the score buffer
+    WS_IVF_CPLANES, WS_IVF_PQPLANES, WS_IVF_HALFNORM, WS_IVF_SIMS,
+    WS_IVF_QPLANES, WS_IVF_BLKCNT, WS_IVF_PCOUNTS, WS_IVF_POFFSETS, WS_IVF_PORDER, WS_IVF_SCORES,
     WS_COUNT
 };
 

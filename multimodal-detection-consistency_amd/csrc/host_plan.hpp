@@ -70,6 +70,60 @@ inline void kmeans_update_plan(int64_t R, int K, int* nblocks, int* rows_per_blo
     *nblocks = (int)((R + *rows_per_block - 1) / *rows_per_block > 0 ? (R + *rows_per_block - 1) / *rows_per_block : 1);
 }
 
+// IVF scan (ivf.hip): the scan writes every (query, probe) pair's similarities with the rows of its list into a score buffer
+// [pairs, pitch] fp32, pitch = round_up(max_list_rows, 16); the queries are cut into chunks so that the buffer of a chunk
+// stays under IVF_SCORE_BUDGET (256 MiB: 4 608 queries x 10 probes x lists of up to 1 450 rows go in one chunk).  A single
+// query whose nprobe x pitch floats exceed the budget is refused (ok = false): the scan never truncates.
+#define IVF_SCORE_BUDGET ((int64_t)256 << 20)
+#define IVF_CHUNK_ROWS 512              // a work item = (list, chunk of <= 512 rows): the split rule for skewed lists
+#define IVF_LDS_BYTES (160 * 1024)
+#define IVF_MAX_NLIST 65536
+#define IVF_MAX_GRID_CHUNKS 1024        // row chunks of a list on the grid's y; a longer list's items loop
+#define IVF_SELECT_LDS_FLOATS 32768     // the select pass keeps a query's segments in LDS when nprobe * pitch fits this
+#define IVF_PROBE_SIMS_FLOATS ((int64_t)16 << 20)   // the probe's [chunk, nlist] score workspace: 64 MiB
+inline bool ivf_scan_covers(int D) { return D == 128 || D == 512 || D == 768; }      // the D of the skinny stream
+struct IvfScanPlan {
+    bool ok = false;
+    int64_t pitch = 0;                  // floats per (query, probe) pair
+    int chunk = 0, n_chunks = 0;        // queries per chunk, chunks
+    int group = 0;                      // pairs per LDS image: both query planes of `group` queries fit IVF_LDS_BYTES
+    int nqt = 0;                        // 16-query tiles per image the kernel is instantiated with: 1, 2 or 4, <= group / 16
+    int grid_lists = 0, grid_chunks = 0;// the scan's grid
+    int sort_blocks = 0, sort_rows_per_block = 0;    // the counting sort of a full chunk's pairs (kmeans_update_plan)
+    size_t scan_lds = 0, select_lds = 0;// dynamic LDS bytes of the two kernels
+    int64_t score_bytes = 0;            // of one chunk
+};
+inline IvfScanPlan ivf_scan_plan(int M, int nprobe, int nlist, int64_t max_list_rows, int D, int bank_planes) {
+    IvfScanPlan p;
+    if (M < 1 || nprobe < 1 || nprobe > 128 || nlist < 1 || nlist > IVF_MAX_NLIST || max_list_rows < 1 ||
+        max_list_rows > 0x7fffffffLL || !ivf_scan_covers(D) || bank_planes < 1 || bank_planes > 2)
+        return p;
+    p.pitch = (max_list_rows + 15) / 16 * 16;
+    const int64_t per_query = (int64_t)nprobe * p.pitch * 4;
+    if (per_query > IVF_SCORE_BUDGET) return p;
+    int64_t mc = IVF_SCORE_BUDGET / per_query;
+    if (mc > M) mc = M;
+    p.chunk = (int)mc;
+    p.n_chunks = (int)(((int64_t)M + mc - 1) / mc);
+    p.score_bytes = mc * per_query;
+    const int qpitch = 4 * D + 16;      // both planes of a query row + the 16 bytes that keep the fragment reads conflict-free
+    p.group = 64;
+    while (p.group > 16 && p.group * qpitch > IVF_LDS_BYTES) p.group /= 2;
+    // a list is read by at most one pair per query of the chunk
+    const int need = (int)((mc + 15) / 16);
+    p.nqt = need >= 3 ? 4 : need;
+    if (p.nqt > p.group / 16) p.nqt = p.group / 16;
+    p.scan_lds = (size_t)p.nqt * 16 * qpitch;
+    p.grid_lists = nlist;
+    int64_t gc = (max_list_rows + IVF_CHUNK_ROWS - 1) / IVF_CHUNK_ROWS;
+    if (gc > IVF_MAX_GRID_CHUNKS) gc = IVF_MAX_GRID_CHUNKS;
+    p.grid_chunks = (int)gc;
+    kmeans_update_plan(mc * nprobe, nlist, &p.sort_blocks, &p.sort_rows_per_block);
+    p.select_lds = (int64_t)nprobe * p.pitch <= IVF_SELECT_LDS_FLOATS ? (size_t)nprobe * p.pitch * 4 : 0;
+    p.ok = true;
+    return p;
+}
+
 // GroupNorm statistics slabs: small slabs = many workgroups (the pass is latency-bound on few), at most 1024 slabs per image
 inline int gn_slab_tokens(int HW) { int s = 64; while ((HW + s - 1) / s > 1024) s *= 2; return s; }
 // ws: >= n * nslab * groups * 2 + n * groups * 2 floats

@@ -178,6 +178,60 @@ struct KmeansUpdateLaunch {
     int32_t* order = nullptr;         // [R]: row indices grouped by cluster, ascending inside a cluster
 };
 hipError_t launch_kmeans_update(const KmeansUpdateLaunch& L, hipStream_t stream);
+// halfnorm[k] = |c_k|^2 / 2, k < K; NaN for K <= k < Kpad
+hipError_t launch_kmeans_halfnorm(const float* centroids, int D, int K, int Kpad, float* halfnorm, hipStream_t stream);
+// the update's stable counting sort on its own: the indices 0 .. R - 1 grouped by label
+struct LabelSortLaunch {
+    const int32_t* labels = nullptr;  // [R]; labels outside [0, K) are in no group
+    int64_t R = 0;
+    int K = 0;
+    int nblocks = 0, rows_per_block = 0;   // kmeans_update_plan
+    int32_t* blk_cnt = nullptr;       // workspace [nblocks, K]
+    int32_t* counts = nullptr;        // [K]
+    int32_t* offsets = nullptr;       // [K + 1]
+    int32_t* order = nullptr;         // [R]: entries [0, offsets[K]) are written
+};
+hipError_t launch_label_sort(const LabelSortLaunch& L, hipStream_t stream);
+
+// ---- ivf.hip: inverted-file search (probe: the nprobe best lists of a query; scan: exact top-k over the probed lists)
+struct IvfProbeLaunch {
+    const uint16_t* cplanes = nullptr;// [nlist, 2 * D] bf16 (hi | lo) planes of the centroids
+    const uint16_t* qplanes = nullptr;// [M, 2 * D] bf16 (hi | lo) planes of the queries
+    const float* centroids = nullptr; // [nlist, D] fp32
+    float* halfnorm = nullptr;        // workspace [nlist]: |c|^2 / 2
+    int M = 0, D = 0, nlist = 0, nprobe = 0;
+    int chunk = 0;                    // queries per GEMM (the rows of sims)
+    float* sims = nullptr;            // workspace [chunk, nlist]
+    int32_t* lists = nullptr;         // [M, nprobe]: list ids, best first; -1 from the first rank that has no list
+    float* score = nullptr;           // [M, nprobe] or nullptr: q.c - |c|^2 / 2; -inf where lists is -1
+};
+hipError_t launch_ivf_probe(const IvfProbeLaunch& L, hipStream_t stream);
+struct IvfScanLaunch {
+    const uint16_t* bank = nullptr;   // [R, ldb] bf16 planes of the rows in list order
+    int64_t ldb = 0;
+    int64_t R = 0;
+    int D = 0;
+    int bank_planes = 1;
+    const uint16_t* qplanes = nullptr;// [M, 2 * D] query planes
+    int M = 0, k = 0, nprobe = 0, nlist = 0, max_list_rows = 0;
+    const int32_t* probes = nullptr;  // [M, nprobe]
+    const int32_t* list_offsets = nullptr;   // [nlist + 1]
+    const int32_t* row_ids = nullptr; // [R] or nullptr (identity)
+    int64_t idx_offset = 0;
+    IvfScanPlan plan;                 // ivf_scan_plan
+    // workspace
+    int32_t* blk_cnt = nullptr;       // [plan.sort_blocks, nlist]
+    int32_t* pair_counts = nullptr;   // [nlist]
+    int32_t* pair_offsets = nullptr;  // [nlist + 1]
+    int32_t* pair_order = nullptr;    // [plan.chunk * nprobe]
+    float* scores = nullptr;          // [plan.chunk * nprobe, plan.pitch]
+    int32_t* overflow = nullptr;      // [1]: bit 2 = a probed list was longer than max_list_rows
+    // outputs
+    int32_t* topk_idx = nullptr;
+    float* topk_sim = nullptr;
+    int32_t* topk_pos = nullptr;      // or nullptr
+};
+hipError_t launch_ivf_scan(const IvfScanLaunch& L, hipStream_t stream);
 
 // ---- consistency.hip
 struct ConsistencyParams {

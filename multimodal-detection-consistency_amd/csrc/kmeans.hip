@@ -15,7 +15,8 @@
 //           scan over the blocks, an exclusive scan over the clusters, a STABLE scatter (rank inside a 256-row chunk by
 //           comparison, chunks in order) -- gives the member lists in ascending row order; one workgroup per cluster then
 //           sums its members in a fixed order in fp32.  No floating-point atomics: the centres are a pure function of
-//           (bank, labels).
+//           (bank, labels).  The sort is a launch of its own (launch_label_sort): ivf.hip groups (query, probe) pairs by list
+//           with it, and takes the half norms of its centroids from kmeans_halfnorm_kernel.
 #include "gemm_core.hpp"
 #include "kernels.hpp"
 #include "launch.hpp"
@@ -133,12 +134,16 @@ __global__ __launch_bounds__(GEMM_THREADS) void kmeans_assign_kernel(GemmOperand
     }
 }
 
+hipError_t launch_kmeans_halfnorm(const float* centroids, int D, int K, int Kpad, float* halfnorm, hipStream_t stream) {
+    return launch<kmeans_halfnorm_kernel>(dim3((Kpad + 3) / 4), dim3(256), 0, stream, centroids, D, K, Kpad, halfnorm);
+}
+
 hipError_t launch_kmeans_assign(const KmeansAssignLaunch& L, hipStream_t stream) {
     if (L.R < 1 || L.R > 0x7fffffffLL || L.K < 1 || L.D < 64 || L.D % 64 != 0 || L.bank_planes < 1 || L.bank_planes > 2)
         return hipErrorInvalidValue;
     const int n_ctiles = (L.K + GEMM_BM - 1) / GEMM_BM;
     const int Kpad = n_ctiles * GEMM_BM;
-    hipError_t st = launch<kmeans_halfnorm_kernel>(dim3(Kpad / 4), dim3(256), 0, stream, L.centroids, L.D, L.K, Kpad, L.halfnorm);
+    hipError_t st = launch_kmeans_halfnorm(L.centroids, L.D, L.K, Kpad, L.halfnorm, stream);
     if (st != hipSuccess) return st;
     if (L.dist2) {
         int64_t grid = (L.R + 3) / 4;
@@ -301,9 +306,11 @@ __global__ __launch_bounds__(256) void kmeans_centroid_kernel(const uint16_t* __
     }
 }
 
-hipError_t launch_kmeans_update(const KmeansUpdateLaunch& L, hipStream_t stream) {
-    if (L.R < 1 || L.R > 0x7fffffffLL || L.K < 1 || L.D < 64 || L.D % 64 != 0 || L.bank_planes < 1 || L.bank_planes > 2 ||
-        L.nblocks < 1 || L.rows_per_block < 1 || (int64_t)L.nblocks * L.rows_per_block < L.R)
+// the stable counting sort alone: the indices 0 .. R - 1 grouped by label (ascending inside a label) -> order, offsets, counts.
+// The k-means update sorts bank rows by cluster; the IVF scan (ivf.hip) sorts (query, probe) pairs by the list they read.
+hipError_t launch_label_sort(const LabelSortLaunch& L, hipStream_t stream) {
+    if (L.R < 1 || L.R > 0x7fffffffLL || L.K < 1 || L.nblocks < 1 || L.rows_per_block < 1 ||
+        (int64_t)L.nblocks * L.rows_per_block < L.R)
         return hipErrorInvalidValue;
     hipError_t st = hipMemsetAsync(L.blk_cnt, 0, (size_t)L.nblocks * L.K * 4, stream);
     if (st != hipSuccess) return st;
@@ -313,8 +320,18 @@ hipError_t launch_kmeans_update(const KmeansUpdateLaunch& L, hipStream_t stream)
     if (st != hipSuccess) return st;
     st = launch<kmeans_offsets_kernel>(dim3(1), dim3(1024), 0, stream, (const int32_t*)L.counts, L.K, (L.K + 1023) / 1024, L.offsets);
     if (st != hipSuccess) return st;
-    st = launch<kmeans_scatter_kernel>(dim3(L.nblocks), dim3(256), 0, stream, L.labels, L.R, L.K, L.rows_per_block, L.blk_cnt,
-                                       (const int32_t*)L.offsets, L.order);
+    return launch<kmeans_scatter_kernel>(dim3(L.nblocks), dim3(256), 0, stream, L.labels, L.R, L.K, L.rows_per_block, L.blk_cnt,
+                                         (const int32_t*)L.offsets, L.order);
+}
+
+hipError_t launch_kmeans_update(const KmeansUpdateLaunch& L, hipStream_t stream) {
+    if (L.R < 1 || L.R > 0x7fffffffLL || L.K < 1 || L.D < 64 || L.D % 64 != 0 || L.bank_planes < 1 || L.bank_planes > 2 ||
+        L.nblocks < 1 || L.rows_per_block < 1 || (int64_t)L.nblocks * L.rows_per_block < L.R)
+        return hipErrorInvalidValue;
+    LabelSortLaunch S;
+    S.labels = L.labels; S.R = L.R; S.K = L.K; S.nblocks = L.nblocks; S.rows_per_block = L.rows_per_block;
+    S.blk_cnt = L.blk_cnt; S.counts = L.counts; S.offsets = L.offsets; S.order = L.order;
+    hipError_t st = launch_label_sort(S, stream);
     if (st != hipSuccess) return st;
     return launch<kmeans_centroid_kernel>(dim3(L.K), dim3(256), 0, stream, L.bank, L.ldb, L.bank_planes, L.D, (const int32_t*)L.order,
                                           (const int32_t*)L.offsets, L.centroids_in, L.centroids_out);

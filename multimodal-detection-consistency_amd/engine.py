@@ -41,6 +41,22 @@ class ConsistencyConfig:
         return p
 
 
+@dataclass
+class IVFIndex:
+    """An inverted-file index built by ``TVCEngine.ivf_build``: the centroids, the list layout and the bank slot ``name``
+    of the engine, which holds the bank rows in list order and belongs to the index (``TVCEngine.ivf_release`` frees it).
+    List l = the stored rows ``offsets[l]:offsets[l + 1]``; ``ids[p]`` = the original row index of stored row p, ascending
+    inside a list."""
+    name: str
+    nlist: int
+    centroids: torch.Tensor      # fp32 [nlist, D]
+    offsets: torch.Tensor        # int32 [nlist + 1]
+    ids: torch.Tensor            # int32 [rows]
+    max_list_rows: int
+    rows: int
+    dim: int
+
+
 def _stream() -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -587,6 +603,106 @@ class TVCEngine:
         _, _, offsets, order = self.kmeans_update(labels, Cc, bank=bank, want_lists=True)
         return Cc, labels, inertia, n_iter, order, offsets
 
+    # ---- IVF search over a bank slot in list order -------------------------
+    def ivf_probe(self, rows: torch.Tensor, centroids: torch.Tensor, nprobe: int):
+        """rows fp32 [M, D], centroids fp32 [nlist, D] -> (lists int32 [M, nprobe], score fp32 [M, nprobe]): the nprobe
+        lists with the largest q.c - |c|^2 / 2, best first, ties to the lower list id (``kmeans_assign``'s rule).  Ranks
+        beyond nlist, or that only NaN scores could fill, are -1 / -inf."""
+        if not 1 <= nprobe <= _lib.TVC_MAX_TOPK:
+            raise ValueError(f"nprobe must be in [1, {_lib.TVC_MAX_TOPK}] (got {nprobe})")
+        rows = _require_cuda(rows, torch.float32, "rows")
+        centroids = _require_cuda(centroids, torch.float32, "centroids")
+        if rows.dim() != 2 or centroids.dim() != 2 or rows.shape[1] != centroids.shape[1]:
+            raise ValueError(f"rows [M, D] and centroids [nlist, D] must share D (got {tuple(rows.shape)}, {tuple(centroids.shape)})")
+        M, D = rows.shape
+        lists = torch.empty((M, nprobe), dtype=torch.int32, device=self.device)
+        score = torch.empty((M, nprobe), dtype=torch.float32, device=self.device)
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.tvc_ivf_probe(self.handle, _ptr(rows), M, D, _ptr(centroids), centroids.shape[0], nprobe,
+                                               _ptr(lists), _ptr(score), _stream()))
+        return lists, score
+
+    def ivf_scan(self, rows: torch.Tensor, k: int, probes: torch.Tensor, index: "IVFIndex", idx_offset: int = 0):
+        """rows fp32 [M, D], probes int32 [M, nprobe] (-1 = skip) -> (idx int32 [M, k], sim fp32 [M, k], pos int32 [M, k]):
+        the exact top-k of every query over the rows of its probed lists, in ``bank_search``'s contract (idx = the original
+        row index + idx_offset, (sim desc, idx asc), -1 / -inf padded); ``pos`` is the stored position, what
+        ``bank_gather(pos, bank=index.name)`` takes.  A probed list longer than ``index.max_list_rows`` shows in
+        ``bank_status()`` as TVC_E_OVERFLOW."""
+        if not 1 <= k <= _lib.TVC_MAX_TOPK:
+            raise ValueError(f"top-k must be in [1, {_lib.TVC_MAX_TOPK}] (got {k}): tvc_ivf_scan never truncates silently")
+        rows = _require_cuda(rows, torch.float32, "rows")
+        probes = _require_cuda(probes, torch.int32, "probes")
+        M = rows.shape[0]
+        if probes.dim() != 2 or probes.shape[0] != M:
+            raise ValueError(f"probes must be [{M}, nprobe] (got {tuple(probes.shape)})")
+        idx = torch.empty((M, k), dtype=torch.int32, device=self.device)
+        sim = torch.empty((M, k), dtype=torch.float32, device=self.device)
+        pos = torch.empty((M, k), dtype=torch.int32, device=self.device)
+        with self._lock, torch.cuda.device(self.device):
+            b = self._select(index.name)
+            if rows.dim() != 2 or rows.shape[1] != b["dim"]:
+                raise ValueError(f"rows must be [M, {b['dim']}] (got {tuple(rows.shape)})")
+            self._check(self.lib.tvc_ivf_scan(self.handle, _ptr(rows), M, k, _ptr(probes), probes.shape[1], _ptr(index.offsets),
+                                              index.nlist, index.max_list_rows, _ptr(index.ids), idx_offset, _ptr(idx), _ptr(sim),
+                                              _ptr(pos), _stream()))
+        return idx, sim, pos
+
+    def ivf_search(self, rows: torch.Tensor, k: int, nprobe: int, index: "IVFIndex", idx_offset: int = 0):
+        """``ivf_probe`` (nprobe clamped to nlist, as faiss does) + ``ivf_scan`` -> (idx, sim, pos); no host synchronisation."""
+        lists, _ = self.ivf_probe(rows, index.centroids, max(1, min(int(nprobe), index.nlist)))
+        return self.ivf_scan(rows, k, lists, index, idx_offset)
+
+    def ivf_build(self, bank: torch.Tensor, nlist: int, name: str, train_rows: Optional[int] = None, max_iter: int = 10,
+                  seed: int = 1234) -> "IVFIndex":
+        """Train ``nlist`` centroids on ``bank`` [R, D] (bf16 or fp32), store the rows in list order under the bank slot
+        ``name`` (which the index then owns) and return the ``IVFIndex``.
+
+        faiss's level-1 training (``IndexIVFFlat.train`` -> ``Clustering``: niter = 10, seed 1234, at most 256 points
+        per centroid, random distinct rows as the start) as far as ``TVCEngine.kmeans`` allows: k-means with
+        ``init="random"``, ``n_init=1``, ``max_iter`` iterations on at most ``train_rows`` (default 256 * nlist) rows.
+        Where it differs: the subsample and the start are drawn with the seeded numpy generator
+        (``default_rng(seed)``), not faiss's own; the loop may stop early by sklearn's rule; an empty cluster takes the
+        farthest row instead of splitting a big cluster.  One assign + update over ALL rows then gives the lists.  Two
+        builds with the same arguments are bit-identical."""
+        import numpy as np
+        if bank.dim() != 2:
+            raise ValueError("bank must be [R, D]")
+        if bank.dtype not in (torch.bfloat16, torch.float32):
+            bank = bank.float()
+        bank = _require_cuda(bank, bank.dtype, "bank")
+        R = bank.shape[0]
+        if not 1 <= nlist <= min(R, 65536):
+            raise ValueError(f"need 1 <= nlist <= min(R, 65536) (got nlist = {nlist}, R = {R})")
+        n_train = min(R, int(train_rows) if train_rows else 256 * nlist)
+        if n_train < nlist:
+            raise ValueError(f"train_rows = {n_train} is fewer than nlist = {nlist}")
+        tmp = name + ":ivf-train"
+        try:
+            if n_train < R:
+                sel = np.sort(np.random.default_rng(seed).choice(R, n_train, replace=False))
+                self.set_bank(bank[torch.from_numpy(sel).to(self.device)], name=tmp)
+            else:
+                self.set_bank(bank, name=tmp)
+            centroids = self.kmeans(nlist, bank=tmp, init="random", n_init=1, max_iter=max_iter, seed=seed)[0]
+        finally:
+            self.release_bank(tmp)
+        try:
+            self.set_bank(bank, name=name)
+            labels, _, _ = self.kmeans_assign(centroids, bank=name)
+            _, counts, offsets, order = self.kmeans_update(labels, centroids, bank=name, want_lists=True)
+            n_in = int(offsets[-1].item())             # rows whose scores are all NaN are in no list
+            ids = order[:n_in].contiguous()
+            self.set_bank(bank[ids.long()], name=name)
+        except Exception:
+            self.release_bank(name)
+            raise
+        return IVFIndex(name=name, nlist=nlist, centroids=centroids.contiguous(), offsets=offsets, ids=ids,
+                        max_list_rows=max(1, int(counts.max().item())), rows=n_in, dim=bank.shape[1])
+
+    def ivf_release(self, index: "IVFIndex") -> None:
+        """Free the bank slot the index owns."""
+        self.release_bank(index.name)
+
     def topk_merge(self, idx_parts, sim_parts, feat_parts=None, mom_parts=None):
         """parts [W, M, k] (+ feat [W, M, kf, D], mom [W, M, 4]) -> merged (idx, sim, feat, mom)."""
         idx_parts = _require_cuda(idx_parts, torch.int32, "idx_parts")
@@ -632,11 +748,19 @@ class TVCEngine:
         return rec
 
     def detect_embeddings(self, img: torch.Tensor, txt: torch.Tensor, cfg: ConsistencyConfig,
-                          use_bank: bool = True, robust: bool = False, bank: str = DEFAULT_BANK) -> torch.Tensor:
+                          use_bank: bool = True, robust: bool = False, bank: str = DEFAULT_BANK,
+                          ivf: Optional["IVFIndex"] = None, nprobe: int = 1) -> torch.Tensor:
         """Bank search of the text rows -> gather -> consistency; all on the current stream.
         ``robust=False``: no host synchronisation, the caller checks ``bank_status()`` later;
-        ``robust=True``: synchronises once and falls back to the brute-force search on overflow."""
+        ``robust=True``: synchronises once and falls back to the brute-force search on overflow.
+        ``ivf``: search the ``nprobe`` nearest lists of that index instead of the whole bank (``ivf_search``; the rows
+        are gathered from the index's slot by stored position); ``bank`` / ``robust`` are then not used."""
         B, N1, D = txt.shape
+        if use_bank and ivf is not None and ivf.rows > 0:
+            k = max(cfg.search_k, cfg.reference_count)
+            idx, sim, pos = self.ivf_search(txt.reshape(B * N1, D), k, nprobe, ivf)
+            feat = self.bank_gather(pos[:, :cfg.reference_count].contiguous(), bank=ivf.name)
+            return self.consistency(img, txt, cfg, idx, sim, feat)
         if use_bank and self.bank_size(bank) > 0:
             k = max(cfg.search_k, cfg.reference_count)
             search = self.bank_search_robust if robust else self.bank_search

@@ -2,12 +2,22 @@
 (``src/retrieval.py:316``) and ``RetrievalReferenceGenerator``
 (``experiments/defenses/retrieval_ref.py:34``).  FAISS ``IndexFlatIP`` /
 ``index_cpu_to_gpu`` (``src/retrieval.py:100-112``) is replaced by the fused
-exact top-k kernel behind ``tvc_bank_search``; IVF / HNSW approximations are not
-needed (the search is exact at 1M-10M rows).
+exact top-k kernel behind ``tvc_bank_search``, which stays the default of both
+classes.  ``faiss.IndexIVFFlat`` (``src/retrieval.py:101-103,496-498``,
+``retrieval_ref.py:141-160``) is ``TVCEngine.ivf_build`` + ``ivf_search``: k-means
+lists over the bank, a probe of the ``nprobe`` nearest lists and an exact top-k
+inside them.  One difference from the reference is deliberate: it builds
+``IndexIVFFlat(IndexFlatIP(d), d, nlist)`` without a metric argument, so its
+in-list distances are squared L2 (ascending) which its callers read as
+similarities; on unit rows the ranking is the same (d^2 = 2 - 2 cos) and this
+path returns the cosines, as the flat search does, so thresholds keep their
+meaning.  HNSW is not built: it falls back to the exact search with a warning,
+as does a feature width the list scan does not cover (it covers 128, 512, 768).
 """
 from __future__ import annotations
 
 import json
+import logging
 import time
 from dataclasses import dataclass
 from pathlib import Path
@@ -18,6 +28,27 @@ import torch
 
 from .clip import CLIPConfig, CLIPModel
 
+logger = logging.getLogger(__name__)
+IVF_DIMS = (128, 512, 768)          # the widths tvc_ivf_scan covers
+_warned = set()
+
+
+def _ivf_wanted(index_type: str, dim: int, rows: int) -> bool:
+    """True when ``index_type`` asks for an IVF index that can be built; HNSW and an uncovered width fall back to the
+    exact search with ONE logged warning each."""
+    t = index_type.lower()
+    why = None
+    if "hnsw" in t:
+        why = f"index type {index_type!r} is not built"
+    elif "ivf" in t and dim not in IVF_DIMS:
+        why = f"the IVF list scan covers D in {IVF_DIMS}, not D = {dim}"
+    if why is not None:
+        if why not in _warned:
+            _warned.add(why)
+            logger.warning(f"{why}: falling back to the exact search")
+        return False
+    return "ivf" in t and rows > 0
+
 
 @dataclass
 class RetrievalConfig:
@@ -27,9 +58,10 @@ class RetrievalConfig:
     batch_size: int = 256
     top_k: int = 10
     similarity_metric: str = "cosine"     # cosine, dot_product, euclidean
-    index_type: str = "faiss"             # accepted for compatibility; the search is always exact
-    faiss_index_type: str = "IndexFlatIP"
+    index_type: str = "faiss"             # accepted for compatibility; faiss_index_type picks the search
+    faiss_index_type: str = "IndexFlatIP" # "IndexIVFFlat": an IVF index of n_clusters lists; "IndexHNSWFlat": exact + a warning
     n_clusters: int = 100
+    nprobe: int = 1                       # lists probed per query (faiss's default; src/retrieval.py never sets it)
     enable_cache: bool = True
     cache_dir: Optional[str] = None
     normalize_features: bool = True
@@ -51,6 +83,7 @@ class MultiModalRetriever:
         self.retrieval_cache: Dict[str, Tuple[List[str], List[float]]] = {}
         self._bank_is = None        # "image" / "text": which index lives on the engine
         self.bank_name = f"retriever:{id(self):x}"      # this retriever's own bank slot on the (shared) engine
+        self._ivf = None            # the IVFIndex that owns the slot instead of a flat bank (faiss_index_type "IndexIVFFlat")
 
     def __del__(self):          # give the bank slot back to the shared engine
         try:
@@ -61,7 +94,13 @@ class MultiModalRetriever:
     # -- index construction (src/retrieval.py:372-432, scripts/build_faiss_indices.py:59-158)
     def _set_bank(self, feats: torch.Tensor, kind: str) -> None:
         dt = torch.bfloat16 if self.config.bank_dtype == "bfloat16" else torch.float32
-        self.clip_model.engine.set_bank(feats.to(self.clip_model.device, dt), name=self.bank_name)
+        eng = self.clip_model.engine
+        rows = feats.to(self.clip_model.device, dt)
+        self._ivf = None
+        if _ivf_wanted(self.config.faiss_index_type, rows.shape[1], rows.shape[0]):
+            self._ivf = eng.ivf_build(rows, min(self.config.n_clusters, rows.shape[0]), self.bank_name)   # :124-126
+        else:
+            eng.set_bank(rows, name=self.bank_name)
         self._bank_is = kind
 
     def build_image_index(self, images: Union[Sequence[str], torch.Tensor], batch_size: Optional[int] = None) -> np.ndarray:
@@ -104,7 +143,10 @@ class MultiModalRetriever:
         eng = self.clip_model.engine
         # the reference accepts any top_k (src/retrieval.py:636); the kernel's limit is TVC_MAX_TOPK and the
         # engine raises beyond it -- never a silent truncation.  More than R rows cannot be returned (-1 padded).
-        idx, sim, _ = eng.bank_search_robust(q, top_k, want_moments=False, bank=self.bank_name)
+        if self._ivf is not None:
+            idx, sim, _ = eng.ivf_search(q, top_k, self.config.nprobe, self._ivf)
+        else:
+            idx, sim, _ = eng.bank_search_robust(q, top_k, want_moments=False, bank=self.bank_name)
         idx, sim = idx.cpu().numpy(), sim.cpu().numpy()
         return idx, sim
 
@@ -202,10 +244,15 @@ def create_retriever(config: Optional[RetrievalConfig] = None, **kw) -> MultiMod
 # ---------------------------------------------------------------------------
 @dataclass
 class RetrievalRefConfig:
-    """experiments/defenses/retrieval_ref.py:20-32."""
+    """experiments/defenses/retrieval_ref.py:20-32.  ``faiss_index_type`` defaults to "Flat" here, NOT to the reference's
+    "IVF" (:26): the default stays the exact search so that no existing result moves; "IVF" builds an index of
+    ``min(nlist, rows)`` lists (:144) searched with ``nprobe`` probes, "HNSW" falls back to the exact search."""
     reference_count: int = 5
     similarity_threshold: float = 0.3
-    use_faiss: bool = True           # accepted; the HIP search is exact either way
+    use_faiss: bool = True           # accepted; the search runs in HIP either way
+    faiss_index_type: str = "Flat"   # "Flat", "IVF", "HNSW" (:26)
+    nlist: int = 100                 # :27
+    nprobe: int = 10                 # :28
     device: str = "cuda"
     cache_size: int = 1000
     enable_reranking: bool = True
@@ -225,6 +272,7 @@ class RetrievalReferenceGenerator:
         self.reference_metadata: list = []
         self.feature_cache: Dict[int, List[Dict[str, Any]]] = {}
         self.bank_name = f"retrieval_ref:{id(self):x}"  # own bank slot on the (shared) engine
+        self._ivf = None                                # the IVFIndex that owns the slot (faiss_index_type "IVF")
         self.retrieval_stats = {"total_queries": 0, "successful_retrievals": 0, "cache_hits": 0}
         self.reference_db_path = Path(reference_db_path) if reference_db_path is not None else None
         if features is not None:
@@ -246,8 +294,12 @@ class RetrievalReferenceGenerator:
     def _register(self, feats: torch.Tensor, meta: list) -> None:
         self.reference_features = feats
         self.reference_metadata = meta
-        self.clip_model.engine.set_bank(feats.float().to(self.clip_model.device) if feats.dtype != torch.bfloat16
-                                        else feats.to(self.clip_model.device), name=self.bank_name)
+        rows = feats.float().to(self.clip_model.device) if feats.dtype != torch.bfloat16 else feats.to(self.clip_model.device)
+        self._ivf = None
+        if rows.dim() == 2 and _ivf_wanted(self.config.faiss_index_type, rows.shape[1], rows.shape[0]):
+            self._ivf = self.clip_model.engine.ivf_build(rows, min(self.config.nlist, rows.shape[0]), self.bank_name)   # :144
+        else:
+            self.clip_model.engine.set_bank(rows, name=self.bank_name)
 
     # -- bank construction -------------------------------------------------------
     def _save_reference_database(self, path: Optional[str] = None) -> Path:
@@ -315,9 +367,13 @@ class RetrievalReferenceGenerator:
         c = self.config
         q = self.clip_model.encode_tokens(self.clip_model.tokenize(list(texts)), True)    # :238-244
         search_k = min(c.rerank_top_k if c.enable_reranking else c.reference_count, rows)   # :249
-        idx, sim, _ = eng.bank_search_robust(q, search_k, c.similarity_threshold, want_moments=False, bank=self.bank_name)
         keep = min(c.reference_count, search_k)
-        feats = eng.bank_gather(idx[:, :keep].contiguous(), bank=self.bank_name).cpu().numpy()
+        if self._ivf is not None:
+            idx, sim, pos = eng.ivf_search(q, search_k, c.nprobe, self._ivf)
+            feats = eng.bank_gather(pos[:, :keep].contiguous(), bank=self.bank_name).cpu().numpy()      # stored positions
+        else:
+            idx, sim, _ = eng.bank_search_robust(q, search_k, c.similarity_threshold, want_moments=False, bank=self.bank_name)
+            feats = eng.bank_gather(idx[:, :keep].contiguous(), bank=self.bank_name).cpu().numpy()
         idx, sim = idx.cpu().numpy(), sim.cpu().numpy()
         out = []
         for r in range(len(texts)):
