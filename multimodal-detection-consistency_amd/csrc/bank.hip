@@ -36,7 +36,10 @@
 // three products hi.hi + lo.hi + hi.lo.
 //
 // Written once, ahead of the kernels that use them:
-//   cand_better / argmax_reduce<W>    the (v desc, idx asc) order and its shuffle reduction (select; row_topk: cand_better)
+//   cand_better / Best<NP> / block_best / block_exclusive_scan
+//                                     the (v desc, idx asc) order (common.hpp), the rounds of block arg-max in it (select,
+//                                     row_topk) and the block-wide scan (select): select.hpp, shared with kmeans.hip and ivf.hip
+//   BankRows                          the stored rows of a slot, as every launch over one takes them (kernels.hpp)
 //   Moments / combine / mom_lanes<>   the (sum, sumsq, max, count) 4-tuple and its reductions (search, select, merge)
 //   cand_append / cand_count_out      the listing rule of all four filter kernels: slot, cap, overflow flag
 //   bank_item / bank_lane_setup       item order and lane set-up of bank_search_kernel<FILTER> and bank_filter_ring_kernel
@@ -48,6 +51,7 @@
 #include "skinny.hpp"
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "select.hpp"
 #include <cstdlib>
 
 #define BANK_POOL 6144
@@ -58,18 +62,8 @@ struct Cand {
     float v;
     int32_t idx;
 };
-// (cand_better, the (v desc, idx asc) ordering: common.hpp -- kmeans.hip orders its centres by it too)
-// all-lane arg-max of (v, idx) in that order over groups of W lanes; pos < 0 = this lane brings no candidate
-template <int W>
-__device__ __forceinline__ void argmax_reduce(float& v, int& idx, int& pos) {
-#pragma unroll
-    for (int o = W / 2; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o, 64);
-        const int oi = __shfl_xor(idx, o, 64);
-        const int op = __shfl_xor(pos, o, 64);
-        if (op >= 0 && (pos < 0 || cand_better(ov, oi, v, idx))) { v = ov; idx = oi; pos = op; }
-    }
-}
+// (cand_better, the (v desc, idx asc) ordering: common.hpp -- kmeans.hip orders its centres by it too; the rounds of block
+// arg-max in that order: select.hpp)
 
 // A query's moments over a set of bank rows, [sum, sum of squares, max, count >= count_thr] as stored in mom_part / moments.
 // Every reduction over lanes, waves, chunks and shards is a chain of combine() calls in a fixed order.
@@ -192,13 +186,11 @@ __global__ __launch_bounds__(256) void kth_groups_kernel(const float* __restrict
 }
 
 // max over rows of |hi plane| and |lo plane| (squared, as ordered uint bit patterns)
-__global__ __launch_bounds__(256) void bank_bounds_kernel(const uint16_t* __restrict__ bank, int64_t ld,
-                                                          int planes, int D, int64_t R,
-                                                          uint32_t* __restrict__ out_sq) {
-    const int lane = threadIdx.x & 63;
+__global__ __launch_bounds__(256) void bank_bounds_kernel(BankRows bank, uint32_t* __restrict__ out_sq) {
+    const int lane = threadIdx.x & 63, D = bank.D;
     float mh = 0.f, ml = 0.f;
-    for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < R; r += (int64_t)gridDim.x * 4) {
-        const uint16_t* br = bank + r * ld;
+    for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < bank.R; r += (int64_t)gridDim.x * 4) {
+        const uint16_t* br = bank.p + r * bank.ld;
         float h2 = 0.f, l2 = 0.f;
         for (int c = lane * 8; c < D; c += 512) {
             const u32x4_t h = *(const u32x4_t*)(br + c);
@@ -207,7 +199,7 @@ __global__ __launch_bounds__(256) void bank_bounds_kernel(const uint16_t* __rest
                 const float a = Op16<false>::lo(h[e]), b = Op16<false>::hi(h[e]);
                 h2 = fmaf(a, a, fmaf(b, b, h2));
             }
-            if (planes > 1) {
+            if (bank.planes > 1) {
                 const u32x4_t l = *(const u32x4_t*)(br + D + c);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -229,13 +221,12 @@ __global__ void bank_bounds_finish_kernel(float* b) {
     b[0] = sqrtf(b[0]) * 1.0001f; b[1] = sqrtf(b[1]) * 1.0001f;
 }
 
-hipError_t launch_bank_bounds(const uint16_t* bank, int64_t ld, int planes, int D, int64_t R, float* bounds,
-                              hipStream_t stream) {
+hipError_t launch_bank_bounds(const BankRows& bank, float* bounds, hipStream_t stream) {
     hipError_t st = hipMemsetAsync(bounds, 0, 8, stream);
-    if (st != hipSuccess || R == 0) return st;
-    int64_t grid = (R + 3) / 4;
+    if (st != hipSuccess || bank.R == 0) return st;
+    int64_t grid = (bank.R + 3) / 4;
     if (grid > 4096) grid = 4096;
-    st = launch<bank_bounds_kernel>(dim3((int)grid), dim3(256), 0, stream, bank, ld, planes, D, R, (uint32_t*)bounds);
+    st = launch<bank_bounds_kernel>(dim3((int)grid), dim3(256), 0, stream, bank, (uint32_t*)bounds);
     if (st != hipSuccess) return st;
     return launch<bank_bounds_finish_kernel>(dim3(1), dim3(1), 0, stream, bounds);
 }
@@ -655,19 +646,15 @@ __global__ __launch_bounds__(SEL_T) void bank_select_kernel(const Cand* __restri
                                                             int k, int32_t* __restrict__ topk_idx,
                                                             float* __restrict__ topk_sim,
                                                             float* __restrict__ moments,
-                                                            int32_t* __restrict__ overflow,
-                                                            const uint16_t* __restrict__ rs_bank, int64_t rs_ld,
-                                                            int rs_planes, int D,
+                                                            int32_t* __restrict__ overflow, BankRows rs,      // re-scoring: the bank (rs.p null: none)
                                                             const float* __restrict__ rs_rows,
                                                             int64_t idx_offset) {
     __shared__ Cand pool[BANK_POOL];
     __shared__ __attribute__((aligned(16))) float qs[BANK_MAX_RESCORE_D];
     __shared__ int wsum[SEL_W];
-    __shared__ float red_v[2][SEL_W];
-    __shared__ int red_i[2][SEL_W];
-    __shared__ int red_p[2][SEL_W];
+    __shared__ BestSlots<SEL_T, 1> red;      // payload: the pool slot
     __shared__ float mom_red[SEL_W][4];
-    const int q = blockIdx.x, t = threadIdx.x;
+    const int q = blockIdx.x, t = threadIdx.x, D = rs.D;
     const int lane = t & 63, wave = t >> 6;
 
     // chunks handled by this thread: c = t, t + SEL_T, ...
@@ -685,23 +672,8 @@ __global__ __launch_bounds__(SEL_T) void bank_select_kernel(const Cand* __restri
     } else {
         for (int c = t; c < S; c += SEL_T) mine += cand_cnt[(int64_t)c * M + q];
     }
-    // exclusive prefix of `mine` over the workgroup: wave scan + the waves' totals
-    int incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int wbase = 0, total_all = 0;
-#pragma unroll
-    for (int w = 0; w < SEL_W; ++w) {
-        const int v = wsum[w];
-        if (w < wave) wbase += v;
-        total_all += v;
-    }
-    int off = wbase + incl - mine;
+    int total_all;
+    int off = block_exclusive_scan<SEL_T>(mine, wsum, total_all);
     if (few) {
 #pragma unroll
         for (int u = 0; u < SEL_CPT; ++u) {
@@ -726,12 +698,12 @@ __global__ __launch_bounds__(SEL_T) void bank_select_kernel(const Cand* __restri
     }
     if (t == 0 && total_all > BANK_POOL) atomicOr(overflow, 2);
     const int total = total_all < BANK_POOL ? total_all : BANK_POOL;
-    if (rs_bank) {
+    if (rs.p) {
         for (int c = t; c < D; c += SEL_T) qs[c] = rs_rows[(int64_t)q * D + c];
     }
     __syncthreads();
 
-    if (rs_bank) {
+    if (rs.p) {
         // exact fp32 re-scoring of the listed rows: one wave per row, four rows in flight per wave
         for (int i0 = wave; i0 < total; i0 += 4 * SEL_W) {
             float part[4];
@@ -740,15 +712,16 @@ __global__ __launch_bounds__(SEL_T) void bank_select_kernel(const Cand* __restri
             for (int u = 0; u < 4; ++u) {
                 int i = i0 + u * SEL_W;
                 i = i < total ? i : total - 1;
-                br[u] = rs_bank + ((int64_t)pool[i].idx - idx_offset) * rs_ld;
+                br[u] = rs.p + ((int64_t)pool[i].idx - idx_offset) * rs.ld;
                 part[u] = 0.f;
             }
             for (int c = lane * 8; c < D; c += 512) {
+                // (not bank_row8: its zero lo plane costs this loop registers -- EXPERIMENTS.md)
                 u32x4_t h[4], l[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     h[u] = *(const u32x4_t*)(br[u] + c);
-                    if (rs_planes > 1) l[u] = *(const u32x4_t*)(br[u] + D + c);
+                    if (rs.planes > 1) l[u] = *(const u32x4_t*)(br[u] + D + c);
                 }
                 const f32x4_t q0 = *(const f32x4_t*)(qs + c), q1 = *(const f32x4_t*)(qs + c + 4);
 #pragma unroll
@@ -756,7 +729,7 @@ __global__ __launch_bounds__(SEL_T) void bank_select_kernel(const Cand* __restri
 #pragma unroll
                     for (int e2 = 0; e2 < 4; ++e2) {
                         float a = Op16<false>::lo(h[u][e2]), b = Op16<false>::hi(h[u][e2]);
-                        if (rs_planes > 1) {
+                        if (rs.planes > 1) {
                             a += Op16<false>::lo(l[u][e2]);
                             b += Op16<false>::hi(l[u][e2]);
                         }
@@ -776,26 +749,20 @@ __global__ __launch_bounds__(SEL_T) void bank_select_kernel(const Cand* __restri
         __syncthreads();
     }
 
-    // k rounds of arg-max, ONE barrier each: the waves' bests go to a slot pair indexed by the round's parity, every wave
-    // reduces the SEL_W entries again by shuffles (same result in every wave), and the winner is struck out by the thread
-    // that owns its pool slot (slot % SEL_T: the only thread that ever reads it again)
+    // k rounds of arg-max (select.hpp); a pool entry is admitted while its idx >= 0: a similarity of -inf can win, a NaN never.
+    // The winner's pool slot, not its id (any int32), says whether there was one; the slot's owner (slot % SEL_T) strikes it
     for (int r = 0; r < k; ++r) {
-        float bv = -INFINITY;
-        int bi = 0x7fffffff, bp = -1;
+        Best<1> b;
+        b.pay[0] = -1;
         for (int i = t; i < total; i += SEL_T) {
             const Cand c = pool[i];
-            if (c.idx >= 0 && cand_better(c.v, c.idx, bv, bi)) { bv = c.v; bi = c.idx; bp = i; }
+            if (c.idx >= 0) best_take(b, Best<1>{c.v, c.idx, {i}});
         }
-        argmax_reduce<64>(bv, bi, bp);
-        const int par = r & 1;
-        if (lane == 0) { red_v[par][wave] = bv; red_i[par][wave] = bi; red_p[par][wave] = bp; }
-        __syncthreads();
-        float fv = red_v[par][lane & (SEL_W - 1)];
-        int fi = red_i[par][lane & (SEL_W - 1)], fp = red_p[par][lane & (SEL_W - 1)];
-        argmax_reduce<SEL_W>(fv, fi, fp);
+        const Best<1> f = block_best(b, red, r);
+        const int fp = f.pay[0];
         if (t == 0) {
-            topk_idx[(int64_t)q * k + r] = fp >= 0 ? fi : -1;
-            topk_sim[(int64_t)q * k + r] = fp >= 0 ? fv : -INFINITY;
+            topk_idx[(int64_t)q * k + r] = fp >= 0 ? f.id : -1;
+            topk_sim[(int64_t)q * k + r] = fp >= 0 ? f.v : -INFINITY;
         }
         if (fp >= 0 && (fp & (SEL_T - 1)) == t) pool[fp].idx = -1;     // taken
     }
@@ -824,8 +791,7 @@ __global__ __launch_bounds__(1024) void row_topk_kernel(float* __restrict__ sims
                                                         int32_t* __restrict__ topk_idx,
                                                         float* __restrict__ topk_sim,
                                                         float* __restrict__ moments) {
-    __shared__ float rv[16];
-    __shared__ int ri[16];
+    __shared__ BestSlots<1024, 0> red;
     __shared__ float rs[16], rq[16], rc[16];
     const int q = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     float* row = sims + (int64_t)q * R;
@@ -841,53 +807,35 @@ __global__ __launch_bounds__(1024) void row_topk_kernel(float* __restrict__ sims
             for (int w = 0; w < 16; ++w) { a += rs[w]; b += rq[w]; d += rc[w]; }
             moments[(int64_t)q * 4 + 0] = a; moments[(int64_t)q * 4 + 1] = b; moments[(int64_t)q * 4 + 3] = d;
         }
-        __syncthreads();
     }
+    // k rounds of arg-max (select.hpp); thread i & 1023 owns element i; a round without a candidate writes -1 / -inf
     for (int r = 0; r < k; ++r) {
-        float bv = -INFINITY;
-        int bi = 0x7fffffff;
-        bool has = false;
+        Best<0> b;
         for (int64_t i = t; i < R; i += 1024) {
             const float v = row[i];
-            // NaN similarities (NaN bank rows / zero-norm queries) are never returned
-            if (v == v && v != -INFINITY && (!has || cand_better(v, (int)i, bv, bi))) { bv = v; bi = (int)i; has = true; }
+            // NaN similarities (NaN bank rows / zero-norm queries), -inf and struck entries are never returned
+            if (v > -INFINITY) best_take(b, Best<0>{v, (int)i});
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (oi != 0x7fffffff && (bi == 0x7fffffff || cand_better(ov, oi, bv, bi))) { bv = ov; bi = oi; }
-        }
-        if (lane == 0) { rv[wave] = bv; ri[wave] = bi; }
-        __syncthreads();
+        const Best<0> f = block_best(b, red, r);
+        const bool none = f.id == CAND_NONE;
         if (t == 0) {
-            float fv = rv[0]; int fi = ri[0];
-            for (int w = 1; w < 16; ++w)
-                if (ri[w] != 0x7fffffff && (fi == 0x7fffffff || cand_better(rv[w], ri[w], fv, fi))) { fv = rv[w]; fi = ri[w]; }
-            if (fi != 0x7fffffff) {
-                topk_idx[(int64_t)q * k + r] = (int32_t)(fi + idx_offset);
-                topk_sim[(int64_t)q * k + r] = fv;
-                if (r == 0 && moments) moments[(int64_t)q * 4 + 2] = fv;
-                row[fi] = -INFINITY;      // taken
-            } else {
-                topk_idx[(int64_t)q * k + r] = -1;
-                topk_sim[(int64_t)q * k + r] = -INFINITY;
-                if (r == 0 && moments) moments[(int64_t)q * 4 + 2] = -INFINITY;
-            }
+            topk_idx[(int64_t)q * k + r] = none ? -1 : (int32_t)(f.id + idx_offset);
+            topk_sim[(int64_t)q * k + r] = f.v;                  // -inf when none
+            if (r == 0 && moments) moments[(int64_t)q * 4 + 2] = f.v;
         }
-        __syncthreads();
+        if (!none && (f.id & 1023) == t) row[f.id] = -INFINITY;      // taken
     }
 }
 
 hipError_t launch_bank_search_dense(const BankSearchLaunch& L, float* sims_ws, int block_rows, hipStream_t stream) {
-    const int D = L.D;
+    const int D = L.bank.D;
     for (int m0 = 0; m0 < L.M; m0 += block_rows) {
         const int m = (L.M - m0 < block_rows) ? L.M - m0 : block_rows;
-        const GemmLaunch G = gemm_launch_planes(L.bank, L.ldb, (int)L.R, L.bank_planes, L.qplanes + (int64_t)m0 * 2 * D, m, D,
-                                                sims_ws, L.R);
+        const GemmLaunch G = gemm_launch_planes(L.bank.p, L.bank.ld, (int)L.bank.R, L.bank.planes, L.qplanes + (int64_t)m0 * 2 * D, m, D,
+                                                sims_ws, L.bank.R);
         hipError_t st = launch_gemm_bf16(G, stream);
         if (st != hipSuccess) return st;
-        st = launch<row_topk_kernel>(dim3(m), dim3(1024), 0, stream, sims_ws, L.R, L.k, L.count_thr, L.idx_offset,
+        st = launch<row_topk_kernel>(dim3(m), dim3(1024), 0, stream, sims_ws, L.bank.R, L.k, L.count_thr, L.idx_offset,
                                      L.topk_idx + (int64_t)m0 * L.k, L.topk_sim + (int64_t)m0 * L.k,
                                      L.moments ? L.moments + (int64_t)m0 * 4 : nullptr);
         if (st != hipSuccess) return st;
@@ -902,7 +850,8 @@ static bool env_flag(const char* name) {
 }
 
 hipError_t launch_bank_search(const BankSearchLaunch& L, hipStream_t stream) {
-    const int D = L.D;
+    const BankRows& B = L.bank;
+    const int D = B.D;
     // products: (bank plane, query plane) pairs accumulated into one tile
     //   bf16 bank : b.qhi + b.qlo
     //   fp32 bank : bhi.qhi + bhi.qlo + blo.qhi
@@ -911,20 +860,20 @@ hipError_t launch_bank_search(const BankSearchLaunch& L, hipStream_t stream) {
 
     // small query batches: the bank streamed once from HBM against <= 64 query columns (TVC_BANK_SKINNY=0: off, for A/B runs)
     static const bool skinny_on = env_flag("TVC_BANK_SKINNY");
-    const bool skinny = filter && skinny_on && skinny_covers(D, L.M) && L.ldb % 8 == 0;
+    const bool skinny = filter && skinny_on && skinny_covers(D, L.M) && B.ld % 8 == 0;
     // ... and, over a bf16 bank, the sample's group maxima by the same route (TVC_BANK_SKINNY_SAMPLE=0: the dense sample GEMM)
     static const bool skinny_sample_on = env_flag("TVC_BANK_SKINNY_SAMPLE");
 
     // ---- pass 0: sample GEMM + tau ----------------------------------------
     hipError_t st;
-    if (skinny && skinny_sample_on && L.bank_planes == 1) {
+    if (skinny && skinny_sample_on && B.planes == 1) {
         // s0 holds >= M * n_sample floats, n_sample >= 256 or the whole bank: the first [M, 256] of it take the group maxima
-        st = launch_bank_sample_skinny(L.bank, L.ldb, D, L.qplanes, L.M, L.n_sample, L.sample_stride, L.gmax, stream);
+        st = launch_bank_sample_skinny(B.p, B.ld, D, L.qplanes, L.M, L.n_sample, L.sample_stride, L.gmax, stream);
         if (st != hipSuccess) return st;
         st = launch<kth_groups_kernel>(dim3(L.M), dim3(256), 0, stream, L.gmax, L.k, L.tau, L.qplanes, D, L.bank_bounds, L.overflow);
         if (st != hipSuccess) return st;
     } else {
-        const GemmLaunch G = gemm_launch_planes(L.bank, L.ldb * (int64_t)L.sample_stride, L.n_sample, L.bank_planes, L.qplanes, L.M, D,
+        const GemmLaunch G = gemm_launch_planes(B.p, B.ld * (int64_t)L.sample_stride, L.n_sample, B.planes, L.qplanes, L.M, D,
                                                 L.s0, L.n_sample);
         st = launch_gemm_bf16(G, stream);
         if (st != hipSuccess) return st;
@@ -936,21 +885,21 @@ hipError_t launch_bank_search(const BankSearchLaunch& L, hipStream_t stream) {
     }
 
     // ---- pass 1: fused GEMM + filter ---------------------------------------
-    GemmOperands g = gemm_operands(gemm_launch_planes(L.bank, L.ldb, (int)L.R, L.bank_planes, L.qplanes, L.M, D, nullptr, 0));
+    GemmOperands g = gemm_operands(gemm_launch_planes(B.p, B.ld, (int)B.R, B.planes, L.qplanes, L.M, D, nullptr, 0));
     if (filter) g.planes = 1;       // the first product alone: bank hi x query hi
     BankEpilogue e;
     e.tau = L.tau; e.cand = (Cand*)L.cand; e.cand_cnt = L.cand_cnt; e.mom_part = L.mom_part;
-    e.overflow = L.overflow; e.R = L.R; e.idx_offset = L.idx_offset; e.M = L.M; e.count_thr = L.count_thr;
+    e.overflow = L.overflow; e.R = B.R; e.idx_offset = L.idx_offset; e.M = L.M; e.count_thr = L.count_thr;
     const int nQt = (L.M + GEMM_BN - 1) / GEMM_BN;
-    const int nbt = (int)((L.R + GEMM_BM - 1) / GEMM_BM);
+    const int nbt = (int)((B.R + GEMM_BM - 1) / GEMM_BM);
     const int tpc = (nbt + L.S - 1) / L.S;
     // the filter pass streams its bank tiles through GEMM form 4 where that form's preconditions hold (TVC_BANK_RING=0:
     // the one-tile-at-a-time loop, for A/B runs); the ragged last bank tile is handled inside the kernel
     static const bool ring_on = env_flag("TVC_BANK_RING");
-    const bool ring = filter && ring_on && L.q_rows_padded && (g.lda % 64 == 0) && (g.ldb % 64 == 0) && L.R >= GEMM_BM;
+    const bool ring = filter && ring_on && L.q_rows_padded && (g.lda % 64 == 0) && (g.ldb % 64 == 0) && B.R >= GEMM_BM;
     const dim3 grid(nQt * L.S), block(GEMM_THREADS);
     if (skinny)
-        st = launch_bank_filter_skinny(L.bank, L.ldb, D, L.qplanes, e, L.S, tpc * GEMM_BM, stream);
+        st = launch_bank_filter_skinny(B.p, B.ld, D, L.qplanes, e, L.S, tpc * GEMM_BM, stream);
     else if (ring)
         st = launch<bank_filter_ring_kernel, BANK_LDS_BYTES>(grid, block, BANK_LDS_BYTES, stream, g, e, nQt, L.S, tpc, nbt);
     else
@@ -960,9 +909,10 @@ hipError_t launch_bank_search(const BankSearchLaunch& L, hipStream_t stream) {
     if (st != hipSuccess) return st;
 
     // ---- pass 2: select -----------------------------------------------------
+    BankRows rs = B;
+    if (!filter) rs.p = nullptr;
     return launch<bank_select_kernel>(dim3(L.M), dim3(SEL_T), 0, stream, (const Cand*)L.cand, L.cand_cnt, L.mom_part, L.S, L.M, L.k,
-                                      L.topk_idx, L.topk_sim, L.moments, L.overflow, filter ? L.bank : nullptr, L.ldb,
-                                      L.bank_planes, D, L.rows, L.idx_offset);
+                                      L.topk_idx, L.topk_sim, L.moments, L.overflow, rs, L.rows, L.idx_offset);
 }
 
 // ---------------------------------------------------------------------------

@@ -90,6 +90,18 @@ __device__ __forceinline__ bool cand_better(float v, int idx, float ov, int oidx
     return (v > ov) || (v == ov && idx < oidx);
 }
 
+// Eight elements of a stored bank row as fp32: 16 bytes of the hi plane at br, plus the lo plane's at br + D (planes > 1: the
+// hi | lo split of an fp32 bank); a one-plane slot adds a zero lo.  x + 0.0f differs from x only for x = -0.0f, and the users
+// square x (kmeans_rownorm_kernel) or add it to a sum that starts at +0.0f and so is never -0.0f (kmeans_centroid_kernel): the
+// bits of skipping the add.  (bank_select_kernel's re-scoring skips it, in its own loop: EXPERIMENTS.md has the registers.)
+__device__ __forceinline__ void bank_row8(const uint16_t* br, int D, int planes, float (&x)[8]) {
+    const u32x4_t h = *(const u32x4_t*)br;
+    u32x4_t l = u32x4_t{0u, 0u, 0u, 0u};
+    if (planes > 1) l = *(const u32x4_t*)(br + D);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { x[2 * e] = Op16<false>::lo(h[e]) + Op16<false>::lo(l[e]); x[2 * e + 1] = Op16<false>::hi(h[e]) + Op16<false>::hi(l[e]); }
+}
+
 // 16-byte async global->LDS copy (global_load_lds_dwordx4).  `lds_wave_base`
 // must be wave-uniform: the hardware writes lane L at lds_wave_base + 16*L.
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {

@@ -482,31 +482,27 @@ hipError_t launch_split_planes(const float* x, uint16_t* out, int64_t rows, int 
 // ---------------------------------------------------------------------------
 // bank row gather: out[n, :] = fp32(bank[idx[n] - idx_offset]) (hi + lo)
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gather_rows_kernel(const uint16_t* __restrict__ bank, int64_t ld,
-                                                          int planes, int D, int64_t R,
-                                                          const int32_t* __restrict__ idx,
-                                                          int64_t idx_offset, int n,
+__global__ __launch_bounds__(256) void gather_rows_kernel(BankRows bank, const int32_t* __restrict__ idx, int64_t idx_offset, int n,
                                                           float* __restrict__ out) {
     const int lane = row_lane();
     const int row = wave_row();
     if (row >= n) return;
+    const int D = bank.D;
     const int64_t src = (int64_t)idx[row] - idx_offset;
     float* o = out + (int64_t)row * D;
-    if (idx[row] < 0 || src < 0 || src >= R) {
+    if (idx[row] < 0 || src < 0 || src >= bank.R) {
         for (int c = lane; c < D; c += 64) o[c] = 0.f;
         return;
     }
-    const uint16_t* br = bank + src * ld;
+    const uint16_t* br = bank.p + src * bank.ld;
     for (int c = lane; c < D; c += 64) {
         float v = bf16_bits_to_f32(br[c]);
-        if (planes > 1) v += bf16_bits_to_f32(br[D + c]);
+        if (bank.planes > 1) v += bf16_bits_to_f32(br[D + c]);
         o[c] = v;
     }
 }
 
-hipError_t launch_gather_rows(const uint16_t* bank, int64_t ld, int planes, int D, int64_t R,
-                              const int32_t* idx, int64_t idx_offset, int n, float* out,
-                              hipStream_t stream) {
+hipError_t launch_gather_rows(const BankRows& bank, const int32_t* idx, int64_t idx_offset, int n, float* out, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    return launch<gather_rows_kernel>(row_grid(n), dim3(256), 0, stream, bank, ld, planes, D, R, idx, idx_offset, n, out);
+    return launch<gather_rows_kernel>(row_grid(n), dim3(256), 0, stream, bank, idx, idx_offset, n, out);
 }

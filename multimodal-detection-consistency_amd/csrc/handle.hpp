@@ -57,6 +57,10 @@ struct BankSlot {
     float* bounds = nullptr;          // device [2]: max row norms of the bank planes
 };
 
+inline BankRows bank_rows(const BankSlot& bk) { return BankRows{bk.bank, (int64_t)bk.planes * bk.D, bk.R, bk.D, bk.planes}; }
+// plane products of a full-precision pass over a slot: b.qhi + b.qlo, or bhi.qhi + bhi.qlo + blo.qhi
+inline int bank_products(int planes) { return planes == 2 ? 3 : 2; }
+
 constexpr int WS_P_N = WS_P_N_END - WS_PX;    // offset from a vision fp32-grade slot to its text twin
 constexpr int WS_S_N = WS_S_END - WS_SX;      // offset from a vision split slot to its text twin
 

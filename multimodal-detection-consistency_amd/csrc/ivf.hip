@@ -4,8 +4,8 @@
 //
 //   probe   the nprobe best lists of a query by q.c - |c|^2 / 2 (kmeans_assign's score and order, so a row sits in the list
 //           this rule ranks first for it): the plane GEMM writes [chunk, nlist] scores, `ivf_probe_select_kernel` (one
-//           workgroup per query) subtracts the half norms and takes nprobe rounds of block arg-max by cand_better.  NaN
-//           scores never win; ranks without a list are -1 / -inf.
+//           workgroup per query) subtracts the half norms and takes nprobe rounds of block arg-max by cand_better
+//           (select.hpp, no payload).  NaN scores never win; ranks without a list are -1 / -inf.
 //   invert  the flattened probes [chunk * nprobe] are labels over the lists: kmeans.hip's stable counting sort gives, per
 //           list, the (query, probe) pairs that read it.
 //   scan    `ivf_scan_kernel`, list-major: a work item = (list, chunk of <= 512 rows).  The item walks its rows with the skinny
@@ -18,67 +18,35 @@
 //           64-deep block has a short MFMA chain of its own, added by the vector ALU (skinny_mfma_blocks).  Every lane stores its 4 rows x one query as one 16-byte store into
 //           scores[pair * pitch + row in list]: no atomics, no candidate lists, every value written exactly once.
 //   select  `ivf_select_kernel`, one workgroup per query over its nprobe segments (lengths from list_offsets): k rounds of
-//           block arg-max by (similarity desc, original row id asc); the segments are copied to LDS first when they fit.
+//           block arg-max by (similarity desc, original row id asc) (select.hpp; the winner's stored position and segment
+//           travel with it); the segments are copied to LDS first when they fit.
 //           NaN and -inf similarities are never returned; short results are padded with -1 / -inf.
 // A probed list longer than the declared max_list_rows is read up to max_list_rows rows and raises bit 2 of the overflow word.
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "select.hpp"
 #include "skinny.hpp"
 
-#define IVF_NONE 0x7fffffff
 #define IVF_T 1024
-#define IVF_W (IVF_T / 64)
-
-// the block's best (v desc, id asc) of every thread's candidate (id == IVF_NONE: none), known to all threads after ONE
-// barrier: the waves' bests go to the slots of the round's parity and every wave reduces the IVF_W entries again
-struct IvfBest {
-    float v;
-    int id, pos, seg;
-};
-__device__ __forceinline__ void ivf_take(IvfBest& b, float v, int id, int pos, int seg) {
-    if (id != IVF_NONE && (b.id == IVF_NONE || cand_better(v, id, b.v, b.id))) { b.v = v; b.id = id; b.pos = pos; b.seg = seg; }
-}
-template <int W>
-__device__ __forceinline__ void ivf_best_lanes(IvfBest& b) {
-#pragma unroll
-    for (int o = W / 2; o > 0; o >>= 1)
-        ivf_take(b, __shfl_xor(b.v, o, 64), __shfl_xor(b.id, o, 64), __shfl_xor(b.pos, o, 64), __shfl_xor(b.seg, o, 64));
-}
-struct IvfRed {
-    float v[2][IVF_W];
-    int id[2][IVF_W], pos[2][IVF_W], seg[2][IVF_W];
-};
-__device__ __forceinline__ IvfBest ivf_block_best(IvfBest b, IvfRed& red, int round) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, par = round & 1;
-    ivf_best_lanes<64>(b);
-    if (lane == 0) { red.v[par][wave] = b.v; red.id[par][wave] = b.id; red.pos[par][wave] = b.pos; red.seg[par][wave] = b.seg; }
-    __syncthreads();
-    const int w = lane & (IVF_W - 1);
-    IvfBest f;
-    f.v = red.v[par][w]; f.id = red.id[par][w]; f.pos = red.pos[par][w]; f.seg = red.seg[par][w];
-    ivf_best_lanes<IVF_W>(f);
-    return f;
-}
 
 // ---- probe -------------------------------------------------------------------------------------------------------
 // sims [*, nlist]: the plane GEMM's q.c of one chunk of queries; lists / score [*, nprobe] of the same queries
 __global__ __launch_bounds__(IVF_T) void ivf_probe_select_kernel(float* __restrict__ sims, const float* __restrict__ halfnorm,
                                                                  int nlist, int nprobe, int32_t* __restrict__ lists,
                                                                  float* __restrict__ score) {
-    __shared__ IvfRed red;
+    __shared__ BestSlots<IVF_T, 0> red;
     const int q = blockIdx.x, t = threadIdx.x;
     float* row = sims + (int64_t)q * nlist;
     // thread t owns the entries t, t + IVF_T, ...: it alone reads and strikes them, so no barrier orders the two
     for (int i = t; i < nlist; i += IVF_T) row[i] = row[i] - halfnorm[i];
     for (int r = 0; r < nprobe; ++r) {
-        IvfBest b;
-        b.v = -INFINITY; b.id = IVF_NONE; b.pos = 0; b.seg = 0;
+        Best<0> b;
         for (int i = t; i < nlist; i += IVF_T) {
             const float v = row[i];
-            if (v > -INFINITY) ivf_take(b, v, i, i, 0);      // false for NaN and for a struck entry
+            if (v > -INFINITY) best_take(b, Best<0>{v, i});      // false for NaN and for a struck entry
         }
-        const IvfBest f = ivf_block_best(b, red, r);
-        const bool none = f.id == IVF_NONE;
+        const Best<0> f = block_best(b, red, r);
+        const bool none = f.id == CAND_NONE;
         if (t == 0) {
             lists[(int64_t)q * nprobe + r] = none ? -1 : f.id;
             if (score) score[(int64_t)q * nprobe + r] = none ? -INFINITY : f.v;
@@ -216,7 +184,7 @@ __global__ __launch_bounds__(IVF_T) void ivf_select_kernel(float* __restrict__ s
                                                            float* __restrict__ topk_sim, int32_t* __restrict__ topk_pos) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* vals = (float*)smem;
-    __shared__ IvfRed red;
+    __shared__ BestSlots<IVF_T, 2> red;      // payload: the stored position and the segment
     __shared__ int seg_beg[128], seg_len[128], seg_base[128];
     const int q = blockIdx.x, t = threadIdx.x;
     if (t < nprobe) {
@@ -242,8 +210,8 @@ __global__ __launch_bounds__(IVF_T) void ivf_select_kernel(float* __restrict__ s
         }
     }
     for (int r = 0; r < k; ++r) {
-        IvfBest b;
-        b.v = -INFINITY; b.id = IVF_NONE; b.pos = 0; b.seg = 0;
+        Best<2> b;
+        b.pay[0] = 0; b.pay[1] = 0;
         for (int j = 0; j < nprobe; ++j) {
             const int len = seg_len[j];
             if (len == 0) continue;
@@ -252,11 +220,11 @@ __global__ __launch_bounds__(IVF_T) void ivf_select_kernel(float* __restrict__ s
             for (int i = t; i < len; i += IVF_T) {
                 const float v = src[i];
                 // NaN, -inf and struck entries fail the first test; the original id is read only where it can decide
-                if (v > -INFINITY && (b.id == IVF_NONE || v >= b.v)) ivf_take(b, v, row_ids ? row_ids[beg + i] : beg + i, beg + i, j);
+                if (v > -INFINITY && v >= b.v) best_take(b, Best<2>{v, row_ids ? row_ids[beg + i] : beg + i, {beg + i, j}});
             }
         }
-        const IvfBest f = ivf_block_best(b, red, r);
-        if (f.id == IVF_NONE) {                               // the probed lists hold fewer than k rows: pad the rest
+        const Best<2> f = block_best(b, red, r);
+        if (f.id == CAND_NONE) {                               // the probed lists hold fewer than k rows: pad the rest
             for (int rr = r + t; rr < k; rr += IVF_T) {
                 topk_idx[(int64_t)q * k + rr] = -1;
                 topk_sim[(int64_t)q * k + rr] = -INFINITY;
@@ -267,12 +235,12 @@ __global__ __launch_bounds__(IVF_T) void ivf_select_kernel(float* __restrict__ s
         if (t == 0) {
             topk_idx[(int64_t)q * k + r] = (int32_t)(f.id + idx_offset);
             topk_sim[(int64_t)q * k + r] = f.v;
-            if (topk_pos) topk_pos[(int64_t)q * k + r] = f.pos;
+            if (topk_pos) topk_pos[(int64_t)q * k + r] = f.pay[0];
         }
-        const int i = f.pos - seg_beg[f.seg];
+        const int seg = f.pay[1], i = f.pay[0] - seg_beg[seg];
         if ((i & (IVF_T - 1)) == t) {
-            if (use_lds) vals[seg_base[f.seg] + i] = -INFINITY;
-            else mine[(int64_t)f.seg * pitch + i] = -INFINITY;
+            if (use_lds) vals[seg_base[seg] + i] = -INFINITY;
+            else mine[(int64_t)seg * pitch + i] = -INFINITY;
         }
     }
 }
@@ -284,7 +252,7 @@ static hipError_t launch_ivf_scan_kb(const IvfScanLaunch& L, const uint16_t* qpl
     const dim3 grid(L.plan.grid_lists, L.plan.grid_chunks);
     auto go = [&](auto n) {
         constexpr size_t lds = (size_t)n.value * 16 * QPITCH;
-        return launch<ivf_scan_kernel<KB, n.value, BP>, lds>(grid, dim3(512), lds, stream, L.bank, L.ldb, qplanes, L.list_offsets, L.R,
+        return launch<ivf_scan_kernel<KB, n.value, BP>, lds>(grid, dim3(512), lds, stream, L.bank.p, L.bank.ld, qplanes, L.list_offsets, L.bank.R,
                                                              (const int32_t*)L.pair_offsets, (const int32_t*)L.pair_order, L.nprobe,
                                                              L.max_list_rows, L.plan.pitch, L.scores, L.overflow);
     };
@@ -294,7 +262,8 @@ static hipError_t launch_ivf_scan_kb(const IvfScanLaunch& L, const uint16_t* qpl
 
 hipError_t launch_ivf_scan(const IvfScanLaunch& L, hipStream_t stream) {
     const IvfScanPlan& P = L.plan;
-    if (!P.ok || L.M < 1 || L.k < 1 || L.k > 128 || L.bank_planes < 1 || L.bank_planes > 2 || L.ldb % 8 != 0 || L.R < 1)
+    const BankRows& B = L.bank;
+    if (!P.ok || L.M < 1 || L.k < 1 || L.k > 128 || B.planes < 1 || B.planes > 2 || B.ld % 8 != 0 || B.R < 1)
         return hipErrorInvalidValue;
     hipError_t st = hipMemsetAsync(L.overflow, 0, sizeof(int32_t), stream);
     if (st != hipSuccess) return st;
@@ -309,16 +278,16 @@ hipError_t launch_ivf_scan(const IvfScanLaunch& L, hipStream_t stream) {
         st = launch_label_sort(S, stream);
         if (st != hipSuccess) return st;
         // ---- scan
-        const uint16_t* qplanes = L.qplanes + (int64_t)m0 * 2 * L.D;
-        st = dispatch<128, 512, 768>(L.D, [&](auto d) {
-            return dispatch<1, 2>(L.bank_planes, [&](auto bp) {
+        const uint16_t* qplanes = L.qplanes + (int64_t)m0 * 2 * B.D;
+        st = dispatch<128, 512, 768>(B.D, [&](auto d) {
+            return dispatch<1, 2>(B.planes, [&](auto bp) {
                 return launch_ivf_scan_kb<d.value / 64, bp.value>(L, qplanes, P.nqt, stream);
             });
         });
         if (st != hipSuccess) return st;
         // ---- select
         st = launch<ivf_select_kernel, (size_t)IVF_SELECT_LDS_FLOATS * 4>(
-            dim3(m), dim3(IVF_T), P.select_lds, stream, L.scores, P.pitch, probes, L.nprobe, L.list_offsets, L.nlist, L.R, L.max_list_rows,
+            dim3(m), dim3(IVF_T), P.select_lds, stream, L.scores, P.pitch, probes, L.nprobe, L.list_offsets, L.nlist, B.R, L.max_list_rows,
             L.row_ids, L.idx_offset, L.k, P.select_lds ? 1 : 0, L.topk_idx + (int64_t)m0 * L.k, L.topk_sim + (int64_t)m0 * L.k,
             L.topk_pos ? L.topk_pos + (int64_t)m0 * L.k : nullptr);
         if (st != hipSuccess) return st;

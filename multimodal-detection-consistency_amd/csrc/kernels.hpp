@@ -5,6 +5,16 @@
 #include <stdint.h>
 #include "host_plan.hpp"
 
+// The stored rows of a bank slot: R rows of `planes` D-wide bf16 planes side by side at row pitch ld (elements); planes 1 = a
+// bf16 bank, 2 = the (hi | lo) split of an fp32 bank.  What every launch over a bank slot reads (handle.hpp: bank_rows).
+struct BankRows {
+    const uint16_t* p = nullptr;
+    int64_t ld = 0;
+    int64_t R = 0;
+    int D = 0;
+    int planes = 1;
+};
+
 enum { TVC_EPI_F32 = 0, TVC_EPI_BF16 = 1, TVC_EPI_GELU_BF16 = 2, TVC_EPI_RESID_F32 = 3 };
 
 struct GemmLaunch {
@@ -92,9 +102,7 @@ hipError_t launch_gelu_erf_16(uint16_t* x, int64_t n, int f16, hipStream_t strea
 hipError_t launch_gelu_erf_f32(float* x, int64_t n, hipStream_t stream);
 hipError_t launch_split_planes(const float* x, uint16_t* out, int64_t rows, int d, int planes,
                                hipStream_t stream);
-hipError_t launch_gather_rows(const uint16_t* bank, int64_t ld, int planes, int D, int64_t R,
-                              const int32_t* idx, int64_t idx_offset, int n, float* out,
-                              hipStream_t stream);
+hipError_t launch_gather_rows(const BankRows& bank, const int32_t* idx, int64_t idx_offset, int n, float* out, hipStream_t stream);
 
 // ---- attention.hip
 // pfx (optional, causal packed rows only): sequence s = pfx[s] rows starting at packed row
@@ -107,11 +115,7 @@ hipError_t launch_attention(const uint16_t* qkv, uint16_t* out, const int32_t* s
 
 // ---- bank.hip
 struct BankSearchLaunch {
-    const uint16_t* bank = nullptr;   // [R, ldb] bf16 planes
-    int64_t ldb = 0;
-    int64_t R = 0;
-    int D = 0;
-    int bank_planes = 1;              // 1 = bf16 bank, 2 = (hi | lo) split of an fp32 bank
+    BankRows bank;
     const uint16_t* qplanes = nullptr;// [M, 2*D] bf16 (hi | lo) query planes
     const float* rows = nullptr;      // [M, D] the fp32 query rows (exact re-scoring of the fast form)
     const float* bank_bounds = nullptr;// [2] device: max |hi plane row|, max |lo plane row|
@@ -136,8 +140,7 @@ struct BankSearchLaunch {
     float* moments = nullptr;
 };
 hipError_t launch_bank_search(const BankSearchLaunch& L, hipStream_t stream);
-hipError_t launch_bank_bounds(const uint16_t* bank, int64_t ld, int planes, int D, int64_t R, float* bounds,
-                              hipStream_t stream);
+hipError_t launch_bank_bounds(const BankRows& bank, float* bounds, hipStream_t stream);
 // brute force: sims_ws fp32 [block_rows, R]
 hipError_t launch_bank_search_dense(const BankSearchLaunch& L, float* sims_ws, int block_rows, hipStream_t stream);
 hipError_t launch_topk_merge(const int32_t* idx_parts, const float* sim_parts, const float* feat_parts,
@@ -147,11 +150,7 @@ hipError_t launch_topk_merge(const int32_t* idx_parts, const float* sim_parts, c
 
 // ---- kmeans.hip: k-means over a bank slot (assign: nearest centre per bank row; update: deterministic cluster means)
 struct KmeansAssignLaunch {
-    const uint16_t* bank = nullptr;   // [R, ldb] bf16 planes, as BankSearchLaunch
-    int64_t ldb = 0;
-    int64_t R = 0;
-    int D = 0;
-    int bank_planes = 1;
+    BankRows bank;
     const float* centroids = nullptr; // [K, D] fp32
     const uint16_t* cplanes = nullptr;// [K, 2 * D] bf16 (hi | lo) planes of the centres
     int K = 0;
@@ -162,11 +161,7 @@ struct KmeansAssignLaunch {
 };
 hipError_t launch_kmeans_assign(const KmeansAssignLaunch& L, hipStream_t stream);
 struct KmeansUpdateLaunch {
-    const uint16_t* bank = nullptr;
-    int64_t ldb = 0;
-    int64_t R = 0;
-    int D = 0;
-    int bank_planes = 1;
+    BankRows bank;
     const int32_t* labels = nullptr;  // [R]; labels outside [0, K) belong to no cluster
     const float* centroids_in = nullptr;   // [K, D]: the row an empty cluster keeps
     int K = 0;
@@ -207,11 +202,7 @@ struct IvfProbeLaunch {
 };
 hipError_t launch_ivf_probe(const IvfProbeLaunch& L, hipStream_t stream);
 struct IvfScanLaunch {
-    const uint16_t* bank = nullptr;   // [R, ldb] bf16 planes of the rows in list order
-    int64_t ldb = 0;
-    int64_t R = 0;
-    int D = 0;
-    int bank_planes = 1;
+    BankRows bank;                    // the rows in list order
     const uint16_t* qplanes = nullptr;// [M, 2 * D] query planes
     int M = 0, k = 0, nprobe = 0, nlist = 0, max_list_rows = 0;
     const int32_t* probes = nullptr;  // [M, nprobe]

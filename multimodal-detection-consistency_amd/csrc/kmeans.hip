@@ -17,11 +17,13 @@
 //           sums its members in a fixed order in fp32.  No floating-point atomics: the centres are a pure function of
 //           (bank, labels).  The sort is a launch of its own (launch_label_sort): ivf.hip groups (query, probe) pairs by list
 //           with it, and takes the half norms of its centroids from kmeans_halfnorm_kernel.
+// The slot's rows arrive as a BankRows (kernels.hpp); the row kernels decode them with bank_row8 (common.hpp); the "no centre"
+// index CAND_NONE and the offsets' block-wide scan are select.hpp's.
 #include "gemm_core.hpp"
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "select.hpp"
 
-#define KM_NONE 0x7fffffff
 #define KM_LDS_BYTES (GEMM_LDS_BYTES + 256 * 8)
 
 // ---- assign ------------------------------------------------------------------------------------------------------
@@ -45,21 +47,16 @@ __global__ __launch_bounds__(256) void kmeans_halfnorm_kernel(const float* __res
 }
 
 // out[r] = |x_r|^2 of the stored row (hi + lo of an fp32 bank), one wave per row
-__global__ __launch_bounds__(256) void kmeans_rownorm_kernel(const uint16_t* __restrict__ bank, int64_t ld, int planes, int D,
-                                                             int64_t R, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void kmeans_rownorm_kernel(BankRows bank, float* __restrict__ out) {
     const int lane = threadIdx.x & 63;
-    for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < R; r += (int64_t)gridDim.x * 4) {
-        const uint16_t* br = bank + r * ld;
+    for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < bank.R; r += (int64_t)gridDim.x * 4) {
+        const uint16_t* br = bank.p + r * bank.ld;
         float s = 0.f;
-        for (int c = lane * 8; c < D; c += 512) {
-            const u32x4_t h = *(const u32x4_t*)(br + c);
-            u32x4_t l = u32x4_t{0u, 0u, 0u, 0u};
-            if (planes > 1) l = *(const u32x4_t*)(br + D + c);
+        for (int c = lane * 8; c < bank.D; c += 512) {
+            float x[8];
+            bank_row8(br + c, bank.D, bank.planes, x);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float a = Op16<false>::lo(h[e]) + Op16<false>::lo(l[e]), b = Op16<false>::hi(h[e]) + Op16<false>::hi(l[e]);
-                s = fmaf(a, a, fmaf(b, b, s));
-            }
+            for (int e = 0; e < 4; ++e) s = fmaf(x[2 * e], x[2 * e], fmaf(x[2 * e + 1], x[2 * e + 1], s));
         }
         s = wave_sum(s);
         if (lane == 0) out[r] = s;
@@ -85,7 +82,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void kmeans_assign_kernel(GemmOperand
     float bv[4];
     int bi[4];
 #pragma unroll
-    for (int n = 0; n < 4; ++n) { bv[n] = -INFINITY; bi[n] = KM_NONE; }
+    for (int n = 0; n < 4; ++n) { bv[n] = -INFINITY; bi[n] = CAND_NONE; }
     for (int ct = 0; ct < n_ctiles; ++ct) {
         gemm_acc_t acc;
         gemm_zero_acc(acc);
@@ -126,7 +123,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void kmeans_assign_kernel(GemmOperand
             float v = bv[n];
             int i = bi[n];
             if (cand_better(red_v[jl], red_i[jl], v, i)) { v = red_v[jl]; i = red_i[jl]; }
-            const bool none = i == KM_NONE;
+            const bool none = i == CAND_NONE;
             e.labels[row] = none ? -1 : i;
             if (e.score) e.score[row] = v;
             if (e.dist2) e.dist2[row] = none ? 0.f : fmaxf(0.f, e.dist2[row] - 2.f * v);
@@ -139,37 +136,38 @@ hipError_t launch_kmeans_halfnorm(const float* centroids, int D, int K, int Kpad
 }
 
 hipError_t launch_kmeans_assign(const KmeansAssignLaunch& L, hipStream_t stream) {
-    if (L.R < 1 || L.R > 0x7fffffffLL || L.K < 1 || L.D < 64 || L.D % 64 != 0 || L.bank_planes < 1 || L.bank_planes > 2)
+    const BankRows& B = L.bank;
+    if (B.R < 1 || B.R > 0x7fffffffLL || L.K < 1 || B.D < 64 || B.D % 64 != 0 || B.planes < 1 || B.planes > 2)
         return hipErrorInvalidValue;
     const int n_ctiles = (L.K + GEMM_BM - 1) / GEMM_BM;
     const int Kpad = n_ctiles * GEMM_BM;
-    hipError_t st = launch_kmeans_halfnorm(L.centroids, L.D, L.K, Kpad, L.halfnorm, stream);
+    hipError_t st = launch_kmeans_halfnorm(L.centroids, B.D, L.K, Kpad, L.halfnorm, stream);
     if (st != hipSuccess) return st;
     if (L.dist2) {
-        int64_t grid = (L.R + 3) / 4;
+        int64_t grid = (B.R + 3) / 4;
         if (grid > 16384) grid = 16384;
-        st = launch<kmeans_rownorm_kernel>(dim3((int)grid), dim3(256), 0, stream, L.bank, L.ldb, L.bank_planes, L.D, L.R, L.dist2);
+        st = launch<kmeans_rownorm_kernel>(dim3((int)grid), dim3(256), 0, stream, B, L.dist2);
         if (st != hipSuccess) return st;
     }
     // centres on the MFMA row dimension (A), bank rows on the lane dimension (B)
     //   bf16 bank : chi.b + clo.b
     //   fp32 bank : chi.bhi + chi.blo + clo.bhi
     GemmOperands g;
-    g.A = L.cplanes; g.lda = 2 * (int64_t)L.D; g.I = L.K;
-    g.B = L.bank; g.ldb = L.ldb; g.J = (int)L.R;
-    g.ksteps_per_plane = L.D / GEMM_BK;
+    g.A = L.cplanes; g.lda = 2 * (int64_t)B.D; g.I = L.K;
+    g.B = B.p; g.ldb = B.ld; g.J = (int)B.R;
+    g.ksteps_per_plane = B.D / GEMM_BK;
     for (int p = 0; p < GEMM_MAX_PLANES; ++p) { g.a_plane_off[p] = 0; g.b_plane_off[p] = 0; }
-    if (L.bank_planes == 2) {
+    if (B.planes == 2) {
         g.planes = 3;
-        g.b_plane_off[1] = L.D;
-        g.a_plane_off[2] = L.D;
+        g.b_plane_off[1] = B.D;
+        g.a_plane_off[2] = B.D;
     } else {
         g.planes = 2;
-        g.a_plane_off[1] = L.D;
+        g.a_plane_off[1] = B.D;
     }
     KmeansAssignArgs e;
-    e.halfnorm = L.halfnorm; e.labels = L.labels; e.score = L.score; e.dist2 = L.dist2; e.R = (int)L.R;
-    const int64_t n_btiles = (L.R + GEMM_BN - 1) / GEMM_BN;
+    e.halfnorm = L.halfnorm; e.labels = L.labels; e.score = L.score; e.dist2 = L.dist2; e.R = (int)B.R;
+    const int64_t n_btiles = (B.R + GEMM_BN - 1) / GEMM_BN;
     return launch<kmeans_assign_kernel, KM_LDS_BYTES>(dim3((unsigned)n_btiles), dim3(GEMM_THREADS), KM_LDS_BYTES, stream, g, e, n_ctiles);
 }
 
@@ -202,25 +200,12 @@ __global__ __launch_bounds__(256) void kmeans_colscan_kernel(int32_t* __restrict
 __global__ __launch_bounds__(1024) void kmeans_offsets_kernel(const int32_t* __restrict__ counts, int K, int per,
                                                               int32_t* __restrict__ offsets) {
     __shared__ int wsum[16];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const int j0 = t * per, j1 = (j0 + per < K) ? j0 + per : K;
     int mine = 0;
     for (int j = j0; j < j1; ++j) mine += counts[j];
-    int incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int base = incl - mine, total = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-        const int v = wsum[w];
-        if (w < wave) base += v;
-        total += v;
-    }
+    int total;
+    int base = block_exclusive_scan<1024>(mine, wsum, total);
     for (int j = j0; j < j1; ++j) { offsets[j] = base; base += counts[j]; }
     if (t == 0) offsets[K] = total;
 }
@@ -257,11 +242,11 @@ __global__ __launch_bounds__(256) void kmeans_scatter_kernel(const int32_t* __re
 }
 // one workgroup per cluster: thread (g, p) sums the 8 columns of piece p over the members g, g + G, ... in list order, the G
 // partial sums are added in the order of g; an empty cluster copies its input row
-__global__ __launch_bounds__(256) void kmeans_centroid_kernel(const uint16_t* __restrict__ bank, int64_t ld, int planes, int D,
-                                                              const int32_t* __restrict__ order, const int32_t* __restrict__ offsets,
-                                                              const float* __restrict__ cin, float* __restrict__ cout) {
+__global__ __launch_bounds__(256) void kmeans_centroid_kernel(BankRows bank, const int32_t* __restrict__ order,
+                                                              const int32_t* __restrict__ offsets, const float* __restrict__ cin,
+                                                              float* __restrict__ cout) {
     __shared__ float red[256 * 8];
-    const int k = blockIdx.x, t = threadIdx.x;
+    const int k = blockIdx.x, t = threadIdx.x, D = bank.D;
     const int beg = offsets[k], n = offsets[k + 1] - beg;
     if (n <= 0) {
         for (int c = t; c < D; c += 256) cout[(int64_t)k * D + c] = cin[(int64_t)k * D + c];
@@ -280,15 +265,10 @@ __global__ __launch_bounds__(256) void kmeans_centroid_kernel(const uint16_t* __
         if (live) {
 #pragma unroll 4
             for (int i = g; i < n; i += G) {
-                const uint16_t* br = bank + (int64_t)order[beg + i] * ld + c;
-                const u32x4_t h = *(const u32x4_t*)br;
-                u32x4_t l = u32x4_t{0u, 0u, 0u, 0u};
-                if (planes > 1) l = *(const u32x4_t*)(br + D);
+                float x[8];
+                bank_row8(bank.p + (int64_t)order[beg + i] * bank.ld + c, D, bank.planes, x);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    s[2 * e] += Op16<false>::lo(h[e]) + Op16<false>::lo(l[e]);
-                    s[2 * e + 1] += Op16<false>::hi(h[e]) + Op16<false>::hi(l[e]);
-                }
+                for (int e = 0; e < 8; ++e) s[e] += x[e];
             }
 #pragma unroll
             for (int e = 0; e < 8; ++e) red[(g * P + p) * 8 + e] = s[e];
@@ -325,14 +305,15 @@ hipError_t launch_label_sort(const LabelSortLaunch& L, hipStream_t stream) {
 }
 
 hipError_t launch_kmeans_update(const KmeansUpdateLaunch& L, hipStream_t stream) {
-    if (L.R < 1 || L.R > 0x7fffffffLL || L.K < 1 || L.D < 64 || L.D % 64 != 0 || L.bank_planes < 1 || L.bank_planes > 2 ||
-        L.nblocks < 1 || L.rows_per_block < 1 || (int64_t)L.nblocks * L.rows_per_block < L.R)
+    const BankRows& B = L.bank;
+    if (B.R < 1 || B.R > 0x7fffffffLL || L.K < 1 || B.D < 64 || B.D % 64 != 0 || B.planes < 1 || B.planes > 2 ||
+        L.nblocks < 1 || L.rows_per_block < 1 || (int64_t)L.nblocks * L.rows_per_block < B.R)
         return hipErrorInvalidValue;
     LabelSortLaunch S;
-    S.labels = L.labels; S.R = L.R; S.K = L.K; S.nblocks = L.nblocks; S.rows_per_block = L.rows_per_block;
+    S.labels = L.labels; S.R = B.R; S.K = L.K; S.nblocks = L.nblocks; S.rows_per_block = L.rows_per_block;
     S.blk_cnt = L.blk_cnt; S.counts = L.counts; S.offsets = L.offsets; S.order = L.order;
     hipError_t st = launch_label_sort(S, stream);
     if (st != hipSuccess) return st;
-    return launch<kmeans_centroid_kernel>(dim3(L.K), dim3(256), 0, stream, L.bank, L.ldb, L.bank_planes, L.D, (const int32_t*)L.order,
-                                          (const int32_t*)L.offsets, L.centroids_in, L.centroids_out);
+    return launch<kmeans_centroid_kernel>(dim3(L.K), dim3(256), 0, stream, B, (const int32_t*)L.order, (const int32_t*)L.offsets,
+                                          L.centroids_in, L.centroids_out);
 }

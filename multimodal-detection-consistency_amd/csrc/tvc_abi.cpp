@@ -436,8 +436,9 @@ int tvc_bank_set(tvc_handle* h, const void* bank_dev, int64_t R, int32_t D, int3
         return fail(h, TVC_E_INVALID, "tvc_bank_set: dtype must be TVC_DTYPE_BF16 or TVC_DTYPE_F32");
     }
     if (!bk.bounds) HIP_TRY(hipMalloc((void**)&bk.bounds, 8));
-    HIP_TRY(launch_bank_bounds(bk.bank, (int64_t)bk.planes * D, bk.planes, D, R, bk.bounds,
-                               (hipStream_t)stream));
+    BankRows rows = bank_rows(bk);
+    rows.R = R;                       // the slot holds them only once their bounds are under way
+    HIP_TRY(launch_bank_bounds(rows, bk.bounds, (hipStream_t)stream));
     bk.R = R;
     return TVC_OK;
 }
@@ -479,7 +480,7 @@ int tvc_bank_search(tvc_handle* h, const float* rows_dev, int32_t M, int32_t k, 
     if ((rc = ensure(h, WS_MOM_PART, (size_t)L.S * M * 16))) return rc;
     if ((rc = ensure(h, WS_OVERFLOW, 16))) return rc;
     HIP_TRY(launch_split_planes(rows_dev, (uint16_t*)h->ws[WS_QPLANES].p, M, D, 2, st));
-    L.bank = bk.bank; L.ldb = (int64_t)bk.planes * D; L.R = bk.R; L.D = D; L.bank_planes = bk.planes;
+    L.bank = bank_rows(bk);
     L.qplanes = (const uint16_t*)h->ws[WS_QPLANES].p; L.q_rows_padded = true; L.M = M; L.k = k; L.count_thr = count_thr;
     L.idx_offset = idx_offset;
     L.rows = rows_dev; L.bank_bounds = bk.bounds; L.allow_filter = h->bank_filter;
@@ -489,7 +490,7 @@ int tvc_bank_search(tvc_handle* h, const float* rows_dev, int32_t M, int32_t k, 
     L.topk_idx = topk_idx_dev; L.topk_sim = topk_sim_dev; L.moments = moments_dev;
     {
         const bool filter = !moments_dev && h->bank_filter && D <= 2048;
-        const int planes = filter ? 1 : (bk.planes == 2 ? 3 : 2);
+        const int planes = filter ? 1 : bank_products(bk.planes);
         ProfScope ps(h, st, TVC_PROF_BANK, 2.0 * (double)bk.R * M * D * planes);
         HIP_TRY(launch_bank_search(L, st));
     }
@@ -516,7 +517,7 @@ int tvc_bank_search_dense(tvc_handle* h, const float* rows_dev, int32_t M, int32
     if ((rc = ensure(h, WS_S0, (size_t)block * bk.R * 4))) return rc;
     HIP_TRY(launch_split_planes(rows_dev, (uint16_t*)h->ws[WS_QPLANES].p, M, D, 2, st));
     BankSearchLaunch L;
-    L.bank = bk.bank; L.ldb = (int64_t)bk.planes * D; L.R = bk.R; L.D = D; L.bank_planes = bk.planes;
+    L.bank = bank_rows(bk);
     L.qplanes = (const uint16_t*)h->ws[WS_QPLANES].p; L.q_rows_padded = true; L.M = M; L.k = k; L.count_thr = count_thr;
     L.idx_offset = idx_offset;
     L.topk_idx = topk_idx_dev; L.topk_sim = topk_sim_dev; L.moments = moments_dev;
@@ -547,8 +548,7 @@ int tvc_bank_gather(tvc_handle* h, const int32_t* idx_dev, int32_t n, int64_t id
     if (n < 0 || (n > 0 && (!idx_dev || !out_dev))) return fail(h, TVC_E_INVALID, "tvc_bank_gather: bad arguments");
     if (n == 0) return TVC_OK;
     if (bk.R == 0) { HIP_TRY(hipMemsetAsync(out_dev, 0, (size_t)n * bk.D * 4, (hipStream_t)stream)); return TVC_OK; }
-    HIP_TRY(launch_gather_rows(bk.bank, (int64_t)bk.planes * bk.D, bk.planes, bk.D, bk.R, idx_dev,
-                               idx_offset, n, out_dev, (hipStream_t)stream));
+    HIP_TRY(launch_gather_rows(bank_rows(bk), idx_dev, idx_offset, n, out_dev, (hipStream_t)stream));
     return TVC_OK;
 }
 

@@ -61,7 +61,7 @@ int tvc_ivf_scan(tvc_handle* h, const float* rows_dev, int32_t M, int32_t k, con
     if ((rc = ensure(h, WS_IVF_SCORES, (size_t)L.plan.score_bytes))) return rc;
     if ((rc = ensure(h, WS_OVERFLOW, 16))) return rc;
     HIP_TRY(launch_split_planes(rows_dev, (uint16_t*)h->ws[WS_IVF_QPLANES].p, M, D, 2, st));
-    L.bank = bk.bank; L.ldb = (int64_t)bk.planes * D; L.R = bk.R; L.D = D; L.bank_planes = bk.planes;
+    L.bank = bank_rows(bk);
     L.qplanes = (const uint16_t*)h->ws[WS_IVF_QPLANES].p;
     L.M = M; L.k = k; L.nprobe = nprobe; L.nlist = nlist; L.max_list_rows = max_list_rows;
     L.probes = probes_dev; L.list_offsets = list_offsets_dev; L.row_ids = row_ids_dev; L.idx_offset = idx_offset;
@@ -70,7 +70,7 @@ int tvc_ivf_scan(tvc_handle* h, const float* rows_dev, int32_t M, int32_t k, con
     L.scores = (float*)h->ws[WS_IVF_SCORES].p; L.overflow = (int32_t*)h->ws[WS_OVERFLOW].p;
     L.topk_idx = topk_idx_dev; L.topk_sim = topk_sim_dev; L.topk_pos = topk_pos_dev;
     // work as the bank search counts it: the rows of nprobe lists of R / nlist rows per query, 2 or 3 plane products
-    ProfScope ps(h, st, TVC_PROF_BANK, 2.0 * (double)M * nprobe * ((double)bk.R / nlist) * D * (bk.planes == 2 ? 3 : 2));
+    ProfScope ps(h, st, TVC_PROF_BANK, 2.0 * (double)M * nprobe * ((double)bk.R / nlist) * D * bank_products(bk.planes));
     HIP_TRY(launch_ivf_scan(L, st));
     return TVC_OK;
 }

@@ -25,11 +25,11 @@ int tvc_kmeans_assign(tvc_handle* h, const float* centroids_dev, int32_t K, int3
     if ((rc = ensure(h, WS_KM_HALFNORM, Kpad * 4))) return rc;
     HIP_TRY(launch_split_planes(centroids_dev, (uint16_t*)h->ws[WS_KM_CPLANES].p, K, D, 2, st));
     KmeansAssignLaunch L;
-    L.bank = bk->bank; L.ldb = (int64_t)bk->planes * D; L.R = bk->R; L.D = D; L.bank_planes = bk->planes;
+    L.bank = bank_rows(*bk);
     L.centroids = centroids_dev; L.cplanes = (const uint16_t*)h->ws[WS_KM_CPLANES].p; L.K = K;
     L.halfnorm = (float*)h->ws[WS_KM_HALFNORM].p;
     L.labels = labels_dev; L.score = score_dev; L.dist2 = dist2_dev;
-    ProfScope ps(h, st, TVC_PROF_BANK, 2.0 * (double)bk->R * K * D * (bk->planes == 2 ? 3 : 2));
+    ProfScope ps(h, st, TVC_PROF_BANK, 2.0 * (double)bk->R * K * D * bank_products(bk->planes));
     HIP_TRY(launch_kmeans_assign(L, st));
     return TVC_OK;
 }
@@ -54,7 +54,7 @@ int tvc_kmeans_update(tvc_handle* h, const int32_t* labels_dev, const float* cen
         if ((rc = ensure(h, WS_KM_ORDER, (size_t)bk->R * 4))) return rc;
         order_dev = (int32_t*)h->ws[WS_KM_ORDER].p;
     }
-    L.bank = bk->bank; L.ldb = (int64_t)bk->planes * bk->D; L.R = bk->R; L.D = bk->D; L.bank_planes = bk->planes;
+    L.bank = bank_rows(*bk);
     L.labels = labels_dev; L.centroids_in = centroids_in_dev; L.K = K;
     L.blk_cnt = (int32_t*)h->ws[WS_KM_BLKCNT].p;
     L.centroids_out = centroids_out_dev; L.counts = counts_dev; L.offsets = offsets_dev; L.order = order_dev;

@@ -212,7 +212,7 @@ extern "C" int tvc_tower_op(tvc_handle* h, int32_t op, const tvc_tower_op_args* 
         if (!ok || i[4] < 1 || i[4] > 2 || i[5] < 0) return bad();
         stride(i[3], i[4] * i[1], 1);
         if (!ok) return bad();
-        HIP_TRY(launch_gather_rows(bank, i[3], (int)i[4], (int)i[1], i[2], idx, i[5], (int)i[0], out, st));
+        HIP_TRY(launch_gather_rows(BankRows{bank, i[3], i[2], (int)i[1], (int)i[4]}, idx, i[5], (int)i[0], out, st));
         return TVC_OK;
     }
     case TVC_TOWER_OP_GATHER_F32_ROWS: {

@@ -14,7 +14,9 @@ B = 2); the kernel entries layernorm, layernorm_f16 and layernorm_backward (with
 shapes; one latent-diffusion transformer block and one resnet block at 8 x 8 (ln_bf16_kernel with and without `add`, GEGLU,
 the adds); the bank search (bank_cases below: every filter kernel, both tau kernels, the select, the dense fallback and the
 shard merge; the children inherit TVC_BANK_RING / TVC_BANK_SKINNY / TVC_BANK_SKINNY_SAMPLE, so a run with all three at 0
-reaches bank_search_kernel<true> and the dense sample for small M).
+reaches bank_search_kernel<true> and the dense sample for small M); k-means on a bank slot and the IVF search (cluster_cases
+below: assign and update with an empty cluster and an out-of-range label, the probe, the scan with padding and with the select's
+LDS and global-memory paths).
 """
 import argparse
 import importlib
@@ -80,6 +82,31 @@ def bank_cases(pkg, save) -> None:
             save("bank_dense_idx", i2)
             save("bank_dense_sim", s2)
             save("bank_dense_mom", m2)
+    # row_topk_kernel where its order and admission rule decide (tests/test_gpu_path.py::test_bank_search_dense_degenerate_rows):
+    # a row stored three times, 10 rows of zeros, a zero query, k = 128 over 100 rows of which one is all NaN
+    rows = unit((100, 128), 51)
+    rows[60] = rows[93] = rows[17]
+    rows[70:80] = 0.0
+    q = unit((5, 128), 52)
+    q[1] = 0.0
+    q = q.cuda()
+    for tag, dt in (("bf16", torch.bfloat16), ("f32", torch.float32)):
+        for nan in (True, False):                 # moments only over the NaN-free bank
+            b = rows.to(dt)
+            if nan:
+                b[41] = float("nan")
+            eng.set_bank(b.cuda())
+            i2 = torch.empty((5, 128), dtype=torch.int32, device="cuda:0")
+            s2 = torch.empty((5, 128), dtype=torch.float32, device="cuda:0")
+            m2 = None if nan else torch.empty((5, 4), dtype=torch.float32, device="cuda:0")
+            rc = eng.lib.tvc_bank_search_dense(eng.handle, C.c_void_p(q.data_ptr()), 5, 128, 0.05, 0, C.c_void_p(i2.data_ptr()),
+                                               C.c_void_p(s2.data_ptr()), None if nan else C.c_void_p(m2.data_ptr()),
+                                               C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            assert rc == 0, rc
+            save(f"bank_dense_short_{tag}_nan{int(nan)}_idx", i2)
+            save(f"bank_dense_short_{tag}_nan{int(nan)}_sim", s2)
+            if m2 is not None:
+                save(f"bank_dense_short_{tag}_mom", m2)
     # topk_merge_kernel on the inputs of tests/test_gpu_api.py::test_topk_merge_kernel
     W, M, k, kf, D = 4, 37, 8, 3, 128
     g = torch.Generator().manual_seed(0)
@@ -90,6 +117,62 @@ def bank_cases(pkg, save) -> None:
     mom = torch.rand((W, M, 4), generator=g)
     for name, t in zip(("idx", "sim", "feat", "mom"), eng.topk_merge(idx.cuda(), sim.cuda(), feat.cuda(), mom.cuda())):
         save(f"merge_{name}", t)
+    torch.cuda.synchronize()
+    eng.close()
+
+
+def cluster_cases(pkg, save) -> None:
+    """k-means assign and update on a bf16 and an fp32 slot, the IVF probe, and IVF scans over hand-made lists (kmeans.hip and
+    ivf.hip name the kernels); the entries and call forms of tests/test_gpu_kmeans.py and tests/test_gpu_ivf.py."""
+    import numpy as np
+    import torch
+    eng = pkg.TVCEngine()
+    dev = eng.device
+
+    def unit(shape, seed):
+        return torch.nn.functional.normalize(torch.randn(shape, generator=torch.Generator().manual_seed(seed)), dim=-1)
+
+    R, K, D = 1000, 37, 128
+    X, cent = unit((R, D), 21), (unit((K, D), 22) * 0.9).to(dev)
+    for tag, dt in (("bf16", torch.bfloat16), ("f32", torch.float32)):
+        eng.set_bank(X.to(dt).to(dev), name="ab")
+        labels, score, dist2 = eng.kmeans_assign(cent, bank="ab")
+        lab = labels.clone()
+        lab[lab == 5] = 6                         # cluster 5 stays empty
+        lab[3] = K + 9                            # a label outside [0, K)
+        out = eng.kmeans_update(lab, cent, bank="ab", want_lists=True)
+        for name, t in zip(("labels", "score", "dist2", "centroids", "counts", "offsets", "order"), (labels, score, dist2) + tuple(out)):
+            save(f"km_{tag}_{name}", t)
+    M, nlist, nprobe, k = 9, 300, 8, 10
+    Q = unit((M, D), 23).to(dev)
+    C = unit((nlist, D), 24) * 0.8
+    lists, score = eng.ivf_probe(Q, C.to(dev), nprobe)
+    save("ivf_probe_lists", lists)
+    save("ivf_probe_score", score)
+    # lists of 0 .. 20 rows, original ids shuffled (ascending inside a list)
+    rng = np.random.default_rng(25)
+    lengths = rng.integers(0, 21, nlist)
+    offsets = np.concatenate([[0], np.cumsum(lengths)])
+    rows = int(offsets[-1])
+    ids = rng.permutation(rows)
+    for l in range(nlist):
+        ids[offsets[l]:offsets[l + 1]].sort()
+    probes = np.stack([rng.choice(nlist, nprobe, replace=False) for _ in range(M)])
+    probes[2, 5] = -1
+    probes[4, 3] = probes[4, 0]                   # a list probed twice
+    short = probes.copy()
+    short[:, 1:] = -1                             # one list of at most 20 rows per query: most have fewer than k, the rest is padding
+    Xs = unit((rows, D), 26)
+    for tag, dt in (("bf16", torch.bfloat16), ("f32", torch.float32)):
+        eng.set_bank(Xs.to(dt).to(dev), name="ab")
+        # 4097 declared rows: nprobe x pitch floats no longer fit the select's LDS (plan.select_lds == 0)
+        for case, p, max_rows in (("lds", probes, 20), ("pad", short, 20), ("nolds", probes, 4097)):
+            ix = pkg.IVFIndex(name="ab", nlist=nlist, centroids=C.to(dev), offsets=torch.from_numpy(offsets.astype(np.int32)).to(dev),
+                              ids=torch.from_numpy(ids.astype(np.int32)).to(dev), max_list_rows=max_rows, rows=rows, dim=D)
+            got = eng.ivf_scan(Q, k, torch.from_numpy(p.astype(np.int32)).to(dev), ix, idx_offset=1000)
+            eng.bank_status()
+            for name, t in zip(("idx", "sim", "pos"), got):
+                save(f"ivf_scan_{tag}_{case}_{name}", t)
     torch.cuda.synchronize()
     eng.close()
 
@@ -154,6 +237,7 @@ def child(out_dir: Path) -> None:
     torch.cuda.synchronize()
     eng.close()
     bank_cases(pkg, save)
+    cluster_cases(pkg, save)
 
 
 def main() -> int:

@@ -137,6 +137,36 @@ def test_scan_edges_against_fp64(pkg, gpu_engine, D, bf16, k, shuffled):
             assert idx[q, 1] == hi + OFF and sim[q, 0] == sim[q, 1]
 
 
+NO_LDS_MAX_LIST_ROWS = 4097     # 8 probes x pitch 4112 = 32 896 floats > IVF_SELECT_LDS_FLOATS (tests/test_ivf_host.py: select_lds == 0)
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
+def test_scan_select_without_lds(pkg, gpu_engine, bf16):
+    """The select pass reading its segments from global memory: the edge index's first three queries (lists 6 and 7 with the
+    planted ties) under a declared maximum so large that nprobe x pitch no longer fits the select's LDS.  Every other scan
+    here stays below that size."""
+    c = ivf_ref.edge_case(128, bf16, True)
+    assert _select_floats(NO_LDS_MAX_LIST_ROWS) > 32768 >= _select_floats(c["max_list_rows"])
+    eng, k = gpu_engine, 20
+    Q, probes = c["Q"][:3].contiguous(), c["probes"][:3]
+    try:
+        ix = make_index(pkg, eng, c, max_list_rows=NO_LDS_MAX_LIST_ROWS)
+        got = eng.ivf_scan(Q.to(eng.device), k, torch.from_numpy(probes.astype(np.int32)).to(eng.device), ix, idx_offset=OFF)
+        eng.bank_status()
+    finally:
+        eng.release_bank(BANK)
+    ref = tuple(a[:3] for a in edge_ref(128, bf16, True))
+    check_scan(c, Q, probes, k, got, ref, f"select without LDS {'bf16' if bf16 else 'f32'}")
+    idx, sim, _ = (t.cpu().numpy() for t in got)
+    for q, (a, b) in zip(range(3), c["dup"]):
+        lo, hi = sorted((int(c["ids"][a]), int(c["ids"][b])))
+        assert idx[q, 0] == lo + OFF and idx[q, 1] == hi + OFF and sim[q, 0] == sim[q, 1]
+
+
+def _select_floats(max_list_rows):
+    return ivf_ref.EDGE_NPROBE * ((max_list_rows + 15) // 16 * 16)
+
+
 @pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
 def test_declared_maximum_too_small(pkg, gpu_engine, bf16):
     c = ivf_ref.edge_case(128, bf16, True)

@@ -211,6 +211,78 @@ def test_bank_search_dense_fallback(gpu_engine, pkg):
     assert (sim.double() - S[:, :5]).abs().max().item() < 1e-5
 
 
+def _stored64(bank):
+    """fp64 values of bank rows as the kernels hold them: the bf16 values, or hi + lo of an fp32 row's bf16 planes."""
+    if bank.dtype == torch.bfloat16:
+        return bank.double().numpy()
+    hi = bank.bfloat16().float()
+    return (hi.double() + (bank - hi).bfloat16().double()).numpy()
+
+
+def _dense(eng, q, k, count_thr, moments):
+    import ctypes as C
+    M = q.shape[0]
+    idx = torch.empty((M, k), dtype=torch.int32, device="cuda:0")
+    sim = torch.empty((M, k), dtype=torch.float32, device="cuda:0")
+    mom = torch.empty((M, 4), dtype=torch.float32, device="cuda:0") if moments else None
+    rc = eng.lib.tvc_bank_search_dense(eng.handle, C.c_void_p(q.data_ptr()), M, k, count_thr, 0, C.c_void_p(idx.data_ptr()),
+                                       C.c_void_p(sim.data_ptr()), C.c_void_p(mom.data_ptr()) if moments else None,
+                                       C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0
+    torch.cuda.synchronize()
+    return idx.cpu().numpy(), sim.cpu().numpy(), None if mom is None else mom.cpu().numpy()
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "f32"])
+def test_bank_search_dense_degenerate_rows(gpu_engine, dtype):
+    """row_topk_kernel's contract on the rows that decide its order and its admission rule: one row stored three times
+    (bit-equal similarities -> ascending index), an all-NaN row (never returned), 20 rows of zeros and a zero query (every
+    similarity ties at 0), and k larger than the number of admissible rows (the ranks beyond are exactly -1 / -inf).
+    Bounds: the dense-fallback test's 1e-5 on similarities and rtol 1e-4 / atol 1e-3 on the moments, against fp64 products
+    of the stored values (R = 100 with k = 128 runs through the dense GEMM as it is: no larger slice needed)."""
+    R, D, M, NAN_ROW, DUP = 300, 128, 5, 41, (17, 60, 93)
+    bank = _unit((R, D), 51)
+    for j in DUP[1:]:
+        bank[j] = bank[DUP[0]]
+    bank[70:80] = 0.0
+    bank[200:210] = 0.0
+    clean = bank.to(dtype)                                # NaN-free: the moment assertions
+    bank = clean.clone()
+    bank[NAN_ROW] = float("nan")
+    q = _unit((M, D), 52)
+    q[1] = 0.0                                            # the zero query
+    q[2] = _unit((1, D), 53)[0] * 0.1 + clean[DUP[0]].float()
+    q[2] /= q[2].norm()                                   # aimed at the row stored three times
+    qd = q.cuda()
+    for rows, k in ((R, 7), (100, 128)):
+        gpu_engine.set_bank(bank[:rows].contiguous().cuda())
+        idx, sim, _ = _dense(gpu_engine, qd, k, 0.05, False)
+        S = q.double().numpy() @ _stored64(bank[:rows]).T
+        n_ok = min(k, rows - 1)                           # every row but the NaN row is admissible
+        assert k == 7 or k - n_ok >= 28
+        assert (idx[:, n_ok:] == -1).all() and (sim[:, n_ok:] == -np.inf).all()
+        assert (idx[:, :n_ok] >= 0).all() and (idx[:, :n_ok] < rows).all() and not (idx == NAN_ROW).any()
+        Sok = np.where(np.isnan(S), -np.inf, S)
+        want = -np.sort(-Sok, axis=1)[:, :n_ok]
+        for m in range(M):
+            got = idx[m, :n_ok]
+            assert len(set(got.tolist())) == n_ok
+            assert (np.diff(sim[m, :n_ok]) <= 0).all()
+            ties = np.diff(sim[m, :n_ok]) == 0
+            assert (np.diff(got)[ties] > 0).all()         # equal similarities: ascending index
+            assert np.abs(sim[m, :n_ok] - S[m, got]).max() < 1e-5 and np.abs(sim[m, :n_ok] - want[m]).max() < 1e-5
+        assert idx[1, :n_ok].tolist() == [i for i in range(rows) if i != NAN_ROW][:n_ok] and (sim[1, :n_ok] == 0).all()
+        dups = [j for j in DUP if j < rows]
+        assert idx[2, :len(dups)].tolist() == dups and (sim[2, :len(dups)] == sim[2, 0]).all()
+        # moments on the NaN-free bank
+        gpu_engine.set_bank(clean[:rows].contiguous().cuda())
+        idx, sim, mom = _dense(gpu_engine, qd, k, 0.05, True)
+        S = q.double().numpy() @ _stored64(clean[:rows]).T
+        ref = np.stack([S.sum(1), (S * S).sum(1), (S >= 0.05).sum(1).astype(np.float64)], 1)
+        assert np.allclose(mom[:, [0, 1, 3]], ref, rtol=1e-4, atol=1e-3)
+        assert np.array_equal(mom[:, 2].view(np.int32), sim[:, 0].view(np.int32))      # max: bit-equal to the first rank
+
+
 def test_bank_search_overflow_is_reported(gpu_engine, pkg):
     """A degenerate bank (all rows identical) cannot be bounded by sampling: the
     overflow must be reported, never silently truncated."""

@@ -74,6 +74,14 @@ int main() {
         printf("a bad argument was accepted\n");
         return 1;
     }
+    // tests/test_gpu_ivf.py: the edge index (8 probes, lists of up to 600 rows) selects from LDS, test_scan_select_without_lds
+    // (the same index under a declared maximum of 4097 rows, M = 3) does not
+    for (int planes = 1; planes <= 2; ++planes)
+        if (ivf_scan_plan(106, 8, 20, 600, 128, planes).select_lds == 0 || ivf_scan_plan(3, 8, 20, 4097, 128, planes).select_lds != 0 ||
+            !ivf_scan_plan(3, 8, 20, 4097, 128, planes).ok) {
+            printf("the GPU tests' select paths are not the ones they name\n");
+            return 1;
+        }
     if (accepted == 0 || refused == 0) { printf("the sweep must see both outcomes\n"); return 1; }
     printf("PLAN_OK %ld accepted %ld refused\n", accepted, refused);
     return 0;
