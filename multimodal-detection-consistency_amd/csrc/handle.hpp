@@ -1,8 +1,9 @@
 // Internal: the handle behind include/tvc.h, its workspace slots and the launch helpers shared by the translation
 // units that implement the C-ABI (tvc_abi.cpp: the CLIP tower encode drivers of every precision mode and the bf16 /
 // fp16 towers, bank, consistency; tvc_precise.cpp: the fp32-grade towers' stem, layer loop and head; tvc_split.cpp: the
-// split-bf16 towers' stem, layer loop, head and weight planes; tvc_sd.cpp: latent-diffusion reference generator;
-// tvc_kmeans.cpp: k-means over a bank slot; tvc_ivf.cpp: IVF probe and list scan).
+// split-bf16 towers' stem, layer loop, head and weight planes; tvc_sd.cpp: latent-diffusion reference generator,
+// tvc_sd_op.cpp: its entry points that read no model state; tvc_kmeans.cpp: k-means over a bank slot;
+// tvc_ivf.cpp: IVF probe and list scan).
 #pragma once
 #include "../../include/tvc.h"
 #include "kernels.hpp"

@@ -2,8 +2,10 @@
 // functions of sizes, no HIP.  Kept in a header so that the host-only sanitizer build of the C-ABI (tests/host_san:
 // -fsanitize=address,undefined with the kernels stubbed out) runs the SAME arithmetic as the product.
 #pragma once
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <vector>
 
 #define BANK_CAP 128
 #define BANK_KEFF 16       // tau = max(k, 16)-th largest group maximum: a looser but far less noisy bound
@@ -224,4 +226,69 @@ inline GemmPlan gemm_form(const GemmFormArgs& a, const GemmFormEnv& env) {
         p.S = S;
     }
     return p;
+}
+
+// GEMM operand rows: readable to the next multiple of 256 plus one tile (gemm.hip's ring forms stage whole tiles and prefetch one)
+inline int64_t tile_rows(int64_t r) { return (r + 255) / 256 * 256 + 256; }
+
+// ---- the latent-diffusion sampler's scheduler (tvc_sd.cpp): PNDMScheduler with skip_prk_steps (PLMS), scalar fp32.
+// The scaled-linear schedule: betas = linspace(sqrt(b0), sqrt(b1), T)^2, out[i] = alphas_cumprod[i] = prod_{j <= i} (1 - beta_j)
+inline void sd_alphas_cumprod(float beta_start, float beta_end, int T, float* out) {
+    const float s0 = sqrtf(beta_start), s1 = sqrtf(beta_end);
+    const float step = (s1 - s0) / (float)(T - 1);
+    float prod = 1.0f;
+    for (int i = 0; i < T; ++i) {
+        const float r = i < T / 2 ? s0 + step * (float)i : s1 - step * (float)(T - 1 - i);
+        prod *= 1.0f - r * r;
+        out[i] = prod;
+    }
+}
+// One UNet evaluation of the sampling loop and the update that follows it:
+//   latents = cs * sample - ce * sum_k w[k] * e(age[k]),  sample = latents, or `cur` (the latents saved one evaluation earlier)
+// e(a >= 0) = the a-th newest noise estimate of the 4-entry history ring, counted AFTER this evaluation's own estimate was
+// appended (`append`); e(-1) = this evaluation's estimate where it is not appended (the 2nd evaluation: the ring keeps the 1st)
+struct SdPlmsStep {
+    int t = 0;                       // timestep the UNet is evaluated at
+    bool append = true;
+    int cur = 0;                     // 1: the latents are saved to `cur` before the update; 2: `cur` is the update's sample
+    int n = 0;                       // terms of the sum
+    int age[4] = {0, 0, 0, 0};
+    float w[4] = {0.f, 0.f, 0.f, 0.f}, cs = 0.f, ce = 0.f;
+};
+// steps + 1 evaluations (PNDMScheduler.set_timesteps visits the second-to-last timestep twice), 2 <= steps <= T;
+// prediction_type 1 = v-prediction; table = sd_alphas_cumprod's [T]
+inline std::vector<SdPlmsStep> sd_plms_plan(const float* table, int T, int steps, int steps_offset, int prediction_type) {
+    static const float AB[4][4] = {{1.f}, {1.5f, -0.5f}, {23.f / 12.f, -16.f / 12.f, 5.f / 12.f},
+                                   {55.f / 24.f, -59.f / 24.f, 37.f / 24.f, -9.f / 24.f}};      // Adams-Bashforth, newest first
+    const int ratio = T / steps;
+    auto acp = [&](int t) { return t >= 0 ? table[t < T ? t : T - 1] : table[0]; };
+    std::vector<SdPlmsStep> plan(steps + 1);
+    int n_ets = 0;
+    for (int i = 0; i <= steps; ++i) {
+        SdPlmsStep& p = plan[i];
+        p.t = (i < 2 ? steps - 1 - i : steps - i) * ratio + steps_offset;      // descending, the second one twice
+        int prev_t = p.t - ratio, tt = p.t;
+        if (i != 1) {
+            if (n_ets < 4) ++n_ets;
+            p.n = n_ets;
+            for (int k = 0; k < n_ets; ++k) { p.age[k] = k; p.w[k] = AB[n_ets - 1][k]; }
+            p.cur = i == 0 ? 1 : 0;
+        } else {                     // the corrector of the first step: the mean of both estimates, from the saved sample
+            p.append = false; p.cur = 2;
+            prev_t = p.t; tt = p.t + ratio;
+            p.n = 2; p.age[0] = -1; p.w[0] = 0.5f; p.age[1] = 0; p.w[1] = 0.5f;
+        }
+        const float a_t = acp(tt), a_prev = acp(prev_t);
+        const float b_t = 1.f - a_t, b_prev = 1.f - a_prev;
+        p.cs = sqrtf(a_prev / a_t);
+        const float denom = a_t * sqrtf(b_prev) + sqrtf(a_t * b_t * a_prev);
+        p.ce = (a_prev - a_t) / denom;
+        if (prediction_type == 1) {
+            // v-prediction (PNDMScheduler._get_prev_sample): the combined model output E stands for
+            // sqrt(a_t) E + sqrt(b_t) sample -- folded into the two coefficients of prev = cs * sample - ce * E
+            p.cs -= p.ce * sqrtf(b_t);
+            p.ce *= sqrtf(a_t);
+        }
+    }
+    return plan;
 }

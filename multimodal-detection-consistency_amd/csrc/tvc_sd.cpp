@@ -50,7 +50,29 @@ struct Act {             // 16-bit token-major activation (bf16, or fp16 with Ru
     int64_t rows() const { return pad ? (int64_t)n * (H + 2) * (W + 2) : tok(); }
 };
 
-// One evaluation: arena bump allocator + first-error latch (after an error every op is a no-op).
+// A bump region: 256-byte aligned pieces of [base, base + cap).  Without a base (a sizing pass) it only counts: `high` is the
+// size a real pass needs.  A piece beyond cap is refused (nullptr) and latches `over`: never a wild pointer.
+struct Bump {
+    char* base = nullptr;
+    size_t off = 0, high = 0, cap = 0;
+    bool over = false;
+    void* alloc(size_t bytes) {
+        off = (off + 255) & ~(size_t)255;
+        void* p = base ? base + off : nullptr;
+        off += bytes;
+        if (off > high) high = off;
+        if (base && off > cap) { over = true; return nullptr; }
+        return p;
+    }
+};
+// scratch of a scope: what the region hands out after this point is released at the scope's end
+struct Scratch {
+    Bump& b;
+    const size_t mark = b.off;
+    ~Scratch() { b.off = mark; }
+};
+
+// One evaluation: the arena + first-error latch (after an error every op is a no-op).
 struct Run {
     tvc_handle* h;
     SdState* S;
@@ -60,26 +82,22 @@ struct Run {
     // the f16 MFMA.  Passed to every GEMM and to every row kernel that converts; sizes, splits, streams and chunking do not see it
     // (TVC_EPI_BF16 below reads "the 16-bit epilogue", as in the towers' fp16 mode).
     bool f16 = h->sd_precision == 1;
-    char* base = nullptr;
-    size_t off = 0, high = 0;
-    size_t cap = 0;           // bytes behind `base` (the real pass): an allocation beyond it is an error, never a wild pointer
+    Bump arena;               // cap: the bytes the sizing pass counted -- it and the real pass must walk the same allocations
     int rc = TVC_OK;
     // Step-invariant tensors of a sampling loop (the bf16 text states and every cross-attention's key / value projection
     // of them: functions of the prompt only) live in their OWN bump region, walked in the same order by every evaluation:
     // keep = 1 computes them (the loop's first evaluation), keep = 2 finds them there; keep = 0 (a lone evaluation): arena.
     int keep = 0;
-    char* keep_base = nullptr;
-    size_t keep_off = 0, keep_high = 0, keep_cap = 0;
+    Bump kept;
+    void* alloc(size_t bytes) {
+        void* p = arena.alloc(bytes);
+        if (arena.over && rc == TVC_OK) rc = fail(h, TVC_E_STATE, "tvc_sd: arena overrun (the dry run sized " + std::to_string(arena.cap) + " bytes)");
+        return p;
+    }
     void* alloc_keep(size_t bytes) {
         if (!keep) return alloc(bytes);
-        keep_off = (keep_off + 255) & ~(size_t)255;
-        void* p = keep_base ? keep_base + keep_off : nullptr;
-        keep_off += bytes;
-        if (keep_off > keep_high) keep_high = keep_off;
-        if (keep_base && keep_off > keep_cap) {
-            if (rc == TVC_OK) rc = fail(h, TVC_E_STATE, "tvc_sd: step-invariant region overrun");
-            return nullptr;
-        }
+        void* p = kept.alloc(bytes);
+        if (kept.over && rc == TVC_OK) rc = fail(h, TVC_E_STATE, "tvc_sd: step-invariant region overrun");
         return p;
     }
     bool keep_fill() const { return keep != 2; }      // these tensors are computed in this evaluation
@@ -114,45 +132,37 @@ struct Run {
     void launch_fixed(GemmLaunch& g, int64_t rows_per_sample, const char* what) {
         const int S = fixed_split(g.I, g.K, g.planes, rows_per_sample);
         g.splitk_fixed = S;
-        const size_t mark = off;
+        Scratch scratch{arena};
         if (S >= 2) {
             const size_t tiles = (size_t)((g.I + 255) / 256) * (((size_t)g.J + 255) / 256);
             g.splitk_ws_bytes = tiles * S * 256 * 256 * 4;
             g.splitk_ws = (float*)alloc(g.splitk_ws_bytes);
         }
         g.f16 = f16;
-        if (live()) hip(timed_gemm(h, g, st), what);
-        off = mark;
+        launch(what, [&] { return timed_gemm(h, g, st); });      // (timed_gemm is its own profile bracket)
     }
 
-    bool live() const { return rc == TVC_OK && !dry; }
-    void hip(hipError_t e, const char* what) {
-        if (rc == TVC_OK && e != hipSuccess) rc = fail(h, TVC_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    // THE launch step: `f` -- one call that returns a hipError_t -- runs in a real pass that has seen no error, inside a
+    // profile bracket of category `cat` (TVC_PROF_*) and `work` unless cat is NO_PROF; its failure is the evaluation's error
+    static constexpr int NO_PROF = -1;
+    template <class F>
+    void launch(const char* what, F&& f, int cat = NO_PROF, double work = 0.0) {
+        if (rc != TVC_OK || dry) return;
+        hipError_t e;
+        if (cat == NO_PROF) e = f();
+        else { ProfScope ps(h, st, cat, work); e = f(); }
+        if (e != hipSuccess) rc = fail(h, TVC_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
     }
-    void* alloc(size_t bytes) {
-        off = (off + 255) & ~(size_t)255;
-        void* p = base ? base + off : nullptr;
-        off += bytes;
-        if (off > high) high = off;
-        if (base && off > cap) {          // the sizing pass and the real pass must walk the same allocations
-            if (rc == TVC_OK) rc = fail(h, TVC_E_STATE, "tvc_sd: arena overrun (the dry run sized " + std::to_string(cap) + " bytes)");
-            return nullptr;
-        }
-        return p;
-    }
-    // GEMM operands get readable rows up to the next multiple of 256 (+ one tile): gemm.hip's ring form stages whole tiles
-    static int64_t pad_rows_of(int64_t r) { return (r + 255) / 256 * 256 + 256; }
+    // GEMM operands get readable rows up to the next multiple of 256 (+ one tile): tile_rows (host_plan.hpp)
     Act act(int n, int H, int W, int C) {
         Act a; a.n = n; a.H = H; a.W = W; a.C = C;
-        const int64_t rows = pad_rows_of(a.tok());
-        a.p = (uint16_t*)alloc((size_t)rows * C * 2);
+        a.p = (uint16_t*)alloc((size_t)tile_rows(a.tok()) * C * 2);
         return a;
     }
     // padded layout: + the rows a shifted tap reads beyond the last tile
     Act act_padded(int n, int H, int W, int C) {
         Act a; a.n = n; a.H = H; a.W = W; a.C = C; a.pad = true;
-        const int64_t rows = (a.rows() + 255) / 256 * 256 + 256 + 3 * (W + 2);
-        a.p = (uint16_t*)alloc((size_t)rows * C * 2);
+        a.p = (uint16_t*)alloc((size_t)(tile_rows(a.rows()) + 3 * (W + 2)) * C * 2);
         return a;
     }
     const void* W(const std::string& name) {
@@ -203,6 +213,15 @@ struct Run {
         launch_fixed(g, (int64_t)(xp.H + 2) * Wp, "sd conv gemm");
         return y;
     }
+    // the first convolution, on fp32 NCHW input of at most 7 channels: im2col rows of 64 columns, one GEMM
+    Act conv_in(const float* in, int n, int Cin, int H, int W_, const std::string& prefix, int Cout) {
+        Act x = act(n, H, W_, Cout);
+        Scratch scratch{arena};
+        uint16_t* col = (uint16_t*)alloc((size_t)tile_rows(x.tok()) * 64 * 2);
+        launch("im2col_in", [&] { return sd_im2col_in(in, col, n, Cin, H, W_, 64, 1.0f, st, f16); });
+        gemm(W(prefix + "weight"), Cout, 64, col, x.tok(), (const float*)W(prefix + "bias"), x.p, Cout, TVC_EPI_BF16, (int64_t)H * W_);
+        return x;
+    }
     // linear / 1x1 convolution on token rows
     Act linear(const Act& x, const std::string& wname, const std::string& bname, int Cout) {
         Act y = act(x.n, x.H, x.W, Cout);
@@ -216,92 +235,68 @@ struct Run {
     // input's rows, not the 36x of im2col rows) and convolved as nine planes; the dense result is what the next block reads
     Act upsample_conv(const Act& x, const std::string& prefix, int Cout) {
         Act y = act(x.n, 2 * x.H, 2 * x.W, Cout);
-        const size_t mark = off;
+        Scratch scratch{arena};
         Act xp = act_padded(x.n, 2 * x.H, 2 * x.W, x.C);
-        if (live()) {
-            ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)xp.rows() * x.C * 2.5);
-            hip(sd_relayout(x.p, xp.p, x.n, 2 * x.H, 2 * x.W, x.C, x.pad, 1, 1, st), "sd_relayout(up)");
-        }
+        launch("sd_relayout(up)", [&] { return sd_relayout(x.p, xp.p, x.n, 2 * x.H, 2 * x.W, x.C, x.pad, 1, 1, st); },
+               TVC_PROF_ROWOPS, (double)xp.rows() * x.C * 2.5);
         Act yp = conv3x3_planes(xp, prefix, Cout);
-        if (live()) {
-            ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)y.tok() * Cout * 4.0);
-            hip(sd_relayout(yp.p, y.p, y.n, y.H, y.W, Cout, 1, 0, 0, st), "sd_relayout");
-        }
-        off = mark;
+        launch("sd_relayout", [&] { return sd_relayout(yp.p, y.p, y.n, y.H, y.W, Cout, 1, 0, 0, st); },
+               TVC_PROF_ROWOPS, (double)y.tok() * Cout * 4.0);
         return y;
     }
     Act conv3x3(const Act& x, const std::string& prefix, int Cout, int stride = 1, int up = 0) {
         const int Hs = up ? 2 * x.H : x.H, Ws = up ? 2 * x.W : x.W;
         const int Ho = (Hs - 1) / stride + 1, Wo = (Ws - 1) / stride + 1;
         Act y = act(x.n, Ho, Wo, Cout);
-        const size_t mark = off;
+        Scratch scratch{arena};
         Act col = act(x.n, Ho, Wo, 9 * x.C);
         const void* w = W(prefix + "weight");
         const float* b = (const float*)W(prefix + "bias");
-        if (live()) {
-            ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)col.tok() * 9 * x.C * 4.0);      // rows written once, read once by the GEMM
-            hip(sd_im2col3x3(x.p, col.p, x.n, x.H, x.W, x.C, stride, up, st), "sd_im2col3x3");
-        }
+        launch("sd_im2col3x3", [&] { return sd_im2col3x3(x.p, col.p, x.n, x.H, x.W, x.C, stride, up, st); },
+               TVC_PROF_ROWOPS, (double)col.tok() * 9 * x.C * 4.0);      // rows written once, read once by the GEMM
         gemm(w, Cout, 9 * x.C, col.p, col.tok(), b, y.p, Cout, TVC_EPI_BF16, (int64_t)Ho * Wo);
-        off = mark;
         return y;
     }
     Act groupnorm(const Act& x, const std::string& prefix, float eps, int silu, const float* tadd = nullptr, int64_t ld_t = 0,
                   bool out_pad = false) {
         Act y = out_pad ? act_padded(x.n, x.H, x.W, x.C) : act(x.n, x.H, x.W, x.C);
-        const size_t mark = off;
+        Scratch scratch{arena};
         float* ws = (float*)alloc(sd_groupnorm_ws_floats(x.n, x.H * x.W, S->d.norm_groups) * 4);
         const float* g = (const float*)W(prefix + "weight");
         const float* b = (const float*)W(prefix + "bias");
-        if (live()) {
-            ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)x.tok() * x.C * 6.0);
-            hip(sd_groupnorm(x.p, tadd, ld_t, g, b, y.p, x.n, x.H, x.W, x.C, S->d.norm_groups, eps, silu, x.pad, out_pad, ws, st, f16),
-                "sd_groupnorm");
-        }
-        off = mark;
+        launch("sd_groupnorm", [&] {
+            return sd_groupnorm(x.p, tadd, ld_t, g, b, y.p, x.n, x.H, x.W, x.C, S->d.norm_groups, eps, silu, x.pad, out_pad, ws, st, f16);
+        }, TVC_PROF_ROWOPS, (double)x.tok() * x.C * 6.0);
         return y;
     }
-    Act layernorm(const Act& x, const std::string& prefix) {
-        Act y = act(x.n, x.H, x.W, x.C);
-        const float* g = (const float*)W(prefix + "weight");
-        const float* b = (const float*)W(prefix + "bias");
-        if (live()) {
-            ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)x.tok() * x.C * 4.0);
-            hip(sd_layernorm_bf16(x.p, g, b, y.p, x.tok(), x.C, 1e-5f, st, nullptr, nullptr, f16), "sd_layernorm");
-        }
-        return y;
-    }
-    // sum = a + b (the residual stream) and LayerNorm(sum) in one pass; bit-identical to add() followed by layernorm()
-    Act add_layernorm(const Act& a, const Act& b, const std::string& prefix, Act& sum) {
-        sum = act(a.n, a.H, a.W, a.C);
+    // LayerNorm(a); with b: s = a + b (the residual stream, to *sum) and LayerNorm(s) in one pass, bit-identical to add() then layernorm()
+    Act layernorm(const Act& a, const std::string& prefix, const Act* b = nullptr, Act* sum = nullptr) {
+        Act s;
+        if (b) s = act(a.n, a.H, a.W, a.C);
         Act y = act(a.n, a.H, a.W, a.C);
         const float* g = (const float*)W(prefix + "weight");
         const float* bb = (const float*)W(prefix + "bias");
-        if (live()) {
-            ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)a.tok() * a.C * 8.0);
-            hip(sd_layernorm_bf16(a.p, g, bb, y.p, a.tok(), a.C, 1e-5f, st, b.p, sum.p, f16), "sd_add_layernorm");
-        }
+        launch(b ? "sd_add_layernorm" : "sd_layernorm", [&] {
+            return sd_layernorm_bf16(a.p, g, bb, y.p, a.tok(), a.C, 1e-5f, st, b ? b->p : nullptr, s.p, f16);
+        }, TVC_PROF_ROWOPS, (double)a.tok() * a.C * (b ? 8.0 : 4.0));
+        if (sum) *sum = s;
         return y;
     }
     Act add(const Act& a, const Act& b) {
         Act y = act(a.n, a.H, a.W, a.C);
-        if (live()) {
-            ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)a.tok() * a.C * 6.0);
-            hip(sd_add_bf16(a.p, b.p, y.p, a.tok() * a.C, st, f16), "sd_add");
-        }
+        launch("sd_add", [&] { return sd_add_bf16(a.p, b.p, y.p, a.tok() * a.C, st, f16); }, TVC_PROF_ROWOPS, (double)a.tok() * a.C * 6.0);
         return y;
     }
     void attention(const uint16_t* q, int64_t ldq, const uint16_t* k, int64_t ldk, const uint16_t* v, int64_t ldv, uint16_t* o,
                    int64_t ldo, int n, int heads, int Tq, int Tk, int dh) {
-        if (!live()) return;
-        ProfScope ps(h, st, TVC_PROF_ATTENTION, 4.0 * n * heads * (double)Tq * Tk * dh);
-        hip(sd_flash_attention(q, ldq, k, ldk, v, ldv, o, ldo, n, heads, Tq, Tk, dh, st, f16), "sd_flash_attention");
+        launch("sd_flash_attention", [&] { return sd_flash_attention(q, ldq, k, ldk, v, ldv, o, ldo, n, heads, Tq, Tk, dh, st, f16); },
+               TVC_PROF_ATTENTION, 4.0 * n * heads * (double)Tq * Tk * dh);
     }
 
     // ResnetBlock2D: x + conv2(silu(gn2(conv1(silu(gn1(x))) + time projection))), 1x1 shortcut when the widths differ
     Act resnet(const Act& x, const std::string& p, int Cout, const float* tadd_all, float eps) {
         Act out = act(x.n, x.H, x.W, Cout);
-        const size_t mark = off;
+        Scratch scratch{arena};
         Act h1 = groupnorm(x, p + "norm1.", eps, 1, nullptr, 0, true);
         Act h2 = conv3x3_planes(h1, p + "conv1.", Cout);
         const float* tadd = nullptr;
@@ -314,11 +309,8 @@ struct Run {
         Act h4 = conv3x3_planes(h3, p + "conv2.", Cout);
         Act sc = x;
         if (x.C != Cout) sc = linear(x, p + "conv_shortcut.weight", p + "conv_shortcut.bias", Cout);
-        if (live()) {
-            ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)x.tok() * Cout * 6.0);
-            hip(sd_add_padded(sc.p, h4.p, out.p, x.n, x.H, x.W, Cout, st, f16), "sd_add_padded");
-        }
-        off = mark;
+        launch("sd_add_padded", [&] { return sd_add_padded(sc.p, h4.p, out.p, x.n, x.H, x.W, Cout, st, f16); },
+               TVC_PROF_ROWOPS, (double)x.tok() * Cout * 6.0);
         return out;
     }
 
@@ -327,7 +319,7 @@ struct Run {
         const int C = x.C, dh = C / heads, T = x.H * x.W, n = x.n;
         const std::string t = p + "transformer_blocks.0.";
         Act out = act(n, x.H, x.W, C);
-        const size_t mark = off;
+        Scratch scratch{arena};
         Act g = groupnorm(x, p + "norm.", 1e-6f, 0);
         Act hs = linear(g, p + "proj_in.weight", p + "proj_in.bias", C);
         Act n2, n3, hs1;
@@ -337,35 +329,31 @@ struct Run {
             Act a = act(n, x.H, x.W, C);
             attention(qkv.p, 3 * C, qkv.p + C, 3 * C, qkv.p + 2 * C, 3 * C, a.p, C, n, heads, T, T, dh);
             Act o = linear(a, t + "attn1.to_out.0.weight", t + "attn1.to_out.0.bias", C);
-            n2 = add_layernorm(hs, o, t + "norm2.", hs1);      // hs1 = hs + o; n2 = norm2(hs1)
+            n2 = layernorm(hs, t + "norm2.", &o, &hs1);      // hs1 = hs + o; n2 = norm2(hs1)
             hs = hs1;
         }
         {   // cross-attention onto the text states
             Act q = linear(n2, t + "attn2.to_q.weight", "", C);
             Act cx; cx.n = n; cx.H = 1; cx.W = S->d.ctx; cx.C = S->d.cross_attention_dim; cx.p = const_cast<uint16_t*>(ctx16);
             Act kv = cx; kv.C = 2 * C;                       // step-invariant (alloc_keep)
-            kv.p = (uint16_t*)alloc_keep((size_t)pad_rows_of(cx.tok()) * 2 * C * 2);
-            if (keep_fill()) gemm(W(t + "attn2.to_kv.weight"), 2 * C, cx.C, cx.p, cx.tok(), nullptr, kv.p, 2 * C, TVC_EPI_BF16, S->d.ctx);
-            else (void)W(t + "attn2.to_kv.weight");
+            kv.p = (uint16_t*)alloc_keep((size_t)tile_rows(cx.tok()) * 2 * C * 2);
+            const void* wkv = W(t + "attn2.to_kv.weight");
+            if (keep_fill()) gemm(wkv, 2 * C, cx.C, cx.p, cx.tok(), nullptr, kv.p, 2 * C, TVC_EPI_BF16, S->d.ctx);
             Act a = act(n, x.H, x.W, C);
             attention(q.p, C, kv.p, 2 * C, kv.p + C, 2 * C, a.p, C, n, heads, T, S->d.ctx, dh);
             Act o = linear(a, t + "attn2.to_out.0.weight", t + "attn2.to_out.0.bias", C);
-            n3 = add_layernorm(hs, o, t + "norm3.", hs1);
+            n3 = layernorm(hs, t + "norm3.", &o, &hs1);
             hs = hs1;
         }
         {   // GEGLU feed-forward
             Act gg = linear(n3, t + "ff.net.0.proj.weight", t + "ff.net.0.proj.bias", 8 * C);
             Act ge = act(n, x.H, x.W, 4 * C);
-            if (live()) {
-                ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)x.tok() * C * 24.0);
-                hip(sd_geglu(gg.p, ge.p, gg.tok(), 4 * C, st, f16), "sd_geglu");
-            }
+            launch("sd_geglu", [&] { return sd_geglu(gg.p, ge.p, gg.tok(), 4 * C, st, f16); }, TVC_PROF_ROWOPS, (double)x.tok() * C * 24.0);
             Act o = linear(ge, t + "ff.net.2.weight", t + "ff.net.2.bias", C);
             hs = add(hs, o);
         }
         Act po = linear(hs, p + "proj_out.weight", p + "proj_out.bias", C);
-        if (live()) hip(sd_add_bf16(x.p, po.p, out.p, out.tok() * C, st, f16), "sd_add");
-        off = mark;
+        launch("sd_add", [&] { return sd_add_bf16(x.p, po.p, out.p, out.tok() * C, st, f16); });
         return out;
     }
 
@@ -373,11 +361,11 @@ struct Run {
     Act vae_attention(const Act& x, const std::string& p) {
         const int C = x.C, T = x.H * x.W, n = x.n;
         Act out = act(n, x.H, x.W, C);
-        const size_t mark = off;
+        Scratch scratch{arena};
         Act g = groupnorm(x, p + "group_norm.", 1e-6f, 0);
         Act qkv = linear(g, p + "to_qkv.weight", p + "to_qkv.bias", 3 * C);
         Act a = act(n, x.H, x.W, C);
-        const int64_t Tp = ((int64_t)T + 255) / 256 * 256 + 256;
+        const int64_t Tp = tile_rows(T);
         uint16_t* qc = (uint16_t*)alloc((size_t)Tp * C * 2);      // compact q / k rows of one image
         uint16_t* kc = (uint16_t*)alloc((size_t)Tp * C * 2);
         uint16_t* vT = (uint16_t*)alloc((size_t)(C + 512) * (size_t)((T + 63) / 64 * 64) * 2);     // [C, T]
@@ -387,25 +375,23 @@ struct Run {
         if (T % 64 != 0 && rc == TVC_OK) rc = fail(h, TVC_E_INVALID, "tvc_sd: VAE attention needs H * W % 64 == 0");
         for (int i = 0; i < (dry ? 1 : n) && rc == TVC_OK; ++i) {          // (dry run: one image sizes the per-image scratch)
             const uint16_t* rows = qkv.p + (int64_t)i * T * 3 * C;
-            if (live()) {
-                hip(hipMemcpy2DAsync(qc, (size_t)C * 2, rows, (size_t)3 * C * 2, (size_t)C * 2, T, hipMemcpyDeviceToDevice, st), "copy q");
-                hip(hipMemcpy2DAsync(kc, (size_t)C * 2, rows + C, (size_t)3 * C * 2, (size_t)C * 2, T, hipMemcpyDeviceToDevice, st), "copy k");
-                hip(hipMemcpy2DAsync(pr, (size_t)C * 2, rows + 2 * C, (size_t)3 * C * 2, (size_t)C * 2, T, hipMemcpyDeviceToDevice, st), "copy v");
-                hip(launch_transpose_bf16(pr, vT, T, C, st), "transpose v");      // moves 16-bit words: either format
-            }
+            const struct { const char* what; uint16_t* dst; } part[3] = {{"copy q", qc}, {"copy k", kc}, {"copy v", pr}};      // [T, C] out of [T, 3 C]
+            for (int j = 0; j < 3; ++j)
+                launch(part[j].what, [&] { return hipMemcpy2DAsync(part[j].dst, (size_t)C * 2, rows + j * C, (size_t)3 * C * 2, (size_t)C * 2, T, hipMemcpyDeviceToDevice, st); });
+            launch("transpose v", [&] { return launch_transpose_bf16(pr, vT, T, C, st); });      // moves 16-bit words: either format
             // scores[q, key] = q . k  (A = keys, B = queries), probabilities, out[q, c] = sum_key P[q, key] V^T[c, key]
             gemm(kc, T, C, qc, T, nullptr, sc, T, TVC_EPI_F32, T);
-            if (live()) hip(sd_softmax_rows(sc, pr, T, T, 1.0f / sqrtf((float)C), st, f16), "sd_softmax_rows");
+            launch("sd_softmax_rows", [&] { return sd_softmax_rows(sc, pr, T, T, 1.0f / sqrtf((float)C), st, f16); });
             gemm(vT, C, T, pr, T, nullptr, a.p + (int64_t)i * T * C, C, TVC_EPI_BF16, T);
         }
         Act o = linear(a, p + "proj_attn.weight", p + "proj_attn.bias", C);
-        if (live()) hip(sd_add_bf16(x.p, o.p, out.p, out.tok() * C, st, f16), "sd_add");
-        off = mark;
+        launch("sd_add", [&] { return sd_add_bf16(x.p, o.p, out.p, out.tok() * C, st, f16); });
         return out;
     }
 };
 
-int64_t pad_rows(int64_t r) { return (r + 255) / 256 * 256 + 256; }
+// attention heads of the Transformer2DModels at a resolution level (tvc_sd_desc: heads_per_block, 0 = `heads`)
+int level_heads(const tvc_sd_desc& d, int level) { return d.heads_per_block[level] > 0 ? d.heads_per_block[level] : d.heads; }
 
 // ---- UNet2DConditionModel.forward on 2-D latents
 void unet_forward(Run& R, const float* latents, int n, int H, int W, float timestep, const float* ctx, float* eps_out) {
@@ -413,44 +399,34 @@ void unet_forward(Run& R, const float* latents, int n, int H, int W, float times
     const tvc_sd_desc& d = S->d;
     const int nb = d.n_blocks, c0 = d.block_out_channels[0], Tdim = 4 * c0;
     // text states -> 16-bit rows
-    uint16_t* ctx16 = (uint16_t*)R.alloc_keep((size_t)pad_rows((int64_t)n * d.ctx) * d.cross_attention_dim * 2);
-    if (R.live() && R.keep_fill()) R.hip(sd_cast_silu(ctx, ctx16, (int64_t)n * d.ctx * d.cross_attention_dim, 0, R.st, R.f16), "ctx cast");
+    uint16_t* ctx16 = (uint16_t*)R.alloc_keep((size_t)tile_rows((int64_t)n * d.ctx) * d.cross_attention_dim * 2);
+    if (R.keep_fill()) R.launch("ctx cast", [&] { return sd_cast_silu(ctx, ctx16, (int64_t)n * d.ctx * d.cross_attention_dim, 0, R.st, R.f16); });
     // time embedding MLP, then every resnet's time projection in one GEMM: tadd fp32 [n, temb_total]
-    uint16_t* te = (uint16_t*)R.alloc((size_t)pad_rows(n) * c0 * 2);
+    uint16_t* te = (uint16_t*)R.alloc((size_t)tile_rows(n) * c0 * 2);
     float* t1 = (float*)R.alloc((size_t)n * Tdim * 4);
-    uint16_t* t1b = (uint16_t*)R.alloc((size_t)pad_rows(n) * Tdim * 2);
+    uint16_t* t1b = (uint16_t*)R.alloc((size_t)tile_rows(n) * Tdim * 2);
     float* t2 = (float*)R.alloc((size_t)n * Tdim * 4);
-    uint16_t* t2b = (uint16_t*)R.alloc((size_t)pad_rows(n) * Tdim * 2);
+    uint16_t* t2b = (uint16_t*)R.alloc((size_t)tile_rows(n) * Tdim * 2);
     float* tadd = (float*)R.alloc((size_t)n * S->temb_total * 4);
     const void* w1 = R.W("time_embedding.linear_1.weight"); const float* b1 = (const float*)R.W("time_embedding.linear_1.bias");
     const void* w2 = R.W("time_embedding.linear_2.weight"); const float* b2 = (const float*)R.W("time_embedding.linear_2.bias");
-    if (R.live()) R.hip(sd_timestep_embed(te, n, c0, timestep, R.st, R.f16), "timestep embed");
+    R.launch("timestep embed", [&] { return sd_timestep_embed(te, n, c0, timestep, R.st, R.f16); });
     R.gemm(w1, Tdim, c0, te, n, b1, t1, Tdim, TVC_EPI_F32, 1);
-    if (R.live()) R.hip(sd_cast_silu(t1, t1b, (int64_t)n * Tdim, 1, R.st, R.f16), "silu");
+    R.launch("silu", [&] { return sd_cast_silu(t1, t1b, (int64_t)n * Tdim, 1, R.st, R.f16); });
     R.gemm(w2, Tdim, Tdim, t1b, n, b2, t2, Tdim, TVC_EPI_F32, 1);
-    if (R.live()) R.hip(sd_cast_silu(t2, t2b, (int64_t)n * Tdim, 1, R.st, R.f16), "silu");       // resnets apply SiLU to temb first
+    R.launch("silu", [&] { return sd_cast_silu(t2, t2b, (int64_t)n * Tdim, 1, R.st, R.f16); });       // resnets apply SiLU to temb first
     R.gemm(S->temb_w, S->temb_total, Tdim, t2b, n, (const float*)S->temb_b, tadd, S->temb_total, TVC_EPI_F32, 1);
 
-    // conv_in on the fp32 NCHW latents
-    Act x = R.act(n, H, W, c0);
-    {
-        const size_t mark = R.off;
-        uint16_t* col = (uint16_t*)R.alloc((size_t)pad_rows((int64_t)n * H * W) * 64 * 2);
-        if (R.live()) R.hip(sd_im2col_in(latents, col, n, d.in_channels, H, W, 64, 1.0f, R.st, R.f16), "im2col_in");
-        R.gemm(R.W("conv_in.weight"), c0, 64, col, (int64_t)n * H * W, (const float*)R.W("conv_in.bias"), x.p, c0, TVC_EPI_BF16,
-               (int64_t)H * W);
-        R.off = mark;
-    }
+    Act x = R.conv_in(latents, n, d.in_channels, H, W, "conv_in.", c0);      // on the fp32 NCHW latents
     std::vector<Act> skips;
     skips.push_back(x);
     const float eps = d.norm_eps;
-    auto heads_at = [&](int level) { return d.heads_per_block[level] > 0 ? d.heads_per_block[level] : d.heads; };
     for (int i = 0; i < nb; ++i) {
         const int c = d.block_out_channels[i];
         for (int j = 0; j < d.layers_per_block; ++j) {
             const std::string pi = "down_blocks." + std::to_string(i);
             x = R.resnet(x, pi + ".resnets." + std::to_string(j) + ".", c, tadd, eps);
-            if (d.down_block_attn[i]) x = R.transformer(x, pi + ".attentions." + std::to_string(j) + ".", ctx16, heads_at(i));
+            if (d.down_block_attn[i]) x = R.transformer(x, pi + ".attentions." + std::to_string(j) + ".", ctx16, level_heads(d, i));
             skips.push_back(x);
         }
         if (i != nb - 1) {
@@ -460,7 +436,7 @@ void unet_forward(Run& R, const float* latents, int n, int H, int W, float times
     }
     const int cm = d.block_out_channels[nb - 1];
     x = R.resnet(x, "mid_block.resnets.0.", cm, tadd, eps);
-    x = R.transformer(x, "mid_block.attentions.0.", ctx16, heads_at(nb - 1));
+    x = R.transformer(x, "mid_block.attentions.0.", ctx16, level_heads(d, nb - 1));
     x = R.resnet(x, "mid_block.resnets.1.", cm, tadd, eps);
     for (int i = 0; i < nb; ++i) {
         const int c = d.block_out_channels[nb - 1 - i];
@@ -470,18 +446,16 @@ void unet_forward(Run& R, const float* latents, int n, int H, int W, float times
             const Act sk = skips.back();
             skips.pop_back();
             Act cat = R.act(x.n, x.H, x.W, x.C + sk.C);
-            if (R.live()) R.hip(sd_concat(x.p, x.C, sk.p, sk.C, cat.p, cat.tok(), R.st), "sd_concat");
+            R.launch("sd_concat", [&] { return sd_concat(x.p, x.C, sk.p, sk.C, cat.p, cat.tok(), R.st); });
             x = R.resnet(cat, pi + ".resnets." + std::to_string(j) + ".", c, tadd, eps);
-            if (attn) x = R.transformer(x, pi + ".attentions." + std::to_string(j) + ".", ctx16, heads_at(nb - 1 - i));
+            if (attn) x = R.transformer(x, pi + ".attentions." + std::to_string(j) + ".", ctx16, level_heads(d, nb - 1 - i));
         }
         if (i != nb - 1) x = R.upsample_conv(x, pi + ".upsamplers.0.conv.", c);
     }
     Act y = R.groupnorm(x, "conv_norm_out.", eps, 1, nullptr, 0, true);
-    {
-        float* o = nullptr;
-        R.conv3x3_planes(y, "conv_out.", d.out_channels, &o);
-        if (R.live()) R.hip(sd_tokens_to_nchw(o, d.out_channels, eps_out, n, d.out_channels, H, W, 1.0f, 0.0f, 0, 1, R.st), "to nchw");
-    }
+    float* o = nullptr;
+    R.conv3x3_planes(y, "conv_out.", d.out_channels, &o);
+    R.launch("to nchw", [&] { return sd_tokens_to_nchw(o, d.out_channels, eps_out, n, d.out_channels, H, W, 1.0f, 0.0f, 0, 1, R.st); });
 }
 
 // ---- AutoencoderKL.decode(z / scaling) -> (x / 2 + 0.5).clamp(0, 1), fp32 NCHW
@@ -490,19 +464,9 @@ void vae_forward(Run& R, const float* latents, int n, int H, int W, float* image
     const tvc_sd_desc& d = S->d;
     const int nb = d.vae_n_blocks, L = d.latent_channels, top = d.vae_block_out_channels[nb - 1];
     float* z = (float*)R.alloc((size_t)n * L * H * W * 4);
-    if (R.live())
-        R.hip(sd_pointwise_small(latents, (const float*)R.W("post_quant_conv.weight"), (const float*)R.W("post_quant_conv.bias"), z,
-                                 n, L, H * W, 1.0f / d.vae_scaling, R.st), "post_quant_conv");
-    else { (void)R.W("post_quant_conv.weight"); (void)R.W("post_quant_conv.bias"); }
-    Act x = R.act(n, H, W, top);
-    {
-        const size_t mark = R.off;
-        uint16_t* col = (uint16_t*)R.alloc((size_t)pad_rows((int64_t)n * H * W) * 64 * 2);
-        if (R.live()) R.hip(sd_im2col_in(z, col, n, L, H, W, 64, 1.0f, R.st, R.f16), "im2col_in");
-        R.gemm(R.W("decoder.conv_in.weight"), top, 64, col, (int64_t)n * H * W, (const float*)R.W("decoder.conv_in.bias"), x.p, top,
-               TVC_EPI_BF16, (int64_t)H * W);
-        R.off = mark;
-    }
+    const float *pw = (const float*)R.W("post_quant_conv.weight"), *pb = (const float*)R.W("post_quant_conv.bias");
+    R.launch("post_quant_conv", [&] { return sd_pointwise_small(latents, pw, pb, z, n, L, H * W, 1.0f / d.vae_scaling, R.st); });
+    Act x = R.conv_in(z, n, L, H, W, "decoder.conv_in.", top);
     const float eps = 1e-6f;
     x = R.resnet(x, "decoder.mid_block.resnets.0.", top, nullptr, eps);
     x = R.vae_attention(x, "decoder.mid_block.attentions.0.");
@@ -516,7 +480,7 @@ void vae_forward(Run& R, const float* latents, int n, int H, int W, float* image
     Act y = R.groupnorm(x, "decoder.conv_norm_out.", eps, 1, nullptr, 0, true);
     float* o = nullptr;
     R.conv3x3_planes(y, "decoder.conv_out.", 3, &o);
-    if (R.live()) R.hip(sd_tokens_to_nchw(o, 3, images, y.n, 3, y.H, y.W, 0.5f, 0.5f, 1, 1, R.st), "to nchw");
+    R.launch("to nchw", [&] { return sd_tokens_to_nchw(o, 3, images, y.n, 3, y.H, y.W, 0.5f, 0.5f, 1, 1, R.st); });
 }
 
 // run `body` twice: a dry pass that sizes the arena, then the real one
@@ -525,13 +489,22 @@ int with_arena(tvc_handle* h, hipStream_t st, Slot slot, F&& body) {
     Run dry{h, h->sd, st, true};
     body(dry);
     if (dry.rc != TVC_OK) return dry.rc;
-    int rc = ensure(h, slot, dry.high + 4096);
+    int rc = ensure(h, slot, dry.arena.high + 4096);
     if (rc) return rc;
     Run run{h, h->sd, st, false};
-    run.base = (char*)h->ws[slot].p;
-    run.cap = h->ws[slot].n;
+    run.arena.base = (char*)h->ws[slot].p;
+    run.arena.cap = h->ws[slot].n;
     body(run);
     return run.rc;
+}
+
+// what one UNet evaluation of n samples needs: the arena's bytes and (keep != 0) the step-invariant region's
+struct UnetSize { int rc; size_t high, keep_high; };
+UnetSize unet_size(tvc_handle* h, hipStream_t st, int n, int H, int W, int keep) {
+    Run dry{h, h->sd, st, true};
+    dry.keep = keep;
+    unet_forward(dry, nullptr, n, H, W, 0.f, nullptr, nullptr);
+    return {dry.rc, dry.arena.high, dry.kept.high};
 }
 
 // UNet2DConditionModel halves H, W (blocks - 1) times with ceil sizes and doubles them back: any size that is not a multiple
@@ -551,7 +524,7 @@ int block_heads(const tvc_sd_desc& d, const std::string& p) {
     if (p.compare(0, 12, "down_blocks.") == 0 && p.size() > 12) level = p[12] - '0';
     else if (p.compare(0, 10, "up_blocks.") == 0 && p.size() > 10) level = d.n_blocks - 1 - (p[10] - '0');
     if (level < 0 || level >= d.n_blocks) level = d.n_blocks - 1;
-    return d.heads_per_block[level] > 0 ? d.heads_per_block[level] : d.heads;
+    return level_heads(d, level);
 }
 
 int need_sd(tvc_handle* h, bool unet, bool vae, const char* who) {
@@ -575,7 +548,7 @@ int tvc_sd_load(tvc_handle* h, const tvc_sd_desc* desc, const tvc_named_tensor* 
         return fail(h, TVC_E_INVALID, "tvc_sd_load: unsupported geometry");
     for (int i = 0; i < d.n_blocks; ++i) {
         const int c = d.block_out_channels[i];
-        const int nh = d.heads_per_block[i] > 0 ? d.heads_per_block[i] : d.heads;
+        const int nh = level_heads(d, i);
         const int dh = c % nh == 0 ? c / nh : 0;
         const bool dh_ok = dh == 8 || dh == 16 || dh == 24 || dh == 32 || dh == 40 || dh == 48 || dh == 56 || dh == 64 || dh == 80 ||
                            dh == 96 || dh == 128 || dh == 160;         // the instantiations of sd_flash_attention_kernel
@@ -607,8 +580,7 @@ int tvc_sd_load(tvc_handle* h, const tvc_sd_desc* desc, const tvc_named_tensor* 
             if (kv.first.size() > suffix.size() && kv.first.compare(kv.first.size() - suffix.size(), suffix.size(), suffix) == 0)
                 order.push_back({kv.first.substr(0, kv.first.size() - suffix.size()), 0});
         std::sort(order.begin(), order.end());
-        // widths: the resnet's conv2 is [Cout, 9 * Cout]; the host tells us Cout through "<prefix>time_emb_proj.rows"? No --
-        // derive it from the architecture walk instead.
+        // widths: from the architecture walk
         std::unordered_map<std::string, int> width;
         {
             const int nb = d.n_blocks;
@@ -645,14 +617,7 @@ int tvc_sd_load(tvc_handle* h, const tvc_sd_desc* desc, const tvc_named_tensor* 
     {
         const int T = d.num_train_timesteps > 0 ? d.num_train_timesteps : 1000;
         S->alphas_cumprod.resize(T);
-        const float s0 = sqrtf(d.beta_start), s1 = sqrtf(d.beta_end);
-        const float step = (s1 - s0) / (float)(T - 1);
-        float prod = 1.0f;
-        for (int i = 0; i < T; ++i) {
-            const float r = i < T / 2 ? s0 + step * (float)i : s1 - step * (float)(T - 1 - i);
-            prod *= 1.0f - r * r;
-            S->alphas_cumprod[i] = prod;
-        }
+        sd_alphas_cumprod(d.beta_start, d.beta_end, T, S->alphas_cumprod.data());
     }
     return TVC_OK;
 }
@@ -709,17 +674,8 @@ static int sd_generate_chunk(tvc_handle* h, const float* cond_dev, const float* 
     float* tmp = cur + ne;
     HIP_TRY(hipMemcpyAsync(ctx2, uncond_dev, ctx_elems * 4, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(ctx2 + ctx_elems, cond_dev, ctx_elems * 4, hipMemcpyDeviceToDevice, st));
-    // PNDMScheduler.set_timesteps with skip_prk_steps: the second-to-last value is visited twice
-    const int ratio = T / steps;
-    std::vector<int> ts;
-    for (int i = 0; i < steps; ++i) ts.push_back(i * ratio + d.steps_offset);
-    std::vector<int> plms(ts.begin(), ts.end() - 1);
-    plms.push_back(ts[steps - 2]);
-    plms.push_back(ts[steps - 1]);
-    std::vector<int> order(plms.rbegin(), plms.rend());
-    auto acp = [&](int t) { return t >= 0 ? S->alphas_cumprod[t < T ? t : T - 1] : S->alphas_cumprod[0]; };
-    int counter = 0, n_ets = 0, head = 0;            // ets ring: slot (head - 1 - k) mod 4 = k-th newest
-    auto slot = [&](int k) { return ets + (size_t)((head - 1 - k + 8) % 4) * ne; };
+    const std::vector<SdPlmsStep> plan = sd_plms_plan(S->alphas_cumprod.data(), T, steps, d.steps_offset, d.prediction_type);
+    int head = 0;                                    // ets ring: slot (head - 1 - k) mod 4 = k-th newest
     // the step-invariant tensors (bf16 text states, every cross-attention's K / V of them) are computed by the first
     // evaluation and kept for the others: 16 projections per evaluation less, bit-identical
     // Two streams (TVC_OPT_SD_STREAMS): the unconditional and the conditional half of an evaluation are independent until
@@ -736,17 +692,15 @@ static int sd_generate_chunk(tvc_handle* h, const float* cond_dev, const float* 
     }
     size_t keep_part = 0, arena_part[2] = {0, 0};     // arena: [0] the loop's first evaluation (fills the kept tensors), [1] the others
     for (int pass = 0; pass < 2; ++pass) {
-        Run dry{h, S, st, true};
-        dry.keep = pass == 0 ? 1 : 2;
-        unet_forward(dry, nullptr, pn, H, W, 0.f, nullptr, nullptr);
-        if (dry.rc != TVC_OK) return dry.rc;
-        if (pass == 0) keep_part = (dry.keep_high + 4096 + 255) & ~(size_t)255;
-        arena_part[pass] = (dry.high + 4096 + 255) & ~(size_t)255;
+        const UnetSize sz = unet_size(h, st, pn, H, W, pass == 0 ? 1 : 2);
+        if (sz.rc != TVC_OK) return sz.rc;
+        if (pass == 0) keep_part = (sz.keep_high + 4096 + 255) & ~(size_t)255;
+        arena_part[pass] = (sz.high + 4096 + 255) & ~(size_t)255;
     }
     if ((rc = ensure(h, WS_SD3, keep_part * parts))) return rc;
     if ((rc = ensure(h, WS_SD0, std::max(arena_part[0], arena_part[1]) * parts))) return rc;
     bool first = true;
-    for (int t : order) {
+    for (const SdPlmsStep& p : plan) {
         HIP_TRY(hipMemcpyAsync(lat2, latents_dev, ne * 4, hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMemcpyAsync(lat2 + ne, latents_dev, ne * 4, hipMemcpyDeviceToDevice, st));
         const size_t ap = arena_part[first ? 0 : 1];
@@ -757,13 +711,13 @@ static int sd_generate_chunk(tvc_handle* h, const float* cond_dev, const float* 
         rc = TVC_OK;
         for (int part = 0; part < parts; ++part) {
             Run run{h, S, part == 0 ? st : h->sd_aux, false};
-            run.base = (char*)h->ws[WS_SD0].p + (size_t)part * ap;
-            run.cap = ap;
+            run.arena.base = (char*)h->ws[WS_SD0].p + (size_t)part * ap;
+            run.arena.cap = ap;
             run.keep = first ? 1 : 2;
-            run.keep_base = (char*)h->ws[WS_SD3].p + (size_t)part * keep_part;
-            run.keep_cap = keep_part;
+            run.kept.base = (char*)h->ws[WS_SD3].p + (size_t)part * keep_part;
+            run.kept.cap = keep_part;
             const size_t so = (size_t)part * pn;          // first sample of this part
-            unet_forward(run, lat2 + so * (ne / n), pn, H, W, (float)t, ctx2 + so * (ctx_elems / n), eps2 + so * (ne / n));
+            unet_forward(run, lat2 + so * (ne / n), pn, H, W, (float)p.t, ctx2 + so * (ctx_elems / n), eps2 + so * (ne / n));
             if (run.rc != TVC_OK && rc == TVC_OK) rc = run.rc;
         }
         if (parts == 2) {          // joined even after an error: the caller's stream must not run ahead of the other half
@@ -773,45 +727,16 @@ static int sd_generate_chunk(tvc_handle* h, const float* cond_dev, const float* 
         if (rc) return rc;
         first = false;
         // classifier-free guidance, then PNDMScheduler.step_plms
-        int prev_t = t - ratio, tt = t;
-        float* e_new = tmp;
-        if (counter != 1) {
-            e_new = ets + (size_t)head * ne;         // append (the ring drops the oldest of 4)
-            head = (head + 1) % 4;
-            if (n_ets < 4) ++n_ets;
-        } else {
-            prev_t = t; tt = t + ratio;
-        }
+        float* e_new = p.append ? ets + (size_t)head * ne : tmp;      // appended: the ring drops the oldest of 4
+        if (p.append) head = (head + 1) % 4;
         HIP_TRY(sd_cfg(eps2, e_new, ne, guidance, st));
-        const float* sample = latents_dev;
-        const float *e0 = nullptr, *e1 = nullptr, *e2 = nullptr, *e3 = nullptr;
-        float c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-        if (n_ets == 1 && counter == 0) {
-            e0 = slot(0); c0 = 1.f;
-            HIP_TRY(hipMemcpyAsync(cur, latents_dev, ne * 4, hipMemcpyDeviceToDevice, st));
-        } else if (n_ets == 1 && counter == 1) {
-            e0 = e_new; c0 = 0.5f; e1 = slot(0); c1 = 0.5f;
-            sample = cur;
-        } else if (n_ets == 2) {
-            e0 = slot(0); c0 = 1.5f; e1 = slot(1); c1 = -0.5f;
-        } else if (n_ets == 3) {
-            e0 = slot(0); c0 = 23.f / 12.f; e1 = slot(1); c1 = -16.f / 12.f; e2 = slot(2); c2 = 5.f / 12.f;
-        } else {
-            e0 = slot(0); c0 = 55.f / 24.f; e1 = slot(1); c1 = -59.f / 24.f; e2 = slot(2); c2 = 37.f / 24.f; e3 = slot(3); c3 = -9.f / 24.f;
-        }
-        const float a_t = acp(tt), a_prev = acp(prev_t);
-        const float b_t = 1.f - a_t, b_prev = 1.f - a_prev;
-        float cs = sqrtf(a_prev / a_t);
-        const float denom = a_t * sqrtf(b_prev) + sqrtf(a_t * b_t * a_prev);
-        float ce = (a_prev - a_t) / denom;
-        if (d.prediction_type == 1) {
-            // v-prediction (PNDMScheduler._get_prev_sample): the combined model output E stands for
-            // sqrt(a_t) E + sqrt(b_t) sample -- folded into the two coefficients of prev = cs * sample - ce * E
-            cs -= ce * sqrtf(b_t);
-            ce *= sqrtf(a_t);
-        }
-        HIP_TRY(sd_lincomb(latents_dev, sample, cs, ce, e0, c0, e1, c1, e2, c2, e3, c3, ne, st));
-        ++counter;
+        if (p.cur == 1) HIP_TRY(hipMemcpyAsync(cur, latents_dev, ne * 4, hipMemcpyDeviceToDevice, st));
+        const float* e[4];
+        for (int k = 0; k < 4; ++k)
+            e[k] = k >= p.n ? nullptr : p.age[k] < 0 ? tmp : ets + (size_t)((head - 1 - p.age[k] + 8) % 4) * ne;
+        const float *sample = p.cur == 2 ? cur : latents_dev, *e0 = e[0], *e1 = e[1], *e2 = e[2], *e3 = e[3];
+        const float cs = p.cs, ce = p.ce, c0 = p.w[0], c1 = p.w[1], c2 = p.w[2], c3 = p.w[3];
+        HIP_TRY(sd_lincomb(latents_dev, sample, cs, ce, e0, c0, e1, c1, e2, c2, e3, c3, ne, st));      // (HIP_TRY's error text quotes these names)
     }
     return TVC_OK;
 }
@@ -831,10 +756,9 @@ int tvc_sd_generate(tvc_handle* h, const float* cond_dev, const float* uncond_de
     // linear in the sample count -- a dry run of one image's (unconditional | conditional) pair measures it, and the batch
     // runs in chunks that keep the arena within TVC_OPT_SD_ARENA_BYTES.  A chunk is a whole sampling loop of its images
     // (every sample's arithmetic is independent of its batch mates), so chunking changes no image.
-    Run dry{h, S, st, true};
-    unet_forward(dry, nullptr, 2, H, W, 0.f, nullptr, nullptr);
-    if (dry.rc != TVC_OK) return dry.rc;
-    const size_t per_image = dry.high;
+    const UnetSize pair = unet_size(h, st, 2, H, W, 0);
+    if (pair.rc != TVC_OK) return pair.rc;
+    const size_t per_image = pair.high;
     int64_t chunk = (int64_t)(h->sd_arena_bytes / (per_image ? per_image : 1));
     if (chunk < 1) chunk = 1;
     if (chunk > n) chunk = n;
@@ -861,281 +785,38 @@ int tvc_sd_block(tvc_handle* h, int32_t kind, const char* prefix, const float* x
     const std::string p(prefix);
     return with_arena(h, (hipStream_t)stream, WS_SD0, [&](Run& R) {
         Act x = R.act(n, H, W, Cin);
-        if (R.live()) R.hip(sd_nchw_to_tokens(x_dev, x.p, n, Cin, H * W, R.st, R.f16), "nchw_to_tokens");
+        R.launch("nchw_to_tokens", [&] { return sd_nchw_to_tokens(x_dev, x.p, n, Cin, H * W, R.st, R.f16); });
         Act y;
         if (kind == 0) {
             // the block's own time projection: tadd[n, Cout] = silu(temb) W^T + b, laid out as one slice of temb_total
             const float* tadd_all = nullptr;
             if (temb_dev) {
                 const int Tdim = 4 * d.block_out_channels[0];
-                uint16_t* tb = (uint16_t*)R.alloc((size_t)pad_rows(n) * Tdim * 2);
+                uint16_t* tb = (uint16_t*)R.alloc((size_t)tile_rows(n) * Tdim * 2);
                 float* tadd = (float*)R.alloc((size_t)n * S->temb_total * 4);
-                if (R.live()) R.hip(sd_cast_silu(temb_dev, tb, (int64_t)n * Tdim, 1, R.st, R.f16), "silu");
+                R.launch("silu", [&] { return sd_cast_silu(temb_dev, tb, (int64_t)n * Tdim, 1, R.st, R.f16); });
                 R.gemm(S->temb_w, S->temb_total, Tdim, tb, n, (const float*)S->temb_b, tadd, S->temb_total, TVC_EPI_F32, 1);
                 tadd_all = tadd;
             }
             y = R.resnet(x, p, Cout, tadd_all, vae ? 1e-6f : d.norm_eps);
         } else if (kind == 1) {
-            uint16_t* ctx16 = (uint16_t*)R.alloc((size_t)pad_rows((int64_t)n * d.ctx) * d.cross_attention_dim * 2);
-            if (R.live()) R.hip(sd_cast_silu(ctx_dev, ctx16, (int64_t)n * d.ctx * d.cross_attention_dim, 0, R.st, R.f16), "ctx cast");
+            uint16_t* ctx16 = (uint16_t*)R.alloc((size_t)tile_rows((int64_t)n * d.ctx) * d.cross_attention_dim * 2);
+            R.launch("ctx cast", [&] { return sd_cast_silu(ctx_dev, ctx16, (int64_t)n * d.ctx * d.cross_attention_dim, 0, R.st, R.f16); });
             y = R.transformer(x, p, ctx16, block_heads(d, p));
         } else if (kind == 2) {
             y = R.vae_attention(x, p);
         } else if (kind == 3) {
             // stride 1: the 9-plane GEMM on the padded layout (dense -> padded with zero borders -> conv -> dense)
             Act xp = R.act_padded(n, H, W, Cin);
-            if (R.live()) R.hip(sd_relayout(x.p, xp.p, n, H, W, Cin, 0, 1, 0, R.st), "relayout");
+            R.launch("relayout", [&] { return sd_relayout(x.p, xp.p, n, H, W, Cin, 0, 1, 0, R.st); });
             Act yp = R.conv3x3_planes(xp, p, Cout);
             y = R.act(n, H, W, Cout);
-            if (R.live()) R.hip(sd_relayout(yp.p, y.p, n, H, W, Cout, 1, 0, 0, R.st), "relayout");
+            R.launch("relayout", [&] { return sd_relayout(yp.p, y.p, n, H, W, Cout, 1, 0, 0, R.st); });
         } else {
             y = kind == 5 ? R.upsample_conv(x, p, Cout) : R.conv3x3(x, p, Cout, 2, 0);
         }
-        if (R.live()) R.hip(sd_tokens_bf16_to_nchw(y.p, out_dev, y.n, y.C, y.H * y.W, R.st, R.f16), "tokens_to_nchw");
+        R.launch("tokens_to_nchw", [&] { return sd_tokens_bf16_to_nchw(y.p, out_dev, y.n, y.C, y.H * y.W, R.st, R.f16); });
     });
-}
-
-int tvc_preprocess_images(tvc_handle* h, const float* images_dev, int32_t n, int32_t H, int32_t W, int32_t S, int32_t filter,
-                          int32_t keep_aspect, const float* mean3, const float* std3, float* out_dev, void* stream) {
-    if (!h) return TVC_E_INVALID;
-    if (n < 0 || H < 1 || W < 1 || S < 1 || !mean3 || !std3 || (n > 0 && (!images_dev || !out_dev)) || filter < 0 || filter > 1)
-        return fail(h, TVC_E_INVALID, "tvc_preprocess_images: bad arguments");
-    int Hr = S, Wr = S;
-    if (keep_aspect) {               // short side -> S (rounded as PIL does), centre crop
-        if (H <= W) Wr = (int)((double)W * S / H + 0.5); else Hr = (int)((double)H * S / W + 0.5);
-        if (Hr < S) Hr = S;
-        if (Wr < S) Wr = S;
-    }
-    HIP_TRY(sd_resize_norm(images_dev, out_dev, n, H, W, Hr, Wr, (Hr - S) / 2, (Wr - S) / 2, S, filter, mean3, std3, (hipStream_t)stream));
-    return TVC_OK;
-}
-
-int tvc_sd_attention(tvc_handle* h, const uint16_t* q_dev, const uint16_t* k_dev, const uint16_t* v_dev, uint16_t* out_dev, int32_t n,
-                     int32_t heads, int32_t Tq, int32_t Tk, int32_t dh, void* stream) {
-    if (!h) return TVC_E_INVALID;
-    if (!q_dev || !k_dev || !v_dev || !out_dev || n < 1 || heads < 1 || Tq < 1 || Tk < 1 || dh < 8 || dh > 160 || dh % 8)
-        return fail(h, TVC_E_INVALID, "tvc_sd_attention: need head_dim % 8 == 0 and <= 160, non-NULL buffers");
-    const int64_t ld = (int64_t)heads * dh;
-    HIP_TRY(sd_flash_attention(q_dev, ld, k_dev, ld, v_dev, ld, out_dev, ld, n, heads, Tq, Tk, dh, (hipStream_t)stream, h->sd_precision == 1));
-    return TVC_OK;
-}
-
-int tvc_sd_attention_ex(tvc_handle* h, const uint16_t* q_dev, int64_t ldq, const uint16_t* k_dev, int64_t ldk, const uint16_t* v_dev,
-                        int64_t ldv, uint16_t* out_dev, int64_t ldo, int32_t n, int32_t heads, int32_t Tq, int32_t Tk, int32_t dh,
-                        void* stream) {
-    if (!h) return TVC_E_INVALID;
-    if (!q_dev || !k_dev || !v_dev || !out_dev || n < 1 || heads < 1 || Tq < 1 || Tk < 1 || dh < 8 || dh > 160 || dh % 8)
-        return fail(h, TVC_E_INVALID, "tvc_sd_attention_ex: need head_dim % 8 == 0 and <= 160, non-NULL buffers");
-    // the alignment rule of sd_flash_attention (16-byte loads of q / k / v pieces, 8-byte stores) and rows that hold all heads
-    const int64_t w = (int64_t)heads * dh;
-    if (ldq < w || ldk < w || ldv < w || ldo < w || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 ||
-        ((uintptr_t)q_dev & 15) || ((uintptr_t)k_dev & 15) || ((uintptr_t)v_dev & 15) || ((uintptr_t)out_dev & 7))
-        return fail(h, TVC_E_INVALID, "tvc_sd_attention_ex: need ldq / ldk / ldv % 8 == 0, ldo % 4 == 0, every stride >= heads * dh, "
-                                      "q / k / v 16-byte and out 8-byte aligned");
-    HIP_TRY(sd_flash_attention(q_dev, ldq, k_dev, ldk, v_dev, ldv, out_dev, ldo, n, heads, Tq, Tk, dh, (hipStream_t)stream,
-                               h->sd_precision == 1));
-    return TVC_OK;
-}
-
-// One row kernel on the caller's buffers (include/tvc.h, tvc_sd_op_args: which slot carries what).  Every case checks its
-// own pointers and extents, then calls ONE launcher of kernels.hpp; what a launcher itself rejects comes back as TVC_E_HIP.
-int tvc_sd_op(tvc_handle* h, int32_t op, const tvc_sd_op_args* a, void* stream) {
-    if (!h) return TVC_E_INVALID;
-    if (!a) return fail(h, TVC_E_INVALID, "tvc_sd_op: NULL arguments");
-    if (op < 0 || op >= TVC_SD_OP_COUNT) return fail(h, TVC_E_INVALID, "tvc_sd_op: unknown op");
-    const hipStream_t st = (hipStream_t)stream;
-    const int f16 = h->sd_precision == 1;
-    const int64_t* i = a->i;
-    const float* f = a->f;
-    bool ok = true;
-    // a required pointer: non-NULL and aligned for the kernel's accesses (16-byte vectors of 16-bit tensors, fp32 words)
-    auto p16 = [&](const void* p) { ok = ok && p && !((uintptr_t)p & 15); return (uint16_t*)p; };
-    auto p32 = [&](const void* p) { ok = ok && p && !((uintptr_t)p & 3); return (float*)p; };
-    auto opt16 = [&](const void* p) { ok = ok && !((uintptr_t)p & 15); return (uint16_t*)p; };
-    auto opt32 = [&](const void* p) { ok = ok && !((uintptr_t)p & 3); return (float*)p; };
-    // the first `k` extents: positive, and their product (what the kernels index rows with) inside int32
-    auto dims = [&](int k, int64_t lo = 1) {
-        int64_t prod = 1;
-        for (int j = 0; j < k; ++j) {
-            if (i[j] < lo || i[j] > INT32_MAX) { ok = false; return; }
-            prod *= i[j] > 0 ? i[j] + 2 : 1;          // + 2: the padded layout's rows
-            if (prod > INT32_MAX) { ok = false; return; }
-        }
-    };
-    auto flag = [&](int j) { ok = ok && (i[j] == 0 || i[j] == 1); return (int)i[j]; };
-    auto bad = [&]() { return fail(h, TVC_E_INVALID, "tvc_sd_op: a NULL or misaligned pointer, or an extent that is not positive / too large"); };
-    switch (op) {
-    case TVC_SD_OP_GROUPNORM: {
-        const uint16_t* x = p16(a->in[0]);
-        const float *tadd = opt32(a->in[1]), *g = p32(a->in[2]), *b = p32(a->in[3]);
-        uint16_t* y = p16(a->out[0]);
-        dims(4);
-        const int silu = flag(5), in_pad = flag(6), out_pad = flag(7);
-        if (!ok || i[4] < 1 || i[4] > INT32_MAX || (tadd && i[8] < i[3])) return bad();
-        const int n = (int)i[0], H = (int)i[1], W = (int)i[2], C = (int)i[3], groups = (int)i[4];
-        if (int rc = ensure(h, WS_SD0, sd_groupnorm_ws_floats(n, H * W, groups) * 4)) return rc;
-        HIP_TRY(sd_groupnorm(x, tadd, i[8], g, b, y, n, H, W, C, groups, f[0], silu, in_pad, out_pad, (float*)h->ws[WS_SD0].p, st, f16));
-        return TVC_OK;
-    }
-    case TVC_SD_OP_LAYERNORM: {
-        const uint16_t* x = p16(a->in[0]);
-        const float *g = p32(a->in[1]), *b = p32(a->in[2]);
-        const uint16_t* add = opt16(a->in[3]);
-        uint16_t *y = p16(a->out[0]), *sum_out = opt16(a->out[1]);
-        dims(1, 0);
-        if (!ok || i[1] < 1 || i[1] > INT32_MAX) return bad();
-        HIP_TRY(sd_layernorm_bf16(x, g, b, y, i[0], (int)i[1], f[0], st, add, sum_out, f16));
-        return TVC_OK;
-    }
-    case TVC_SD_OP_GEGLU: {
-        const uint16_t* in = p16(a->in[0]);
-        uint16_t* out = p16(a->out[0]);
-        dims(2);
-        if (!ok) return bad();
-        HIP_TRY(sd_geglu(in, out, i[0], (int)i[1], st, f16));
-        return TVC_OK;
-    }
-    case TVC_SD_OP_ADD: {
-        const uint16_t *x = p16(a->in[0]), *y = p16(a->in[1]);
-        uint16_t* out = p16(a->out[0]);
-        dims(1);
-        if (!ok) return bad();
-        HIP_TRY(sd_add_bf16(x, y, out, i[0], st, f16));
-        return TVC_OK;
-    }
-    case TVC_SD_OP_ADD_PADDED: {
-        const uint16_t *x = p16(a->in[0]), *y = p16(a->in[1]);
-        uint16_t* out = p16(a->out[0]);
-        dims(4);
-        if (!ok) return bad();
-        HIP_TRY(sd_add_padded(x, y, out, (int)i[0], (int)i[1], (int)i[2], (int)i[3], st, f16));
-        return TVC_OK;
-    }
-    case TVC_SD_OP_RELAYOUT: {
-        const uint16_t* in = p16(a->in[0]);
-        uint16_t* out = p16(a->out[0]);
-        dims(4);
-        const int in_pad = flag(4), out_pad = flag(5), up = flag(6);
-        if (!ok) return bad();
-        HIP_TRY(sd_relayout(in, out, (int)i[0], (int)i[1], (int)i[2], (int)i[3], in_pad, out_pad, up, st));
-        return TVC_OK;
-    }
-    case TVC_SD_OP_IM2COL3X3: {
-        const uint16_t* in = p16(a->in[0]);
-        uint16_t* out = p16(a->out[0]);
-        dims(4);
-        const int up = flag(5);
-        // 9 columns per source pixel of the (upsampled) source: the output's element count stays inside int32 too
-        if (!ok || i[4] < 1 || i[4] > INT32_MAX || i[0] * i[1] * i[2] * i[3] * (up ? 36 : 9) > INT32_MAX) return bad();
-        HIP_TRY(sd_im2col3x3(in, out, (int)i[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], up, st));
-        return TVC_OK;
-    }
-    case TVC_SD_OP_IM2COL_IN: {
-        const float* in = p32(a->in[0]);
-        uint16_t* out = p16(a->out[0]);
-        dims(4);
-        if (!ok || i[4] < 1 || i[4] > INT32_MAX) return bad();
-        HIP_TRY(sd_im2col_in(in, out, (int)i[0], (int)i[1], (int)i[2], (int)i[3], (int)i[4], f[0], st, f16));
-        return TVC_OK;
-    }
-    case TVC_SD_OP_CONCAT: {
-        const uint16_t *x = p16(a->in[0]), *y = p16(a->in[1]);
-        uint16_t* out = p16(a->out[0]);
-        dims(3);
-        if (!ok) return bad();
-        HIP_TRY(sd_concat(x, (int)i[0], y, (int)i[1], out, i[2], st));
-        return TVC_OK;
-    }
-    case TVC_SD_OP_CAST_SILU: {
-        const float* in = p32(a->in[0]);
-        uint16_t* out = (uint16_t*)a->out[0];
-        ok = ok && out && !((uintptr_t)out & 1);         // scalar 16-bit stores
-        dims(1);
-        const int silu = flag(1);
-        if (!ok) return bad();
-        HIP_TRY(sd_cast_silu(in, out, i[0], silu, st, f16));
-        return TVC_OK;
-    }
-    case TVC_SD_OP_TOKENS_TO_NCHW: {
-        const float* in = p32(a->in[0]);
-        float* out = p32(a->out[0]);
-        dims(4);
-        const int clamp = flag(5), in_pad = flag(6);
-        if (!ok || i[4] < i[1] || i[4] > INT32_MAX) return bad();
-        HIP_TRY(sd_tokens_to_nchw(in, i[4], out, (int)i[0], (int)i[1], (int)i[2], (int)i[3], f[0], f[1], clamp, in_pad, st));
-        return TVC_OK;
-    }
-    case TVC_SD_OP_POINTWISE_SMALL: {
-        const float *in = p32(a->in[0]), *w = p32(a->in[1]), *b = p32(a->in[2]);
-        float* out = p32(a->out[0]);
-        dims(3);
-        if (!ok) return bad();
-        HIP_TRY(sd_pointwise_small(in, w, b, out, (int)i[0], (int)i[1], (int)i[2], f[0], st));
-        return TVC_OK;
-    }
-    case TVC_SD_OP_CFG: {
-        const float* e = p32(a->in[0]);
-        float* out = p32(a->out[0]);
-        dims(1);
-        if (!ok) return bad();
-        HIP_TRY(sd_cfg(e, out, i[0], f[0], st));
-        return TVC_OK;
-    }
-    case TVC_SD_OP_LINCOMB: {
-        const float *sample = p32(a->in[0]), *e0 = p32(a->in[1]);
-        const float *e1 = opt32(a->in[2]), *e2 = opt32(a->in[3]), *e3 = opt32(a->in[4]);
-        float* out = p32(a->out[0]);
-        dims(1);
-        if (!ok) return bad();
-        HIP_TRY(sd_lincomb(out, sample, f[0], f[1], e0, f[2], e1, f[3], e2, f[4], e3, f[5], i[0], st));
-        return TVC_OK;
-    }
-    case TVC_SD_OP_SOFTMAX_ROWS: {
-        const float* s = p32(a->in[0]);
-        uint16_t* p = (uint16_t*)a->out[0];
-        ok = ok && p && !((uintptr_t)p & 1);
-        dims(2);
-        if (!ok || !(f[0] > 0.f)) return bad();
-        HIP_TRY(sd_softmax_rows(s, p, i[0], (int)i[1], f[0], st, f16));
-        return TVC_OK;
-    }
-    case TVC_SD_OP_NCHW_TO_TOKENS: {
-        const float* in = p32(a->in[0]);
-        uint16_t* out = (uint16_t*)a->out[0];
-        ok = ok && out && !((uintptr_t)out & 1);
-        dims(3);
-        if (!ok) return bad();
-        HIP_TRY(sd_nchw_to_tokens(in, out, (int)i[0], (int)i[1], (int)i[2], st, f16));
-        return TVC_OK;
-    }
-    case TVC_SD_OP_TOKENS16_TO_NCHW: {
-        const uint16_t* in = (const uint16_t*)a->in[0];
-        ok = ok && in && !((uintptr_t)in & 1);
-        float* out = p32(a->out[0]);
-        dims(3);
-        if (!ok) return bad();
-        HIP_TRY(sd_tokens_bf16_to_nchw(in, out, (int)i[0], (int)i[1], (int)i[2], st, f16));
-        return TVC_OK;
-    }
-    case TVC_SD_OP_TIMESTEP_EMBED: {
-        uint16_t* out = (uint16_t*)a->out[0];
-        ok = ok && out && !((uintptr_t)out & 1);
-        dims(2);
-        if (!ok || (i[1] & 1)) return bad();
-        HIP_TRY(sd_timestep_embed(out, (int)i[0], (int)i[1], f[0], st, f16));
-        return TVC_OK;
-    }
-    case TVC_SD_OP_TRANSPOSE: {
-        const uint16_t* in = (const uint16_t*)a->in[0];
-        uint16_t* out = (uint16_t*)a->out[0];
-        ok = ok && in && out && !(((uintptr_t)in | (uintptr_t)out) & 1);
-        dims(2);
-        if (!ok) return bad();
-        HIP_TRY(launch_transpose_bf16(in, out, (int)i[0], (int)i[1], st));
-        return TVC_OK;
-    }
-    }
-    return fail(h, TVC_E_INVALID, "tvc_sd_op: unknown op");
 }
 
 }  // extern "C"

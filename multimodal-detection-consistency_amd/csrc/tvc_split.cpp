@@ -21,8 +21,6 @@ namespace {
 
 struct SBufs { float *X, *QKV, *U, *D1, *D2, *CLS; uint16_t *Hs, *Ms; };
 
-int64_t pad_tile_rows(int64_t rows) { return (rows + 255) / 256 * 256 + 256; }
-
 SBufs split_bufs(tvc_handle* h, bool text) {
     const int wso = text ? WS_S_N : 0;
     SBufs b;
@@ -111,12 +109,12 @@ int split_ensure(tvc_handle* h, bool text, int n_seq, float** X) {
     const tvc_model_desc& m = h->desc;
     const tvc_tower_arch& a = text ? m.text : m.vision;
     const int P = (m.image_size / m.patch) * (m.image_size / m.patch), K = 3 * m.patch * m.patch, Kp = (K + 63) / 64 * 64;
-    const int64_t rp = pad_tile_rows((int64_t)n_seq * (text ? m.ctx : P + 1));     // GEMM operands: readable rows to the next tile (+ one)
+    const int64_t rp = tile_rows((int64_t)n_seq * (text ? m.ctx : P + 1));     // GEMM operands: readable rows to the next tile (+ one)
     const int wso = text ? WS_S_N : 0;
     size_t u_bytes = (size_t)rp * a.mlp * 4, m_bytes = (size_t)rp * a.mlp * 2 * 2;
     if (!text) {
         // the stem parks its fp32 im2col rows in U, their planes in Ms and the patch embeddings in QKV ([n * P, d] fits [rows, 3d])
-        const size_t u_min = (size_t)pad_tile_rows((int64_t)n_seq * P) * K * 4, m_min = (size_t)pad_tile_rows((int64_t)n_seq * P) * 2 * Kp * 2;
+        const size_t u_min = (size_t)tile_rows((int64_t)n_seq * P) * K * 4, m_min = (size_t)tile_rows((int64_t)n_seq * P) * 2 * Kp * 2;
         if (u_bytes < u_min) u_bytes = u_min;
         if (m_bytes < m_min) m_bytes = m_min;
     }
@@ -206,7 +204,7 @@ extern "C" int tvc_gemm_split(tvc_handle* h, const float* w_dev, const float* x_
         return fail(h, TVC_E_INVALID, "tvc_gemm_split: need K % 4 == 0, ld_out >= I and a multiple of 4");
     hipStream_t st = (hipStream_t)stream;
     const int Kp = (K + 63) / 64 * 64;
-    const int64_t Ip = ((int64_t)I + 255) / 256 * 256, Jp = pad_tile_rows(J);
+    const int64_t Ip = ((int64_t)I + 255) / 256 * 256, Jp = tile_rows(J);
     int rc;
     if ((rc = ensure(h, WS_SH, (size_t)Ip * 2 * Kp * 2))) return rc;
     if ((rc = ensure(h, WS_SM, (size_t)Jp * 2 * Kp * 2))) return rc;

@@ -16,7 +16,8 @@ the adds); the bank search (bank_cases below: every filter kernel, both tau kern
 shard merge; the children inherit TVC_BANK_RING / TVC_BANK_SKINNY / TVC_BANK_SKINNY_SAMPLE, so a run with all three at 0
 reaches bank_search_kernel<true> and the dense sample for small M); k-means on a bank slot and the IVF search (cluster_cases
 below: assign and update with an empty cluster and an out-of-range label, the probe, the scan with padding and with the select's
-LDS and global-memory paths).
+LDS and global-memory paths); the latent-diffusion generator end to end (sd_cases below: the UNet at two sizes, the VAE decode,
+the sampling loop on two streams and on one, chunked, and with v-prediction, all six block kinds, in bf16 and in fp16).
 """
 import argparse
 import importlib
@@ -177,6 +178,53 @@ def cluster_cases(pkg, save) -> None:
     eng.close()
 
 
+def sd_cases(pkg, save) -> None:
+    """Every latent-diffusion entry point that runs the model's host code (csrc/tvc_sd.cpp) at the toy geometry, in both 16-bit
+    formats: tvc_sd_unet (n = 2 at 16 x 16, n = 3 at 8 x 24), tvc_sd_vae_decode (n = 3), tvc_sd_generate of 6 steps with
+    TVC_OPT_SD_STREAMS 2 and 1, once in chunks (3 images at 96 x 96 latents under TVC_OPT_SD_ARENA_BYTES = 1 << 28, the option's
+    minimum: a pair needs over 100 MB there, so the images run as 2 + 1), 4 steps of a v-prediction model, and the six kinds of
+    tvc_sd_block."""
+    import dataclasses
+    import torch
+    L = pkg._lib
+    arch = pkg.SDArch(block_out_channels=(64, 128), down_block_attn=(True, False), layers_per_block=1, heads=8,
+                      cross_attention_dim=128, vae_block_out_channels=(64, 128), vae_layers_per_block=1, sample_size=16)
+    uw, vw = pkg.make_sd_weights(arch, seed=3)
+    g = torch.Generator().manual_seed(31)
+    lat = torch.randn((3, 4, 16, 16), generator=g)
+    lat_wide = torch.randn((3, 4, 8, 24), generator=g)
+    lat96 = torch.randn((3, 4, 96, 96), generator=g)
+    cond, uncond = torch.randn((3, arch.ctx, 128), generator=g), torch.randn((3, arch.ctx, 128), generator=g)
+    x64, x128, x256 = (torch.randn((2, c, hw, hw), generator=g) for c, hw in ((64, 16), (128, 8), (256, 8)))
+    temb = torch.randn((2, arch.time_dim), generator=g)
+    for prec in ("bf16", "fp16"):
+        eng = pkg.TVCEngine()
+        k = pkg.SDKernels(eng, arch, uw, vw, precision=prec)
+        save(f"sd_{prec}_unet_2x16x16", k.unet(lat[:2], 951.0, cond[:2]))
+        save(f"sd_{prec}_unet_3x8x24", k.unet(lat_wide, 1.0, cond))
+        save(f"sd_{prec}_vae_3", k.vae_decode(lat))
+        for streams in (2, 1):
+            eng.set_option(L.TVC_OPT_SD_STREAMS, streams)
+            out, img = k.generate(cond, uncond, lat, 6, 7.5)
+            save(f"sd_{prec}_gen6_streams{streams}_lat", out)
+            save(f"sd_{prec}_gen6_streams{streams}_img", img)
+        eng.set_option(L.TVC_OPT_SD_STREAMS, 2)
+        eng.set_option(L.TVC_OPT_SD_ARENA_BYTES, 1 << 28)
+        save(f"sd_{prec}_gen6_chunked_lat", k.generate(cond, uncond, lat96, 6, 7.5, decode=False)[0])
+        eng.set_option(L.TVC_OPT_SD_ARENA_BYTES, 48 << 30)
+        blocks = ((0, "down_blocks.0.resnets.0.", x64, 64, dict(temb=temb)), (0, "up_blocks.0.resnets.0.", x256, 128, dict(temb=temb)),
+                  (1, "down_blocks.0.attentions.0.", x64, 64, dict(ctx=cond[:2])),
+                  (2, "decoder.mid_block.attentions.0.", x128, 128, dict(vae=True)),
+                  (3, "down_blocks.0.resnets.0.conv1.", x64, 64, {}), (4, "down_blocks.0.downsamplers.0.conv.", x64, 64, {}),
+                  (5, "up_blocks.0.upsamplers.0.conv.", x128, 128, {}))
+        for j, (kind, prefix, x, cout, kw) in enumerate(blocks):
+            save(f"sd_{prec}_block{j}_kind{kind}", k.block(kind, prefix, x, cout, **kw))
+        kv = pkg.SDKernels(eng, dataclasses.replace(arch, prediction_type="v_prediction"), uw, vw, precision=prec)
+        save(f"sd_{prec}_gen4_vpred_lat", kv.generate(cond[:2], uncond[:2], lat[:2], 4, 7.5, decode=False)[0])
+        torch.cuda.synchronize()
+        eng.close()
+
+
 def child(out_dir: Path) -> None:
     import torch
     sys.path.insert(0, str(ROOT))
@@ -238,6 +286,7 @@ def child(out_dir: Path) -> None:
     eng.close()
     bank_cases(pkg, save)
     cluster_cases(pkg, save)
+    sd_cases(pkg, save)
 
 
 def main() -> int:

@@ -1,6 +1,8 @@
 """Writes stubs.cpp: a no-op definition of every kernel launcher declared in csrc/kernels.hpp (the host-only sanitizer
 build links the C-ABI's host code against these instead of the HIP kernels).  Launchers whose RESULT the host code reads
-back get a minimal host implementation: launch_text_lens_scan (dense rows)."""
+back get a minimal host implementation: launch_text_lens_scan (dense rows).  With --trace as a third argument every stub first
+writes its name and arguments to the stand-in's trace file (hip/hip_runtime.h: hip_trace_line); without it the output is
+unchanged."""
 import re
 import sys
 from pathlib import Path
@@ -33,10 +35,25 @@ special = {
     "launch_text_lens_scan": "{ for (int i = 0; i <= n_text; ++i) starts[i] = i * ctx; starts[n_text + 1] = ctx;"
                              " if (pfx) for (int i = 0; i < n_text; ++i) { pfx[i] = 0; pfx[n_text + i] = i * ctx; } return hipSuccess; }",
 }
+# --trace: launch_gemm_bf16 prints the fields of its GemmLaunch (the plane offsets it uses), every other launcher its arguments
+TRACE = len(sys.argv) > 3 and sys.argv[3] == "--trace"
+GEMM_TRACE = """    if (FILE* f = hip_trace()) {
+        auto put = [&](const auto&... a) { (hip_trace_arg(f, a), ...); };
+        fputs("launch_gemm_bf16", f);
+        put(L.A, L.B, L.lda, L.ldb, L.I, L.J, L.K, L.planes, L.splitk_small, L.splitk_fixed, L.a_rows_padded, L.b_rows_padded, L.bias, L.out,
+            L.ldo, L.epilogue, L.splitk_ws, L.splitk_ws_bytes, L.f16, stream);
+        fputs(" planes", f);
+        for (int p = 0; p < L.planes && p < 9; ++p) { hip_trace_arg(f, L.a_plane_off[p]); hip_trace_arg(f, L.b_plane_off[p]); }
+        fputc('\\n', f);
+    }
+"""
 for m in re.finditer(r"\bhipError_t\s+(\w+)\s*\(([^;{]*)\)\s*;", src):
     name, args = m.group(1), " ".join(m.group(2).split())
     args = re.sub(r"\s*=\s*[^,)]+", "", args)                # default arguments belong to the declaration
     body = special.get(name, "{ return hipSuccess; }")
+    if TRACE:
+        names = "".join(", " + re.search(r"(\w+)\s*$", a).group(1) for a in args.split(",") if a.strip() not in ("", "void"))
+        body = "{\n" + GEMM_TRACE + body[2:] if name == "launch_gemm_bf16" else f'{{ hip_trace_line("{name}"{names}); ' + body[2:]
     out.append(f"hipError_t {name}({args}) {body}")
 Path(sys.argv[2]).write_text("\n".join(out) + "\n")
 print(len(out) - 2, "stubs")

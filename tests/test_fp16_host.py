@@ -33,7 +33,7 @@ def test_fp16_mode_host_code_under_address_and_ub_sanitizers(tmp_path):
     subprocess.run([sys.executable, str(san / "gen_stubs.py"), str(csrc / "kernels.hpp"), str(stubs)], check=True)
     exe = tmp_path / "driver_f16"
     cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           f"-I{san}", f"-I{csrc}", "-x", "c++"] + [str(csrc / f) for f in ("tvc_abi.cpp", "tvc_precise.cpp", "tvc_split.cpp", "tvc_sd.cpp", "tvc_tower_op.cpp")] + \
+           f"-I{san}", f"-I{csrc}", "-x", "c++"] + [str(csrc / f) for f in ("tvc_abi.cpp", "tvc_precise.cpp", "tvc_split.cpp", "tvc_sd.cpp", "tvc_sd_op.cpp", "tvc_tower_op.cpp")] + \
           [str(stubs), str(ROOT / "tests" / "host_san_f16" / "driver.cpp"), "-o", str(exe)]
     b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert b.returncode == 0, b.stderr[-3000:]

@@ -110,7 +110,7 @@ def test_ivf_host_code_under_address_and_ub_sanitizers(tmp_path):
     stubs = tmp_path / "stubs.cpp"
     subprocess.run([sys.executable, str(san / "gen_stubs.py"), str(csrc / "kernels.hpp"), str(stubs)], check=True)
     exe = tmp_path / "driver_ivf"
-    srcs = ("tvc_abi.cpp", "tvc_precise.cpp", "tvc_split.cpp", "tvc_sd.cpp", "tvc_tower_op.cpp", "tvc_kmeans.cpp", "tvc_ivf.cpp")
+    srcs = ("tvc_abi.cpp", "tvc_precise.cpp", "tvc_split.cpp", "tvc_sd.cpp", "tvc_sd_op.cpp", "tvc_tower_op.cpp", "tvc_kmeans.cpp", "tvc_ivf.cpp")
     cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            f"-I{san}", f"-I{csrc}", "-x", "c++"] + [str(csrc / f) for f in srcs] + \
           [str(stubs), str(ROOT / "tests" / "host_san_ivf" / "driver.cpp"), "-o", str(exe)]

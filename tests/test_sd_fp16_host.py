@@ -125,7 +125,7 @@ def test_sd_fp16_host_code_under_address_and_ub_sanitizers(pkg, tmp_path):
             f.write(f"{n} {x.shape[0]} {x.numel() // x.shape[0]} {x.element_size()}\n")
     exe = tmp_path / "driver_sd_f16"
     cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           f"-I{san}", f"-I{csrc}", "-x", "c++"] + [str(csrc / f) for f in ("tvc_abi.cpp", "tvc_precise.cpp", "tvc_split.cpp", "tvc_sd.cpp", "tvc_tower_op.cpp")] + \
+           f"-I{san}", f"-I{csrc}", "-x", "c++"] + [str(csrc / f) for f in ("tvc_abi.cpp", "tvc_precise.cpp", "tvc_split.cpp", "tvc_sd.cpp", "tvc_sd_op.cpp", "tvc_tower_op.cpp")] + \
           [str(stubs), str(ROOT / "tests" / "host_san_sd_f16" / "driver.cpp"), "-o", str(exe)]
     b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert b.returncode == 0, b.stderr[-3000:]
