@@ -2,20 +2,8 @@
 //
 // One workgroup (4 waves) per (sequence, head).  The head's K and V live in
 // LDS for the whole workgroup (T <= 288 rows x 64), so the softmax is exact
-// and single-pass: no online rescale.  Each wave walks 16-query blocks:
-//
-//   S^T[key, q]  = K . Q^T      MFMA 16x16x32, A = K rows from LDS (ds_read_b128,
-//                               XOR-swizzled 128-B rows), B = Q straight from HBM
-//   softmax over keys           lane-local over the accumulator registers, then
-//                               two xor-shuffles across the 4 lane groups
-//   O^T[dh, q]   = V^T . P^T    A = V^T via ds_read_b64_tr_b16 (hardware
-//                               transpose of the row-major V image), B = P^T packed
-//                               from the S^T accumulators with NO lane movement
-//                               (k-slot order chosen to match the accumulator map)
-//
-// "Swapped" products keep the query on the lane (column) dimension, so row
-// statistics are per-lane scalars; a lane's output is 4 consecutive head dims per 16-wide tile, swapped between
-// neighbouring tiles (v_permlane16_swap) into 16-byte store pieces.
+// and single-pass: no online rescale.  Each wave walks 16-query blocks with the "swapped" products of attn_frag.hpp
+// (S^T = K . Q^T with Q straight from HBM, softmax lane-local + two xor-shuffles, O^T = V^T . P^T), stored as 16-byte pieces.
 //
 // A persistent form (item i + 1's K / V rows requested before item i's query blocks and written to LDS after them) was
 // built and measured in round 4 (git show 410b4a7:multimodal-detection-consistency_amd/csrc/attention.hip; EXPERIMENTS.md): bit-identical,
@@ -38,13 +26,9 @@
 // per-head pieces, not vector issue.  Hence the XCD-contiguous item order, the unconditional one-latency fill, the wait
 // for the next block's Q fragments placed BEFORE the block's stores (vmcnt counts stores), and the 16-byte stores.
 
-#include "common.hpp"
+#include "attn_frag.hpp"     // the swapped idiom's lane maps and fragments; K image ATT_KROW rows, V image ATT_VROW rows
 #include "kernels.hpp"
 #include "launch.hpp"
-
-#define ATT_DH 64
-#define ATT_KROW 128     // K image: 64 bf16 per row
-#define ATT_VROW 160     // V image: 64 bf16 + 32 B pad (conflict-free tr reads)
 
 // EXACT: every sequence has exactly MAXT key tiles (fixed-length, non-causal: the vision tower).
 // The per-tile guards become compile-time true, so the 16-key tiles of a query block are
@@ -101,23 +85,10 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
     const bool active = item < n_items;
     if (!active) item = n_items - 1;
     const int seq = item / heads, h = item - seq * heads;
-    int64_t row0;      // first of the sequence's own rows
-    int T;             // keys: P shared-prefix rows (from prow0) + the own rows
-    int P = 0;         // shared prefix length: queries are the own rows only (positions P .. T-1)
-    int64_t prow0 = 0;
-    if (starts) {
-        const int s0 = __builtin_amdgcn_readfirstlane(starts[seq]);
-        const int s1 = __builtin_amdgcn_readfirstlane(starts[seq + 1]);
-        row0 = s0; T = s1 - s0;
-        if (CAUSAL && pfx) {
-            P = __builtin_amdgcn_readfirstlane(pfx[seq]);
-            prow0 = __builtin_amdgcn_readfirstlane(pfx[n_seq + seq]);
-            T += P;
-        }
-    } else { row0 = (int64_t)seq * T_fixed; T = T_fixed; }
-    // packed row of key / position t
-    auto key_row = [&](int t) -> int64_t { return t < P ? prow0 + t : row0 + (t - P); };
-    if (T > MAXT * 16) T = MAXT * 16;      // host guarantees this; never index past the region
+    const SeqView<CAUSAL> sv(starts, pfx, T_fixed, seq, n_seq, MAXT * 16);
+    const int64_t row0 = sv.row0;
+    auto key_row = [&](int t) -> int64_t { return sv.key_row(t); };      // called directly, the causal forms' instruction streams move
+    const int T = sv.T, P = sv.P;          // keys (P shared-prefix rows + the own rows); the queries are the own rows only
     const int NT = EXACT ? MAXT : (T + 15) >> 4;          // key tiles of 16
     const int NP = (NT + 1) >> 1;          // key pairs of 32
     const int KT = NT * 16, VT = EXACT ? NT * 16 : NP * 32;   // EXACT: an unpaired last tile multiplies its own V rows by zeros
@@ -127,12 +98,9 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
     const int tsub = wsub * 64 + lane;     // thread index within the item's waves
 
     const int g = lane >> 4, r16 = lane & 15;
-    const int sw0 = ((0 + g) ^ ((lane >> 1) & 7)) << 4;
-    const int sw1 = ((4 + g) ^ ((lane >> 1) & 7)) << 4;
-    // transposed-read lane address: lane i of a 16-lane group supplies row (i>>2),
-    // columns 4*(i&3) .. +3 of a [4 keys][16 dh] block
-    const int tr_off = (4 * g + (r16 >> 2)) * ATT_VROW + ((r16 & 3) << 3);
-    const float scale_log2 = 0.125f * 1.4426950408889634f;   // dh^-0.5 * log2(e)
+    const int sw0 = swz_chunk(0 + g, lane), sw1 = swz_chunk(4 + g, lane);
+    const int tr_off = tr_lane_off<ATT_VROW>(g, r16);
+    const float scale_log2 = ATT_SCALE_LOG2;
     const int own = T - P;                     // query rows (all of them unless a prefix is shared)
     // Pooled form (the LAST layer of a tower: only the pooled token's output is ever read -- the class token
     // of the vision tower, the EOT token of the text tower): ONE query per sequence, at absolute position
@@ -141,11 +109,9 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
     int pool_pos = 0;
     if (pool_mode == 2) pool_pos = starts ? T - 1 : __builtin_amdgcn_readfirstlane(pool_row[seq]) - (int)row0;
     const int NQ = pool_mode ? 1 : (own + 15) >> 4;
-    // Masking costs nothing after the MFMA: the accumulator is INITIALISED with 0 or -inf
-    // (-inf + q.k = -inf).  Only the last key tile holds keys >= T.
-    f32x4_t pen_tail;
+    f32x4_t pen_tail;          // only the last key tile holds keys >= T
 #pragma unroll
-    for (int r = 0; r < 4; ++r) pen_tail[r] = ((NT - 1) * 16 + 4 * g + r >= T) ? -INFINITY : 0.f;
+    for (int r = 0; r < 4; ++r) pen_tail[r] = key_penalty((NT - 1) * 16 + 4 * g + r, T);
 
     // Q fragments come straight from HBM/L2: fetch the NEXT block's while this one computes
     auto q_ptr = [&](int qb) {
@@ -184,7 +150,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
         for (int i = 0; i < KIT; ++i) {
             const int idx = tsub + i * STEP;
             const int key = idx >> 3, c = idx & 7;
-            if (idx < KT * 8) *(u32x4_t*)(ldsK + key * ATT_KROW + ((c ^ ((key >> 1) & 7)) << 4)) = key < T ? kv[i] : u32x4_t{0u, 0u, 0u, 0u};
+            if (idx < KT * 8) *(u32x4_t*)(ldsK + key * ATT_KROW + swz_chunk(c, key)) = key < T ? kv[i] : u32x4_t{0u, 0u, 0u, 0u};
         }
 #pragma unroll
         for (int i = 0; i < VIT; ++i) {
@@ -217,9 +183,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
         const int qmin = pool_mode ? pool_pos : P + qb * 16;
         const int qmax = pool_mode ? pool_pos : qmin + 15;
         const int qpos = pool_mode ? pool_pos : P + qr;
-        // causal: keys up to the block's last query position
-        const int nt_c = (qmax >> 4) + 1;
-        const int nt_q = EXACT ? MAXT : (CAUSAL ? (nt_c < NT ? nt_c : NT) : NT);
+        const int nt_q = EXACT ? MAXT : sv.nt_q(qmax, NT);      // causal: keys up to the block's last query position
 
         int zoff = 0;
         asm volatile("" : "+v"(zoff));          // opaque 0: keeps the un-pinned K reads inside the loop
@@ -240,16 +204,15 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
                 const x8 a1 = t < KPIN ? kb[t < KPIN ? t : 0] : *(const x8*)(ldsK_i + (t * 16 + r16) * ATT_KROW + sw1);
                 s[t] = Op16<F16>::mfma(a1, bq1, s[t]);
             }
-            // IEEE-754-2019 maximum (NaN-propagating): hipcc emits v_maximum3_f32 with no canonicalising copy of the
-            // MFMA outputs -- 54 max instructions per block where fmaxf costs 121.  A NaN score makes the query's
+            // mx3 (v_maximum3_f32): 54 max instructions per block where fmaxf costs 121.  A NaN score makes the query's
             // output NaN either way.
             float m0 = -INFINITY, m1 = -INFINITY;
 #pragma unroll
             for (int t = 0; t < MAXT; ++t) {
-                m0 = __builtin_elementwise_maximum(m0, __builtin_elementwise_maximum(s[t][0], s[t][1]));
-                m1 = __builtin_elementwise_maximum(m1, __builtin_elementwise_maximum(s[t][2], s[t][3]));
+                m0 = mx3(m0, mx3(s[t][0], s[t][1]));
+                m1 = mx3(m1, mx3(s[t][2], s[t][3]));
             }
-            mx = __builtin_elementwise_maximum(m0, m1);
+            mx = mx3(m0, m1);
         } else {
 #pragma unroll
         for (int t = 0; t < MAXT; ++t) {
@@ -259,7 +222,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
                 if (CAUSAL && t * 16 + 15 > qmin) {      // tile reaches past the block's first query position
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        if (t * 16 + 4 * g + r > qpos) c0[r] = -INFINITY;
+                        if (sv.hidden(t * 16 + 4 * g + r, qpos)) c0[r] = -INFINITY;
                 }
                 const char* kr = ldsK + (t * 16 + r16) * ATT_KROW;
                 const x8 a0 = *(const x8*)(kr + sw0);
@@ -270,8 +233,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
             }
         }
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        mx = group_max4(mx);
         const float mxs = mx * scale_log2;
 
 #pragma unroll
@@ -287,8 +249,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
         // and two cross-lane shuffles per query block sat on the vector issue slots that bound it).  The sum is
         // over the SAME bf16-rounded probabilities the numerator uses.
         f32x4_t osum = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        constexpr uint32_t one2 = Op16<F16>::ONE2;
-        const x8 ones = __builtin_bit_cast(x8, u32x4_t{one2, one2, one2, one2});
+        const x8 ones = ones8<F16>();
 
         f32x4_t o[4];
 #pragma unroll
@@ -300,23 +261,11 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
                 // k-slots j<4: keys 16*t0 + 4g + j ; j>=4: keys 16*t1 + 4g + (j-4)
                 const f32x4_t p0 = s[t0];
                 const f32x4_t p1 = (t1 < MAXT) ? s[t1 < MAXT ? t1 : 0] : f32x4_t{0.f, 0.f, 0.f, 0.f};
-                u32x4_t pk;
-                pk[0] = Op16<F16>::pack2(p0[0], p0[1]);
-                pk[1] = Op16<F16>::pack2(p0[2], p0[3]);
-                pk[2] = Op16<F16>::pack2(p1[0], p1[1]);
-                pk[3] = Op16<F16>::pack2(p1[2], p1[3]);
-                const x8 pb = __builtin_bit_cast(x8, pk);
+                const x8 pb = pack8<F16>(p0, p1);
 #pragma unroll
                 for (int md = 0; md < 4; ++md) {
                     const char* vb = ldsV + tr_off + md * 32;
-                    const bf16x4_t v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                        (__attribute__((address_space(3))) bf16x4_t*)(vb + t0 * 16 * ATT_VROW));
-                    const bf16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                        (__attribute__((address_space(3))) bf16x4_t*)(vb + ((EXACT && t1 >= MAXT) ? t0 : t1) * 16 * ATT_VROW));
-                    bf16x8_t a;
-                    a[0] = v0[0]; a[1] = v0[1]; a[2] = v0[2]; a[3] = v0[3];
-                    a[4] = v1[0]; a[5] = v1[1]; a[6] = v1[2]; a[7] = v1[3];
-                    o[md] = Op16<F16>::mfma(__builtin_bit_cast(x8, a), pb, o[md]);
+                    o[md] = Op16<F16>::mfma(tr16_frag<F16>(vb + t0 * 16 * ATT_VROW, vb + ((EXACT && t1 >= MAXT) ? t0 : t1) * 16 * ATT_VROW), pb, o[md]);
                 }
                 osum = Op16<F16>::mfma(ones, pb, osum);
             }
@@ -328,21 +277,13 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(const uint16
         // products are done.
         asm volatile("" : "+v"(nq0), "+v"(nq1));
         const float lsum = osum[0];          // every row of the ones tile holds the column (= query) sum
-        // A lane's 4 features per 16-wide tile are 8 B; swapping 16-lane rows between the tiles md and md + 1
-        // (v_permlane16_swap, as the GEMM's bf16 epilogue does) leaves every lane with 8 consecutive features: two 16-byte
-        // stores per lane and 64 contiguous bytes per query row and instruction, instead of four 8-byte stores that
-        // scatter 32-byte pieces.  The partner lanes carry the same query column, so the swap sits outside the mask.
+        // two 16-byte stores per lane (swap_pack16) instead of four 8-byte stores that scatter 32-byte pieces
         const float inv = 1.0f / lsum;
         u32x4_t ow[2];
 #pragma unroll
-        for (int mp = 0; mp < 2; ++mp) {
-            const f32x4_t v0 = o[2 * mp] * inv, v1 = o[2 * mp + 1] * inv;
-            const auto r0 = __builtin_amdgcn_permlane16_swap(Op16<F16>::pack2(v0[0], v0[1]), Op16<F16>::pack2(v1[0], v1[1]), false, false);
-            const auto r1 = __builtin_amdgcn_permlane16_swap(Op16<F16>::pack2(v0[2], v0[3]), Op16<F16>::pack2(v1[2], v1[3]), false, false);
-            ow[mp][0] = r0[0]; ow[mp][1] = r1[0]; ow[mp][2] = r0[1]; ow[mp][3] = r1[1];
-        }
+        for (int mp = 0; mp < 2; ++mp) ow[mp] = swap_pack16<F16>(o[2 * mp] * inv, o[2 * mp + 1] * inv);
         if (pool_mode ? (r16 == 0) : (qr < own)) {
-            uint16_t* op = out + (pool_mode ? (int64_t)seq : row0 + qr) * (int64_t)width + h * ATT_DH + (g & 1) * 16 + (g >> 1) * 8;
+            uint16_t* op = swap_store_ptr(out + (pool_mode ? (int64_t)seq : row0 + qr) * (int64_t)width + h * ATT_DH, g);
             ATT_ST_O((u32x4_t*)op, ow[0]);
             ATT_ST_O((u32x4_t*)(op + 32), ow[1]);
         }

@@ -2,7 +2,7 @@
 // attack needs (src/attacks/pgd_attack.py:456-486).  Non-causal, fixed-length
 // sequences of T <= 288 tokens, head_dim 64: everything of one (sequence, head) fits in LDS, so the scores are
 // recomputed (never stored) and the softmax is exact, as in the forward kernel (attention.hip), whose "swapped"
-// MFMA idiom (the reduction-free index on the lane) both passes reuse:
+// MFMA idiom (the reduction-free index on the lane; attn_frag.hpp) both passes reuse:
 //
 //   pass A  (lane = query)  S^T = K Q^T,  P,  dP^T = V dO^T,  delta = rowsum(P * dP),  dS = P * (dP - delta) / 8,
 //                           dQ^T = K^T dS^T;   writes dQ and the per-(row, head) softmax statistics
@@ -12,63 +12,24 @@
 // Operands read along rows come from LDS by ds_read_b128, operands read along columns by ds_read_b64_tr_b16;
 // ONE image per tensor with 160-byte rows serves both (conflict-free for both read kinds: rows 8 apart differ
 // by 32 dwords, the 16 lanes a ds_read_b128 services together hit 16 distinct 16-byte slots).
-#include "common.hpp"
+#include "attn_frag.hpp"     // the swapped idiom's lane maps and fragments, and the one-latency fill_two_images
 #include "kernels.hpp"
 #include "launch.hpp"
 
-#define ATT_DH 64
-#define ATT_ROW 160
 #ifndef DKV_NW
 #define DKV_NW 8         // waves per workgroup of the 257-token dK / dV kernel (4: 741 us per call, 8: ~325)
 #endif
 
 namespace {
 
-// Fill two [rows_pad][160 B] images with `T` rows of 64 bf16 each, taken from qkv-like rows (zero beyond T).  ALL loads of
-// both images are issued before the first LDS write and none sits behind a condition (row index clamped, zeros selected at
-// the write), so a workgroup pays one memory latency for its operands: the first cut -- a load, a wait and an LDS write
-// per 16-byte piece and loop trip -- paid eighteen in series (attention.hip's fill, round 3).
-// SWZ_B: image b has 128-byte rows with the 16-byte chunk c of row r stored at chunk c ^ ((r >> 1) & 7) (row reads only:
-// conflict-free ds_read_b128, as attention.hip's K image) instead of the padded 160-byte rows both read kinds need.
-template <int MAXROWS, bool SWZ_B = false, int NTHR = 256>
-__device__ __forceinline__ void fill_two_images(char* lds_a, const uint16_t* __restrict__ src_a, int64_t ld_a, int col_a, int rows_a,
-                                                char* lds_b, const uint16_t* __restrict__ src_b, int64_t ld_b, int col_b, int rows_b,
-                                                int64_t row0, int T, int tid) {
-    constexpr int NIT = (MAXROWS * 8 + NTHR - 1) / NTHR;
-    u32x4_t va[NIT], vb[NIT];
-#pragma unroll
-    for (int i = 0; i < NIT; ++i) {
-        const int idx = tid + i * NTHR, r = idx >> 3, c = idx & 7;
-        const int rc = r < T ? r : T - 1;
-        va[i] = __builtin_nontemporal_load((const u32x4_t*)(src_a + (row0 + rc) * ld_a + col_a + c * 8));
-        vb[i] = __builtin_nontemporal_load((const u32x4_t*)(src_b + (row0 + rc) * ld_b + col_b + c * 8));
-    }
-#pragma unroll
-    for (int i = 0; i < NIT; ++i) {
-        const int idx = tid + i * NTHR, r = idx >> 3, c = idx & 7;
-        const u32x4_t z = u32x4_t{0u, 0u, 0u, 0u};
-        if (r < rows_a) *(u32x4_t*)(lds_a + r * ATT_ROW + (c << 4)) = r < T ? va[i] : z;
-        if (r < rows_b) {
-            if (SWZ_B) *(u32x4_t*)(lds_b + r * 128 + ((c ^ ((r >> 1) & 7)) << 4)) = r < T ? vb[i] : z;
-            else *(u32x4_t*)(lds_b + r * ATT_ROW + (c << 4)) = r < T ? vb[i] : z;
-        }
-    }
-}
-
 __device__ __forceinline__ bf16x8_t row_frag(const char* img, int row, int ks, int g) {
-    return *(const bf16x8_t*)(img + row * ATT_ROW + ((ks * 4 + g) << 4));
+    return *(const bf16x8_t*)(img + row * ATT_VROW + ((ks * 4 + g) << 4));
 }
 
-// A operand [16 x 32] = columns (dh md*16 ..) of the rows of two 16-row tiles t0, t1 (k-slots j < 4: tile t0 rows
-// 4g + j, j >= 4: tile t1) -- the transposed read of attention.hip
+// A operand [16 x 32] = columns (dh md*16 ..) of the rows of two 16-row tiles t0, t1 of an ATT_VROW image (tr16_frag)
 __device__ __forceinline__ bf16x8_t tr_frag(const char* img, int tr_off, int md, int t0, int t1) {
     const char* vb = img + tr_off + md * 32;
-    const bf16x4_t v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)(vb + t0 * 16 * ATT_ROW));
-    const bf16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)(vb + t1 * 16 * ATT_ROW));
-    bf16x8_t a;
-    a[0] = v0[0]; a[1] = v0[1]; a[2] = v0[2]; a[3] = v0[3];
-    a[4] = v1[0]; a[5] = v1[1]; a[6] = v1[2]; a[7] = v1[3];
-    return a;
+    return tr16_frag<false>(vb + t0 * 16 * ATT_VROW, vb + t1 * 16 * ATT_VROW);
 }
 
 }  // namespace
@@ -93,7 +54,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq_kernel(const uint16_t
     // K [NT*16][160]: row reads (S) and transposed reads (dQ); V [NT*16][128, swizzled]: row reads (dP).  78.3 KB at 257
     // tokens: two workgroups per CU (the first cut held 89.6 KB and one).
     char* ldsK = smem;
-    char* ldsV = smem + NT * 16 * ATT_ROW;
+    char* ldsV = smem + NT * 16 * ATT_VROW;
     const int g = lane >> 4, r16 = lane & 15;
     const int NQ = NT;
     // the Q / dO fragments of a block come straight from HBM: fetched one block ahead (the first block's before the fill)
@@ -110,12 +71,12 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq_kernel(const uint16_t
     fill_two_images<MAXT * 16, true>(ldsK, qkv, ld, width + h * ATT_DH, NT * 16, ldsV, qkv, ld, 2 * width + h * ATT_DH, NT * 16, row0, T, tid);
     __syncthreads();
 
-    const int tr_off = (4 * g + (r16 >> 2)) * ATT_ROW + ((r16 & 3) << 3);
-    const int vsw0 = ((0 + g) ^ ((lane >> 1) & 7)) << 4, vsw1 = ((4 + g) ^ ((lane >> 1) & 7)) << 4;     // swizzled chunk of the V image
-    const float scale_log2 = 0.125f * 1.4426950408889634f;
+    const int tr_off = tr_lane_off<ATT_VROW>(g, r16);
+    const int vsw0 = swz_chunk(0 + g, lane), vsw1 = swz_chunk(4 + g, lane);     // swizzled chunk of the V image
+    const float scale_log2 = ATT_SCALE_LOG2;
     f32x4_t pen_tail;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) pen_tail[r] = ((NT - 1) * 16 + 4 * g + r >= T) ? -INFINITY : 0.f;
+    for (int r = 0; r < 4; ++r) pen_tail[r] = key_penalty((NT - 1) * 16 + 4 * g + r, T);
     for (int qb = wave; qb < NQ; qb += 4) {
         const int qr = qb * 16 + r16;
         const bf16x8_t bq0 = nq0, bq1 = nq1, bd0 = nd0, bd1 = nd1;
@@ -124,7 +85,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq_kernel(const uint16_t
         // dP^T = V dO^T is multiplied TWICE (once for delta = rowsum(P * dP), once for dS) instead of being kept: 72 fewer
         // live registers per lane, which is what lets two workgroups share a CU; the matrix pipe has the time.
         auto dp_tile = [&](int t) __attribute__((always_inline)) {
-            const char* vr = ldsV + (t * 16 + r16) * 128;
+            const char* vr = ldsV + (t * 16 + r16) * ATT_KROW;
             const f32x4_t d0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8_t*)(vr + vsw0), bd0, f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
             return __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8_t*)(vr + vsw1), bd1, d0, 0, 0, 0);
         };
@@ -140,8 +101,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq_kernel(const uint16_t
                 mx = fmaxf(mx, fmaxf(fmaxf(s[t][0], s[t][1]), fmaxf(s[t][2], s[t][3])));
             }
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        mx = group_max4(mx);
         const float mxs = mx * scale_log2;
         float lsum = 0.f, dl = 0.f;
 #pragma unroll
@@ -157,8 +117,8 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq_kernel(const uint16_t
                 }
             }
         }
-        lsum += __shfl_xor(lsum, 16, 64); lsum += __shfl_xor(lsum, 32, 64);
-        dl += __shfl_xor(dl, 16, 64); dl += __shfl_xor(dl, 32, 64);
+        lsum = group_sum4(lsum);
+        dl = group_sum4(dl);
         const float inv = 1.0f / lsum;
         const float delta = dl * inv;
         // dS^T = P (dP - delta) / 8, packed for the dQ product
@@ -179,10 +139,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq_kernel(const uint16_t
 #pragma unroll
                     for (int r = 0; r < 4; ++r) e1[r] = s[t1 < MAXT ? t1 : 0][r] * k8 * (d1[r] - delta);
                 }
-                u32x4_t pk;
-                pk[0] = pack_bf16x2(e0[0], e0[1]); pk[1] = pack_bf16x2(e0[2], e0[3]);
-                pk[2] = pack_bf16x2(e1[0], e1[1]); pk[3] = pack_bf16x2(e1[2], e1[3]);
-                const bf16x8_t pb = __builtin_bit_cast(bf16x8_t, pk);
+                const bf16x8_t pb = pack8<false>(e0, e1);
 #pragma unroll
                 for (int md = 0; md < 4; ++md)      // a tile without a partner multiplies its own rows by zeros
                     o[md] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_frag(ldsK, tr_off, md, t0, t1 < NT ? t1 : t0), pb, o[md], 0, 0, 0);
@@ -191,13 +148,13 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq_kernel(const uint16_t
         asm volatile("" : "+v"(nq0), "+v"(nq1), "+v"(nd0), "+v"(nd1));      // the next block's fragments are waited for here, not behind the stores
         u32x4_t ow[2];
 #pragma unroll
-        for (int mp = 0; mp < 2; ++mp) {           // 16-byte stores: v_permlane16_swap between the tiles md, md + 1 (attention.hip)
+        for (int mp = 0; mp < 2; ++mp) {           // swap_pack16's text: through the call, dq<18>'s registers are allocated differently (EXPERIMENTS.md)
             const auto r0 = __builtin_amdgcn_permlane16_swap(pack_bf16x2(o[2 * mp][0], o[2 * mp][1]), pack_bf16x2(o[2 * mp + 1][0], o[2 * mp + 1][1]), false, false);
             const auto r1 = __builtin_amdgcn_permlane16_swap(pack_bf16x2(o[2 * mp][2], o[2 * mp][3]), pack_bf16x2(o[2 * mp + 1][2], o[2 * mp + 1][3]), false, false);
             ow[mp][0] = r0[0]; ow[mp][1] = r1[0]; ow[mp][2] = r0[1]; ow[mp][3] = r1[1];
         }
         if (qr < T) {
-            uint16_t* op = dqkv + (row0 + qr) * ld + h * ATT_DH + (g & 1) * 16 + (g >> 1) * 8;
+            uint16_t* op = swap_store_ptr(dqkv + (row0 + qr) * ld + h * ATT_DH, g);
             *(u32x4_t*)op = ow[0];
             *(u32x4_t*)(op + 32) = ow[1];
             if (g == 0) *(f32x4_t*)(stats + ((row0 + qr) * heads + h) * 4) = f32x4_t{mxs, inv, delta, 0.f};
@@ -226,8 +183,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void attention_bwd_dkv_kernel(cons
     const int64_t row0 = (int64_t)seq * T, ld = 3 * (int64_t)width;
     const int NT = (T + 15) >> 4, NP = XNP > 0 ? XNP : (NT + 1) >> 1;
     char* ldsQ = smem;                                   // [NP*32][160] queries: row reads (S) + transposed reads (dK)
-    char* ldsO = smem + NP * 32 * ATT_ROW;               // [NP*32][160] dO: row reads (dP) + transposed reads (dV)
-    float* ldsS = (float*)(smem + 2 * NP * 32 * ATT_ROW);    // [NP*32][4] statistics per query
+    char* ldsO = smem + NP * 32 * ATT_VROW;               // [NP*32][160] dO: row reads (dP) + transposed reads (dV)
+    float* ldsS = (float*)(smem + 2 * NP * 32 * ATT_VROW);    // [NP*32][4] statistics per query
     const int g = lane >> 4, r16 = lane & 15;
     // this lane's key: its K / V fragments come straight from HBM, fetched one key block ahead (the first before the fill)
     bf16x8_t nk0, nk1, nv0, nv1;
@@ -247,8 +204,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void attention_bwd_dkv_kernel(cons
     }
     __syncthreads();
 
-    const int tr_off = (4 * g + (r16 >> 2)) * ATT_ROW + ((r16 & 3) << 3);
-    const float scale_log2 = 0.125f * 1.4426950408889634f;
+    const int tr_off = tr_lane_off<ATT_VROW>(g, r16);
+    const float scale_log2 = ATT_SCALE_LOG2;
     for (int kb = wave; kb < NT; kb += NW) {
         const int kc = kb * 16 + r16;                    // this lane's key
         const bool kvalid = kc < T;
@@ -277,12 +234,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void attention_bwd_dkv_kernel(cons
                     dsv[w2][r] = p * 0.125f * (dp[r] - st[2]);
                 }
             }
-            u32x4_t pk, sk;
-            pk[0] = pack_bf16x2(pv[0][0], pv[0][1]); pk[1] = pack_bf16x2(pv[0][2], pv[0][3]);
-            pk[2] = pack_bf16x2(pv[1][0], pv[1][1]); pk[3] = pack_bf16x2(pv[1][2], pv[1][3]);
-            sk[0] = pack_bf16x2(dsv[0][0], dsv[0][1]); sk[1] = pack_bf16x2(dsv[0][2], dsv[0][3]);
-            sk[2] = pack_bf16x2(dsv[1][0], dsv[1][1]); sk[3] = pack_bf16x2(dsv[1][2], dsv[1][3]);
-            const bf16x8_t pb = __builtin_bit_cast(bf16x8_t, pk), sb = __builtin_bit_cast(bf16x8_t, sk);
+            const bf16x8_t pb = pack8<false>(pv[0], pv[1]), sb = pack8<false>(dsv[0], dsv[1]);
 #pragma unroll
             for (int md = 0; md < 4; ++md) {
                 dv[md] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_frag(ldsO, tr_off, md, 2 * u, 2 * u + 1), pb, dv[md], 0, 0, 0);
@@ -299,16 +251,12 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void attention_bwd_dkv_kernel(cons
         asm volatile("" : "+v"(nk0), "+v"(nk1), "+v"(nv0), "+v"(nv1));      // the next block's fragments are waited for here, not behind the stores
         u32x4_t wk[2], wv[2];
 #pragma unroll
-        for (int mp = 0; mp < 2; ++mp) {           // 16-byte stores: v_permlane16_swap between the tiles md, md + 1 (attention.hip)
-            auto r0 = __builtin_amdgcn_permlane16_swap(pack_bf16x2(dk[2 * mp][0], dk[2 * mp][1]), pack_bf16x2(dk[2 * mp + 1][0], dk[2 * mp + 1][1]), false, false);
-            auto r1 = __builtin_amdgcn_permlane16_swap(pack_bf16x2(dk[2 * mp][2], dk[2 * mp][3]), pack_bf16x2(dk[2 * mp + 1][2], dk[2 * mp + 1][3]), false, false);
-            wk[mp][0] = r0[0]; wk[mp][1] = r1[0]; wk[mp][2] = r0[1]; wk[mp][3] = r1[1];
-            r0 = __builtin_amdgcn_permlane16_swap(pack_bf16x2(dv[2 * mp][0], dv[2 * mp][1]), pack_bf16x2(dv[2 * mp + 1][0], dv[2 * mp + 1][1]), false, false);
-            r1 = __builtin_amdgcn_permlane16_swap(pack_bf16x2(dv[2 * mp][2], dv[2 * mp][3]), pack_bf16x2(dv[2 * mp + 1][2], dv[2 * mp + 1][3]), false, false);
-            wv[mp][0] = r0[0]; wv[mp][1] = r1[0]; wv[mp][2] = r0[1]; wv[mp][3] = r1[1];
+        for (int mp = 0; mp < 2; ++mp) {           // 16-byte stores
+            wk[mp] = swap_pack16<false>(dk[2 * mp], dk[2 * mp + 1]);
+            wv[mp] = swap_pack16<false>(dv[2 * mp], dv[2 * mp + 1]);
         }
         if (kvalid) {
-            uint16_t* ok = dqkv + (row0 + kc) * ld + width + h * ATT_DH + (g & 1) * 16 + (g >> 1) * 8;
+            uint16_t* ok = swap_store_ptr(dqkv + (row0 + kc) * ld + width + h * ATT_DH, g);
             uint16_t* ov = ok + width;
             *(u32x4_t*)ok = wk[0]; *(u32x4_t*)(ok + 32) = wk[1];
             *(u32x4_t*)ov = wv[0]; *(u32x4_t*)(ov + 32) = wv[1];
@@ -323,8 +271,8 @@ hipError_t launch_attention_bwd(const uint16_t* qkv, const uint16_t* dao, uint16
     if (n_seq <= 0) return hipSuccess;
     if (T < 1 || T > 288 || heads < 1) return hipErrorInvalidValue;
     const int NT = (T + 15) / 16, NP = (NT + 1) / 2;
-    const size_t lds_a = (size_t)NT * 16 * ATT_ROW + (size_t)NT * 16 * 128;
-    const size_t lds_b = (size_t)2 * NP * 32 * ATT_ROW + (size_t)NP * 32 * 16;
+    const size_t lds_a = (size_t)NT * 16 * ATT_VROW + (size_t)NT * 16 * ATT_KROW;
+    const size_t lds_b = (size_t)2 * NP * 32 * ATT_VROW + (size_t)NP * 32 * 16;
     constexpr size_t MAX_LDS = 150 * 1024;
     const dim3 grid(n_seq * heads), block(256);
     const hipError_t st = NT > 4 ? launch<attention_bwd_dq_kernel<18>, MAX_LDS>(grid, block, lds_a, stream, qkv, dao, dqkv, stats_ws, T, heads)

@@ -3,7 +3,7 @@
 // 40, 48, 56, 64, 80, 96, 128, 160).
 //
 // One workgroup of NW (4 or 8) waves per (NW * 16 * QB queries, head, sample); keys / values stream through LDS in tiles of 64 with an
-// online softmax.  The products are "swapped" as in attention.hip so that the query sits on the lane (column) index:
+// online softmax.  The products are "swapped" (attn_frag.hpp) so that the query sits on the lane (column) index:
 //   S^T[key, q] = K . Q^T     MFMA 16x16x32: A = K rows from LDS (ds_read_b128), B = Q fragments held in registers
 //   O^T[d, q]  += V^T . P^T   A = V^T by ds_read_b64_tr_b16 (hardware transpose of the row-major V tile), B = P^T packed
 //                             from the S^T accumulators with no lane movement
@@ -24,26 +24,12 @@
 // probabilities / outputs are rounded to fp16.  The lazy maximum keeps the probabilities <= 2^8, far inside fp16's range;
 // a probability below fp16's subnormal floor (2^-24 of the row's reference maximum) becomes 0, where bf16 would keep it with
 // 8 bits: it is below half an ulp of the row sum either way.  Inputs beyond 65504 are the caller's +-inf (never clamped).
-#include "common.hpp"
+#include "attn_frag.hpp"
 #include "kernels.hpp"
 #include "launch.hpp"
 #include <cstdlib>
 
 namespace {
-
-__device__ __forceinline__ float mx3(float a, float b) { return __builtin_elementwise_maximum(a, b); }
-
-// Two transposed 8-byte LDS reads (ds_read_b64_tr_b16) -> one MFMA A fragment of 8.  The instruction moves 16-bit words, so
-// both formats read through the bf16-typed builtin and the fragment is bit-cast to the format's x8 (as attention.hip does).
-template <bool F16>
-__device__ __forceinline__ typename Op16<F16>::x8 read_tr16_pair(const char* p0, const char* p1) {
-    const bf16x4_t v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)p0);
-    const bf16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)p1);
-    bf16x8_t a;
-    a[0] = v0[0]; a[1] = v0[1]; a[2] = v0[2]; a[3] = v0[3];
-    a[4] = v1[0]; a[5] = v1[1]; a[6] = v1[2]; a[7] = v1[3];
-    return __builtin_bit_cast(typename Op16<F16>::x8, a);
-}
 
 template <int DH, int QB, int NW>
 struct FaCfg {
@@ -171,14 +157,12 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && DH <= 48) ? 4 : 1)    /* = FaC
         }
     };
 
-    // transposed-read lane address (attention.hip): lane i of a 16-lane group supplies key row 4 g + (i >> 2),
-    // head dims 4 (i & 3) .. + 3 of a [16 keys][16 dims] block
-    const int tr_off = (4 * g + (r16 >> 2)) * C::VROW + ((r16 & 3) << 3);
+    const int tr_off = tr_lane_off<C::VROW>(g, r16);
 
     // Softmax bookkeeping per 16-query block (second session of round 4; the tile loop is bound by vector issue at head_dim
     // 40: 0.47 clocks per score and SIMD against 0.22 of MFMA):
     //  * the row sums come out of the matrix pipe -- one more "V^T tile" of ones per 32 keys gives sum_k P[k, q] in every
-    //    accumulator row (as attention.hip does), over the SAME bf16-rounded probabilities the numerator uses and over all
+    //    accumulator row (ones8, attn_frag.hpp), over the SAME bf16-rounded probabilities the numerator uses and over all
     //    four lane groups' keys at once: 16 adds per block and tile and the two closing shuffles less;
     //  * the reference maximum `m_run` is LAZY: it moves (and the running output / sum are rescaled) only when the true
     //    maximum has grown by more than 2^8 in the exponent's units -- the probabilities are then at most 2^8 instead of
@@ -187,7 +171,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && DH <= 48) ? 4 : 1)    /* = FaC
     //    block and tile are skipped by a wave-uniform branch.
     f32x4_t o[QB][DV], osum[QB];
     float m_run[QB];
-    const x8 ones = __builtin_bit_cast(x8, u32x4_t{Op16<F16>::ONE2, Op16<F16>::ONE2, Op16<F16>::ONE2, Op16<F16>::ONE2});
+    const x8 ones = ones8<F16>();
 #pragma unroll
     for (int u = 0; u < QB; ++u) {
         m_run[u] = -INFINITY;
@@ -213,7 +197,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && DH <= 48) ? 4 : 1)    /* = FaC
             f32x4_t init = f32x4_t{0.f, 0.f, 0.f, 0.f};
             if (ragged) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) init[r] = (key0 + t * 16 + 4 * g + r >= Tk) ? -INFINITY : 0.f;
+                for (int r = 0; r < 4; ++r) init[r] = key_penalty(key0 + t * 16 + 4 * g + r, Tk);
             }
 #pragma unroll
             for (int u = 0; u < QB; ++u) s[u][t] = init;
@@ -232,8 +216,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && DH <= 48) ? 4 : 1)    /* = FaC
             float mx = mx3(mx3(s[u][0][0], s[u][0][1]), mx3(s[u][0][2], s[u][0][3]));
 #pragma unroll
             for (int t = 1; t < 4; ++t) mx = mx3(mx, mx3(mx3(s[u][t][0], s[u][t][1]), mx3(s[u][t][2], s[u][t][3])));
-            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            mx = group_max4(mx);
             const float m_new = fmaxf(m_run[u], mx);          // finite: every tile holds at least one key < Tk
             // a row's first tile: m_run = -inf, so the difference is +inf and the reference is set (alpha = 0 on zeros)
             const bool move = (m_new - m_run[u]) * scale_log2 > 8.0f;
@@ -251,11 +234,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && DH <= 48) ? 4 : 1)    /* = FaC
 #pragma unroll
                 for (int r = 0; r < 4; ++r) s[u][t][r] = __builtin_amdgcn_exp2f(fmaf(s[u][t][r], scale_log2, -mns));
 #pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                const f32x4_t p0 = s[u][2 * kk], p1 = s[u][2 * kk + 1];
-                pb[u][kk] = __builtin_bit_cast(x8, u32x4_t{Op16<F16>::pack2(p0[0], p0[1]), Op16<F16>::pack2(p0[2], p0[3]),
-                                                            Op16<F16>::pack2(p1[0], p1[1]), Op16<F16>::pack2(p1[2], p1[3])});
-            }
+            for (int kk = 0; kk < 2; ++kk) pb[u][kk] = pack8<F16>(s[u][2 * kk], s[u][2 * kk + 1]);
         }
         // ---- O^T += V^T . P^T, two k-steps of 32 keys; a V^T fragment feeds all QB blocks
 #pragma unroll
@@ -263,7 +242,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 && DH <= 48) ? 4 : 1)    /* = FaC
 #pragma unroll
             for (int md = 0; md < DV; ++md) {
                 const char* vb = ldsV + tr_off + md * 32;
-                const x8 a = read_tr16_pair<F16>(vb + (2 * kk) * 16 * C::VROW, vb + (2 * kk + 1) * 16 * C::VROW);
+                const x8 a = tr16_frag<F16>(vb + (2 * kk) * 16 * C::VROW, vb + (2 * kk + 1) * 16 * C::VROW);
 #pragma unroll
                 for (int u = 0; u < QB; ++u) o[u][md] = Op16<F16>::mfma(a, pb[u][kk], o[u][md]);
             }

@@ -7,7 +7,7 @@
 // Plane layout of a GEMM operand: [rows, 2 * K] bf16, hi plane in columns 0 .. K-1, lo plane in K .. 2K-1 -- the
 // GEMM's "planes" mechanism (gemm_core.hpp) addresses them as column offsets, so the tower GEMMs run on the same
 // ring kernel as the bf16 mode with planes = 3.  The row shape, the LayerNorm statistics and the GELU forms come from rows.hpp.
-#include "common.hpp"
+#include "attn_frag.hpp"
 #include "kernels.hpp"
 #include "launch.hpp"
 #include "rows.hpp"
@@ -103,23 +103,22 @@ __global__ __launch_bounds__(256) void rows_split_kernel(const float* __restrict
 // softmax), with K, V, Q and the probabilities each held as hi | lo bf16 and three MFMAs per product:
 //   S = K_hi Q_lo + K_lo Q_hi + K_hi Q_hi,   O = V_hi P_lo + V_lo P_hi + V_hi P_hi   (small terms first)
 // The probabilities are exp2 of fp32 scores, their row sum is taken in fp32 over the un-rounded values.
-// Ragged / prefix-sharing sequences as attention.hip (starts, pfx).  LDS: 2 x KT x 128 B + 2 x KT x 160 B
-// (T = 257: 156 672 B, one workgroup per CU).
+// Ragged / prefix-sharing sequences as attention.hip (SeqView; the lane maps and fragments are attn_frag.hpp's).
+// LDS: 2 x KT x 128 B + 2 x KT x 160 B (T = 257: 156 672 B, one workgroup per CU).
 // ---------------------------------------------------------------------------------------------------------------
-#define SA_KROW 128
-#define SA_VROW 160
 
 template <int MAXT, bool CAUSAL>
 __global__ __launch_bounds__(256) void attention_split_kernel(const float* __restrict__ qkv, uint16_t* __restrict__ out,
                                                               const int32_t* __restrict__ starts, int T_fixed, int heads,
                                                               int n_items, int kt_alloc, const int32_t* __restrict__ pfx, int n_seq) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int width = heads * 64;
+    const int width = heads * ATT_DH;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int item = xcd_contiguous(blockIdx.x, gridDim.x);
     if (item >= n_items) return;
     const int seq = item / heads, h = item - seq * heads;
+    // SeqView's decode, in its own text: through the constructor the <2> and <6> forms' registers are allocated differently (EXPERIMENTS.md)
     int64_t row0, prow0 = 0;
     int T, P = 0;
     if (starts) {
@@ -136,22 +135,21 @@ __global__ __launch_bounds__(256) void attention_split_kernel(const float* __res
     if (T > MAXT * 16) T = MAXT * 16;
     const int NT = (T + 15) >> 4, KT = NT * 16;
     char* ldsKh = smem;
-    char* ldsKl = ldsKh + kt_alloc * SA_KROW;
-    char* ldsVh = ldsKl + kt_alloc * SA_KROW;
-    char* ldsVl = ldsVh + kt_alloc * SA_VROW;
+    char* ldsKl = ldsKh + kt_alloc * ATT_KROW;
+    char* ldsVh = ldsKl + kt_alloc * ATT_KROW;
+    char* ldsVl = ldsVh + kt_alloc * ATT_VROW;
     const int64_t ld = 3 * (int64_t)width;
     const int g = lane >> 4, r16 = lane & 15;
-    const int sw0 = ((0 + g) ^ ((lane >> 1) & 7)) << 4;
-    const int sw1 = ((4 + g) ^ ((lane >> 1) & 7)) << 4;
-    const int tr_off = (4 * g + (r16 >> 2)) * SA_VROW + ((r16 & 3) << 3);
-    const float scale_log2 = 0.125f * 1.4426950408889634f;
+    const int sw0 = swz_chunk(0 + g, lane), sw1 = swz_chunk(4 + g, lane);
+    const int tr_off = tr_lane_off<ATT_VROW>(g, r16);
+    const float scale_log2 = ATT_SCALE_LOG2;
     const int own = T - P;
     const int NQ = (own + 15) >> 4;
 
     // ---- fill: 8 fp32 (two 16-byte loads) -> one hi piece + one lo piece; zero rows beyond T
     for (int idx = tid; idx < KT * 8; idx += 256) {
         const int key = idx >> 3, c = idx & 7;
-        const float* src = qkv + key_row(key < T ? key : T - 1) * ld + h * 64 + c * 8;
+        const float* src = qkv + key_row(key < T ? key : T - 1) * ld + h * ATT_DH + c * 8;
         const f32x4_t k0 = *(const f32x4_t*)(src + width), k1 = *(const f32x4_t*)(src + width + 4);
         const f32x4_t v0 = *(const f32x4_t*)(src + 2 * width), v1 = *(const f32x4_t*)(src + 2 * width + 4);
         u32x4_t kh, kl, vh, vl;
@@ -159,7 +157,7 @@ __global__ __launch_bounds__(256) void attention_split_kernel(const float* __res
         split8(v0, v1, vh, vl);
         const u32x4_t z = u32x4_t{0u, 0u, 0u, 0u};
         const bool ok = key < T;
-        const int ko = key * SA_KROW + ((c ^ ((key >> 1) & 7)) << 4), vo = key * SA_VROW + (c << 4);
+        const int ko = key * ATT_KROW + swz_chunk(c, key), vo = key * ATT_VROW + (c << 4);
         *(u32x4_t*)(ldsKh + ko) = ok ? kh : z;
         *(u32x4_t*)(ldsKl + ko) = ok ? kl : z;
         *(u32x4_t*)(ldsVh + vo) = ok ? vh : z;
@@ -169,20 +167,19 @@ __global__ __launch_bounds__(256) void attention_split_kernel(const float* __res
 
     f32x4_t pen_tail;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) pen_tail[r] = ((NT - 1) * 16 + 4 * g + r >= T) ? -INFINITY : 0.f;
+    for (int r = 0; r < 4; ++r) pen_tail[r] = key_penalty((NT - 1) * 16 + 4 * g + r, T);
 
     for (int qb = wave; qb < NQ; qb += 4) {
         const int qr = qb * 16 + r16;
         const int qrow = qr < own ? qr : own - 1;
-        const float* qp = qkv + (row0 + qrow) * ld + h * 64 + 8 * g;
+        const float* qp = qkv + (row0 + qrow) * ld + h * ATT_DH + 8 * g;
         u32x4_t q0h, q0l, q1h, q1l;
         split8(*(const f32x4_t*)qp, *(const f32x4_t*)(qp + 4), q0h, q0l);
         split8(*(const f32x4_t*)(qp + 32), *(const f32x4_t*)(qp + 36), q1h, q1l);
         const bf16x8_t bq0h = __builtin_bit_cast(bf16x8_t, q0h), bq0l = __builtin_bit_cast(bf16x8_t, q0l);
         const bf16x8_t bq1h = __builtin_bit_cast(bf16x8_t, q1h), bq1l = __builtin_bit_cast(bf16x8_t, q1l);
         const int qmin = P + qb * 16, qmax = qmin + 15, qpos = P + qr;
-        const int nt_c = (qmax >> 4) + 1;
-        const int nt_q = CAUSAL ? (nt_c < NT ? nt_c : NT) : NT;
+        const int nt_q = SeqView<CAUSAL>::nt_q(qmax, NT);
 
         f32x4_t s[MAXT];
         float mx = -INFINITY;
@@ -194,9 +191,9 @@ __global__ __launch_bounds__(256) void attention_split_kernel(const float* __res
                 if (CAUSAL && t * 16 + 15 > qmin) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        if (t * 16 + 4 * g + r > qpos) c0[r] = -INFINITY;
+                        if (SeqView<CAUSAL>::hidden(t * 16 + 4 * g + r, qpos)) c0[r] = -INFINITY;
                 }
-                const int ro = (t * 16 + r16) * SA_KROW;
+                const int ro = (t * 16 + r16) * ATT_KROW;
                 const bf16x8_t a0h = *(const bf16x8_t*)(ldsKh + ro + sw0), a1h = *(const bf16x8_t*)(ldsKh + ro + sw1);
                 const bf16x8_t a0l = *(const bf16x8_t*)(ldsKl + ro + sw0), a1l = *(const bf16x8_t*)(ldsKl + ro + sw1);
                 c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0h, bq0l, c0, 0, 0, 0);
@@ -208,8 +205,7 @@ __global__ __launch_bounds__(256) void attention_split_kernel(const float* __res
                 mx = fmaxf(mx, fmaxf(fmaxf(s[t][0], s[t][1]), fmaxf(s[t][2], s[t][3])));
             }
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        mx = group_max4(mx);
         const float mxs = mx * scale_log2;
         float lsum = 0.f;
 #pragma unroll
@@ -222,8 +218,7 @@ __global__ __launch_bounds__(256) void attention_split_kernel(const float* __res
                 }
             }
         }
-        lsum += __shfl_xor(lsum, 16, 64);
-        lsum += __shfl_xor(lsum, 32, 64);
+        lsum = group_sum4(lsum);
 
         f32x4_t o[4];
 #pragma unroll
@@ -237,24 +232,20 @@ __global__ __launch_bounds__(256) void attention_split_kernel(const float* __res
                 const bool pair = t1 < nt_q;
                 const f32x4_t p0 = s[t0];
                 const f32x4_t p1 = (t1 < MAXT && pair) ? s[t1 < MAXT ? t1 : 0] : f32x4_t{0.f, 0.f, 0.f, 0.f};
-                float ph[8], pl[8];
+                f32x4_t ph0, pl0, ph1, pl1;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) { split2(p0[e], ph[e], pl[e]); split2(p1[e], ph[4 + e], pl[4 + e]); }
-                u32x4_t pkh, pkl;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { pkh[e] = pack_bf16x2(ph[2 * e], ph[2 * e + 1]); pkl[e] = pack_bf16x2(pl[2 * e], pl[2 * e + 1]); }
-                const bf16x8_t pbh = __builtin_bit_cast(bf16x8_t, pkh), pbl = __builtin_bit_cast(bf16x8_t, pkl);
+                for (int e = 0; e < 4; ++e) {
+                    float hh, ll;
+                    split2(p0[e], hh, ll); ph0[e] = hh; pl0[e] = ll;
+                    split2(p1[e], hh, ll); ph1[e] = hh; pl1[e] = ll;
+                }
+                const bf16x8_t pbh = pack8<false>(ph0, ph1), pbl = pack8<false>(pl0, pl1);
                 const int tt1 = pair ? t1 : t0;
 #pragma unroll
                 for (int md = 0; md < 4; ++md) {
-                    const int o0 = tr_off + md * 32 + t0 * 16 * SA_VROW, o1 = tr_off + md * 32 + tt1 * 16 * SA_VROW;
-                    const bf16x4_t h0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)(ldsVh + o0));
-                    const bf16x4_t h1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)(ldsVh + o1));
-                    const bf16x4_t l0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)(ldsVl + o0));
-                    const bf16x4_t l1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4_t*)(ldsVl + o1));
-                    bf16x8_t ah, al;
-                    ah[0] = h0[0]; ah[1] = h0[1]; ah[2] = h0[2]; ah[3] = h0[3]; ah[4] = h1[0]; ah[5] = h1[1]; ah[6] = h1[2]; ah[7] = h1[3];
-                    al[0] = l0[0]; al[1] = l0[1]; al[2] = l0[2]; al[3] = l0[3]; al[4] = l1[0]; al[5] = l1[1]; al[6] = l1[2]; al[7] = l1[3];
+                    const int o0 = tr_off + md * 32 + t0 * 16 * ATT_VROW, o1 = tr_off + md * 32 + tt1 * 16 * ATT_VROW;
+                    const bf16x4_t h0 = tr16_read(ldsVh + o0), h1 = tr16_read(ldsVh + o1), l0 = tr16_read(ldsVl + o0), l1 = tr16_read(ldsVl + o1);
+                    const bf16x8_t ah = join8<false>(h0, h1), al = join8<false>(l0, l1);
                     o[md] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, pbl, o[md], 0, 0, 0);
                     o[md] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, pbh, o[md], 0, 0, 0);
                     o[md] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, pbh, o[md], 0, 0, 0);
@@ -263,7 +254,7 @@ __global__ __launch_bounds__(256) void attention_split_kernel(const float* __res
         }
         const float inv = 1.0f / lsum;
         if (qr < own) {
-            uint16_t* op = out + (row0 + qr) * (int64_t)(2 * width) + h * 64 + 4 * g;
+            uint16_t* op = out + (row0 + qr) * (int64_t)(2 * width) + h * ATT_DH + 4 * g;
 #pragma unroll
             for (int md = 0; md < 4; ++md) {
                 float hh[4], ll[4];
@@ -280,7 +271,7 @@ template <int MAXT, bool CAUSAL>
 hipError_t launch_split_one(const float* qkv, uint16_t* out, const int32_t* starts, int n_seq, int T, int heads,
                             hipStream_t stream, const int32_t* pfx) {
     const int kt = (T + 15) / 16 * 16;
-    const size_t lds = (size_t)kt * (2 * SA_KROW + 2 * SA_VROW);
+    const size_t lds = (size_t)kt * (2 * ATT_KROW + 2 * ATT_VROW);
     const int n_items = n_seq * heads;
     return launch<attention_split_kernel<MAXT, CAUSAL>, 160 * 1024>(dim3(n_items), dim3(256), lds, stream, qkv, out, starts, T, heads,
                                                                     n_items, kt, pfx, n_seq);

@@ -1,8 +1,7 @@
 """GPU micro-benchmark of tvc_attention at the ViT-L/14 shape (not part of the product)."""
-import sys
-sys.path.insert(0, ".")
-import torch
-import tvc_amd as pkg
+import importlib, os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+pkg = importlib.import_module("multimodal-detection-consistency_amd")
 eng = pkg.TVCEngine(); dev = "cuda:0"; torch.manual_seed(0)
 def bench(n_seq, T, heads, causal, iters=5):
     qkv = torch.randn((n_seq * T, 3 * heads * 64), device=dev).to(torch.bfloat16)

@@ -1,6 +1,6 @@
 """Bit-identity of two builds of libtvc_hip.so (a refactor against its parent commit):
 
-    python scripts/lib_ab.py OLD.so NEW.so [--timeout 240] [--keep DIR]
+    python scripts/lib_ab.py OLD.so NEW.so [--timeout 240] [--keep DIR] [--only attention|bank|cluster|sd]
 
 One fresh child process per library (selected with TVC_LIB_PATH, each child under its own ``timeout -k 10``; the second starts
 only if the first exited 0).  A child runs seed-fixed inputs through the library and writes one .npy file per result; the
@@ -17,7 +17,11 @@ shard merge; the children inherit TVC_BANK_RING / TVC_BANK_SKINNY / TVC_BANK_SKI
 reaches bank_search_kernel<true> and the dense sample for small M); k-means on a bank slot and the IVF search (cluster_cases
 below: assign and update with an empty cluster and an out-of-range label, the probe, the scan with padding and with the select's
 LDS and global-memory paths); the latent-diffusion generator end to end (sd_cases below: the UNet at two sizes, the VAE decode,
-the sampling loop on two streams and on one, chunked, and with v-prediction, all six block kinds, in bf16 and in fp16).
+the sampling loop on two streams and on one, chunked, and with v-prediction, all six block kinds, in bf16 and in fp16); the
+five swapped-MFMA attention kernels at every instantiation their launchers can pick (attention_cases below: attention_ex in bf16 and fp16 -- <17, EXACT>, <4, EXACT>, <2>, <6>, <18>, <4, WPS 2>, the causal
+<2>, <6>, <18> on packed rows with and without shared prefixes, both pooled forms --, attention_split_ex's six, attention_backward
+at T = 257, 50, 100 and 1, the streaming kernel at every head dim and workgroup shape in both SD precisions and with separate
+strides).  --only NAME runs one of the *_cases functions alone.
 """
 import argparse
 import importlib
@@ -225,7 +229,100 @@ def sd_cases(pkg, save) -> None:
         eng.close()
 
 
-def child(out_dir: Path) -> None:
+def attention_cases(pkg, save) -> None:
+    """The five swapped-MFMA attention kernels (csrc/attn_frag.hpp) through their own entry points on seeded random rows, at
+    the smallest shape that selects each instantiation a launcher can pick: attention_ex in bf16 and fp16 (<17, EXACT>,
+    <4, EXACT>, <2>, <6>, <18>, <4, WPS 2> non-causal; causal <2>, <6>, <18> on packed rows, plain and with shared prefixes;
+    both pooled forms), attention_split_ex (<2 | 6 | 18, causal | not>, dense, packed, with prefixes), attention_backward
+    (T = 257, 50, 100, 1) and the streaming kernel (every head dim at workgroup shape 1, head dims <= 80 at shapes 2 and 3,
+    both SD precisions, separate strides)."""
+    import torch
+    eng = pkg.TVCEngine()
+    dev = eng.device
+    pool = torch.randn(3 * 32 * 257 * 8 * 80, generator=torch.Generator().manual_seed(41)).to(dev)
+
+    def rows(n, width, dt, skip=0):                       # [n, width] of the seeded pool, from element `skip` on
+        return pool[skip:skip + n * width].view(n, width).to(dt).contiguous()
+
+    def i32(v):
+        return None if v is None else torch.tensor(v, dtype=torch.int32, device=dev)
+
+    def packed(lens, prefix=None):                        # starts, and pfx from (P, base sequence) pairs
+        st = [0]
+        for n in lens:
+            st.append(st[-1] + n)
+        return st, None if prefix is None else [P for P, _ in prefix] + [st[b] for _, b in prefix]
+
+    # own rows per sequence: lengths that straddle a 16-row tile; (P, base): P rows of the base sequence's are shared
+    CAUSAL = {20: ((15, 16, 17, 20), (17, 5, 1, 16), ((0, 0), (15, 0), (16, 0), (0, 3))),
+              77: ((33, 77, 16, 15), (33, 44, 15, 16), ((0, 0), (33, 0), (17, 0), (0, 3))),
+              200: ((200, 17, 129), (100, 100, 33, 17), ((0, 0), (100, 0), (15, 0), (0, 3)))}
+    heads = 3
+    for f16 in (False, True):
+        dt, tag = (torch.float16, "att_f16") if f16 else (torch.bfloat16, "att_bf16")
+
+        def ex(name, n_seq, seq_len, causal, lens=None, prefix=None, n_rows=None, **kw):
+            st, pf = packed(lens, prefix) if lens is not None else (None, None)
+            n_rows = n_rows if n_rows is not None else (st[-1] if st else n_seq * seq_len)
+            out = torch.zeros((n_seq if kw.get("pool_mode") else n_rows, heads * 64), dtype=dt, device=dev)
+            save(f"{tag}_{name}", eng.attention_ex(rows(n_rows, 3 * heads * 64, dt), n_seq, seq_len, heads, causal, starts=i32(st),
+                                                   pfx=i32(pf), f16=f16, out=out, **kw))
+
+        for T in (257, 50, 20, 90, 200):
+            ex(f"full_dense_{T}", 2, T, False)
+        ex("full_packed_50", 4, 50, False, lens=(15, 16, 17, 33))
+        for T, (plain, own, prefix) in CAUSAL.items():
+            ex(f"causal_packed_{T}", len(plain), T, True, lens=plain)
+            ex(f"causal_prefix_{T}", len(own), T, True, lens=own, prefix=prefix)
+        ex("pool1_full_dense_257", 2, 257, False, pool_mode=1)
+        ex("pool1_causal_packed_77", 4, 77, True, lens=CAUSAL[77][0], pool_mode=1)
+        ex("pool2_causal_packed_77", 4, 77, True, lens=CAUSAL[77][0], pool_mode=2)
+        ex("pool2_causal_prefix_20", 4, 20, True, lens=CAUSAL[20][1], prefix=CAUSAL[20][2], pool_mode=2)
+        ex("pool2_causal_dense_77", 3, 77, True, pool_mode=2, pool_row=i32((76, 77 + 16, 2 * 77 + 15)))
+        ex("pool2_full_dense_50", 3, 50, False, pool_mode=2, pool_row=i32((49, 50 + 17, 100)))
+
+    def split(name, n_seq, seq_len, causal, lens=None, prefix=None):
+        st, pf = packed(lens, prefix) if lens is not None else (None, None)
+        n_rows = st[-1] if st else n_seq * seq_len
+        save(f"att_split_{name}", eng.attention_split_ex(rows(n_rows, 3 * heads * 64, torch.float32), n_seq, seq_len, heads, causal,
+                                                         starts=i32(st), pfx=i32(pf)))
+
+    for T, (plain, own, prefix) in CAUSAL.items():
+        split(f"full_dense_{T}", 2, T, False)
+        split(f"full_packed_{T}", len(plain), T, False, lens=plain)
+        split(f"causal_dense_{T}", 2, T, True)
+        split(f"causal_packed_{T}", len(plain), T, True, lens=plain)
+        split(f"causal_prefix_{T}", len(own), T, True, lens=own, prefix=prefix)
+
+    for T in (257, 50, 100, 1):
+        qkv, dout = rows(2 * T, 3 * 2 * 64, torch.bfloat16), rows(2 * T, 2 * 64, torch.bfloat16, skip=2 * T * 3 * 2 * 64)
+        save(f"att_bwd_{T}", eng.attention_backward(qkv, dout, 2, T, 2))
+
+    sa = pkg.sd_model.streaming_attention
+    DIMS = (8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 128, 160)
+    for prec, dt in (("bf16", torch.bfloat16), ("fp16", torch.float16)):
+        eng.set_sd_precision(prec)
+
+        def sd(name, n, hd, dh, Tq, Tk, pad=None):
+            C, (pq, pk, pv, po) = hd * dh, pad or (0, 0, 0, 0)
+            q, k = rows(n * Tq, C + pq, dt), rows(n * Tk, C + pk, dt, skip=n * Tq * (C + pq))
+            v = rows(n * Tk, C + pv, dt, skip=n * Tq * (C + pq) + n * Tk * (C + pk))
+            out = sa(eng, q, k, v, n, hd, ld=(C + pq, C + pk, C + pv, C + po), dh=dh) if pad else sa(eng, q, k, v, n, hd)
+            save(f"att_sd_{prec}_{name}_dh{dh}_{Tq}x{Tk}", out)
+
+        for j, dh in enumerate(DIMS):
+            sd("shape1", 2, 3, dh, (65, 130, 257)[j % 3], (77, 130)[j % 2])          # 6 items: 4 waves x 1 block
+            if dh <= 80:                                  # 256 items: 4 waves x 2 blocks at Tq = 130, 8 waves x 2 blocks at 257
+                sd("shape2", 32, 8, dh, 130, (130, 77)[j % 2])
+                sd("shape3", 32, 8, dh, 257, (77, 130)[j % 2])
+        for name, n, hd, Tq in (("strides1", 2, 3, 65), ("strides2", 32, 8, 130), ("strides3", 32, 8, 257)):
+            sd(name, n, hd, 40, Tq, 130, pad=(8, 16, 24, 4))
+    eng.set_sd_precision("bf16")
+    torch.cuda.synchronize()
+    eng.close()
+
+
+def child(out_dir: Path, only: str = "") -> None:
     import torch
     sys.path.insert(0, str(ROOT))
     pkg = importlib.import_module("multimodal-detection-consistency_amd")
@@ -236,6 +333,10 @@ def child(out_dir: Path) -> None:
         if t.dtype in (torch.bfloat16, torch.float16):
             t = t.view(torch.int16)
         np.save(out_dir / (name + ".npy"), t.numpy())
+
+    if only:
+        {"attention": attention_cases, "bank": bank_cases, "cluster": cluster_cases, "sd": sd_cases}[only](pkg, save)
+        return
 
     arch = pkg.get_arch("ViT-T/16-test")
     vw, tw = pkg.synth.make_clip_weights(arch, seed=0)
@@ -287,6 +388,7 @@ def child(out_dir: Path) -> None:
     bank_cases(pkg, save)
     cluster_cases(pkg, save)
     sd_cases(pkg, save)
+    attention_cases(pkg, save)
 
 
 def main() -> int:
@@ -295,10 +397,11 @@ def main() -> int:
     ap.add_argument("new")
     ap.add_argument("--timeout", type=int, default=240, help="seconds per child")
     ap.add_argument("--keep", default=None, help="directory that keeps the .npy files (default: a temporary one)")
+    ap.add_argument("--only", default="", choices=("", "attention", "bank", "cluster", "sd"), help="one *_cases function alone")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        child(Path(a.child))
+        child(Path(a.child), a.only)
         return 0
     with tempfile.TemporaryDirectory() as tmp:
         base = Path(a.keep) if a.keep else Path(tmp)
@@ -308,7 +411,7 @@ def main() -> int:
             d.mkdir(parents=True, exist_ok=True)
             dirs.append(d)
             env = dict(os.environ, TVC_LIB_PATH=str(Path(lib).resolve()))
-            rc = subprocess.run(["timeout", "-k", "10", str(a.timeout), sys.executable, __file__, a.old, a.new, "--child", str(d)],
+            rc = subprocess.run(["timeout", "-k", "10", str(a.timeout), sys.executable, __file__, a.old, a.new, "--child", str(d), "--only", a.only],
                                 env=env).returncode
             if rc != 0:
                 print(json.dumps({"lib_ab": "child failed", "library": lib, "exit": rc}), flush=True)
