@@ -457,6 +457,46 @@ int tvc_pgd_step(tvc_handle* h, float* adv_dev, const float* clean_dev, const fl
 int tvc_l2_step(tvc_handle* h, float* adv_dev, const float* clean_dev, const float* grad_dev, int32_t B, int64_t n, float eps,
                 float step, float clip_min, float clip_max, int32_t descent, void* stream);
 
+/* ---- FSTA / SMA attacks (src/attacks/fsta_attack.py, src/attacks/sma_attack.py) -------- */
+
+#define TVC_ATTACK_METRIC_COSINE 0
+#define TVC_ATTACK_METRIC_EUCLIDEAN 1
+#define TVC_ATTACK_NORM_INF 0
+#define TVC_ATTACK_NORM_L2 1
+
+/* d(loss)/d(image embedding) of the feature loss both attacks share (fsta_attack.py:203-207,254-297, sma_attack.py:262-266,
+ * 320-373).  f (image rows, as tvc_encode_image_grad wrote them), t (text rows), g (target rows): fp32 [B, D], rows of any
+ * length.  With n_i = |f_i|, fh = f / n, vh = v / |v|, S = sum_j fh_j:
+ *   L = a_tgt mean_i cos(f_i, g_i) + a_txt mean_i cos(f_i, t_i) + w_out mse(f, g) + w_div sum_{i != j} cos(f_i, f_j) / (B (B - 1))
+ *   grad_i = a_tgt (gh_i - (fh_i.gh_i) fh_i) / (n_i B) + a_txt (th_i - (fh_i.th_i) fh_i) / (n_i B)
+ *          + 2 w_out (f_i - g_i) / (B D) + 2 w_div ((S - fh_i) - (fh_i.S - 1) fh_i) / (n_i B (B - 1))
+ * metric = TVC_ATTACK_METRIC_EUCLIDEAN: the two cosine terms are -a_tgt mean |f_i - g_i| - a_txt mean |f_i - t_i| instead,
+ *   with gradient -a (f_i - v_i) / (|f_i - v_i| B), 0 where the distance is 0.
+ * B = 1: the diversity term and its gradient are 0.  A weight of 0 switches its term off (a NaN row then cannot reach the
+ * other rows).  grad is the exact gradient, not projected onto the tangent of the unit sphere: tvc_encode_image_backward's
+ * own L2-normalise backward does that.
+ * loss_rows fp32 [B, 4] = cos(f_i, g_i) | cos(f_i, t_i) | sum_c (f_ic - g_ic)^2 / D | sum_{j != i} cos(f_i, f_j)  (columns 0 and
+ *   1 hold the distances under the Euclidean metric): every loss term is a mean of a column.
+ * FSTA: a_tgt = -feature_weight, a_txt = +feature_weight, w_out = output_weight, w_div = diversity_weight.
+ * SMA : a_tgt = -k, a_txt = +k, k = semantic_weight (1 + semantic_shift_strength), w_out = 0, w_div = diversity_weight.
+ * Fixed summation order, no atomics: bit-identical from run to run.  B = 0 or D = 0: nothing is done. */
+int tvc_attack_feature_grad(tvc_handle* h, const float* f_dev, const float* t_dev, const float* g_dev, int32_t B, int32_t D,
+                            float a_tgt, float a_txt, int32_t metric, float w_out, float w_div, float* grad_dev,
+                            float* loss_rows_dev, void* stream);
+
+/* One step of the FSTA / SMA loops on B images of n elements, in place on adv_dev and mom_dev (fsta_attack.py:213-243,
+ * sma_attack.py:272-302,701-731):
+ *   g = grad + p (adv - clean);  clip > 0: g = clamp(g, -clip, clip);  m = mu m + g
+ *   TVC_ATTACK_NORM_INF: a = adv - lr sign(m);  adv = clamp(clean + clamp(a - clean, -eps, eps), clip_min, clip_max)
+ *   TVC_ATTACK_NORM_L2 : a = adv - lr m;  d = a - clean;  d *= min(1, eps / (|d|_2 + 1e-8)) per image;
+ *                        adv = clamp(clean + d, clip_min, clip_max)
+ * p = 2 perceptual_weight / (B n) is SMA's pixel-space term perceptual_weight mse(adv, clean), which never passes the tower;
+ * p = 0 and clip <= 0 leave their operation out (the bits are those of a step without it).  mom_dev is required.
+ * B = 0 or n = 0: nothing is done. */
+int tvc_attack_step(tvc_handle* h, float* adv_dev, const float* clean_dev, const float* grad_dev, float* mom_dev, int32_t B,
+                    int64_t n, float eps, float lr, float mu, float clip, float p, float clip_min, float clip_max, int32_t norm,
+                    void* stream);
+
 /* ---- per-query consistency (K4, K6, K7) ------------------------------ */
 
 typedef struct {

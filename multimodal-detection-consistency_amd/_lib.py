@@ -148,6 +148,10 @@ SIGNATURES = {
     "tvc_pgd_step": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                                C.c_float, C.c_int32, _P]),
     "tvc_l2_step": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, _P]),
+    "tvc_attack_feature_grad": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_float,
+                                          C.c_float, _P, _P, _P]),
+    "tvc_attack_step": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
+                                  C.c_float, C.c_float, C.c_float, C.c_int32, _P]),
     "tvc_attention_backward": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "tvc_layernorm_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     # fp32-grade towers: the *_f32 weight structs have the field order of LayerWeights / VisionWeights / TextWeights

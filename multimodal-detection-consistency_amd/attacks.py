@@ -11,7 +11,11 @@ result dictionaries.  What runs per step is different:
 * momentum, sign step, eps projection and clamp (:500-521) are ONE kernel (``tvc_pgd_step``), in place.
 
 ``CLIPModel.encode_image_tensor(x, requires_grad=True)`` offers the same gradient behind ``torch.autograd`` for
-callers that write the loop themselves (Hubness / C&W, ``src/attacks/hubness_attack.py:586``).
+callers that write the loop themselves (``src/attacks/hubness_attack.py:586``).
+
+FSTA and SMA (``src/attacks/fsta_attack.py``, ``src/attacks/sma_attack.py``) are at the end of this file: their loss couples
+the rows of a batch, so its embedding gradient is a kernel of its own (``tvc_attack_feature_grad``), and their step is
+another recipe (``tvc_attack_step``); the tower forward and backward between the two are the ones PGD uses.
 
 On purpose not carried over: nn.DataParallel (:131-133; one process per GPU instead -- shard the image list across
 ranks), the GradScaler branch (:452-471; the tower is bf16-MFMA / fp32-accumulate already, there is nothing to
@@ -547,3 +551,424 @@ class HubnessAttackPresets:
 
 def create_hubness_attacker(config: Optional[HubnessAttackConfig] = None, clip_model=None) -> HubnessAttack:
     return HubnessAttack(config or HubnessAttackConfig(), clip_model=clip_model)
+
+
+# ================================================================================================
+# FSTA (src/attacks/fsta_attack.py) and SMA (src/attacks/sma_attack.py): ONE loop with different constants.
+#   loss = a_tgt mean cos(f, target) + a_txt mean cos(f, text) + w_out mse(f, target) + w_div diversity(f)
+#          [+ perceptual_weight mse(adv, clean), SMA]
+# The loss couples the rows of a batch (diversity) and is not linear in f, so its embedding gradient is a kernel
+# (tvc_attack_feature_grad); the pixel-space term never passes the tower and is added inside the step kernel
+# (tvc_attack_step: gradient clamp, un-normalised momentum, sign step + L-inf ball or momentum step + L2 ball).
+# Per iteration: encode_image_grad -> attack_feature_grad -> encode_image_backward -> attack_step, no host
+# synchronisation unless a history is asked for.  On purpose not carried over: nn.DataParallel, GradScaler /
+# autocast, tqdm, `feature_layer` (read by nothing in the reference).  Generated targets and the JPEG noise draw
+# from a seeded CPU generator (the reference uses the global device RNG), so a run is reproducible.
+# ================================================================================================
+def attack_lr_schedule(learning_rate: float, num_iter: int, decay_factor: float, every: int = 1, enabled: bool = True) -> List[float]:
+    """The learning rate of each iteration: ``lr *= decay_factor`` after every ``every``-th iteration when ``enabled``.
+    FSTA (:249-250): every 1, enabled = adaptive_step_size.  SMA ``attack`` (:308): every gamma_epochs, always.  SMA batch
+    core (:734): every gamma_epochs, enabled = adaptive_step_size.  Python floats, multiplied as the reference multiplies them."""
+    out, lr = [], float(learning_rate)
+    for k in range(int(num_iter)):
+        out.append(lr)
+        if enabled and (k + 1) % max(int(every), 1) == 0:
+            lr *= decay_factor
+    return out
+
+
+def attack_targets(text_f: torch.Tensor, selection: str, gen: torch.Generator) -> torch.Tensor:
+    """Target rows when the caller names none (fsta_attack.py:299-315, sma_attack.py:375-411), on the device of ``text_f``:
+    'random' unit Gaussian rows; 'centroid' minus the unit mean text row, repeated; 'semantic' a Gaussian draw made
+    orthogonal to its text row (row-wise Gram-Schmidt) and normalised; 'adversarial' minus the unit text row."""
+    B, D = text_f.shape
+    if selection == "random":
+        out = torch.nn.functional.normalize(torch.randn((B, D), generator=gen), p=2, dim=1).to(text_f.device)
+    elif selection == "centroid":
+        out = -torch.nn.functional.normalize(text_f.mean(dim=0, keepdim=True), p=2, dim=1).repeat(B, 1)
+    elif selection == "semantic":
+        r = torch.randn((B, D), generator=gen).to(text_f.device)
+        r = r - (r * text_f).sum(1, keepdim=True) / text_f.norm(dim=1, keepdim=True) ** 2 * text_f
+        out = torch.nn.functional.normalize(r, p=2, dim=1)
+    elif selection == "adversarial":
+        out = -torch.nn.functional.normalize(text_f, p=2, dim=1)
+    else:
+        raise ValueError(f"target_selection must be 'random', 'centroid', 'semantic' or 'adversarial' (got {selection!r})")
+    return out.contiguous()
+
+
+def feature_attack_loop(engine, clean: torch.Tensor, text_f: torch.Tensor, target_f: torch.Tensor, *, lrs: Sequence[float],
+                        a_tgt: float, a_txt: float, metric: str = "cosine", w_out: float = 0.0, w_div: float = 0.0,
+                        eps: float, mu: float, clip: float, perceptual_weight: float = 0.0, lo: float = 0.0, hi: float = 1.0,
+                        norm: str = "inf", noise_std: float = 0.0, gen: Optional[torch.Generator] = None,
+                        history: Optional[Dict[str, list]] = None) -> torch.Tensor:
+    """The loop of fsta_attack.py:169-252 / sma_attack.py:221-318,605-735 on a device batch: starts at adv = clean (no
+    random start; the ball is around the unclamped clean image), one iteration per entry of ``lrs``.  ``noise_std`` > 0 is
+    SMA's JPEG stand-in (:413-422): clamp(adv + noise, 0, 1) goes to the tower, with torch ops, and the tower's input
+    gradient is zeroed where that clamp is active."""
+    B = clean.shape[0]
+    adv = clean.clone().contiguous()
+    mom = torch.zeros_like(adv)
+    p = 2.0 * perceptual_weight / max(adv.numel(), 1)
+    for lr in lrs:
+        if noise_std > 0.0:
+            noisy = adv + (torch.randn(adv.shape, generator=gen) * noise_std).to(adv.device)
+            x = torch.clamp(noisy, 0.0, 1.0).contiguous()
+        else:
+            x = adv
+        f = engine.encode_image_grad(x, True)
+        gf, rows = engine.attack_feature_grad(f, text_f, target_f, a_tgt=a_tgt, a_txt=a_txt, metric=metric, w_out=w_out, w_div=w_div)
+        grad = engine.encode_image_backward(gf)
+        if noise_std > 0.0:
+            grad = (grad * ((noisy >= 0.0) & (noisy <= 1.0))).contiguous()
+        if history is not None:                                  # the only host synchronisation of the loop
+            m = rows.double().mean(0).tolist()
+            sgn = -1.0 if metric == "euclidean" else 1.0
+            div = m[3] / (B - 1) if B > 1 else 0.0
+            pix = perceptual_weight * float(((adv - clean).double() ** 2).mean())
+            history["loss_history"].append(sgn * (a_tgt * m[0] + a_txt * m[1]) + w_out * m[2] + w_div * div + pix)
+            history["target_history"].append(m[0])
+            history["text_history"].append(m[1])
+            history["lr_history"].append(float(lr))
+        engine.attack_step(adv, clean, grad, mom, eps, lr, mu, clip, p, lo, hi, norm)
+    return adv
+
+
+class _FeatureSpaceAttacker:
+    """What FSTAAttacker and SMAAttacker share: the tensors in, the loop, the per-sample dictionaries, stats and cache.
+    A subclass gives the loop's constants per path ('attack' / 'batch'), the success rule without targets and its stats keys."""
+    _name = "feature"
+    _untargeted_threshold = 0.5
+
+    def __init__(self, clip_model, config):
+        self.config = config
+        self.clip_model = clip_model
+        self.engine = clip_model.engine
+        self.device = clip_model.device
+        self.device_ids = [self.device.index or 0]
+        self._gen = torch.Generator().manual_seed(self.config.random_seed)
+        if self.config.enable_cache:
+            self.cache: Dict[Any, Dict[str, Any]] = {}
+            self.cache_keys: List[Any] = []
+        self.reset_stats()
+
+    # ---- helpers ---------------------------------------------------------------------------------
+    def _to_batch(self, images) -> torch.Tensor:
+        if isinstance(images, torch.Tensor):
+            x = images if images.dim() == 4 else images.unsqueeze(0)
+        else:
+            x = torch.stack([im if isinstance(im, torch.Tensor) else self.clip_model.preprocess(im) for im in images])
+        return x.to(self.device, torch.float32).contiguous()
+
+    def _text_unit(self, texts: Sequence[str]) -> torch.Tensor:
+        return self.clip_model.encode_tokens(self.clip_model.tokenize(list(texts)), True)
+
+    def _norm(self) -> str:
+        return "inf" if self.config.norm_type == "inf" else "l2"       # the reference's else branch is the L2 one
+
+    def _loop_kwargs(self, path: str) -> Dict[str, Any]:
+        raise NotImplementedError
+
+    def _loop(self, clean: torch.Tensor, text_f: torch.Tensor, target_f: torch.Tensor, path: str,
+              history: Optional[Dict[str, list]] = None) -> torch.Tensor:
+        c = self.config
+        return feature_attack_loop(self.engine, clean, text_f.contiguous(), target_f.contiguous(), eps=c.epsilon, mu=c.momentum,
+                                   lo=c.clamp_min, hi=c.clamp_max, norm=self._norm(), gen=self._gen, history=history,
+                                   **self._loop_kwargs(path))
+
+    def _similarities(self, adv: torch.Tensor, text_f: torch.Tensor, target_f: Optional[torch.Tensor]):
+        f = self.engine.encode_image(adv, True)
+        cos = torch.nn.functional.cosine_similarity
+        return cos(f, text_f, dim=1), (cos(f, target_f, dim=1) if target_f is not None else None)
+
+    def _judge(self, adv: torch.Tensor, text_f: torch.Tensor, target_f: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Per image (success flag, semantic score).  With named targets: target similarity above text similarity, score
+        their difference (fsta :334-341, sma :445-455,747-752); without: text similarity under the threshold, score minus
+        the text similarity (fsta :342-344, sma :456-459,753-755)."""
+        ts, gs = self._similarities(adv, text_f, target_f)
+        if gs is not None:
+            return gs > ts, gs - ts
+        return ts < self._untargeted_threshold, -ts
+
+    def _batches(self, images, texts: Sequence[str], targets: Optional[Sequence[str]]):
+        """(clean, text rows, target rows, named-target rows or None, texts, targets) per `batch_size` images."""
+        x = self._to_batch(images)
+        bs = max(1, int(self.config.batch_size))
+        for i in range(0, x.shape[0], bs):
+            clean = x[i:i + bs].contiguous()
+            tx = list(texts[i:i + bs])
+            tg = list(targets[i:i + bs]) if targets else None
+            text_f = self._text_unit(tx)
+            named = self._text_unit(tg) if tg else None
+            target_f = named if named is not None else attack_targets(text_f, self.config.target_selection, self._gen)
+            yield clean, text_f, target_f, named, tx, tg
+
+    # ---- the public surface ------------------------------------------------------------------------
+    def perturb(self, images: torch.Tensor, texts: Sequence[str], targets: Optional[Sequence[str]] = None) -> torch.Tensor:
+        """Device tensor in, adversarial device tensor out (the batch path, no per-sample dictionaries)."""
+        return torch.cat([self._loop(clean, text_f, target_f, "batch") for clean, text_f, target_f, _, _, _ in
+                          self._batches(images, texts, targets)])
+
+    def _batch_results(self, images, texts: Sequence[str], targets: Optional[Sequence[str]]) -> List[Dict[str, Any]]:
+        out: List[Dict[str, Any]] = []
+        for clean, text_f, target_f, named, tx, tg in self._batches(images, texts, targets):
+            adv = self._loop(clean, text_f, target_f, "batch")
+            ok, score = self._judge(adv, text_f, named)
+            linf = (adv - clean).abs().flatten(1).max(dim=1).values.cpu().tolist()
+            ok, score, adv_c, clean_c = ok.cpu().tolist(), score.cpu().tolist(), adv.cpu(), clean.cpu()
+            for i in range(clean.shape[0]):
+                out.append({"adversarial_images": adv_c[i], "original_images": clean_c[i], "success_rate": float(ok[i]),
+                            "semantic_misalignment_score": float(score[i]), "perturbation_norm": float(linf[i]),
+                            "text": tx[i], "target_semantic": tg[i] if tg else None,
+                            "success": bool(ok[i]), "adversarial_image": adv_c[i], "original_image": clean_c[i]})
+        return out
+
+    def batch_attack(self, images, texts: List[str], targets: Optional[List[str]] = None) -> List[Dict[str, Any]]:
+        """Per-sample dictionaries (sma_attack.py:508-575,763-772; the experiment driver calls it on both attackers and reads
+        'success' and 'adversarial_image', so both key sets are present)."""
+        t0 = time.time()
+        out = self._batch_results(images, texts, targets)
+        n, good = len(out), sum(1 for r in out if r["success"])
+        self.attack_stats["total_attacks"] += n
+        self.attack_stats["successful_attacks"] += good
+        logging.info("batch %s: %d/%d succeeded in %.2f s", self._name, good, n, time.time() - t0)
+        return out
+
+    def _attack(self, images, texts: List[str], targets: Optional[List[str]]):
+        clean = self._to_batch(images)
+        text_f = self._text_unit(texts)
+        named = self._text_unit(targets) if targets else None
+        target_f = named if named is not None else attack_targets(text_f, self.config.target_selection, self._gen)
+        adv = self._loop(clean, text_f, target_f, "attack")
+        ok, score = self._judge(adv, text_f, named)
+        B = clean.shape[0]
+        rate = float(ok.float().mean())
+        self.attack_stats["total_attacks"] += B
+        self.attack_stats["successful_attacks"] += int(rate * B)
+        if self.config.enable_cache:
+            self._cache_results(clean, adv, texts)
+        linf = float((adv - clean).abs().flatten(1).max(dim=1).values.mean())
+        return clean, adv, rate, float(score.mean()), linf
+
+    def _cache_results(self, images: torch.Tensor, adv_images: torch.Tensor, texts: List[str]) -> None:
+        """fsta :348-367 / sma :463-482: first in, first out.  (The key is the image batch's shape and sum and the texts,
+        not a tuple of every pixel.)"""
+        if len(self.cache_keys) >= self.config.cache_size:
+            del self.cache[self.cache_keys.pop(0)]
+        key = hash((tuple(images.shape), float(images.sum()), tuple(texts)))
+        if key not in self.cache:
+            self.cache_keys.append(key)
+        self.cache[key] = {"adversarial_images": adv_images.clone(), "original_images": images.clone(), "texts": list(texts)}
+
+
+@dataclass
+class FSTAAttackConfig:
+    """src/attacks/fsta_attack.py:20-69 (same names and defaults), plus what the experiment driver passes
+    (run_experiments.py:599-609): ``num_iterations`` (an alias of ``num_iter``) and the multi-GPU fields, accepted and
+    unused as in PGDAttackConfig.  ``feature_layer`` is kept for the constructor only (nothing reads it)."""
+    random_seed: int = 42
+    device: str = "cuda"
+    epsilon: float = 0.031
+    alpha: float = 0.008
+    num_iter: int = 20
+    feature_layer: str = "penultimate"
+    target_feature_method: str = "centroid"
+    feature_distance_metric: str = "cosine"
+    targeted: bool = True
+    target_selection: str = "random"
+    num_targets: int = 10
+    feature_weight: float = 1.0
+    output_weight: float = 0.1
+    diversity_weight: float = 0.05
+    momentum: float = 0.9
+    decay_factor: float = 0.99
+    learning_rate: float = 0.01
+    norm_type: str = "inf"
+    clamp_min: float = 0.0
+    clamp_max: float = 1.0
+    adaptive_step_size: bool = True
+    gradient_clipping: bool = True
+    clip_value: float = 1.0
+    batch_size: int = 32
+    enable_cache: bool = True
+    cache_size: int = 1000
+    num_iterations: Optional[int] = None
+    enable_multi_gpu: bool = False
+    gpu_ids: Optional[List[int]] = None
+    batch_size_per_gpu: int = 8
+    num_workers: int = 4
+
+    def __post_init__(self):
+        if self.num_iterations is not None:
+            self.num_iter = int(self.num_iterations)
+        if self.feature_distance_metric not in ("cosine", "euclidean"):
+            raise ValueError(f"feature_distance_metric must be 'cosine' or 'euclidean' (got {self.feature_distance_metric!r})")
+
+
+class FSTAAttacker(_FeatureSpaceAttacker):
+    """Mirror of ``FSTAAttacker`` (fsta_attack.py:72-389) plus the ``batch_attack`` the driver calls (:646) and ``perturb``."""
+    _name = "FSTA"
+    _untargeted_threshold = 0.5                                                                       # :344
+
+    def _loop_kwargs(self, path: str) -> Dict[str, Any]:
+        c = self.config
+        return dict(lrs=attack_lr_schedule(c.learning_rate, c.num_iter, c.decay_factor, 1, c.adaptive_step_size),
+                    a_tgt=-c.feature_weight, a_txt=c.feature_weight, metric=c.feature_distance_metric, w_out=c.output_weight,
+                    w_div=c.diversity_weight, clip=c.clip_value if c.gradient_clipping else 0.0)
+
+    def attack(self, images, texts: List[str], target_texts: Optional[List[str]] = None) -> Dict[str, Any]:
+        """:105-154."""
+        clean, adv, rate, _, linf = self._attack(images, texts, target_texts)
+        return {"adversarial_images": adv, "original_images": clean, "success_rate": rate, "perturbation_norm": linf}
+
+    def _fsta_attack(self, images: torch.Tensor, text_features: torch.Tensor, target_features: torch.Tensor) -> torch.Tensor:
+        """:156-252 on rows the caller encoded."""
+        dev = lambda t: t.to(self.device, torch.float32).contiguous()
+        return self._loop(self._to_batch(images), dev(text_features), dev(target_features), "attack")
+
+    def get_attack_stats(self) -> Dict[str, Any]:
+        s = dict(self.attack_stats)
+        s["success_rate"] = s["successful_attacks"] / s["total_attacks"] if s["total_attacks"] > 0 else 0.0
+        return s
+
+    def reset_stats(self) -> None:
+        self.attack_stats = {"total_attacks": 0, "successful_attacks": 0, "avg_iterations": 0, "avg_perturbation_norm": 0.0}
+
+
+def create_fsta_attacker(clip_model, config: Optional[FSTAAttackConfig] = None) -> FSTAAttacker:
+    return FSTAAttacker(clip_model, config or FSTAAttackConfig())
+
+
+class FSTAAttackPresets:
+    """:409-451."""
+    @staticmethod
+    def weak_attack() -> FSTAAttackConfig:
+        return FSTAAttackConfig(epsilon=0.016, num_iter=10, learning_rate=0.005)
+
+    @staticmethod
+    def strong_attack() -> FSTAAttackConfig:
+        return FSTAAttackConfig(epsilon=0.047, num_iter=40, learning_rate=0.02)
+
+    @staticmethod
+    def targeted_attack() -> FSTAAttackConfig:
+        return FSTAAttackConfig(targeted=True, target_selection="centroid", feature_weight=2.0, num_iter=30)
+
+    @staticmethod
+    def paper_config() -> FSTAAttackConfig:
+        return FSTAAttackConfig(epsilon=0.031, alpha=0.008, num_iter=20, feature_layer="penultimate", feature_distance_metric="cosine")
+
+
+@dataclass
+class SMAAttackConfig:
+    """src/attacks/sma_attack.py:21-82 (same names and defaults), plus the driver's ``num_iterations`` alias of
+    ``num_iter`` (run_experiments.py:686)."""
+    random_seed: int = 42
+    device: str = "cuda"
+    epsilon: float = 0.031
+    alpha: float = 0.008
+    num_iter: int = 15
+    semantic_weight: float = 2.0
+    perceptual_weight: float = 0.5
+    diversity_weight: float = 0.1
+    targeted: bool = True
+    target_selection: str = "semantic"
+    semantic_shift_strength: float = 1.5
+    momentum: float = 0.9
+    decay_factor: float = 0.95
+    learning_rate: float = 0.01
+    gamma_epochs: int = 5
+    norm_type: str = "inf"
+    clamp_min: float = 0.0
+    clamp_max: float = 1.0
+    jpeg_compression: bool = False
+    jpeg_quality: int = 95
+    adaptive_step_size: bool = True
+    gradient_clipping: bool = True
+    clip_value: float = 1.0
+    batch_size: int = 32
+    enable_multi_gpu: bool = False
+    gpu_ids: Optional[List[int]] = None
+    batch_size_per_gpu: int = 8
+    num_workers: int = 4
+    gradient_accumulation_steps: int = 1
+    mixed_precision: bool = False
+    pin_memory: bool = True
+    gradient_clip_value: float = 1.0
+    enable_cache: bool = True
+    cache_size: int = 1000
+    num_iterations: Optional[int] = None
+
+    def __post_init__(self):
+        if self.num_iterations is not None:
+            self.num_iter = int(self.num_iterations)
+
+
+class SMAAttacker(_FeatureSpaceAttacker):
+    """Mirror of ``SMAAttacker`` (sma_attack.py:85-774).  ``attack`` runs the loop of :207-318 (``clip_value``, the
+    learning rate decays every ``gamma_epochs`` iterations), ``batch_attack`` / ``perturb`` the batch core of :577-735
+    (``gradient_clip_value``, the decay only with ``adaptive_step_size``)."""
+    _name = "SMA"
+    _untargeted_threshold = 0.3                                                                       # :459,755
+
+    def _loop_kwargs(self, path: str) -> Dict[str, Any]:
+        c = self.config
+        k = c.semantic_weight * (1.0 + c.semantic_shift_strength)                                      # :335-342
+        batch = path == "batch"
+        clip = (c.gradient_clip_value if batch else c.clip_value) if c.gradient_clipping else 0.0
+        return dict(lrs=attack_lr_schedule(c.learning_rate, c.num_iter, c.decay_factor, c.gamma_epochs,
+                                           c.adaptive_step_size if batch else True),
+                    a_tgt=-k, a_txt=k, metric="cosine", w_out=0.0, w_div=c.diversity_weight, clip=clip,
+                    perceptual_weight=c.perceptual_weight,
+                    noise_std=(100 - c.jpeg_quality) / 100.0 * 0.01 if c.jpeg_compression else 0.0)   # :420-421
+
+    def attack(self, images, texts: List[str], target_semantics: Optional[List[str]] = None) -> Dict[str, Any]:
+        """:154-205."""
+        clean, adv, rate, score, linf = self._attack(images, texts, target_semantics)
+        self.attack_stats["semantic_misalignment_score"] += score
+        return {"adversarial_images": adv, "original_images": clean, "success_rate": rate,
+                "semantic_misalignment_score": score, "perturbation_norm": linf}
+
+    def _batch_sma_attack(self, batch_images: torch.Tensor, batch_texts: List[str],
+                          batch_targets: Optional[List[str]] = None) -> List[Dict[str, Any]]:
+        """:577-774 (no statistics; more than `batch_size` images are run `batch_size` at a time)."""
+        return self._batch_results(batch_images, batch_texts, batch_targets)
+
+    def get_attack_stats(self) -> Dict[str, Any]:
+        s = dict(self.attack_stats)
+        n = s["total_attacks"]
+        s["success_rate"] = s["successful_attacks"] / n if n > 0 else 0.0
+        s["avg_semantic_score"] = s["semantic_misalignment_score"] / n if n > 0 else 0.0
+        return s
+
+    def reset_stats(self) -> None:
+        self.attack_stats = {"total_attacks": 0, "successful_attacks": 0, "semantic_misalignment_score": 0.0,
+                             "avg_perturbation_norm": 0.0}
+
+
+def create_sma_attacker(clip_model, config: Optional[SMAAttackConfig] = None) -> SMAAttacker:
+    return SMAAttacker(clip_model, config or SMAAttackConfig())
+
+
+class SMAAttackPresets:
+    """:794-851."""
+    @staticmethod
+    def weak_attack() -> SMAAttackConfig:
+        return SMAAttackConfig(epsilon=0.016, num_iter=10, semantic_weight=1.0, learning_rate=0.005)
+
+    @staticmethod
+    def strong_attack() -> SMAAttackConfig:
+        return SMAAttackConfig(epsilon=0.047, num_iter=25, semantic_weight=3.0, learning_rate=0.02)
+
+    @staticmethod
+    def semantic_targeted_attack() -> SMAAttackConfig:
+        return SMAAttackConfig(targeted=True, target_selection="semantic", semantic_weight=2.5, semantic_shift_strength=2.0,
+                               num_iter=20)
+
+    @staticmethod
+    def paper_config() -> SMAAttackConfig:
+        return SMAAttackConfig(epsilon=0.031, alpha=0.008, num_iter=15, semantic_weight=2.0, target_selection="semantic",
+                               jpeg_compression=False)
+
+    @staticmethod
+    def jpeg_robust_attack() -> SMAAttackConfig:
+        return SMAAttackConfig(epsilon=0.039, num_iter=20, semantic_weight=2.0, jpeg_compression=True, jpeg_quality=85)

@@ -256,6 +256,14 @@ hipError_t launch_l2_step(float* adv, const float* clean, const float* grad, int
 hipError_t launch_attention_bwd(const uint16_t* qkv, const uint16_t* dao, uint16_t* dqkv, float* stats_ws, int n_seq, int T,
                                 int heads, hipStream_t stream);
 
+// ---- attack.hip: the FSTA / SMA loops' embedding gradient and step (formulas in include/tvc.h)
+// f, t, g, grad fp32 [B, D]; loss_rows fp32 [B, 4]; euclid 0: cosine terms, 1: Euclidean distances
+hipError_t launch_attack_feature_grad(const float* f, const float* t, const float* g, int B, int D, float a_tgt, float a_txt,
+                                      int euclid, float w_out, float w_div, float* grad, float* loss_rows, hipStream_t stream);
+// in place on adv and mom, B images of n elements; l2 0: sign step and L-inf ball, 1: momentum step and L2 ball
+hipError_t launch_attack_step(float* adv, const float* clean, const float* grad, float* mom, int B, int64_t n, float eps, float lr,
+                              float mu, float clip, float p, float lo, float hi, int l2, hipStream_t stream);
+
 // ---- precise.hip: fp32-grade towers (exact-f32 MFMA GEMM, fp32 attention)
 // out[j, i] (op)= sum_k X[j, k] W[i, k] + bias[i]; epi 0 store, 1 QuickGELU, 2 out += ; K, ldw, ldx multiples of 4
 hipError_t launch_gemm_f32(const float* W, int64_t ldw, const float* X, int64_t ldx, const float* bias, float* out,

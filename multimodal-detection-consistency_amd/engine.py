@@ -337,6 +337,43 @@ class TVCEngine:
             self._check(self.lib.tvc_l2_step(self.handle, _ptr(adv), _ptr(clean), _ptr(grad), B, adv.numel() // max(B, 1),
                                              eps, step, clip_min, clip_max, int(descent), _stream()))
 
+    def attack_feature_grad(self, f: torch.Tensor, t: torch.Tensor, g: torch.Tensor, *, a_tgt: float, a_txt: float,
+                            metric: str = "cosine", w_out: float = 0.0, w_div: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Embedding gradient of the FSTA / SMA feature loss (``tvc_attack_feature_grad``, formulas in include/tvc.h):
+        f, t, g fp32 [B, D] (image, text, target rows) -> (grad [B, D], loss_rows [B, 4]).  The gradient is what
+        ``encode_image_backward`` takes; the loss terms are means of the columns of ``loss_rows``."""
+        if metric not in ("cosine", "euclidean"):
+            raise ValueError(f"metric must be 'cosine' or 'euclidean' (got {metric!r})")
+        if f.dim() != 2:
+            raise ValueError(f"f: [B, D] expected, got {tuple(f.shape)}")
+        for name, x in (("f", f), ("t", t), ("g", g)):
+            if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape == f.shape):
+                raise ValueError(f"{name}: contiguous fp32 device tensor shaped like f expected")
+        B, D = f.shape
+        grad = torch.empty_like(f)
+        loss_rows = torch.empty((B, 4), dtype=torch.float32, device=f.device)
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.tvc_attack_feature_grad(self.handle, _ptr(f), _ptr(t), _ptr(g), B, D, a_tgt, a_txt,
+                                                         int(metric == "euclidean"), w_out, w_div, _ptr(grad),
+                                                         _ptr(loss_rows), _stream()))
+        return grad, loss_rows
+
+    def attack_step(self, adv: torch.Tensor, clean: torch.Tensor, grad: torch.Tensor, mom: torch.Tensor, eps: float,
+                    lr: float, mu: float, clip: float, p: float, clip_min: float, clip_max: float, norm: str = "inf") -> None:
+        """One FSTA / SMA step, in place on ``adv`` and ``mom`` (``tvc_attack_step``): gradient clamp (``clip`` > 0), the
+        pixel-space term ``p * (adv - clean)``, un-normalised momentum, then the sign step and L-inf ball (``norm='inf'``) or
+        the momentum step and L2 ball (``'l2'``), and the clamp to [clip_min, clip_max]."""
+        if norm not in ("inf", "l2"):
+            raise ValueError(f"norm must be 'inf' or 'l2' (got {norm!r})")
+        for name, x in (("adv", adv), ("clean", clean), ("grad", grad), ("mom", mom)):
+            if x is None or not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape == adv.shape):
+                raise ValueError(f"{name}: contiguous fp32 device tensor shaped like adv expected")
+        B = adv.shape[0]
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.tvc_attack_step(self.handle, _ptr(adv), _ptr(clean), _ptr(grad), _ptr(mom), B,
+                                                 adv.numel() // max(B, 1), eps, lr, mu, clip, p, clip_min, clip_max,
+                                                 int(norm == "l2"), _stream()))
+
     def encode_text(self, tokens: torch.Tensor, normalize: bool = True, group: int = 0) -> torch.Tensor:
         """tokens int [T, ctx] (on the GPU) -> fp32 [T, D].  ``group`` = N + 1 declares that the rows
         are consecutive (original, variant_1 .. variant_N) groups: variants then share the rows of

@@ -1,0 +1,73 @@
+"""Image-steps per second of the FSTA and SMA loops beside PGD's single-batch loop: ViT-L/14, one batch of B = 32 (``--batch``)
+images, the three loops alternating in one process, each window ``--steps`` (default 10) iterations between two device events
+after one warm-up window, the median of ``--windows`` (default 5) windows each.  A step of either attack is PGD's forward and
+backward plus two small launches (tvc_attack_feature_grad, tvc_attack_step), so the three rates should sit within a few
+per cent of each other.  Prints one JSON line.  Run under ``timeout``; there is no result without a GPU."""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+pkg = importlib.import_module("multimodal-detection-consistency_amd")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="ViT-L/14")
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--windows", type=int, default=5)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "attack_bench.py needs a GPU"
+    A = pkg.attacks
+    arch = pkg.get_arch(a.model)
+    model = pkg.CLIPModel(pkg.CLIPConfig(model_name=a.model, device="cuda:0"), weights=pkg.synth.make_clip_weights(arch, seed=0))
+    B = a.batch
+    clean = torch.rand((B, 3, arch.image_size, arch.image_size), generator=torch.Generator().manual_seed(1)).cuda()
+    unit = lambda seed: torch.nn.functional.normalize(
+        torch.randn((B, arch.embed_dim), generator=torch.Generator().manual_seed(seed)), dim=-1).cuda()
+    text_f, target_f = unit(2), unit(3)
+    eng = model.engine
+    g_out = (text_f / B).contiguous()
+
+    def pgd():                                                       # PGDAttacker._steps without its host-side random start
+        adv, mom = clean.clone(), torch.zeros_like(clean)
+        for _ in range(a.steps):
+            eng.encode_image_grad(adv, True)
+            grad = eng.encode_image_backward(g_out)
+            eng.pgd_step(adv, clean, grad, mom, 8 / 255, 2 / 255, 0.9, 0.0, 1.0, False)
+        return adv
+
+    fsta = A.FSTAAttacker(model, A.FSTAAttackConfig(batch_size=B, num_iter=a.steps, enable_cache=False))
+    sma = A.SMAAttacker(model, A.SMAAttackConfig(batch_size=B, num_iter=a.steps, enable_cache=False))
+    loops = {"pgd": pgd,
+             "fsta": lambda: fsta._loop(clean, text_f, target_f, "batch"),
+             "sma": lambda: sma._loop(clean, text_f, target_f, "batch")}
+    for run in loops.values():                                       # warm-up: code objects, workspaces, kept activations
+        run()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in loops}
+    for _ in range(a.windows):
+        for name, run in loops.items():                              # alternating: a drift of the machine hits all three alike
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[name].append(e0.elapsed_time(e1))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    out = {"model": a.model, "batch": B, "steps_per_window": a.steps, "windows": a.windows,
+           "ms_per_step": {k: round(v / a.steps, 3) for k, v in med.items()},
+           "image_steps_per_s": {k: round(B * a.steps / (v / 1e3), 1) for k, v in med.items()},
+           "window_ms_min_max": {k: [round(min(v), 2), round(max(v), 2)] for k, v in ms.items()},
+           "rate_vs_pgd": {k: round(med["pgd"] / med[k], 4) for k in ("fsta", "sma")}}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
