@@ -613,7 +613,9 @@ int tvc_attention_ex(tvc_handle* h, const uint16_t* qkv_dev, uint16_t* out_dev, 
                      int32_t pool_mode, const int32_t* pool_row_dev, int32_t f16, void* stream);
 
 /* Backward of tvc_attention (non-causal, fixed-length sequences, head_dim 64): qkv as the forward saw it,
- * dout bf16 [rows, width] = gradient w.r.t. the attention output, dqkv bf16 [rows, 3*width] (dq | dk | dv). */
+ * dout bf16 [rows, width] = gradient w.r.t. the attention output, dqkv bf16 [rows, 3*width] (dq | dk | dv).
+ * Launches nothing and returns TVC_E_INVALID for a NULL buffer or a negative count, TVC_E_HIP for seq_len outside
+ * 1..288 or heads < 1 with n_seq > 0; n_seq = 0 is TVC_OK and writes nothing. */
 int tvc_attention_backward(tvc_handle* h, const uint16_t* qkv_dev, const uint16_t* dout_dev, uint16_t* dqkv_dev,
                            int32_t n_seq, int32_t seq_len, int32_t heads, void* stream);
 

@@ -794,6 +794,9 @@ int tvc_attention_backward(tvc_handle* h, const uint16_t* qkv_dev, const uint16_
                            int32_t seq_len, int32_t heads, void* stream) {
     if (!h) return TVC_E_INVALID;
     if (!qkv_dev || !dout_dev || !dqkv_dev) return fail(h, TVC_E_INVALID, "tvc_attention_backward: NULL buffer");
+    // a negative count would reach ensure() as a size near 2^64, which frees the workspace before the allocation fails
+    if (n_seq < 0 || seq_len < 0 || heads < 0)
+        return fail(h, TVC_E_INVALID, "tvc_attention_backward: n_seq, seq_len and heads must not be negative");
     int rc;
     if ((rc = ensure(h, WS_GSTATS, (size_t)n_seq * seq_len * heads * 16))) return rc;
     HIP_TRY(launch_attention_bwd(qkv_dev, dout_dev, dqkv_dev, (float*)h->ws[WS_GSTATS].p, n_seq, seq_len, heads, (hipStream_t)stream));

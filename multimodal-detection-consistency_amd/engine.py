@@ -877,12 +877,21 @@ class TVCEngine:
                                                   heads, int(causal), pool_mode, _ptr(pool_row), int(f16), _stream()))
         return out
 
-    def attention_backward(self, qkv: torch.Tensor, dout: torch.Tensor, n_seq: int, seq_len: int, heads: int) -> torch.Tensor:
+    def attention_backward(self, qkv: torch.Tensor, dout: torch.Tensor, n_seq: int, seq_len: int, heads: int,
+                           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """dQ | dK | dV bf16 [rows, 3 * width] of the dense non-causal tower attention (``tvc_attention_backward``); ``out``
+        (optional) is written in place: a buffer with more rows is handed in as its first ``rows`` rows."""
         qkv = _require_cuda(qkv, torch.bfloat16, "qkv")
         dout = _require_cuda(dout, torch.bfloat16, "dout")
         if qkv.shape != (n_seq * seq_len, 3 * heads * 64) or dout.shape != (n_seq * seq_len, heads * 64):
             raise ValueError("attention_backward: qkv [rows, 3*heads*64] and dout [rows, heads*64] expected")
-        dqkv = torch.empty_like(qkv)
+        if out is None:
+            dqkv = torch.empty_like(qkv)
+        elif not out.is_cuda or out.dtype != torch.bfloat16 or out.shape != qkv.shape or not out.is_contiguous():
+            raise ValueError(f"attention_backward: out must be a contiguous {torch.bfloat16} tensor of shape "
+                             f"{tuple(qkv.shape)} on the GPU")
+        else:
+            dqkv = out
         with self._lock, torch.cuda.device(self.device):
             self._check(self.lib.tvc_attention_backward(self.handle, _ptr(qkv), _ptr(dout), _ptr(dqkv), n_seq, seq_len,
                                                         heads, _stream()))
