@@ -491,13 +491,27 @@ class TVCEngine:
         except _lib.TVCError as e:
             if e.code != _lib.TVC_E_OVERFLOW:
                 raise
-        idx, sim, mom = out
+        out = self.bank_search_dense(rows, k, count_thr, idx_offset, want_moments, bank, out=out)
+        self.dense_fallbacks += 1
+        return out
+
+    def bank_search_dense(self, rows: torch.Tensor, k: int, count_thr: float = 0.3, idx_offset: int = 0,
+                          want_moments: bool = True, bank: str = DEFAULT_BANK, out=None):
+        """``bank_search``'s contract by the brute-force kernels (``tvc_bank_search_dense``): every similarity is
+        materialised, nothing can overflow.  ``out``: the (idx, sim, moments) tensors of a ``bank_search`` call to fill."""
+        if not 1 <= k <= _lib.TVC_MAX_TOPK:
+            raise ValueError(f"top-k must be in [1, {_lib.TVC_MAX_TOPK}] (got {k})")
         rows = _require_cuda(rows, torch.float32, "rows")
+        M = rows.shape[0]
+        if out is None:
+            out = (torch.empty((M, k), dtype=torch.int32, device=self.device),
+                   torch.empty((M, k), dtype=torch.float32, device=self.device),
+                   torch.empty((M, 4), dtype=torch.float32, device=self.device) if want_moments else None)
+        idx, sim, mom = out
         with self._lock, torch.cuda.device(self.device):
             self._select(bank)
-            self._check(self.lib.tvc_bank_search_dense(self.handle, _ptr(rows), rows.shape[0], k, count_thr, idx_offset,
+            self._check(self.lib.tvc_bank_search_dense(self.handle, _ptr(rows), M, k, count_thr, idx_offset,
                                                        _ptr(idx), _ptr(sim), _ptr(mom), _stream()))
-        self.dense_fallbacks += 1
         return idx, sim, mom
 
     def bank_status(self) -> None:

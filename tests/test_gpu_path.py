@@ -192,12 +192,7 @@ def test_bank_search_dense_fallback(gpu_engine, pkg):
     gpu_engine.set_bank(bank)
     i1, s1, m1 = gpu_engine.bank_search(q, 7, 0.05)
     gpu_engine.bank_status()
-    import ctypes as C
-    i2 = torch.empty_like(i1); s2 = torch.empty_like(s1); m2 = torch.empty_like(m1)
-    rc = gpu_engine.lib.tvc_bank_search_dense(gpu_engine.handle, C.c_void_p(q.data_ptr()), 70, 7, 0.05, 0,
-                                              C.c_void_p(i2.data_ptr()), C.c_void_p(s2.data_ptr()), C.c_void_p(m2.data_ptr()),
-                                              C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0
+    i2, s2, m2 = gpu_engine.bank_search_dense(q, 7, 0.05)
     assert torch.equal(i1, i2) and torch.equal(s1, s2)
     assert torch.allclose(m1, m2, rtol=1e-4, atol=1e-3)
     row = _unit((1, D), 5)
@@ -220,15 +215,7 @@ def _stored64(bank):
 
 
 def _dense(eng, q, k, count_thr, moments):
-    import ctypes as C
-    M = q.shape[0]
-    idx = torch.empty((M, k), dtype=torch.int32, device="cuda:0")
-    sim = torch.empty((M, k), dtype=torch.float32, device="cuda:0")
-    mom = torch.empty((M, 4), dtype=torch.float32, device="cuda:0") if moments else None
-    rc = eng.lib.tvc_bank_search_dense(eng.handle, C.c_void_p(q.data_ptr()), M, k, count_thr, 0, C.c_void_p(idx.data_ptr()),
-                                       C.c_void_p(sim.data_ptr()), C.c_void_p(mom.data_ptr()) if moments else None,
-                                       C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == 0
+    idx, sim, mom = eng.bank_search_dense(q, k, count_thr, 0, moments)
     torch.cuda.synchronize()
     return idx.cpu().numpy(), sim.cpu().numpy(), None if mom is None else mom.cpu().numpy()
 
@@ -283,26 +270,49 @@ def test_bank_search_dense_degenerate_rows(gpu_engine, dtype):
         assert np.array_equal(mom[:, 2].view(np.int32), sim[:, 0].view(np.int32))      # max: bit-equal to the first rank
 
 
-def test_bank_search_overflow_is_reported(gpu_engine, pkg):
-    """A degenerate bank (all rows identical) cannot be bounded by sampling: the
-    overflow must be reported, never silently truncated."""
+def overflow_bank(exact=False):
+    """The degenerate bank of test_bank_search_overflow_is_reported: (bank, query, fp32 accumulation bound of a similarity).
+    ``exact``: the same rows on a grid of 2^-6, so that every product and partial sum is exact in fp32 (bound 0)."""
     D = 128
     row = _unit((1, D), 5)
+    q = row + 0.01 * _unit((1, D), 6)
+    if exact:
+        row, q = torch.round(row * 64) / 64, torch.round(q * 64) / 64
     bank = row.repeat(40000, 1).to(torch.bfloat16)
-    gpu_engine.set_bank(bank.cuda())
-    gpu_engine.bank_search((row + 0.01 * _unit((1, D), 6)).cuda(), 5)
-    try:
-        gpu_engine.bank_status()
-        ok = True
-    except pkg.TVCError as e:
-        ok = False
-        assert e.code == pkg._lib.TVC_E_OVERFLOW
-    # identical rows tie exactly with tau (strict >), so either outcome is legal; what is
-    # not legal is a wrong answer without an error, checked here:
-    if ok:
-        idx, sim, _ = gpu_engine.bank_search((row + 0.01 * _unit((1, D), 6)).cuda(), 5)
-        gpu_engine.bank_status()
-        assert idx.cpu().numpy().tolist()[0] == [0, 1, 2, 3, 4]
+    acc_err = 0.0 if exact else D * 2.0 ** -24 * float((bank[:1].double().abs() * q.double().abs()).sum())
+    return bank, q, acc_err
+
+
+def test_bank_search_overflow_is_reported(gpu_engine, pkg):
+    """A degenerate bank (all rows identical) cannot be bounded by sampling: the overflow must be reported, never silently
+    truncated.  The model of tests/bank_witness.py says which outcome is right: every row's similarity clears tau (the
+    sampled value less kth_finish's slack) and every list overflows.  On the grid-exact bank that holds for both forms bit
+    for bit; on the unit-vector bank the one-product form clears tau by 9e-4, far beyond the accumulation bound of 8e-6,
+    while the all-products form clears it by 2e-6 only, which that bound cannot decide: there the old rule stays -- either
+    outcome, never a wrong answer without an error (tests/test_bank_witness.py::test_degenerate_bank_overflows_by_the_model)."""
+    import bank_witness as W
+    for exact in (True, False):
+        bank, q, acc_err = overflow_bank(exact)
+        gpu_engine.set_bank(bank.cuda())
+        for want_moments in (True, False):
+            want = W.model(bank, q, 5, 0.3, W.form_of(40000, 1, 128, True, want_moments), acc_err=acc_err)
+            gpu_engine.bank_search(q.cuda(), 5, want_moments=want_moments)
+            try:
+                gpu_engine.bank_status()
+                ok = True
+            except pkg.TVCError as e:
+                ok = False
+                assert e.code == pkg._lib.TVC_E_OVERFLOW
+            if want.decided:
+                assert want.overflow and not ok, (exact, want_moments)
+            elif ok:
+                idx, sim, _ = gpu_engine.bank_search(q.cuda(), 5, want_moments=want_moments)
+                gpu_engine.bank_status()
+                assert idx.cpu().numpy().tolist()[0] == [0, 1, 2, 3, 4]
+    # a search after an overflowed one is clean
+    gpu_engine.set_bank(_unit((300, 128), 8).to(torch.bfloat16).cuda())
+    gpu_engine.bank_search(_unit((2, 128), 9).cuda(), 5)
+    gpu_engine.bank_status()
 
 
 @pytest.mark.parametrize("B,N,D,R", [(8, 4, 512, 1000), (33, 8, 768, 3000), (5, 0, 128, 100)])
