@@ -183,7 +183,7 @@ const char* tvc_last_error(tvc_handle* h);
  * ~1e-6 of the reference's fp32 CPU path (src/detector.py:461-485; configs/attacks/pgd.yaml:80 asks for fp32), so the
  * consistency scores meet the 1e-4 bar END TO END.  About 10x slower; validation and attack-generation mode, never the
  * benchmarked one.  Needs tvc_set_weights_f32 first (TVC_E_STATE otherwise).  The input-gradient entry points
- * (tvc_encode_image_grad / _backward) always run the bf16 path.
+ * (tvc_encode_image_grad / _backward) do not follow this option: their precision is TVC_OPT_GRAD_PRECISION's.
  * 2 = split-bf16 towers, the FAST <= 1e-4 mode: every activation and weight travels to the matrix cores as hi | lo bf16
  * planes (x = hi + lo to ~2^-17) and every product is three bf16 MFMAs (hi hi + hi lo + lo hi, fp32 accumulation); fp32
  * residual stream, LayerNorm, softmax and QuickGELU.  Scores within 1e-4 of the reference's fp32 CPU path END TO END at
@@ -196,9 +196,23 @@ const char* tvc_last_error(tvc_handle* h);
  * becomes +-inf (never clamped) and the embedding goes non-finite.  EOT packing, prefix sharing and the pooled last layer
  * are kept, each with its bf16 guarantee.  The reference runs its towers in fp16 (configs/defenses/tvc.yaml: precision).
  * Needs tvc_set_weights_f16 first (TVC_E_INVALID otherwise: without fp16 weights the handle offers no mode 3).
- * The input-gradient entry points run the bf16 path in every mode.
+ * The input-gradient entry points run in TVC_OPT_GRAD_PRECISION's mode whatever this option is.
  * Geometry limits: head_dim 64 and sequences of at most 288 tokens in modes 0, 1 and 3 (tvc_create refuses other towers),
  * at most 272 tokens in mode 2 (TVC_E_INVALID when the option is set).
+ * TVC_OPT_GRAD_PRECISION (default 0): the precision of tvc_encode_image_grad / tvc_encode_image_backward, independent of
+ * TVC_OPT_TOWER_PRECISION (bf16 detection with fp32-grade attack gradients is a legal pair).  0 = the bf16 path.  2 =
+ * split-bf16 (the number of the tower mode it shares its forward with): the vision tower runs forward AND backward at fp32
+ * grade -- every GEMM is three bf16 MFMA products on hi | lo planes (hi hi + hi lo + lo hi, fp32 accumulation), activations,
+ * kept state and gradients travel in fp32, the attention forward and backward form their products the same way with an fp32
+ * softmax -- so the input gradient agrees with fp64 autograd to ~1e-5 relative where mode 0 gives ~1e-2.  Mode 2 keeps the
+ * scope of mode 0: vision tower, QuickGELU, one pass (B <= TVC_OPT_MAX_CHUNK_IMAGES), the input gradient only, no atomics,
+ * bit-reproducible from run to run; at most 272 tokens, as tower mode 2.  It needs tvc_set_weights_f32 and the split weight
+ * planes: setting the option to 2 builds them when the fp32 vision weights are registered (as TVC_OPT_TOWER_PRECISION = 2
+ * does; synchronises the device), otherwise it is only recorded and tvc_encode_image_grad returns TVC_E_STATE naming what is
+ * missing.  The planes of the transposed weights are built by the first backward and freed with the others.  Any other
+ * value: TVC_E_INVALID (1 and 3 are left for exact-f32 and fp16 gradient modes).  The mode is fixed per forward:
+ * tvc_encode_image_backward runs in the mode of the last tvc_encode_image_grad on the handle and returns TVC_E_STATE,
+ * computing nothing, when the option has changed in between.
  * TVC_OPT_SD_ARENA_BYTES (default 48 GiB): budget of the activation arena of ONE UNet evaluation inside tvc_sd_generate.
  * The arena grows linearly with the samples of an evaluation (about 0.75 GB per image at 64 x 64 latents: both halves of
  * classifier-free guidance); a batch that would exceed the budget is generated in chunks of whole sampling loops -- every
@@ -220,7 +234,7 @@ const char* tvc_last_error(tvc_handle* h);
  * Independent of TVC_OPT_TOWER_PRECISION: the text states arrive as fp32 whatever mode the towers ran in. */
 enum { TVC_OPT_TEXT_PACKING = 1, TVC_OPT_MAX_CHUNK_IMAGES = 2, TVC_OPT_MAX_CHUNK_TEXTS = 3,
        TVC_OPT_BANK_FILTER = 4, TVC_OPT_TEXT_GROUP = 5, TVC_OPT_POOLED_LAST_LAYER = 6, TVC_OPT_TOWER_PRECISION = 7,
-       TVC_OPT_SD_ARENA_BYTES = 8, TVC_OPT_SD_STREAMS = 9, TVC_OPT_SD_PRECISION = 10 };
+       TVC_OPT_SD_ARENA_BYTES = 8, TVC_OPT_SD_STREAMS = 9, TVC_OPT_SD_PRECISION = 10, TVC_OPT_GRAD_PRECISION = 11 };
 int tvc_set_option(tvc_handle* h, int32_t option, int64_t value);
 
 /* Register fp32 copies of the tower weights for TVC_OPT_TOWER_PRECISION = 1 (either may be NULL).  Referenced, not
@@ -439,7 +453,11 @@ int tvc_encode_text_hidden(tvc_handle* h, const int32_t* tok_dev, int32_t T, flo
  *   handle) -> grad_pix fp32 [B, 3, S, S] in the preprocessed (normalised) pixel space.  Four dX GEMMs per layer
  *   (= the forward's GEMM work once more) with fused row kernels between them and a two-pass attention backward;
  *   nothing of the forward is recomputed.  Gradients travel between GEMMs in bf16 and accumulate along the
- *   residual stream in fp32.  Deterministic (no atomics).  May be called repeatedly for different grad_out. */
+ *   residual stream in fp32.  Deterministic (no atomics).  May be called repeatedly for different grad_out.
+ * The above is TVC_OPT_GRAD_PRECISION = 0.  With 2 both calls run the split-bf16 tower instead: the forward is tower mode 2's
+ *   over every token of every layer (embeddings as tvc_encode_image's in that mode), what it keeps is fp32 -- 4 * (5 * width +
+ *   mlp) bytes per token row and layer, 7.3 GB at ViT-L/14 and 32 images --, and the backward runs the same steps with fp32
+ *   gradients, each dX GEMM as three plane products against the transposed weight's hi | lo planes. */
 int tvc_encode_image_grad(tvc_handle* h, const float* pix_dev, int32_t B, float* out_dev, int32_t normalize, void* stream);
 int tvc_encode_image_backward(tvc_handle* h, const float* grad_out_dev, float* grad_pix_dev, void* stream);
 
@@ -862,6 +880,32 @@ int tvc_attention_split(tvc_handle* h, const float* qkv_dev, uint16_t* out_plane
 int tvc_attention_split_ex(tvc_handle* h, const float* qkv_dev, uint16_t* out_planes_dev, const int32_t* starts_dev,
                            const int32_t* pfx_dev, int32_t n_seq, int32_t seq_len, int32_t heads, int32_t causal,
                            void* stream);
+
+/* Building blocks of the split-bf16 input gradient (TVC_OPT_GRAD_PRECISION = 2), exported for parity tests.
+ * tvc_attention_split_backward: the attention backward on fp32 operands.  qkv fp32 [n_seq * seq_len, 3 * width] (q | k | v, head_dim 64), dout fp32 [rows, width] =
+ * d(loss)/d(attention output) -> dqkv fp32 [rows, 3 * width].  Non-causal dense sequences, 1 <= seq_len <= 288.  Scores
+ * and probabilities are recomputed from qkv; every product (S, dP, dQ, dK, dV) is three bf16 MFMAs on hi | lo operands,
+ * the softmax and the row sums are fp32.  Buffers 16-byte aligned.  Deterministic. */
+int tvc_attention_split_backward(tvc_handle* h, const float* qkv_dev, const float* dout_dev, float* dqkv_dev, int32_t n_seq,
+                                 int32_t seq_len, int32_t heads, void* stream);
+/* One fp32 row kernel of the split-bf16 input gradient on the caller's device buffers (parity tests), under tvc_tower_op's
+ * rules: one launcher per op, no weights, no handle state, the slots of tvc_tower_op_args, the same refusals (TVC_E_INVALID
+ * for a NULL / misaligned pointer, a bad stride, extent or flag and an unknown op; TVC_E_HIP for what a launcher rejects).
+ *   GELU_BWD       in0 u fp32 [n]; out0 dm fp32 [n], in place: dm *= s + 1.702 u s (1 - s), s = 1 / (1 + exp(-1.702 u)) (expf and
+ *                  an IEEE division); i = n (% 4).
+ *   L2NORM_BWD     in0 x fp32 [rows, d] (not read, may be NULL, with normalize 0), in1 dy fp32 [rows, d]; out0 fp32 [rows, d]
+ *                  = (dy - y (y . dy)) / |x| with y = x / |x|, or dy with normalize 0; i = rows, d, normalize.
+ *   LNPRE_BWD      in0 patch_out fp32 [B * (T - 1), d], in1 pos fp32 [T, d], in2 gamma fp32 [d], in3 dy fp32 [B * T, d] (its
+ *                  class rows are not read); out0 fp32 [B * (T - 1), d] = LayerNorm backward at patch_out + pos[t]; i = B, T (>= 2), d.
+ *   ROWS_SPLIT_T   in0 w fp32 [I, ld]; out0 bf16 [K, 2 * Ip]: row k = hi | lo planes of w[0 .. I - 1][k] (the planes of w^T);
+ *                  columns I .. Ip of both planes are NOT written (the caller zeroes the padding); i = I, K, Ip (>= I), ld (>= K).
+ *   LAYERNORM_BWD  in0 x fp32 (row r at r * x_row_stride), in1 delta fp32 or NULL (x's layout), in2 dy fp32 [rows, d] dense,
+ *                  in3 gamma fp32 [d], in4 dres fp32 or NULL (row r at r * out_row_stride; may be out0: in place); out0 dx fp32
+ *                  = rstd * (g - mean(g) - xhat * mean(g * xhat)) + dres, g = dy * gamma, xhat of x + delta;
+ *                  i = rows, d, x_row_stride, out_row_stride (>= d, % 4).  d % 4 == 0, d <= 1024. */
+enum { TVC_GRAD_SPLIT_OP_GELU_BWD = 0, TVC_GRAD_SPLIT_OP_L2NORM_BWD = 1, TVC_GRAD_SPLIT_OP_LNPRE_BWD = 2,
+       TVC_GRAD_SPLIT_OP_ROWS_SPLIT_T = 3, TVC_GRAD_SPLIT_OP_LAYERNORM_BWD = 4, TVC_GRAD_SPLIT_OP_COUNT = 5 };
+int tvc_grad_split_op(tvc_handle* h, int32_t op, const tvc_tower_op_args* a, void* stream);
 
 #ifdef __cplusplus
 }

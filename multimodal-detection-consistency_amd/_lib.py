@@ -26,6 +26,7 @@ TVC_OPT_TOWER_PRECISION = 7
 TVC_OPT_SD_ARENA_BYTES = 8
 TVC_OPT_SD_STREAMS = 9
 TVC_OPT_SD_PRECISION = 10
+TVC_OPT_GRAD_PRECISION = 11
 
 
 class TVCError(RuntimeError):
@@ -110,6 +111,9 @@ TOWER_OPS = {name: code for code, name in enumerate((
     "gelu_erf_16", "gelu_erf_f32", "l2norm_rows", "l2norm_bwd", "ln_split", "rows_split", "split_planes", "gather_rows",
     "gather_f32_rows", "text_lens_scan", "text_embed"))}
 
+# TVC_GRAD_SPLIT_OP_* (include/tvc.h): the fp32 row kernels of the split-bf16 input gradient behind tvc_grad_split_op
+GRAD_SPLIT_OPS = {name: code for code, name in enumerate(("gelu_bwd", "l2norm_bwd", "lnpre_bwd", "rows_split_t", "layernorm_bwd"))}
+
 
 # name -> (restype, argtypes); must list every symbol include/tvc.h declares
 SIGNATURES = {
@@ -169,6 +173,9 @@ SIGNATURES = {
     # the attention kernels with every launch option (parity tests)
     "tvc_attention_ex": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
     "tvc_attention_split_ex": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    # the split-bf16 input gradient's attention backward (parity tests)
+    "tvc_attention_split_backward": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "tvc_grad_split_op": (C.c_int, [_P, C.c_int32, C.POINTER(TowerOpArgs), _P]),
     # latent-diffusion reference generator
     "tvc_sd_load": (C.c_int, [_P, C.POINTER(SDDesc), C.POINTER(NamedTensor), C.c_int32, _P]),
     "tvc_sd_unet": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P, _P]),

@@ -102,7 +102,8 @@ class PGDAttacker:
             self._pool, self._streams = [self.engine], []
         while len(self._pool) < n:
             from .engine import TVCEngine
-            self._pool.append(TVCEngine(self.engine.arch, self.engine._w_host[0], None, device=str(self.device)))
+            self._pool.append(TVCEngine(self.engine.arch, self.engine._w_host[0], None, device=str(self.device),
+                                        grad_precision=self.engine.grad_precision))
         while len(self._streams) < n:
             self._streams.append(torch.cuda.Stream(self.device))
         return self._pool[:n], self._streams[:n]

@@ -45,6 +45,13 @@ class CLIPConfig:
                                           # "fp32": the exact-f32 reference mode (~1e-6; ~15x slower)
                                           # "fp16": IEEE fp16 towers at the bf16 rate (the reference's
                                           # configs/defenses/tvc.yaml precision: "fp16"; overflow beyond 65504 -> inf)
+    grad_precision: str = "bf16"          # arithmetic of encode_image_tensor(x, requires_grad=True) and of the attack loops'
+                                          # gradients, independent of `precision`: "split" = the vision tower forward and
+                                          # backward at fp32 grade (the reference's attacks run fp32 autograd)
+
+    def __post_init__(self):
+        if self.grad_precision not in TVCEngine.GRAD_PRECISIONS:
+            raise ValueError(f"grad_precision must be one of {sorted(TVCEngine.GRAD_PRECISIONS)} (got {self.grad_precision!r})")
 
 
 class HashTokenizer:
@@ -166,7 +173,7 @@ class CLIPModel:
                 from safetensors.torch import load_file
                 weights = weights_from_hf_state_dict(load_file(self.config.weights), self.arch)
         self.engine = TVCEngine(self.arch, weights[0], weights[1], device=str(self.device),
-                                precision=self.config.precision)
+                                precision=self.config.precision, grad_precision=self.config.grad_precision)
         self.tokenizer = (BPETokenizer(self.config.tokenizer_dir, self.arch.ctx) if self.config.tokenizer_dir
                           else HashTokenizer(self.arch.ctx))
         self.model = self          # `.model` is handed to nn.DataParallel by attacks (out of scope)

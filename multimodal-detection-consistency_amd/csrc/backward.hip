@@ -10,7 +10,7 @@
 
 // ---------------------------------------------------------------------------
 // LayerNorm backward with the residual path folded in:
-//   x_eff = x (+ delta)            the forward's LN input (fp32 residual stream + the bf16 delta it folded)
+//   x_eff = x (+ delta)            the forward's LN input (fp32 residual stream + the delta it folded: bf16, or fp32 when D32)
 //   g     = dy * gamma             dy: gradient w.r.t. the LN output (bf16, or fp32 when DY32)
 //   dx    = rstd * (g - mean(g) - xhat * mean(g * xhat)) (+ dres)
 // dres / dx are fp32 [*, d] rows of the residual-stream gradient (may alias: in place); dx16 (optional) receives
@@ -18,9 +18,9 @@
 // row r at r * x_row_stride -- delta shares x's layout, as in the forward --; dy dense [rows, d]; dres, dx and dx16 row r at
 // r * out_row_stride (ln_post scatters into the class rows of a zeroed [B * T, d] buffer: what lies between the rows is not written).
 // ---------------------------------------------------------------------------
-template <bool DY32>
+template <bool DY32, bool D32 = false>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ x, int64_t x_row_stride,
-                                                            const uint16_t* __restrict__ delta,
+                                                            const void* __restrict__ delta,
                                                             const void* __restrict__ dy, const float* __restrict__ gamma,
                                                             const float* dres, float* dx, uint16_t* __restrict__ dx16,
                                                             int rows, int d, int64_t out_row_stride) {
@@ -28,13 +28,15 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
     const int row = wave_row();
     if (row >= rows) return;
     const f32x4_t* xr = (const f32x4_t*)(x + (int64_t)row * x_row_stride);
-    const u32x2_t* dr = delta ? (const u32x2_t*)(delta + (int64_t)row * x_row_stride) : nullptr;
+    const u32x2_t* dr = delta && !D32 ? (const u32x2_t*)((const uint16_t*)delta + (int64_t)row * x_row_stride) : nullptr;
+    const f32x4_t* dr32 = delta && D32 ? (const f32x4_t*)((const float*)delta + (int64_t)row * x_row_stride) : nullptr;
     const int nv = d >> 2;
     f32x4_t v[4] = {}, g[4] = {};
     float s = 0.f;
     for_pieces(lane, nv, [&](int i, int c) {
         v[i] = xr[c];
         if (dr) v[i] += unpack4(dr[c]);
+        if (D32 && dr32) v[i] += dr32[c];
         s += piece_sum(v[i]);
         const f32x4_t gm = ((const f32x4_t*)gamma)[c];
         if (DY32) g[i] = ((const f32x4_t*)((const float*)dy + (int64_t)row * d))[c] * gm;
@@ -58,19 +60,29 @@ hipError_t launch_layernorm_bwd(const float* x, int64_t x_row_stride, const uint
     if (d % 4 != 0 || d > 1024 || rows < 0) return hipErrorInvalidValue;
     if (rows == 0) return hipSuccess;
     return dispatch<true, false>(dy_fp32 != 0, [&](auto f32) {
-        return launch<layernorm_bwd_kernel<f32.value>>(row_grid(rows), dim3(256), 0, stream, x, x_row_stride, delta, dy, gamma, dres, dx, dx16,
-                                                       rows, d, out_row_stride);
+        return launch<layernorm_bwd_kernel<f32.value>>(row_grid(rows), dim3(256), 0, stream, x, x_row_stride, (const void*)delta, dy, gamma,
+                                                       dres, dx, dx16, rows, d, out_row_stride);
     });
+}
+
+// the split-bf16 gradient's form: fp32 delta, fp32 dy, fp32 dx only
+hipError_t launch_layernorm_bwd_f32(const float* x, int64_t x_row_stride, const float* delta, const float* dy, const float* gamma,
+                                    const float* dres, float* dx, int rows, int d, int64_t out_row_stride, hipStream_t stream) {
+    if (d % 4 != 0 || d > 1024 || rows < 0) return hipErrorInvalidValue;
+    if (rows == 0) return hipSuccess;
+    return launch<layernorm_bwd_kernel<true, true>>(row_grid(rows), dim3(256), 0, stream, x, x_row_stride, (const void*)delta, (const void*)dy,
+                                                    gamma, dres, dx, (uint16_t*)nullptr, rows, d, out_row_stride);
 }
 
 // ---------------------------------------------------------------------------
 // ln_pre backward: the forward's input row is (t == 0 ? cls : patch_out[b, t-1]) + pos[t] (assemble_lnpre_kernel);
-// dy = fp32 gradient w.r.t. the residual stream after ln_pre; out = bf16 gradient w.r.t. patch_out rows
+// dy = fp32 gradient w.r.t. the residual stream after ln_pre; out = bf16 (fp32 with OUT32) gradient w.r.t. patch_out rows
 // [B * (T-1), d] (the class row's gradient goes to a parameter and is dropped).
 // ---------------------------------------------------------------------------
+template <bool OUT32>
 __global__ __launch_bounds__(256) void lnpre_bwd_kernel(const float* __restrict__ patch_out, const float* __restrict__ pos,
                                                         const float* __restrict__ gamma, const float* __restrict__ dy,
-                                                        uint16_t* __restrict__ dpatch, int B, int T, int d) {
+                                                        void* __restrict__ dpatch, int B, int T, int d) {
     const int lane = row_lane();
     const int64_t prow = wave_row<int64_t>();     // row of patch_out
     if (prow >= (int64_t)B * (T - 1)) return;
@@ -89,8 +101,12 @@ __global__ __launch_bounds__(256) void lnpre_bwd_kernel(const float* __restrict_
     });
     const float mean = row_mean(s, d);
     const float rstd = row_rstd(v, mean, lane, nv, d);
-    u32x2_t* o = (u32x2_t*)(dpatch + prow * d);
-    ln_bwd_tail(v, g, mean, rstd, lane, nv, d, [&](int c, f32x4_t r) { o[c] = pack4(r); });
+    u32x2_t* o = (u32x2_t*)((uint16_t*)dpatch + prow * d);
+    f32x4_t* o32 = (f32x4_t*)((float*)dpatch + prow * d);
+    ln_bwd_tail(v, g, mean, rstd, lane, nv, d, [&](int c, f32x4_t r) {
+        if (OUT32) o32[c] = r;
+        else o[c] = pack4(r);
+    });
 }
 
 hipError_t launch_lnpre_bwd(const float* patch_out, const float* pos, const float* gamma, const float* dy,
@@ -98,8 +114,16 @@ hipError_t launch_lnpre_bwd(const float* patch_out, const float* pos, const floa
     if (d % 4 != 0 || d > 1024) return hipErrorInvalidValue;
     const int64_t rows = (int64_t)B * (T - 1);
     if (rows == 0) return hipSuccess;
-    return launch<lnpre_bwd_kernel>(row_grid(rows), dim3(256), 0, stream, patch_out, pos,
-                                    gamma, dy, dpatch, B, T, d);
+    return launch<lnpre_bwd_kernel<false>>(row_grid(rows), dim3(256), 0, stream, patch_out, pos,
+                                           gamma, dy, (void*)dpatch, B, T, d);
+}
+
+hipError_t launch_lnpre_bwd_f32(const float* patch_out, const float* pos, const float* gamma, const float* dy, float* dpatch, int B,
+                                int T, int d, hipStream_t stream) {
+    if (d % 4 != 0 || d > 1024) return hipErrorInvalidValue;
+    const int64_t rows = (int64_t)B * (T - 1);
+    if (rows == 0) return hipSuccess;
+    return launch<lnpre_bwd_kernel<true>>(row_grid(rows), dim3(256), 0, stream, patch_out, pos, gamma, dy, (void*)dpatch, B, T, d);
 }
 
 // ---------------------------------------------------------------------------
@@ -122,6 +146,28 @@ hipError_t launch_gelu_bwd(uint16_t* dm, const uint16_t* u, int64_t n, hipStream
     return launch<gelu_bwd_kernel>(stride_grid(n / 8, 16384), dim3(256), 0, stream, dm, u, n / 8);
 }
 
+// the same on fp32 dm and fp32 u (split-bf16 gradient), the expf / division sigmoid of the fp32-grade modes:
+//   s = 1 / (1 + exp(-1.702 u)): u -> -inf: exp = inf, s = 0; the second term runs on u clamped as quick_gelu_grad's
+__global__ __launch_bounds__(256) void gelu_bwd_f32_kernel(float* __restrict__ dm, const float* __restrict__ u, int64_t n4) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        f32x4_t g = ((const f32x4_t*)dm)[i];
+        const f32x4_t x = __builtin_nontemporal_load((const f32x4_t*)u + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float s = 1.0f / (1.0f + expf(-1.702f * x[e]));
+            const float xc = fminf(fmaxf(x[e], -1e38f), 1e38f);
+            g[e] *= s + 1.702f * xc * s * (1.0f - s);
+        }
+        ((f32x4_t*)dm)[i] = g;
+    }
+}
+
+hipError_t launch_gelu_bwd_f32(float* dm, const float* u, int64_t n, hipStream_t stream) {
+    if (n % 4 != 0 || n < 0) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    return launch<gelu_bwd_f32_kernel>(stride_grid(n / 4, 16384), dim3(256), 0, stream, dm, u, n / 4);
+}
+
 // quick-GELU forward on a bf16 buffer (the grad-mode forward stores the pre-activation and applies this)
 __global__ __launch_bounds__(256) void gelu_fwd_kernel(const uint16_t* __restrict__ u, uint16_t* __restrict__ out, int64_t n8) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
@@ -140,19 +186,25 @@ hipError_t launch_gelu_fwd(const uint16_t* u, uint16_t* out, int64_t n, hipStrea
 }
 
 // ---------------------------------------------------------------------------
-// y = x / |x| backward (rows of the projected embedding):  dx = (dy - y (y . dy)) / |x|;  out bf16 (GEMM operand)
-// normalize == 0: plain cast.
+// y = x / |x| backward (rows of the projected embedding):  dx = (dy - y (y . dy)) / |x|;  out bf16 (GEMM operand), or fp32
+// with OUT32.  normalize == 0: plain cast / copy.
 // ---------------------------------------------------------------------------
+template <bool OUT32>
 __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                         uint16_t* __restrict__ dx16, int rows, int d, int normalize) {
+                                                         void* __restrict__ dx, int rows, int d, int normalize) {
     const int lane = row_lane();
     const int row = wave_row();
     if (row >= rows) return;
     const float* xr = x + (int64_t)row * d;
     const float* gr = dy + (int64_t)row * d;
-    uint16_t* o = dx16 + (int64_t)row * d;
+    uint16_t* o = (uint16_t*)dx + (int64_t)row * d;
+    float* o32 = (float*)dx + (int64_t)row * d;
+    auto put = [&](int c, float v) {
+        if (OUT32) o32[c] = v;
+        else o[c] = f32_to_bf16_bits(v);
+    };
     if (!normalize) {
-        for (int c = lane; c < d; c += 64) o[c] = f32_to_bf16_bits(gr[c]);
+        for (int c = lane; c < d; c += 64) put(c, gr[c]);
         return;
     }
     float ss = 0.f, sd = 0.f;
@@ -160,13 +212,18 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict
     ss = wave_sum(ss); sd = wave_sum(sd);
     const float inv = 1.0f / sqrtf(ss);
     const float k = sd * inv * inv;                     // (y . dy) / |x| = (x . dy) / |x|^2
-    for (int c = lane; c < d; c += 64) o[c] = f32_to_bf16_bits((gr[c] - xr[c] * k) * inv);
+    for (int c = lane; c < d; c += 64) put(c, (gr[c] - xr[c] * k) * inv);
 }
 
 hipError_t launch_l2norm_bwd(const float* x, const float* dy, uint16_t* dx16, int rows, int d, int normalize, hipStream_t stream) {
     if (rows == 0) return hipSuccess;
-    return launch<l2norm_bwd_kernel>(row_grid(rows), dim3(256), 0, stream, x, dy, dx16, rows, d,
-                                     normalize);
+    return launch<l2norm_bwd_kernel<false>>(row_grid(rows), dim3(256), 0, stream, x, dy, (void*)dx16, rows, d,
+                                            normalize);
+}
+
+hipError_t launch_l2norm_bwd_f32(const float* x, const float* dy, float* dx, int rows, int d, int normalize, hipStream_t stream) {
+    if (rows == 0) return hipSuccess;
+    return launch<l2norm_bwd_kernel<true>>(row_grid(rows), dim3(256), 0, stream, x, dy, (void*)dx, rows, d, normalize);
 }
 
 // ---------------------------------------------------------------------------

@@ -27,6 +27,20 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
     return __builtin_bit_cast(uint32_t, v);
 }
 
+// ---- the hi | lo split of the split-bf16 kernels: x = hi + lo to ~2^-17 relative, hi = bf16(x), lo = bf16(x - hi)
+__device__ __forceinline__ void split2(float x, float& hi, float& lo) {
+    hi = bf16_bits_to_f32(f32_to_bf16_bits(x));
+    lo = x - hi;                                 // exact in fp32; rounded to bf16 when packed
+}
+// 8 consecutive fp32 -> one 16-byte hi piece + one 16-byte lo piece
+__device__ __forceinline__ void split8(const f32x4_t a, const f32x4_t b, u32x4_t& hi, u32x4_t& lo) {
+    float h[8], l[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { split2(a[e], h[e], l[e]); split2(b[e], h[4 + e], l[4 + e]); }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { hi[e] = pack_bf16x2(h[2 * e], h[2 * e + 1]); lo[e] = pack_bf16x2(l[2 * e], l[2 * e + 1]); }
+}
+
 // IEEE fp16 (TVC_OPT_TOWER_PRECISION = 3).  The casts round to nearest even (v_cvt_pk_f16_f32) and overflow to +-inf;
 // the round-toward-zero packer (which also saturates at 65504) is deliberately not used.
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;

@@ -3,7 +3,7 @@
 // fp16 towers, bank, consistency; tvc_precise.cpp: the fp32-grade towers' stem, layer loop and head; tvc_split.cpp: the
 // split-bf16 towers' stem, layer loop, head and weight planes; tvc_sd.cpp: latent-diffusion reference generator,
 // tvc_sd_op.cpp: its entry points that read no model state; tvc_kmeans.cpp: k-means over a bank slot;
-// tvc_ivf.cpp: IVF probe and list scan).
+// tvc_ivf.cpp: IVF probe and list scan; tvc_grad_split.cpp: the split-bf16 input gradient).
 #pragma once
 #include "../../include/tvc.h"
 #include "kernels.hpp"
@@ -41,6 +41,9 @@ enum Slot {
     // counting sort of its (query, probe) pairs and the score buffer
     WS_IVF_CPLANES, WS_IVF_PQPLANES, WS_IVF_HALFNORM, WS_IVF_SIMS,
     WS_IVF_QPLANES, WS_IVF_BLKCNT, WS_IVF_PCOUNTS, WS_IVF_POFFSETS, WS_IVF_PORDER, WS_IVF_SCORES,
+    // split-bf16 input gradient (TVC_OPT_GRAD_PRECISION = 2, tvc_grad_split.cpp): what the forward keeps, the gradient's planes
+    // (d-wide; mlp- / 3d-wide), fp32 scratch (mlp- / 3d- / Kp-wide; d-wide) and the head's small rows
+    WS_GS_KEEP, WS_GS_GP, WS_GS_MP, WS_GS_WIDE, WS_GS_ROW, WS_GS_SMALL,
     WS_COUNT
 };
 
@@ -67,6 +70,9 @@ constexpr int WS_S_N = WS_S_END - WS_SX;      // offset from a vision split slot
 
 // hi | lo bf16 planes [round_up(out, 256), 2 * in] of one layer's GEMM weights (split-bf16 mode), handle-owned
 struct SplitLayer { uint16_t *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr; };
+// what split_layers keeps for the split-bf16 input gradient, fp32, layer l at l * rows * (the width): the layer's input rows
+// [rows, d], its QKV rows [rows, 3d], its out-projection output [rows, d] and the FC1 pre-activation [rows, mlp]
+struct SplitKeep { float *x = nullptr, *qkv = nullptr, *d1 = nullptr, *u = nullptr; };
 
 struct ProfRec {
     hipEvent_t a, b;
@@ -113,6 +119,8 @@ struct tvc_handle {
     int grad_B = 0;
     int grad_normalize = 0;
     const float* grad_pix = nullptr;
+    int grad_precision = 0;    // TVC_OPT_GRAD_PRECISION: 0 = bf16, 2 = split-bf16 (tvc_grad_split.cpp)
+    int grad_mode = 0;         // the mode the last tvc_encode_image_grad ran in: its backward runs in no other
     bool prof = false;
     std::vector<ProfRec> prof_recs;
     // fp32 copies of every weight (tvc_set_weights_f32): precision 1, and the source of precision 2's planes
@@ -127,6 +135,10 @@ struct tvc_handle {
     uint16_t* vsplit_patch = nullptr;
     std::vector<void*> split_owned;
     bool split_ready = false;
+    // split-bf16 input gradient: planes [round_up(in, 256), 2 * out] of the transposed vision GEMM weights, built on first use
+    // from the fp32 copies; owned through split_owned (they live and die with the planes above)
+    std::vector<SplitLayer> vsplit_t;
+    uint16_t *vsplit_proj_t = nullptr, *vsplit_patch_t = nullptr;
     struct SdState* sd = nullptr;   // latent-diffusion model (tvc_sd.cpp), owned
     int sd_precision = 0;           // TVC_OPT_SD_PRECISION: 0 = bf16, 1 = IEEE fp16; fixed while a model is loaded (its tensors are one format)
     size_t sd_arena_bytes = (size_t)48 << 30;   // TVC_OPT_SD_ARENA_BYTES: activation arena of one UNet evaluation
@@ -157,6 +169,22 @@ int split_layers(tvc_handle* h, bool text, int n_seq, int seq_len, const int32_t
                  const int32_t* pfx, hipStream_t st);
 int split_head(tvc_handle* h, bool text, int64_t x_stride, const int32_t* row_idx, int rows, float* out, bool hidden,
                hipStream_t st);
+// split_layers with the state of every layer kept for the backward (dense rows; see SplitKeep).  *d1_last / *d2_last: the last
+// layer's two pending deltas, which the caller's final LayerNorm folds in.
+int split_layers_keep(tvc_handle* h, int n_seq, int seq_len, const SplitKeep& keep, const float** d1_last, const float** d2_last,
+                      hipStream_t st);
+// out fp32 [J, ldo] = (W_hi + W_lo)[I, K] x (B_hi + B_lo)[J, K]^T + bias on planes [*, 2K], without the lo x lo term; both
+// operands are readable to whole row tiles
+int split_gemm3(tvc_handle* h, const uint16_t* Ws, int I, int K, const uint16_t* Bs, int64_t J, const float* bias, float* out,
+                int64_t ldo, hipStream_t st);
+
+// The split-bf16 input gradient (TVC_OPT_GRAD_PRECISION = 2) registers its two drivers here when tvc_grad_split.cpp is linked:
+// tvc_encode_image_grad / _backward (tvc_abi.cpp) reach it through this table, so the C-ABI also links without that unit.
+struct GradSplitOps {
+    int (*forward)(tvc_handle* h, const float* pix, int B, float* out, int normalize, hipStream_t st);
+    int (*backward)(tvc_handle* h, const float* grad_out, float* grad_pix, hipStream_t st);
+};
+inline const GradSplitOps* g_grad_split_ops = nullptr;
 
 inline int fail(tvc_handle* h, int code, const std::string& msg) {
     if (h) h->err = msg; else g_create_error = msg;

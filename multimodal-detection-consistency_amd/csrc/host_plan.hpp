@@ -231,6 +231,39 @@ inline GemmPlan gemm_form(const GemmFormArgs& a, const GemmFormEnv& env) {
 // GEMM operand rows: readable to the next multiple of 256 plus one tile (gemm.hip's ring forms stage whole tiles and prefetch one)
 inline int64_t tile_rows(int64_t r) { return (r + 255) / 256 * 256 + 256; }
 
+// ---- what the split-bf16 input gradient keeps between its forward and its backward (tvc_grad_split.cpp), in ONE block of
+// fp32: per layer the layer's input rows, QKV rows, out-projection output and FC1 pre-activation -- 4 * rows * (5 * width + mlp)
+// bytes a layer, 7.3 GB at ViT-L/14 and 32 images --, then the ln_post input [B, width] and the un-normalised embedding
+// [B, embed_dim].  Offsets in floats.  ok = false: an extent is not positive or a size does not fit size_t.
+struct GradSplitKeepPlan {
+    bool ok = false;
+    size_t rows = 0;
+    size_t x_off = 0, qkv_off = 0, d1_off = 0, u_off = 0, xl_off = 0, emb_off = 0;
+    size_t per_layer_bytes = 0, total_bytes = 0;
+};
+inline GradSplitKeepPlan grad_split_keep_plan(int64_t B, int64_t T, int64_t width, int64_t mlp, int64_t layers, int64_t embed_dim) {
+    GradSplitKeepPlan p;
+    if (B < 1 || T < 1 || width < 1 || mlp < 1 || layers < 1 || embed_dim < 1) return p;
+    size_t rows, per_row, per_layer, all_layers, head, total, bytes;
+    if (__builtin_mul_overflow((size_t)B, (size_t)T, &rows)) return p;
+    if (__builtin_mul_overflow((size_t)5, (size_t)width, &per_row) || __builtin_add_overflow(per_row, (size_t)mlp, &per_row)) return p;
+    if (__builtin_mul_overflow(rows, per_row, &per_layer) || __builtin_mul_overflow(per_layer, (size_t)layers, &all_layers)) return p;
+    if (__builtin_add_overflow((size_t)width, (size_t)embed_dim, &head) || __builtin_mul_overflow(head, (size_t)B, &head)) return p;
+    if (__builtin_add_overflow(all_layers, head, &total) || __builtin_mul_overflow(total, (size_t)4, &bytes)) return p;
+    const size_t lr = (size_t)layers * rows;       // <= all_layers: no overflow below
+    p.rows = rows;
+    p.x_off = 0;
+    p.qkv_off = lr * (size_t)width;
+    p.d1_off = p.qkv_off + lr * 3 * (size_t)width;
+    p.u_off = p.d1_off + lr * (size_t)width;
+    p.xl_off = all_layers;
+    p.emb_off = all_layers + (size_t)B * (size_t)width;
+    p.per_layer_bytes = per_layer * 4;
+    p.total_bytes = bytes;
+    p.ok = true;
+    return p;
+}
+
 // ---- the latent-diffusion sampler's scheduler (tvc_sd.cpp): PNDMScheduler with skip_prk_steps (PLMS), scalar fp32.
 // The scaled-linear schedule: betas = linspace(sqrt(b0), sqrt(b1), T)^2, out[i] = alphas_cumprod[i] = prod_{j <= i} (1 - beta_j)
 inline void sd_alphas_cumprod(float beta_start, float beta_end, int T, float* out) {

@@ -256,6 +256,21 @@ hipError_t launch_l2_step(float* adv, const float* clean, const float* grad, int
 hipError_t launch_attention_bwd(const uint16_t* qkv, const uint16_t* dao, uint16_t* dqkv, float* stats_ws, int n_seq, int T,
                                 int heads, hipStream_t stream);
 
+// ---- the same path at fp32 grade (TVC_OPT_GRAD_PRECISION = 2; backward.hip, attention_split_bwd.hip, split.hip): fp32 in, fp32 out
+// LayerNorm backward with an fp32 delta and fp32 dy (row addressing as launch_layernorm_bwd)
+hipError_t launch_layernorm_bwd_f32(const float* x, int64_t x_row_stride, const float* delta, const float* dy, const float* gamma,
+                                    const float* dres, float* dx, int rows, int d, int64_t out_row_stride, hipStream_t stream);
+hipError_t launch_lnpre_bwd_f32(const float* patch_out, const float* pos, const float* gamma, const float* dy, float* dpatch, int B,
+                                int T, int d, hipStream_t stream);
+hipError_t launch_gelu_bwd_f32(float* dm, const float* u, int64_t n, hipStream_t stream);      // in place on dm; n % 4 == 0
+hipError_t launch_l2norm_bwd_f32(const float* x, const float* dy, float* dx, int rows, int d, int normalize, hipStream_t stream);
+// qkv fp32 [n_seq * T, 3 * width] (kept), dao fp32 [n_seq * T, width] -> dqkv fp32 [n_seq * T, 3 * width]; every product on
+// hi | lo planes; stats_ws fp32 [n_seq * T, heads, 4] scratch; T <= 288
+hipError_t launch_attention_split_bwd(const float* qkv, const float* dao, float* dqkv, float* stats_ws, int n_seq, int T, int heads,
+                                      hipStream_t stream);
+// fp32 W [I, ld] (K columns) -> planes of W^T [*, 2 * Ip]: rows k < K, columns i < I of each plane (the caller zeroes the padding)
+hipError_t launch_rows_split_t(const float* w, int64_t ld, uint16_t* out, int I, int K, int Ip, hipStream_t stream);
+
 // ---- attack.hip: the FSTA / SMA loops' embedding gradient and step (formulas in include/tvc.h)
 // f, t, g, grad fp32 [B, D]; loss_rows fp32 [B, 4]; euclid 0: cosine terms, 1: Euclidean distances
 hipError_t launch_attack_feature_grad(const float* f, const float* t, const float* g, int B, int D, float a_tgt, float a_txt,

@@ -6,27 +6,13 @@
 //
 // Plane layout of a GEMM operand: [rows, 2 * K] bf16, hi plane in columns 0 .. K-1, lo plane in K .. 2K-1 -- the
 // GEMM's "planes" mechanism (gemm_core.hpp) addresses them as column offsets, so the tower GEMMs run on the same
-// ring kernel as the bf16 mode with planes = 3.  The row shape, the LayerNorm statistics and the GELU forms come from rows.hpp.
+// ring kernel as the bf16 mode with planes = 3.  split2 / split8 are common.hpp's; the row shape, the LayerNorm statistics and the GELU forms come from rows.hpp.
 #include "attn_frag.hpp"
 #include "kernels.hpp"
 #include "launch.hpp"
 #include "rows.hpp"
 
 namespace {
-
-__device__ __forceinline__ void split2(float x, float& hi, float& lo) {
-    hi = bf16_bits_to_f32(f32_to_bf16_bits(x));
-    lo = x - hi;                                 // exact in fp32; rounded to bf16 when packed
-}
-
-// 8 consecutive fp32 -> one 16-byte hi piece + one 16-byte lo piece
-__device__ __forceinline__ void split8(const f32x4_t a, const f32x4_t b, u32x4_t& hi, u32x4_t& lo) {
-    float h[8], l[8];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { split2(a[e], h[e], l[e]); split2(b[e], h[4 + e], l[4 + e]); }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { hi[e] = pack_bf16x2(h[2 * e], h[2 * e + 1]); lo[e] = pack_bf16x2(l[2 * e], l[2 * e + 1]); }
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // LayerNorm of the fp32 residual stream (+ up to two fp32 deltas: the previous store-only projections, folded in here
@@ -93,6 +79,28 @@ __global__ __launch_bounds__(256) void rows_split_kernel(const float* __restrict
         uint16_t* o = out + r * (int64_t)(2 * Kp) + c * 4;
         *(u32x2_t*)o = u32x2_t{pack_bf16x2(h[0], h[1]), pack_bf16x2(h[2], h[3])};
         *(u32x2_t*)(o + Kp) = u32x2_t{pack_bf16x2(l[0], l[1]), pack_bf16x2(l[2], l[3])};
+    }
+}
+
+// fp32 W [I, ld] (first K columns used) -> planes of W^T: out [*, 2 * Ip] bf16, row k = (hi | lo) of W[0 .. I-1][k] (the A
+// operand of the split-bf16 gradient's dX GEMMs).  Writes rows k < K, columns i < I of each plane only: the caller zeroes the
+// padding (rows up to the GEMM's row tile, columns I .. Ip).  32 x 32 tiles through LDS, 256 threads.
+__global__ __launch_bounds__(256) void rows_split_t_kernel(const float* __restrict__ w, int64_t ld, uint16_t* __restrict__ out, int I,
+                                                           int K, int Ip) {
+    __shared__ float tile[32][33];
+    const int k0 = blockIdx.x * 32, i0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;      // 32 x 8
+    for (int j = ty; j < 32; j += 8)
+        if (i0 + j < I && k0 + tx < K) tile[j][tx] = w[(int64_t)(i0 + j) * ld + k0 + tx];
+    __syncthreads();
+    for (int j = ty; j < 32; j += 8) {
+        if (k0 + j < K && i0 + tx < I) {
+            float hi, lo;
+            split2(tile[tx][j], hi, lo);
+            uint16_t* o = out + (int64_t)(k0 + j) * (2 * Ip) + i0 + tx;
+            o[0] = f32_to_bf16_bits(hi);
+            o[Ip] = f32_to_bf16_bits(lo);
+        }
     }
 }
 
@@ -291,6 +299,11 @@ hipError_t launch_rows_split(const float* x, int64_t ld_in, uint16_t* out, int64
     if (K % 4 != 0 || Kp % 4 != 0 || Kp < K || rows < 0) return hipErrorInvalidValue;
     if (rows == 0) return hipSuccess;
     return launch<rows_split_kernel>(stride_grid(rows * (Kp >> 2), 32768), dim3(256), 0, stream, x, ld_in, out, rows, K, Kp, gelu);
+}
+
+hipError_t launch_rows_split_t(const float* w, int64_t ld, uint16_t* out, int I, int K, int Ip, hipStream_t stream) {
+    if (I < 1 || K < 1 || Ip < I || ld < K || (I + 31) / 32 > 65535) return hipErrorInvalidValue;
+    return launch<rows_split_t_kernel>(dim3((K + 31) / 32, (I + 31) / 32), dim3(256), 0, stream, w, ld, out, I, K, Ip);
 }
 
 // starts == nullptr: n_seq sequences of seq_len rows; else packed rows (+ pfx: shared prefixes), seq_len = the maximum

@@ -657,6 +657,14 @@ int tvc_encode_image_grad(tvc_handle* h, const float* pix_dev, int32_t B, float*
     if (B > h->max_chunk_images) return fail(h, TVC_E_INVALID, "tvc_encode_image_grad: B exceeds TVC_OPT_MAX_CHUNK_IMAGES (one pass only)");
     if (h->desc.vision.act != TVC_ACT_QUICK_GELU) return fail(h, TVC_E_INVALID, "tvc_encode_image_grad: only QuickGELU towers have a backward pass");
     hipStream_t st = (hipStream_t)stream;
+    if (h->grad_precision == 2) {            // the split-bf16 path (tvc_grad_split.cpp)
+        if (!g_grad_split_ops) return fail(h, TVC_E_STATE, "tvc_encode_image_grad: this build has no split-bf16 gradient (TVC_OPT_GRAD_PRECISION = 2)");
+        h->grad_B = 0;                       // a failed forward leaves nothing for a backward
+        const int rc2 = g_grad_split_ops->forward(h, pix_dev, B, out_dev, normalize, st);
+        if (rc2) return rc2;
+        h->grad_B = B; h->grad_normalize = normalize; h->grad_pix = pix_dev; h->grad_mode = 2;
+        return TVC_OK;
+    }
     const tvc_model_desc& m = h->desc;
     const tvc_tower_arch& a = m.vision;
     const int gside = m.image_size / m.patch, P = gside * gside, T = P + 1, d = a.width;
@@ -687,7 +695,7 @@ int tvc_encode_image_grad(tvc_handle* h, const float* pix_dev, int32_t B, float*
                        WS_SPLITK));
     HIP_TRY(hipMemcpyAsync(out_dev, h->ws[WS_GOUT].p, (size_t)B * m.embed_dim * 4, hipMemcpyDeviceToDevice, st));
     if (normalize) HIP_TRY(launch_l2norm_rows(out_dev, B, m.embed_dim, st));
-    h->grad_B = B; h->grad_normalize = normalize; h->grad_pix = pix_dev;
+    h->grad_B = B; h->grad_normalize = normalize; h->grad_pix = pix_dev; h->grad_mode = 0;
     return TVC_OK;
 }
 
@@ -695,7 +703,14 @@ int tvc_encode_image_backward(tvc_handle* h, const float* grad_out_dev, float* g
     if (!h) return TVC_E_INVALID;
     if (!h->vision.set || h->grad_B < 1) return fail(h, TVC_E_STATE, "tvc_encode_image_backward: call tvc_encode_image_grad first");
     if (!grad_out_dev || !grad_pix_dev) return fail(h, TVC_E_INVALID, "tvc_encode_image_backward: NULL buffer");
+    if (h->grad_mode != h->grad_precision)
+        return fail(h, TVC_E_STATE, "tvc_encode_image_backward: TVC_OPT_GRAD_PRECISION changed since tvc_encode_image_grad (it ran in mode " +
+                                        std::to_string(h->grad_mode) + "): a forward / backward pair runs in one mode");
     hipStream_t st = (hipStream_t)stream;
+    if (h->grad_mode == 2) {
+        if (!g_grad_split_ops) return fail(h, TVC_E_STATE, "tvc_encode_image_backward: this build has no split-bf16 gradient");
+        return g_grad_split_ops->backward(h, grad_out_dev, grad_pix_dev, st);
+    }
     const tvc_model_desc& m = h->desc;
     const tvc_tower_arch& a = m.vision;
     const int B = h->grad_B, gside = m.image_size / m.patch, P = gside * gside, T = P + 1, d = a.width, D = m.embed_dim;
@@ -835,6 +850,16 @@ int tvc_set_option(tvc_handle* h, int32_t option, int64_t value) {
             }
             h->tower_precision = (int)value; return TVC_OK;
         }
+        case TVC_OPT_GRAD_PRECISION:
+            if (value != 0 && value != 2)
+                return fail(h, TVC_E_INVALID, "tvc_set_option: TVC_OPT_GRAD_PRECISION must be 0 (bf16) or 2 (split-bf16)");
+            // the weight planes are the tower mode's: built here once when the fp32 weights are there (synchronises the device);
+            // without them the option is recorded and tvc_encode_image_grad reports what is missing
+            if (value == 2 && h->vision32.set) {
+                const int rc = tvc_split_prepare(h);
+                if (rc) return rc;
+            }
+            h->grad_precision = (int)value; return TVC_OK;
         case TVC_OPT_TEXT_GROUP:
             if (value < 0 || value > 4096) return fail(h, TVC_E_INVALID, "tvc_set_option: TVC_OPT_TEXT_GROUP out of range");
             h->text_group = (int)value; return TVC_OK;

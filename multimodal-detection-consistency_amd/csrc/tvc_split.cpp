@@ -17,6 +17,19 @@
 // the work skipped is work whose results the causal tower never reads.  No pooled last layer (the mode is for parity).
 #include "handle.hpp"
 
+// out fp32 [J, ldo] = (W_hi + W_lo)[I, K] x (B_hi + B_lo)[J, K]^T + bias, without the lo x lo term
+int split_gemm3(tvc_handle* h, const uint16_t* Ws, int I, int K, const uint16_t* Bs, int64_t J, const float* bias, float* out, int64_t ldo,
+          hipStream_t st) {
+    GemmLaunch g = gemm_launch(Ws, 2 * (int64_t)K, I, Bs, 2 * (int64_t)K, (int)J, K, bias, out, ldo, TVC_EPI_F32);
+    g.planes = 3;                                       // small terms first, the hi x hi products last
+    g.a_plane_off[0] = 0; g.b_plane_off[0] = K;         // A_hi x B_lo
+    g.a_plane_off[1] = K; g.b_plane_off[1] = 0;         // A_lo x B_hi
+    g.a_plane_off[2] = 0; g.b_plane_off[2] = 0;         // A_hi x B_hi
+    g.a_rows_padded = true; g.b_rows_padded = true;     // split weights / workspaces are allocated to whole tiles
+    HIP_TRY(timed_gemm(h, g, st));
+    return TVC_OK;
+}
+
 namespace {
 
 struct SBufs { float *X, *QKV, *U, *D1, *D2, *CLS; uint16_t *Hs, *Ms; };
@@ -29,19 +42,6 @@ SBufs split_bufs(tvc_handle* h, bool text) {
     b.Ms = (uint16_t*)h->ws[WS_SM + wso].p; b.D1 = (float*)h->ws[WS_SDELTA1 + wso].p;
     b.D2 = (float*)h->ws[WS_SDELTA2 + wso].p; b.CLS = (float*)h->ws[WS_SCLS + wso].p;
     return b;
-}
-
-// out fp32 [J, ldo] = (W_hi + W_lo)[I, K] x (B_hi + B_lo)[J, K]^T + bias, without the lo x lo term
-int gemm3(tvc_handle* h, const uint16_t* Ws, int I, int K, const uint16_t* Bs, int64_t J, const float* bias, float* out, int64_t ldo,
-          hipStream_t st) {
-    GemmLaunch g = gemm_launch(Ws, 2 * (int64_t)K, I, Bs, 2 * (int64_t)K, (int)J, K, bias, out, ldo, TVC_EPI_F32);
-    g.planes = 3;                                       // small terms first, the hi x hi products last
-    g.a_plane_off[0] = 0; g.b_plane_off[0] = K;         // A_hi x B_lo
-    g.a_plane_off[1] = K; g.b_plane_off[1] = 0;         // A_lo x B_hi
-    g.a_plane_off[2] = 0; g.b_plane_off[2] = 0;         // A_hi x B_hi
-    g.a_rows_padded = true; g.b_rows_padded = true;     // split weights / workspaces are allocated to whole tiles
-    HIP_TRY(timed_gemm(h, g, st));
-    return TVC_OK;
 }
 
 // fp32 [I, K] -> handle-owned hi | lo planes [round_up(I, 256), 2 * Kp] (zero rows / columns beyond I / K)
@@ -75,6 +75,8 @@ void tvc_split_free(tvc_handle* h) {
     h->split_owned.clear();
     h->vsplit.clear(); h->tsplit.clear();
     h->vsplit_patch = nullptr;
+    h->vsplit_t.clear();
+    h->vsplit_proj_t = h->vsplit_patch_t = nullptr;
     h->split_ready = false;
 }
 
@@ -140,15 +142,19 @@ int split_stem(tvc_handle* h, const float* pix, int n, const float** patch_out, 
     HIP_TRY(launch_im2col_f32(pix, cols, n, m.image_size, m.patch, st));
     HIP_TRY(launch_rows_split(cols, K, b.Ms, (int64_t)n * P, K, Kp, 0, st));
     *patch_out = b.QKV;                  // [n * P, d] fp32
-    return gemm3(h, h->vsplit_patch, d, Kp, b.Ms, (int64_t)n * P, nullptr, b.QKV, d, st);
+    return split_gemm3(h, h->vsplit_patch, d, Kp, b.Ms, (int64_t)n * P, nullptr, b.QKV, d, st);
 }
 
-int split_layers(tvc_handle* h, bool text, int n_seq, int seq_len, const int32_t* starts, int total_rows,
-                 const int32_t* pfx, hipStream_t st) {
+namespace {
+// keep (the split-bf16 input gradient's forward; dense vision rows): layer l's QKV, out-projection output and FC1 pre-activation go
+// to its slices of *keep instead of the workspace, and the layer's input rows are copied there once ln_1 has folded the pending
+// deltas into X.  d1_last / d2_last: where the last layer's deltas are.
+int layers_impl(tvc_handle* h, bool text, int n_seq, int seq_len, const int32_t* starts, int total_rows, const int32_t* pfx,
+                const SplitKeep* keep, const float** d1_last, const float** d2_last, hipStream_t st) {
     const tvc_tower_arch& a = text ? h->desc.text : h->desc.vision;
     const SplitLayer* sw = (text ? h->tsplit : h->vsplit).data();
     const tvc_layer_weights_f32* lw = text ? h->text32.w.layers : h->vision32.w.layers;
-    const SBufs b = split_bufs(h, text);
+    SBufs b = split_bufs(h, text);
     const int causal = text ? 1 : 0;
     const int d = a.width;
     const int rows = starts ? total_rows : n_seq * seq_len;
@@ -161,26 +167,45 @@ int split_layers(tvc_handle* h, bool text, int n_seq, int seq_len, const int32_t
             HIP_TRY(launch_ln_split(b.X, d, nullptr, pending ? b.D1 : nullptr, pending ? b.D2 : nullptr, 1, w.ln1_g, w.ln1_b, b.Hs,
                                     nullptr, rows, d, st));
         }
-        if ((rc = gemm3(h, sw[l].wqkv, 3 * d, d, b.Hs, rows, w.bqkv, b.QKV, 3 * d, st))) return rc;
+        if (keep) {
+            HIP_TRY(hipMemcpyAsync(keep->x + (size_t)l * rows * d, b.X, (size_t)rows * d * 4, hipMemcpyDeviceToDevice, st));
+            b.QKV = keep->qkv + (size_t)l * rows * 3 * d;
+            b.D1 = keep->d1 + (size_t)l * rows * d;        // read again by the next layer's ln_1 (or the caller's final LayerNorm)
+            b.U = keep->u + (size_t)l * rows * a.mlp;
+        }
+        if ((rc = split_gemm3(h, sw[l].wqkv, 3 * d, d, b.Hs, rows, w.bqkv, b.QKV, 3 * d, st))) return rc;
         {
             const double avg_len = starts ? (double)rows / n_seq : (double)seq_len;
             ProfScope ps(h, st, TVC_PROF_ATTENTION, 3.0 * 4.0 * n_seq * a.heads * avg_len * avg_len * 64 * (causal ? 0.5 : 1.0));
             HIP_TRY(launch_attention_split(b.QKV, b.Hs, starts, n_seq, seq_len, a.heads, causal, st, pfx));
         }
-        if ((rc = gemm3(h, sw[l].wo, d, d, b.Hs, rows, w.bo, b.D1, d, st))) return rc;
+        if ((rc = split_gemm3(h, sw[l].wo, d, d, b.Hs, rows, w.bo, b.D1, d, st))) return rc;
         {
             ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)rows * d * 12.0);
             HIP_TRY(launch_ln_split(b.X, d, nullptr, b.D1, nullptr, 0, w.ln2_g, w.ln2_b, b.Hs, nullptr, rows, d, st));
         }
-        if ((rc = gemm3(h, sw[l].w1, a.mlp, d, b.Hs, rows, w.b1, b.U, a.mlp, st))) return rc;
+        if ((rc = split_gemm3(h, sw[l].w1, a.mlp, d, b.Hs, rows, w.b1, b.U, a.mlp, st))) return rc;
         {
             ProfScope ps(h, st, TVC_PROF_ROWOPS, (double)rows * a.mlp * 8.0);
             HIP_TRY(launch_rows_split(b.U, a.mlp, b.Ms, rows, a.mlp, a.mlp, a.act == TVC_ACT_GELU ? 2 : 1, st));
         }
-        if ((rc = gemm3(h, sw[l].w2, d, a.mlp, b.Ms, rows, w.b2, b.D2, d, st))) return rc;
+        if ((rc = split_gemm3(h, sw[l].w2, d, a.mlp, b.Ms, rows, w.b2, b.D2, d, st))) return rc;
         pending = true;
     }
+    if (d1_last) *d1_last = b.D1;
+    if (d2_last) *d2_last = b.D2;
     return TVC_OK;
+}
+}  // namespace
+
+int split_layers(tvc_handle* h, bool text, int n_seq, int seq_len, const int32_t* starts, int total_rows,
+                 const int32_t* pfx, hipStream_t st) {
+    return layers_impl(h, text, n_seq, seq_len, starts, total_rows, pfx, nullptr, nullptr, nullptr, st);
+}
+
+int split_layers_keep(tvc_handle* h, int n_seq, int seq_len, const SplitKeep& keep, const float** d1_last, const float** d2_last,
+                      hipStream_t st) {
+    return layers_impl(h, false, n_seq, seq_len, nullptr, 0, nullptr, &keep, d1_last, d2_last, st);
 }
 
 // the LayerNorm folds in the last layer's two pending deltas; the projection runs exact f32 (rows is small)
@@ -213,7 +238,7 @@ extern "C" int tvc_gemm_split(tvc_handle* h, const float* w_dev, const float* x_
     HIP_TRY(hipMemsetAsync(ws, 0, (size_t)Ip * 2 * Kp * 2, st));
     HIP_TRY(launch_rows_split(w_dev, K, ws, I, K, Kp, 0, st));
     HIP_TRY(launch_rows_split(x_dev, K, xs, J, K, Kp, 0, st));
-    return gemm3(h, ws, I, Kp, xs, J, bias_dev, out_dev, ld_out, st);
+    return split_gemm3(h, ws, I, Kp, xs, J, bias_dev, out_dev, ld_out, st);
 }
 
 extern "C" int tvc_attention_split(tvc_handle* h, const float* qkv_dev, uint16_t* out_planes_dev, const int32_t* starts_dev,

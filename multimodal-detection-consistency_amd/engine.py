@@ -5,6 +5,7 @@ the hot path is a HIP kernel launched through ``include/tvc.h``.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import threading
 from dataclasses import dataclass, field
@@ -90,7 +91,8 @@ class TVCEngine:
     """Owns a ``tvc_handle`` and the device copies of the tower weights."""
 
     def __init__(self, arch: Optional[ClipArch] = None, vision_w: Optional[Dict] = None,
-                 text_w: Optional[Dict] = None, device: str = "cuda:0", precision: str = "bf16"):
+                 text_w: Optional[Dict] = None, device: str = "cuda:0", precision: str = "bf16",
+                 grad_precision: str = "bf16"):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.TVCError(_lib.TVC_E_HIP, "no GPU visible to PyTorch-ROCm; the TVC path has no CPU fallback")
@@ -124,8 +126,12 @@ class TVCEngine:
         self._has_f16 = False
         self.precision = "bf16"
         self.sd_precision = "bf16"            # TVC_OPT_SD_PRECISION (set_sd_precision): the latent-diffusion model's 16-bit format
+        self.grad_precision = "bf16"          # TVC_OPT_GRAD_PRECISION (set_grad_precision): the input-gradient entry points' mode
+        self._grad_pair = None                # the option value the last encode_image_grad ran under, when it named one
         if precision != "bf16":
             self.set_precision(precision)
+        if grad_precision != "bf16":
+            self.set_grad_precision(grad_precision)
 
     # ---- weights -------------------------------------------------------
     def _layers_f32(self, layers) -> "C.Array":
@@ -173,8 +179,8 @@ class TVCEngine:
 
         ``"split"`` and ``"fp32"`` upload fp32 copies of the caller's weights, ``"fp16"`` fp16 copies (rounded to nearest
         even on the host).  The input-gradient entry points
-        (``encode_image_grad`` / ``encode_image_backward``: the PGD / Hubness loops) ALWAYS run the bf16 path, whatever
-        this is set to."""
+        (``encode_image_grad`` / ``encode_image_backward``: the attack loops) do not follow this: see
+        ``set_grad_precision``."""
         if precision not in self.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(self.PRECISIONS)} (got {precision!r})")
         with self._lock, torch.cuda.device(self.device):
@@ -188,6 +194,25 @@ class TVCEngine:
                 self._upload_f16_weights()
             self._check(self.lib.tvc_set_option(self.handle, _lib.TVC_OPT_TOWER_PRECISION, self.PRECISIONS[precision]))
         self.precision = precision
+
+    GRAD_PRECISIONS = {"bf16": 0, "split": 2}
+
+    def _grad_option(self, value: int) -> None:
+        """``TVC_OPT_GRAD_PRECISION`` under the held lock; mode 2 first uploads the fp32 weights it is built from, when the
+        engine has host weights it has not uploaded yet (without them the C-ABI reports what is missing at the forward)."""
+        if value == 2 and not self._has_f32 and self._w_host[0] is not None:
+            self._upload_f32_weights()
+        self._check(self.lib.tvc_set_option(self.handle, _lib.TVC_OPT_GRAD_PRECISION, value))
+
+    def set_grad_precision(self, precision: str) -> None:
+        """Arithmetic of ``encode_image_grad`` / ``encode_image_backward`` (``TVC_OPT_GRAD_PRECISION``), independent of
+        ``set_precision``: ``"bf16"`` (default) or ``"split"`` -- the vision tower forward and backward at fp32 grade (three
+        bf16 MFMA products per element on hi | lo planes, fp32 activations, kept state and gradients)."""
+        if precision not in self.GRAD_PRECISIONS:
+            raise ValueError(f"grad_precision must be one of {sorted(self.GRAD_PRECISIONS)} (got {precision!r})")
+        with self._lock, torch.cuda.device(self.device):
+            self._grad_option(self.GRAD_PRECISIONS[precision])
+        self.grad_precision = precision
 
     def _upload_f16_weights(self) -> None:
         """IEEE fp16 copies of every GEMM weight for ``TVC_OPT_TOWER_PRECISION = 3`` (rounded on the host: ``.to(float16)``
@@ -281,17 +306,24 @@ class TVCEngine:
         return out
 
     # ---- input gradient of the vision tower (attacks: PGD / Hubness inner loop) ----------------
-    def encode_image_grad(self, pixels: torch.Tensor, normalize: bool = True) -> torch.Tensor:
+    def encode_image_grad(self, pixels: torch.Tensor, normalize: bool = True, precision: Optional[str] = None) -> torch.Tensor:
         """As ``encode_image`` but keeps what ``encode_image_backward`` needs inside the handle.  ``pixels`` must stay
-        alive and unchanged until the backward (the engine holds a reference)."""
+        alive and unchanged until the backward (the engine holds a reference).  ``precision``: ``None`` = the engine's
+        gradient precision (``set_grad_precision``); ``"bf16"`` / ``"split"`` = that mode for this forward and its backward(s),
+        the option set and put back under the engine lock around each of the calls."""
+        if precision is not None and precision not in self.GRAD_PRECISIONS:
+            raise ValueError(f"precision must be None or one of {sorted(self.GRAD_PRECISIONS)} (got {precision!r})")
         a = self.arch
         if pixels.dim() != 4 or pixels.shape[1:] != (3, a.image_size, a.image_size):
             raise ValueError(f"expected [B, 3, {a.image_size}, {a.image_size}], got {tuple(pixels.shape)}")
         pixels = _require_cuda(pixels, torch.float32, "pixels")
         out = torch.empty((pixels.shape[0], a.embed_dim), dtype=torch.float32, device=self.device)
+        pair = None if precision is None else self.GRAD_PRECISIONS[precision]
         with self._lock, torch.cuda.device(self.device):
-            self._check(self.lib.tvc_encode_image_grad(self.handle, _ptr(pixels), pixels.shape[0], _ptr(out),
-                                                       int(normalize), _stream()))
+            with self._grad_mode(pair):
+                self._check(self.lib.tvc_encode_image_grad(self.handle, _ptr(pixels), pixels.shape[0], _ptr(out),
+                                                           int(normalize), _stream()))
+            self._grad_pair = pair
             self._grad_pixels = pixels
             self._grad_generation = getattr(self, "_grad_generation", 0) + 1
         return out
@@ -308,9 +340,21 @@ class TVCEngine:
         if tuple(grad_out.shape) != (px.shape[0], self.arch.embed_dim):
             raise ValueError(f"grad_out must be [{px.shape[0]}, {self.arch.embed_dim}], got {tuple(grad_out.shape)}")
         gp = torch.empty_like(px)
-        with self._lock, torch.cuda.device(self.device):
+        with self._lock, torch.cuda.device(self.device), self._grad_mode(self._grad_pair):
             self._check(self.lib.tvc_encode_image_backward(self.handle, _ptr(grad_out), _ptr(gp), _stream()))
         return gp
+
+    @contextlib.contextmanager
+    def _grad_mode(self, value: Optional[int]):
+        """Under the held lock: ``TVC_OPT_GRAD_PRECISION`` = value for the body, the engine's configured mode after it."""
+        if value is None or value == self.GRAD_PRECISIONS[self.grad_precision]:
+            yield
+            return
+        self._grad_option(value)
+        try:
+            yield
+        finally:
+            self._check(self.lib.tvc_set_option(self.handle, _lib.TVC_OPT_GRAD_PRECISION, self.GRAD_PRECISIONS[self.grad_precision]))
 
     def pgd_step(self, adv: torch.Tensor, clean: torch.Tensor, grad: torch.Tensor, momentum: Optional[torch.Tensor],
                  eps: float, alpha: float, mu: float = 0.9, clip_min: float = 0.0, clip_max: float = 1.0,
@@ -911,6 +955,19 @@ class TVCEngine:
                                                         heads, _stream()))
         return dqkv
 
+    def attention_split_backward(self, qkv: torch.Tensor, dout: torch.Tensor, n_seq: int, seq_len: int, heads: int) -> torch.Tensor:
+        """dQ | dK | dV fp32 [rows, 3 * width] of the dense non-causal tower attention on fp32 operands, every product on
+        hi | lo planes (``tvc_attention_split_backward``: the split-bf16 input gradient's attention backward)."""
+        qkv = _require_cuda(qkv, torch.float32, "qkv")
+        dout = _require_cuda(dout, torch.float32, "dout")
+        if qkv.shape != (n_seq * seq_len, 3 * heads * 64) or dout.shape != (n_seq * seq_len, heads * 64):
+            raise ValueError("attention_split_backward: qkv [rows, 3*heads*64] and dout [rows, heads*64] expected")
+        dqkv = torch.empty_like(qkv)
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.tvc_attention_split_backward(self.handle, _ptr(qkv), _ptr(dout), _ptr(dqkv), n_seq, seq_len,
+                                                              heads, _stream()))
+        return dqkv
+
     def layernorm_backward(self, x: torch.Tensor, dy: torch.Tensor, g: torch.Tensor,
                            dres: Optional[torch.Tensor] = None) -> torch.Tensor:
         x = _require_cuda(x, torch.float32, "x")
@@ -1032,6 +1089,19 @@ class TVCEngine:
             a.i[k] = int(v)
         with self._lock, torch.cuda.device(self.device):
             self._check(self.lib.tvc_tower_op(self.handle, _lib.TOWER_OPS[op], C.byref(a), _stream()))
+
+    def grad_split_op(self, op: str, ins=(), outs=(), i=()) -> None:
+        """One fp32 row kernel of the split-bf16 input gradient on the caller's tensors (``tvc_grad_split_op``): ``tower_op``'s
+        conventions, ``op`` a key of ``_lib.GRAD_SPLIT_OPS``."""
+        a = _lib.TowerOpArgs()
+        for k, t in enumerate(ins):
+            a.inp[k] = None if t is None else t.data_ptr()
+        for k, t in enumerate(outs):
+            a.out[k] = None if t is None else t.data_ptr()
+        for k, v in enumerate(i):
+            a.i[k] = int(v)
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.tvc_grad_split_op(self.handle, _lib.GRAD_SPLIT_OPS[op], C.byref(a), _stream()))
 
     PROF_CATEGORIES = ("gemm", "attention", "bank", "rowops")
 

@@ -2,7 +2,10 @@
 images, the three loops alternating in one process, each window ``--steps`` (default 10) iterations between two device events
 after one warm-up window, the median of ``--windows`` (default 5) windows each.  A step of either attack is PGD's forward and
 backward plus two small launches (tvc_attack_feature_grad, tvc_attack_step), so the three rates should sit within a few
-per cent of each other.  Prints one JSON line.  Run under ``timeout``; there is no result without a GPU."""
+per cent of each other.  ``--grad-precision both`` adds PGD's loop with the split-bf16 gradient (``pgd_split``:
+TVC_OPT_GRAD_PRECISION = 2, set per call) to the alternation, its cost relative to the bf16 step measured in the same process
+(``split_vs_bf16_step``) and the size of the state the two forwards keep; ``split`` runs every loop in that mode.
+Prints one JSON line.  Run under ``timeout``; there is no result without a GPU."""
 import argparse
 import importlib
 import json
@@ -22,11 +25,13 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--grad-precision", choices=("bf16", "split", "both"), default="bf16")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "attack_bench.py needs a GPU"
     A = pkg.attacks
     arch = pkg.get_arch(a.model)
-    model = pkg.CLIPModel(pkg.CLIPConfig(model_name=a.model, device="cuda:0"), weights=pkg.synth.make_clip_weights(arch, seed=0))
+    model = pkg.CLIPModel(pkg.CLIPConfig(model_name=a.model, device="cuda:0", grad_precision="split" if a.grad_precision == "split" else "bf16"),
+                          weights=pkg.synth.make_clip_weights(arch, seed=0))
     B = a.batch
     clean = torch.rand((B, 3, arch.image_size, arch.image_size), generator=torch.Generator().manual_seed(1)).cuda()
     unit = lambda seed: torch.nn.functional.normalize(
@@ -35,10 +40,10 @@ def main():
     eng = model.engine
     g_out = (text_f / B).contiguous()
 
-    def pgd():                                                       # PGDAttacker._steps without its host-side random start
+    def pgd(precision=None):                                         # PGDAttacker._steps without its host-side random start
         adv, mom = clean.clone(), torch.zeros_like(clean)
         for _ in range(a.steps):
-            eng.encode_image_grad(adv, True)
+            eng.encode_image_grad(adv, True, precision=precision)
             grad = eng.encode_image_backward(g_out)
             eng.pgd_step(adv, clean, grad, mom, 8 / 255, 2 / 255, 0.9, 0.0, 1.0, False)
         return adv
@@ -48,6 +53,8 @@ def main():
     loops = {"pgd": pgd,
              "fsta": lambda: fsta._loop(clean, text_f, target_f, "batch"),
              "sma": lambda: sma._loop(clean, text_f, target_f, "batch")}
+    if a.grad_precision == "both":
+        loops["pgd_split"] = lambda: pgd("split")
     for run in loops.values():                                       # warm-up: code objects, workspaces, kept activations
         run()
     torch.cuda.synchronize()
@@ -66,6 +73,11 @@ def main():
            "image_steps_per_s": {k: round(B * a.steps / (v / 1e3), 1) for k, v in med.items()},
            "window_ms_min_max": {k: [round(min(v), 2), round(max(v), 2)] for k, v in ms.items()},
            "rate_vs_pgd": {k: round(med["pgd"] / med[k], 4) for k in ("fsta", "sma")}}
+    out["grad_precision"] = a.grad_precision
+    if "pgd_split" in med:
+        out["split_vs_bf16_step"] = round(med["pgd_split"] / med["pgd"], 3)
+    v, rows = arch.vision, B * arch.vision_tokens
+    out["kept_state_bytes"] = {"bf16": v.layers * rows * (12 * v.width + 2 * v.mlp), "split": v.layers * rows * 4 * (5 * v.width + v.mlp)}
     print(json.dumps(out))
 
 

@@ -1,0 +1,102 @@
+"""CPU: the C-ABI surface and the host code of the split-bf16 input gradient (TVC_OPT_GRAD_PRECISION = 2) -- the option,
+tvc_grad_split_op and tvc_attention_split_backward are declared in include/tvc.h, bound in _lib and exported without an ABI version
+bump; the keep-size plan (csrc/host_plan.hpp: grad_split_keep_plan) gives the documented sizes and refuses what does not fit
+size_t, run under UBSan in a stand-alone program; the host code of both gradient entry points runs clean under AddressSanitizer /
+UBSan with leak detection through every refusal (tests/host_san_grad_split/driver.cpp on tests/host_san's HIP stand-in)."""
+import os
+import re
+import subprocess
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[1]
+CSRC = ROOT / "multimodal-detection-consistency_amd" / "csrc"
+HERE = ROOT / "tests" / "host_san_grad_split"
+NEW_OPS = ("gelu_bwd", "l2norm_bwd", "lnpre_bwd", "rows_split_t", "layernorm_bwd")
+
+
+def test_option_ops_and_entry_point_declared_bound_and_exported(pkg):
+    raw = (ROOT / "include" / "tvc.h").read_text()
+    h = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
+    L = pkg._lib
+    assert int(re.search(r"\bTVC_OPT_GRAD_PRECISION\s*=\s*(\d+)", h).group(1)) == L.TVC_OPT_GRAD_PRECISION == 11
+    # every TVC_OPT_* of the header has its value in _lib
+    for name, val in re.findall(r"\b(TVC_OPT_[A-Z_]+)\s*=\s*(\d+)", h):
+        assert getattr(L, name) == int(val), name
+    # the tower ops are the ones they were (tests/host_san/driver.cpp walks all of them); the new row kernels have an entry of
+    # their own, whose op codes the header and _lib.GRAD_SPLIT_OPS list alike, each documented in the slot table
+    assert int(re.search(r"\bTVC_TOWER_OP_COUNT\s*=\s*(\d+)", h).group(1)) == len(L.TOWER_OPS) == 20
+    ops = {n.lower(): int(v) for n, v in re.findall(r"\bTVC_GRAD_SPLIT_OP_([A-Z0-9_]+)\s*=\s*(\d+)", h)}
+    assert ops.pop("count") == len(L.GRAD_SPLIT_OPS) == 5 and ops == L.GRAD_SPLIT_OPS
+    for n in NEW_OPS:
+        assert n in ops and re.search(r"^ \*   " + n.upper() + r"\s", raw, flags=re.M), n
+    declared = set(re.findall(r"\b(tvc_[a-z0-9_]+)\s*\(", h)) - {"tvc_rec_stride"}       # a static inline helper
+    new = {"tvc_attention_split_backward", "tvc_grad_split_op"}
+    assert new <= declared and declared == set(L.SIGNATURES)
+    assert len(L.SIGNATURES["tvc_attention_split_backward"][1]) == 8 and len(L.SIGNATURES["tvc_grad_split_op"][1]) == 4
+    lib = L.load()
+    assert all(hasattr(lib, n) for n in new)
+    out = subprocess.run(["nm", "-D", "--defined-only", str(L.LIB_PATH)], capture_output=True, text=True).stdout
+    assert new <= set(re.findall(r"\bT (tvc_[a-z0-9_]+)", out))
+    assert lib.tvc_abi_version() == L.TVC_ABI_VERSION == 4                  # additive: no ABI version bump
+    assert "always run the bf16 path" not in raw and "TVC_OPT_GRAD_PRECISION (default 0)" in raw
+    # the Python surface
+    assert pkg.TVCEngine.GRAD_PRECISIONS == {"bf16": 0, "split": 2}
+    assert all(callable(getattr(pkg.TVCEngine, n)) for n in ("set_grad_precision", "attention_split_backward", "grad_split_op"))
+    assert pkg.CLIPConfig().grad_precision == "bf16" and pkg.CLIPConfig(grad_precision="split").precision == "bf16"
+    import pytest
+    with pytest.raises(ValueError):
+        pkg.CLIPConfig(grad_precision="fp64")
+
+
+def test_no_fixed_source_list_needs_the_grad_split_unit():
+    """The other host-sanitizer tests compile fixed source lists without tvc_grad_split.cpp: tvc_abi.cpp reaches it through the
+    table it registers in (handle.hpp: g_grad_split_ops), and nothing outside it names its entry point."""
+    for p in sorted(CSRC.glob("*.cpp")):
+        if p.name != "tvc_grad_split.cpp":
+            t = p.read_text()
+            assert "tvc_attention_split_backward" not in t and "tvc_grad_split_op" not in t and "build_transposed_planes" not in t, p.name
+    assert "g_grad_split_ops" in (CSRC / "tvc_abi.cpp").read_text() and "g_grad_split_ops = &OPS" in (CSRC / "tvc_grad_split.cpp").read_text()
+
+
+def test_keep_plan_sizes_under_ubsan(tmp_path):
+    exe = tmp_path / "plan"
+    b = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=undefined", "-fno-sanitize-recover=undefined", f"-I{CSRC}",
+                        str(HERE / "plan.cpp"), "-o", str(exe)], capture_output=True, text=True, timeout=300)
+    assert b.returncode == 0, b.stderr[-3000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60,
+                       env=dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
+    assert r.returncode == 0 and "runtime error" not in r.stderr, (r.stdout[-500:], r.stderr[-2000:])
+    lines = r.stdout.strip().splitlines()
+    assert lines[-1] == "refused 15 of 15"
+    rows_seen = set()
+    for line in lines[:-1]:
+        B, T, w, mlp, Ln, D, ok, rows, x, qkv, d1, u, xl, emb, per_layer, total = (int(v) for v in line.split())
+        rows_seen.add((B, T))
+        assert ok == 1 and rows == B * T
+        assert (x, qkv, d1, u) == (0, Ln * rows * w, Ln * rows * 4 * w, Ln * rows * 5 * w)          # x | qkv | d1 | u, in floats
+        assert xl == Ln * rows * (5 * w + mlp) and emb == xl + B * w
+        assert per_layer == 4 * rows * (5 * w + mlp)                                                # the issue's formula
+        assert total == Ln * per_layer + 4 * B * (w + D)
+    assert rows_seen == {(B, T) for B in (1, 32, 512) for T in (17, 50, 257)}
+    # ViT-L/14, 32 images: the 7.3 GB of DESIGN.md
+    vl = [ln for ln in lines if ln.startswith("32 257 1024 ")][0].split()
+    assert 7.2e9 < int(vl[-1]) < 7.4e9
+
+
+def test_grad_split_host_code_under_address_and_ub_sanitizers(tmp_path):
+    san = ROOT / "tests" / "host_san"
+    stubs = tmp_path / "stubs.cpp"
+    subprocess.run([sys.executable, str(san / "gen_stubs.py"), str(CSRC / "kernels.hpp"), str(stubs)], check=True)
+    for fn in ("launch_attention_split_bwd", "launch_rows_split_t", "launch_layernorm_bwd_f32", "launch_lnpre_bwd_f32",
+               "launch_gelu_bwd_f32", "launch_l2norm_bwd_f32"):
+        assert fn in stubs.read_text(), fn
+    exe = tmp_path / "driver_grad_split"
+    srcs = ("tvc_abi.cpp", "tvc_precise.cpp", "tvc_split.cpp", "tvc_sd.cpp", "tvc_sd_op.cpp", "tvc_tower_op.cpp", "tvc_grad_split.cpp")
+    cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           f"-I{san}", f"-I{CSRC}", "-x", "c++"] + [str(CSRC / f) for f in srcs] + [str(stubs), str(HERE / "driver.cpp"), "-o", str(exe)]
+    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert b.returncode == 0, b.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0 and "HOST_SAN_GRAD_SPLIT_OK" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])
