@@ -371,6 +371,57 @@ int tvc_kmeans_update(tvc_handle* h, const int32_t* labels_dev, const float* cen
                       float* centroids_out_dev, int32_t* counts_dev, int32_t* offsets_dev, int32_t* order_dev,
                       void* stream);
 
+/* ---- radius graph of a bank slot, and DBSCAN on a radius graph ---------------------------------------------- */
+
+/* DBSCAN(eps, min_samples).fit_predict(vectors) of src/ref_bank.py:302-315 is a pure function of the eps-graph
+ * A[i, j] = (|x_i - x_j|^2 <= eps^2), self included:
+ *   1. degree[i] = sum_j A[i, j]; row i is a CORE row iff degree[i] >= min_samples;
+ *   2. clusters = the connected components of the core-core subgraph, numbered 0 .. C - 1 in ascending order of each
+ *      component's lowest core index;
+ *   3. a non-core row with a core neighbour (a BORDER row) takes the lowest cluster id among its core neighbours, every
+ *      other non-core row is noise (-1).
+ * The graph is a bitmask uint32 [R, W], W = round_up(R, 64) / 32 (W(R) below): bit (j & 31) of word j / 32 of row i is
+ * A[i, j].  tvc_radius_graph builds it from the selected bank slot; the two component calls take ANY such bitmask (they
+ * read no bank slot), so a caller may cluster a graph of its own.  The centres of the clusters are tvc_kmeans_update
+ * with K = n_clusters on the labels (it ignores -1, and its sums are in a fixed order).  The driver loop over the sweeps
+ * is the caller's. */
+#define TVC_RADIUS_MAX_ROWS 131072   /* rows of a radius graph: 2 GiB of bits */
+
+/* The eps-graph of the rows of the selected slot (any [R, D] matrix; the rows need not be unit length).
+ *   eps         finite, > 0 (an fp32 value: the test is against its square in fp32)
+ *   adj_dev     uint32 [R, W(R)], 8-byte aligned.  Symmetric bit for bit; the padding bits (j >= R) are zero; the
+ *               diagonal bit of every row with a finite norm is set; a row whose squared norm is not finite (NaN, inf
+ *               or fp32 overflow) has no neighbours, not even itself
+ *   degree_dev  int32 [R]: the popcount of the row, self included
+ * The [R, R] products live in MFMA accumulators tile by tile (a self-GEMM of the slot, upper triangle of 256 x 256
+ * tiles, then adj |= adj^T): a bf16 slot multiplies its stored values (exact products), an fp32 slot all four hi / lo
+ * plane products.  The test is  x_i . x_j >= h_i + h_j,  h = |x|^2 / 2 - eps^2 / 4, in fp32: a pair whose squared
+ * distance is within ~1e-5 |x_i| |x_j| of eps^2 may fall on either side.
+ * TVC_E_STATE when the slot holds no bank or R == 0; TVC_E_INVALID when eps is not finite and positive, R >
+ * TVC_RADIUS_MAX_ROWS, a buffer is NULL or adj is misaligned.  Nothing is launched on a refusal. */
+int tvc_radius_graph(tvc_handle* h, float eps, uint32_t* adj_dev, int32_t* degree_dev, void* stream);
+
+/* One sweep of minimum-label propagation on the bitmask adj [R, W(R)] with degrees degree [R].
+ *   comp_dev     int32 [R]: with init != 0 first set to i for core rows and R for the others.  The sweep lowers comp[i]
+ *                and comp[comp[i]] to the lowest label among row i's core neighbours (integer atomicMin), then every
+ *                core row follows its chain of labels to its end.  The fixed point -- every core row holds the lowest
+ *                core index of its component -- is unique; the number of sweeps that reach it is not.
+ *   changed_dev  int32 [1]: a sweep that lowered a label ORs 1 into it (the caller zeroes it).  The labels are final
+ *                after a sweep that left it 0; R sweeps always suffice.
+ * Set bits at j >= R and labels outside [0, R) are skipped, never dereferenced. */
+int tvc_dbscan_sweep(tvc_handle* h, const uint32_t* adj_dev, const int32_t* degree_dev, int32_t R, int32_t min_samples,
+                     int32_t* comp_dev, int32_t* changed_dev, int32_t init, void* stream);
+
+/* comp at its fixed point -> the labels of rules 2 and 3.
+ *   labels_dev      int32 [R]
+ *   core_dev        uint8 [R]: 1 for core rows
+ *   n_clusters_dev  int32 [1]: C
+ * Both component calls return TVC_E_INVALID for R < 1, R > TVC_RADIUS_MAX_ROWS, min_samples < 1 or a NULL buffer;
+ * nothing is launched then. */
+int tvc_dbscan_finish(tvc_handle* h, const uint32_t* adj_dev, const int32_t* degree_dev, int32_t R, int32_t min_samples,
+                      const int32_t* comp_dev, int32_t* labels_dev, uint8_t* core_dev, int32_t* n_clusters_dev,
+                      void* stream);
+
 /* ---- IVF search: probe + list scan over a bank slot ------------------------------------------------ */
 
 /* An IVF index over R rows is four things:

@@ -3,7 +3,8 @@
 // fp16 towers, bank, consistency; tvc_precise.cpp: the fp32-grade towers' stem, layer loop and head; tvc_split.cpp: the
 // split-bf16 towers' stem, layer loop, head and weight planes; tvc_sd.cpp: latent-diffusion reference generator,
 // tvc_sd_op.cpp: its entry points that read no model state; tvc_kmeans.cpp: k-means over a bank slot;
-// tvc_ivf.cpp: IVF probe and list scan; tvc_grad_split.cpp: the split-bf16 input gradient).
+// tvc_ivf.cpp: IVF probe and list scan; tvc_grad_split.cpp: the split-bf16 input gradient; tvc_dbscan.cpp: radius graph and
+// DBSCAN labels).
 #pragma once
 #include "../../include/tvc.h"
 #include "kernels.hpp"
@@ -44,6 +45,8 @@ enum Slot {
     // split-bf16 input gradient (TVC_OPT_GRAD_PRECISION = 2, tvc_grad_split.cpp): what the forward keeps, the gradient's planes
     // (d-wide; mlp- / 3d-wide), fp32 scratch (mlp- / 3d- / Kp-wide; d-wide) and the head's small rows
     WS_GS_KEEP, WS_GS_GP, WS_GS_MP, WS_GS_WIDE, WS_GS_ROW, WS_GS_SMALL,
+    // radius graph over a bank slot (tvc_dbscan.cpp): the rows' squared norms and the padded half-norm vector of the distance test
+    WS_DB_NORM2, WS_DB_HALF,
     WS_COUNT
 };
 

@@ -72,6 +72,36 @@ inline void kmeans_update_plan(int64_t R, int K, int* nblocks, int* rows_per_blo
     *nblocks = (int)((R + *rows_per_block - 1) / *rows_per_block > 0 ? (R + *rows_per_block - 1) / *rows_per_block : 1);
 }
 
+// Radius graph / DBSCAN (dbscan.hip): the graph of R rows is a bitmask uint32 [R, words], words = round_up(R, 64) / 32 (an even
+// count: a wave of the tile kernel stores one 64-bit word per row).  The tile kernel's grid is tiles x tiles 256 x 256 tiles of
+// which the upper triangle computes; the half-norm vector is padded to whole tiles (hpad floats, NaN beyond R).  The
+// symmetrise pass owns one pair of 32 x 32 bit blocks per half wave: blocks32 row blocks on the grid's y, 8 column blocks per
+// 256-thread workgroup on its x.  RADIUS_MAX_ROWS is include/tvc.h's TVC_RADIUS_MAX_ROWS: 2 GiB of bits.
+#define RADIUS_MAX_ROWS 131072
+struct RadiusPlan {
+    bool ok = false;
+    int64_t words = 0;                  // uint32 per row of adj
+    int tiles = 0;                      // 256-row tiles per side
+    int64_t hpad = 0;                   // floats of the padded half-norm vector
+    int blocks32 = 0;                   // 32-row blocks per side (= words)
+    int sym_grid_x = 0;                 // ceil(blocks32 / 8)
+    int64_t adj_bytes = 0;
+    double tile_pairs = 0;              // computed tiles: tiles * (tiles + 1) / 2
+};
+inline RadiusPlan radius_plan(int64_t R) {
+    RadiusPlan p;
+    if (R < 1 || R > RADIUS_MAX_ROWS) return p;
+    p.words = (R + 63) / 64 * 2;
+    p.tiles = (int)((R + HOST_PLAN_GEMM_BM - 1) / HOST_PLAN_GEMM_BM);
+    p.hpad = (int64_t)p.tiles * HOST_PLAN_GEMM_BM;
+    p.blocks32 = (int)p.words;
+    p.sym_grid_x = (p.blocks32 + 7) / 8;
+    p.adj_bytes = R * p.words * 4;
+    p.tile_pairs = 0.5 * p.tiles * (p.tiles + 1.0);
+    p.ok = true;
+    return p;
+}
+
 // IVF scan (ivf.hip): the scan writes every (query, probe) pair's similarities with the rows of its list into a score buffer
 // [pairs, pitch] fp32, pitch = round_up(max_list_rows, 16); the queries are cut into chunks so that the buffer of a chunk
 // stays under IVF_SCORE_BUDGET (256 MiB: 4 608 queries x 10 probes x lists of up to 1 450 rows go in one chunk).  A single

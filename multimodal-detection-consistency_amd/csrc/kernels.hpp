@@ -187,6 +187,28 @@ struct LabelSortLaunch {
     int32_t* order = nullptr;         // [R]: entries [0, offsets[K]) are written
 };
 hipError_t launch_label_sort(const LabelSortLaunch& L, hipStream_t stream);
+// out[r] = |x_r|^2 of every stored row of the slot (hi + lo of an fp32 bank), fp32 [R]
+hipError_t launch_kmeans_rownorm(const BankRows& bank, float* out, hipStream_t stream);
+
+// ---- dbscan.hip: the eps-graph of a bank slot as a bitmask, and DBSCAN's labels from such a graph (exact integer work)
+struct RadiusGraphLaunch {
+    BankRows bank;
+    float eps = 0.f;
+    RadiusPlan plan;                  // radius_plan(bank.R)
+    float* norm2 = nullptr;           // workspace [R]: |x|^2
+    float* half = nullptr;            // workspace [plan.hpad]: |x|^2 / 2 - eps^2 / 4; NaN for a non-finite norm and in the padding
+    uint32_t* adj = nullptr;          // [R, plan.words]: bit j of row i = (|x_i - x_j|^2 <= eps^2), symmetric, padding bits zero
+    int32_t* degree = nullptr;        // [R]: popcount of the row, self included
+};
+hipError_t launch_radius_graph(const RadiusGraphLaunch& L, hipStream_t stream);
+// one sweep of minimum-label propagation over the core-core edges of adj [R, round_up(R, 64) / 32], then a pointer jump;
+// init: comp[i] = i for core rows (degree >= min_samples), R otherwise, first.  A sweep that lowered a label ORs 1 into *changed.
+hipError_t launch_dbscan_sweep(const uint32_t* adj, const int32_t* degree, int R, int min_samples, int32_t* comp, int32_t* changed,
+                               int init, hipStream_t stream);
+// comp at its fixed point -> labels [R] (clusters numbered by their lowest core row; border rows the lowest id among their core
+// neighbours; -1 noise), core [R] (0 / 1) and *n_clusters
+hipError_t launch_dbscan_finish(const uint32_t* adj, const int32_t* degree, int R, int min_samples, const int32_t* comp,
+                                int32_t* labels, uint8_t* core, int32_t* n_clusters, hipStream_t stream);
 
 // ---- ivf.hip: inverted-file search (probe: the nprobe best lists of a query; scan: exact top-k over the probed lists)
 struct IvfProbeLaunch {

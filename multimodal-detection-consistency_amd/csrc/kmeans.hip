@@ -135,6 +135,13 @@ hipError_t launch_kmeans_halfnorm(const float* centroids, int D, int K, int Kpad
     return launch<kmeans_halfnorm_kernel>(dim3((Kpad + 3) / 4), dim3(256), 0, stream, centroids, D, K, Kpad, halfnorm);
 }
 
+hipError_t launch_kmeans_rownorm(const BankRows& bank, float* out, hipStream_t stream) {
+    if (bank.R < 1 || bank.D < 8 || bank.D % 8 != 0 || bank.planes < 1 || bank.planes > 2) return hipErrorInvalidValue;
+    int64_t grid = (bank.R + 3) / 4;
+    if (grid > 16384) grid = 16384;
+    return launch<kmeans_rownorm_kernel>(dim3((int)grid), dim3(256), 0, stream, bank, out);
+}
+
 hipError_t launch_kmeans_assign(const KmeansAssignLaunch& L, hipStream_t stream) {
     const BankRows& B = L.bank;
     if (B.R < 1 || B.R > 0x7fffffffLL || L.K < 1 || B.D < 64 || B.D % 64 != 0 || B.planes < 1 || B.planes > 2)
@@ -144,9 +151,7 @@ hipError_t launch_kmeans_assign(const KmeansAssignLaunch& L, hipStream_t stream)
     hipError_t st = launch_kmeans_halfnorm(L.centroids, B.D, L.K, Kpad, L.halfnorm, stream);
     if (st != hipSuccess) return st;
     if (L.dist2) {
-        int64_t grid = (B.R + 3) / 4;
-        if (grid > 16384) grid = 16384;
-        st = launch<kmeans_rownorm_kernel>(dim3((int)grid), dim3(256), 0, stream, B, L.dist2);
+        st = launch_kmeans_rownorm(B, L.dist2, stream);
         if (st != hipSuccess) return st;
     }
     // centres on the MFMA row dimension (A), bank rows on the lane dimension (B)

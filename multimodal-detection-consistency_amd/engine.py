@@ -698,6 +698,89 @@ class TVCEngine:
         _, _, offsets, order = self.kmeans_update(labels, Cc, bank=bank, want_lists=True)
         return Cc, labels, inertia, n_iter, order, offsets
 
+    # ---- radius graph of a bank slot, DBSCAN on a radius graph -------------
+    DBSCAN_SWEEP_BATCH = 4
+
+    @staticmethod
+    def radius_words(R: int) -> int:
+        """uint32 words per row of a radius graph over R rows: round_up(R, 64) / 32."""
+        return (R + 63) // 64 * 2
+
+    def radius_graph(self, eps: float, bank: str = DEFAULT_BANK):
+        """-> (adj int32 [R, W], degree int32 [R]) over the rows of ``bank``: bit ``j & 31`` of ``adj[i, j // 32]`` is
+        ``|x_i - x_j|^2 <= eps^2`` (the words are uint32 bit patterns held in int32, W = ``radius_words(R)``).  Symmetric bit
+        for bit, zero padding bits, the diagonal set for every row of finite norm; ``degree`` is the popcount of the row,
+        self included.  ``eps`` is taken as an fp32 value."""
+        eps = float(eps)
+        if not (eps > 0.0 and eps != float("inf")):
+            raise ValueError(f"eps must be finite and positive (got {eps})")
+        with self._lock, torch.cuda.device(self.device):
+            b = self._select(bank)
+            R = b["rows"]
+            adj = torch.empty((R, self.radius_words(R)), dtype=torch.int32, device=self.device)
+            degree = torch.empty(R, dtype=torch.int32, device=self.device)
+            self._check(self.lib.tvc_radius_graph(self.handle, eps, _ptr(adj), _ptr(degree), _stream()))
+        return adj, degree
+
+    def dbscan_labels(self, adj: torch.Tensor, degree: torch.Tensor, min_samples: int):
+        """adj int32 [R, radius_words(R)] (any symmetric bitmask graph, ``radius_graph``'s or the caller's), degree int32
+        [R] -> (labels int32 [R], core bool [R], n_clusters int, sweeps int).  Core rows have ``degree >= min_samples``;
+        clusters are the components of the core-core graph, numbered by their lowest core row; a border row takes the
+        lowest id among its core neighbours; noise is -1.  The labels are exact and deterministic; ``sweeps`` (label
+        propagation sweeps up to and including the first that lowered nothing) is not.  The loop is Python, as the k-means
+        loop is: sweeps run in batches of ``DBSCAN_SWEEP_BATCH``, each sweep of a batch flags its own ``changed`` word and
+        the words are read once per batch, so up to ``DBSCAN_SWEEP_BATCH - 1`` idle sweeps run after the confirming one.
+        R sweeps always suffice: a graph still changing after them raises ``RuntimeError``."""
+        adj = _require_cuda(adj, torch.int32, "adj")
+        degree = _require_cuda(degree, torch.int32, "degree")
+        if adj.dim() != 2 or adj.shape[0] < 1 or adj.shape[1] != self.radius_words(adj.shape[0]):
+            raise ValueError(f"adj must be [R, round_up(R, 64) / 32] with R >= 1 (got {tuple(adj.shape)})")
+        R = adj.shape[0]
+        if degree.shape != (R,):
+            raise ValueError(f"degree must be [{R}] (got {tuple(degree.shape)})")
+        min_samples = int(min_samples)
+        if min_samples < 1:
+            raise ValueError(f"min_samples must be >= 1 (got {min_samples})")
+        comp = torch.empty(R, dtype=torch.int32, device=self.device)
+        changed = torch.zeros(self.DBSCAN_SWEEP_BATCH, dtype=torch.int32, device=self.device)    # one word per sweep of a batch
+        labels = torch.empty(R, dtype=torch.int32, device=self.device)
+        core = torch.empty(R, dtype=torch.uint8, device=self.device)
+        n_clusters = torch.zeros(1, dtype=torch.int32, device=self.device)
+        done = 0
+        with self._lock, torch.cuda.device(self.device):
+            while True:
+                if done >= R:
+                    raise RuntimeError(f"dbscan_labels: the labels still change after {done} sweeps over {R} rows")
+                changed.zero_()
+                n = min(self.DBSCAN_SWEEP_BATCH, R - done)
+                for k in range(n):
+                    self._check(self.lib.tvc_dbscan_sweep(self.handle, _ptr(adj), _ptr(degree), R, min_samples, _ptr(comp),
+                                                          C.c_void_p(changed.data_ptr() + 4 * k), 1 if done + k == 0 else 0,
+                                                          _stream()))
+                flags = changed[:n].tolist()
+                if 0 in flags:                    # the first sweep that lowered nothing: the sweeps after it were idle
+                    sweeps = done + flags.index(0) + 1
+                    break
+                done += n
+            self._check(self.lib.tvc_dbscan_finish(self.handle, _ptr(adj), _ptr(degree), R, min_samples, _ptr(comp), _ptr(labels),
+                                                   _ptr(core), _ptr(n_clusters), _stream()))
+        return labels, core.bool(), int(n_clusters.item()), sweeps
+
+    def dbscan(self, eps: float = 0.5, min_samples: int = 5, bank: str = DEFAULT_BANK):
+        """``DBSCAN(eps, min_samples).fit_predict`` over the rows of ``bank`` (src/ref_bank.py:302-315) -> (labels int32 [R],
+        core bool [R], centres fp32 [C, D] | None, order int32 [R], offsets int32 [C + 1]): ``radius_graph``, ``dbscan_labels``
+        and the mean of every cluster's rows, core and border, through ``kmeans_update`` (bit-reproducible).
+        ``order[offsets[c]:offsets[c + 1]]`` are cluster c's rows in ascending order, the rest of ``order`` is -1.  Without
+        a cluster the centres are ``None`` and nothing is launched for them.  More than 65 536 clusters are refused by
+        ``tvc_kmeans_update``."""
+        adj, degree = self.radius_graph(eps, bank=bank)
+        labels, core, n_clusters, _ = self.dbscan_labels(adj, degree, min_samples)
+        if n_clusters == 0:
+            return (labels, core, None, torch.full_like(labels, -1), torch.zeros(1, dtype=torch.int32, device=self.device))
+        zeros = torch.zeros((n_clusters, self._banks[bank]["dim"]), dtype=torch.float32, device=self.device)
+        centres, _, offsets, order = self.kmeans_update(labels, zeros, bank=bank, want_lists=True)
+        return labels, core, centres, order, offsets
+
     # ---- IVF search over a bank slot in list order -------------------------
     def ivf_probe(self, rows: torch.Tensor, centroids: torch.Tensor, nprobe: int):
         """rows fp32 [M, D], centroids fp32 [nlist, D] -> (lists int32 [M, nprobe], score fp32 [M, nprobe]): the nprobe

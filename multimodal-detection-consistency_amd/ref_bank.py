@@ -13,9 +13,14 @@ vectors are registered under a second, temporary bank slot and clustered by
 ``TVCEngine.kmeans`` (``tvc_kmeans_assign`` / ``tvc_kmeans_update``) with the
 reference's ``n_init=10``, seed 42.  The restarts draw their starting centres from
 numpy's generator, not sklearn's, so the clusters are a k-means optimum of the same
-data but not sklearn's own labelling.  Out of scope: DBSCAN clustering (the method
-is accepted by the config and fails as the reference's own ``except`` does: an
-error is logged and ``perform_clustering`` returns False) and JSON persistence.
+data but not sklearn's own labelling.  DBSCAN (``src/ref_bank.py:302-315``) runs over
+the same temporary slot through ``TVCEngine.dbscan`` (``tvc_radius_graph``, the
+``tvc_dbscan_*`` component calls and ``tvc_kmeans_update`` for the centres) once
+``ReferenceBankConfig.dbscan_eps`` is set -- the reference's value is 0.5, which on
+raw CLIP vectors of norm ~10 makes every row noise; with the default ``None`` the
+method is refused as before (an error is logged and ``perform_clustering`` returns
+False).  Its labels are sklearn's own: DBSCAN is a pure function of the eps-graph.
+Out of scope: JSON persistence.
 """
 from __future__ import annotations
 
@@ -47,12 +52,18 @@ class ReferenceBankConfig:
     auto_clustering: bool = False
     clustering_interval: int = 1000
     feature_dim: int = 512
+    dbscan_eps: Optional[float] = None      # None: "dbscan" is refused; the reference hard-codes 0.5 (:304)
+    dbscan_min_samples: int = 5             # :304
 
     def __post_init__(self):
         if self.clustering_method not in ("kmeans", "dbscan", "none"):
             raise ValueError(f"unsupported clustering method: {self.clustering_method}")
         if self.update_strategy not in ("fifo", "lru", "random", "similarity"):
             raise ValueError(f"unsupported update strategy: {self.update_strategy}")
+        if self.dbscan_eps is not None and not (0.0 < float(self.dbscan_eps) < float("inf")):
+            raise ValueError(f"dbscan_eps must be positive and finite, or None (got {self.dbscan_eps})")
+        if int(self.dbscan_min_samples) < 1:
+            raise ValueError(f"dbscan_min_samples must be >= 1 (got {self.dbscan_min_samples})")
 
 
 @dataclass
@@ -220,14 +231,16 @@ class ReferenceBank:
         if method == "none":                 # without force :289-290; with force the method falls through to :317-318
             return False
         try:
-            if method != "kmeans":
+            if method != "kmeans" and not (method == "dbscan" and self.config.dbscan_eps is not None):
                 raise NotImplementedError(f"clustering method {method!r} is not built on the GPU path")
             D, Dp = self.config.feature_dim, self._padded_dim()
             V = np.zeros((len(self.references), Dp), dtype=np.float32)
             for i, r in enumerate(self.references):
                 V[i, :D] = r.vector
-            n_clusters = min(self.config.num_clusters, len(self.references))
             name = self.bank_name + ":raw"
+            if method == "dbscan":
+                return self._cluster_dbscan(V, name)
+            n_clusters = min(self.config.num_clusters, len(self.references))
             try:
                 self.engine.set_bank(torch.from_numpy(V).to(self.engine.device), name=name)
                 centres, labels, _, _, order, offsets = self.engine.kmeans(n_clusters, bank=name, n_init=10, seed=42, n_features=D)
@@ -250,6 +263,29 @@ class ReferenceBank:
         except Exception as e:               # the reference's failure contract (:337-339)
             logger.error(f"clustering failed: {e}")
             return False
+
+    def _cluster_dbscan(self, V: np.ndarray, name: str) -> bool:
+        """src/ref_bank.py:302-315 (lock held): DBSCAN(eps, min_samples) over the raw vectors, the mean of every non-noise
+        cluster as its centre; no cluster at all is a success with ``clusters == {}`` and no centres, as in the reference."""
+        D = self.config.feature_dim
+        try:
+            self.engine.set_bank(torch.from_numpy(V).to(self.engine.device), name=name)
+            labels, _, centres, order, offsets = self.engine.dbscan(float(self.config.dbscan_eps), int(self.config.dbscan_min_samples),
+                                                                    bank=name)
+        finally:
+            self.engine.release_bank(name)
+        self.cluster_centers = centres[:, :D].double().cpu().numpy() if centres is not None else None
+        self.cluster_init = None
+        labels, order, offsets = labels.cpu().numpy(), order.cpu().numpy(), offsets.cpu().numpy()
+        self.clusters.clear()
+        for j in range(len(offsets) - 1):         # the member lists come grouped and ascending from the counting sort
+            self.clusters[j] = order[offsets[j]:offsets[j + 1]].tolist()
+        for i, r in enumerate(self.references):
+            r.cluster_id = int(labels[i]) if labels[i] >= 0 else None
+        self.stats["clustering_count"] += 1
+        self.stats["last_clustering_time"] = time.time()
+        logger.info(f"clustering done: {len(self.clusters)} clusters")
+        return True
 
     def query_similar(self, query_vector: np.ndarray, top_k: int = 10,
                       similarity_threshold: Optional[float] = None) -> List[Tuple[ReferenceItem, float]]:
