@@ -422,6 +422,47 @@ int tvc_dbscan_finish(tvc_handle* h, const uint32_t* adj_dev, const int32_t* deg
                       const int32_t* comp_dev, int32_t* labels_dev, uint8_t* core_dev, int32_t* n_clusters_dev,
                       void* stream);
 
+/* ---- pair lists of a bitmask graph, and the cosine of listed pairs ------------------------------------------- */
+
+/* The data validator's near-duplicate and leakage checks (src/evaluation/data_validator.py:353-543) are pure functions of
+ * "which pairs i < j have cosine >= t, and what is that cosine".  On unit rows cosine >= t is |x_i - x_j|^2 <= 2 - 2t, a
+ * radius graph; these calls turn such a graph into the reference's pair list and give the listed pairs an fp32-grade
+ * cosine (the graph itself is decided to ~1e-5 only).  The graph calls take ANY bitmask uint32 [R, W(R)] in
+ * tvc_radius_graph's layout, symmetric or not, and read no bank slot. */
+
+/* The rows' pair counts, scanned.
+ *   adj_dev      uint32 [R, W(R)]
+ *   group_dev    int32 [R] or NULL
+ *   offsets_dev  int64 [R + 1]: offsets[i] = the number of pairs of the rows before i, offsets[R] = the exact total (int64:
+ *                it may exceed 2^31)
+ * The count of row i is the number of set bits j with i < j < R; with group_dev a bit also needs group[i] >= 0,
+ * group[j] >= 0 and group[i] != group[j].  The lower triangle, the diagonal and the padding bits j >= R never count. */
+int tvc_graph_pair_count(tvc_handle* h, const uint32_t* adj_dev, int32_t R, const int32_t* group_dev, int64_t* offsets_dev,
+                         void* stream);
+
+/* The pairs themselves, with the same adj, R and group and the offsets tvc_graph_pair_count wrote.
+ *   pairs_dev    int32 [P, 2]: row i writes its pairs (i, j) in ascending j from slot offsets[i], so the list is
+ *                lexicographic in (i, j) -- the order of the reference's nested loops -- and a pure function of
+ *                (adj, group): no atomics.  A slot outside [0, P) is never written: with P < offsets[R] exactly the first
+ *                P pairs arrive and nothing behind them is touched.
+ * P == 0 is legal and launches nothing (pairs_dev may then be NULL).
+ * Both graph calls return TVC_E_INVALID for R < 1, R > TVC_RADIUS_MAX_ROWS, P < 0 or a NULL adj, offsets or (P > 0)
+ * pairs; nothing is launched then. */
+int tvc_graph_pair_fill(tvc_handle* h, const uint32_t* adj_dev, int32_t R, const int32_t* group_dev,
+                        const int64_t* offsets_dev, int32_t* pairs_dev, int64_t P, void* stream);
+
+/* sim[p] = x . y / sqrt(|x|^2 |y|^2) for the stored rows x = pairs[p, 0], y = pairs[p, 1] of the selected slot (a bf16
+ * slot: its stored values; an fp32 slot: hi + lo of every element).
+ *   pairs_dev    int32 [P, 2]; any pairs, not only a graph's
+ *   sim_dev      fp32 [P]
+ * The three sums are fp32 FMA chains in a fixed order that depends on D alone, reduced in a fixed order:
+ *   |sim - cos64(stored rows)| <= 2^-24 (2 D + 16),
+ * bit-identical between runs and for (i, j) and (j, i).  sim is 0 when either row is all zero (and the other is not NaN);
+ * NaN propagates; a pair with an index outside [0, R) gets NaN and its rows are never dereferenced.
+ * TVC_E_STATE when the slot holds no bank rows; TVC_E_INVALID for P < 0 or, with P > 0, a NULL buffer.  P == 0 is legal
+ * and launches nothing. */
+int tvc_pair_cosine(tvc_handle* h, const int32_t* pairs_dev, int64_t P, float* sim_dev, void* stream);
+
 /* ---- IVF search: probe + list scan over a bank slot ------------------------------------------------ */
 
 /* An IVF index over R rows is four things:

@@ -14,6 +14,7 @@ from .attacks import (FSTAAttackConfig, FSTAAttacker, FSTAAttackPresets, Hubness
                       create_fsta_attacker, create_hubness_attacker, create_pgd_attacker, create_sma_attacker)
 from .arch import ARCHS, ClipArch, Tower, get_arch
 from .clip import CLIPConfig, CLIPModel
+from .data_validator import DataValidationConfig, DataValidator, ValidationResult, create_data_validator
 from .detector import (AdversarialDetector, ConsistencyChecker, DetectionConfig, DetectorConfig,
                        MultiModalDefenseDetector, aggregate_scores, create_adversarial_detector, unpack_records)
 from .engine import ConsistencyConfig, IVFIndex, TVCEngine

@@ -4,7 +4,7 @@
 // split-bf16 towers' stem, layer loop, head and weight planes; tvc_sd.cpp: latent-diffusion reference generator,
 // tvc_sd_op.cpp: its entry points that read no model state; tvc_kmeans.cpp: k-means over a bank slot;
 // tvc_ivf.cpp: IVF probe and list scan; tvc_grad_split.cpp: the split-bf16 input gradient; tvc_dbscan.cpp: radius graph and
-// DBSCAN labels).
+// DBSCAN labels; tvc_pairs.cpp: pair lists of a bitmask graph and the cosine of listed pairs).
 #pragma once
 #include "../../include/tvc.h"
 #include "kernels.hpp"

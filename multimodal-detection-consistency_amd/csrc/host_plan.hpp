@@ -102,6 +102,37 @@ inline RadiusPlan radius_plan(int64_t R) {
     return p;
 }
 
+// Pair lists of a bitmask graph and the cosine of listed pairs (pairs.hip).  The count and the fill give one wave to a row, four
+// rows to a 256-thread workgroup, on a grid-stride loop of at most PAIRS_MAX_GRID workgroups; the scan of the counts is one
+// workgroup of PAIRS_SCAN_THREADS threads that own scan_per consecutive rows each.  The cosine gives PAIR_COS_LANES lanes to a
+// pair, so a workgroup takes 256 / PAIR_COS_LANES pairs per trip of its grid-stride loop.
+#define PAIRS_MAX_GRID 16384
+#define PAIRS_SCAN_THREADS 1024
+#define PAIR_COS_LANES 16
+struct PairsPlan {
+    bool ok = false;
+    int words = 0;                      // uint32 per row of adj: radius_plan(R).words
+    int row_grid = 0;                   // workgroups of the count and of the fill
+    int scan_per = 0;                   // rows per thread of the scan: ceil(R / PAIRS_SCAN_THREADS)
+};
+inline PairsPlan pairs_plan(int64_t R) {
+    PairsPlan p;
+    if (R < 1 || R > RADIUS_MAX_ROWS) return p;
+    p.words = (int)((R + 63) / 64 * 2);
+    const int64_t g = (R + 3) / 4;
+    p.row_grid = (int)(g < PAIRS_MAX_GRID ? g : PAIRS_MAX_GRID);
+    p.scan_per = (int)((R + PAIRS_SCAN_THREADS - 1) / PAIRS_SCAN_THREADS);
+    p.ok = true;
+    return p;
+}
+// workgroups of the cosine over P pairs (0 for P <= 0: nothing to launch)
+inline int pair_cosine_grid(int64_t P) {
+    if (P <= 0) return 0;
+    const int64_t per = 256 / PAIR_COS_LANES;
+    const int64_t g = (P + per - 1) / per;
+    return (int)(g < 65536 ? g : 65536);
+}
+
 // IVF scan (ivf.hip): the scan writes every (query, probe) pair's similarities with the rows of its list into a score buffer
 // [pairs, pitch] fp32, pitch = round_up(max_list_rows, 16); the queries are cut into chunks so that the buffer of a chunk
 // stays under IVF_SCORE_BUDGET (256 MiB: 4 608 queries x 10 probes x lists of up to 1 450 rows go in one chunk).  A single

@@ -210,6 +210,17 @@ hipError_t launch_dbscan_sweep(const uint32_t* adj, const int32_t* degree, int R
 hipError_t launch_dbscan_finish(const uint32_t* adj, const int32_t* degree, int R, int min_samples, const int32_t* comp,
                                 int32_t* labels, uint8_t* core, int32_t* n_clusters, hipStream_t stream);
 
+// ---- pairs.hip: the upper triangle of a bitmask graph as a pair list, and the fp32-grade cosine of listed pairs of a bank slot
+// offsets int64 [R + 1]: the exclusive scan of the rows' counts of set bits j, i < j < R (with group: both groups >= 0 and
+// different); adj [R, round_up(R, 64) / 32] is any bitmask
+hipError_t launch_graph_pair_count(const uint32_t* adj, int R, const int32_t* group, int64_t* offsets, hipStream_t stream);
+// pairs int32 [P, 2]: row i's pairs (i, j) in ascending j from slot offsets[i]; a slot outside [0, P) is not written
+hipError_t launch_graph_pair_fill(const uint32_t* adj, int R, const int32_t* group, const int64_t* offsets, int32_t* pairs, int64_t P,
+                                  hipStream_t stream);
+// sim[p] = x.y / sqrt(|x|^2 |y|^2) of the stored rows pairs[p] of the slot in fp32 FMAs of a fixed order; 0 for a zero row, NaN
+// for an index outside [0, R)
+hipError_t launch_pair_cosine(const BankRows& bank, const int32_t* pairs, int64_t P, float* sim, hipStream_t stream);
+
 // ---- ivf.hip: inverted-file search (probe: the nprobe best lists of a query; scan: exact top-k over the probed lists)
 struct IvfProbeLaunch {
     const uint16_t* cplanes = nullptr;// [nlist, 2 * D] bf16 (hi | lo) planes of the centroids

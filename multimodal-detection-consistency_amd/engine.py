@@ -781,6 +781,89 @@ class TVCEngine:
         centres, _, offsets, order = self.kmeans_update(labels, zeros, bank=bank, want_lists=True)
         return labels, core, centres, order, offsets
 
+    # ---- pair lists of a bitmask graph, cosine of listed pairs, similar pairs of a slot of unit rows ----
+    SIMILAR_TAU = 1.1e-5       # DESIGN.md 4.13's tau_ij for rows of norm <= 1 + 2^-8: (8e-6 + 2^-19) (1 + 2^-8)^2 < 1.1e-5
+
+    def graph_pairs(self, adj: torch.Tensor, groups: Optional[torch.Tensor] = None, max_pairs: int = 1 << 27):
+        """adj int32 [R, radius_words(R)] (any bitmask graph, symmetric or not), groups int32 [R] | None -> (pairs int32
+        [P, 2], offsets int64 [R + 1]): the set bits ``i < j < R`` of the upper triangle in lexicographic (i, j) order, the
+        order of a double loop ``for i: for j > i``; row i's pairs are ``pairs[offsets[i]:offsets[i + 1]]``.  With ``groups``
+        a pair also needs both groups ``>= 0`` and different.  One host read (the total) sits between the count and the
+        fill; a total above ``max_pairs`` raises ``ValueError`` naming it -- the list is never truncated."""
+        adj = _require_cuda(adj, torch.int32, "adj")
+        if adj.dim() != 2 or adj.shape[0] < 1 or adj.shape[1] != self.radius_words(adj.shape[0]):
+            raise ValueError(f"adj must be [R, round_up(R, 64) / 32] with R >= 1 (got {tuple(adj.shape)})")
+        R = adj.shape[0]
+        if groups is not None:
+            groups = _require_cuda(groups, torch.int32, "groups")
+            if groups.shape != (R,):
+                raise ValueError(f"groups must be [{R}] (got {tuple(groups.shape)})")
+        with self._lock, torch.cuda.device(self.device):
+            offsets = torch.empty(R + 1, dtype=torch.int64, device=self.device)
+            self._check(self.lib.tvc_graph_pair_count(self.handle, _ptr(adj), R, _ptr(groups), _ptr(offsets), _stream()))
+            total = int(offsets[R].item())
+            if total > int(max_pairs):
+                raise ValueError(f"the graph holds {total} pairs, more than max_pairs = {int(max_pairs)}: raise the threshold "
+                                 f"or max_pairs (the list is never truncated)")
+            pairs = torch.empty((total, 2), dtype=torch.int32, device=self.device)
+            self._check(self.lib.tvc_graph_pair_fill(self.handle, _ptr(adj), R, _ptr(groups), _ptr(offsets), _ptr(pairs), total,
+                                                     _stream()))
+        return pairs, offsets
+
+    def pair_cosine(self, pairs: torch.Tensor, bank: str = DEFAULT_BANK) -> torch.Tensor:
+        """pairs int32 [P, 2] -> fp32 [P]: the cosine of the stored rows of every pair of ``bank`` (a bf16 slot: the stored
+        values; an fp32 slot: hi + lo), within ``cosine_bound(D)`` of fp64 on those rows, bit-identical between runs and for
+        (i, j) and (j, i).  0 for an all-zero row, NaN for a NaN row and for an index outside [0, R)."""
+        pairs = _require_cuda(pairs, torch.int32, "pairs")
+        if pairs.dim() != 2 or pairs.shape[1] != 2:
+            raise ValueError(f"pairs must be [P, 2] (got {tuple(pairs.shape)})")
+        P = pairs.shape[0]
+        with self._lock, torch.cuda.device(self.device):
+            self._select(bank)
+            sims = torch.empty(P, dtype=torch.float32, device=self.device)
+            self._check(self.lib.tvc_pair_cosine(self.handle, _ptr(pairs), P, _ptr(sims), _stream()))
+        return sims
+
+    @staticmethod
+    def cosine_bound(D: int) -> float:
+        """B(D) = 2^-24 (2 D + 16): the bound on ``|pair_cosine - cos64(stored rows)|`` for any summation order of the D fp32
+        FMA terms of the dot product and of the two norms, plus the sqrt, the multiply and the divide."""
+        return 2.0 ** -24 * (2 * D + 16)
+
+    @classmethod
+    def similar_margin(cls, D: int, t: float, bf16: bool) -> float:
+        """m: ``similar_pairs`` asks the radius graph for ``eps^2 = 2 - 2 t + m`` (the one place m is
+        computed).  Stored rows of norm ``1 + d``, ``|d| <= nu``, with cosine ``c >= t - B(D)`` lie at
+        ``|x - y|^2 = (|x| - |y|)^2 + 2 |x| |y| (1 - c) <= 4 nu^2 + 2 (1 + nu)^2 (1 - t + B)``; adding 4.13's tau for such rows
+        and 2^-19 for the fp32 rounding of eps and of its square makes every such pair a DECIDED in-graph pair.
+        nu = 2^-24 (D + 8) for the fp32 normalisation, plus 2^-16 for the hi | lo planes of an fp32 slot or 2^-9 for the
+        rounding of the elements to a bf16 slot."""
+        nu = 2.0 ** -24 * (D + 8) + (2.0 ** -9 if bf16 else 2.0 ** -16)
+        eps2 = 4 * nu * nu + 2 * (1 + nu) ** 2 * (1 - t + cls.cosine_bound(D)) + cls.SIMILAR_TAU + 2.0 ** -19
+        return eps2 - (2 - 2 * t)
+
+    def similar_pairs(self, t: float, bank: str = DEFAULT_BANK, groups: Optional[torch.Tensor] = None, max_pairs: int = 1 << 27):
+        """The pairs ``i < j`` of a slot of UNIT rows with cosine ``>= float32(t)`` -> (pairs int32 [P, 2], sims fp32 [P]) in
+        lexicographic (i, j) order: ``radius_graph`` at the widened radius ``eps^2 = 2 - 2 t + similar_margin(D, t, bf16)``,
+        ``graph_pairs`` (``groups``: only pairs of two different groups ``>= 0``), ``pair_cosine``, and the filter
+        ``sims >= float32(t)`` -- the fp32-grade cosine decides a pair, the graph only nominates it: a pair differs from
+        fp64 on the stored rows only inside ``|cos64 - t| <= cosine_bound(D)``.  ``t > 1`` gives empty lists without a
+        launch; a non-finite ``t`` raises; more than ``max_pairs`` nominated pairs raise ``ValueError``."""
+        import math
+        t = float(t)
+        if not math.isfinite(t):
+            raise ValueError(f"t must be finite (got {t})")
+        if t > 1.0:
+            return (torch.empty((0, 2), dtype=torch.int32, device=self.device), torch.empty(0, dtype=torch.float32, device=self.device))
+        b = self._slot(bank)
+        eps2 = 2 - 2 * t + self.similar_margin(b["dim"], t, bool(b.get("bf16")))
+        adj, _ = self.radius_graph(math.sqrt(eps2), bank=bank)
+        pairs, _ = self.graph_pairs(adj, groups=groups, max_pairs=max_pairs)
+        del adj
+        sims = self.pair_cosine(pairs, bank=bank)
+        keep = sims >= torch.tensor(t, dtype=torch.float32, device=self.device)
+        return pairs[keep], sims[keep]
+
     # ---- IVF search over a bank slot in list order -------------------------
     def ivf_probe(self, rows: torch.Tensor, centroids: torch.Tensor, nprobe: int):
         """rows fp32 [M, D], centroids fp32 [nlist, D] -> (lists int32 [M, nprobe], score fp32 [M, nprobe]): the nprobe
