@@ -463,6 +463,72 @@ int tvc_graph_pair_fill(tvc_handle* h, const uint32_t* adj_dev, int32_t R, const
  * and launches nothing. */
 int tvc_pair_cosine(tvc_handle* h, const int32_t* pairs_dev, int64_t P, float* sim_dev, void* stream);
 
+/* ---- retrieval evaluation over a bank slot: the rank of every relevant row ------------------------------------ */
+
+/* Recall@K, Precision@K, mAP, MRR and NDCG@K (src/utils/metrics.py:379-573) are pure functions of the POSITIONS of a query's
+ * relevant rows in its ranking of the gallery.  The reference takes them from a dense [Q, N] similarity matrix, a dense
+ * [Q, N] relevance matrix, an argsort of every row and Python loops over every query and rank; these calls take them from
+ * counts, over the rows of the selected bank slot (the gallery: bf16 in place or fp32 as (hi | lo) planes), and never
+ * hold a [Q, N] matrix.
+ *   score      S[i, j] = q_i . x_j in tvc_kmeans_assign's arithmetic: the queries split into (hi | lo) bf16 planes, two
+ *              products on a bf16 slot, three (hi.hi + hi.lo + lo.hi) on an fp32 slot.  The caller normalises when cosines
+ *              are wanted, as for tvc_bank_search.
+ *   relevance  (i, j) is relevant iff qlabel[i] == glabel[j] >= 0.  A negative glabel is a distractor, relevant to nobody; a
+ *              negative qlabel, or a label no row carries, is a query with no relevant row.  A relevant row of a query is
+ *              one of its TARGETS; T is the total over the queries.
+ *   order      (score descending, row index ascending): np.argsort(-S, kind = "stable"), tvc_bank_search's rule.
+ *   position   of a target t of query i, 0-based:
+ *                  pos(t) = (targets of i ahead of t) + (irrelevant rows j with (S[i, j], j) ahead of (S[i, t], t)).
+ *              A NaN score is ahead of nothing.
+ * Three calls.  tvc_rank_targets emits every query's targets; the caller puts each query's list in rank order (two stable
+ * sorts); tvc_rank_count counts, per target, the irrelevant rows whose first target behind them it is; tvc_rank_metrics
+ * turns the counts into positions and per-query metric terms.  The means over the queries are the caller's.
+ * All three return TVC_E_STATE when the selected slot holds no bank rows, and TVC_E_INVALID for M < 1, T < 0 or a NULL
+ * required buffer (tvc_rank_metrics also: more than TVC_RANK_MAX_K values of k, or a k < 1); nothing is launched then.
+ * T == 0 is legal: the two tile calls launch nothing, tvc_rank_metrics writes its per-query zeros. */
+#define TVC_RANK_MAX_K 8
+
+/* EMIT: one pass over the [M, R] score tiles; every relevant element writes its score and row.
+ *   rows_dev     fp32 [M, D], D = the slot's
+ *   qlabel_dev   int32 [M]
+ *   glabel_dev   int32 [R]
+ *   gpos_dev     int32 [R]: the place of row j among the rows of its label, in ascending row order (unused where
+ *                glabel[j] < 0)
+ *   tgt_off_dev  int64 [M + 1]: the exclusive scan over the queries of their target counts; tgt_off[M] = T
+ *   tgt_sim_dev  fp32 [T], tgt_row_dev int32 [T]: target (i, j) goes to slot tgt_off[i] + gpos[j], so a query's list is in
+ *                ascending row order and every slot is written exactly once: no atomics, bit-identical between runs.  A
+ *                slot outside the query's list (a gpos that is not the group's) is never written. */
+int tvc_rank_targets(tvc_handle* h, const float* rows_dev, int32_t M, const int32_t* qlabel_dev, const int32_t* glabel_dev,
+                     const int32_t* gpos_dev, const int64_t* tgt_off_dev, int64_t T, float* tgt_sim_dev, int32_t* tgt_row_dev,
+                     void* stream);
+
+/* COUNT: the same pass with the lists back, every query's in rank order (score descending, row ascending; finite scores).
+ *   tgt_sim_dev, tgt_row_dev   [T], sorted
+ *   hist_dev     int32 [T], zeroed by the caller: hist[tgt_off[i] + b] += 1 for every irrelevant row of query i that is
+ *                ahead of the query's b-th target and of none before it (integer atomics: the result does not depend on the
+ *                scheduling).  Relevant rows never count: the mutual order of a query's targets is the list's.
+ * An irrelevant element is first compared with the score of the query's last target; only those at or above it search
+ * the list (a binary search) and add.  Cost: one tile pass, plus one search and one atomic per irrelevant element that
+ * is not below every target of its query -- at worst M * R of them. */
+int tvc_rank_count(tvc_handle* h, const float* rows_dev, int32_t M, const int32_t* qlabel_dev, const int32_t* glabel_dev,
+                   const int64_t* tgt_off_dev, const float* tgt_sim_dev, const int32_t* tgt_row_dev, int64_t T,
+                   int32_t* hist_dev, void* stream);
+
+/* Metrics: per query, with P its target count and pos[c] = c + sum_{b <= c} hist[b] the position of its c-th target in
+ * rank order, in fp64:
+ *   pos_dev    int32 [T]
+ *   ap_dev     fp64 [M]: mean over c of (c + 1) / (pos[c] + 1)
+ *   rr_dev     fp64 [M]: 1 / (pos[0] + 1)
+ *   k_values   HOST int32 [n_k], n_k <= TVC_RANK_MAX_K, each >= 1
+ *   hits_dev   int32 [M, n_k]: the number of targets with pos < k
+ *   dcg_dev    fp64 [M, n_k]: sum over those targets of 1 / log2(pos + 2)
+ *   idcg_dev   fp64 [M, n_k]: sum over c < min(k, P) of 1 / log2(c + 2)
+ * A query without targets gets zeros (src/utils/metrics.py:469-470,511-512,558).  Any P from 0 to R works.  Nothing is
+ * reduced over the queries on the device.  Reads no bank row. */
+int tvc_rank_metrics(tvc_handle* h, int32_t M, const int64_t* tgt_off_dev, const int32_t* hist_dev, int64_t T,
+                     const int32_t* k_values, int32_t n_k, int32_t* pos_dev, double* ap_dev, double* rr_dev,
+                     int32_t* hits_dev, double* dcg_dev, double* idcg_dev, void* stream);
+
 /* ---- IVF search: probe + list scan over a bank slot ------------------------------------------------ */
 
 /* An IVF index over R rows is four things:

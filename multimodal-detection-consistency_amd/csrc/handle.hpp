@@ -4,7 +4,7 @@
 // split-bf16 towers' stem, layer loop, head and weight planes; tvc_sd.cpp: latent-diffusion reference generator,
 // tvc_sd_op.cpp: its entry points that read no model state; tvc_kmeans.cpp: k-means over a bank slot;
 // tvc_ivf.cpp: IVF probe and list scan; tvc_grad_split.cpp: the split-bf16 input gradient; tvc_dbscan.cpp: radius graph and
-// DBSCAN labels; tvc_pairs.cpp: pair lists of a bitmask graph and the cosine of listed pairs).
+// DBSCAN labels; tvc_pairs.cpp: pair lists of a bitmask graph and the cosine of listed pairs; tvc_rank.cpp: retrieval evaluation).
 #pragma once
 #include "../../include/tvc.h"
 #include "kernels.hpp"
@@ -47,6 +47,8 @@ enum Slot {
     WS_GS_KEEP, WS_GS_GP, WS_GS_MP, WS_GS_WIDE, WS_GS_ROW, WS_GS_SMALL,
     // radius graph over a bank slot (tvc_dbscan.cpp): the rows' squared norms and the padded half-norm vector of the distance test
     WS_DB_NORM2, WS_DB_HALF,
+    // retrieval evaluation (tvc_rank.cpp): the query planes, the query labels and the last-target scores padded to whole tiles
+    WS_RK_QPLANES, WS_RK_QLAB, WS_RK_TLOW,
     WS_COUNT
 };
 

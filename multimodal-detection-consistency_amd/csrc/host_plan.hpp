@@ -72,6 +72,32 @@ inline void kmeans_update_plan(int64_t R, int K, int* nblocks, int* rows_per_blo
     *nblocks = (int)((R + *rows_per_block - 1) / *rows_per_block > 0 ? (R + *rows_per_block - 1) / *rows_per_block : 1);
 }
 
+// Retrieval evaluation (rank.hip): the tile kernels read the query labels and the last-target scores as whole 16-byte pieces, so
+// both vectors are padded to whole query tiles; the metrics kernel takes at most RANK_MAX_K values of k (include/tvc.h's
+// TVC_RANK_MAX_K).  ok = false: M < 1, or more than RANK_MAX_K values, or a k < 1.
+#define RANK_MAX_K 8
+struct RankPlan {
+    bool ok = false;
+    int n_qtiles = 0;                   // 256-query tiles
+    int64_t mpad = 0;                   // entries of the padded per-query vectors
+    double flops = 0;                   // of one tile pass over R rows of D columns with `products` plane products
+};
+inline RankPlan rank_plan(int64_t M, int64_t R, int D, int products) {
+    RankPlan p;
+    if (M < 1 || M > 0x7fffffffLL - HOST_PLAN_GEMM_BM) return p;
+    p.n_qtiles = (int)((M + HOST_PLAN_GEMM_BM - 1) / HOST_PLAN_GEMM_BM);
+    p.mpad = (int64_t)p.n_qtiles * HOST_PLAN_GEMM_BM;
+    p.flops = 2.0 * (double)R * (double)M * D * products;
+    p.ok = true;
+    return p;
+}
+inline bool rank_k_values_ok(const int32_t* k, int n_k) {
+    if (n_k < 0 || n_k > RANK_MAX_K || (n_k > 0 && !k)) return false;
+    for (int t = 0; t < n_k; ++t)
+        if (k[t] < 1) return false;
+    return true;
+}
+
 // Radius graph / DBSCAN (dbscan.hip): the graph of R rows is a bitmask uint32 [R, words], words = round_up(R, 64) / 32 (an even
 // count: a wave of the tile kernel stores one 64-bit word per row).  The tile kernel's grid is tiles x tiles 256 x 256 tiles of
 // which the upper triangle computes; the half-norm vector is padded to whole tiles (hpad floats, NaN beyond R).  The

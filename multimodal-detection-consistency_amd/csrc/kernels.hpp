@@ -190,6 +190,37 @@ hipError_t launch_label_sort(const LabelSortLaunch& L, hipStream_t stream);
 // out[r] = |x_r|^2 of every stored row of the slot (hi + lo of an fp32 bank), fp32 [R]
 hipError_t launch_kmeans_rownorm(const BankRows& bank, float* out, hipStream_t stream);
 
+// ---- rank.hip: retrieval evaluation over a bank slot (the rank of every relevant row of every query; metrics from the ranks)
+struct RankTileLaunch {
+    BankRows bank;
+    const uint16_t* qplanes = nullptr;// [M, 2 * D] bf16 (hi | lo) query planes
+    int M = 0;
+    const int32_t* qlabel = nullptr;  // [M]
+    const int32_t* glabel = nullptr;  // [R]
+    const int32_t* gpos = nullptr;    // [R]: the row's place inside its label group, ascending row order (targets)
+    const int64_t* tgt_off = nullptr; // [M + 1]: exclusive scan of the queries' target counts
+    float* tgt_sim = nullptr;         // [T]: targets writes it; count reads it, every query's list in rank order
+    int32_t* tgt_row = nullptr;       // [T]: as tgt_sim
+    int32_t* hist = nullptr;          // [T] (count): += the irrelevant rows whose first target behind them is this one
+    int32_t* qlab = nullptr;          // workspace [rank_plan().mpad]
+    float* tlow = nullptr;            // workspace [rank_plan().mpad] (count)
+};
+hipError_t launch_rank_targets(const RankTileLaunch& L, hipStream_t stream);
+hipError_t launch_rank_count(const RankTileLaunch& L, hipStream_t stream);
+struct RankMetricsLaunch {
+    int M = 0, n_k = 0;
+    int k[RANK_MAX_K] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int64_t* tgt_off = nullptr; // [M + 1]
+    const int32_t* hist = nullptr;    // [T]
+    int32_t* pos = nullptr;           // [T]
+    double* ap = nullptr;             // [M]
+    double* rr = nullptr;             // [M]
+    int32_t* hits = nullptr;          // [M, n_k]
+    double* dcg = nullptr;            // [M, n_k]
+    double* idcg = nullptr;           // [M, n_k]
+};
+hipError_t launch_rank_metrics(const RankMetricsLaunch& L, hipStream_t stream);
+
 // ---- dbscan.hip: the eps-graph of a bank slot as a bitmask, and DBSCAN's labels from such a graph (exact integer work)
 struct RadiusGraphLaunch {
     BankRows bank;

@@ -58,6 +58,30 @@ class IVFIndex:
     dim: int
 
 
+@dataclass
+class RetrievalRanks:
+    """What ``TVCEngine.retrieval_ranks`` returns.  Query i's relevant rows (its targets) are the entries
+    ``tgt_off[i]:tgt_off[i + 1]`` of ``tgt_row`` / ``tgt_sim`` / ``pos``, best first; ``pos`` is the 0-based position of the
+    target in the query's ranking of the whole slot.  The per-query arrays follow ``tvc_rank_metrics`` (include/tvc.h); a
+    query without targets has zeros."""
+    k_values: Tuple[int, ...]
+    tgt_off: torch.Tensor        # int64 [M + 1]
+    tgt_row: torch.Tensor        # int32 [T]
+    tgt_sim: torch.Tensor        # fp32 [T]
+    pos: torch.Tensor            # int32 [T]
+    hist: torch.Tensor           # int32 [T]: the irrelevant rows between the target before this one and this one
+    ap: torch.Tensor             # fp64 [M]
+    rr: torch.Tensor             # fp64 [M]
+    hits: torch.Tensor           # int32 [M, len(k_values)]
+    dcg: torch.Tensor            # fp64 [M, len(k_values)]
+    idcg: torch.Tensor           # fp64 [M, len(k_values)]
+
+    @property
+    def n_targets(self) -> torch.Tensor:
+        """int64 [M]: the number of relevant rows of every query."""
+        return self.tgt_off[1:] - self.tgt_off[:-1]
+
+
 def _stream() -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -697,6 +721,134 @@ class TVCEngine:
         self.kmeans_last_init = C0
         _, _, offsets, order = self.kmeans_update(labels, Cc, bank=bank, want_lists=True)
         return Cc, labels, inertia, n_iter, order, offsets
+
+    # ---- retrieval evaluation over a bank slot -----------------------------
+    RANK_MAX_K = 8
+
+    def _rank_inputs(self, b: Dict, rows, qlabel, glabel, tgt_off):
+        rows = _require_cuda(rows, torch.float32, "rows")
+        if rows.dim() != 2 or rows.shape[1] != b["dim"]:
+            raise ValueError(f"rows must be [M, {b['dim']}] (got {tuple(rows.shape)})")
+        M = rows.shape[0]
+        qlabel = _require_cuda(qlabel, torch.int32, "qlabel")
+        glabel = _require_cuda(glabel, torch.int32, "glabel")
+        tgt_off = _require_cuda(tgt_off, torch.int64, "tgt_off")
+        if qlabel.shape != (M,) or glabel.shape != (b["rows"],) or tgt_off.shape != (M + 1,):
+            raise ValueError(f"need qlabel [{M}], glabel [{b['rows']}] and tgt_off [{M + 1}] (got {tuple(qlabel.shape)}, "
+                             f"{tuple(glabel.shape)}, {tuple(tgt_off.shape)})")
+        return rows, M, qlabel, glabel, tgt_off
+
+    def rank_targets(self, rows: torch.Tensor, qlabel: torch.Tensor, glabel: torch.Tensor, gpos: torch.Tensor,
+                     tgt_off: torch.Tensor, T: int, bank: str = DEFAULT_BANK):
+        """``tvc_rank_targets``: rows fp32 [M, D], qlabel int32 [M], glabel / gpos int32 [R], tgt_off int64 [M + 1], T =
+        ``tgt_off[M]`` -> (tgt_sim fp32 [T], tgt_row int32 [T]), every query's relevant rows in ascending row order."""
+        with self._lock, torch.cuda.device(self.device):
+            b = self._select(bank)
+            rows, M, qlabel, glabel, tgt_off = self._rank_inputs(b, rows, qlabel, glabel, tgt_off)
+            gpos = _require_cuda(gpos, torch.int32, "gpos")
+            if gpos.shape != glabel.shape:
+                raise ValueError(f"gpos must be [{b['rows']}] (got {tuple(gpos.shape)})")
+            tgt_sim = torch.empty(T, dtype=torch.float32, device=self.device)
+            tgt_row = torch.empty(T, dtype=torch.int32, device=self.device)
+            self._check(self.lib.tvc_rank_targets(self.handle, _ptr(rows), M, _ptr(qlabel), _ptr(glabel), _ptr(gpos), _ptr(tgt_off),
+                                                  T, _ptr(tgt_sim), _ptr(tgt_row), _stream()))
+        return tgt_sim, tgt_row
+
+    def rank_count(self, rows: torch.Tensor, qlabel: torch.Tensor, glabel: torch.Tensor, tgt_off: torch.Tensor,
+                   tgt_sim: torch.Tensor, tgt_row: torch.Tensor, bank: str = DEFAULT_BANK) -> torch.Tensor:
+        """``tvc_rank_count``: the lists of ``rank_targets`` with every query's in rank order -> hist int32 [T]."""
+        with self._lock, torch.cuda.device(self.device):
+            b = self._select(bank)
+            rows, M, qlabel, glabel, tgt_off = self._rank_inputs(b, rows, qlabel, glabel, tgt_off)
+            tgt_sim = _require_cuda(tgt_sim, torch.float32, "tgt_sim")
+            tgt_row = _require_cuda(tgt_row, torch.int32, "tgt_row")
+            T = tgt_sim.numel()
+            if tgt_sim.dim() != 1 or tgt_row.shape != tgt_sim.shape:
+                raise ValueError(f"tgt_sim and tgt_row must be [T] (got {tuple(tgt_sim.shape)}, {tuple(tgt_row.shape)})")
+            hist = torch.zeros(T, dtype=torch.int32, device=self.device)
+            self._check(self.lib.tvc_rank_count(self.handle, _ptr(rows), M, _ptr(qlabel), _ptr(glabel), _ptr(tgt_off), _ptr(tgt_sim),
+                                                _ptr(tgt_row), T, _ptr(hist), _stream()))
+        return hist
+
+    def rank_metrics(self, tgt_off: torch.Tensor, hist: torch.Tensor, k_values=(1, 5, 10), bank: str = DEFAULT_BANK):
+        """``tvc_rank_metrics``: tgt_off int64 [M + 1], hist int32 [T] -> (pos int32 [T], ap fp64 [M], rr fp64 [M], hits int32
+        [M, n_k], dcg fp64 [M, n_k], idcg fp64 [M, n_k])."""
+        tgt_off = _require_cuda(tgt_off, torch.int64, "tgt_off")
+        hist = _require_cuda(hist, torch.int32, "hist")
+        ks = [int(k) for k in k_values]
+        M, T, n_k = tgt_off.numel() - 1, hist.numel(), len(ks)
+        karr = (C.c_int32 * max(n_k, 1))(*ks)
+        with self._lock, torch.cuda.device(self.device):
+            self._select(bank)
+            pos = torch.empty(T, dtype=torch.int32, device=self.device)
+            ap = torch.empty(max(M, 0), dtype=torch.float64, device=self.device)
+            rr = torch.empty_like(ap)
+            hits = torch.empty((max(M, 0), n_k), dtype=torch.int32, device=self.device)
+            dcg = torch.empty((max(M, 0), n_k), dtype=torch.float64, device=self.device)
+            idcg = torch.empty_like(dcg)
+            self._check(self.lib.tvc_rank_metrics(self.handle, M, _ptr(tgt_off), _ptr(hist), T, karr, n_k, _ptr(pos), _ptr(ap),
+                                                  _ptr(rr), _ptr(hits), _ptr(dcg), _ptr(idcg), _stream()))
+        return pos, ap, rr, hits, dcg, idcg
+
+    def rank_layout(self, qlabels: torch.Tensor, glabels: torch.Tensor):
+        """Labels of any integer type -> (qlabel int32 [M], glabel int32 [R], gpos int32 [R], tgt_off int64 [M + 1]) for the rank
+        calls: the non-negative gallery labels renumbered 0 .. G - 1 (negative ones stay -1), a query label no gallery row
+        carries becomes -1, ``gpos[j]`` = the place of row j among the rows of its label in ascending row order, ``tgt_off``
+        = the exclusive scan of the queries' group sizes.  Integer torch ops on the engine's device."""
+        ql = torch.as_tensor(qlabels).to(self.device).long().reshape(-1)
+        gl = torch.as_tensor(glabels).to(self.device).long().reshape(-1)
+        R = gl.numel()
+        valid = gl >= 0
+        uniq, inv = torch.unique(gl[valid], return_inverse=True)
+        G = uniq.numel()
+        gc = torch.full((R,), -1, dtype=torch.int64, device=self.device)
+        gc[valid] = inv
+        counts = torch.bincount(inv, minlength=max(G, 1))
+        # a stable sort by label puts every group in ascending row order behind the distractors
+        order = torch.sort(gc, stable=True).indices
+        start = torch.cumsum(counts, 0) - counts + (R - int(valid.sum()))
+        gpos = torch.zeros(R, dtype=torch.int64, device=self.device)
+        gpos[order] = torch.arange(R, device=self.device) - start[gc[order].clamp(min=0)]
+        gpos[~valid] = 0
+        if G:
+            at = torch.searchsorted(uniq, ql.clamp(min=0)).clamp(max=G - 1)
+            qc = torch.where((uniq[at] == ql) & (ql >= 0), at, torch.full_like(at, -1))
+        else:
+            qc = torch.full_like(ql, -1)
+        sizes = torch.where(qc >= 0, counts[qc.clamp(min=0)], torch.zeros_like(qc))
+        tgt_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), torch.cumsum(sizes, 0)])
+        return qc.int(), gc.int(), gpos.int(), tgt_off
+
+    def retrieval_ranks(self, rows: torch.Tensor, qlabels, glabels, bank: str = DEFAULT_BANK, k_values=(1, 5, 10)) -> RetrievalRanks:
+        """The position of every relevant row of every query in its ranking of the rows of ``bank``, and the per-query metric
+        terms (``RetrievalRanks``).  rows fp32 [M, D]; (i, j) is relevant iff ``qlabels[i] == glabels[j] >= 0``; the order is
+        (score descending, row ascending), ``tvc_bank_search``'s.  Two tile passes over the slot (``tvc_rank_targets``,
+        ``tvc_rank_count``) with two stable sorts of the T targets between them; no [M, R] matrix exists.  Synchronises (it
+        reads T, and checks the target scores): an evaluation call.  ``ValueError`` for a non-finite target score."""
+        ks = tuple(int(k) for k in k_values)
+        if len(ks) > self.RANK_MAX_K or any(k < 1 for k in ks):
+            raise ValueError(f"need at most {self.RANK_MAX_K} values of k, each >= 1 (got {ks})")
+        rows = _require_cuda(rows, torch.float32, "rows")
+        if rows.dim() != 2 or rows.shape[0] < 1:
+            raise ValueError(f"rows must be [M >= 1, D] (got {tuple(rows.shape)})")
+        M = rows.shape[0]
+        with torch.cuda.device(self.device):
+            qlabel, glabel, gpos, tgt_off = self.rank_layout(qlabels, glabels)
+            if qlabel.numel() != M or glabel.numel() != self.bank_size(bank):
+                raise ValueError(f"need {M} query labels and {self.bank_size(bank)} gallery labels "
+                                 f"(got {qlabel.numel()}, {glabel.numel()})")
+            T = int(tgt_off[-1])
+            tgt_sim, tgt_row = self.rank_targets(rows, qlabel, glabel, gpos, tgt_off, T, bank=bank)
+            if not bool(torch.isfinite(tgt_sim).all()):
+                raise ValueError("retrieval_ranks: a relevant row has a non-finite score")
+            # rank order inside every query: by score over the row-ascending lists, then by query, both stable
+            qid = torch.repeat_interleave(torch.arange(M, device=self.device), tgt_off[1:] - tgt_off[:-1])
+            by_score = torch.sort(tgt_sim, descending=True, stable=True).indices
+            perm = by_score[torch.sort(qid[by_score], stable=True).indices]
+            tgt_sim, tgt_row = tgt_sim[perm].contiguous(), tgt_row[perm].contiguous()
+            hist = self.rank_count(rows, qlabel, glabel, tgt_off, tgt_sim, tgt_row, bank=bank)
+            pos, ap, rr, hits, dcg, idcg = self.rank_metrics(tgt_off, hist, ks, bank=bank)
+        return RetrievalRanks(ks, tgt_off, tgt_row, tgt_sim, pos, hist, ap, rr, hits, dcg, idcg)
 
     # ---- radius graph of a bank slot, DBSCAN on a radius graph -------------
     DBSCAN_SWEEP_BATCH = 4

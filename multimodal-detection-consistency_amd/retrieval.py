@@ -182,6 +182,26 @@ class MultiModalRetriever:
         """Name used by the efficiency harness (experiments/run_experiments.py:3143)."""
         return self.retrieve_images_by_text(text, top_k=k)
 
+    def rank_queries(self, query_rows: torch.Tensor, query_labels, gallery_labels, k_values: Sequence[int] = (1, 5, 10)):
+        """``TVCEngine.retrieval_ranks`` of already encoded query rows [M, D] over this retriever's own index slot, in place
+        (no copy of the index): gallery row j (``gallery_labels[j]``, in the order the index was built from) is relevant to
+        query i iff the labels are equal and non-negative.  An IVF index is ranked exhaustively over its stored rows; its
+        ``tgt_row`` are stored positions (``index.ids`` maps them back), and exact ties follow the stored order."""
+        if self._bank_is is None:
+            raise ValueError("index not built")
+        eng = self.clip_model.engine
+        gl = torch.as_tensor(gallery_labels).to(eng.device)
+        if self._ivf is not None:
+            gl = gl[self._ivf.ids.long()]
+        q = torch.as_tensor(query_rows, dtype=torch.float32).to(eng.device).contiguous()
+        return eng.retrieval_ranks(q, query_labels, gl, bank=self.bank_name, k_values=tuple(k_values))
+
+    def evaluate_retrieval(self, query_rows: torch.Tensor, query_labels, gallery_labels, k_values: Sequence[int] = (1, 5, 10)):
+        """-> ``RetrievalMetrics`` (Recall@K, Precision@K, mAP, NDCG@K, MRR) of the queries over the registered index: the
+        "Top-k" column of the reference's tables (src/utils/metrics.py:379-573) without a similarity matrix."""
+        from .metrics import RetrievalEvaluator
+        return RetrievalEvaluator.from_ranks(self.rank_queries(query_rows, query_labels, gallery_labels, k_values))
+
     def compute_similarity_matrix(self, text_features: Optional[np.ndarray] = None,
                                   image_features: Optional[np.ndarray] = None) -> np.ndarray:
         """src/retrieval.py:682-722: [N_text, N_image] cosine (HIP split-bf16 GEMM);
