@@ -867,7 +867,9 @@ int tvc_sd_generate(tvc_handle* h, const float* cond_dev, const float* uncond_de
  * VAE AttentionBlock, 3 = 3x3 conv (stride 1), 4 = stride-2 downsample conv, 5 = nearest-2x upsample + conv;
  * `prefix` = the block's state-dict prefix with the trailing dot (conv kinds: up to and including "conv." / "conv_in.").
  * x [n, Cin, H, W]; temb fp32 [n, time_dim] (resnets of the UNet; NULL for the VAE's); ctx as tvc_sd_unet (kind 1);
- * out [n, Cout, H', W'].  vae != 0 uses the VAE's eps (1e-6). */
+ * out [n, Cout, H', W'] with H', W' = H, W; kind 4: (H + 1) / 2, (W + 1) / 2 (stride 2, padding 1: odd sizes round up);
+ * kind 5: 2H, 2W.  vae != 0 uses the VAE's eps (1e-6).  Cin must be a multiple of 64 (every GEMM behind a block reads
+ * whole 64-column K-tiles): any other Cin is TVC_E_INVALID for every kind, and nothing is launched. */
 int tvc_sd_block(tvc_handle* h, int32_t kind, const char* prefix, const float* x_dev, int32_t n, int32_t Cin, int32_t H,
                  int32_t W, const float* temb_dev, const float* ctx_dev, int32_t Cout, int32_t vae, float* out_dev, void* stream);
 

@@ -315,6 +315,34 @@ inline GemmPlan gemm_form(const GemmFormArgs& a, const GemmFormEnv& env) {
     return p;
 }
 
+// ---- K split of a latent-diffusion GEMM (tvc_sd.cpp: Run::fixed_split -> GemmLaunch::splitk_fixed; here so that
+// tests/gemm_form/driver.cpp evaluates the same arithmetic on the host), chosen
+// from the PER-SAMPLE shape only (never from the launch size): every sample's arithmetic is then the same whatever batch it is generated in, so an image is bit-for-bit independent of its batch mates and of the
+// chunking of tvc_sd_generate (the reference's seed policy, src/sd_ref.py:389-412, promises reproducible references).
+// Nominal batch: 24 samples (12 images x classifier-free guidance, the batch bench.py generates) -- K is split only
+// where even that batch leaves most CUs without a tile (the 8 x 8 level, the time / text projections).  A split that
+// filled the chip for a single image (S = 4 .. 16 at the 16 x 16 level) cost the 12-image batch 20 % of its GEMM time
+// (r04_bench1: 602 against 497 ms) -- throughput of the batched generator is what configs[4] measures; one image alone
+// runs its low-resolution levels on fewer workgroups than CUs.
+#ifndef TVC_SD_NOMINAL
+#define TVC_SD_NOMINAL 24
+#endif
+inline int sd_fixed_split(int I, int K, int planes, int64_t rows_per_sample, int nominal_samples = TVC_SD_NOMINAL) {
+    const int64_t tiles0 = (int64_t)((I + 255) / 256) * ((nominal_samples * rows_per_sample + 255) / 256);
+    const int nk64 = (int)((int64_t)K * planes / 64);
+    int64_t S = tiles0 > 0 ? 256 / tiles0 : 1;
+    if (S > nk64 / 4) S = nk64 / 4;
+    if (S > 16) S = 16;
+    // the split kernels run the one-tile loop at about half the ring kernel's rate: a two-way split of a shallow K
+    // (the 16 x 16 level's linear layers: 120 tiles x 20 K-tiles) loses to 120 ring workgroups (measured 418 against
+    // ~550 TFLOP/s); it pays from three ways on, or on a deep K (>= 32 K-tiles per slice)
+    if (S == 2 && nk64 / 2 < 32) S = 1;
+    // slices of equal depth (S divides the K-tile count) run in the ring kernel (gemm.hip, gemm_ring4_split_kernel)
+    while (S > 2 && nk64 % S != 0) --S;
+    if (S == 2 && (nk64 % 2 != 0 || nk64 / 2 < 32)) S = 1;
+    return S >= 2 ? (int)S : 1;
+}
+
 // GEMM operand rows: readable to the next multiple of 256 plus one tile (gemm.hip's ring forms stage whole tiles and prefetch one)
 inline int64_t tile_rows(int64_t r) { return (r + 255) / 256 * 256 + 256; }
 

@@ -101,33 +101,8 @@ struct Run {
         return p;
     }
     bool keep_fill() const { return keep != 2; }      // these tensors are computed in this evaluation
-    // K split of a GEMM, chosen from the PER-SAMPLE shape only (never from the launch size): every sample's arithmetic is
-    // then the same whatever batch it is generated in, so an image is bit-for-bit independent of its batch mates and of the
-    // chunking of tvc_sd_generate (the reference's seed policy, src/sd_ref.py:389-412, promises reproducible references).
-    // Nominal batch: 24 samples (12 images x classifier-free guidance, the batch bench.py generates) -- K is split only
-    // where even that batch leaves most CUs without a tile (the 8 x 8 level, the time / text projections).  A split that
-    // filled the chip for a single image (S = 4 .. 16 at the 16 x 16 level) cost the 12-image batch 20 % of its GEMM time
-    // (r04_bench1: 602 against 497 ms) -- throughput of the batched generator is what configs[4] measures; one image alone
-    // runs its low-resolution levels on fewer workgroups than CUs.
-#ifndef TVC_SD_NOMINAL
-#define TVC_SD_NOMINAL 24
-#endif
-    static constexpr int NOMINAL_SAMPLES = TVC_SD_NOMINAL;
-    static int fixed_split(int I, int K, int planes, int64_t rows_per_sample) {
-        const int64_t tiles0 = (int64_t)((I + 255) / 256) * ((NOMINAL_SAMPLES * rows_per_sample + 255) / 256);
-        const int nk64 = (int)((int64_t)K * planes / 64);
-        int64_t S = tiles0 > 0 ? 256 / tiles0 : 1;
-        if (S > nk64 / 4) S = nk64 / 4;
-        if (S > 16) S = 16;
-        // the split kernels run the one-tile loop at about half the ring kernel's rate: a two-way split of a shallow K
-        // (the 16 x 16 level's linear layers: 120 tiles x 20 K-tiles) loses to 120 ring workgroups (measured 418 against
-        // ~550 TFLOP/s); it pays from three ways on, or on a deep K (>= 32 K-tiles per slice)
-        if (S == 2 && nk64 / 2 < 32) S = 1;
-        // slices of equal depth (S divides the K-tile count) run in the ring kernel (gemm.hip, gemm_ring4_split_kernel)
-        while (S > 2 && nk64 % S != 0) --S;
-        if (S == 2 && (nk64 % 2 != 0 || nk64 / 2 < 32)) S = 1;
-        return S >= 2 ? (int)S : 1;
-    }
+    // K split of a GEMM: sd_fixed_split (host_plan.hpp), chosen from the PER-SAMPLE shape only, at the nominal batch TVC_SD_NOMINAL
+    static int fixed_split(int I, int K, int planes, int64_t rows_per_sample) { return sd_fixed_split(I, K, planes, rows_per_sample); }
     // launch with the fixed split; the fp32 partial tiles are scratch of the arena
     void launch_fixed(GemmLaunch& g, int64_t rows_per_sample, const char* what) {
         const int S = fixed_split(g.I, g.K, g.planes, rows_per_sample);
@@ -779,6 +754,9 @@ int tvc_sd_block(tvc_handle* h, int32_t kind, const char* prefix, const float* x
     if (rc) return rc;
     if (kind < 0 || kind > 5 || !prefix || !x_dev || !out_dev || n < 1 || Cin < 8 || Cin % 8 || Cout < 1 || H < 1 || W < 1)
         return fail(h, TVC_E_INVALID, "tvc_sd_block: bad arguments");
+    // every GEMM behind a block reads K-tiles of 64 columns per plane (GemmLaunch::K): a narrower or ragged Cin would run a
+    // plane of no K-tiles (kinds 3, 5, 0) or drop the columns beyond the last whole K-tile (kind 4)
+    if (Cin % 64) return fail(h, TVC_E_INVALID, "tvc_sd_block: Cin must be a multiple of 64");
     if (kind == 1 && !ctx_dev) return fail(h, TVC_E_INVALID, "tvc_sd_block: a transformer block needs ctx");
     SdState* S = h->sd;
     const tvc_sd_desc& d = S->d;

@@ -191,7 +191,7 @@ class SDKernels:
         e = self.engine
         x = x.to(e.device, torch.float32).contiguous()
         n, cin, H, W = x.shape
-        Ho, Wo = (H // 2, W // 2) if kind == 4 else ((2 * H, 2 * W) if kind == 5 else (H, W))
+        Ho, Wo = ((H + 1) // 2, (W + 1) // 2) if kind == 4 else ((2 * H, 2 * W) if kind == 5 else (H, W))
         out = torch.empty((n, cout, Ho, Wo), dtype=torch.float32, device=e.device)
         temb = None if temb is None else temb.to(e.device, torch.float32).contiguous()
         ctx = None if ctx is None else ctx.to(e.device, torch.float32).contiguous()

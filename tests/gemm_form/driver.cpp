@@ -2,7 +2,9 @@
 //   I J K planes lda ldb epilogue splitk_small splitk_fixed has_ws ws_bytes a_rows_padded b_rows_padded
 //   TVC_GEMM_VARIANT TVC_GEMM_RING_MIN_TILES TVC_GEMM_RING_FORM TVC_GEMM_SPLITK_TAIL TVC_GEMM_SPLITK_SMALL TVC_GEMM_RING_SPLIT
 // -- and prints the form csrc/host_plan.hpp's gemm_form gives it (the one launch_gemm_bf16 takes) and its K split.
-// With the arguments `bank_plan R M k` it prints bank_plan's cut of that search instead.
+// and, for a caller-fixed split, whether its slices run in the ring kernel (1) or in the partial and finish kernels (0).
+// With the arguments `bank_plan R M k` it prints bank_plan's cut of that search instead; with `fixed_split I K planes
+// rows_per_sample` the K split the latent-diffusion model fixes for that GEMM (csrc/host_plan.hpp's sd_fixed_split).
 #include "host_plan.hpp"
 
 #include <cstdio>
@@ -35,6 +37,10 @@ static int print_bank_plan(long long R, int M, int k) {
 
 int main(int argc, char** argv) {
     if (argc == 5 && !strcmp(argv[1], "bank_plan")) return print_bank_plan(atoll(argv[2]), atoi(argv[3]), atoi(argv[4]));
+    if (argc == 6 && !strcmp(argv[1], "fixed_split")) {
+        printf("%d\n", sd_fixed_split(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoll(argv[5])));
+        return 0;
+    }
     long long v[19];
     for (;;) {
         for (int i = 0; i < 19; ++i)
@@ -47,6 +53,6 @@ int main(int argc, char** argv) {
         e.variant = (int)v[13]; e.ring_min_tiles = (int)v[14]; e.ring_form = (int)v[15]; e.splitk_tail = v[16] != 0;
         e.splitk_small = v[17] != 0; e.ring_split = v[18] != 0;
         const GemmPlan p = gemm_form(a, e);
-        printf("%s %d\n", form_name(p.form), p.S);
+        printf("%s %d %d\n", form_name(p.form), p.S, (int)p.ring_split);
     }
 }

@@ -2,7 +2,9 @@
 dispatches on csrc/host_plan.hpp's gemm_form; tests/gemm_form/driver.cpp runs that function on the host, and every
 labelled shape of the GPU suite -- tests/test_gpu_gemm_contract.py's cases, scripts/gemm_form_check.py (ring form
 bit-identity), _FORM_LABELS of tests/test_gpu_fp16_mode.py and _SHORT_K_FORMS of tests/test_gpu_kernels.py -- is checked
-against it, so a test cannot claim a kernel it does not reach."""
+against it, so a test cannot claim a kernel it does not reach.  The convolution cases of tests/sd_conv_witness.py are
+checked with the K split the latent-diffusion model fixes for them (host_plan.hpp's sd_fixed_split): the form, the S and
+whether the slices run in the ring kernel, in the default process and under each switch a case is labelled for."""
 import importlib.util
 import subprocess
 from pathlib import Path
@@ -15,7 +17,8 @@ WS_BYTES = 256 * 256 * 256 * 4          # tvc_gemm_bf16 / tvc_gemm_f16's split-K
 # env key -> (TVC_GEMM_VARIANT, TVC_GEMM_RING_MIN_TILES, TVC_GEMM_RING_FORM, TVC_GEMM_SPLITK_TAIL, TVC_GEMM_SPLITK_SMALL,
 #             TVC_GEMM_RING_SPLIT); "" = none set
 ENV = {"": (-1, 8, 4, 0, 0, 1), "TVC_GEMM_RING_FORM=1": (-1, 8, 1, 0, 0, 1), "TVC_GEMM_VARIANT=0": (0, 8, 4, 0, 0, 1),
-       "TVC_GEMM_SPLITK_SMALL=1": (-1, 8, 4, 0, 1, 1), "TVC_GEMM_SPLITK_TAIL=1": (-1, 8, 4, 1, 0, 1)}
+       "TVC_GEMM_SPLITK_SMALL=1": (-1, 8, 4, 0, 1, 1), "TVC_GEMM_SPLITK_TAIL=1": (-1, 8, 4, 1, 0, 1),
+       "TVC_GEMM_RING_SPLIT=0": (-1, 8, 4, 0, 0, 0)}
 
 
 def _load(path, name):
@@ -35,17 +38,21 @@ def gemm_form(tmp_path_factory):
     b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     assert b.returncode == 0, b.stderr[-3000:]
 
-    def many(queries):
-        lines = []
-        for I, J, K, lda, ldb, epi, env_key in queries:
-            lines.append(" ".join(map(str, (I, J, K, 1, lda, ldb, epi, 0, 0, 1, WS_BYTES, 0, 0) + ENV[env_key])))
-        r = subprocess.run([str(exe)], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=120)
+    def raw(lines):
+        """one driver line (a tuple of its 19 numbers) per launch -> (form name, K split, slices in the ring kernel)"""
+        r = subprocess.run([str(exe)], input="\n".join(" ".join(map(str, ln)) for ln in lines) + "\n", capture_output=True,
+                           text=True, timeout=120)
         assert r.returncode == 0, r.stderr[-3000:]
         out = [ln.split() for ln in r.stdout.splitlines()]
-        assert len(out) == len(queries)
-        return [(f, int(s)) for f, s in out]
+        assert len(out) == len(lines)
+        return [(f, int(s), int(rs)) for f, s, rs in out]
+
+    def many(queries):
+        lines = [(I, J, K, 1, lda, ldb, epi, 0, 0, 1, WS_BYTES, 0, 0) + ENV[env_key] for I, J, K, lda, ldb, epi, env_key in queries]
+        return [(f, s) for f, s, _ in raw(lines)]
 
     many.exe = exe
+    many.raw = raw
     return many
 
 
@@ -120,3 +127,45 @@ def test_short_k_shapes_reach_their_labelled_forms(gemm_form):
     got = [f for f, _ in gemm_form([(I, J, K, K, K, epi, "") for I, J, K, epi in shapes])]
     assert got == [ns["_SHORT_K_FORMS"][s] for s in shapes]
     assert "ONE_TILE" in got and "RING4" in got and "RING1" in got
+
+
+def test_sd_conv_witness_cases_reach_their_labelled_forms(gemm_form):
+    """tests/test_gpu_sd_conv_witness.py: each convolution case launches the GEMM tvc_sd.cpp builds for it (nine K-planes over
+    the padded layout, or one plane over im2col rows; both operands padded to whole tiles; the 16-bit epilogue) with the
+    split sd_fixed_split gives its per-sample shape.  Form, S and ring_split must be what LABELS claims, in every process."""
+    wit = _load(ROOT / "tests" / "sd_conv_witness.py", "sd_conv_witness_labels")
+    assert set(wit.LABELS) == set(wit.CASES)
+    lines, want = [], []
+    for cid, c in wit.CASES.items():
+        g = wit.gemm_shape(*c)
+        r = subprocess.run([str(gemm_form.exe), "fixed_split", str(g["I"]), str(g["K"]), str(g["planes"]), str(g["rows_per_sample"])],
+                           capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0, r.stderr[-3000:]
+        S = int(r.stdout)
+        tiles = ((g["I"] + 255) // 256) * ((g["J"] + 255) // 256)
+        ws = tiles * S * 256 * 256 * 4 if S >= 2 else 0            # Run::launch_fixed: a workspace only for a real split
+        assert "" in wit.LABELS[cid] and set(wit.LABELS[cid]) <= set(wit.ENVS)
+        for env_key, label in wit.LABELS[cid].items():
+            lines.append((g["I"], g["J"], g["K"], g["planes"], g["lda"], g["ldb"], 1, 0, S, int(S >= 2), ws, 1, 1) + ENV[env_key])
+            want.append((cid, env_key, S, tuple(label)))
+    got = gemm_form.raw(lines)
+    bad = [(w, g) for w, g in zip(want, got) if w[3] != g or (w[3][1] or 1) != w[2]]
+    assert not bad, bad
+    # what the table promises: every fixed-split case in the ring-split kernel AND in the partial / finish kernels, the
+    # minimum slice depth, ring form 4 with a ragged last row tile and its form-1 twin, on stride-1, stride-2 and upsampled cases
+    lab = wit.LABELS
+    for cid in ("B", "C", "G", "I"):
+        assert lab[cid][""][0] == "SPLITK_FIXED" and lab[cid][""][2] == 1 and lab[cid]["TVC_GEMM_RING_SPLIT=0"][2] == 0
+    gC = wit.gemm_shape(*wit.CASES["C"])
+    assert gC["K"] * gC["planes"] // 64 // lab["C"][""][1] == 4 and gC["I"] % 256 != 0
+    for cid in ("D", "J"):
+        g = wit.gemm_shape(*wit.CASES[cid])
+        assert lab[cid][""][0] == "RING4" and lab[cid]["TVC_GEMM_RING_FORM=1"][0] == "RING1"
+        assert g["I"] % 256 != 0 and g["J"] % 256 != 0 and ((g["I"] + 255) // 256) * ((g["J"] + 255) // 256) == 10
+    assert {wit.CASES[c][0] for c in ("B", "C", "G", "I")} == {3, 4, 5} and {wit.CASES[c][0] for c in ("D", "J")} == {3, 5}
+    # the resnet blocks of the GPU file: conv1 / conv2 of the first run unsplit, conv1 of the second (Cin = 128) splits three ways
+    for (n, Cin, Cout, H, W), S in zip(wit.RESNET_SHAPES, (1, 3)):
+        g = wit.gemm_shape(3, n, Cin, Cout, H, W)
+        r = subprocess.run([str(gemm_form.exe), "fixed_split", str(g["I"]), str(g["K"]), "9", str(g["rows_per_sample"])],
+                           capture_output=True, text=True, timeout=60)
+        assert int(r.stdout) == S
