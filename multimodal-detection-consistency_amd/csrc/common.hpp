@@ -87,16 +87,49 @@ template <> struct Op16<true> {
     __device__ static __forceinline__ float hi(uint32_t w) { return f16x2_hi(w); }
 };
 
-// wave-level all-lane sum / max over 64 lanes
-__device__ __forceinline__ float wave_sum(float v) {
+// All-lane sum over groups of W lanes (float, int, double): an xor butterfly, distances W / 2 ... 1.  The distances are the
+// order of the floating-point additions, so they are part of every result's bits; every lane of a group ends with the same bits.
+template <int W, class T>
+__device__ __forceinline__ T lanes_sum(T v) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// wave-level all-lane sum / max / min over 64 lanes (distances 32 ... 1)
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) { return lanes_sum<64>(v); }
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
+}
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int u = __shfl_xor(v, o, 64);
+        v = u < v ? u : v;
+    }
+    return v;
+}
+// the inclusive prefix sum of v over the wave's lanes 0 .. lane (int, long long); lane 63 holds the wave's total
+template <class T>
+__device__ __forceinline__ T wave_inclusive_scan(T v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T u = __shfl_up(v, o, 64);
+        if (lane >= o) v += u;
+    }
+    return v;
+}
+
+// f(b) for every set bit b of x, in ascending order
+template <class F>
+__device__ __forceinline__ void for_each_set_bit(uint32_t x, F&& f) {
+    while (x) {
+        const int b = __ffs(x) - 1;
+        x &= x - 1;
+        f(b);
+    }
 }
 
 // (v desc, idx asc): the order of the bank search's candidates and of k-means' centres; false whenever v is NaN

@@ -1,13 +1,13 @@
 // DBSCAN over a registered bank slot (src/ref_bank.py:302-315), as two independent halves.
 //
 //   graph   `radius_tile_kernel`: the eps-graph A[i, j] = (|x_i - x_j|^2 <= eps^2) of the slot's rows as a bitmask uint32
-//           [R, words] -- a self-GEMM on the main loop of the k-means assign (A = B = the slot's rows, 256 x 256 tiles), the
-//           scores never leave the accumulators.  The test is  x_i.x_j >= h_i + h_j  with h = |x|^2 / 2 - eps^2 / 4 (fp32
+//           [R, words] -- a self-GEMM on gemm_core.hpp's main loop (slot_self_operands: A = B = the slot's rows, 256 x 256
+//           tiles), the scores never leave the accumulators.  The test is  x_i.x_j >= h_i + h_j  with h = |x|^2 / 2 - eps^2 / 4 (fp32
 //           addition commutes: the right side is the same number for (i, j) and (j, i)); h is NaN for a row whose norm is not
 //           finite and in the padding up to whole tiles, so such a row or column compares false everywhere.  A bf16 slot
 //           multiplies one plane (both operands are the stored values), an fp32 slot all four hi / lo products: a radius graph
 //           is asked about near-duplicate rows, where the lo.lo term is ~1e-6 |x|^2 of a squared distance near zero.
-//           In the accumulator layout the 16 lanes `lane & 15` hold 16 consecutive columns of one row: a __ballot per (m, n, r)
+//           In gemm_acc_t's layout the 16 lanes `lane & 15` hold 16 consecutive columns of one row: a __ballot per (m, n, r)
 //           is 4 rows x 16 columns, four of them one 64-bit word for each of the 4 rows, stored by lanes 0 .. 3.
 //           Only the tiles on and above the diagonal compute (the rest of adj is zeroed first); `radius_symmetrise_kernel`
 //           then ORs adj with its bit transpose, one pair of 32 x 32 bit blocks per half wave, so adj is symmetric bit for
@@ -45,31 +45,29 @@ __global__ __launch_bounds__(GEMM_THREADS) void radius_tile_kernel(GemmOperands 
     if (tj < ti) return;                                  // the symmetrise pass fills the lower triangle
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    const int wm = wave >> 2, wn = wave & 3;
     const int i0 = ti * GEMM_BM, j0 = tj * GEMM_BN;
     const bool diag = ti == tj;
     gemm_acc_t acc;
     gemm_zero_acc(acc);
     gemm_mainloop(acc, g, i0, j0, smem);
-    const int jc = j0 + wn * 64;                          // the wave's 64 columns: words jw, jw + 1 of a row
-    const int jw = jc >> 5;
+    const int jw = gemm_acc_col(j0, wave, 0, 0) >> 5;     // the wave's 64 columns: words jw, jw + 1 of a row
     float hj[4];
 #pragma unroll
-    for (int n = 0; n < 4; ++n) hj[n] = half[jc + n * 16 + (lane & 15)];
+    for (int n = 0; n < 4; ++n) hj[n] = half[gemm_acc_col(j0, wave, lane, n)];
     const int shift = (lane & 3) * 16;                    // lanes 0 .. 3 assemble the words of the lane groups 0 .. 3
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
-        const int ib = i0 + wm * 128 + m * 16;
-        const f32x4_t hi = *(const f32x4_t*)(half + ib + (lane >> 4) * 4);
+        const int ib = gemm_acc_row(i0, wave, 0, m);      // the first of the block's 16 rows
+        const f32x4_t hi = *(const f32x4_t*)(half + gemm_acc_row(i0, wave, lane, m));
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int i = ib + (lane >> 4) * 4 + r;
+            const int i = gemm_acc_row(i0, wave, lane, m) + r;
             uint64_t word = 0;
 #pragma unroll
             for (int n = 0; n < 4; ++n) {
                 bool in = acc[m][n][r] >= hi[r] + hj[n];
                 // the diagonal bit of a finite row is set, not computed
-                if (diag) in = in || (i == jc + n * 16 + (lane & 15) && hi[r] == hi[r]);
+                if (diag) in = in || (i == gemm_acc_col(j0, wave, lane, n) && hi[r] == hi[r]);
                 const uint64_t b = __ballot(in);
                 word |= ((b >> shift) & 0xffffull) << (n * 16);
             }
@@ -110,15 +108,14 @@ __global__ __launch_bounds__(256) void radius_symmetrise_kernel(uint32_t* __rest
 
 __global__ __launch_bounds__(256) void radius_degree_kernel(const uint32_t* __restrict__ adj, int R, int words,
                                                             int32_t* __restrict__ degree) {
-    const int lane = threadIdx.x & 63;
-    for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < R; i += gridDim.x * 4) {
+    const int lane = row_lane();
+    for_wave_rows(R, [&](int i) {
         const uint32_t* row = adj + (int64_t)i * words;
         int s = 0;
         for (int w = lane; w < words; w += 64) s += __popc(row[w]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        s = wave_sum(s);
         if (lane == 0) degree[i] = s;
-    }
+    });
 }
 
 hipError_t launch_radius_graph(const RadiusGraphLaunch& L, hipStream_t stream) {
@@ -135,27 +132,12 @@ hipError_t launch_radius_graph(const RadiusGraphLaunch& L, hipStream_t stream) {
     if (st != hipSuccess) return st;
     st = hipMemsetAsync(L.adj, 0, (size_t)P.adj_bytes, stream);
     if (st != hipSuccess) return st;
-    // both operands are the slot's rows.  bf16 slot: b.b; fp32 slot: hi.hi + hi.lo + lo.hi + lo.lo
-    GemmOperands g;
-    g.A = B.p; g.lda = B.ld; g.I = R;
-    g.B = B.p; g.ldb = B.ld; g.J = R;
-    g.ksteps_per_plane = B.D / GEMM_BK;
-    for (int p = 0; p < GEMM_MAX_PLANES; ++p) { g.a_plane_off[p] = 0; g.b_plane_off[p] = 0; }
-    g.planes = 1;
-    if (B.planes == 2) {
-        g.planes = 4;
-        g.b_plane_off[1] = B.D;
-        g.a_plane_off[2] = B.D;
-        g.a_plane_off[3] = B.D; g.b_plane_off[3] = B.D;
-    }
-    st = launch<radius_tile_kernel, GEMM_LDS_BYTES>(dim3(P.tiles, P.tiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, stream, g,
-                                                    (const float*)L.half, L.adj, R, words);
+    st = launch<radius_tile_kernel, GEMM_LDS_BYTES>(dim3(P.tiles, P.tiles), dim3(GEMM_THREADS), GEMM_LDS_BYTES, stream,
+                                                    slot_self_operands(B), (const float*)L.half, L.adj, R, words);
     if (st != hipSuccess) return st;
     st = launch<radius_symmetrise_kernel>(dim3(P.sym_grid_x, P.blocks32), dim3(256), 0, stream, L.adj, R, words);
     if (st != hipSuccess) return st;
-    int grid = (R + 3) / 4;
-    if (grid > 16384) grid = 16384;
-    return launch<radius_degree_kernel>(dim3(grid), dim3(256), 0, stream, (const uint32_t*)L.adj, R, words, L.degree);
+    return launch<radius_degree_kernel>(dim3(wave_stride_grid(R)), dim3(256), 0, stream, (const uint32_t*)L.adj, R, words, L.degree);
 }
 
 // ---- labels ------------------------------------------------------------------------------------------------------
@@ -169,32 +151,24 @@ __global__ __launch_bounds__(256) void dbscan_init_kernel(const int32_t* __restr
 template <class F>
 __device__ __forceinline__ int core_neighbour_min(const uint32_t* __restrict__ row, const int32_t* __restrict__ degree, int R,
                                                   int words, int min_samples, int none, F f) {
-    const int lane = threadIdx.x & 63;
     int m = none;
-    for (int w = lane; w < words; w += 64) {
-        uint32_t bits = row[w];
-        while (bits) {
-            const int j = w * 32 + __ffs(bits) - 1;
-            bits &= bits - 1;
+    for (int w = row_lane(); w < words; w += 64) {
+        for_each_set_bit(row[w], [&](int b) {
+            const int j = w * 32 + b;
             if (j < R && degree[j] >= min_samples) {
                 const int v = f(j);
                 m = v < m ? v : m;
             }
-        }
+        });
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int v = __shfl_xor(m, o, 64);
-        m = v < m ? v : m;
-    }
-    return m;
+    return wave_min(m);
 }
 
 __global__ __launch_bounds__(256) void dbscan_sweep_kernel(const uint32_t* __restrict__ adj, const int32_t* __restrict__ degree,
                                                            int R, int words, int min_samples, int32_t* comp, int32_t* changed) {
-    const int lane = threadIdx.x & 63;
-    for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < R; i += gridDim.x * 4) {
-        if (degree[i] < min_samples) continue;
+    const int lane = row_lane();
+    for_wave_rows(R, [&](int i) {
+        if (degree[i] < min_samples) return;
         const int mine = comp[i];
         const int m = core_neighbour_min(adj + (int64_t)i * words, degree, R, words, min_samples, R, [&](int j) {
             const int c = comp[j];
@@ -205,7 +179,7 @@ __global__ __launch_bounds__(256) void dbscan_sweep_kernel(const uint32_t* __res
             if ((unsigned)mine < (unsigned)R) atomicMin(&comp[mine], m);      // hook the old root as well
             atomicOr(changed, 1);
         }
-    }
+    });
 }
 
 // comp[i] = the end of the chain i -> comp[i] -> ... (strictly falling, so it ends); other threads lower entries meanwhile,
@@ -243,16 +217,16 @@ __global__ __launch_bounds__(1024) void dbscan_roots_kernel(const int32_t* __res
 __global__ __launch_bounds__(256) void dbscan_labels_kernel(const uint32_t* __restrict__ adj, const int32_t* __restrict__ degree,
                                                             const int32_t* __restrict__ comp, int R, int words, int min_samples,
                                                             int32_t* labels, uint8_t* __restrict__ core) {
-    const int lane = threadIdx.x & 63;
+    const int lane = row_lane();
     const int none = 0x7fffffff;
-    for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < R; i += gridDim.x * 4) {
+    for_wave_rows(R, [&](int i) {
         if (degree[i] >= min_samples) {
             const int r = comp[i];
             if (lane == 0) {
                 core[i] = 1;
                 if (r != i) labels[i] = (unsigned)r < (unsigned)R ? labels[r] : -1;
             }
-            continue;
+            return;
         }
         const int m = core_neighbour_min(adj + (int64_t)i * words, degree, R, words, min_samples, none, [&](int j) {
             const int r = comp[j];
@@ -262,7 +236,7 @@ __global__ __launch_bounds__(256) void dbscan_labels_kernel(const uint32_t* __re
             core[i] = 0;
             labels[i] = m == none ? -1 : m;
         }
-    }
+    });
 }
 
 static bool dbscan_args_ok(int R, int min_samples) { return R >= 1 && R <= RADIUS_MAX_ROWS && min_samples >= 1; }
@@ -276,9 +250,7 @@ hipError_t launch_dbscan_sweep(const uint32_t* adj, const int32_t* degree, int R
         st = launch<dbscan_init_kernel>(dim3((R + 255) / 256), dim3(256), 0, stream, degree, R, min_samples, comp);
         if (st != hipSuccess) return st;
     }
-    int grid = (R + 3) / 4;
-    if (grid > 16384) grid = 16384;
-    st = launch<dbscan_sweep_kernel>(dim3(grid), dim3(256), 0, stream, adj, degree, R, words, min_samples, comp, changed);
+    st = launch<dbscan_sweep_kernel>(dim3(wave_stride_grid(R)), dim3(256), 0, stream, adj, degree, R, words, min_samples, comp, changed);
     if (st != hipSuccess) return st;
     return launch<dbscan_jump_kernel>(dim3((R + 255) / 256), dim3(256), 0, stream, degree, R, min_samples, comp);
 }
@@ -290,7 +262,6 @@ hipError_t launch_dbscan_finish(const uint32_t* adj, const int32_t* degree, int 
     hipError_t st = launch<dbscan_roots_kernel>(dim3(1), dim3(1024), 0, stream, degree, comp, R, min_samples, (R + 1023) / 1024, labels,
                                                 n_clusters);
     if (st != hipSuccess) return st;
-    int grid = (R + 3) / 4;
-    if (grid > 16384) grid = 16384;
-    return launch<dbscan_labels_kernel>(dim3(grid), dim3(256), 0, stream, adj, degree, comp, R, words, min_samples, labels, core);
+    return launch<dbscan_labels_kernel>(dim3(wave_stride_grid(R)), dim3(256), 0, stream, adj, degree, comp, R, words, min_samples, labels,
+                                        core);
 }

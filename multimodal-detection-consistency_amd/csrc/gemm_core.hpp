@@ -53,7 +53,50 @@ inline GemmOperands gemm_operands(const GemmLaunch& L) {
     return g;
 }
 
+// The operands of a pass over a bank slot.  The plane order is part of the contract: it is the order in which a tile's fp32
+// products are added, so reordering two planes changes result bits (and nothing else).
+// slot_operands: X rows of (hi | lo) planes at pitch 2 * D on A (the MFMA row dimension), the slot's rows on B (the lane
+// dimension).  bf16 slot: xhi.b + xlo.b; fp32 slot: xhi.bhi + xhi.blo + xlo.bhi (the lo.lo term is below fp32).
+inline GemmOperands slot_operands(const uint16_t* xplanes, int X, const BankRows& bank) {
+    GemmOperands g;
+    g.A = xplanes; g.lda = 2 * (int64_t)bank.D; g.I = X;
+    g.B = bank.p; g.ldb = bank.ld; g.J = (int)bank.R;
+    g.ksteps_per_plane = bank.D / GEMM_BK;
+    for (int p = 0; p < GEMM_MAX_PLANES; ++p) { g.a_plane_off[p] = 0; g.b_plane_off[p] = 0; }
+    if (bank.planes == 2) {
+        g.planes = 3;
+        g.b_plane_off[1] = bank.D;
+        g.a_plane_off[2] = bank.D;
+    } else {
+        g.planes = 2;
+        g.a_plane_off[1] = bank.D;
+    }
+    return g;
+}
+// slot_self_operands: the slot's rows on both sides.  bf16 slot: b.b; fp32 slot: hi.hi + hi.lo + lo.hi + lo.lo
+inline GemmOperands slot_self_operands(const BankRows& bank) {
+    GemmOperands g;
+    g.A = bank.p; g.lda = bank.ld; g.I = (int)bank.R;
+    g.B = bank.p; g.ldb = bank.ld; g.J = (int)bank.R;
+    g.ksteps_per_plane = bank.D / GEMM_BK;
+    for (int p = 0; p < GEMM_MAX_PLANES; ++p) { g.a_plane_off[p] = 0; g.b_plane_off[p] = 0; }
+    g.planes = 1;
+    if (bank.planes == 2) {
+        g.planes = 4;
+        g.b_plane_off[1] = bank.D;
+        g.a_plane_off[2] = bank.D;
+        g.a_plane_off[3] = bank.D; g.b_plane_off[3] = bank.D;
+    }
+    return g;
+}
+
+// The accumulators of a workgroup tile: wave w = (w >> 2, w & 3) of the 2 x 4 waves owns 128 x 64 of it as 8 x 4 MFMA blocks
+// (m, n); in a block the 16 lanes `lane & 15` hold 16 consecutive columns and `lane >> 4` picks a group of four rows, whose
+// row r is element r of acc[m][n].  In a tile whose first row / column is i0 / j0 (0: tile-local), gemm_acc_row is the row of
+// element r = 0 and gemm_acc_col the lane's column.
 typedef f32x4_t gemm_acc_t[8][4];
+__device__ __forceinline__ int gemm_acc_row(int i0, int wave, int lane, int m) { return i0 + (wave >> 2) * 128 + m * 16 + (lane >> 4) * 4; }
+__device__ __forceinline__ int gemm_acc_col(int j0, int wave, int lane, int n) { return j0 + (wave & 3) * 64 + n * 16 + (lane & 15); }
 
 // Stage one [256][64] bf16 tile: wave w copies rows w*32 .. w*32+31 with four
 // 1-KiB LDS-DMA pieces (8 rows each).

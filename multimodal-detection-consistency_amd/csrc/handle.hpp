@@ -5,6 +5,8 @@
 // tvc_sd_op.cpp: its entry points that read no model state; tvc_kmeans.cpp: k-means over a bank slot;
 // tvc_ivf.cpp: IVF probe and list scan; tvc_grad_split.cpp: the split-bf16 input gradient; tvc_dbscan.cpp: radius graph and
 // DBSCAN labels; tvc_pairs.cpp: pair lists of a bitmask graph and the cosine of listed pairs; tvc_rank.cpp: retrieval evaluation).
+// The entry points that pass over a bank slot share filled_slot (the TVC_E_STATE refusal of an empty slot) and ensure_planes /
+// split_planes (a workspace slot of (hi | lo) query planes); their work estimate is host_plan.hpp's slot_pass_flops.
 #pragma once
 #include "../../include/tvc.h"
 #include "kernels.hpp"
@@ -220,6 +222,29 @@ inline int ensure(tvc_handle* h, Slot s, size_t bytes) {
         return fail(h, TVC_E_NOMEM, m);
     }
     b.n = want;
+    return TVC_OK;
+}
+
+// The slot the bank calls address, for an entry point that reads its stored rows; no bank (never set, or released) and an empty
+// bank are its TVC_E_STATE refusal.  `fn` names the entry point in the message.
+inline int filled_slot(tvc_handle* h, const char* fn, BankSlot** out) {
+    BankSlot& bk = h->banks[h->cur_bank];
+    if (bk.D == 0 || !bk.bank || bk.R == 0) return fail(h, TVC_E_STATE, std::string(fn) + ": the selected slot holds no bank rows");
+    *out = &bk;
+    return TVC_OK;
+}
+
+// The (hi | lo) bf16 planes of fp32 rows, kept in a workspace slot.  Two steps, because an entry point sizes all its slots
+// before its first launch (a refusal for lack of memory comes before any work, and `ensure` may free and so synchronise):
+//   ensure_planes  room for `rows` rows of D columns, the count rounded up to a multiple of row_pad (256 where the reader
+//                  stages whole row tiles: the bank searches; else 1)
+//   split_planes   splits x [rows, D] into the slot; *out = the slot's planes [rows, 2 * D]
+inline int ensure_planes(tvc_handle* h, Slot s, int64_t rows, int row_pad, int D) {
+    return ensure(h, s, (size_t)((rows + row_pad - 1) / row_pad * row_pad) * 2 * D * 2);
+}
+inline int split_planes(tvc_handle* h, Slot s, const float* x, int64_t rows, int D, hipStream_t st, const uint16_t** out) {
+    *out = (const uint16_t*)h->ws[s].p;
+    HIP_TRY(launch_split_planes(x, (uint16_t*)h->ws[s].p, rows, D, 2, st));
     return TVC_OK;
 }
 

@@ -12,6 +12,17 @@
 #define HOST_PLAN_GEMM_BM 256
 #define HOST_PLAN_GEMM_BN 256
 
+// Workgroups of a wave-per-row grid-stride kernel over `rows` rows (rows.hpp: for_wave_rows): one wave to a row, the four rows
+// of launch.hpp's ROWS_PER_BLOCK to a 256-thread workgroup, at most WAVE_STRIDE_MAX_GRID workgroups; the waves loop beyond it.
+#define WAVE_STRIDE_MAX_GRID 16384
+inline int wave_stride_grid(int64_t rows) {
+    const int64_t g = (rows + 3) / 4;
+    return (int)(g < WAVE_STRIDE_MAX_GRID ? g : WAVE_STRIDE_MAX_GRID);
+}
+
+// the work of one GEMM pass of X rows over R stored rows of D columns with `products` plane products
+inline double slot_pass_flops(int64_t R, int64_t X, int D, int products) { return 2.0 * (double)R * (double)X * D * products; }
+
 inline void bank_plan(int64_t R, int M, int k, int* n_sample, int* sample_stride, int* S, int* cap) {
     const int64_t nbt = (R + HOST_PLAN_GEMM_BM - 1) / HOST_PLAN_GEMM_BM;
     const int nqt = (M + HOST_PLAN_GEMM_BN - 1) / HOST_PLAN_GEMM_BN;
@@ -87,7 +98,7 @@ inline RankPlan rank_plan(int64_t M, int64_t R, int D, int products) {
     if (M < 1 || M > 0x7fffffffLL - HOST_PLAN_GEMM_BM) return p;
     p.n_qtiles = (int)((M + HOST_PLAN_GEMM_BM - 1) / HOST_PLAN_GEMM_BM);
     p.mpad = (int64_t)p.n_qtiles * HOST_PLAN_GEMM_BM;
-    p.flops = 2.0 * (double)R * (double)M * D * products;
+    p.flops = slot_pass_flops(R, M, D, products);
     p.ok = true;
     return p;
 }
@@ -128,11 +139,11 @@ inline RadiusPlan radius_plan(int64_t R) {
     return p;
 }
 
-// Pair lists of a bitmask graph and the cosine of listed pairs (pairs.hip).  The count and the fill give one wave to a row, four
-// rows to a 256-thread workgroup, on a grid-stride loop of at most PAIRS_MAX_GRID workgroups; the scan of the counts is one
-// workgroup of PAIRS_SCAN_THREADS threads that own scan_per consecutive rows each.  The cosine gives PAIR_COS_LANES lanes to a
-// pair, so a workgroup takes 256 / PAIR_COS_LANES pairs per trip of its grid-stride loop.
-#define PAIRS_MAX_GRID 16384
+// Pair lists of a bitmask graph and the cosine of listed pairs (pairs.hip).  The count and the fill are wave-per-row grid-stride
+// kernels (wave_stride_grid: at most PAIRS_MAX_GRID workgroups); the scan of the counts is one workgroup of PAIRS_SCAN_THREADS
+// threads that own scan_per consecutive rows each.  The cosine gives PAIR_COS_LANES lanes to a pair, so a workgroup takes
+// 256 / PAIR_COS_LANES pairs per trip of its grid-stride loop.
+#define PAIRS_MAX_GRID WAVE_STRIDE_MAX_GRID
 #define PAIRS_SCAN_THREADS 1024
 #define PAIR_COS_LANES 16
 struct PairsPlan {
@@ -145,8 +156,7 @@ inline PairsPlan pairs_plan(int64_t R) {
     PairsPlan p;
     if (R < 1 || R > RADIUS_MAX_ROWS) return p;
     p.words = (int)((R + 63) / 64 * 2);
-    const int64_t g = (R + 3) / 4;
-    p.row_grid = (int)(g < PAIRS_MAX_GRID ? g : PAIRS_MAX_GRID);
+    p.row_grid = wave_stride_grid(R);
     p.scan_per = (int)((R + PAIRS_SCAN_THREADS - 1) / PAIRS_SCAN_THREADS);
     p.ok = true;
     return p;

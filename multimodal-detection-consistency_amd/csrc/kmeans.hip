@@ -9,8 +9,8 @@
 //           The (score desc, centre asc) order is cand_better; NaN scores lose every comparison, a row whose scores are all
 //           NaN keeps the "none" index and gets label -1.  The four lane groups of a wave and the two wave rows that share
 //           a bank row are reduced once, after the last centre tile.
-//           Products as in the bank search: centres are split into (hi | lo) bf16 planes; a bf16 bank multiplies both
-//           (exact products), an fp32 bank's planes take hi.hi + lo.hi + hi.lo.
+//           Products as in the bank search (slot_operands, gemm_core.hpp): centres are split into (hi | lo) bf16 planes; a bf16
+//           bank multiplies both (exact products), an fp32 bank's planes take hi.hi + hi.lo + lo.hi.
 //   update  a counting sort -- per-block label histogram (integer atomics into the block's own counter row), a column
 //           scan over the blocks, an exclusive scan over the clusters, a STABLE scatter (rank inside a 256-row chunk by
 //           comparison, chunks in order) -- gives the member lists in ascending row order; one workgroup per cluster then
@@ -48,8 +48,8 @@ __global__ __launch_bounds__(256) void kmeans_halfnorm_kernel(const float* __res
 
 // out[r] = |x_r|^2 of the stored row (hi + lo of an fp32 bank), one wave per row
 __global__ __launch_bounds__(256) void kmeans_rownorm_kernel(BankRows bank, float* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < bank.R; r += (int64_t)gridDim.x * 4) {
+    const int lane = row_lane();
+    for_wave_rows(bank.R, [&](int64_t r) {
         const uint16_t* br = bank.p + r * bank.ld;
         float s = 0.f;
         for (int c = lane * 8; c < bank.D; c += 512) {
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void kmeans_rownorm_kernel(BankRows bank, floa
         }
         s = wave_sum(s);
         if (lane == 0) out[r] = s;
-    }
+    });
 }
 
 struct KmeansAssignArgs {
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void kmeans_assign_kernel(GemmOperand
     int* red_i = (int*)(red_v + 256);
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    const int wm = wave >> 2, wn = wave & 3;
+    const int wm = wave >> 2;
     const int j0 = blockIdx.x * GEMM_BN;
     float bv[4];
     int bi[4];
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void kmeans_assign_kernel(GemmOperand
         gemm_mainloop(acc, g, ct * GEMM_BM, j0, smem);
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
-            const int c0 = ct * GEMM_BM + wm * 128 + m * 16 + (lane >> 4) * 4;
+            const int c0 = gemm_acc_row(ct * GEMM_BM, wave, lane, m);
             const f32x4_t hn = *(const f32x4_t*)(e.halfnorm + c0);
 #pragma unroll
             for (int n = 0; n < 4; ++n) {
@@ -110,14 +110,14 @@ __global__ __launch_bounds__(GEMM_THREADS) void kmeans_assign_kernel(GemmOperand
             const int oi = __shfl_xor(bi[n], o, 64);
             if (cand_better(ov, oi, bv[n], bi[n])) { bv[n] = ov; bi[n] = oi; }
         }
-        const int jl = wn * 64 + n * 16 + (lane & 15);
+        const int jl = gemm_acc_col(0, wave, lane, n);
         if (wm == 1 && (lane >> 4) == 0) { red_v[jl] = bv[n]; red_i[jl] = bi[n]; }
     }
     __syncthreads();
     if (wm == 0 && (lane >> 4) == 0) {
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
-            const int jl = wn * 64 + n * 16 + (lane & 15);
+            const int jl = gemm_acc_col(0, wave, lane, n);
             const int row = j0 + jl;
             if (row >= e.R) continue;
             float v = bv[n];
@@ -137,9 +137,7 @@ hipError_t launch_kmeans_halfnorm(const float* centroids, int D, int K, int Kpad
 
 hipError_t launch_kmeans_rownorm(const BankRows& bank, float* out, hipStream_t stream) {
     if (bank.R < 1 || bank.D < 8 || bank.D % 8 != 0 || bank.planes < 1 || bank.planes > 2) return hipErrorInvalidValue;
-    int64_t grid = (bank.R + 3) / 4;
-    if (grid > 16384) grid = 16384;
-    return launch<kmeans_rownorm_kernel>(dim3((int)grid), dim3(256), 0, stream, bank, out);
+    return launch<kmeans_rownorm_kernel>(dim3(wave_stride_grid(bank.R)), dim3(256), 0, stream, bank, out);
 }
 
 hipError_t launch_kmeans_assign(const KmeansAssignLaunch& L, hipStream_t stream) {
@@ -155,21 +153,7 @@ hipError_t launch_kmeans_assign(const KmeansAssignLaunch& L, hipStream_t stream)
         if (st != hipSuccess) return st;
     }
     // centres on the MFMA row dimension (A), bank rows on the lane dimension (B)
-    //   bf16 bank : chi.b + clo.b
-    //   fp32 bank : chi.bhi + chi.blo + clo.bhi
-    GemmOperands g;
-    g.A = L.cplanes; g.lda = 2 * (int64_t)B.D; g.I = L.K;
-    g.B = B.p; g.ldb = B.ld; g.J = (int)B.R;
-    g.ksteps_per_plane = B.D / GEMM_BK;
-    for (int p = 0; p < GEMM_MAX_PLANES; ++p) { g.a_plane_off[p] = 0; g.b_plane_off[p] = 0; }
-    if (B.planes == 2) {
-        g.planes = 3;
-        g.b_plane_off[1] = B.D;
-        g.a_plane_off[2] = B.D;
-    } else {
-        g.planes = 2;
-        g.a_plane_off[1] = B.D;
-    }
+    const GemmOperands g = slot_operands(L.cplanes, L.K, B);
     KmeansAssignArgs e;
     e.halfnorm = L.halfnorm; e.labels = L.labels; e.score = L.score; e.dist2 = L.dist2; e.R = (int)B.R;
     const int64_t n_btiles = (B.R + GEMM_BN - 1) / GEMM_BN;

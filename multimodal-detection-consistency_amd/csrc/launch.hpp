@@ -1,10 +1,14 @@
-// The one place a kernel is started, and the grids of the two common kernel shapes (included by the .hip files only;
-// kernels.hpp and handle.hpp stay free of it).
+// The one place a kernel is started, and the grids of the common kernel shapes (included by the .hip files only;
+// kernels.hpp and handle.hpp stay free of it).  The third shape's grid, wave_stride_grid of a wave-per-row grid-stride
+// kernel, is host_plan.hpp's: the host-only builds plan with it too.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <type_traits>
+#include "host_plan.hpp" // wave_stride_grid
 #include "rows.hpp"      // ROWS_PER_BLOCK
+
+static_assert(ROWS_PER_BLOCK == 4, "wave_stride_grid (host_plan.hpp) gives four rows to a workgroup");
 
 // Starts Kernel and returns hipGetLastError().  MaxLds > 0: the kernel takes more than 64 KiB of dynamic LDS, so its first
 // launch registers MaxLds bytes with the runtime (once per kernel, thread-safe: the Python lock is per engine, two engines

@@ -12,8 +12,8 @@
 //           lexicographic in (i, j), a pure function of (adj, group): no atomics.  A slot outside [0, P) is never written.
 //   cosine  `pair_cosine_kernel`: PAIR_COS_LANES = 16 lanes per pair whatever D is; lane s owns the elements [128 c + 8 s,
 //           128 c + 8 s + 8) of every 128-wide chunk c and adds x.y, |x|^2 and |y|^2 with one fp32 FMA chain each, elements
-//           in ascending order; the 16 partial sums meet in an xor butterfly (distances 8, 4, 2, 1), which leaves the same
-//           bits in every lane.  Products and fp32 additions commute, so swapping the two rows of a pair changes no bit:
+//           in ascending order; the 16 partial sums meet in lanes_sum's xor butterfly (distances 8, 4, 2, 1), which leaves the
+//           same bits in every lane.  Products and fp32 additions commute, so swapping the two rows of a pair changes no bit:
 //           sim(i, j) == sim(j, i), and nothing depends on the launch.  sim = dot / sqrt(|x|^2 |y|^2), both correctly rounded.
 #include "kernels.hpp"
 #include "launch.hpp"
@@ -32,19 +32,17 @@ __device__ __forceinline__ uint32_t pair_upper_word(const uint32_t* __restrict__
 // of the bits of x (word w, all < R), those whose row is in a group and in another group than gi
 __device__ __forceinline__ uint32_t pair_group_filter(uint32_t x, int w, int gi, const int32_t* __restrict__ group) {
     uint32_t keep = 0u;
-    while (x) {
-        const int b = __ffs(x) - 1;
-        x &= x - 1;
+    for_each_set_bit(x, [&](int b) {
         const int gj = group[w * 32 + b];
         if (gj >= 0 && gj != gi) keep |= 1u << b;
-    }
+    });
     return keep;
 }
 
 __global__ __launch_bounds__(256) void pair_count_kernel(const uint32_t* __restrict__ adj, int R, int words,
                                                          const int32_t* __restrict__ group, int64_t* __restrict__ offsets) {
-    const int lane = threadIdx.x & 63;
-    for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < R; i += gridDim.x * 4) {
+    const int lane = row_lane();
+    for_wave_rows(R, [&](int i) {
         const uint32_t* row = adj + (int64_t)i * words;
         const int gi = group ? group[i] : 0;
         int s = 0;
@@ -55,33 +53,9 @@ __global__ __launch_bounds__(256) void pair_count_kernel(const uint32_t* __restr
                 s += __popc(x);
             }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        s = wave_sum(s);
         if (lane == 0) offsets[i] = s;
-    }
-}
-
-// block_exclusive_scan (select.hpp) with 64-bit sums
-template <int T>
-__device__ __forceinline__ long long block_exclusive_scan64(long long mine, long long* wsum, long long& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    long long base = incl - mine;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < T / 64; ++w) {
-        const long long v = wsum[w];
-        if (w < wave) base += v;
-        total += v;
-    }
-    return base;
+    });
 }
 
 // one workgroup: thread t owns the rows [t * per, (t + 1) * per); counts -> exclusive offsets in place, offsets[R] = the total
@@ -92,7 +66,7 @@ __global__ __launch_bounds__(PAIRS_SCAN_THREADS) void pair_scan_kernel(int64_t* 
     long long mine = 0;
     for (int j = j0; j < j1; ++j) mine += offsets[j];
     long long total;
-    long long base = block_exclusive_scan64<PAIRS_SCAN_THREADS>(mine, wsum, total);
+    long long base = block_exclusive_scan<PAIRS_SCAN_THREADS>(mine, wsum, total);
     for (int j = j0; j < j1; ++j) {
         const long long c = offsets[j];
         offsets[j] = base;
@@ -104,11 +78,11 @@ __global__ __launch_bounds__(PAIRS_SCAN_THREADS) void pair_scan_kernel(int64_t* 
 __global__ __launch_bounds__(256) void pair_fill_kernel(const uint32_t* __restrict__ adj, int R, int words,
                                                         const int32_t* __restrict__ group, const int64_t* __restrict__ offsets,
                                                         int32_t* __restrict__ pairs, int64_t P) {
-    const int lane = threadIdx.x & 63;
-    for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < R; i += gridDim.x * 4) {
+    const int lane = row_lane();
+    for_wave_rows(R, [&](int i) {
         const uint32_t* row = adj + (int64_t)i * words;
         const int gi = group ? group[i] : 0;
-        if (gi < 0) continue;
+        if (gi < 0) return;
         int64_t base = offsets[i];
         for (int w0 = i >> 5; w0 < words; w0 += 64) {
             const int w = w0 + lane;
@@ -118,25 +92,18 @@ __global__ __launch_bounds__(256) void pair_fill_kernel(const uint32_t* __restri
                 if (group) x = pair_group_filter(x, w, gi, group);
             }
             const int c = __popc(x);
-            int incl = c;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int v = __shfl_up(incl, o, 64);
-                if (lane >= o) incl += v;
-            }
+            const int incl = wave_inclusive_scan(c, lane);
             int64_t slot = base + (incl - c);
-            while (x) {
-                const int j = w * 32 + __ffs(x) - 1;
-                x &= x - 1;
+            for_each_set_bit(x, [&](int b) {
                 if ((uint64_t)slot < (uint64_t)P) {
                     pairs[2 * slot] = i;
-                    pairs[2 * slot + 1] = j;
+                    pairs[2 * slot + 1] = w * 32 + b;
                 }
                 ++slot;
-            }
+            });
             base += __shfl(incl, 63, 64);
         }
-    }
+    });
 }
 
 __global__ __launch_bounds__(256) void pair_cosine_kernel(BankRows bank, const int32_t* __restrict__ pairs, int64_t P,
@@ -165,12 +132,9 @@ __global__ __launch_bounds__(256) void pair_cosine_kernel(BankRows bank, const i
                 }
             }
         }
-#pragma unroll
-        for (int o = PAIR_COS_LANES / 2; o > 0; o >>= 1) {
-            dot += __shfl_xor(dot, o, 64);
-            nx += __shfl_xor(nx, o, 64);
-            ny += __shfl_xor(ny, o, 64);
-        }
+        dot = lanes_sum<PAIR_COS_LANES>(dot);
+        nx = lanes_sum<PAIR_COS_LANES>(nx);
+        ny = lanes_sum<PAIR_COS_LANES>(ny);
         if (live && sub == 0) {
             float s = __builtin_nanf("");
             if (in) {

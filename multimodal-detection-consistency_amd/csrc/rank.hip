@@ -6,8 +6,8 @@
 //     pos(t) = (targets of i ahead of t) + (irrelevant rows of i ahead of t),
 // and every metric is a pure function of the positions.
 //
-//   tile    `rank_tile_kernel<COUNT>`: kmeans_assign_kernel's shape -- a workgroup owns 256 bank rows on the lane dimension and
-//           walks the query tiles on the MFMA row dimension; no score leaves the accumulators except a target's.
+//   tile    `rank_tile_kernel<COUNT>`: a workgroup owns 256 bank rows on the lane dimension and walks the query tiles on the MFMA
+//           row dimension (gemm_core.hpp: gemm_mainloop, the gemm_acc_t layout); no score leaves the accumulators except a target's.
 //     EMIT    every relevant element writes (score, row) to slot tgt_off[i] + gpos[j] of the query's target list; gpos[j] is
 //             row j's place inside its label group in ascending row order, so every slot is written exactly once: no atomics.
 //     COUNT   takes the lists back in rank order.  An irrelevant element is dropped by one compare against the score of the
@@ -17,8 +17,8 @@
 //             is the list's, so its positions are distinct whatever the rounding.  A NaN score fails every compare.
 //   metrics `rank_metrics_kernel`: one wave per query; pos[c] = c + sum_{b <= c} hist[b] by a wave scan in chunks of 64, then
 //           AP, RR and per k (hits, DCG, IDCG) in fp64.  Nothing is reduced over the queries on the device.
-// Products as in the bank search and kmeans_assign: queries split into (hi | lo) bf16 planes, 2 products on a bf16 slot, 3 on
-// an fp32 slot.  LDS holds the main loop's 128 KiB and nothing else: the counters are global, which is why the slow path of
+// Products as slot_operands (gemm_core.hpp) orders them: queries split into (hi | lo) bf16 planes, 2 products on a bf16 slot, 3
+// on an fp32 slot.  LDS holds the main loop's 128 KiB and nothing else: the counters are global, which is why the slow path of
 // COUNT must be (and, behind the tlow compare, is) rare.
 #include "gemm_core.hpp"
 #include "kernels.hpp"
@@ -70,14 +70,13 @@ __global__ __launch_bounds__(GEMM_THREADS) void rank_tile_kernel(GemmOperands g,
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    const int wm = wave >> 2, wn = wave & 3;
     const int j0 = blockIdx.x * GEMM_BN;
     // the lane's four bank rows: label, place in the label group, in range
     int gl[4], gp[4];
     bool jin[4];
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
-        const int j = j0 + wn * 64 + n * 16 + (lane & 15);
+        const int j = gemm_acc_col(j0, wave, lane, n);
         jin[n] = j < e.R;
         gl[n] = jin[n] ? e.glabel[j] : -1;
         gp[n] = (!COUNT && jin[n]) ? e.gpos[j] : 0;
@@ -88,7 +87,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void rank_tile_kernel(GemmOperands g,
         gemm_mainloop(acc, g, qt * GEMM_BM, j0, smem);
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
-            const int i0 = qt * GEMM_BM + wm * 128 + m * 16 + (lane >> 4) * 4;
+            const int i0 = gemm_acc_row(qt * GEMM_BM, wave, lane, m);
             const i32x4_t ql = *(const i32x4_t*)(e.qlab + i0);
             f32x4_t tl = f32x4_t{0.f, 0.f, 0.f, 0.f};
             if (COUNT) tl = *(const f32x4_t*)(e.tlow + i0);
@@ -102,7 +101,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void rank_tile_kernel(GemmOperands g,
                     const bool hit = COUNT ? (!rel && jin[n] && acc[m][n][r] >= tl[r]) : rel;
                     todo |= (unsigned)hit << r;
                 }
-                const int j = j0 + wn * 64 + n * 16 + (lane & 15);
+                const int j = gemm_acc_col(j0, wave, lane, n);
                 while (todo) {
                     const int r = __builtin_ctz(todo);
                     todo &= todo - 1;
@@ -136,17 +135,6 @@ struct RankMetricsArgs {
     int k[RANK_MAX_K];
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void rank_metrics_kernel(RankMetricsArgs a) {
     const int lane = threadIdx.x & 63;
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -160,12 +148,7 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(RankMetricsArgs a) {
     int carry = 0, first = 0;                                // irrelevant rows ahead of the chunk; pos of target 0
     for (int64_t c0 = 0; c0 < P; c0 += 64) {
         const int64_t c = c0 + lane;
-        int v = c < P ? a.hist[beg + c] : 0;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {                   // inclusive scan over the lanes
-            const int u = __shfl_up(v, o, 64);
-            if (lane >= o) v += u;
-        }
+        const int v = wave_inclusive_scan(c < P ? a.hist[beg + c] : 0, lane);
         if (c < P) {
             const int64_t p = c + carry + v;
             a.pos[beg + c] = (int32_t)p;
@@ -178,7 +161,7 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(RankMetricsArgs a) {
         if (c0 == 0) first = __shfl(v, 0, 64);
         carry += __shfl(v, 63, 64);
     }
-    ap = wave_sum_f64(ap);
+    ap = wave_sum(ap);
     if (lane == 0) {
         a.ap[q] = P > 0 ? ap / (double)P : 0.0;
         a.rr[q] = P > 0 ? 1.0 / (double)(first + 1) : 0.0;
@@ -189,9 +172,9 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(RankMetricsArgs a) {
         const int64_t n_ideal = P < a.k[t] ? P : a.k[t];
         double ideal = 0.0;
         for (int64_t c = lane; c < n_ideal; c += 64) ideal += 1.0 / log2((double)(c + 2));
-        ideal = wave_sum_f64(ideal);
-        const double d = wave_sum_f64(dcg[t]);
-        const int hsum = wave_sum_i32(hits[t]);
+        ideal = wave_sum(ideal);
+        const double d = wave_sum(dcg[t]);
+        const int hsum = wave_sum(hits[t]);
         if (lane == 0) {
             a.hits[(int64_t)q * a.n_k + t] = hsum;
             a.dcg[(int64_t)q * a.n_k + t] = d;
@@ -211,22 +194,8 @@ static hipError_t launch_rank_tile(const RankTileLaunch& L, hipStream_t stream) 
                                              COUNT ? L.tgt_off : (const int64_t*)nullptr, (const float*)L.tgt_sim, L.qlab,
                                              COUNT ? L.tlow : (float*)nullptr);
     if (st != hipSuccess) return st;
-    // queries on the MFMA row dimension (A), bank rows on the lane dimension (B): kmeans_assign's operands
-    //   bf16 bank : qhi.b + qlo.b
-    //   fp32 bank : qhi.bhi + qhi.blo + qlo.bhi
-    GemmOperands g;
-    g.A = L.qplanes; g.lda = 2 * (int64_t)B.D; g.I = L.M;
-    g.B = B.p; g.ldb = B.ld; g.J = (int)B.R;
-    g.ksteps_per_plane = B.D / GEMM_BK;
-    for (int p = 0; p < GEMM_MAX_PLANES; ++p) { g.a_plane_off[p] = 0; g.b_plane_off[p] = 0; }
-    if (B.planes == 2) {
-        g.planes = 3;
-        g.b_plane_off[1] = B.D;
-        g.a_plane_off[2] = B.D;
-    } else {
-        g.planes = 2;
-        g.a_plane_off[1] = B.D;
-    }
+    // queries on the MFMA row dimension (A), bank rows on the lane dimension (B)
+    const GemmOperands g = slot_operands(L.qplanes, L.M, B);
     RankTileArgs e;
     e.qlab = L.qlab; e.glabel = L.glabel; e.gpos = L.gpos; e.tlow = L.tlow; e.tgt_off = L.tgt_off;
     e.tgt_sim = L.tgt_sim; e.tgt_row = L.tgt_row; e.hist = L.hist; e.M = L.M; e.R = (int)B.R;

@@ -15,6 +15,13 @@ __device__ __forceinline__ int row_lane() { return threadIdx.x & 63; }
 // the row of this wave (R = int64_t where rows * d may pass 2^31)
 template <class R = int>
 __device__ __forceinline__ R wave_row() { return (R)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6); }
+// The grid-stride form of the shape: f(row) for the rows wave_row(), + gridDim.x * ROWS_PER_BLOCK, ... below `rows` (the whole
+// wave calls f; a `return` in f goes on to the wave's next row).  Its grid is wave_stride_grid(rows) (host_plan.hpp), whose cap
+// keeps the first row and the step far inside 32 bits.
+template <class R, class F>
+__device__ __forceinline__ void for_wave_rows(R rows, F&& f) {
+    for (R i = (R)(blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6)); i < rows; i += (R)(gridDim.x * ROWS_PER_BLOCK)) f(i);
+}
 
 // f(i, c) for the pieces i = 0..3 of this lane that exist in a row of nv vector columns
 template <class F>

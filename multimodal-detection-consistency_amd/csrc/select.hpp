@@ -1,5 +1,6 @@
 // Device code only: "k rounds of block arg-max by (value desc, id asc)" and the block-wide exclusive scan, written once for
-// bank_select_kernel and row_topk_kernel (bank.hip), the two selects of ivf.hip and kmeans_offsets_kernel (kmeans.hip).
+// bank_select_kernel and row_topk_kernel (bank.hip), the two selects of ivf.hip, kmeans_offsets_kernel (kmeans.hip),
+// dbscan_roots_kernel (dbscan.hip) and, with 64-bit sums, pair_scan_kernel (pairs.hip).
 // A round: every thread scans the elements it owns into a Best (WHAT it admits stays with the kernel: they differ), block_best()
 // gives every thread the block's best after ONE barrier, thread 0 writes it out and the thread that owns the winning element
 // strikes it -- the only thread that ever reads it again, so nothing has to order the two.
@@ -62,23 +63,18 @@ __device__ __forceinline__ Best<NP> block_best(Best<NP> b, BestSlots<T, NP>& red
 }
 
 // -> the exclusive prefix of `mine` over the workgroup's T threads, `total` = the sum over all of them: a wave scan, the waves'
-// totals through wsum (T / 64 ints of LDS), one barrier
-template <int T>
-__device__ __forceinline__ int block_exclusive_scan(int mine, int* wsum, int& total) {
+// totals through wsum (T / 64 values of LDS), one barrier.  V = int, or long long where the total can pass 2^31
+template <int T, class V>
+__device__ __forceinline__ V block_exclusive_scan(V mine, V* wsum, V& total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
+    const V incl = wave_inclusive_scan(mine, lane);
     if (lane == 63) wsum[wave] = incl;
     __syncthreads();
-    int base = incl - mine;
+    V base = incl - mine;
     total = 0;
 #pragma unroll
     for (int w = 0; w < T / 64; ++w) {
-        const int v = wsum[w];
+        const V v = wsum[w];
         if (w < wave) base += v;
         total += v;
     }

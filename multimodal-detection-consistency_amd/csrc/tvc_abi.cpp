@@ -472,16 +472,16 @@ int tvc_bank_search(tvc_handle* h, const float* rows_dev, int32_t M, int32_t k, 
     BankSearchLaunch L;
     bank_plan(bk.R, M, k, &L.n_sample, &L.sample_stride, &L.S, &L.cap);
     int rc;
-    if ((rc = ensure(h, WS_QPLANES, (size_t)((M + 255) / 256 * 256) * 2 * D * 2))) return rc;
+    if ((rc = ensure_planes(h, WS_QPLANES, M, 256, D))) return rc;
     if ((rc = ensure(h, WS_S0, (size_t)M * (L.n_sample > 256 ? L.n_sample : 256) * 4))) return rc;
     if ((rc = ensure(h, WS_TAU, (size_t)M * 4))) return rc;
     if ((rc = ensure(h, WS_CAND, (size_t)L.S * M * L.cap * 8))) return rc;
     if ((rc = ensure(h, WS_CAND_CNT, (size_t)L.S * M * 4))) return rc;
     if ((rc = ensure(h, WS_MOM_PART, (size_t)L.S * M * 16))) return rc;
     if ((rc = ensure(h, WS_OVERFLOW, 16))) return rc;
-    HIP_TRY(launch_split_planes(rows_dev, (uint16_t*)h->ws[WS_QPLANES].p, M, D, 2, st));
+    if ((rc = split_planes(h, WS_QPLANES, rows_dev, M, D, st, &L.qplanes))) return rc;
     L.bank = bank_rows(bk);
-    L.qplanes = (const uint16_t*)h->ws[WS_QPLANES].p; L.q_rows_padded = true; L.M = M; L.k = k; L.count_thr = count_thr;
+    L.q_rows_padded = true; L.M = M; L.k = k; L.count_thr = count_thr;
     L.idx_offset = idx_offset;
     L.rows = rows_dev; L.bank_bounds = bk.bounds; L.allow_filter = h->bank_filter;
     L.s0 = (float*)h->ws[WS_S0].p; L.gmax = L.s0; L.tau = (float*)h->ws[WS_TAU].p; L.cand = h->ws[WS_CAND].p;
@@ -491,7 +491,7 @@ int tvc_bank_search(tvc_handle* h, const float* rows_dev, int32_t M, int32_t k, 
     {
         const bool filter = !moments_dev && h->bank_filter && D <= 2048;
         const int planes = filter ? 1 : bank_products(bk.planes);
-        ProfScope ps(h, st, TVC_PROF_BANK, 2.0 * (double)bk.R * M * D * planes);
+        ProfScope ps(h, st, TVC_PROF_BANK, slot_pass_flops(bk.R, M, D, planes));
         HIP_TRY(launch_bank_search(L, st));
     }
     return TVC_OK;
@@ -513,12 +513,12 @@ int tvc_bank_search_dense(tvc_handle* h, const float* rows_dev, int32_t M, int32
     if (block > 64) block = 64;
     if (block < 1) block = 1;
     int rc;
-    if ((rc = ensure(h, WS_QPLANES, (size_t)((M + 255) / 256 * 256) * 2 * D * 2))) return rc;
+    if ((rc = ensure_planes(h, WS_QPLANES, M, 256, D))) return rc;
     if ((rc = ensure(h, WS_S0, (size_t)block * bk.R * 4))) return rc;
-    HIP_TRY(launch_split_planes(rows_dev, (uint16_t*)h->ws[WS_QPLANES].p, M, D, 2, st));
     BankSearchLaunch L;
+    if ((rc = split_planes(h, WS_QPLANES, rows_dev, M, D, st, &L.qplanes))) return rc;
     L.bank = bank_rows(bk);
-    L.qplanes = (const uint16_t*)h->ws[WS_QPLANES].p; L.q_rows_padded = true; L.M = M; L.k = k; L.count_thr = count_thr;
+    L.q_rows_padded = true; L.M = M; L.k = k; L.count_thr = count_thr;
     L.idx_offset = idx_offset;
     L.topk_idx = topk_idx_dev; L.topk_sim = topk_sim_dev; L.moments = moments_dev;
     HIP_TRY(launch_bank_search_dense(L, (float*)h->ws[WS_S0].p, block, st));
@@ -579,18 +579,17 @@ int tvc_cosine_matrix(tvc_handle* h, const float* x_dev, int32_t N, const float*
     int rc;
     if ((rc = ensure(h, WS_COSX, (size_t)N * D * 4))) return rc;
     if ((rc = ensure(h, WS_COSY, (size_t)M * D * 4))) return rc;
-    if ((rc = ensure(h, WS_COSXP, (size_t)N * D * 4))) return rc;
-    if ((rc = ensure(h, WS_COSYP, (size_t)M * D * 4))) return rc;
+    if ((rc = ensure_planes(h, WS_COSXP, N, 1, D))) return rc;
+    if ((rc = ensure_planes(h, WS_COSYP, M, 1, D))) return rc;
     float* xn = (float*)h->ws[WS_COSX].p;
     float* yn = (float*)h->ws[WS_COSY].p;
     HIP_TRY(hipMemcpyAsync(xn, x_dev, (size_t)N * D * 4, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(yn, y_dev, (size_t)M * D * 4, hipMemcpyDeviceToDevice, st));
     HIP_TRY(launch_l2norm_rows(xn, N, D, st));
     HIP_TRY(launch_l2norm_rows(yn, M, D, st));
-    uint16_t* xp = (uint16_t*)h->ws[WS_COSXP].p;
-    uint16_t* yp = (uint16_t*)h->ws[WS_COSYP].p;
-    HIP_TRY(launch_split_planes(xn, xp, N, D, 2, st));
-    HIP_TRY(launch_split_planes(yn, yp, M, D, 2, st));
+    const uint16_t *xp, *yp;
+    if ((rc = split_planes(h, WS_COSXP, xn, N, D, st, &xp))) return rc;
+    if ((rc = split_planes(h, WS_COSYP, yn, M, D, st, &yp))) return rc;
     // out[n, m]: "A rows" (fast output dim) = y, "B rows" = x; hi.hi + hi.lo + lo.hi
     HIP_TRY(timed_gemm(h, gemm_launch_planes(yp, 2 * (int64_t)D, M, 2, xp, N, D, out_dev, M), st));
     return TVC_OK;

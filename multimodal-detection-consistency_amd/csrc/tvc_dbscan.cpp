@@ -8,8 +8,10 @@ static_assert(TVC_RADIUS_MAX_ROWS == RADIUS_MAX_ROWS, "include/tvc.h and host_pl
 
 int tvc_radius_graph(tvc_handle* h, float eps, uint32_t* adj_dev, int32_t* degree_dev, void* stream) {
     if (!h) return TVC_E_INVALID;
-    BankSlot& bk = h->banks[h->cur_bank];
-    if (bk.D == 0 || !bk.bank || bk.R == 0) return fail(h, TVC_E_STATE, "tvc_radius_graph: the selected slot holds no bank rows");
+    BankSlot* slot;
+    int rc;
+    if ((rc = filled_slot(h, "tvc_radius_graph", &slot))) return rc;
+    const BankSlot& bk = *slot;
     if (!std::isfinite(eps) || !(eps > 0.f)) return fail(h, TVC_E_INVALID, "tvc_radius_graph: eps must be finite and positive");
     if (bk.R > TVC_RADIUS_MAX_ROWS) return fail(h, TVC_E_INVALID, "tvc_radius_graph: the slot holds more than TVC_RADIUS_MAX_ROWS rows");
     if (!adj_dev || !degree_dev) return fail(h, TVC_E_INVALID, "tvc_radius_graph: adj and degree must not be NULL");
@@ -17,7 +19,6 @@ int tvc_radius_graph(tvc_handle* h, float eps, uint32_t* adj_dev, int32_t* degre
     hipStream_t st = (hipStream_t)stream;
     RadiusGraphLaunch L;
     L.plan = radius_plan(bk.R);
-    int rc;
     if ((rc = ensure(h, WS_DB_NORM2, (size_t)bk.R * 4))) return rc;
     if ((rc = ensure(h, WS_DB_HALF, (size_t)L.plan.hpad * 4))) return rc;
     L.bank = bank_rows(bk);

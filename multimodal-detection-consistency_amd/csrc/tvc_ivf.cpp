@@ -17,13 +17,12 @@ int tvc_ivf_probe(tvc_handle* h, const float* rows_dev, int32_t M, int32_t D, co
     if (chunk > M) chunk = M;
     L.chunk = (int)chunk;
     int rc;
-    if ((rc = ensure(h, WS_IVF_CPLANES, (size_t)nlist * 2 * D * 2))) return rc;
-    if ((rc = ensure(h, WS_IVF_PQPLANES, (size_t)M * 2 * D * 2))) return rc;
+    if ((rc = ensure_planes(h, WS_IVF_CPLANES, nlist, 1, D))) return rc;
+    if ((rc = ensure_planes(h, WS_IVF_PQPLANES, M, 1, D))) return rc;
     if ((rc = ensure(h, WS_IVF_HALFNORM, (size_t)nlist * 4))) return rc;
     if ((rc = ensure(h, WS_IVF_SIMS, (size_t)chunk * nlist * 4))) return rc;
-    HIP_TRY(launch_split_planes(centroids_dev, (uint16_t*)h->ws[WS_IVF_CPLANES].p, nlist, D, 2, st));
-    HIP_TRY(launch_split_planes(rows_dev, (uint16_t*)h->ws[WS_IVF_PQPLANES].p, M, D, 2, st));
-    L.cplanes = (const uint16_t*)h->ws[WS_IVF_CPLANES].p; L.qplanes = (const uint16_t*)h->ws[WS_IVF_PQPLANES].p;
+    if ((rc = split_planes(h, WS_IVF_CPLANES, centroids_dev, nlist, D, st, &L.cplanes))) return rc;
+    if ((rc = split_planes(h, WS_IVF_PQPLANES, rows_dev, M, D, st, &L.qplanes))) return rc;
     L.centroids = centroids_dev; L.halfnorm = (float*)h->ws[WS_IVF_HALFNORM].p;
     L.M = M; L.D = D; L.nlist = nlist; L.nprobe = nprobe;
     L.sims = (float*)h->ws[WS_IVF_SIMS].p; L.lists = lists_dev; L.score = score_dev;
@@ -36,8 +35,10 @@ int tvc_ivf_scan(tvc_handle* h, const float* rows_dev, int32_t M, int32_t k, con
                  const int32_t* list_offsets_dev, int32_t nlist, int32_t max_list_rows, const int32_t* row_ids_dev,
                  int64_t idx_offset, int32_t* topk_idx_dev, float* topk_sim_dev, int32_t* topk_pos_dev, void* stream) {
     if (!h) return TVC_E_INVALID;
-    BankSlot& bk = h->banks[h->cur_bank];
-    if (bk.D == 0 || !bk.bank || bk.R == 0) return fail(h, TVC_E_STATE, "tvc_ivf_scan: the selected slot holds no bank rows");
+    BankSlot* slot;
+    int rc;
+    if ((rc = filled_slot(h, "tvc_ivf_scan", &slot))) return rc;
+    const BankSlot& bk = *slot;
     if (k < 1 || k > TVC_MAX_TOPK || nprobe < 1 || nprobe > TVC_MAX_TOPK)
         return fail(h, TVC_E_INVALID, "tvc_ivf_scan: need 1 <= k <= 128 and 1 <= nprobe <= 128");
     if (nlist < 1 || nlist > IVF_MAX_NLIST || max_list_rows < 1 || M < 0)
@@ -52,17 +53,15 @@ int tvc_ivf_scan(tvc_handle* h, const float* rows_dev, int32_t M, int32_t k, con
     if (!L.plan.ok)
         return fail(h, TVC_E_INVALID, "tvc_ivf_scan: nprobe x round_up(max_list_rows, 16) floats exceed the 256 MiB score workspace");
     hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if ((rc = ensure(h, WS_IVF_QPLANES, (size_t)M * 2 * D * 2))) return rc;
+    if ((rc = ensure_planes(h, WS_IVF_QPLANES, M, 1, D))) return rc;
     if ((rc = ensure(h, WS_IVF_BLKCNT, (size_t)L.plan.sort_blocks * nlist * 4))) return rc;
     if ((rc = ensure(h, WS_IVF_PCOUNTS, (size_t)nlist * 4))) return rc;
     if ((rc = ensure(h, WS_IVF_POFFSETS, ((size_t)nlist + 1) * 4))) return rc;
     if ((rc = ensure(h, WS_IVF_PORDER, (size_t)L.plan.chunk * nprobe * 4))) return rc;
     if ((rc = ensure(h, WS_IVF_SCORES, (size_t)L.plan.score_bytes))) return rc;
     if ((rc = ensure(h, WS_OVERFLOW, 16))) return rc;
-    HIP_TRY(launch_split_planes(rows_dev, (uint16_t*)h->ws[WS_IVF_QPLANES].p, M, D, 2, st));
+    if ((rc = split_planes(h, WS_IVF_QPLANES, rows_dev, M, D, st, &L.qplanes))) return rc;
     L.bank = bank_rows(bk);
-    L.qplanes = (const uint16_t*)h->ws[WS_IVF_QPLANES].p;
     L.M = M; L.k = k; L.nprobe = nprobe; L.nlist = nlist; L.max_list_rows = max_list_rows;
     L.probes = probes_dev; L.list_offsets = list_offsets_dev; L.row_ids = row_ids_dev; L.idx_offset = idx_offset;
     L.blk_cnt = (int32_t*)h->ws[WS_IVF_BLKCNT].p; L.pair_counts = (int32_t*)h->ws[WS_IVF_PCOUNTS].p;

@@ -2,12 +2,11 @@
 // translation unit: nothing here is called from tvc_abi.cpp.
 #include "handle.hpp"
 
-// the slot the call addresses, or the refusal: no bank (never set, or released) and an empty bank are TVC_E_STATE
+// the slot the call addresses, or the refusal
 static int kmeans_slot(tvc_handle* h, const char* fn, int32_t K, BankSlot** out) {
-    BankSlot& bk = h->banks[h->cur_bank];
-    if (bk.D == 0 || !bk.bank || bk.R == 0) return fail(h, TVC_E_STATE, std::string(fn) + ": the selected slot holds no bank rows");
-    if (K < 1 || K > bk.R || K > KMEANS_MAX_K) return fail(h, TVC_E_INVALID, std::string(fn) + ": need 1 <= K <= min(R, 65536)");
-    *out = &bk;
+    int rc;
+    if ((rc = filled_slot(h, fn, out))) return rc;
+    if (K < 1 || K > (*out)->R || K > KMEANS_MAX_K) return fail(h, TVC_E_INVALID, std::string(fn) + ": need 1 <= K <= min(R, 65536)");
     return TVC_OK;
 }
 
@@ -21,15 +20,15 @@ int tvc_kmeans_assign(tvc_handle* h, const float* centroids_dev, int32_t K, int3
     hipStream_t st = (hipStream_t)stream;
     const int D = bk->D;
     const size_t Kpad = ((size_t)K + HOST_PLAN_GEMM_BM - 1) / HOST_PLAN_GEMM_BM * HOST_PLAN_GEMM_BM;
-    if ((rc = ensure(h, WS_KM_CPLANES, (size_t)K * 2 * D * 2))) return rc;
+    if ((rc = ensure_planes(h, WS_KM_CPLANES, K, 1, D))) return rc;
     if ((rc = ensure(h, WS_KM_HALFNORM, Kpad * 4))) return rc;
-    HIP_TRY(launch_split_planes(centroids_dev, (uint16_t*)h->ws[WS_KM_CPLANES].p, K, D, 2, st));
     KmeansAssignLaunch L;
+    if ((rc = split_planes(h, WS_KM_CPLANES, centroids_dev, K, D, st, &L.cplanes))) return rc;
     L.bank = bank_rows(*bk);
-    L.centroids = centroids_dev; L.cplanes = (const uint16_t*)h->ws[WS_KM_CPLANES].p; L.K = K;
+    L.centroids = centroids_dev; L.K = K;
     L.halfnorm = (float*)h->ws[WS_KM_HALFNORM].p;
     L.labels = labels_dev; L.score = score_dev; L.dist2 = dist2_dev;
-    ProfScope ps(h, st, TVC_PROF_BANK, 2.0 * (double)bk->R * K * D * bank_products(bk->planes));
+    ProfScope ps(h, st, TVC_PROF_BANK, slot_pass_flops(bk->R, K, D, bank_products(bk->planes)));
     HIP_TRY(launch_kmeans_assign(L, st));
     return TVC_OK;
 }

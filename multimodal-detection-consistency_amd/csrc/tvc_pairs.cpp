@@ -35,8 +35,9 @@ int tvc_graph_pair_fill(tvc_handle* h, const uint32_t* adj_dev, int32_t R, const
 
 int tvc_pair_cosine(tvc_handle* h, const int32_t* pairs_dev, int64_t P, float* sim_dev, void* stream) {
     if (!h) return TVC_E_INVALID;
-    BankSlot& bk = h->banks[h->cur_bank];
-    if (bk.D == 0 || !bk.bank || bk.R == 0) return fail(h, TVC_E_STATE, "tvc_pair_cosine: the selected slot holds no bank rows");
+    BankSlot* slot;
+    if (int rc = filled_slot(h, "tvc_pair_cosine", &slot)) return rc;
+    const BankSlot& bk = *slot;
     if (P < 0) return fail(h, TVC_E_INVALID, "tvc_pair_cosine: need P >= 0");
     if (P == 0) return TVC_OK;
     if (!pairs_dev || !sim_dev) return fail(h, TVC_E_INVALID, "tvc_pair_cosine: pairs and sim must not be NULL when P > 0");

@@ -6,12 +6,11 @@ static_assert(TVC_RANK_MAX_K == RANK_MAX_K, "include/tvc.h and host_plan.hpp dis
 
 // the slot the call addresses and the plan of M queries over it, or the refusal
 static int rank_slot(tvc_handle* h, const char* fn, int32_t M, int64_t T, BankSlot** out, RankPlan* plan) {
-    BankSlot& bk = h->banks[h->cur_bank];
-    if (bk.D == 0 || !bk.bank || bk.R == 0) return fail(h, TVC_E_STATE, std::string(fn) + ": the selected slot holds no bank rows");
-    *plan = rank_plan(M, bk.R, bk.D, bank_products(bk.planes));
+    int rc;
+    if ((rc = filled_slot(h, fn, out))) return rc;
+    *plan = rank_plan(M, (*out)->R, (*out)->D, bank_products((*out)->planes));
     if (!plan->ok) return fail(h, TVC_E_INVALID, std::string(fn) + ": need M >= 1");
     if (T < 0) return fail(h, TVC_E_INVALID, std::string(fn) + ": need T >= 0");
-    *out = &bk;
     return TVC_OK;
 }
 
@@ -19,12 +18,12 @@ static int rank_slot(tvc_handle* h, const char* fn, int32_t M, int64_t T, BankSl
 static int rank_tile_setup(tvc_handle* h, const BankSlot& bk, const RankPlan& plan, const float* rows_dev, int32_t M, bool count,
                            RankTileLaunch* L, hipStream_t st) {
     int rc;
-    if ((rc = ensure(h, WS_RK_QPLANES, (size_t)M * 2 * bk.D * 2))) return rc;
+    if ((rc = ensure_planes(h, WS_RK_QPLANES, M, 1, bk.D))) return rc;
     if ((rc = ensure(h, WS_RK_QLAB, (size_t)plan.mpad * 4))) return rc;
     if (count && (rc = ensure(h, WS_RK_TLOW, (size_t)plan.mpad * 4))) return rc;
-    HIP_TRY(launch_split_planes(rows_dev, (uint16_t*)h->ws[WS_RK_QPLANES].p, M, bk.D, 2, st));
+    if ((rc = split_planes(h, WS_RK_QPLANES, rows_dev, M, bk.D, st, &L->qplanes))) return rc;
     L->bank = bank_rows(bk);
-    L->qplanes = (const uint16_t*)h->ws[WS_RK_QPLANES].p; L->M = M;
+    L->M = M;
     L->qlab = (int32_t*)h->ws[WS_RK_QLAB].p;
     L->tlow = count ? (float*)h->ws[WS_RK_TLOW].p : nullptr;
     return TVC_OK;
