@@ -19,6 +19,10 @@ A mask is a yes / no property, so it is read back exactly instead of being infer
                        The needle does NOT check the streaming kernel's softmax VALUES: its 12-nat margin makes
                        everything accumulated before a move of the reference e^-12 of the result, so a wrong rescale
                        passes it.  That is tests/sd_attn_ref.py and tests/test_gpu_sd_attention_values.py.
+                       Nor do the two witnesses check the TOWER kernels' softmax values: they stand at its two ends (q = 0,
+                       every weight 1 / n; the needle, one weight 1), where a wrong scale or a stale denominator changes
+                       nothing.  That is tests/tower_attn_ref.py and tests/test_gpu_tower_attention_values.py: every
+                       config below, per-element fp64 bounds, for attention.hip, the split and the fp32 kernel.
 
 ``kernel`` arguments are callables ``qkv fp32 [rows, 3 * width] -> out [output rows, width]`` (any float dtype); every
 probe value is exact in bf16 and fp16.
