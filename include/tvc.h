@@ -1011,7 +1011,11 @@ int tvc_tower_op(tvc_handle* h, int32_t op, const tvc_tower_op_args* a, void* st
  * antialiased resize of the short side to S (filter 0 = bilinear: torchvision Resize as in
  * experiments/defenses/generative_ref.py:55-59 -- which resizes BOTH sides to S; 1 = bicubic: the CLIP preprocess of
  * src/attacks/hubness_attack.py:223), centre crop, (x - mean[c]) / std[c].  keep_aspect 0 resizes both sides to S.
- * PIL / torch(antialias) filter semantics on float pixels (no uint8 rounding). */
+ * The size rule (the contract; CLIPModel.preprocess follows it): the short side becomes S, the long side
+ * floor(long * S / short + 1/2) -- a half rounds up: 449 x 448 -> 225 x 224 -- and never less than S; the crop starts at
+ * (resized - S) / 2, rounded down.  The filter: scale = in / resized per axis, f = max(scale, 1), support (bilinear 1,
+ * bicubic 2 with a = -0.5) * f around the centre (o + 0.5) * scale, tap argument (i + 0.5 - centre) / f, the taps clipped to
+ * the image and normalised per output pixel, on float pixels (no uint8 rounding). */
 int tvc_preprocess_images(tvc_handle* h, const float* images_dev, int32_t n, int32_t H, int32_t W, int32_t S, int32_t filter,
                           int32_t keep_aspect, const float* mean3, const float* std3, float* out_dev, void* stream);
 

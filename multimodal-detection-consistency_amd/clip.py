@@ -195,13 +195,14 @@ class CLIPModel:
 
     def preprocess(self, image) -> torch.Tensor:
         """PIL image -> fp32 [3, S, S]: bicubic resize of the short side, centre
-        crop, CLIP mean/std."""
+        crop, CLIP mean/std.  The resized size is the rule of ``tvc_preprocess_images`` (include/tvc.h): short side to S,
+        long side floor(long * S / short + 1/2) in integers -- 449 x 448 gives 225 x 224 on both paths."""
         from PIL import Image
         S = self.arch.image_size
         img = image.convert("RGB")
         w, h = img.size
-        s = S / min(w, h)
-        img = img.resize((max(S, round(w * s)), max(S, round(h * s))), Image.BICUBIC)
+        long_side = max(S, (2 * max(w, h) * S + min(w, h)) // (2 * min(w, h)))
+        img = img.resize((S, long_side) if w <= h else (long_side, S), Image.BICUBIC)
         w, h = img.size
         l, t = (w - S) // 2, (h - S) // 2
         img = img.crop((l, t, l + S, t + S))
@@ -213,7 +214,9 @@ class CLIPModel:
     def preprocess_tensor(self, images01: torch.Tensor) -> torch.Tensor:
         """Device images fp32 [n, 3, H, W] with values in [0, 1] -> [n, 3, S, S]: the same bicubic resize of the short side,
         centre crop and CLIP mean / std as ``preprocess``, in one HIP kernel (``tvc_preprocess_images``) -- generated
-        references never leave the GPU.  (``preprocess`` works on 8-bit PIL pixels: the two agree to the 8-bit rounding.)"""
+        references never leave the GPU.  (``preprocess`` works on 8-bit PIL pixels and rounds to 8 bits after each of Pillow's
+        two passes: on smooth images it stays within 2 / 255 / std of the fp64 form of this kernel's rule applied to the same
+        8-bit pixels, tests/test_preprocess_host.py; the kernel is held to that form by tests/test_gpu_preprocess_values.py.)"""
         return self.engine.preprocess_images(images01.to(self.device, torch.float32), self.arch.image_size, CLIP_MEAN, CLIP_STD,
                                              bicubic=True, keep_aspect=True)
 
