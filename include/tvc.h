@@ -529,6 +529,81 @@ int tvc_rank_metrics(tvc_handle* h, int32_t M, const int64_t* tgt_off_dev, const
                      const int32_t* k_values, int32_t n_k, int32_t* pos_dev, double* ap_dev, double* rr_dev,
                      int32_t* hits_dev, double* dcg_dev, double* idcg_dev, void* stream);
 
+/* ---- detection evaluation: the ROC sweep of N scores under B integer weightings --------------------------------- */
+
+/* AUROC, average precision, the Youden threshold, the FPR at a TPR target, the ROC / PR curves and their bootstrap
+ * (src/utils/metrics.py:286-376, 816-874) are functions of the cumulative (TP, FP) counts over the scores in descending
+ * order.  The caller sorts the N scores ONCE (descending, stable in the original index; finite fp32; -0.0 and 0.0 are one tie
+ * group) and passes
+ *   scores_dev  fp32  [N] sorted
+ *   labels_dev  uint8 [N] in sorted order, 0 / 1
+ *   order_dev   int32 [N]: the original index of every sorted position (an entry outside [0, N) weighs nothing)
+ * A ROW weights the N samples by integer multiplicities w >= 0 (total < 2^31); the full sample is w = 1, a bootstrap resample
+ * only changes w.  The multiplicities of the call's B rows come from one of three sources:
+ *   TVC_ROC_SRC_WEIGHTS  src_dev int32 [B, N] over the ORIGINAL indices; NULL = all ones; a negative entry counts as 0
+ *   TVC_ROC_SRC_INDICES  src_dev int32 [B, N] draws in [0, N) (any host RNG: np.random.choice(n, size = n)); a draw outside
+ *                        the range is dropped
+ *   TVC_ROC_SRC_PHILOX   drawn in the kernel, src_dev unused: draw t of resample b = first + row is word t & 3 of
+ *                        Philox4x32-10 with counter (t >> 2, b, 0, 0) and key (seed & 0xffffffff, seed >> 32), mapped to
+ *                        (uint64(x) * N) >> 32 -- a bias of at most N / 2^32.  `first` numbers the resamples across calls,
+ *                        so a call cut into pieces gives the same rows.
+ * The POINTS of a row are the ends of the tie groups whose weight is > 0, in sorted order, each with its cumulative (TP, FP);
+ * P and N are the totals.  A row with P == 0 or N == 0 is invalid: valid = 0 and every other output 0, not an error.
+ *   auc2     int64: sum over the points of (FP_g - FP_{g-1}) * (TP_g + TP_{g-1}); auc = double(auc2) / (2.0 * P * N)
+ *   ap       fp64: sum of ((TP_g - TP_{g-1}) / P) * (TP_g / (TP_g + FP_g)); a fixed order, identical between runs
+ *   curve    sklearn's roc_curve(drop_intermediate = True): a point is KEPT iff it is the first, the last, or the second
+ *            difference of FP or of TP over the points is non-zero at it; the origin (0, 0), threshold +inf, comes first;
+ *            tpr = double(TP) / double(P), fpr = double(FP) / double(N)
+ *   youden   the first arg-max of tpr - fpr over the curve (origin included): its J, sorted position (-1: the origin), TP, FP
+ *   target   the first arg-min of |tpr - target_tpr| over the same curve: sorted position, TP, FP
+ *   thr      for each of n_thr <= TVC_ROC_MAX_THR fp32 thresholds (a HOST array): (TP, FP) of `score >= thr`
+ * Up to TVC_ROC_LDS_ROWS samples a row's multiplicities live in LDS; above, in a handle workspace of at most 1 GiB, and the
+ * rows of the call run in chunks that fit it.  Results never depend on the chunking.  Integer atomics only.
+ * All three calls return TVC_E_INVALID, and launch nothing, for N < 1, N > TVC_ROC_MAX_N, B < 1, first < 0, an unknown source,
+ * n_thr outside [0, TVC_ROC_MAX_THR], a target outside [0, 1] or a NULL required buffer (src_dev with INDICES). */
+#define TVC_ROC_MAX_THR 8
+#define TVC_ROC_LDS_ROWS 36864
+#define TVC_ROC_MAX_N 16777216
+#define TVC_ROC_SRC_WEIGHTS 0
+#define TVC_ROC_SRC_INDICES 1
+#define TVC_ROC_SRC_PHILOX 2
+
+typedef struct tvc_roc_rows {
+    const float* scores_dev;
+    const uint8_t* labels_dev;
+    const int32_t* order_dev;
+    int32_t N;
+    int32_t source;          /* TVC_ROC_SRC_* */
+    const int32_t* src_dev;
+    int64_t B;
+    int64_t first;           /* PHILOX: the resample number of row 0 */
+    uint64_t seed;           /* PHILOX */
+} tvc_roc_rows;
+
+/* per row, device arrays of B entries (thr_*: [B, n_thr], required when n_thr > 0) */
+typedef struct tvc_roc_out {
+    int32_t *n_pos, *n_neg, *valid, *n_points, *n_kept;
+    int64_t* auc2;
+    double *auc, *ap, *youden_j;
+    int32_t *youden_pos, *youden_tp, *youden_fp;
+    int32_t *target_pos, *target_tp, *target_fp;
+    int32_t *thr_tp, *thr_fp;
+} tvc_roc_out;
+
+/* Read-back: w_dev int32 [B, N], the multiplicities of every row over the SORTED positions (w_dev[b, pos] weighs the sample
+ * order[pos]) -- what the sweep gathers, from any source. */
+int tvc_roc_weights(tvc_handle* h, const tvc_roc_rows* rows, int32_t* w_dev, void* stream);
+
+/* The per-row results of every row of the call. */
+int tvc_roc_sweep(tvc_handle* h, const tvc_roc_rows* rows, double target_tpr, const float* thresholds, int32_t n_thr,
+                  const tvc_roc_out* out, void* stream);
+
+/* The points of ONE row (rows->B == 1): pt_tp / pt_fp / pt_pos / pt_kept int32 [N] (the first count_dev[0] entries are
+ * written), count_dev int32 [2] = (points, kept points); an invalid row has (0, 0).  The caller forms fpr / tpr / thresholds
+ * from the kept points and the PR arrays from all of them. */
+int tvc_roc_curve(tvc_handle* h, const tvc_roc_rows* rows, int32_t* pt_tp_dev, int32_t* pt_fp_dev, int32_t* pt_pos_dev,
+                  int32_t* pt_kept_dev, int32_t* count_dev, void* stream);
+
 /* ---- IVF search: probe + list scan over a bank slot ------------------------------------------------ */
 
 /* An IVF index over R rows is four things:

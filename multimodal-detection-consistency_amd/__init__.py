@@ -17,9 +17,9 @@ from .clip import CLIPConfig, CLIPModel
 from .data_validator import DataValidationConfig, DataValidator, ValidationResult, create_data_validator
 from .detector import (AdversarialDetector, ConsistencyChecker, DetectionConfig, DetectorConfig,
                        MultiModalDefenseDetector, aggregate_scores, create_adversarial_detector, unpack_records)
-from .engine import ConsistencyConfig, IVFIndex, RetrievalRanks, TVCEngine
+from .engine import ConsistencyConfig, IVFIndex, RetrievalRanks, RocSweep, TVCEngine
 from .metrics import (DetectionEvaluator, DetectionMetrics, MetricsCalculator, RetrievalEvaluator, RetrievalMetrics,
-                      SimilarityCalculator)
+                      SimilarityCalculator, bootstrap_detection_metrics, bootstrap_metric)
 from .pipeline import (DefensePipeline, MultiModalDetectionPipeline, PipelineConfig, PipelineProfiler,
                        PipelineResult, create_defense_pipeline, create_detection_pipeline)
 from .ref_bank import ReferenceBank, ReferenceBankConfig, ReferenceItem, create_reference_bank

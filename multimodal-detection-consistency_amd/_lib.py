@@ -115,6 +115,23 @@ TOWER_OPS = {name: code for code, name in enumerate((
 GRAD_SPLIT_OPS = {name: code for code, name in enumerate(("gelu_bwd", "l2norm_bwd", "lnpre_bwd", "rows_split_t", "layernorm_bwd"))}
 
 
+class RocRows(C.Structure):
+    """``tvc_roc_rows`` (include/tvc.h)."""
+    _fields_ = [("scores", _P), ("labels", _P), ("order", _P), ("N", C.c_int32), ("source", C.c_int32), ("src", _P),
+                ("B", C.c_int64), ("first", C.c_int64), ("seed", C.c_uint64)]
+
+
+ROC_OUT_FIELDS = ("n_pos", "n_neg", "valid", "n_points", "n_kept", "auc2", "auc", "ap", "youden_j", "youden_pos", "youden_tp",
+                  "youden_fp", "target_pos", "target_tp", "target_fp", "thr_tp", "thr_fp")
+
+
+class RocOut(C.Structure):
+    """``tvc_roc_out`` (include/tvc.h)."""
+    _fields_ = [(n, _P) for n in ROC_OUT_FIELDS]
+
+
+TVC_ROC_SRC_WEIGHTS, TVC_ROC_SRC_INDICES, TVC_ROC_SRC_PHILOX = 0, 1, 2
+
 # name -> (restype, argtypes); must list every symbol include/tvc.h declares
 SIGNATURES = {
     "tvc_abi_version": (C.c_uint32, []),
@@ -142,6 +159,9 @@ SIGNATURES = {
     "tvc_rank_targets": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, _P]),
     "tvc_rank_count": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
     "tvc_rank_metrics": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int64, C.POINTER(C.c_int32), C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "tvc_roc_weights": (C.c_int, [_P, C.POINTER(RocRows), _P, _P]),
+    "tvc_roc_sweep": (C.c_int, [_P, C.POINTER(RocRows), C.c_double, C.POINTER(C.c_float), C.c_int32, C.POINTER(RocOut), _P]),
+    "tvc_roc_curve": (C.c_int, [_P, C.POINTER(RocRows), _P, _P, _P, _P, _P, _P]),
     "tvc_ivf_probe": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     "tvc_ivf_scan": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P, _P]),
     "tvc_topk_merge": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

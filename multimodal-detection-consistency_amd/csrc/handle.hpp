@@ -4,7 +4,8 @@
 // split-bf16 towers' stem, layer loop, head and weight planes; tvc_sd.cpp: latent-diffusion reference generator,
 // tvc_sd_op.cpp: its entry points that read no model state; tvc_kmeans.cpp: k-means over a bank slot;
 // tvc_ivf.cpp: IVF probe and list scan; tvc_grad_split.cpp: the split-bf16 input gradient; tvc_dbscan.cpp: radius graph and
-// DBSCAN labels; tvc_pairs.cpp: pair lists of a bitmask graph and the cosine of listed pairs; tvc_rank.cpp: retrieval evaluation).
+// DBSCAN labels; tvc_pairs.cpp: pair lists of a bitmask graph and the cosine of listed pairs; tvc_rank.cpp: retrieval evaluation;
+// tvc_roc.cpp: detection evaluation).
 // The entry points that pass over a bank slot share filled_slot (the TVC_E_STATE refusal of an empty slot) and ensure_planes /
 // split_planes (a workspace slot of (hi | lo) query planes); their work estimate is host_plan.hpp's slot_pass_flops.
 #pragma once
@@ -51,6 +52,8 @@ enum Slot {
     WS_DB_NORM2, WS_DB_HALF,
     // retrieval evaluation (tvc_rank.cpp): the query planes, the query labels and the last-target scores padded to whole tiles
     WS_RK_QPLANES, WS_RK_QLAB, WS_RK_TLOW,
+    // detection evaluation (tvc_roc.cpp): the multiplicity rows of the global storage form, uint32 [chunk rows, N]
+    WS_ROC_COUNTS,
     WS_COUNT
 };
 

@@ -109,6 +109,47 @@ inline bool rank_k_values_ok(const int32_t* k, int n_k) {
     return true;
 }
 
+// Detection evaluation (roc.hip): one workgroup of ROC_THREADS threads per row (a weighting of the N samples by integer
+// multiplicities).  The row's multiplicities are uint32 counts over the N original indices; up to ROC_LDS_ROWS samples they live
+// in LDS -- 144 KiB of the CU's 160 KiB, the other 16 KiB hold the sweep's scratch (ROC_THREADS points of 12 bytes, the waves'
+// partials, the final reduction) -- and above it in a row of a global workspace, roc_ws_stride(N) uint32 per row of the call (whole
+// 128-byte lines: two rows, whose workgroups may run on two XCDs, never share a cache line).  The rows of a
+// call are cut into chunks so that the workspace of a chunk stays under ROC_WS_BUDGET; a row's results do not depend on the
+// chunk it runs in.  ROC_MAX_N is include/tvc.h's TVC_ROC_MAX_N, ROC_MAX_THR its TVC_ROC_MAX_THR.
+// ok = false: N < 1, B < 1, N over the cap, more than ROC_MAX_THR thresholds or a negative count, a target outside [0, 1] (or NaN).
+#define ROC_THREADS 1024
+#define ROC_LDS_ROWS 36864
+#define ROC_MAX_N (1 << 24)
+#define ROC_MAX_THR 8
+#define ROC_WS_BUDGET ((int64_t)1 << 30)        // 268 rows of a million samples: such a chunk still covers every CU; 16 rows at the cap
+constexpr int64_t roc_ws_stride(int64_t N) { return (N + 31) / 32 * 32; }      // constexpr: the kernel calls it too
+struct RocPlan {
+    bool ok = false;
+    bool lds = false;                   // the storage form: LDS, or a global workspace row
+    size_t lds_bytes = 0;               // dynamic LDS of the LDS form: N uint32 rounded up to 16 bytes
+    int64_t chunk_rows = 0;             // rows per launch
+    int64_t n_chunks = 0;
+    int64_t ws_bytes = 0;               // global workspace of one chunk (0 in the LDS form)
+};
+inline RocPlan roc_plan(int64_t N, int64_t B, int n_thr, double target) {
+    RocPlan p;
+    if (N < 1 || B < 1 || N > ROC_MAX_N || n_thr < 0 || n_thr > ROC_MAX_THR || !(target >= 0.0 && target <= 1.0)) return p;
+    p.lds = N <= ROC_LDS_ROWS;
+    if (p.lds) {
+        p.lds_bytes = (size_t)((N * 4 + 15) / 16 * 16);
+        p.chunk_rows = B;
+        p.n_chunks = 1;
+    } else {
+        int64_t rows = ROC_WS_BUDGET / (roc_ws_stride(N) * 4);      // >= 16: at the cap
+        if (rows > B) rows = B;
+        p.chunk_rows = rows;
+        p.n_chunks = (B + rows - 1) / rows;
+        p.ws_bytes = rows * roc_ws_stride(N) * 4;
+    }
+    p.ok = true;
+    return p;
+}
+
 // Radius graph / DBSCAN (dbscan.hip): the graph of R rows is a bitmask uint32 [R, words], words = round_up(R, 64) / 32 (an even
 // count: a wave of the tile kernel stores one 64-bit word per row).  The tile kernel's grid is tiles x tiles 256 x 256 tiles of
 // which the upper triangle computes; the half-norm vector is padded to whole tiles (hpad floats, NaN beyond R).  The

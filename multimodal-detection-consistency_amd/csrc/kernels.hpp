@@ -221,6 +221,40 @@ struct RankMetricsLaunch {
 };
 hipError_t launch_rank_metrics(const RankMetricsLaunch& L, hipStream_t stream);
 
+// ---- roc.hip: detection evaluation (ROC sweep of N sorted scores under B integer weightings: AUROC, AP, Youden, FPR at a TPR)
+enum RocSource { ROC_SRC_WEIGHTS = 0, ROC_SRC_INDICES = 1, ROC_SRC_PHILOX = 2 };
+enum RocMode { ROC_MODE_WEIGHTS = 0, ROC_MODE_SWEEP = 1, ROC_MODE_CURVE = 2 };
+struct RocLaunch {
+    int mode = ROC_MODE_SWEEP;
+    int source = ROC_SRC_WEIGHTS;
+    int N = 0;
+    int64_t B = 0;                    // rows of this launch
+    int64_t row0 = 0;                 // the first row's place in the caller's arrays (src and every output)
+    int64_t first = 0;                // PHILOX: the resample number of the caller's row 0
+    uint64_t seed = 0;
+    const float* scores = nullptr;    // [N] sorted descending
+    const uint8_t* labels = nullptr;  // [N] in sorted order, 0 / 1
+    const int32_t* order = nullptr;   // [N]: the original index of every sorted position
+    const int32_t* src = nullptr;     // WEIGHTS: [B, N] multiplicities or nullptr (all ones); INDICES: [B, N] draws
+    uint32_t* ws = nullptr;           // the global form's counts [B, roc_ws_stride(N)]; nullptr = the LDS form
+    size_t lds_bytes = 0;             // the LDS form's dynamic LDS (roc_plan)
+    double target = 0.95;
+    int n_thr = 0;
+    float thr[ROC_MAX_THR] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    int32_t* w_out = nullptr;         // ROC_MODE_WEIGHTS: [B, N] multiplicities over the sorted positions
+    // ROC_MODE_SWEEP, per row
+    int32_t *n_pos = nullptr, *n_neg = nullptr, *valid = nullptr, *n_points = nullptr, *n_kept = nullptr;
+    int64_t* auc2 = nullptr;
+    double *auc = nullptr, *ap = nullptr, *youden_j = nullptr;
+    int32_t *youden_pos = nullptr, *youden_tp = nullptr, *youden_fp = nullptr;
+    int32_t *target_pos = nullptr, *target_tp = nullptr, *target_fp = nullptr;
+    int32_t *thr_tp = nullptr, *thr_fp = nullptr;       // [B, n_thr]
+    // ROC_MODE_CURVE (B = 1): the points and their count
+    int32_t *pt_tp = nullptr, *pt_fp = nullptr, *pt_pos = nullptr, *pt_kept = nullptr;      // [N]
+    int32_t* pt_count = nullptr;      // [2]: points, kept points
+};
+hipError_t launch_roc(const RocLaunch& L, hipStream_t stream);
+
 // ---- dbscan.hip: the eps-graph of a bank slot as a bitmask, and DBSCAN's labels from such a graph (exact integer work)
 struct RadiusGraphLaunch {
     BankRows bank;

@@ -343,6 +343,33 @@ class AdversarialDetector:
 
     detect = detect_adversarial
 
+    # -- threshold from validation data (src/detector.py:736-779) --------------
+    @staticmethod
+    def optimal_threshold_from_scores(scores, labels, engine=None) -> float:
+        """The score threshold that maximises TPR - FPR over the ROC curve of (labels, scores): ``roc_curve`` +
+        ``argmax(tpr - fpr)`` (src/detector.py:758-762), from the GPU sweep (``TVCEngine.roc_sweep``).  +inf when no threshold
+        beats flagging nothing."""
+        from .metrics import _engine
+        sw = _engine(engine).roc_sweep(scores, np.asarray(labels).astype(np.int64))
+        return sw.threshold_at(int(sw.youden_pos[0]))
+
+    def compute_optimal_threshold(self, validation_data, methods: Optional[List[str]] = None) -> float:
+        """src/detector.py:736-769: validation_data = [(image, text, is_adversarial), ...] -> the Youden threshold of the
+        aggregated scores (one ``batch_detect``, then the sweep); the configured threshold when anything fails, as the
+        reference returns it."""
+        try:
+            images, texts, flags = zip(*validation_data)
+            batch = torch.stack(list(images)) if all(isinstance(i, torch.Tensor) for i in images) else list(images)
+            results = self.batch_detect(batch, list(texts), methods)
+            scores = [r["aggregated_score"] for r in results]
+            return float(self.optimal_threshold_from_scores(scores, [int(f) for f in flags], self._get_clip_model().engine))
+        except Exception:
+            return self.config.detection_threshold
+
+    def update_threshold(self, new_threshold: float) -> None:
+        """src/detector.py:771-779."""
+        self.config.detection_threshold = new_threshold
+
     @staticmethod
     def _cache_key(image, text, methods) -> str:
         """src/detector.py:684-709."""

@@ -82,6 +82,39 @@ class RetrievalRanks:
         return self.tgt_off[1:] - self.tgt_off[:-1]
 
 
+@dataclass
+class RocSweep:
+    """What ``TVCEngine.roc_sweep`` returns: the sorted sample and the per-row results of ``tvc_roc_sweep`` (include/tvc.h).
+    Row 0 is the full sample (every multiplicity 1), rows 1 .. are the resamples / weightings asked for.  An invalid row (no
+    positive or no negative weight) has ``valid == 0`` and zeros everywhere else."""
+    scores: torch.Tensor         # fp32 [N] sorted descending (stable); -0.0 became 0.0
+    labels: torch.Tensor         # uint8 [N] in sorted order
+    order: torch.Tensor          # int32 [N]: the original index of every sorted position
+    target_tpr: float
+    thresholds: Tuple[float, ...]
+    n_pos: torch.Tensor          # int32 [R]
+    n_neg: torch.Tensor          # int32 [R]
+    valid: torch.Tensor          # int32 [R]
+    n_points: torch.Tensor       # int32 [R]: tie groups of weight > 0
+    n_kept: torch.Tensor         # int32 [R]: the points sklearn's drop_intermediate keeps
+    auc2: torch.Tensor           # int64 [R]: auc = auc2 / (2 P N)
+    auc: torch.Tensor            # fp64 [R]
+    ap: torch.Tensor             # fp64 [R]
+    youden_j: torch.Tensor       # fp64 [R]
+    youden_pos: torch.Tensor     # int32 [R]: sorted position of the Youden point, -1 = the origin (threshold +inf)
+    youden_tp: torch.Tensor      # int32 [R]
+    youden_fp: torch.Tensor      # int32 [R]
+    target_pos: torch.Tensor     # int32 [R]: as youden_pos, of the point nearest to target_tpr
+    target_tp: torch.Tensor      # int32 [R]
+    target_fp: torch.Tensor      # int32 [R]
+    thr_tp: torch.Tensor         # int32 [R, len(thresholds)]: TP of score >= threshold
+    thr_fp: torch.Tensor         # int32 [R, len(thresholds)]
+
+    def threshold_at(self, pos: int) -> float:
+        """The score threshold of a reported sorted position: +inf for the origin (-1)."""
+        return float("inf") if pos < 0 else float(self.scores[pos])
+
+
 def _stream() -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -849,6 +882,119 @@ class TVCEngine:
             hist = self.rank_count(rows, qlabel, glabel, tgt_off, tgt_sim, tgt_row, bank=bank)
             pos, ap, rr, hits, dcg, idcg = self.rank_metrics(tgt_off, hist, ks, bank=bank)
         return RetrievalRanks(ks, tgt_off, tgt_row, tgt_sim, pos, hist, ap, rr, hits, dcg, idcg)
+
+    # ---- detection evaluation: ROC sweep under integer weightings -----------
+    ROC_LDS_ROWS = 36864          # TVC_ROC_LDS_ROWS: up to this many samples a row's multiplicities live in LDS
+    ROC_MAX_THR = 8               # TVC_ROC_MAX_THR
+    ROC_MAX_N = 1 << 24           # TVC_ROC_MAX_N
+
+    def roc_prepare(self, scores, labels, pos_label=1):
+        """scores [N] (finite; taken as fp32), labels [N] -> (scores fp32 [N] sorted descending and stably, labels uint8 [N] =
+        ``labels == pos_label`` in sorted order, order int32 [N]) on the engine's device: the three arrays every ``tvc_roc_*``
+        call takes.  ``-0.0`` becomes ``0.0`` first (one tie group).  ``ValueError`` for N < 1, N > ``ROC_MAX_N``, a length
+        mismatch or a non-finite score (as sklearn raises), before anything is sorted."""
+        s = torch.as_tensor(scores).reshape(-1)
+        lab = torch.as_tensor(labels).reshape(-1)
+        N = s.numel()
+        if N < 1 or N > self.ROC_MAX_N:
+            raise ValueError(f"need 1 <= N <= {self.ROC_MAX_N} scores (got {N})")
+        if lab.numel() != N:
+            raise ValueError(f"need {N} labels (got {lab.numel()})")
+        with torch.cuda.device(self.device):
+            s = s.to(self.device, torch.float32)
+            if not bool(torch.isfinite(s).all()):
+                raise ValueError("scores must be finite (NaN or infinity found)")
+            s = s + 0.0
+            lab = (lab.to(self.device) == pos_label).to(torch.uint8)
+            ss, order = torch.sort(s, descending=True, stable=True)
+            return ss.contiguous(), lab[order].contiguous(), order.to(torch.int32).contiguous()
+
+    def _roc_rows(self, prepared, n_resamples, weights, indices, seed, first):
+        """-> (``_lib.RocRows``, B, what must stay alive): the source of a call's rows.  ``weights`` / ``indices`` int [B, N] over
+        the original indices; neither and ``n_resamples`` > 0: Philox draws; neither and 0: one row of ones."""
+        ss, sl, order = prepared
+        N = ss.numel()
+        if weights is not None and indices is not None:
+            raise ValueError("give weights or indices, not both")
+        src, source, B = None, _lib.TVC_ROC_SRC_WEIGHTS, 1
+        if weights is not None or indices is not None:
+            src = torch.as_tensor(weights if weights is not None else indices).to(self.device, torch.int32)
+            src = (src.reshape(1, -1) if src.dim() == 1 else src).contiguous()
+            if src.dim() != 2 or src.shape[1] != N or src.shape[0] < 1:
+                raise ValueError(f"weights / indices must be [B >= 1, {N}] (got {tuple(src.shape)})")
+            B = src.shape[0]
+            if indices is not None:
+                source = _lib.TVC_ROC_SRC_INDICES
+            elif int(src.to(torch.int64).clamp(min=0).sum(1).max()) >= 1 << 31:
+                raise ValueError("the total weight of a row must be < 2^31")
+        elif n_resamples > 0:
+            source, B = _lib.TVC_ROC_SRC_PHILOX, int(n_resamples)
+        rows = _lib.RocRows(ss.data_ptr(), sl.data_ptr(), order.data_ptr(), N, source, 0 if src is None else src.data_ptr(), B,
+                            int(first), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        return rows, B, (ss, sl, order, src)
+
+    def roc_weights(self, scores, labels, *, n_resamples: int = 0, weights=None, indices=None, seed: int = 0, first: int = 0,
+                    pos_label=1) -> torch.Tensor:
+        """``tvc_roc_weights``: int32 [B, N], the multiplicities of every row of the source over the SORTED positions (column
+        ``pos`` weighs the sample ``order[pos]`` of ``roc_prepare``)."""
+        prepared = self.roc_prepare(scores, labels, pos_label)
+        with self._lock, torch.cuda.device(self.device):
+            rows, B, keep = self._roc_rows(prepared, n_resamples, weights, indices, seed, first)
+            w = torch.empty((B, rows.N), dtype=torch.int32, device=self.device)
+            self._check(self.lib.tvc_roc_weights(self.handle, C.byref(rows), _ptr(w), _stream()))
+        return w
+
+    def roc_sweep(self, scores, labels, *, n_resamples: int = 0, weights=None, indices=None, seed: int = 0,
+                  target_tpr: float = 0.95, thresholds=(), pos_label=1, first: int = 0) -> RocSweep:
+        """The ROC sweep of the full sample (row 0) and of B further rows: ``weights`` / ``indices`` int [B, N] over the original
+        indices, or ``n_resamples`` Philox resamples numbered ``first`` .. (``seed``).  ``ValueError``, before any launch, for
+        non-finite scores, N over ``ROC_MAX_N``, a full sample of one class, more than ``ROC_MAX_THR`` thresholds, a NaN
+        threshold or a target outside [0, 1]."""
+        thr = tuple(float(t) for t in thresholds)
+        if len(thr) > self.ROC_MAX_THR or any(t != t for t in thr):
+            raise ValueError(f"need at most {self.ROC_MAX_THR} thresholds, none NaN (got {thr})")
+        if not 0.0 <= float(target_tpr) <= 1.0:
+            raise ValueError(f"target_tpr must lie in [0, 1] (got {target_tpr})")
+        prepared = self.roc_prepare(scores, labels, pos_label)
+        n_pos = int(prepared[1].sum())
+        if n_pos == 0 or n_pos == prepared[1].numel():
+            raise ValueError("only one class present in labels: the ROC sweep is not defined")
+        extra = weights is not None or indices is not None or n_resamples > 0
+        with self._lock, torch.cuda.device(self.device):
+            rows, B, keep = self._roc_rows(prepared, n_resamples, weights, indices, seed, first)
+            R = 1 + (B if extra else 0)
+            n_thr = len(thr)
+            dt = {"auc2": torch.int64, "auc": torch.float64, "ap": torch.float64, "youden_j": torch.float64}
+            out = {n: torch.empty((R, n_thr) if n.startswith("thr_") else (R,), dtype=dt.get(n, torch.int32), device=self.device)
+                   for n in _lib.ROC_OUT_FIELDS}
+            tarr = (C.c_float * max(n_thr, 1))(*thr)
+            full = _lib.RocRows(rows.scores, rows.labels, rows.order, rows.N, _lib.TVC_ROC_SRC_WEIGHTS, 0, 1, 0, 0)
+            calls = [(full, 0)] + ([(rows, 1)] if extra else [])
+            for r, at in calls:
+                o = _lib.RocOut(*[out[n][at:].data_ptr() if out[n][at:].numel() else 0 for n in _lib.ROC_OUT_FIELDS])
+                self._check(self.lib.tvc_roc_sweep(self.handle, C.byref(r), float(target_tpr), tarr, n_thr, C.byref(o), _stream()))
+        return RocSweep(prepared[0], prepared[1], prepared[2], float(target_tpr), thr, **out)
+
+    def roc_curve(self, scores, labels, *, weights=None, pos_label=1):
+        """``tvc_roc_curve`` of one row (``weights`` int [N] over the original indices; None: the full sample) -> (tp, fp, pos,
+        kept int32 [points], sorted scores fp32 [N], P, N): every tie group of weight > 0 with its cumulative counts, the sorted
+        position of its end and sklearn's drop_intermediate verdict.  Synchronises (it reads the count).  ``ValueError`` when the
+        row has no positive or no negative weight."""
+        prepared = self.roc_prepare(scores, labels, pos_label)
+        with self._lock, torch.cuda.device(self.device):
+            rows, B, keep = self._roc_rows(prepared, 0, weights, None, 0, 0)
+            if B != 1:
+                raise ValueError("roc_curve takes one row of weights")
+            N = rows.N
+            pts = torch.empty((4, N), dtype=torch.int32, device=self.device)
+            count = torch.zeros(2, dtype=torch.int32, device=self.device)
+            self._check(self.lib.tvc_roc_curve(self.handle, C.byref(rows), _ptr(pts[0]), _ptr(pts[1]), _ptr(pts[2]), _ptr(pts[3]),
+                                               _ptr(count), _stream()))
+            n = int(count[0])
+        if n == 0:
+            raise ValueError("only one class present in labels: the ROC curve is not defined")
+        tp, fp, pos, kept = (pts[i, :n] for i in range(4))
+        return tp, fp, pos, kept, prepared[0], int(tp[-1]), int(fp[-1])
 
     # ---- radius graph of a bank slot, DBSCAN on a radius graph -------------
     DBSCAN_SWEEP_BATCH = 4

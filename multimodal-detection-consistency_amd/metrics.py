@@ -1,7 +1,8 @@
 """``SimilarityCalculator`` (``src/utils/metrics.py:109-164``) over the HIP cosine
-kernel, ``DetectionEvaluator.compute_detection_metrics`` (``:286-329``), which
-stays sklearn on the host exactly as in the reference, and the
-retrieval metrics (``:70-86,379-573,951-972``): the dense form on the host, the
+kernel; the detection metrics (``:286-376,816-874``): ``compute_detection_metrics``
+stays sklearn on the host exactly as in the reference, while ``evaluate_scores``, the
+ROC / PR curves and the bootstrap run over the HIP ROC-sweep kernels;
+and the retrieval metrics (``:70-86,379-573,951-972``): the dense form on the host, the
 label form over the HIP rank-count kernels."""
 from __future__ import annotations
 
@@ -89,6 +90,109 @@ class DetectionEvaluator:
             f1_score=float(f1_score(labels, pred, pos_label=pos_label, zero_division=0)),
             fpr_at_95_tpr=float(fpr[i95]), threshold=float(thr[j]),
             confusion_matrix=confusion_matrix(labels, pred))
+
+    @staticmethod
+    def from_counts(auc: float, tp: int, fp: int, n_pos: int, n_neg: int, target_fp: int, threshold: float) -> DetectionMetrics:
+        """The reference's fields from the integers of a sweep row: the prediction ``score >= threshold`` has ``tp`` true and
+        ``fp`` false positives among ``n_pos`` positives and ``n_neg`` negatives (zero_division = 0)."""
+        acc, prec, rec, f1 = _confusion_metrics(tp, fp, n_pos, n_neg)
+        return DetectionMetrics(auc=float(auc), accuracy=float(acc), precision=float(prec), recall=float(rec), f1_score=float(f1),
+                                fpr_at_95_tpr=float(np.float64(target_fp) / np.float64(n_neg)), threshold=float(threshold),
+                                confusion_matrix=np.array([[n_neg - fp, fp], [n_pos - tp, tp]], dtype=np.int64))
+
+    @staticmethod
+    def evaluate_scores(scores, labels, pos_label: int = 1, engine: Optional[TVCEngine] = None) -> DetectionMetrics:
+        """``compute_detection_metrics`` on the GPU (``TVCEngine.roc_sweep``): scores taken as fp32, every field from the
+        sweep's integers.  The Youden threshold is +inf when no threshold beats predicting nothing; it then predicts nothing."""
+        sw = _engine(engine).roc_sweep(scores, labels, pos_label=pos_label)
+        r = {n: getattr(sw, n)[0].item() for n in ("auc", "youden_pos", "youden_tp", "youden_fp", "n_pos", "n_neg", "target_fp")}
+        return DetectionEvaluator.from_counts(r["auc"], r["youden_tp"], r["youden_fp"], r["n_pos"], r["n_neg"], r["target_fp"],
+                                              sw.threshold_at(r["youden_pos"]))
+
+    @staticmethod
+    def compute_roc_curve(scores, labels, pos_label: int = 1, engine: Optional[TVCEngine] = None):
+        """src/utils/metrics.py:348-360 -> (fpr, tpr, thresholds) fp64, sklearn's ``roc_curve`` (drop_intermediate) from the
+        points of ``TVCEngine.roc_curve``: the origin with threshold +inf, then the kept points."""
+        tp, fp, pos, kept, ss, P, Nn = _engine(engine).roc_curve(scores, labels, pos_label=pos_label)
+        k = kept.bool()
+        tpk, fpk = tp[k].cpu().numpy().astype(np.float64), fp[k].cpu().numpy().astype(np.float64)
+        thr = ss[pos[k].long()].cpu().numpy().astype(np.float64)
+        return np.r_[0.0, fpk / np.float64(Nn)], np.r_[0.0, tpk / np.float64(P)], np.r_[np.inf, thr]
+
+    @staticmethod
+    def compute_pr_curve(scores, labels, pos_label: int = 1, engine: Optional[TVCEngine] = None):
+        """src/utils/metrics.py:363-376 -> (precision, recall, thresholds) fp64, sklearn's ``precision_recall_curve``: every
+        point of ``TVCEngine.roc_curve`` in ascending threshold order, then (1, 0)."""
+        tp, fp, pos, kept, ss, P, Nn = _engine(engine).roc_curve(scores, labels, pos_label=pos_label)
+        tpa, fpa = tp.cpu().numpy().astype(np.float64), fp.cpu().numpy().astype(np.float64)
+        thr = ss[pos.long()].cpu().numpy().astype(np.float64)
+        return np.r_[(tpa / (tpa + fpa))[::-1], 1.0], np.r_[(tpa / np.float64(P))[::-1], 0.0], thr[::-1].copy()
+
+
+def _confusion_metrics(tp, fp, n_pos, n_neg):
+    """accuracy, precision, recall, f1 (zero_division = 0) of counts, scalars or arrays, in fp64"""
+    tp, fp, P, Nn = (np.asarray(x, dtype=np.float64) for x in (tp, fp, n_pos, n_neg))
+    some = tp + fp > 0
+    return ((tp + (Nn - fp)) / (P + Nn), np.where(some, tp / np.where(some, tp + fp, 1.0), 0.0), tp / P,
+            2.0 * tp / (2.0 * tp + fp + (P - tp)))
+
+
+BOOTSTRAP_METRICS = ("auc", "ap", "accuracy", "precision", "recall", "f1", "fpr_at_95_tpr")
+
+
+def _summary(values, confidence: float) -> Dict[str, float]:
+    """src/utils/metrics.py:857-874"""
+    if len(values) == 0:
+        return {"mean": 0.0, "lower": 0.0, "upper": 0.0}
+    alpha = 1 - confidence
+    return {"mean": np.mean(values), "lower": np.percentile(values, (alpha / 2) * 100),
+            "upper": np.percentile(values, (1 - alpha / 2) * 100), "std": np.std(values)}
+
+
+def bootstrap_detection_metrics(scores, labels, n_bootstrap: int = 1000, confidence: float = 0.95, seed: int = 0, indices=None,
+                                pos_label: int = 1, engine: Optional[TVCEngine] = None) -> Dict[str, Dict[str, float]]:
+    """The bootstrap of every metric of ``BOOTSTRAP_METRICS`` from ONE sweep of ``n_bootstrap`` resamples: name -> the
+    reference's dict (mean, lower, upper, std).  The resamples are Philox draws on the device (``seed``) or the caller's
+    ``indices`` int [B, N] (any host RNG: ``np.random.choice(n, size=n, replace=True)`` per row reproduces the reference's).
+    accuracy / precision / recall / f1 are taken at the FULL sample's Youden threshold; resamples with one class are dropped,
+    as the reference drops the metric's exception; the percentiles are ``np.percentile`` over the kept values."""
+    eng = _engine(engine)
+    full = eng.roc_sweep(scores, labels, pos_label=pos_label)
+    thr = full.threshold_at(int(full.youden_pos[0]))
+    sw = eng.roc_sweep(scores, labels, n_resamples=0 if indices is not None else int(n_bootstrap), indices=indices, seed=seed,
+                       thresholds=(thr,), pos_label=pos_label)
+    r = {n: getattr(sw, n)[1:].cpu().numpy() for n in ("valid", "auc", "ap", "n_pos", "n_neg", "target_fp", "thr_tp", "thr_fp")}
+    ok = r["valid"] == 1
+    P, Nn = r["n_pos"][ok], r["n_neg"][ok]
+    acc, prec, rec, f1 = _confusion_metrics(r["thr_tp"][ok, 0], r["thr_fp"][ok, 0], P, Nn)
+    values = {"auc": r["auc"][ok], "ap": r["ap"][ok], "accuracy": acc, "precision": prec, "recall": rec, "f1": f1,
+              "fpr_at_95_tpr": r["target_fp"][ok].astype(np.float64) / Nn.astype(np.float64)}
+    return {name: _summary(values[name], confidence) for name in BOOTSTRAP_METRICS}
+
+
+def bootstrap_metric(metric, scores, labels, n_bootstrap: int = 1000, confidence: float = 0.95, seed: int = 0, indices=None,
+                     engine: Optional[TVCEngine] = None) -> Dict[str, float]:
+    """src/utils/metrics.py:816-874.  ``metric`` is one of ``BOOTSTRAP_METRICS`` (the GPU sweep: ``bootstrap_detection_metrics``)
+    or a callable, which keeps the reference's host loop: ``metric(scores[idx], labels[idx])`` over ``np.random.choice`` draws
+    of the legacy global stream (or the rows of ``indices``), values that are not a number and calls that raise dropped."""
+    if callable(metric):
+        args = [np.asarray(scores), np.asarray(labels)]
+        n = len(args[0])
+        if n == 0:
+            return {"mean": 0.0, "lower": 0.0, "upper": 0.0}
+        values = []
+        for b in range(n_bootstrap if indices is None else len(indices)):
+            idx = np.random.choice(n, size=n, replace=True) if indices is None else np.asarray(indices[b])
+            try:
+                v = metric(*[a[idx] for a in args])
+            except Exception:
+                continue
+            if isinstance(v, (int, float)) and not np.isnan(v):
+                values.append(v)
+        return _summary(values, confidence)
+    if metric not in BOOTSTRAP_METRICS:
+        raise ValueError(f"metric must be a callable or one of {BOOTSTRAP_METRICS} (got {metric!r})")
+    return bootstrap_detection_metrics(scores, labels, n_bootstrap, confidence, seed, indices, engine=engine)[metric]
 
 
 @dataclass
