@@ -463,6 +463,31 @@ int tvc_graph_pair_fill(tvc_handle* h, const uint32_t* adj_dev, int32_t R, const
  * and launches nothing. */
 int tvc_pair_cosine(tvc_handle* h, const int32_t* pairs_dev, int64_t P, float* sim_dev, void* stream);
 
+/* ---- the closest pair of a bank slot -------------------------------------------------------------------------- */
+
+/* Similarity eviction (src/ref_bank.py:395-427) asks a full bank for its most similar pair of stored vectors, which the
+ * reference finds with a double loop over i < j.  Here it is one upper-triangle self-GEMM of the selected slot (any [R, D]
+ * matrix; the rows need not be unit length) whose scores never leave the MFMA accumulators: a bf16 slot multiplies its stored
+ * values, an fp32 slot all four hi / lo plane products, as tvc_radius_graph.
+ *   partner_dev   int32 [R]: partner[i] = the arg-max over j > i of cos(x_i, x_j), (value descending, j ascending); -1 where
+ *                 row i has no admissible later row: the last row, a row whose squared norm is not finite, a row all of
+ *                 whose later rows have a non-finite norm
+ *   sim_dev       fp32 [R]: that cosine, (x_i . x_j) / |x_j| / |x_i| in fp32; -inf where partner is -1
+ *   pair_dev      int32 [2]: (i, partner[i]) of the best row under (sim descending, i ascending): the first maximal pair in
+ *                 lexicographic (i, j) order, the pair a strict `>` over the reference's loops keeps; (-1, -1) when no row has
+ *                 a partner
+ *   pair_sim_dev  fp32 [1]: its cosine; -inf for (-1, -1)
+ * An all-zero row has cosine 0 with every row (the reference's _cosine_similarity).  A row of non-finite norm is never a
+ * partner.  With c64 = the fp64 cosine of the stored rows and tau = 1e-6:  |sim[i] - c64(i, partner[i])| <= tau  and
+ * c64(i, partner[i]) >= max_{j > i} c64(i, j) - 2 tau,  and the same for pair / pair_sim over all i < j; where the
+ * arithmetic is exact (rows of one common norm with a power-of-two 1 / norm and small-integer dot products) every tie falls
+ * as stated above.  No atomics and no floating-point reduction across workgroups: the outputs are a pure function of the
+ * slot, bit-identical between runs.
+ * TVC_E_INVALID when h is NULL, the slot holds no bank, R < 1, an output is NULL or D is not a multiple of 64.  R == 1 is
+ * legal and yields partner = -1, pair = (-1, -1).  Nothing is launched on a refusal. */
+int tvc_closest_pair(tvc_handle* h, int32_t* partner_dev /*[R]*/, float* sim_dev /*[R]*/, int32_t* pair_dev /*[2]*/,
+                     float* pair_sim_dev /*[1]*/, void* stream);
+
 /* ---- retrieval evaluation over a bank slot: the rank of every relevant row ------------------------------------ */
 
 /* Recall@K, Precision@K, mAP, MRR and NDCG@K (src/utils/metrics.py:379-573) are pure functions of the POSITIONS of a query's

@@ -156,6 +156,7 @@ SIGNATURES = {
     "tvc_graph_pair_count": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P]),
     "tvc_graph_pair_fill": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int64, _P]),
     "tvc_pair_cosine": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    "tvc_closest_pair": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "tvc_rank_targets": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, _P]),
     "tvc_rank_count": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
     "tvc_rank_metrics": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int64, C.POINTER(C.c_int32), C.c_int32, _P, _P, _P, _P, _P, _P, _P]),

@@ -5,7 +5,7 @@
 // tvc_sd_op.cpp: its entry points that read no model state; tvc_kmeans.cpp: k-means over a bank slot;
 // tvc_ivf.cpp: IVF probe and list scan; tvc_grad_split.cpp: the split-bf16 input gradient; tvc_dbscan.cpp: radius graph and
 // DBSCAN labels; tvc_pairs.cpp: pair lists of a bitmask graph and the cosine of listed pairs; tvc_rank.cpp: retrieval evaluation;
-// tvc_roc.cpp: detection evaluation).
+// tvc_roc.cpp: detection evaluation; tvc_nearest.cpp: closest pair of a bank slot).
 // The entry points that pass over a bank slot share filled_slot (the TVC_E_STATE refusal of an empty slot) and ensure_planes /
 // split_planes (a workspace slot of (hi | lo) query planes); their work estimate is host_plan.hpp's slot_pass_flops.
 #pragma once
@@ -54,6 +54,8 @@ enum Slot {
     WS_RK_QPLANES, WS_RK_QLAB, WS_RK_TLOW,
     // detection evaluation (tvc_roc.cpp): the multiplicity rows of the global storage form, uint32 [chunk rows, N]
     WS_ROC_COUNTS,
+    // closest pair of a bank slot (tvc_nearest.cpp): the padded 1 / |x| vector
+    WS_NN_RINV,
     WS_COUNT
 };
 

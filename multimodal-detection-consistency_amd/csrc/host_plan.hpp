@@ -180,6 +180,26 @@ inline RadiusPlan radius_plan(int64_t R) {
     return p;
 }
 
+// Closest pair of a bank slot (nearest.hip): the workgroup of row tile ti walks the partner tiles ti .. tiles - 1, so the pass
+// multiplies the radius graph's upper triangle; the 1 / |x| vector is padded to whole tiles (rpad floats, NaN beyond R).
+// NEAREST_MAX_ROWS: row ids and rpad stay in int32.  ok = false: R outside [1, NEAREST_MAX_ROWS].
+#define NEAREST_MAX_ROWS (0x7fffffffLL - HOST_PLAN_GEMM_BM)
+struct NearestPlan {
+    bool ok = false;
+    int tiles = 0;                      // 256-row tiles = workgroups of the tile kernel
+    int64_t rpad = 0;                   // floats of the padded 1 / |x| vector
+    double tile_pairs = 0;              // computed tiles: tiles * (tiles + 1) / 2
+};
+inline NearestPlan nearest_plan(int64_t R) {
+    NearestPlan p;
+    if (R < 1 || R > NEAREST_MAX_ROWS) return p;
+    p.tiles = (int)((R + HOST_PLAN_GEMM_BM - 1) / HOST_PLAN_GEMM_BM);
+    p.rpad = (int64_t)p.tiles * HOST_PLAN_GEMM_BM;
+    p.tile_pairs = 0.5 * p.tiles * (p.tiles + 1.0);
+    p.ok = true;
+    return p;
+}
+
 // Pair lists of a bitmask graph and the cosine of listed pairs (pairs.hip).  The count and the fill are wave-per-row grid-stride
 // kernels (wave_stride_grid: at most PAIRS_MAX_GRID workgroups); the scan of the counts is one workgroup of PAIRS_SCAN_THREADS
 // threads that own scan_per consecutive rows each.  The cosine gives PAIR_COS_LANES lanes to a pair, so a workgroup takes

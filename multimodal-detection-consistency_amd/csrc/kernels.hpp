@@ -275,6 +275,18 @@ hipError_t launch_dbscan_sweep(const uint32_t* adj, const int32_t* degree, int R
 hipError_t launch_dbscan_finish(const uint32_t* adj, const int32_t* degree, int R, int min_samples, const int32_t* comp,
                                 int32_t* labels, uint8_t* core, int32_t* n_clusters, hipStream_t stream);
 
+// ---- nearest.hip: every row's most similar LATER row of a bank slot, and the closest pair of the slot
+struct ClosestPairLaunch {
+    BankRows bank;
+    NearestPlan plan;                 // nearest_plan(bank.R)
+    float* rinv = nullptr;            // workspace [plan.rpad]: 1 / |x|; 0 for a zero row, NaN for a non-finite norm and in the padding
+    int32_t* partner = nullptr;       // [R]: arg-max over j > i of cos(x_i, x_j), (value desc, j asc); -1 where no later row is admissible
+    float* sim = nullptr;             // [R]: that cosine; -inf where partner is -1
+    int32_t* pair = nullptr;          // [2]: the first maximal (i, partner[i]) in lexicographic order; (-1, -1) when no row has a partner
+    float* pair_sim = nullptr;        // [1]: its cosine; -inf for (-1, -1)
+};
+hipError_t launch_closest_pair(const ClosestPairLaunch& L, hipStream_t stream);
+
 // ---- pairs.hip: the upper triangle of a bitmask graph as a pair list, and the fp32-grade cosine of listed pairs of a bank slot
 // offsets int64 [R + 1]: the exclusive scan of the rows' counts of set bits j, i < j < R (with group: both groups >= 0 and
 // different); adj [R, round_up(R, 64) / 32] is any bitmask

@@ -1162,6 +1162,35 @@ class TVCEngine:
         keep = sims >= torch.tensor(t, dtype=torch.float32, device=self.device)
         return pairs[keep], sims[keep]
 
+    # ---- closest pair of a bank slot ----------------------------------------
+    CLOSEST_PAIR_TAU = 1e-6    # the contract's tau in cosine units: the bank search's bound
+
+    def closest_pair(self, bank: str = DEFAULT_BANK):
+        """-> (pair int32 [2], pair_sim fp32 [1], partner int32 [R], sim fp32 [R]) over the rows of ``bank``, all device
+        tensors on the current stream; the call does no host synchronisation.  ``partner[i]`` is the arg-max over the LATER
+        rows ``j > i`` of ``cos(x_i, x_j)`` (value descending, ``j`` ascending), ``sim[i]`` that cosine; ``pair`` is
+        ``(i, partner[i])`` of the best row under (sim descending, ``i`` ascending) -- the first maximal pair in lexicographic
+        ``(i, j)`` order, the pair a strict ``>`` over a double loop ``for i: for j > i`` keeps -- and ``pair_sim`` its cosine.
+        A row with no admissible later row (the last row, a row whose norm is not finite, a row all of whose later rows have
+        a non-finite norm) has ``partner = -1, sim = -inf``; without any pair ``pair = (-1, -1), pair_sim = -inf`` (R = 1 is
+        valid).  An all-zero row has cosine 0 with every row; a row of non-finite norm is never a partner.
+
+        Contract.  With ``c64(i, j)`` the fp64 cosine of the STORED rows (a bf16 slot: the bf16 values; an fp32 slot: hi + lo)
+        and ``tau = CLOSEST_PAIR_TAU = 1e-6``: ``|sim[i] - c64(i, partner[i])| <= tau`` and ``c64(i, partner[i]) >=
+        max_{j > i} c64(i, j) - 2 tau``; both hold for ``pair`` / ``pair_sim`` over all ``i < j``.  Where the arithmetic is
+        exact -- rows of one common norm whose ``1 / norm`` is a power of two and whose dot products are small integers --
+        ``partner`` and ``pair`` are exactly the above, including every tie.  The outputs are a pure function of the slot,
+        bit-identical between runs (no atomics, no floating-point reduction across workgroups)."""
+        with self._lock, torch.cuda.device(self.device):
+            b = self._select(bank)
+            R = b["rows"]
+            partner = torch.empty(R, dtype=torch.int32, device=self.device)
+            sim = torch.empty(R, dtype=torch.float32, device=self.device)
+            pair = torch.empty(2, dtype=torch.int32, device=self.device)
+            pair_sim = torch.empty(1, dtype=torch.float32, device=self.device)
+            self._check(self.lib.tvc_closest_pair(self.handle, _ptr(partner), _ptr(sim), _ptr(pair), _ptr(pair_sim), _stream()))
+        return pair, pair_sim, partner, sim
+
     # ---- IVF search over a bank slot in list order -------------------------
     def ivf_probe(self, rows: torch.Tensor, centroids: torch.Tensor, nprobe: int):
         """rows fp32 [M, D], centroids fp32 [nlist, D] -> (lists int32 [M, nprobe], score fp32 [M, nprobe]): the nprobe

@@ -6,7 +6,11 @@ a device matrix of L2-normalised rows (re-registered lazily after additions) and
 ``query_similar`` is one ``tvc_bank_search`` call (fp32 bank -> split-bf16
 planes, fp32-grade cosines).  In scope: ``add_reference`` (admission check
 included), ``query_similar``, ``_compute_similarities``, size / FIFO-LRU-random
-eviction bookkeeping, and the KMeans clustering (``perform_clustering``,
+eviction bookkeeping, similarity eviction (``_remove_most_similar``,
+``src/ref_bank.py:401-427``: the reference's double loop over all pairs on every
+admission at capacity is one ``TVCEngine.closest_pair`` call, ``tvc_closest_pair``,
+over the bank's own slot of unit rows; ``similarity_victim`` is the access-count
+rule), and the KMeans clustering (``perform_clustering``,
 ``query_by_cluster``, ``get_cluster_centers``, the ``auto_clustering`` hook and the
 cluster bookkeeping on eviction, ``src/ref_bank.py:226-339,429-450``): the raw
 vectors are registered under a second, temporary bank slot and clustered by
@@ -75,6 +79,20 @@ class ReferenceItem:
     access_count: int = 0
     cluster_id: Optional[int] = None
     similarity_scores: Dict[str, float] = field(default_factory=dict)
+
+
+def similarity_victim(access_counts, pair, pair_sim) -> Optional[int]:
+    """The row ``_remove_most_similar`` (src/ref_bank.py:401-427) removes, or None: a pure function of the references'
+    access counts and of the closest pair ``(i, j)``, ``i < j``, with its cosine ``pair_sim`` -- the first maximal pair of the
+    reference's loops.  The victim is ``i`` if ``access_counts[i] <= access_counts[j]``, else ``j``.  The reference's quirks
+    stay: with fewer than 2 references nothing is removed, and when no pair's similarity exceeds -1 (``max_similarity``
+    starts at -1 and the compare is strict; also: no pair at all, ``pair`` None or (-1, -1)) index 0 goes."""
+    if len(access_counts) < 2:
+        return None
+    if pair is None or pair[0] < 0 or pair[1] < 0 or not (pair_sim > -1.0):
+        return 0
+    i, j = int(pair[0]), int(pair[1])
+    return i if access_counts[i] <= access_counts[j] else j
 
 
 class ReferenceBank:
@@ -172,11 +190,31 @@ class ReferenceBank:
             self.stats["total_added"] += len(vectors)
             self._dirty = True
 
+    def _remove_most_similar(self) -> None:
+        """src/ref_bank.py:401-427 (lock held): the most similar pair of stored vectors loses the member that was accessed
+        less.  The reference's double loop over i < j becomes ``engine.closest_pair`` over the bank's own slot, whose unit
+        fp32 rows make the scores the cosines of the raw vectors; ``similarity_victim`` picks the row."""
+        pair, pair_sim = None, float("-inf")
+        if len(self.references) >= 2:
+            self._sync_device()
+            p, s, _, _ = self.engine.closest_pair(self.bank_name)
+            pair, pair_sim = tuple(int(v) for v in p.tolist()), float(s.item())
+        idx = similarity_victim([r.access_count for r in self.references], pair, pair_sim)
+        if idx is None:
+            return
+        self.references.pop(idx)
+        self._update_clusters_after_removal(idx)
+        self._dirty = True
+
     def _remove_reference(self) -> None:
-        """src/ref_bank.py:364-400 (fifo / lru / random; 'similarity' falls back to fifo)."""
+        """src/ref_bank.py:364-400 (fifo / lru / random / similarity)."""
         if not self.references:
             return
         s = self.config.update_strategy
+        if s == "similarity":
+            self._remove_most_similar()
+            self.stats["total_removed"] += 1      # :399 counts the call, also when fewer than 2 references kept their row
+            return
         idx = 0
         if s == "lru" and self.access_order:
             idx = self.access_order.popleft()
