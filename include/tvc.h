@@ -629,6 +629,86 @@ int tvc_roc_sweep(tvc_handle* h, const tvc_roc_rows* rows, double target_tpr, co
 int tvc_roc_curve(tvc_handle* h, const tvc_roc_rows* rows, int32_t* pt_tp_dev, int32_t* pt_fp_dev, int32_t* pt_pos_dev,
                   int32_t* pt_kept_dev, int32_t* count_dev, void* stream);
 
+/* ---- similarity metrics of pairs of rows; top-k overlap --------------------------------------------------------- */
+
+/* Cosine similarity, Euclidean and Manhattan distance, Pearson and Spearman correlation (src/utils/metrics.py:89-106,166-276;
+ * src/retrieval.py:158-193) of PAIRS of rows: the metrics of (x[b, :], y[b, :]) for every b in one launch, one workgroup a pair.
+ *   x_dev, y_dev  [B, D] at row pitches ldx, ldy >= D (in elements); fp32 (TVC_SIM_KEY_F32) or int32 (TVC_SIM_KEY_I32: index
+ *                 lists; an element converts to fp64 exactly and is ordered as an integer).  1 <= D <= TVC_SIM_MAX_D, any D.
+ *   out_dev       fp64 [B, TVC_SIM_COLS]: cosine, Euclidean, Manhattan, Pearson, Spearman; columns 5 .. 7 are 0.0
+ *   ints_dev      int64 [B, TVC_SIM_INTS]: the sums of cx cy, cx cx and cy cy over the centred doubled ranks (below), then the
+ *                 number of NaN elements of the pair (x's and y's); the three sums are 0 when that number is not 0
+ * With n = D and the elements taken to fp64:
+ *   float sums    fp64; a thread adds its elements i = t, t + T, ... in that order (T = 64 threads for n <= 256, else 256), the
+ *                 threads' sums meet in a fixed tree: the order depends on n alone, there are no atomics, and the results
+ *                 are bit-identical between runs, launches and batch sizes.  No multiply-add is contracted.
+ *   cosine        sum(x y) / sqrt(sum(x x) * sum(y y));  0.0 when either row is all zero and the pair has no NaN
+ *   Euclidean     sqrt(sum((x - y)^2));   Manhattan  sum(|x - y|)
+ *   Pearson       two passes: mx = sum(x) / n, my = sum(y) / n, then with cx = x - mx, cy = y - my
+ *                 r = sum(cx cy) / sqrt(sum(cx cx) * sum(cy cy)), clamped to [-1, 1] (a NaN stays).  NaN when n < 2 or when
+ *                 min == max over either row (the explicit constant-input test of scipy.stats.pearsonr: the mean of a constant
+ *                 row need not round to its value, so a centred sum is no such test).
+ *   Spearman      exact integers.  The doubled 1-based average rank of an element is lo + hi + 1, lo = the number of the
+ *                 row's elements strictly below it, hi = the number at or below it; -0.0 ties with 0.0, +-inf order as
+ *                 values.  The doubled ranks of a row sum to n (n + 1), so the centred doubled rank c = lo + hi - n is an
+ *                 integer with |c| <= n - 1.  rho = sum(cx cy) / sqrt((double)sum(cx cx) * (double)sum(cy cy)) on the int64
+ *                 sums (no rounding before the conversions).  NaN when n < 2, when an integer sum of squares is 0 (a
+ *                 constant row) or when the pair holds any NaN.
+ *   specials      NaN and +-inf otherwise propagate as the arithmetic yields; every NaN written is 0x7ff8000000000000.  A
+ *                 pair never changes another pair's bits.
+ * Accuracy against the exact value on the given elements, u = 2^-53, kappa = max(mean|x| / sigma_x, mean|y| / sigma_y):
+ *   interface     cosine within B(n) = 2^-52 (2 n + 16) absolute, Euclidean and Manhattan within B(n) relative, Pearson
+ *                 within B(n) + (2^-52 n kappa)^2.  (Products of fp32 values are exact in fp64; an n-term fp64 sum errs by at
+ *                 most (n - 1) u sum|terms|; the error of a mean enters Pearson at second order only.)
+ *   kernel        the same with the kernel's chain length c(n) in place of n: a term passes through at most
+ *                 c(n) = min(n - 1, ceil(n / T) + 8) rounding additions (ceil(n / T) - 1 in its thread, 6 in the wave, 3
+ *                 across the waves): cosine within Bk(n) = 2^-52 (c(n) + 2) absolute (sum(x y) errs by c u sqrt(sum(x x)
+ *                 sum(y y)), the two sums of squares by c u relative each, product, root and quotient add 2.5 u),
+ *                 Manhattan and Euclidean within Bk(n) relative (a term carries 1 u, a squared one 3 u; the root halves),
+ *                 Pearson within 2^-52 (c(n) + 5) + (2^-52 (c(n) + 1) kappa)^2 (centring and the product add 3 u a term; a
+ *                 mean errs by (c + 1) u mean|x|, which shifts each centred sum by n delta_x delta_y).  c(4096) = 24.
+ *                 The long form below: c(n) = min(n - 1, 33).
+ * TVC_E_INVALID, and nothing is launched, when h is NULL, B < 0, D is outside [1, TVC_SIM_MAX_D], a pitch is below D, the key
+ * type is unknown, or a buffer is NULL with B > 0.  B == 0 is legal and launches nothing. */
+#define TVC_SIM_MAX_D 4096
+#define TVC_SIM_MAX_N 1048576
+#define TVC_SIM_COLS 8
+#define TVC_SIM_INTS 4
+#define TVC_SIM_KEY_F32 0
+#define TVC_SIM_KEY_I32 1
+int tvc_sim_rows(tvc_handle* h, const void* x_dev, const void* y_dev, int64_t B, int32_t D, int64_t ldx, int64_t ldy, int32_t key_type,
+                 double* out_dev /*[B, 8]*/, int64_t* ints_dev /*[B, 4]*/, void* stream);
+
+/* The long form: ONE pair of fp32 vectors of n elements, TVC_SIM_MAX_D < n <= TVC_SIM_MAX_N (any n >= 1 is accepted), with the
+ * outputs, formulas and specials of one row of tvc_sim_rows.  The caller sorts each vector's values ascending with NaN last
+ * (only the sorted values are needed, no permutation).
+ *   tvc_sim_flat_rank   crank_dev int32 [n]: the centred doubled rank lo + hi - n of every element of v_dev, by a fixed-step
+ *                       lower and upper bound of the element's own value in sorted_dev: no scan, no dependency between
+ *                       workgroups.  nan_count_dev int64 [1] (may be NULL): the NaN elements of the vector.
+ *   tvc_sim_flat        out_dev fp64 [TVC_SIM_COLS], ints_dev int64 [TVC_SIM_INTS] from x, y and their centred ranks.  Both
+ *                       passes (sums and means; centred sums) run as a partial kernel, whose workgroup b owns the elements
+ *                       [4096 b, 4096 (b + 1)), and a one-workgroup finish kernel that adds the partials in a fixed order: grid
+ *                       and order are functions of n alone, never of the device, and every hand-off between workgroups
+ *                       crosses a kernel boundary.  ws_dev: 8-byte aligned scratch of at least tvc_sim_flat_workspace(n) =
+ *                       8 (16 + 20 ceil(n / 4096)) bytes (0 for an n outside the range), not shared by concurrent calls.
+ * TVC_SIM_MAX_N = 2^20 is what keeps n (n - 1)^2, the bound of a sum of squared centred doubled ranks, inside int64.
+ * TVC_E_INVALID, and nothing is launched, when h is NULL, n < 1, n > TVC_SIM_MAX_N, a buffer is NULL (nan_count_dev excepted),
+ * or the workspace is too small or misaligned. */
+uint64_t tvc_sim_flat_workspace(int64_t n);
+int tvc_sim_flat_rank(tvc_handle* h, const float* v_dev, const float* sorted_dev, int64_t n, int32_t* crank_dev /*[n]*/,
+                      int64_t* nan_count_dev /*[1] or NULL*/, void* stream);
+int tvc_sim_flat(tvc_handle* h, const float* x_dev, const float* y_dev, const int32_t* cx_dev, const int32_t* cy_dev, int64_t n,
+                 double* out_dev /*[8]*/, int64_t* ints_dev /*[4]*/, void* ws_dev, uint64_t ws_bytes, void* stream);
+
+/* Top-k overlap of two retrievals (src/retrieval.py:179-184): count_dev int32 [M], count[i] = |set(a[i, :k]) & set(b[i, :k])|
+ * for a_dev int32 [M, La] and b_dev int32 [M, Lb].  Set semantics: an id repeated inside a list counts once.  A list shorter
+ * than k is taken whole, as a Python slice is.  No id is special (negative ids are ids).  One wave per query, no atomics.
+ * TVC_E_INVALID, and nothing is launched, when h is NULL, M < 0, La < 0, Lb < 0, k is outside [1, TVC_TOPK_OVERLAP_MAX_K], or a
+ * buffer is NULL with M > 0.  M == 0 is legal and launches nothing. */
+#define TVC_TOPK_OVERLAP_MAX_K 1024
+int tvc_topk_overlap(tvc_handle* h, const int32_t* a_dev, const int32_t* b_dev, int64_t M, int32_t La, int32_t Lb, int32_t k,
+                     int32_t* count_dev /*[M]*/, void* stream);
+
 /* ---- IVF search: probe + list scan over a bank slot ------------------------------------------------ */
 
 /* An IVF index over R rows is four things:

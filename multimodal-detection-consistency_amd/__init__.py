@@ -17,13 +17,13 @@ from .clip import CLIPConfig, CLIPModel
 from .data_validator import DataValidationConfig, DataValidator, ValidationResult, create_data_validator
 from .detector import (AdversarialDetector, ConsistencyChecker, DetectionConfig, DetectorConfig,
                        MultiModalDefenseDetector, aggregate_scores, create_adversarial_detector, unpack_records)
-from .engine import ConsistencyConfig, IVFIndex, RetrievalRanks, RocSweep, TVCEngine
+from .engine import ConsistencyConfig, IVFIndex, RetrievalRanks, RocSweep, SimilarityRows, TVCEngine
 from .metrics import (DetectionEvaluator, DetectionMetrics, MetricsCalculator, RetrievalEvaluator, RetrievalMetrics,
-                      SimilarityCalculator, bootstrap_detection_metrics, bootstrap_metric)
+                      SimilarityCalculator, SimilarityMetrics, bootstrap_detection_metrics, bootstrap_metric)
 from .pipeline import (DefensePipeline, MultiModalDetectionPipeline, PipelineConfig, PipelineProfiler,
                        PipelineResult, create_defense_pipeline, create_detection_pipeline)
 from .ref_bank import ReferenceBank, ReferenceBankConfig, ReferenceItem, create_reference_bank
-from .retrieval import (MultiModalRetriever, RetrievalConfig, RetrievalRefConfig, RetrievalReferenceGenerator,
+from .retrieval import (ConsistencyCalculator, MultiModalRetriever, RetrievalConfig, RetrievalRefConfig, RetrievalReferenceGenerator,
                         create_retriever, extract_features)
 from .sd_arch import SDArch, make_sd_weights
 from .sd_model import SDKernels, SDModelConfig, StableDiffusionModel, create_sd_model

@@ -131,6 +131,7 @@ class RocOut(C.Structure):
 
 
 TVC_ROC_SRC_WEIGHTS, TVC_ROC_SRC_INDICES, TVC_ROC_SRC_PHILOX = 0, 1, 2
+TVC_SIM_KEY_F32, TVC_SIM_KEY_I32 = 0, 1
 
 # name -> (restype, argtypes); must list every symbol include/tvc.h declares
 SIGNATURES = {
@@ -163,6 +164,11 @@ SIGNATURES = {
     "tvc_roc_weights": (C.c_int, [_P, C.POINTER(RocRows), _P, _P]),
     "tvc_roc_sweep": (C.c_int, [_P, C.POINTER(RocRows), C.c_double, C.POINTER(C.c_float), C.c_int32, C.POINTER(RocOut), _P]),
     "tvc_roc_curve": (C.c_int, [_P, C.POINTER(RocRows), _P, _P, _P, _P, _P, _P]),
+    "tvc_sim_rows": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P]),
+    "tvc_sim_flat_workspace": (C.c_uint64, [C.c_int64]),
+    "tvc_sim_flat_rank": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P]),
+    "tvc_sim_flat": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_uint64, _P]),
+    "tvc_topk_overlap": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "tvc_ivf_probe": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     "tvc_ivf_scan": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P, _P]),
     "tvc_topk_merge": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

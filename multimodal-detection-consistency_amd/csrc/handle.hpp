@@ -5,7 +5,7 @@
 // tvc_sd_op.cpp: its entry points that read no model state; tvc_kmeans.cpp: k-means over a bank slot;
 // tvc_ivf.cpp: IVF probe and list scan; tvc_grad_split.cpp: the split-bf16 input gradient; tvc_dbscan.cpp: radius graph and
 // DBSCAN labels; tvc_pairs.cpp: pair lists of a bitmask graph and the cosine of listed pairs; tvc_rank.cpp: retrieval evaluation;
-// tvc_roc.cpp: detection evaluation; tvc_nearest.cpp: closest pair of a bank slot).
+// tvc_roc.cpp: detection evaluation; tvc_nearest.cpp: closest pair of a bank slot; tvc_sim.cpp: similarity metrics of row pairs).
 // The entry points that pass over a bank slot share filled_slot (the TVC_E_STATE refusal of an empty slot) and ensure_planes /
 // split_planes (a workspace slot of (hi | lo) query planes); their work estimate is host_plan.hpp's slot_pass_flops.
 #pragma once

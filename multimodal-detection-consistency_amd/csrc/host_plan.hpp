@@ -150,6 +150,44 @@ inline RocPlan roc_plan(int64_t N, int64_t B, int n_thr, double target) {
     return p;
 }
 
+// Similarity metrics (sim.hip).  Row form: one workgroup per pair of rows of D <= SIM_MAX_D elements, sim_row_threads(D)
+// threads (one wave up to 256 elements, four above: the summation order is a function of D alone), the sort keys of one row
+// in LDS (at most SIM_MAX_D uint32 = 16 KiB).  Long form: one pair of n <= SIM_MAX_N elements; workgroup b of the two partial
+// kernels owns the elements [b * SIM_FLAT_CHUNK, (b + 1) * SIM_FLAT_CHUNK), so the grid is a function of n alone, and one
+// workgroup finishes each pass over the caller's workspace of 8-byte words:
+//   [0, SIM_WS_HEAD)                              the totals of pass 1 (what pass 2 reads its means from)
+//   [SIM_WS_HEAD + b * SIM_WS_P1, ...)            pass 1's partials of workgroup b: 7 fp64 sums, 4 extremes, 3 int64 rank sums, NaNs
+//   [SIM_WS_HEAD + grid * SIM_WS_P1 + b * SIM_WS_P2, ...)   pass 2's partials: the 3 centred fp64 sums
+// SIM_MAX_N = 2^20 keeps n (n - 1)^2, the bound of a sum of squared centred doubled ranks, inside int64.
+// ok = false: n outside [1, SIM_MAX_N].
+#define SIM_MAX_D 4096
+#define SIM_MAX_N (1 << 20)
+#define SIM_COLS 8
+#define SIM_INTS 4
+#define SIM_FLAT_CHUNK 4096
+#define SIM_FLAT_THREADS 256
+#define SIM_WS_HEAD 16
+#define SIM_WS_P1 16
+#define SIM_WS_P2 4
+#define TOPK_OVERLAP_MAX_K 1024
+inline int sim_row_threads(int D) { return D <= 256 ? 64 : 256; }
+struct SimFlatPlan {
+    bool ok = false;
+    int grid = 0;                       // workgroups of the two partial kernels
+    int pow2 = 0;                       // the smallest power of two >= n: the first step of the rank searches
+    int64_t ws_bytes = 0;
+};
+inline SimFlatPlan sim_flat_plan(int64_t n) {
+    SimFlatPlan p;
+    if (n < 1 || n > SIM_MAX_N) return p;
+    p.grid = (int)((n + SIM_FLAT_CHUNK - 1) / SIM_FLAT_CHUNK);
+    p.pow2 = 1;
+    while (p.pow2 < n) p.pow2 <<= 1;
+    p.ws_bytes = 8 * ((int64_t)SIM_WS_HEAD + (int64_t)p.grid * (SIM_WS_P1 + SIM_WS_P2));
+    p.ok = true;
+    return p;
+}
+
 // Radius graph / DBSCAN (dbscan.hip): the graph of R rows is a bitmask uint32 [R, words], words = round_up(R, 64) / 32 (an even
 // count: a wave of the tile kernel stores one 64-bit word per row).  The tile kernel's grid is tiles x tiles 256 x 256 tiles of
 // which the upper triangle computes; the half-norm vector is padded to whole tiles (hpad floats, NaN beyond R).  The

@@ -255,6 +255,37 @@ struct RocLaunch {
 };
 hipError_t launch_roc(const RocLaunch& L, hipStream_t stream);
 
+// ---- sim.hip: similarity metrics of pairs of rows (cosine, Euclidean, Manhattan, Pearson, Spearman) and top-k overlap counts
+// out fp64 [*, SIM_COLS]: the five metrics in that order, then zeros; ints int64 [*, SIM_INTS]: the sums of cx cy, cx cx and
+// cy cy over the centred doubled ranks (zeros when the pair holds a NaN), then the number of NaN elements of the pair
+enum SimKey { SIM_KEY_F32 = 0, SIM_KEY_I32 = 1 };
+struct SimRowsLaunch {
+    const void* x = nullptr;          // [B, ldx] fp32 or int32 (key)
+    const void* y = nullptr;          // [B, ldy]
+    int64_t ldx = 0, ldy = 0;         // row pitches in elements, >= D
+    int64_t B = 0;                    // pairs = workgroups; 0 launches nothing
+    int D = 0;                        // 1 .. SIM_MAX_D
+    int key = SIM_KEY_F32;
+    double* out = nullptr;            // [B, SIM_COLS]
+    int64_t* ints = nullptr;          // [B, SIM_INTS]
+};
+hipError_t launch_sim_rows(const SimRowsLaunch& L, hipStream_t stream);
+// crank int32 [n]: lo + hi - n of every element of v in sorted_v (v ascending, NaN last); nan_count int64 [1] or nullptr
+hipError_t launch_sim_flat_rank(const float* v, const float* sorted_v, int64_t n, int32_t* crank, int64_t* nan_count, hipStream_t stream);
+struct SimFlatLaunch {
+    const float* x = nullptr;         // [n]
+    const float* y = nullptr;
+    const int32_t* cx = nullptr;      // [n]: launch_sim_flat_rank's centred doubled ranks
+    const int32_t* cy = nullptr;
+    int64_t n = 0;                    // 1 .. SIM_MAX_N
+    double* out = nullptr;            // [SIM_COLS]
+    int64_t* ints = nullptr;          // [SIM_INTS]
+    void* ws = nullptr;               // sim_flat_plan(n).ws_bytes, 8-byte aligned
+};
+hipError_t launch_sim_flat(const SimFlatLaunch& L, hipStream_t stream);
+// count int32 [M]: |set(a[i, :k]) & set(b[i, :k])|; a int32 [M, La], b int32 [M, Lb], 1 <= k <= TOPK_OVERLAP_MAX_K
+hipError_t launch_topk_overlap(const int32_t* a, const int32_t* b, int64_t M, int La, int Lb, int k, int32_t* count, hipStream_t stream);
+
 // ---- dbscan.hip: the eps-graph of a bank slot as a bitmask, and DBSCAN's labels from such a graph (exact integer work)
 struct RadiusGraphLaunch {
     BankRows bank;

@@ -115,6 +115,15 @@ class RocSweep:
         return float("inf") if pos < 0 else float(self.scores[pos])
 
 
+@dataclass
+class SimilarityRows:
+    """What ``TVCEngine.similarity_rows`` / ``similarity_flat`` return: one row per pair (``tvc_sim_rows``, include/tvc.h)."""
+    values: torch.Tensor         # fp64 [B, 5]: cosine, Euclidean, Manhattan, Pearson, Spearman (NaN where undefined)
+    ints: torch.Tensor           # int64 [B, 4]: the sums of cx cy, cx cx, cy cy over the centred doubled ranks; the NaN elements
+
+    COLUMNS = ("cosine_similarity", "euclidean_distance", "manhattan_distance", "pearson_correlation", "spearman_correlation")
+
+
 def _stream() -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -1190,6 +1199,96 @@ class TVCEngine:
             pair_sim = torch.empty(1, dtype=torch.float32, device=self.device)
             self._check(self.lib.tvc_closest_pair(self.handle, _ptr(partner), _ptr(sim), _ptr(pair), _ptr(pair_sim), _stream()))
         return pair, pair_sim, partner, sim
+
+    # ---- similarity metrics of row pairs; top-k overlap ----------------------
+    SIM_MAX_D = 4096              # TVC_SIM_MAX_D: the row form's widest row
+    SIM_MAX_N = 1 << 20           # TVC_SIM_MAX_N: the long form's cap
+    TOPK_OVERLAP_MAX_K = 1024     # TVC_TOPK_OVERLAP_MAX_K
+
+    def _sim_operand(self, t, dtype, name: str) -> torch.Tensor:
+        """[B, D] on the device with unit column stride (a column view of a wider buffer keeps its row pitch); 1-D = one row"""
+        t = torch.as_tensor(t)
+        if dtype == torch.int32 and t.dtype != torch.int32:
+            if t.is_floating_point() or t.dtype == torch.bool:
+                raise ValueError(f"{name}: key='i32' takes integer elements (got {t.dtype})")
+            if t.numel() and (int(t.min()) < -(1 << 31) or int(t.max()) >= 1 << 31):
+                raise ValueError(f"{name}: an element does not fit int32")
+        t = t.to(self.device, dtype)
+        if t.dim() == 1:
+            t = t.reshape(1, -1)
+        if t.dim() != 2:
+            raise ValueError(f"{name} must be [B, D] or [D] (got shape {tuple(t.shape)})")
+        if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+            t = t.contiguous()
+        return t
+
+    def similarity_rows(self, x, y, key: str = "f32") -> SimilarityRows:
+        """x, y [B, D] (or [D]: one pair), 1 <= D <= ``SIM_MAX_D`` -> ``SimilarityRows`` of the B pairs (x[b], y[b]) from one launch
+        of ``tvc_sim_rows``: device tensors on the current stream, no host synchronisation.  ``key="f32"``: the elements are
+        taken as fp32 (values that fp32 cannot hold are rounded first, which can create ties); ``key="i32"``: integer index
+        lists, taken exactly.  Formulas, specials and error bounds: include/tvc.h.  B == 0 is valid."""
+        if key not in ("f32", "i32"):
+            raise ValueError(f"key must be 'f32' or 'i32' (got {key!r})")
+        dt = torch.int32 if key == "i32" else torch.float32
+        with self._lock, torch.cuda.device(self.device):
+            xd, yd = self._sim_operand(x, dt, "x"), self._sim_operand(y, dt, "y")
+            if xd.shape != yd.shape:
+                raise ValueError(f"x and y must have one shape (got {tuple(xd.shape)}, {tuple(yd.shape)})")
+            B, D = xd.shape
+            if D < 1 or D > self.SIM_MAX_D:
+                raise ValueError(f"need 1 <= D <= {self.SIM_MAX_D} (got {D}); similarity_flat takes one longer pair")
+            out = torch.empty((B, 8), dtype=torch.float64, device=self.device)
+            ints = torch.empty((B, 4), dtype=torch.int64, device=self.device)
+            self._check(self.lib.tvc_sim_rows(self.handle, _ptr(xd), _ptr(yd), B, D, xd.stride(0) if B > 1 else D,
+                                              yd.stride(0) if B > 1 else D, _lib.TVC_SIM_KEY_I32 if key == "i32" else _lib.TVC_SIM_KEY_F32,
+                                              _ptr(out), _ptr(ints), _stream()))
+        return SimilarityRows(out[:, :5], ints)
+
+    def similarity_flat(self, x, y, force_long: bool = False) -> SimilarityRows:
+        """The ``SimilarityRows`` (one row) of ONE pair: x and y of any shape with equally many elements n, flattened and taken
+        as fp32.  n <= ``SIM_MAX_D`` runs the row form; a longer pair (or ``force_long``) the long form: ``torch.sort`` of the
+        values (plumbing: the kernels need only the sorted values), ``tvc_sim_flat_rank`` twice and ``tvc_sim_flat``.
+        ``ValueError`` for n < 1 or n > ``SIM_MAX_N``."""
+        with torch.cuda.device(self.device):
+            xd = torch.as_tensor(x).to(self.device, torch.float32).reshape(-1).contiguous()
+            yd = torch.as_tensor(y).to(self.device, torch.float32).reshape(-1).contiguous()
+        n = xd.numel()
+        if yd.numel() != n:
+            raise ValueError(f"x and y must have equally many elements (got {n}, {yd.numel()})")
+        if n < 1 or n > self.SIM_MAX_N:
+            raise ValueError(f"need 1 <= n <= {self.SIM_MAX_N} elements (got {n})")
+        if n <= self.SIM_MAX_D and not force_long:
+            return self.similarity_rows(xd, yd)
+        with self._lock, torch.cuda.device(self.device):
+            out = torch.empty((1, 8), dtype=torch.float64, device=self.device)
+            ints = torch.empty((1, 4), dtype=torch.int64, device=self.device)
+            ws = torch.empty(int(self.lib.tvc_sim_flat_workspace(n)) // 8, dtype=torch.int64, device=self.device)
+            cranks = []
+            for v in (xd, yd):
+                sv = torch.sort(v).values                  # ascending, NaN last
+                c = torch.empty(n, dtype=torch.int32, device=self.device)
+                self._check(self.lib.tvc_sim_flat_rank(self.handle, _ptr(v), _ptr(sv), n, _ptr(c), None, _stream()))
+                cranks.append(c)
+            self._check(self.lib.tvc_sim_flat(self.handle, _ptr(xd), _ptr(yd), _ptr(cranks[0]), _ptr(cranks[1]), n, _ptr(out),
+                                              _ptr(ints), _ptr(ws), ws.numel() * 8, _stream()))
+        return SimilarityRows(out[:, :5], ints)
+
+    def topk_overlap(self, a, b, k: int) -> torch.Tensor:
+        """a int [M, La], b int [M, Lb] (or 1-D: one query) -> int32 [M] on the device: ``len(set(a[i, :k]) & set(b[i, :k]))``,
+        one wave per query (``tvc_topk_overlap``); 1 <= k <= ``TOPK_OVERLAP_MAX_K``.  Ids must fit int32; none is special."""
+        k = int(k)
+        if k < 1 or k > self.TOPK_OVERLAP_MAX_K:
+            raise ValueError(f"need 1 <= k <= {self.TOPK_OVERLAP_MAX_K} (got {k})")
+        with self._lock, torch.cuda.device(self.device):
+            ad, bd = self._sim_operand(a, torch.int32, "a").contiguous(), self._sim_operand(b, torch.int32, "b").contiguous()
+            if ad.shape[0] != bd.shape[0]:
+                raise ValueError(f"a and b must have equally many rows (got {ad.shape[0]}, {bd.shape[0]})")
+            M = ad.shape[0]
+            if ad.shape[1] == 0 or bd.shape[1] == 0:          # an empty list shares nothing (and has no buffer to pass)
+                return torch.zeros(M, dtype=torch.int32, device=self.device)
+            count = torch.empty(M, dtype=torch.int32, device=self.device)
+            self._check(self.lib.tvc_topk_overlap(self.handle, _ptr(ad), _ptr(bd), M, ad.shape[1], bd.shape[1], k, _ptr(count), _stream()))
+        return count
 
     # ---- IVF search over a bank slot in list order -------------------------
     def ivf_probe(self, rows: torch.Tensor, centroids: torch.Tensor, nprobe: int):

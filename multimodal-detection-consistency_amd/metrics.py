@@ -1,5 +1,6 @@
 """``SimilarityCalculator`` (``src/utils/metrics.py:109-164``) over the HIP cosine
-kernel; the detection metrics (``:286-376,816-874``): ``compute_detection_metrics``
+kernel, and its distances and correlations with ``SimilarityMetrics`` (``:89-106,166-276``)
+over the HIP row-pair kernels; the detection metrics (``:286-376,816-874``): ``compute_detection_metrics``
 stays sklearn on the host exactly as in the reference, while ``evaluate_scores``, the
 ROC / PR curves and the bootstrap run over the HIP ROC-sweep kernels;
 and the retrieval metrics (``:70-86,379-573,951-972``): the dense form on the host, the
@@ -27,7 +28,79 @@ def _engine(engine: Optional[TVCEngine]) -> TVCEngine:
     return _default_engine
 
 
+@dataclass
+class SimilarityMetrics:
+    """src/utils/metrics.py:89-106."""
+    cosine_similarity: float = 0.0
+    euclidean_distance: float = 0.0
+    manhattan_distance: float = 0.0
+    pearson_correlation: float = 0.0
+    spearman_correlation: float = 0.0
+
+    def to_dict(self) -> Dict[str, Any]:
+        return {"cosine_similarity": self.cosine_similarity, "euclidean_distance": self.euclidean_distance,
+                "manhattan_distance": self.manhattan_distance, "pearson_correlation": self.pearson_correlation,
+                "spearman_correlation": self.spearman_correlation}
+
+
+def _host(x):
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def _nan_to_zero(v: np.ndarray) -> np.ndarray:
+    return np.where(np.isnan(v), 0.0, v)
+
+
 class SimilarityCalculator:
+    """src/utils/metrics.py:109-276.  The scalar functions take two arrays of any shape with equally many elements, flatten
+    them as the reference does, and return Python floats; each is one call of ``TVCEngine.similarity_flat`` (the row kernel up
+    to 4 096 elements, the long form up to 2^20; longer inputs raise ``ValueError``).  ``rowwise_similarities`` is the batched
+    form: the five metrics of B pairs of rows from one launch.  Inputs are rounded to fp32 before the kernels, as everywhere in
+    this package: fp64 inputs that fp32 cannot hold are rounded first, which can create ties that the fp64 values did not
+    have (Spearman sees them as ties).  Sums are fp64; formulas, specials and error bounds are in include/tvc.h.  Where the
+    reference turns an undefined correlation into 0.0 (a constant input, a NaN or inf element, a single element) so do these."""
+
+    @staticmethod
+    def _pair(x, y, engine: Optional[TVCEngine]) -> np.ndarray:
+        """fp64 [5] of one flattened pair: the kernel's row, NaN where it is undefined"""
+        return _engine(engine).similarity_flat(_host(x), _host(y)).values[0].cpu().numpy()
+
+    @staticmethod
+    def euclidean_distance(x, y, engine: Optional[TVCEngine] = None) -> float:
+        """src/utils/metrics.py:166-187."""
+        return float(SimilarityCalculator._pair(x, y, engine)[1])
+
+    @staticmethod
+    def manhattan_distance(x, y, engine: Optional[TVCEngine] = None) -> float:
+        """src/utils/metrics.py:189-210."""
+        return float(SimilarityCalculator._pair(x, y, engine)[2])
+
+    @staticmethod
+    def pearson_correlation(x, y, engine: Optional[TVCEngine] = None) -> float:
+        """src/utils/metrics.py:212-233: 0.0 where the correlation is undefined (NaN) and for a single element."""
+        return float(_nan_to_zero(SimilarityCalculator._pair(x, y, engine))[3])
+
+    @staticmethod
+    def spearman_correlation(x, y, engine: Optional[TVCEngine] = None) -> float:
+        """src/utils/metrics.py:235-256: 0.0 where the correlation is undefined (NaN) and for a single element."""
+        return float(_nan_to_zero(SimilarityCalculator._pair(x, y, engine))[4])
+
+    @classmethod
+    def compute_all_similarities(cls, x, y, engine: Optional[TVCEngine] = None) -> SimilarityMetrics:
+        """src/utils/metrics.py:258-276 from ONE kernel row: two matrices are flattened into one pair, as the reference's five
+        functions flatten them.  The cosine is 0.0 for a zero vector (the reference's norm check), NaN if an element is."""
+        v = cls._pair(x, y, engine)
+        return SimilarityMetrics(cosine_similarity=float(v[0]), euclidean_distance=float(v[1]), manhattan_distance=float(v[2]),
+                                 pearson_correlation=float(_nan_to_zero(v)[3]), spearman_correlation=float(_nan_to_zero(v)[4]))
+
+    @staticmethod
+    def rowwise_similarities(x, y, engine: Optional[TVCEngine] = None) -> Dict[str, np.ndarray]:
+        """x, y [B, D], D <= 4 096 -> the reference's five names, each an fp64 array [B]: the metrics of the pairs (x[b], y[b])
+        from one launch (``TVCEngine.similarity_rows``).  Undefined correlations are 0.0, as in the scalar functions."""
+        v = _engine(engine).similarity_rows(_host(x), _host(y)).values.cpu().numpy()
+        v[:, 3:5] = _nan_to_zero(v[:, 3:5])
+        return {name: v[:, j].copy() for j, name in enumerate(SimilarityMetrics().to_dict())}
+
     @staticmethod
     def batch_cosine_similarity(x: Union[np.ndarray, torch.Tensor], y: Union[np.ndarray, torch.Tensor],
                                 engine: Optional[TVCEngine] = None) -> np.ndarray:
@@ -68,6 +141,12 @@ class DetectionMetrics:
     fpr_at_95_tpr: float
     threshold: float
     confusion_matrix: np.ndarray
+
+    def to_dict(self) -> Dict[str, Any]:
+        """src/utils/metrics.py:55-66."""
+        return {"auc": self.auc, "accuracy": self.accuracy, "precision": self.precision, "recall": self.recall,
+                "f1_score": self.f1_score, "fpr_at_95_tpr": self.fpr_at_95_tpr, "threshold": self.threshold,
+                "confusion_matrix": self.confusion_matrix.tolist()}
 
 
 class DetectionEvaluator:
@@ -304,7 +383,7 @@ class RetrievalEvaluator:
 
 
 class MetricsCalculator:
-    """The retrieval half of src/utils/metrics.py:951-972 (its detection half is ``DetectionEvaluator``)."""
+    """src/utils/metrics.py:877-972: the reference's front door to the three evaluators, each on its GPU path."""
 
     def __init__(self, engine: Optional[TVCEngine] = None):
         self.engine = engine
@@ -316,3 +395,20 @@ class MetricsCalculator:
                                     k_values: Sequence[int] = (1, 5, 10)) -> RetrievalMetrics:
         return self.retrieval_evaluator.evaluate_retrieval(query_embeddings, gallery_embeddings, query_labels, gallery_labels,
                                                            k_values, engine=self.engine)
+
+
+    def calculate_detection_metrics(self, predictions, labels) -> DetectionMetrics:
+        """src/utils/metrics.py:921-933 (``DetectionEvaluator.evaluate_scores``: the ROC sweep on the GPU)."""
+        return self.detection_evaluator.evaluate_scores(predictions, labels, engine=self.engine)
+
+    def calculate_similarity_metrics(self, embeddings1, embeddings2) -> Dict[str, float]:
+        """src/utils/metrics.py:935-949: ``compute_all_similarities`` of the two matrices, flattened into one pair, as a dict."""
+        return self.similarity_calculator.compute_all_similarities(embeddings1, embeddings2, engine=self.engine).to_dict()
+
+    def calculate_all_metrics(self, predictions, labels, embeddings1=None, embeddings2=None) -> Dict[str, Any]:
+        """src/utils/metrics.py:888-919 -> {'detection': the detection fields as a dict} and, when both matrices are given,
+        {'similarity': the five similarity metrics}."""
+        results: Dict[str, Any] = {"detection": self.calculate_detection_metrics(predictions, labels).to_dict()}
+        if embeddings1 is not None and embeddings2 is not None:
+            results["similarity"] = self.calculate_similarity_metrics(embeddings1, embeddings2)
+        return results

@@ -226,6 +226,63 @@ class MultiModalRetriever:
         raise ValueError(f"unsupported similarity metric: {self.config.similarity_metric}")
 
 
+class ConsistencyCalculator:
+    """src/retrieval.py:158-193: how far two retrievals of one query agree -- the overlap of their top-k ids, the Spearman
+    correlation of the two index lists and the Pearson correlation of the two similarity lists -- over the HIP row-pair kernels
+    (``TVCEngine.similarity_rows`` / ``similarity_flat`` / ``topk_overlap``).  The reference's four methods take one pair of
+    lists; the ``batch_*`` forms take [M, L] matrices, one row a query, and return [M] arrays from one launch each.  An undefined
+    correlation (a constant list, a single element, a NaN or inf element) is 0.0, as in the reference.  Similarities are taken
+    as fp32; ids are exact (int32).  ``compute_similarity_distribution`` is five numpy reductions of one array and stays on
+    the host."""
+
+    def __init__(self, engine=None):
+        self.engine = engine
+
+    def _eng(self):
+        from .metrics import _engine
+        return _engine(self.engine)
+
+    def compute_similarity_distribution(self, similarities) -> Dict[str, float]:
+        """src/retrieval.py:164-172 (numpy on the host)."""
+        s = np.asarray(similarities)
+        return {"mean": float(np.mean(s)), "std": float(np.std(s)), "min": float(np.min(s)), "max": float(np.max(s)),
+                "median": float(np.median(s))}
+
+    def compute_consistency_score(self, similarities1, similarities2) -> float:
+        """src/retrieval.py:174-177: the Pearson correlation of the two lists."""
+        v = self._eng().similarity_flat(np.asarray(similarities1), np.asarray(similarities2)).values[0, 3].item()
+        return 0.0 if v != v else float(v)
+
+    def compute_top_k_consistency(self, indices1, indices2, k: int) -> float:
+        """src/retrieval.py:179-184: ``len(set(indices1[:k]) & set(indices2[:k])) / k``, 1 <= k <= 1 024."""
+        return float(self.batch_top_k_consistency(np.asarray(indices1).reshape(1, -1), np.asarray(indices2).reshape(1, -1), k)[0])
+
+    def compute_rank_correlation(self, indices1, indices2) -> float:
+        """src/retrieval.py:186-193: the Spearman correlation of the two index lists (exact integer ranks)."""
+        a, b = np.asarray(indices1).reshape(-1), np.asarray(indices2).reshape(-1)
+        eng = self._eng()
+        if a.size <= eng.SIM_MAX_D:
+            return float(self.batch_rank_correlation(a.reshape(1, -1), b.reshape(1, -1))[0])
+        if max(np.abs(a).max(), np.abs(b).max()) > 1 << 24:
+            raise ValueError("index lists longer than 4 096 are ranked as fp32 values: ids beyond 2^24 would collide")
+        v = eng.similarity_flat(a, b).values[0, 4].item()
+        return 0.0 if v != v else float(v)
+
+    def batch_top_k_consistency(self, idx1, idx2, k: int) -> np.ndarray:
+        """idx1 int [M, L1], idx2 int [M, L2] -> fp64 [M]: the top-k overlap of every query's two lists, divided by k."""
+        return self._eng().topk_overlap(idx1, idx2, k).cpu().numpy().astype(np.float64) / np.float64(k)
+
+    def batch_rank_correlation(self, idx1, idx2) -> np.ndarray:
+        """idx1, idx2 int [M, L], L <= 4 096 -> fp64 [M]: Spearman of every query's two index lists (int32 keys)."""
+        v = self._eng().similarity_rows(idx1, idx2, key="i32").values[:, 4].cpu().numpy()
+        return np.where(np.isnan(v), 0.0, v)
+
+    def batch_consistency_score(self, sims1, sims2) -> np.ndarray:
+        """sims1, sims2 [M, L], L <= 4 096 -> fp64 [M]: Pearson of every query's two similarity lists."""
+        v = self._eng().similarity_rows(sims1, sims2).values[:, 3].cpu().numpy()
+        return np.where(np.isnan(v), 0.0, v)
+
+
 def extract_features(clip_model: CLIPModel, dataloader, encode_batch: int = 512):
     """scripts/build_faiss_indices.py:59-120 (``IndexBuilder.extract_features``): batches of
     ``{'image': Tensor [b,3,S,S], 'text': list[str], 'image_id': list}`` -> (image_features [R, D],

@@ -1,0 +1,99 @@
+"""CPU: the similarity-metric surface -- the reference's names exist (``metrics.SimilarityMetrics`` with its fields and
+``to_dict``, the ``SimilarityCalculator`` / ``MetricsCalculator`` functions, ``retrieval.ConsistencyCalculator`` with its four
+methods and the batch forms), the five entry points are declared in include/tvc.h, bound in _lib.SIGNATURES and exported by the
+built library without an ABI version bump, no other source references their unit, and the host code (tvc_sim.cpp: every
+refusal, the empty calls, the workspace sizing of host_plan.hpp) runs clean under AddressSanitizer / UBSan with leak detection
+(tests/host_san_sim/driver.cpp, a stand-alone program on tests/host_san's HIP stand-in: the build of
+test_retrieval_host_san.py with tvc_sim.cpp in place of tvc_rank.cpp)."""
+import dataclasses
+import inspect
+import os
+import re
+import subprocess
+import sys
+from pathlib import Path
+
+import pytest
+
+ROOT = Path(__file__).resolve().parents[1]
+NEW = {"tvc_sim_rows", "tvc_sim_flat_workspace", "tvc_sim_flat_rank", "tvc_sim_flat", "tvc_topk_overlap"}
+FIELDS = ["cosine_similarity", "euclidean_distance", "manhattan_distance", "pearson_correlation", "spearman_correlation"]
+
+
+def test_the_references_names_exist(pkg):
+    m = pkg.metrics.SimilarityMetrics()
+    assert [f.name for f in dataclasses.fields(m)] == FIELDS and all(getattr(m, f) == 0.0 for f in FIELDS)
+    assert list(pkg.metrics.SimilarityMetrics(1.0, 2.0, 3.0, 4.0, 5.0).to_dict().items()) == list(zip(FIELDS, (1.0, 2.0, 3.0, 4.0, 5.0)))
+    assert pkg.SimilarityMetrics is pkg.metrics.SimilarityMetrics and pkg.ConsistencyCalculator is pkg.retrieval.ConsistencyCalculator
+    for name in ("cosine_similarity", "batch_cosine_similarity", "euclidean_distance", "manhattan_distance", "pearson_correlation",
+                 "spearman_correlation", "compute_all_similarities", "rowwise_similarities"):
+        fn = getattr(pkg.metrics.SimilarityCalculator, name)
+        assert callable(fn) and "engine" in inspect.signature(fn).parameters, name
+    for name in ("calculate_all_metrics", "calculate_detection_metrics", "calculate_similarity_metrics", "calculate_retrieval_metrics"):
+        assert callable(getattr(pkg.metrics.MetricsCalculator, name)), name
+    assert list(inspect.signature(pkg.metrics.MetricsCalculator.calculate_all_metrics).parameters) == \
+        ["self", "predictions", "labels", "embeddings1", "embeddings2"]
+    cc = pkg.retrieval.ConsistencyCalculator()
+    for name, args in (("compute_similarity_distribution", ["similarities"]), ("compute_consistency_score", ["similarities1", "similarities2"]),
+                       ("compute_top_k_consistency", ["indices1", "indices2", "k"]), ("compute_rank_correlation", ["indices1", "indices2"])):
+        assert list(inspect.signature(getattr(cc, name)).parameters) == args, name
+    for name in ("batch_top_k_consistency", "batch_rank_correlation", "batch_consistency_score"):
+        assert callable(getattr(cc, name)), name
+    # the host-side method needs no GPU
+    d = cc.compute_similarity_distribution([0.0, 1.0, 2.0, 5.0])
+    assert d == {"mean": 2.0, "std": pytest.approx(1.8708286933869707), "min": 0.0, "max": 5.0, "median": 1.5}
+    for name in ("similarity_rows", "similarity_flat", "topk_overlap"):
+        assert callable(getattr(pkg.TVCEngine, name)), name
+    assert [f.name for f in dataclasses.fields(pkg.SimilarityRows)] == ["values", "ints"]
+    assert pkg.TVCEngine.SIM_MAX_D == 4096 and pkg.TVCEngine.SIM_MAX_N == 1 << 20 and pkg.TVCEngine.TOPK_OVERLAP_MAX_K == 1024
+
+
+def test_similarity_entry_points_declared_bound_and_exported(pkg):
+    h = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "tvc.h").read_text(), flags=re.S)
+    declared = set(re.findall(r"\b(tvc_[a-z0-9_]+)\s*\(", h))
+    assert NEW <= declared
+    assert NEW <= set(pkg._lib.SIGNATURES)
+    for name, nargs in (("tvc_sim_rows", 11), ("tvc_sim_flat_workspace", 1), ("tvc_sim_flat_rank", 7), ("tvc_sim_flat", 11), ("tvc_topk_overlap", 9)):
+        assert len(pkg._lib.SIGNATURES[name][1]) == nargs, name
+    for macro, value in (("TVC_SIM_MAX_D", 4096), ("TVC_SIM_MAX_N", 1048576), ("TVC_SIM_COLS", 8), ("TVC_SIM_INTS", 4), ("TVC_SIM_KEY_F32", 0),
+                         ("TVC_SIM_KEY_I32", 1), ("TVC_TOPK_OVERLAP_MAX_K", 1024)):
+        assert re.search(rf"#define {macro} {value}\b", h), macro
+    assert (pkg._lib.TVC_SIM_KEY_F32, pkg._lib.TVC_SIM_KEY_I32) == (0, 1)
+    lib = pkg._lib.load()
+    for name in NEW:
+        assert hasattr(lib, name)
+    out = subprocess.run(["nm", "-D", "--defined-only", str(pkg._lib.LIB_PATH)], capture_output=True, text=True).stdout
+    assert NEW <= set(re.findall(r"\bT (tvc_[a-z0-9_]+)", out))
+    assert lib.tvc_abi_version() == 4                        # additive: no ABI version bump
+    # the workspace query is host arithmetic: it runs without a GPU
+    assert [lib.tvc_sim_flat_workspace(n) for n in (0, 1, 4096, 4097, 1 << 20, (1 << 20) + 1)] == [0, 288, 288, 448, 8 * (16 + 20 * 256), 0]
+
+
+def test_no_existing_source_references_the_sim_unit():
+    """The other host-sanitizer tests compile fixed source lists without tvc_sim.cpp: nothing outside it may need its symbols."""
+    csrc = ROOT / "multimodal-detection-consistency_amd" / "csrc"
+    for p in sorted(csrc.glob("*.cpp")):
+        if p.name != "tvc_sim.cpp":
+            text = p.read_text()
+            for name in ("tvc_sim_", "tvc_topk_overlap", "launch_sim_", "launch_topk_overlap", "sim_flat_plan"):
+                assert name not in text, (p.name, name)
+
+
+def test_sim_host_code_under_address_and_ub_sanitizers(tmp_path):
+    csrc = ROOT / "multimodal-detection-consistency_amd" / "csrc"
+    san = ROOT / "tests" / "host_san"
+    stubs = tmp_path / "stubs.cpp"
+    subprocess.run([sys.executable, str(san / "gen_stubs.py"), str(csrc / "kernels.hpp"), str(stubs)], check=True)
+    text = stubs.read_text()
+    for name in ("launch_sim_rows", "launch_sim_flat_rank", "launch_sim_flat", "launch_topk_overlap"):
+        assert name in text, name
+    exe = tmp_path / "driver_sim"
+    srcs = ("tvc_abi.cpp", "tvc_precise.cpp", "tvc_split.cpp", "tvc_sd.cpp", "tvc_sd_op.cpp", "tvc_tower_op.cpp", "tvc_sim.cpp")
+    cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           f"-I{san}", f"-I{csrc}", "-x", "c++"] + [str(csrc / f) for f in srcs] + \
+          [str(stubs), str(ROOT / "tests" / "host_san_sim" / "driver.cpp"), "-o", str(exe)]
+    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert b.returncode == 0, b.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env=env)       # run directly: nothing is preloaded
+    assert r.returncode == 0 and "HOST_SAN_SIM_OK" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])
