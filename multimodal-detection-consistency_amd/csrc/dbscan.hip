@@ -20,23 +20,14 @@
 //           does not depend on the order; the number of sweeps does.  The finish numbers the roots by an exclusive scan,
 //           hands core rows their root's id and border rows the lowest id among their core neighbours.
 // Caller-supplied graphs are read defensively: a set bit beyond R or a label outside [0, R) is skipped, never dereferenced.
-#include "gemm_core.hpp"
-#include "kernels.hpp"
-#include "launch.hpp"
-#include "select.hpp"
+#include "slot_tile.hpp"
 
 // ---- graph -------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void radius_half_kernel(const float* __restrict__ norm2, int R, int hpad, float quarter_eps2,
-                                                          float* __restrict__ half) {
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= hpad) return;
-    float v = __builtin_nanf("");
-    if (r < R) {
-        const float n2 = norm2[r];
-        if (__builtin_isfinite(n2)) v = 0.5f * n2 - quarter_eps2;
-    }
-    half[r] = v;
-}
+// h from |x|^2 (launch_slot_row_vector)
+struct RadiusHalf {
+    float quarter_eps2;
+    __device__ __forceinline__ float operator()(float n2) const { return 0.5f * n2 - quarter_eps2; }
+};
 
 __global__ __launch_bounds__(GEMM_THREADS) void radius_tile_kernel(GemmOperands g, const float* __restrict__ half,
                                                                    uint32_t* __restrict__ adj, int R, int words) {
@@ -121,14 +112,11 @@ __global__ __launch_bounds__(256) void radius_degree_kernel(const uint32_t* __re
 hipError_t launch_radius_graph(const RadiusGraphLaunch& L, hipStream_t stream) {
     const BankRows& B = L.bank;
     const RadiusPlan& P = L.plan;
-    if (!P.ok || B.R < 1 || B.R > RADIUS_MAX_ROWS || P.words != (B.R + 63) / 64 * 2 || P.hpad < B.R || B.D < 64 || B.D % 64 != 0 ||
-        B.planes < 1 || B.planes > 2 || !(L.eps > 0.f) || !L.norm2 || !L.half || !L.adj || !L.degree)
+    if (!P.ok || !slot_tile_ok(B, RADIUS_MAX_ROWS) || P.words != (B.R + 63) / 64 * 2 || P.hpad < B.R || !(L.eps > 0.f) || !L.half ||
+        !L.adj || !L.degree)
         return hipErrorInvalidValue;
     const int R = (int)B.R, words = (int)P.words;
-    hipError_t st = launch_kmeans_rownorm(B, L.norm2, stream);
-    if (st != hipSuccess) return st;
-    st = launch<radius_half_kernel>(dim3((unsigned)((P.hpad + 255) / 256)), dim3(256), 0, stream, (const float*)L.norm2, R, (int)P.hpad,
-                                    0.25f * L.eps * L.eps, L.half);
+    hipError_t st = launch_slot_row_vector(B, L.half, P.hpad, RadiusHalf{0.25f * L.eps * L.eps}, stream);
     if (st != hipSuccess) return st;
     st = hipMemsetAsync(L.adj, 0, (size_t)P.adj_bytes, stream);
     if (st != hipSuccess) return st;

@@ -48,8 +48,8 @@ enum Slot {
     // split-bf16 input gradient (TVC_OPT_GRAD_PRECISION = 2, tvc_grad_split.cpp): what the forward keeps, the gradient's planes
     // (d-wide; mlp- / 3d-wide), fp32 scratch (mlp- / 3d- / Kp-wide; d-wide) and the head's small rows
     WS_GS_KEEP, WS_GS_GP, WS_GS_MP, WS_GS_WIDE, WS_GS_ROW, WS_GS_SMALL,
-    // radius graph over a bank slot (tvc_dbscan.cpp): the rows' squared norms and the padded half-norm vector of the distance test
-    WS_DB_NORM2, WS_DB_HALF,
+    // radius graph over a bank slot (tvc_dbscan.cpp): the padded half-norm vector of the distance test
+    WS_DB_HALF,
     // retrieval evaluation (tvc_rank.cpp): the query planes, the query labels and the last-target scores padded to whole tiles
     WS_RK_QPLANES, WS_RK_QLAB, WS_RK_TLOW,
     // detection evaluation (tvc_roc.cpp): the multiplicity rows of the global storage form, uint32 [chunk rows, N]

@@ -14,6 +14,10 @@ struct BankRows {
     int D = 0;
     int planes = 1;
 };
+// what every GEMM-tile pass over a slot needs of it (slot_operands, gemm_core.hpp): 1 .. max_rows rows of whole 64-column K-tiles
+inline bool slot_tile_ok(const BankRows& b, int64_t max_rows) {
+    return b.R >= 1 && b.R <= max_rows && b.D >= 64 && b.D % 64 == 0 && b.planes >= 1 && b.planes <= 2;
+}
 
 enum { TVC_EPI_F32 = 0, TVC_EPI_BF16 = 1, TVC_EPI_GELU_BF16 = 2, TVC_EPI_RESID_F32 = 3 };
 
@@ -291,7 +295,6 @@ struct RadiusGraphLaunch {
     BankRows bank;
     float eps = 0.f;
     RadiusPlan plan;                  // radius_plan(bank.R)
-    float* norm2 = nullptr;           // workspace [R]: |x|^2
     float* half = nullptr;            // workspace [plan.hpad]: |x|^2 / 2 - eps^2 / 4; NaN for a non-finite norm and in the padding
     uint32_t* adj = nullptr;          // [R, plan.words]: bit j of row i = (|x_i - x_j|^2 <= eps^2), symmetric, padding bits zero
     int32_t* degree = nullptr;        // [R]: popcount of the row, self included

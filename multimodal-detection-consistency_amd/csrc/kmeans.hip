@@ -2,13 +2,10 @@
 // an ASSIGN pass (nearest centre of every bank row) and an UPDATE pass (the mean of every cluster's rows).
 //
 //   assign  `kmeans_assign_kernel`: a workgroup owns 256 bank rows and walks the centre tiles.  Per 256 x 256 tile it runs
-//           the GEMM main loop with the CENTRES on the MFMA row dimension and the BANK ROWS on the lane dimension -- a lane
-//           holds 32 centres of one bank row per (m, n) block, so the running (best score, centre) of a row is four register
-//           pairs per lane and no score ever leaves the accumulators.  score = x.c - |c|^2 / 2 (arg-max = Euclidean nearest),
-//           the half norms come from an fp32 [K] vector padded to whole tiles with NaN: a padded centre can never win.
-//           The (score desc, centre asc) order is cand_better; NaN scores lose every comparison, a row whose scores are all
-//           NaN keeps the "none" index and gets label -1.  The four lane groups of a wave and the two wave rows that share
-//           a bank row are reduced once, after the last centre tile.
+//           the GEMM main loop with the CENTRES on the MFMA row dimension and the BANK ROWS on the lane dimension, and
+//           keeps each row's running (best score, centre) in slot_tile.hpp's SlotBest: no score leaves the accumulators.
+//           score = x.c - |c|^2 / 2 (arg-max = Euclidean nearest), the half norms come from an fp32 [K] vector padded to
+//           whole tiles with NaN: a padded centre can never win.  A row whose scores are all NaN gets label -1.
 //           Products as in the bank search (slot_operands, gemm_core.hpp): centres are split into (hi | lo) bf16 planes; a bf16
 //           bank multiplies both (exact products), an fp32 bank's planes take hi.hi + hi.lo + lo.hi.
 //   update  a counting sort -- per-block label histogram (integer atomics into the block's own counter row), a column
@@ -17,14 +14,9 @@
 //           sums its members in a fixed order in fp32.  No floating-point atomics: the centres are a pure function of
 //           (bank, labels).  The sort is a launch of its own (launch_label_sort): ivf.hip groups (query, probe) pairs by list
 //           with it, and takes the half norms of its centroids from kmeans_halfnorm_kernel.
-// The slot's rows arrive as a BankRows (kernels.hpp); the row kernels decode them with bank_row8 (common.hpp); the "no centre"
-// index CAND_NONE and the offsets' block-wide scan are select.hpp's.
-#include "gemm_core.hpp"
-#include "kernels.hpp"
-#include "launch.hpp"
-#include "select.hpp"
-
-#define KM_LDS_BYTES (GEMM_LDS_BYTES + 256 * 8)
+// The slot's rows arrive as a BankRows (kernels.hpp); the row kernels decode them with bank_row8 (common.hpp); the offsets'
+// block-wide scan is select.hpp's.
+#include "slot_tile.hpp"
 
 // ---- assign ------------------------------------------------------------------------------------------------------
 // halfnorm[k] = |c_k|^2 / 2 from the fp32 centres, k < K; NaN for the padding up to Kpad (a multiple of 256)
@@ -73,62 +65,27 @@ struct KmeansAssignArgs {
 
 __global__ __launch_bounds__(GEMM_THREADS) void kmeans_assign_kernel(GemmOperands g, KmeansAssignArgs e, int n_ctiles) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* red_v = (float*)(smem + GEMM_LDS_BYTES);        // the bests of wave row 1, per bank row of the tile
-    int* red_i = (int*)(red_v + 256);
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    const int wm = wave >> 2;
     const int j0 = blockIdx.x * GEMM_BN;
-    float bv[4];
-    int bi[4];
-#pragma unroll
-    for (int n = 0; n < 4; ++n) { bv[n] = -INFINITY; bi[n] = CAND_NONE; }
+    SlotBest best;
     for (int ct = 0; ct < n_ctiles; ++ct) {
         gemm_acc_t acc;
         gemm_zero_acc(acc);
         gemm_mainloop(acc, g, ct * GEMM_BM, j0, smem);
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const int c0 = gemm_acc_row(ct * GEMM_BM, wave, lane, m);
-            const f32x4_t hn = *(const f32x4_t*)(e.halfnorm + c0);
-#pragma unroll
-            for (int n = 0; n < 4; ++n) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float s = acc[m][n][r] - hn[r];
-                    if (cand_better(s, c0 + r, bv[n], bi[n])) { bv[n] = s; bi[n] = c0 + r; }
-                }
-            }
-        }
+        best.take(acc, e.halfnorm, ct * GEMM_BM, wave, lane, [](float a, float hn, int, int, float& s) {
+            s = a - hn;
+            return true;
+        });
     }
-    // the 4 lane groups of a wave, then the 2 wave rows, share a bank row
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-#pragma unroll
-        for (int o = 16; o <= 32; o <<= 1) {
-            const float ov = __shfl_xor(bv[n], o, 64);
-            const int oi = __shfl_xor(bi[n], o, 64);
-            if (cand_better(ov, oi, bv[n], bi[n])) { bv[n] = ov; bi[n] = oi; }
-        }
-        const int jl = gemm_acc_col(0, wave, lane, n);
-        if (wm == 1 && (lane >> 4) == 0) { red_v[jl] = bv[n]; red_i[jl] = bi[n]; }
-    }
-    __syncthreads();
-    if (wm == 0 && (lane >> 4) == 0) {
-#pragma unroll
-        for (int n = 0; n < 4; ++n) {
-            const int jl = gemm_acc_col(0, wave, lane, n);
-            const int row = j0 + jl;
-            if (row >= e.R) continue;
-            float v = bv[n];
-            int i = bi[n];
-            if (cand_better(red_v[jl], red_i[jl], v, i)) { v = red_v[jl]; i = red_i[jl]; }
-            const bool none = i == CAND_NONE;
-            e.labels[row] = none ? -1 : i;
-            if (e.score) e.score[row] = v;
-            if (e.dist2) e.dist2[row] = none ? 0.f : fmaxf(0.f, e.dist2[row] - 2.f * v);
-        }
-    }
+    best.finish(smem, wave, lane, [&](int jl, float v, int i) {
+        const int row = j0 + jl;
+        if (row >= e.R) return;
+        const bool none = i == CAND_NONE;
+        e.labels[row] = none ? -1 : i;
+        if (e.score) e.score[row] = v;
+        if (e.dist2) e.dist2[row] = none ? 0.f : fmaxf(0.f, e.dist2[row] - 2.f * v);
+    });
 }
 
 hipError_t launch_kmeans_halfnorm(const float* centroids, int D, int K, int Kpad, float* halfnorm, hipStream_t stream) {
@@ -142,8 +99,7 @@ hipError_t launch_kmeans_rownorm(const BankRows& bank, float* out, hipStream_t s
 
 hipError_t launch_kmeans_assign(const KmeansAssignLaunch& L, hipStream_t stream) {
     const BankRows& B = L.bank;
-    if (B.R < 1 || B.R > 0x7fffffffLL || L.K < 1 || B.D < 64 || B.D % 64 != 0 || B.planes < 1 || B.planes > 2)
-        return hipErrorInvalidValue;
+    if (!slot_tile_ok(B, 0x7fffffffLL) || L.K < 1) return hipErrorInvalidValue;
     const int n_ctiles = (L.K + GEMM_BM - 1) / GEMM_BM;
     const int Kpad = n_ctiles * GEMM_BM;
     hipError_t st = launch_kmeans_halfnorm(L.centroids, B.D, L.K, Kpad, L.halfnorm, stream);
@@ -157,7 +113,7 @@ hipError_t launch_kmeans_assign(const KmeansAssignLaunch& L, hipStream_t stream)
     KmeansAssignArgs e;
     e.halfnorm = L.halfnorm; e.labels = L.labels; e.score = L.score; e.dist2 = L.dist2; e.R = (int)B.R;
     const int64_t n_btiles = (B.R + GEMM_BN - 1) / GEMM_BN;
-    return launch<kmeans_assign_kernel, KM_LDS_BYTES>(dim3((unsigned)n_btiles), dim3(GEMM_THREADS), KM_LDS_BYTES, stream, g, e, n_ctiles);
+    return launch<kmeans_assign_kernel, SLOT_BEST_LDS_BYTES>(dim3((unsigned)n_btiles), dim3(GEMM_THREADS), SLOT_BEST_LDS_BYTES, stream, g, e, n_ctiles);
 }
 
 // ---- update ------------------------------------------------------------------------------------------------------
@@ -295,8 +251,7 @@ hipError_t launch_label_sort(const LabelSortLaunch& L, hipStream_t stream) {
 
 hipError_t launch_kmeans_update(const KmeansUpdateLaunch& L, hipStream_t stream) {
     const BankRows& B = L.bank;
-    if (B.R < 1 || B.R > 0x7fffffffLL || L.K < 1 || B.D < 64 || B.D % 64 != 0 || B.planes < 1 || B.planes > 2 ||
-        L.nblocks < 1 || L.rows_per_block < 1 || (int64_t)L.nblocks * L.rows_per_block < B.R)
+    if (!slot_tile_ok(B, 0x7fffffffLL) || L.K < 1 || L.nblocks < 1 || L.rows_per_block < 1 || (int64_t)L.nblocks * L.rows_per_block < B.R)
         return hipErrorInvalidValue;
     LabelSortLaunch S;
     S.labels = L.labels; S.R = B.R; S.K = L.K; S.nblocks = L.nblocks; S.rows_per_block = L.rows_per_block;

@@ -186,8 +186,7 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(RankMetricsArgs a) {
 template <bool COUNT>
 static hipError_t launch_rank_tile(const RankTileLaunch& L, hipStream_t stream) {
     const BankRows& B = L.bank;
-    if (B.R < 1 || B.R > 0x7fffffffLL || L.M < 1 || B.D < 64 || B.D % 64 != 0 || B.planes < 1 || B.planes > 2)
-        return hipErrorInvalidValue;
+    if (!slot_tile_ok(B, 0x7fffffffLL) || L.M < 1) return hipErrorInvalidValue;
     const int n_qtiles = (L.M + GEMM_BM - 1) / GEMM_BM;
     const int Mpad = n_qtiles * GEMM_BM;
     hipError_t st = launch<rank_prep_kernel>(dim3((Mpad + 255) / 256), dim3(256), 0, stream, L.qlabel, L.M, Mpad,

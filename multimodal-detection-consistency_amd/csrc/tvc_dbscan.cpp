@@ -19,11 +19,10 @@ int tvc_radius_graph(tvc_handle* h, float eps, uint32_t* adj_dev, int32_t* degre
     hipStream_t st = (hipStream_t)stream;
     RadiusGraphLaunch L;
     L.plan = radius_plan(bk.R);
-    if ((rc = ensure(h, WS_DB_NORM2, (size_t)bk.R * 4))) return rc;
     if ((rc = ensure(h, WS_DB_HALF, (size_t)L.plan.hpad * 4))) return rc;
     L.bank = bank_rows(bk);
     L.eps = eps;
-    L.norm2 = (float*)h->ws[WS_DB_NORM2].p; L.half = (float*)h->ws[WS_DB_HALF].p;
+    L.half = (float*)h->ws[WS_DB_HALF].p;
     L.adj = adj_dev; L.degree = degree_dev;
     const int products = bk.planes == 2 ? 4 : 1;
     ProfScope ps(h, st, TVC_PROF_BANK, 2.0 * L.plan.tile_pairs * HOST_PLAN_GEMM_BM * HOST_PLAN_GEMM_BN * bk.D * products);

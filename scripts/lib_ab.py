@@ -1,6 +1,6 @@
 """Bit-identity of two builds of libtvc_hip.so (a refactor against its parent commit):
 
-    python scripts/lib_ab.py OLD.so NEW.so [--timeout 240] [--keep DIR] [--only attention|bank|cluster|sd]
+    python scripts/lib_ab.py OLD.so NEW.so [--timeout 240] [--keep DIR] [--only attention|bank|cluster|sd|slot]
 
 One fresh child process per library (selected with TVC_LIB_PATH, each child under its own ``timeout -k 10``; the second starts
 only if the first exited 0).  A child runs seed-fixed inputs through the library and writes one .npy file per result; the
@@ -16,7 +16,9 @@ the adds); the bank search (bank_cases below: every filter kernel, both tau kern
 shard merge; the children inherit TVC_BANK_RING / TVC_BANK_SKINNY / TVC_BANK_SKINNY_SAMPLE, so a run with all three at 0
 reaches bank_search_kernel<true> and the dense sample for small M); k-means on a bank slot and the IVF search (cluster_cases
 below: assign and update with an empty cluster and an out-of-range label, the probe, the scan with padding and with the select's
-LDS and global-memory paths); the latent-diffusion generator end to end (sd_cases below: the UNet at two sizes, the VAE decode,
+LDS and global-memory paths); the other tile passes over a slot (slot_cases below: the closest pair over three row tiles and
+over a single row, the radius graph at its median distance, the retrieval ranks' two tile passes and metrics, each on a bf16
+and an fp32 slot); the latent-diffusion generator end to end (sd_cases below: the UNet at two sizes, the VAE decode,
 the sampling loop on two streams and on one, chunked, and with v-prediction, all six block kinds, in bf16 and in fp16); the
 five swapped-MFMA attention kernels at every instantiation their launchers can pick (attention_cases below: attention_ex in bf16 and fp16 -- <17, EXACT>, <4, EXACT>, <2>, <6>, <18>, <4, WPS 2>, the causal
 <2>, <6>, <18> on packed rows with and without shared prefixes, both pooled forms --, attention_split_ex's six, attention_backward
@@ -182,6 +184,41 @@ def cluster_cases(pkg, save) -> None:
     eng.close()
 
 
+def slot_cases(pkg, save) -> None:
+    """The GEMM-tile passes over a bank slot that cluster_cases does not reach, on a bf16 and an fp32 slot: the closest pair
+    (nearest.hip) at R = 700 -- three row tiles: diagonal tiles, off-diagonal tiles and padding -- and at R = 1; the radius graph
+    (dbscan.hip) at R = 513 with eps = the median pairwise distance of the rows, so about half the bits are set; the retrieval
+    ranks (rank.hip: both tile passes and the metrics) of 300 queries over 1000 rows under 20 labels."""
+    import torch
+    eng = pkg.TVCEngine()
+    dev = eng.device
+
+    def unit(shape, seed):
+        return torch.nn.functional.normalize(torch.randn(shape, generator=torch.Generator().manual_seed(seed)), dim=-1)
+
+    D = 128
+    X700, X513, X1000, Q = unit((700, D), 61), unit((513, D), 62), unit((1000, D), 63), unit((300, D), 64).to(dev)
+    i, j = torch.triu_indices(513, 513, offset=1)
+    eps = float(torch.cdist(X513.double(), X513.double())[i, j].median())
+    g = torch.Generator().manual_seed(65)
+    qlabels, glabels = torch.randint(0, 20, (300,), generator=g), torch.randint(0, 20, (1000,), generator=g)
+    for tag, dt in (("bf16", torch.bfloat16), ("f32", torch.float32)):
+        for R in (700, 1):
+            eng.set_bank(X700[:R].to(dt).to(dev), name="ab")
+            for name, t in zip(("pair", "pair_sim", "partner", "sim"), eng.closest_pair(bank="ab")):
+                save(f"nn_{tag}_{R}_{name}", t)
+        eng.set_bank(X513.to(dt).to(dev), name="ab")
+        adj, degree = eng.radius_graph(eps, bank="ab")
+        save(f"radius_{tag}_adj", adj)
+        save(f"radius_{tag}_degree", degree)
+        eng.set_bank(X1000.to(dt).to(dev), name="ab")
+        rk = eng.retrieval_ranks(Q, qlabels, glabels, bank="ab")
+        for name in ("tgt_off", "tgt_row", "tgt_sim", "pos", "hist", "ap", "rr", "hits", "dcg", "idcg"):
+            save(f"rank_{tag}_{name}", getattr(rk, name))
+    torch.cuda.synchronize()
+    eng.close()
+
+
 def sd_cases(pkg, save) -> None:
     """Every latent-diffusion entry point that runs the model's host code (csrc/tvc_sd.cpp) at the toy geometry, in both 16-bit
     formats: tvc_sd_unet (n = 2 at 16 x 16, n = 3 at 8 x 24), tvc_sd_vae_decode (n = 3), tvc_sd_generate of 6 steps with
@@ -335,7 +372,7 @@ def child(out_dir: Path, only: str = "") -> None:
         np.save(out_dir / (name + ".npy"), t.numpy())
 
     if only:
-        {"attention": attention_cases, "bank": bank_cases, "cluster": cluster_cases, "sd": sd_cases}[only](pkg, save)
+        {"attention": attention_cases, "bank": bank_cases, "cluster": cluster_cases, "sd": sd_cases, "slot": slot_cases}[only](pkg, save)
         return
 
     arch = pkg.get_arch("ViT-T/16-test")
@@ -387,6 +424,7 @@ def child(out_dir: Path, only: str = "") -> None:
     eng.close()
     bank_cases(pkg, save)
     cluster_cases(pkg, save)
+    slot_cases(pkg, save)
     sd_cases(pkg, save)
     attention_cases(pkg, save)
 
@@ -397,7 +435,7 @@ def main() -> int:
     ap.add_argument("new")
     ap.add_argument("--timeout", type=int, default=240, help="seconds per child")
     ap.add_argument("--keep", default=None, help="directory that keeps the .npy files (default: a temporary one)")
-    ap.add_argument("--only", default="", choices=("", "attention", "bank", "cluster", "sd"), help="one *_cases function alone")
+    ap.add_argument("--only", default="", choices=("", "attention", "bank", "cluster", "sd", "slot"), help="one *_cases function alone")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
