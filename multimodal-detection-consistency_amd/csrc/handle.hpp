@@ -190,13 +190,10 @@ int split_layers_keep(tvc_handle* h, int n_seq, int seq_len, const SplitKeep& ke
 int split_gemm3(tvc_handle* h, const uint16_t* Ws, int I, int K, const uint16_t* Bs, int64_t J, const float* bias, float* out,
                 int64_t ldo, hipStream_t st);
 
-// The split-bf16 input gradient (TVC_OPT_GRAD_PRECISION = 2) registers its two drivers here when tvc_grad_split.cpp is linked:
-// tvc_encode_image_grad / _backward (tvc_abi.cpp) reach it through this table, so the C-ABI also links without that unit.
-struct GradSplitOps {
-    int (*forward)(tvc_handle* h, const float* pix, int B, float* out, int normalize, hipStream_t st);
-    int (*backward)(tvc_handle* h, const float* grad_out, float* grad_pix, hipStream_t st);
-};
-inline const GradSplitOps* g_grad_split_ops = nullptr;
+// The two drivers of the split-bf16 input gradient (TVC_OPT_GRAD_PRECISION = 2; tvc_grad_split.cpp): tvc_encode_image_grad /
+// _backward (tvc_abi.cpp) check the arguments both modes share and call these.
+int grad_split_forward(tvc_handle* h, const float* pix, int B, float* out, int normalize, hipStream_t st);
+int grad_split_backward(tvc_handle* h, const float* grad_out, float* grad_pix, hipStream_t st);
 
 inline int fail(tvc_handle* h, int code, const std::string& msg) {
     if (h) h->err = msg; else g_create_error = msg;

@@ -657,9 +657,8 @@ int tvc_encode_image_grad(tvc_handle* h, const float* pix_dev, int32_t B, float*
     if (h->desc.vision.act != TVC_ACT_QUICK_GELU) return fail(h, TVC_E_INVALID, "tvc_encode_image_grad: only QuickGELU towers have a backward pass");
     hipStream_t st = (hipStream_t)stream;
     if (h->grad_precision == 2) {            // the split-bf16 path (tvc_grad_split.cpp)
-        if (!g_grad_split_ops) return fail(h, TVC_E_STATE, "tvc_encode_image_grad: this build has no split-bf16 gradient (TVC_OPT_GRAD_PRECISION = 2)");
         h->grad_B = 0;                       // a failed forward leaves nothing for a backward
-        const int rc2 = g_grad_split_ops->forward(h, pix_dev, B, out_dev, normalize, st);
+        const int rc2 = grad_split_forward(h, pix_dev, B, out_dev, normalize, st);
         if (rc2) return rc2;
         h->grad_B = B; h->grad_normalize = normalize; h->grad_pix = pix_dev; h->grad_mode = 2;
         return TVC_OK;
@@ -706,10 +705,7 @@ int tvc_encode_image_backward(tvc_handle* h, const float* grad_out_dev, float* g
         return fail(h, TVC_E_STATE, "tvc_encode_image_backward: TVC_OPT_GRAD_PRECISION changed since tvc_encode_image_grad (it ran in mode " +
                                         std::to_string(h->grad_mode) + "): a forward / backward pair runs in one mode");
     hipStream_t st = (hipStream_t)stream;
-    if (h->grad_mode == 2) {
-        if (!g_grad_split_ops) return fail(h, TVC_E_STATE, "tvc_encode_image_backward: this build has no split-bf16 gradient");
-        return g_grad_split_ops->backward(h, grad_out_dev, grad_pix_dev, st);
-    }
+    if (h->grad_mode == 2) return grad_split_backward(h, grad_out_dev, grad_pix_dev, st);
     const tvc_model_desc& m = h->desc;
     const tvc_tower_arch& a = m.vision;
     const int B = h->grad_B, gside = m.image_size / m.patch, P = gside * gside, T = P + 1, d = a.width, D = m.embed_dim;

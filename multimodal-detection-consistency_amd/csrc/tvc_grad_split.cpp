@@ -10,8 +10,7 @@
 // Backward, per layer (dX = the fp32 gradient of the residual stream, Gp = its planes):
 //     dM = W2^T_s x Gp              dU = dM gelu'(U)           R = W1^T_s x split(dU)        dX += ln_2'(X + D1; R)
 //     dAO = Wo^T_s x Gp             dQKV = attention'(QKV, dAO)   R = Wqkv^T_s x split(dQKV)   dX += ln_1'(X; R)
-// The drivers register themselves in g_grad_split_ops (handle.hpp); tvc_abi.cpp owns the argument checks they share with
-// the bf16 path.
+// The two drivers are declared in handle.hpp; tvc_abi.cpp owns the argument checks they share with the bf16 path.
 #include "handle.hpp"
 
 #include <initializer_list>
@@ -77,7 +76,9 @@ Keep keep_of(tvc_handle* h, const GradSplitKeepPlan& p) {
     return k;
 }
 
-int forward(tvc_handle* h, const float* pix, int B, float* out, int normalize, hipStream_t st) {
+}  // namespace
+
+int grad_split_forward(tvc_handle* h, const float* pix, int B, float* out, int normalize, hipStream_t st) {
     if (!h->vision32.set)
         return fail(h, TVC_E_STATE, std::string(FWD) + ": TVC_OPT_GRAD_PRECISION = 2 needs tvc_set_weights_f32 (vision)");
     if (!h->split_ready || h->vsplit.empty() || !h->vsplit_patch)
@@ -107,7 +108,7 @@ int forward(tvc_handle* h, const float* pix, int B, float* out, int normalize, h
     return TVC_OK;
 }
 
-int backward(tvc_handle* h, const float* grad_out, float* grad_pix, hipStream_t st) {
+int grad_split_backward(tvc_handle* h, const float* grad_out, float* grad_pix, hipStream_t st) {
     if (!h->vision32.set || !h->split_ready || h->vsplit.empty() || !h->ws[WS_GS_KEEP].p)
         return fail(h, TVC_E_STATE, std::string(BWD) + ": the fp32 weights or their split planes changed since tvc_encode_image_grad");
     const Geo g = geo(h, h->grad_B);
@@ -189,11 +190,6 @@ int backward(tvc_handle* h, const float* grad_out, float* grad_pix, hipStream_t 
     HIP_TRY(launch_col2im(W, grad_pix, B, h->desc.image_size, h->desc.patch, g.Kp, st));
     return TVC_OK;
 }
-
-const GradSplitOps OPS = {forward, backward};
-const bool registered = (g_grad_split_ops = &OPS, true);
-
-}  // namespace
 
 // ---- building blocks exported for parity tests (include/tvc.h)
 // tvc_grad_split_op: ONE fp32 row kernel of the split-bf16 backward on the caller's buffers, under tvc_tower_op's rules -- every

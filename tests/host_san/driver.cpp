@@ -1,30 +1,14 @@
 // Host-only sanitizer driver of the C-ABI (tests/test_abi_and_host.py::test_host_code_under_address_and_ub_sanitizers):
-// g++ -fsanitize=address,undefined builds tvc_abi.cpp, tvc_precise.cpp, tvc_split.cpp and tvc_sd.cpp against the HIP
-// stand-in of this directory (kernels = no-ops, "device" memory = host blocks with known sizes) and walks their host
+// tests/host_san_build.py builds the product's host sources under ASan / UBSan against the HIP
+// stand-in of this directory (kernels = no-ops, "device" memory = host blocks with known sizes); this program walks their host
 // logic: descriptor validation, workspace sizing, weight maps, the arena's dry / real passes, prefix-string dispatch,
 // option handling, chunking, the error paths.  argv[1]: file of SD tensor names (one "name rows cols dtype" per line).
-#include "../../include/tvc.h"
-#include <hip/hip_runtime.h>
+#include "driver_common.hpp"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <fstream>
 #include <sstream>
 #include <string>
 #include <vector>
-
-#define CHECK(cond)                                                                              \
-    do {                                                                                         \
-        if (!(cond)) { fprintf(stderr, "driver.cpp:%d: CHECK failed: %s\n", __LINE__, #cond); return 1; } \
-    } while (0)
-#define OK(call)                                                                                           \
-    do {                                                                                                   \
-        int rc__ = (call);                                                                                 \
-        if (rc__ != TVC_OK) { fprintf(stderr, "driver.cpp:%d: %s -> %d (%s)\n", __LINE__, #call, rc__, tvc_last_error(h)); return 1; } \
-    } while (0)
-
-static void* dev(size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) abort(); return p; }
 
 int main(int argc, char** argv) {
     CHECK(argc >= 2);

@@ -1,34 +1,12 @@
-// Host-only sanitizer driver of the FSTA / SMA attack entry points (tests/test_attack_host.py): tvc_abi.cpp ... tvc_attack.cpp
-// with g++ -fsanitize=address,undefined against tests/host_san's HIP stand-in (kernels are no-ops, "device" blocks are exactly
+// Host-only sanitizer driver of the FSTA / SMA attack entry points (tests/test_attack_host.py), built by
+// tests/host_san_build.py under ASan / UBSan against tests/host_san's HIP stand-in (kernels are no-ops, "device" blocks are exactly
 // sized host blocks).  Walks every refusal of tvc_attack_feature_grad / tvc_attack_step (no handle, negative sizes, unknown
 // metric / norm, NULL buffers, an output aliasing an input, a bad eps or clamp range), the zero-size no-ops (which take NULL
 // buffers), valid calls of both metrics and both norms, and a leak-free tvc_destroy: neither call may allocate.
-#include "../../include/tvc.h"
-#include <hip/hip_runtime.h>
+#include "driver_common.hpp"
 
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
-
-#define CHECK(cond)                                                                              \
-    do {                                                                                         \
-        if (!(cond)) { fprintf(stderr, "driver.cpp:%d: CHECK failed: %s\n", __LINE__, #cond); return 1; } \
-    } while (0)
-#define OK(call)                                                                                           \
-    do {                                                                                                   \
-        int rc__ = (call);                                                                                 \
-        if (rc__ != TVC_OK) { fprintf(stderr, "driver.cpp:%d: %s -> %d (%s)\n", __LINE__, #call, rc__, tvc_last_error(h)); return 1; } \
-    } while (0)
-// a refusal through fail(): TVC_E_INVALID and a message that names the entry point
-#define REFUSED(call, fn)                                                                        \
-    do {                                                                                         \
-        CHECK((call) == TVC_E_INVALID);                                                          \
-        CHECK(strstr(tvc_last_error(h), fn) != nullptr);                                         \
-    } while (0)
-
-static void* dev(size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) abort(); return p; }
 
 int main() {
     tvc_handle* h = nullptr;
@@ -46,19 +24,19 @@ int main() {
 
     // ---- tvc_attack_feature_grad
     CHECK(tvc_attack_feature_grad(nullptr, f, t, g, B, D, -1.f, 1.f, COS, 0.1f, 0.05f, grad, rows, nullptr) == TVC_E_INVALID);
-    REFUSED(tvc_attack_feature_grad(h, f, t, g, -1, D, -1.f, 1.f, COS, 0.1f, 0.05f, grad, rows, nullptr), FG);
-    REFUSED(tvc_attack_feature_grad(h, f, t, g, B, -1, -1.f, 1.f, COS, 0.1f, 0.05f, grad, rows, nullptr), FG);
-    REFUSED(tvc_attack_feature_grad(h, f, t, g, B, D, -1.f, 1.f, 2, 0.1f, 0.05f, grad, rows, nullptr), FG);
-    REFUSED(tvc_attack_feature_grad(h, f, t, g, B, D, -1.f, 1.f, -1, 0.1f, 0.05f, grad, rows, nullptr), FG);
-    REFUSED(tvc_attack_feature_grad(h, f, t, g, 0, D, -1.f, 1.f, 7, 0.1f, 0.05f, grad, rows, nullptr), FG);      // also at size 0
-    REFUSED(tvc_attack_feature_grad(h, nullptr, t, g, B, D, -1.f, 1.f, COS, 0.1f, 0.05f, grad, rows, nullptr), FG);
-    REFUSED(tvc_attack_feature_grad(h, f, nullptr, g, B, D, -1.f, 1.f, COS, 0.1f, 0.05f, grad, rows, nullptr), FG);
-    REFUSED(tvc_attack_feature_grad(h, f, t, nullptr, B, D, -1.f, 1.f, COS, 0.1f, 0.05f, grad, rows, nullptr), FG);
-    REFUSED(tvc_attack_feature_grad(h, f, t, g, B, D, -1.f, 1.f, COS, 0.1f, 0.05f, nullptr, rows, nullptr), FG);
-    REFUSED(tvc_attack_feature_grad(h, f, t, g, B, D, -1.f, 1.f, COS, 0.1f, 0.05f, grad, nullptr, nullptr), FG);
-    REFUSED(tvc_attack_feature_grad(h, f, t, g, B, D, -1.f, 1.f, COS, 0.1f, 0.05f, f, rows, nullptr), FG);       // grad aliases f
-    REFUSED(tvc_attack_feature_grad(h, f, t, g, B, D, -1.f, 1.f, COS, 0.1f, 0.05f, t, rows, nullptr), FG);
-    REFUSED(tvc_attack_feature_grad(h, f, t, g, B, D, -1.f, 1.f, EUC, 0.1f, 0.05f, g, rows, nullptr), FG);
+    REFUSED(tvc_attack_feature_grad(h, f, t, g, -1, D, -1.f, 1.f, COS, 0.1f, 0.05f, grad, rows, nullptr), TVC_E_INVALID, FG);
+    REFUSED(tvc_attack_feature_grad(h, f, t, g, B, -1, -1.f, 1.f, COS, 0.1f, 0.05f, grad, rows, nullptr), TVC_E_INVALID, FG);
+    REFUSED(tvc_attack_feature_grad(h, f, t, g, B, D, -1.f, 1.f, 2, 0.1f, 0.05f, grad, rows, nullptr), TVC_E_INVALID, FG);
+    REFUSED(tvc_attack_feature_grad(h, f, t, g, B, D, -1.f, 1.f, -1, 0.1f, 0.05f, grad, rows, nullptr), TVC_E_INVALID, FG);
+    REFUSED(tvc_attack_feature_grad(h, f, t, g, 0, D, -1.f, 1.f, 7, 0.1f, 0.05f, grad, rows, nullptr), TVC_E_INVALID, FG);      // also at size 0
+    REFUSED(tvc_attack_feature_grad(h, nullptr, t, g, B, D, -1.f, 1.f, COS, 0.1f, 0.05f, grad, rows, nullptr), TVC_E_INVALID, FG);
+    REFUSED(tvc_attack_feature_grad(h, f, nullptr, g, B, D, -1.f, 1.f, COS, 0.1f, 0.05f, grad, rows, nullptr), TVC_E_INVALID, FG);
+    REFUSED(tvc_attack_feature_grad(h, f, t, nullptr, B, D, -1.f, 1.f, COS, 0.1f, 0.05f, grad, rows, nullptr), TVC_E_INVALID, FG);
+    REFUSED(tvc_attack_feature_grad(h, f, t, g, B, D, -1.f, 1.f, COS, 0.1f, 0.05f, nullptr, rows, nullptr), TVC_E_INVALID, FG);
+    REFUSED(tvc_attack_feature_grad(h, f, t, g, B, D, -1.f, 1.f, COS, 0.1f, 0.05f, grad, nullptr, nullptr), TVC_E_INVALID, FG);
+    REFUSED(tvc_attack_feature_grad(h, f, t, g, B, D, -1.f, 1.f, COS, 0.1f, 0.05f, f, rows, nullptr), TVC_E_INVALID, FG);       // grad aliases f
+    REFUSED(tvc_attack_feature_grad(h, f, t, g, B, D, -1.f, 1.f, COS, 0.1f, 0.05f, t, rows, nullptr), TVC_E_INVALID, FG);
+    REFUSED(tvc_attack_feature_grad(h, f, t, g, B, D, -1.f, 1.f, EUC, 0.1f, 0.05f, g, rows, nullptr), TVC_E_INVALID, FG);
     OK(tvc_attack_feature_grad(h, nullptr, nullptr, nullptr, 0, D, -1.f, 1.f, COS, 0.1f, 0.05f, nullptr, nullptr, nullptr));   // B = 0
     OK(tvc_attack_feature_grad(h, nullptr, nullptr, nullptr, B, 0, -1.f, 1.f, EUC, 0.1f, 0.05f, nullptr, nullptr, nullptr));   // D = 0
     OK(tvc_attack_feature_grad(h, f, t, g, B, D, -1.f, 1.f, COS, 0.1f, 0.05f, grad, rows, nullptr));
@@ -69,20 +47,20 @@ int main() {
     // ---- tvc_attack_step
     const float eps = 0.031f, lr = 0.01f, mu = 0.9f;
     CHECK(tvc_attack_step(nullptr, adv, clean, gp, mom, B, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, INF, nullptr) == TVC_E_INVALID);
-    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, -1, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, INF, nullptr), ST);
-    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, B, -1, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, INF, nullptr), ST);
-    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, B, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, 2, nullptr), ST);
-    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, B, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, -1, nullptr), ST);
-    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, B, n, -eps, lr, mu, 1.f, 0.f, 0.f, 1.f, INF, nullptr), ST);
-    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, B, n, NAN, lr, mu, 1.f, 0.f, 0.f, 1.f, L2, nullptr), ST);
-    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, B, n, eps, lr, mu, 1.f, 0.f, 1.f, 0.f, INF, nullptr), ST);   // clip_min > clip_max
-    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, B, n, eps, lr, mu, 1.f, 0.f, NAN, 1.f, INF, nullptr), ST);
-    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, 0, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, 9, nullptr), ST);     // also at size 0
-    REFUSED(tvc_attack_step(h, nullptr, clean, gp, mom, B, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, INF, nullptr), ST);
-    REFUSED(tvc_attack_step(h, adv, nullptr, gp, mom, B, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, INF, nullptr), ST);
-    REFUSED(tvc_attack_step(h, adv, clean, nullptr, mom, B, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, L2, nullptr), ST);
-    REFUSED(tvc_attack_step(h, adv, clean, gp, nullptr, B, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, INF, nullptr), ST);   // mom is required
-    REFUSED(tvc_attack_step(h, adv, clean, gp, nullptr, B, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, L2, nullptr), ST);
+    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, -1, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, INF, nullptr), TVC_E_INVALID, ST);
+    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, B, -1, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, INF, nullptr), TVC_E_INVALID, ST);
+    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, B, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, 2, nullptr), TVC_E_INVALID, ST);
+    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, B, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, -1, nullptr), TVC_E_INVALID, ST);
+    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, B, n, -eps, lr, mu, 1.f, 0.f, 0.f, 1.f, INF, nullptr), TVC_E_INVALID, ST);
+    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, B, n, NAN, lr, mu, 1.f, 0.f, 0.f, 1.f, L2, nullptr), TVC_E_INVALID, ST);
+    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, B, n, eps, lr, mu, 1.f, 0.f, 1.f, 0.f, INF, nullptr), TVC_E_INVALID, ST);   // clip_min > clip_max
+    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, B, n, eps, lr, mu, 1.f, 0.f, NAN, 1.f, INF, nullptr), TVC_E_INVALID, ST);
+    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, 0, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, 9, nullptr), TVC_E_INVALID, ST);     // also at size 0
+    REFUSED(tvc_attack_step(h, nullptr, clean, gp, mom, B, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, INF, nullptr), TVC_E_INVALID, ST);
+    REFUSED(tvc_attack_step(h, adv, nullptr, gp, mom, B, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, INF, nullptr), TVC_E_INVALID, ST);
+    REFUSED(tvc_attack_step(h, adv, clean, nullptr, mom, B, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, L2, nullptr), TVC_E_INVALID, ST);
+    REFUSED(tvc_attack_step(h, adv, clean, gp, nullptr, B, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, INF, nullptr), TVC_E_INVALID, ST);   // mom is required
+    REFUSED(tvc_attack_step(h, adv, clean, gp, nullptr, B, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, L2, nullptr), TVC_E_INVALID, ST);
     OK(tvc_attack_step(h, nullptr, nullptr, nullptr, nullptr, 0, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, INF, nullptr));  // B = 0
     OK(tvc_attack_step(h, nullptr, nullptr, nullptr, nullptr, B, 0, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, L2, nullptr));   // n = 0
     OK(tvc_attack_step(h, adv, clean, gp, mom, B, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, INF, nullptr));
@@ -92,8 +70,8 @@ int main() {
 
     CHECK(tvc_workspace_bytes(h) == ws0);                           // neither call owns a workspace
     // a successful call does not clear the last refusal's message; a refusal replaces it
-    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, B, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, 5, nullptr), ST);
-    REFUSED(tvc_attack_feature_grad(h, f, t, g, B, D, -1.f, 1.f, 5, 0.f, 0.f, grad, rows, nullptr), FG);
+    REFUSED(tvc_attack_step(h, adv, clean, gp, mom, B, n, eps, lr, mu, 1.f, 0.f, 0.f, 1.f, 5, nullptr), TVC_E_INVALID, ST);
+    REFUSED(tvc_attack_feature_grad(h, f, t, g, B, D, -1.f, 1.f, 5, 0.f, 0.f, grad, rows, nullptr), TVC_E_INVALID, FG);
     tvc_destroy(h);
     for (void* p : keep) (void)hipFree(p);
     CHECK(hip_stub_blocks().empty());                               // every handle-owned device block was released

@@ -1,36 +1,14 @@
-// Host-only sanitizer driver of the radius-graph / DBSCAN entry points (tests/test_dbscan_host.py): tvc_abi.cpp ...
-// tvc_dbscan.cpp with g++ -fsanitize=address,undefined against tests/host_san's HIP stand-in (kernels are no-ops, "device"
+// Host-only sanitizer driver of the radius-graph / DBSCAN entry points (tests/test_dbscan_host.py), built by
+// tests/host_san_build.py under ASan / UBSan against tests/host_san's HIP stand-in (kernels are no-ops, "device"
 // blocks are exactly sized host blocks).  Walks every refusal of tvc_radius_graph (no handle, no bank, R = 0, a bad eps, too
 // many rows, NULL or misaligned buffers) and of tvc_dbscan_sweep / tvc_dbscan_finish (R and min_samples out of range, NULL
 // buffers), checks that a refusal allocates nothing, runs accepted calls of each entry on an fp32 and a bf16 slot and at the
 // sizes around the word and tile boundaries, the profiling bracket, and a leak-free tvc_destroy.
-#include "../../include/tvc.h"
-#include <hip/hip_runtime.h>
+#include "driver_common.hpp"
 #include "host_plan.hpp"
 
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
-
-#define CHECK(cond)                                                                              \
-    do {                                                                                         \
-        if (!(cond)) { fprintf(stderr, "driver.cpp:%d: CHECK failed: %s\n", __LINE__, #cond); return 1; } \
-    } while (0)
-#define OK(call)                                                                                           \
-    do {                                                                                                   \
-        int rc__ = (call);                                                                                 \
-        if (rc__ != TVC_OK) { fprintf(stderr, "driver.cpp:%d: %s -> %d (%s)\n", __LINE__, #call, rc__, tvc_last_error(h)); return 1; } \
-    } while (0)
-// a refusal through fail(): the code and a message that names the entry point
-#define REFUSED(call, code, fn)                                                                  \
-    do {                                                                                         \
-        CHECK((call) == (code));                                                                 \
-        CHECK(strstr(tvc_last_error(h), fn) != nullptr);                                         \
-    } while (0)
-
-static void* dev(size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) abort(); return p; }
 
 int main() {
     // the plan the product and this build share

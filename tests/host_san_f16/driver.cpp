@@ -1,27 +1,11 @@
 // Host-only sanitizer driver of the fp16 tower mode (tests/test_fp16_host.py): the same build as
-// tests/host_san/driver.cpp -- tvc_abi.cpp, tvc_precise.cpp, tvc_split.cpp and tvc_sd.cpp with g++ -fsanitize=address,undefined
+// tests/host_san/driver.cpp -- tests/host_san_build.py's, the product's host sources under ASan / UBSan
 // against tests/host_san's HIP stand-in, whose GEMM launcher checks every operand / output range -- walking
 // TVC_OPT_TOWER_PRECISION = 3: refused before tvc_set_weights_f16, then image / text (dense, packed, grouped, pooled on and
 // off, chunked) and hidden-state encodes on the fp16 weight set, the switch back to bf16, and a leak-free tvc_destroy.
-#include "../../include/tvc.h"
-#include <hip/hip_runtime.h>
+#include "driver_common.hpp"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
-
-#define CHECK(cond)                                                                              \
-    do {                                                                                         \
-        if (!(cond)) { fprintf(stderr, "driver.cpp:%d: CHECK failed: %s\n", __LINE__, #cond); return 1; } \
-    } while (0)
-#define OK(call)                                                                                           \
-    do {                                                                                                   \
-        int rc__ = (call);                                                                                 \
-        if (rc__ != TVC_OK) { fprintf(stderr, "driver.cpp:%d: %s -> %d (%s)\n", __LINE__, #call, rc__, tvc_last_error(h)); return 1; } \
-    } while (0)
-
-static void* dev(size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) abort(); return p; }
 
 int main() {
     tvc_handle* h = nullptr;

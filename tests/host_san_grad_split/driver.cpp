@@ -1,42 +1,16 @@
-// Host-only sanitizer driver of the split-bf16 input gradient (tests/test_grad_split_host.py): tvc_abi.cpp ... tvc_grad_split.cpp
-// with g++ -fsanitize=address,undefined against tests/host_san's HIP stand-in (kernels are no-ops, "device" blocks are exactly
+// Host-only sanitizer driver of the split-bf16 input gradient (tests/test_grad_split_host.py), built by
+// tests/host_san_build.py under ASan / UBSan against tests/host_san's HIP stand-in (kernels are no-ops, "device" blocks are exactly
 // sized host blocks, the GEMM stub checks every operand / output range against its block).  Walks TVC_OPT_GRAD_PRECISION's
 // values, every refusal of the two gradient entry points in mode 2 (no fp32 weights, no split planes, backward before grad, the
 // option changed between grad and backward, B above the chunk limit, an erf-GELU tower), valid forward / backward pairs of both
 // modes at B = 1 and B = 5 (every workspace and plane range of the mode-2 path goes through the stub's checks), the free path
 // of the transposed planes (tvc_set_weights_f32 again, tvc_destroy) and tvc_attention_split_backward's refusals.
-#include "../../include/tvc.h"
-#include <hip/hip_runtime.h>
+#include "driver_common.hpp"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
 
-#define CHECK(cond)                                                                              \
-    do {                                                                                         \
-        if (!(cond)) { fprintf(stderr, "driver.cpp:%d: CHECK failed: %s (%s)\n", __LINE__, #cond, tvc_last_error(h)); return 1; } \
-    } while (0)
-#define OK(call)                                                                                           \
-    do {                                                                                                   \
-        int rc__ = (call);                                                                                 \
-        if (rc__ != TVC_OK) { fprintf(stderr, "driver.cpp:%d: %s -> %d (%s)\n", __LINE__, #call, rc__, tvc_last_error(h)); return 1; } \
-    } while (0)
-// a refusal with code `code` whose message holds `word`
-#define REFUSED(call, code, word)                                                                \
-    do {                                                                                         \
-        CHECK((call) == (code));                                                                 \
-        CHECK(strstr(tvc_last_error(h), word) != nullptr);                                       \
-    } while (0)
-
 static std::vector<void*> g_keep;
-static void* dev(size_t bytes) {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) abort();
-    g_keep.push_back(p);
-    return p;
-}
-template <class T> static T* buf(size_t elems) { return (T*)dev(elems * sizeof(T)); }
+template <class T> static T* buf(size_t elems) { g_keep.push_back(dev(elems * sizeof(T))); return (T*)g_keep.back(); }
 
 template <class L, class W>
 static std::vector<L> layers(const tvc_tower_arch& a) {

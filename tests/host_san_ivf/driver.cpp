@@ -1,27 +1,11 @@
-// Host-only sanitizer driver of the IVF entry points (tests/test_ivf_host.py): the C-ABI translation units plus tvc_ivf.cpp with
-// g++ -fsanitize=address,undefined against tests/host_san's HIP stand-in (kernels are no-ops, "device" blocks are exactly sized
+// Host-only sanitizer driver of the IVF entry points (tests/test_ivf_host.py), built by tests/host_san_build.py
+// under ASan / UBSan against tests/host_san's HIP stand-in (kernels are no-ops, "device" blocks are exactly sized
 // host blocks).  Walks every refusal of tvc_ivf_probe / tvc_ivf_scan and checks that a refusal allocates nothing, valid calls
 // on an fp32 and on a bf16 slot with the optional outputs present and absent, workspace growth, a released slot and a
 // leak-free tvc_destroy.
-#include "../../include/tvc.h"
-#include <hip/hip_runtime.h>
+#include "driver_common.hpp"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
-
-#define CHECK(cond)                                                                              \
-    do {                                                                                         \
-        if (!(cond)) { fprintf(stderr, "driver.cpp:%d: CHECK failed: %s\n", __LINE__, #cond); return 1; } \
-    } while (0)
-#define OK(call)                                                                                           \
-    do {                                                                                                   \
-        int rc__ = (call);                                                                                 \
-        if (rc__ != TVC_OK) { fprintf(stderr, "driver.cpp:%d: %s -> %d (%s)\n", __LINE__, #call, rc__, tvc_last_error(h)); return 1; } \
-    } while (0)
-
-static void* dev(size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) abort(); return p; }
 
 int main() {
     tvc_handle* h = nullptr;

@@ -1,27 +1,10 @@
-// Host-only sanitizer driver of the k-means entry points (tests/test_kmeans_host.py): tvc_abi.cpp, tvc_precise.cpp,
-// tvc_split.cpp, tvc_sd.cpp, tvc_tower_op.cpp and tvc_kmeans.cpp with g++ -fsanitize=address,undefined against
-// tests/host_san's HIP stand-in (kernels are no-ops, "device" blocks are exactly sized host blocks).  Walks every refusal of
+// Host-only sanitizer driver of the k-means entry points (tests/test_kmeans_host.py), built by tests/host_san_build.py
+// under ASan / UBSan against tests/host_san's HIP stand-in (kernels are no-ops, "device" blocks are exactly sized host blocks).  Walks every refusal of
 // tvc_kmeans_assign / tvc_kmeans_update (no bank, R = 0, K out of range, NULL buffers), a valid call on an fp32 and on a
 // bf16 slot, workspace growth from a small to a larger K, and a leak-free tvc_destroy.
-#include "../../include/tvc.h"
-#include <hip/hip_runtime.h>
+#include "driver_common.hpp"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
-
-#define CHECK(cond)                                                                              \
-    do {                                                                                         \
-        if (!(cond)) { fprintf(stderr, "driver.cpp:%d: CHECK failed: %s\n", __LINE__, #cond); return 1; } \
-    } while (0)
-#define OK(call)                                                                                           \
-    do {                                                                                                   \
-        int rc__ = (call);                                                                                 \
-        if (rc__ != TVC_OK) { fprintf(stderr, "driver.cpp:%d: %s -> %d (%s)\n", __LINE__, #call, rc__, tvc_last_error(h)); return 1; } \
-    } while (0)
-
-static void* dev(size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) abort(); return p; }
 
 int main() {
     tvc_handle* h = nullptr;

@@ -1,35 +1,13 @@
-// Host-only sanitizer driver of the closest-pair entry point (tests/test_nearest_host.py): tvc_abi.cpp ... tvc_nearest.cpp with
-// g++ -fsanitize=address,undefined against tests/host_san's HIP stand-in (kernels are no-ops, "device" blocks are exactly sized
+// Host-only sanitizer driver of the closest-pair entry point (tests/test_nearest_host.py), built by tests/host_san_build.py
+// under ASan / UBSan against tests/host_san's HIP stand-in (kernels are no-ops, "device" blocks are exactly sized
 // host blocks).  A stand-alone program: walks every refusal of tvc_closest_pair (no handle, no bank, a bank of no rows, NULL
 // outputs, more rows than the plan takes; D % 64 != 0 cannot get past tvc_bank_set, the entry point's own check stays as a
 // guard), checks that a refusal allocates nothing, runs accepted calls on an fp32 and a bf16 slot, at R = 1 and around the tile
 // boundary, the profiling bracket, and a leak-free tvc_destroy.
-#include "../../include/tvc.h"
-#include <hip/hip_runtime.h>
+#include "driver_common.hpp"
 #include "host_plan.hpp"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
-
-#define CHECK(cond)                                                                              \
-    do {                                                                                         \
-        if (!(cond)) { fprintf(stderr, "driver.cpp:%d: CHECK failed: %s\n", __LINE__, #cond); return 1; } \
-    } while (0)
-#define OK(call)                                                                                           \
-    do {                                                                                                   \
-        int rc__ = (call);                                                                                 \
-        if (rc__ != TVC_OK) { fprintf(stderr, "driver.cpp:%d: %s -> %d (%s)\n", __LINE__, #call, rc__, tvc_last_error(h)); return 1; } \
-    } while (0)
-// a refusal through fail(): the code and a message that names the entry point
-#define REFUSED(call)                                                                            \
-    do {                                                                                         \
-        CHECK((call) == TVC_E_INVALID);                                                          \
-        CHECK(strstr(tvc_last_error(h), "tvc_closest_pair") != nullptr);                         \
-    } while (0)
-
-static void* dev(size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) abort(); return p; }
 
 int main() {
     // the plan the product and this build share
@@ -55,21 +33,21 @@ int main() {
 
     // ---- no handle, no bank, a bank of no rows
     CHECK(tvc_closest_pair(nullptr, partner, sim, pair, pair_sim, nullptr) == TVC_E_INVALID);
-    REFUSED(tvc_closest_pair(h, partner, sim, pair, pair_sim, nullptr));
+    REFUSED(tvc_closest_pair(h, partner, sim, pair, pair_sim, nullptr), TVC_E_INVALID, "tvc_closest_pair");
     OK(tvc_bank_set(h, rows32, 0, D, TVC_DTYPE_F32, nullptr));
-    REFUSED(tvc_closest_pair(h, partner, sim, pair, pair_sim, nullptr));
+    REFUSED(tvc_closest_pair(h, partner, sim, pair, pair_sim, nullptr), TVC_E_INVALID, "tvc_closest_pair");
     OK(tvc_bank_set(h, rows16, 0, D, TVC_DTYPE_BF16, nullptr));
-    REFUSED(tvc_closest_pair(h, partner, sim, pair, pair_sim, nullptr));
+    REFUSED(tvc_closest_pair(h, partner, sim, pair, pair_sim, nullptr), TVC_E_INVALID, "tvc_closest_pair");
     OK(tvc_bank_set(h, nullptr, 0, D, TVC_DTYPE_BF16, nullptr));
-    REFUSED(tvc_closest_pair(h, partner, sim, pair, pair_sim, nullptr));
+    REFUSED(tvc_closest_pair(h, partner, sim, pair, pair_sim, nullptr), TVC_E_INVALID, "tvc_closest_pair");
     const uint64_t ws0 = tvc_workspace_bytes(h);
     for (int dtype = 0; dtype < 2; ++dtype) {
         OK(tvc_bank_select(h, dtype));
         OK(tvc_bank_set(h, dtype == 0 ? (const void*)rows32 : (const void*)rows16, R, D, dtype == 0 ? TVC_DTYPE_F32 : TVC_DTYPE_BF16, nullptr));
-        REFUSED(tvc_closest_pair(h, nullptr, sim, pair, pair_sim, nullptr));
-        REFUSED(tvc_closest_pair(h, partner, nullptr, pair, pair_sim, nullptr));
-        REFUSED(tvc_closest_pair(h, partner, sim, nullptr, pair_sim, nullptr));
-        REFUSED(tvc_closest_pair(h, partner, sim, pair, nullptr, nullptr));
+        REFUSED(tvc_closest_pair(h, nullptr, sim, pair, pair_sim, nullptr), TVC_E_INVALID, "tvc_closest_pair");
+        REFUSED(tvc_closest_pair(h, partner, nullptr, pair, pair_sim, nullptr), TVC_E_INVALID, "tvc_closest_pair");
+        REFUSED(tvc_closest_pair(h, partner, sim, nullptr, pair_sim, nullptr), TVC_E_INVALID, "tvc_closest_pair");
+        REFUSED(tvc_closest_pair(h, partner, sim, pair, nullptr, nullptr), TVC_E_INVALID, "tvc_closest_pair");
         if (dtype == 0) CHECK(tvc_workspace_bytes(h) == ws0);                                 // a refusal allocates nothing
         OK(tvc_closest_pair(h, partner, sim, pair, pair_sim, nullptr));
         if (dtype == 0) CHECK(tvc_workspace_bytes(h) >= ws0 + (uint64_t)nearest_plan(R).rpad * 4);
@@ -84,9 +62,9 @@ int main() {
     }
     // more rows than the plan takes (a bf16 slot is used in place: only its first rows exist here, nothing reads them)
     OK(tvc_bank_set(h, rows16, NEAREST_MAX_ROWS + 1, 64, TVC_DTYPE_BF16, nullptr));
-    REFUSED(tvc_closest_pair(h, partner, sim, pair, pair_sim, nullptr));
+    REFUSED(tvc_closest_pair(h, partner, sim, pair, pair_sim, nullptr), TVC_E_INVALID, "tvc_closest_pair");
     OK(tvc_bank_set(h, nullptr, 0, 64, TVC_DTYPE_BF16, nullptr));
-    REFUSED(tvc_closest_pair(h, partner, sim, pair, pair_sim, nullptr));       // a released slot refuses again
+    REFUSED(tvc_closest_pair(h, partner, sim, pair, pair_sim, nullptr), TVC_E_INVALID, "tvc_closest_pair");       // a released slot refuses again
 
     // the profiling bracket counts the pass as bank work
     OK(tvc_bank_select(h, 0));

@@ -1,39 +1,18 @@
-// Host-only sanitizer driver of the pair-list / pair-cosine entry points (tests/test_validator_host.py): tvc_abi.cpp ...
-// tvc_pairs.cpp with g++ -fsanitize=address,undefined against tests/host_san's HIP stand-in (kernels are no-ops that write
+// Host-only sanitizer driver of the pair-list / pair-cosine entry points (tests/test_validator_host.py), built by
+// tests/host_san_build.py under ASan / UBSan against tests/host_san's HIP stand-in (kernels are no-ops that write
 // their name to the stand-in's trace, "device" blocks are exactly sized host blocks).  Walks the launch plan of host_plan.hpp,
 // every refusal of tvc_graph_pair_count / tvc_graph_pair_fill (no handle, R out of range, P < 0, NULL buffers) and of
 // tvc_pair_cosine (no handle, an empty slot, P < 0, NULL buffers), checks through the trace that a refusal and P == 0 launch
 // nothing and that an accepted call launches exactly its own kernel, that no call owns a workspace, the profiling bracket,
 // and a leak-free tvc_destroy.
-#include "../../include/tvc.h"
-#include <hip/hip_runtime.h>
+#include "driver_common.hpp"
 #include "host_plan.hpp"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <string>
 #include <vector>
 
-#define CHECK(cond)                                                                              \
-    do {                                                                                         \
-        if (!(cond)) { fprintf(stderr, "driver.cpp:%d: CHECK failed: %s\n", __LINE__, #cond); return 1; } \
-    } while (0)
-#define OK(call)                                                                                           \
-    do {                                                                                                   \
-        int rc__ = (call);                                                                                 \
-        if (rc__ != TVC_OK) { fprintf(stderr, "driver.cpp:%d: %s -> %d (%s)\n", __LINE__, #call, rc__, tvc_last_error(h)); return 1; } \
-    } while (0)
-// a refusal through fail(): the code, a message that names the entry point, and no launch
-#define REFUSED(call, code, fn)                                                                  \
-    do {                                                                                         \
-        const long before__ = launches("launch_");                                               \
-        CHECK((call) == (code));                                                                 \
-        CHECK(strstr(tvc_last_error(h), fn) != nullptr);                                         \
-        CHECK(launches("launch_") == before__);                                                  \
-    } while (0)
-
-static void* dev(size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) abort(); return p; }
+// a refusal through fail() that launches nothing: the shared REFUSED between two counts of the trace's launch lines
+#define QUIET_REFUSED(call, code, fn) do { const long before__ = launches("launch_"); REFUSED(call, code, fn); CHECK(launches("launch_") == before__); } while (0)
 
 // lines of the stand-in's trace that start with `prefix`
 static long launches(const char* prefix) {
@@ -87,17 +66,17 @@ int main() {
     // ---- tvc_graph_pair_count / tvc_graph_pair_fill: they read no bank slot
     CHECK(tvc_graph_pair_count(nullptr, adj, R, group, offsets, nullptr) == TVC_E_INVALID);
     CHECK(tvc_graph_pair_fill(nullptr, adj, R, group, offsets, pairs, P, nullptr) == TVC_E_INVALID);
-    REFUSED(tvc_graph_pair_count(h, adj, 0, group, offsets, nullptr), TVC_E_INVALID, PC);
-    REFUSED(tvc_graph_pair_count(h, adj, -1, group, offsets, nullptr), TVC_E_INVALID, PC);
-    REFUSED(tvc_graph_pair_count(h, adj, TVC_RADIUS_MAX_ROWS + 1, group, offsets, nullptr), TVC_E_INVALID, PC);
-    REFUSED(tvc_graph_pair_count(h, nullptr, R, group, offsets, nullptr), TVC_E_INVALID, PC);
-    REFUSED(tvc_graph_pair_count(h, adj, R, group, nullptr, nullptr), TVC_E_INVALID, PC);
-    REFUSED(tvc_graph_pair_fill(h, adj, 0, group, offsets, pairs, P, nullptr), TVC_E_INVALID, PF);
-    REFUSED(tvc_graph_pair_fill(h, adj, TVC_RADIUS_MAX_ROWS + 1, group, offsets, pairs, P, nullptr), TVC_E_INVALID, PF);
-    REFUSED(tvc_graph_pair_fill(h, adj, R, group, offsets, pairs, -1, nullptr), TVC_E_INVALID, PF);
-    REFUSED(tvc_graph_pair_fill(h, nullptr, R, group, offsets, pairs, P, nullptr), TVC_E_INVALID, PF);
-    REFUSED(tvc_graph_pair_fill(h, adj, R, group, nullptr, pairs, P, nullptr), TVC_E_INVALID, PF);
-    REFUSED(tvc_graph_pair_fill(h, adj, R, group, offsets, nullptr, P, nullptr), TVC_E_INVALID, PF);
+    QUIET_REFUSED(tvc_graph_pair_count(h, adj, 0, group, offsets, nullptr), TVC_E_INVALID, PC);
+    QUIET_REFUSED(tvc_graph_pair_count(h, adj, -1, group, offsets, nullptr), TVC_E_INVALID, PC);
+    QUIET_REFUSED(tvc_graph_pair_count(h, adj, TVC_RADIUS_MAX_ROWS + 1, group, offsets, nullptr), TVC_E_INVALID, PC);
+    QUIET_REFUSED(tvc_graph_pair_count(h, nullptr, R, group, offsets, nullptr), TVC_E_INVALID, PC);
+    QUIET_REFUSED(tvc_graph_pair_count(h, adj, R, group, nullptr, nullptr), TVC_E_INVALID, PC);
+    QUIET_REFUSED(tvc_graph_pair_fill(h, adj, 0, group, offsets, pairs, P, nullptr), TVC_E_INVALID, PF);
+    QUIET_REFUSED(tvc_graph_pair_fill(h, adj, TVC_RADIUS_MAX_ROWS + 1, group, offsets, pairs, P, nullptr), TVC_E_INVALID, PF);
+    QUIET_REFUSED(tvc_graph_pair_fill(h, adj, R, group, offsets, pairs, -1, nullptr), TVC_E_INVALID, PF);
+    QUIET_REFUSED(tvc_graph_pair_fill(h, nullptr, R, group, offsets, pairs, P, nullptr), TVC_E_INVALID, PF);
+    QUIET_REFUSED(tvc_graph_pair_fill(h, adj, R, group, nullptr, pairs, P, nullptr), TVC_E_INVALID, PF);
+    QUIET_REFUSED(tvc_graph_pair_fill(h, adj, R, group, offsets, nullptr, P, nullptr), TVC_E_INVALID, PF);
     long n0 = launches("launch_");
     OK(tvc_graph_pair_fill(h, adj, R, group, offsets, pairs, 0, nullptr));            // P == 0 is legal and launches nothing
     OK(tvc_graph_pair_fill(h, adj, R, nullptr, offsets, nullptr, 0, nullptr));
@@ -114,17 +93,17 @@ int main() {
 
     // ---- tvc_pair_cosine: no handle, no bank, a bank of no rows
     CHECK(tvc_pair_cosine(nullptr, pairs, P, sim, nullptr) == TVC_E_INVALID);
-    REFUSED(tvc_pair_cosine(h, pairs, P, sim, nullptr), TVC_E_STATE, CO);
-    REFUSED(tvc_pair_cosine(h, pairs, 0, sim, nullptr), TVC_E_STATE, CO);             // an empty slot refuses before P is looked at
+    QUIET_REFUSED(tvc_pair_cosine(h, pairs, P, sim, nullptr), TVC_E_STATE, CO);
+    QUIET_REFUSED(tvc_pair_cosine(h, pairs, 0, sim, nullptr), TVC_E_STATE, CO);             // an empty slot refuses before P is looked at
     OK(tvc_bank_set(h, rows32, 0, D, TVC_DTYPE_F32, nullptr));
-    REFUSED(tvc_pair_cosine(h, pairs, P, sim, nullptr), TVC_E_STATE, CO);
+    QUIET_REFUSED(tvc_pair_cosine(h, pairs, P, sim, nullptr), TVC_E_STATE, CO);
     for (int dtype = 0; dtype < 2; ++dtype) {
         OK(tvc_bank_select(h, dtype));
         OK(tvc_bank_set(h, dtype == 0 ? (const void*)rows32 : (const void*)rows16, R, D, dtype == 0 ? TVC_DTYPE_F32 : TVC_DTYPE_BF16, nullptr));
         const uint64_t ws1 = tvc_workspace_bytes(h);
-        REFUSED(tvc_pair_cosine(h, pairs, -1, sim, nullptr), TVC_E_INVALID, CO);
-        REFUSED(tvc_pair_cosine(h, nullptr, P, sim, nullptr), TVC_E_INVALID, CO);
-        REFUSED(tvc_pair_cosine(h, pairs, P, nullptr, nullptr), TVC_E_INVALID, CO);
+        QUIET_REFUSED(tvc_pair_cosine(h, pairs, -1, sim, nullptr), TVC_E_INVALID, CO);
+        QUIET_REFUSED(tvc_pair_cosine(h, nullptr, P, sim, nullptr), TVC_E_INVALID, CO);
+        QUIET_REFUSED(tvc_pair_cosine(h, pairs, P, nullptr, nullptr), TVC_E_INVALID, CO);
         n0 = launches("launch_pair_cosine");
         OK(tvc_pair_cosine(h, pairs, 0, sim, nullptr));
         OK(tvc_pair_cosine(h, nullptr, 0, nullptr, nullptr));
@@ -136,7 +115,7 @@ int main() {
     }
     // a released slot refuses again
     OK(tvc_bank_set(h, nullptr, 0, 64, TVC_DTYPE_BF16, nullptr));
-    REFUSED(tvc_pair_cosine(h, pairs, P, sim, nullptr), TVC_E_STATE, CO);
+    QUIET_REFUSED(tvc_pair_cosine(h, pairs, P, sim, nullptr), TVC_E_STATE, CO);
 
     // the profiling bracket counts the cosine as bank work: three FMAs per element of a pair
     OK(tvc_bank_select(h, 0));

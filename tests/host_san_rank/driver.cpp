@@ -1,29 +1,12 @@
-// Host-only sanitizer driver of the retrieval-evaluation entry points (tests/test_retrieval_host_san.py): tvc_abi.cpp,
-// tvc_precise.cpp, tvc_split.cpp, tvc_sd.cpp, tvc_sd_op.cpp, tvc_tower_op.cpp and tvc_rank.cpp with g++
-// -fsanitize=address,undefined against tests/host_san's HIP stand-in (kernels are no-ops, "device" blocks are exactly sized
+// Host-only sanitizer driver of the retrieval-evaluation entry points (tests/test_retrieval_host_san.py), built by
+// tests/host_san_build.py under ASan / UBSan against tests/host_san's HIP stand-in (kernels are no-ops, "device" blocks are exactly sized
 // host blocks).  Walks every refusal of tvc_rank_targets / tvc_rank_count / tvc_rank_metrics (no bank, R = 0, M < 1, T < 0, NULL
 // buffers, too many or non-positive k values) and checks that none allocates, then valid calls on an fp32 and on a bf16 slot,
 // T = 0, workspace growth from a small to a larger M, the plan of host_plan.hpp, and a leak-free tvc_destroy.
-#include "../../include/tvc.h"
+#include "driver_common.hpp"
 #include "host_plan.hpp"
-#include <hip/hip_runtime.h>
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
-
-#define CHECK(cond)                                                                              \
-    do {                                                                                         \
-        if (!(cond)) { fprintf(stderr, "driver.cpp:%d: CHECK failed: %s\n", __LINE__, #cond); return 1; } \
-    } while (0)
-#define OK(call)                                                                                           \
-    do {                                                                                                   \
-        int rc__ = (call);                                                                                 \
-        if (rc__ != TVC_OK) { fprintf(stderr, "driver.cpp:%d: %s -> %d (%s)\n", __LINE__, #call, rc__, tvc_last_error(h)); return 1; } \
-    } while (0)
-
-static void* dev(size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) abort(); return p; }
 
 int main() {
     // ---- the plan: whole query tiles, refusals

@@ -1,30 +1,13 @@
-// Host-only sanitizer driver of the detection-evaluation entry points (tests/test_detection_host.py): tvc_abi.cpp,
-// tvc_precise.cpp, tvc_split.cpp, tvc_sd.cpp, tvc_sd_op.cpp, tvc_tower_op.cpp and tvc_roc.cpp with g++
-// -fsanitize=address,undefined against tests/host_san's HIP stand-in (kernels are no-ops, "device" blocks are exactly sized
+// Host-only sanitizer driver of the detection-evaluation entry points (tests/test_detection_host.py), built by
+// tests/host_san_build.py under ASan / UBSan against tests/host_san's HIP stand-in (kernels are no-ops, "device" blocks are exactly sized
 // host blocks).  Checks the plan of host_plan.hpp (storage form, chunking, refusals), walks every refusal of tvc_roc_weights /
 // tvc_roc_sweep / tvc_roc_curve and checks that none allocates, then valid calls in the LDS form (no workspace) and in the global
 // form (a workspace that grows with N and never passes the budget), and a leak-free tvc_destroy.
-#include "../../include/tvc.h"
+#include "driver_common.hpp"
 #include "host_plan.hpp"
-#include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
-
-#define CHECK(cond)                                                                              \
-    do {                                                                                         \
-        if (!(cond)) { fprintf(stderr, "driver.cpp:%d: CHECK failed: %s\n", __LINE__, #cond); return 1; } \
-    } while (0)
-#define OK(call)                                                                                           \
-    do {                                                                                                   \
-        int rc__ = (call);                                                                                 \
-        if (rc__ != TVC_OK) { fprintf(stderr, "driver.cpp:%d: %s -> %d (%s)\n", __LINE__, #call, rc__, tvc_last_error(h)); return 1; } \
-    } while (0)
-
-static void* dev(size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) abort(); return p; }
 
 int main() {
     // ---- the plan: refusals

@@ -1,31 +1,15 @@
 // Host-only sanitizer driver of the latent-diffusion model's fp16 mode (tests/test_sd_fp16_host.py): the same build as
-// tests/host_san/driver.cpp -- tvc_abi.cpp, tvc_precise.cpp, tvc_split.cpp and tvc_sd.cpp with g++ -fsanitize=address,undefined
+// tests/host_san/driver.cpp -- tests/host_san_build.py's, the product's host sources under ASan / UBSan
 // against tests/host_san's HIP stand-in, whose GEMM launcher checks every operand / output range -- walking
 // TVC_OPT_SD_PRECISION: its values and refused transitions, then a toy model loaded in mode 1 through tvc_sd_unet,
 // tvc_sd_vae_decode, a 2-step tvc_sd_generate with both stream settings, the block and attention entry points, and a
 // leak-free tvc_destroy.  argv[1]: file of SD tensor names (one "name rows cols element_size" per line).
-#include "../../include/tvc.h"
-#include <hip/hip_runtime.h>
+#include "driver_common.hpp"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <fstream>
 #include <sstream>
 #include <string>
 #include <vector>
-
-#define CHECK(cond)                                                                              \
-    do {                                                                                         \
-        if (!(cond)) { fprintf(stderr, "driver.cpp:%d: CHECK failed: %s\n", __LINE__, #cond); return 1; } \
-    } while (0)
-#define OK(call)                                                                                           \
-    do {                                                                                                   \
-        int rc__ = (call);                                                                                 \
-        if (rc__ != TVC_OK) { fprintf(stderr, "driver.cpp:%d: %s -> %d (%s)\n", __LINE__, #call, rc__, tvc_last_error(h)); return 1; } \
-    } while (0)
-
-static void* dev(size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) abort(); return p; }
 
 int main(int argc, char** argv) {
     CHECK(argc >= 2);

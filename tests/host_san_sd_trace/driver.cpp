@@ -1,31 +1,16 @@
 // Host-only trace driver of the latent-diffusion host code (tests/test_sd_trace_host.py): the same build as
-// tests/host_san_sd_f16/driver.cpp -- g++ -fsanitize=address,undefined against tests/host_san's HIP stand-in -- with the
+// tests/host_san_sd_f16/driver.cpp -- tests/host_san_build.py's, against tests/host_san's HIP stand-in -- with the
 // stubs of gen_stubs.py --trace, so that every launch, its arguments, its stream and its arena offsets, every allocation and
 // every copy of each SD entry point land in the file HIP_STUB_TRACE names, one "# ..." marker line before each call.  The
 // test compares that file with the one recorded before tvc_sd.cpp was refactored.  Both 16-bit formats, the toy geometry of
 // the other host drivers.  argv[1]: file of SD tensor names (one "name rows cols element_size" per line).
-#include "../../include/tvc.h"
-#include <hip/hip_runtime.h>
+#define DRIVER_BEFORE_OK(text) hip_trace_line("# " text)        // one marker line in the trace before each call
+#include "driver_common.hpp"
 
-#include <cstdio>
-#include <cstdlib>
 #include <fstream>
 #include <sstream>
 #include <string>
 #include <vector>
-
-#define CHECK(cond)                                                                              \
-    do {                                                                                         \
-        if (!(cond)) { fprintf(stderr, "driver.cpp:%d: CHECK failed: %s\n", __LINE__, #cond); return 1; } \
-    } while (0)
-#define OK(call)                                                                                           \
-    do {                                                                                                   \
-        hip_trace_line("# " #call);                                                                        \
-        int rc__ = (call);                                                                                 \
-        if (rc__ != TVC_OK) { fprintf(stderr, "driver.cpp:%d: %s -> %d (%s)\n", __LINE__, #call, rc__, tvc_last_error(h)); return 1; } \
-    } while (0)
-
-static void* dev(size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) abort(); return p; }
 
 static int run(const char* names_file, int precision) {
     tvc_handle* h = nullptr;

@@ -1,35 +1,13 @@
-// Host-only sanitizer driver of the similarity-metric entry points (tests/test_similarity_host.py): tvc_abi.cpp ... tvc_sim.cpp
-// with g++ -fsanitize=address,undefined against tests/host_san's HIP stand-in (kernels are no-ops, "device" blocks are exactly
+// Host-only sanitizer driver of the similarity-metric entry points (tests/test_similarity_host.py), built by
+// tests/host_san_build.py under ASan / UBSan against tests/host_san's HIP stand-in (kernels are no-ops, "device" blocks are exactly
 // sized host blocks).  A stand-alone program: walks every refusal of tvc_sim_rows, tvc_sim_flat_rank, tvc_sim_flat and
 // tvc_topk_overlap, the legal empty calls (B == 0, M == 0), the workspace sizing at n = 1, 4096, 4097 and 2^20 with a workspace
 // one byte short and a misaligned one, accepted calls with exactly sized buffers, and a leak-free tvc_destroy (the calls keep
 // nothing in the handle).
-#include "../../include/tvc.h"
-#include <hip/hip_runtime.h>
+#include "driver_common.hpp"
 #include "host_plan.hpp"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
-
-#define CHECK(cond)                                                                              \
-    do {                                                                                         \
-        if (!(cond)) { fprintf(stderr, "driver.cpp:%d: CHECK failed: %s\n", __LINE__, #cond); return 1; } \
-    } while (0)
-#define OK(call)                                                                                           \
-    do {                                                                                                   \
-        int rc__ = (call);                                                                                 \
-        if (rc__ != TVC_OK) { fprintf(stderr, "driver.cpp:%d: %s -> %d (%s)\n", __LINE__, #call, rc__, tvc_last_error(h)); return 1; } \
-    } while (0)
-// a refusal through fail(): the code and a message that names the entry point
-#define REFUSED(fn, call)                                                                        \
-    do {                                                                                         \
-        CHECK((call) == TVC_E_INVALID);                                                          \
-        CHECK(strstr(tvc_last_error(h), fn) != nullptr);                                         \
-    } while (0)
-
-static void* dev(size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) abort(); return p; }
 
 int main() {
     // the plan the product and this build share
@@ -60,22 +38,22 @@ int main() {
     double* out = (double*)buf((size_t)B * TVC_SIM_COLS, 8);
     int64_t* ints = (int64_t*)buf((size_t)B * TVC_SIM_INTS, 8);
     CHECK(tvc_sim_rows(nullptr, x, y, B, D, ld, D, TVC_SIM_KEY_F32, out, ints, nullptr) == TVC_E_INVALID);
-    REFUSED("tvc_sim_rows", tvc_sim_rows(h, x, y, -1, D, ld, D, TVC_SIM_KEY_F32, out, ints, nullptr));
-    REFUSED("tvc_sim_rows", tvc_sim_rows(h, x, y, B, 0, ld, D, TVC_SIM_KEY_F32, out, ints, nullptr));
-    REFUSED("tvc_sim_rows", tvc_sim_rows(h, x, y, B, TVC_SIM_MAX_D + 1, TVC_SIM_MAX_D + 1, TVC_SIM_MAX_D + 1, TVC_SIM_KEY_F32, out, ints, nullptr));
-    REFUSED("tvc_sim_rows", tvc_sim_rows(h, x, y, B, D, D - 1, D, TVC_SIM_KEY_F32, out, ints, nullptr));
-    REFUSED("tvc_sim_rows", tvc_sim_rows(h, x, y, B, D, ld, D - 1, TVC_SIM_KEY_F32, out, ints, nullptr));
-    REFUSED("tvc_sim_rows", tvc_sim_rows(h, x, y, B, D, ld, D, 2, out, ints, nullptr));
-    REFUSED("tvc_sim_rows", tvc_sim_rows(h, x, y, B, D, ld, D, -1, out, ints, nullptr));
-    REFUSED("tvc_sim_rows", tvc_sim_rows(h, nullptr, y, B, D, ld, D, TVC_SIM_KEY_F32, out, ints, nullptr));
-    REFUSED("tvc_sim_rows", tvc_sim_rows(h, x, nullptr, B, D, ld, D, TVC_SIM_KEY_F32, out, ints, nullptr));
-    REFUSED("tvc_sim_rows", tvc_sim_rows(h, x, y, B, D, ld, D, TVC_SIM_KEY_F32, nullptr, ints, nullptr));
-    REFUSED("tvc_sim_rows", tvc_sim_rows(h, x, y, B, D, ld, D, TVC_SIM_KEY_F32, out, nullptr, nullptr));
+    REFUSED(tvc_sim_rows(h, x, y, -1, D, ld, D, TVC_SIM_KEY_F32, out, ints, nullptr), TVC_E_INVALID, "tvc_sim_rows");
+    REFUSED(tvc_sim_rows(h, x, y, B, 0, ld, D, TVC_SIM_KEY_F32, out, ints, nullptr), TVC_E_INVALID, "tvc_sim_rows");
+    REFUSED(tvc_sim_rows(h, x, y, B, TVC_SIM_MAX_D + 1, TVC_SIM_MAX_D + 1, TVC_SIM_MAX_D + 1, TVC_SIM_KEY_F32, out, ints, nullptr), TVC_E_INVALID, "tvc_sim_rows");
+    REFUSED(tvc_sim_rows(h, x, y, B, D, D - 1, D, TVC_SIM_KEY_F32, out, ints, nullptr), TVC_E_INVALID, "tvc_sim_rows");
+    REFUSED(tvc_sim_rows(h, x, y, B, D, ld, D - 1, TVC_SIM_KEY_F32, out, ints, nullptr), TVC_E_INVALID, "tvc_sim_rows");
+    REFUSED(tvc_sim_rows(h, x, y, B, D, ld, D, 2, out, ints, nullptr), TVC_E_INVALID, "tvc_sim_rows");
+    REFUSED(tvc_sim_rows(h, x, y, B, D, ld, D, -1, out, ints, nullptr), TVC_E_INVALID, "tvc_sim_rows");
+    REFUSED(tvc_sim_rows(h, nullptr, y, B, D, ld, D, TVC_SIM_KEY_F32, out, ints, nullptr), TVC_E_INVALID, "tvc_sim_rows");
+    REFUSED(tvc_sim_rows(h, x, nullptr, B, D, ld, D, TVC_SIM_KEY_F32, out, ints, nullptr), TVC_E_INVALID, "tvc_sim_rows");
+    REFUSED(tvc_sim_rows(h, x, y, B, D, ld, D, TVC_SIM_KEY_F32, nullptr, ints, nullptr), TVC_E_INVALID, "tvc_sim_rows");
+    REFUSED(tvc_sim_rows(h, x, y, B, D, ld, D, TVC_SIM_KEY_F32, out, nullptr, nullptr), TVC_E_INVALID, "tvc_sim_rows");
     OK(tvc_sim_rows(h, x, y, B, D, ld, D, TVC_SIM_KEY_F32, out, ints, nullptr));
     OK(tvc_sim_rows(h, x, y, B, D, ld, D, TVC_SIM_KEY_I32, out, ints, nullptr));
     OK(tvc_sim_rows(h, x, y, 1, 1, 1, 1, TVC_SIM_KEY_F32, out, ints, nullptr));
     OK(tvc_sim_rows(h, nullptr, nullptr, 0, D, D, D, TVC_SIM_KEY_F32, nullptr, nullptr, nullptr));      // B == 0: legal, no buffers
-    REFUSED("tvc_sim_rows", tvc_sim_rows(h, nullptr, nullptr, 0, 0, D, D, TVC_SIM_KEY_F32, nullptr, nullptr, nullptr));   // but not a bad D
+    REFUSED(tvc_sim_rows(h, nullptr, nullptr, 0, 0, D, D, TVC_SIM_KEY_F32, nullptr, nullptr, nullptr), TVC_E_INVALID, "tvc_sim_rows");   // but not a bad D
 
     // ---- the long form
     for (int i = 0; i < 4; ++i) {
@@ -90,10 +68,10 @@ int main() {
         OK(tvc_sim_flat_rank(h, v, s, n, cx, nan, nullptr));
         OK(tvc_sim_flat_rank(h, s, v, n, cy, nullptr, nullptr));                                  // the NaN count is optional
         OK(tvc_sim_flat(h, v, s, cx, cy, n, out, ints, ws, need, nullptr));
-        REFUSED("tvc_sim_flat", tvc_sim_flat(h, v, s, cx, cy, n, out, ints, ws, need - 1, nullptr));      // too small a workspace
-        REFUSED("tvc_sim_flat", tvc_sim_flat(h, v, s, cx, cy, n, out, ints, ws + 4, need, nullptr));      // misaligned
-        REFUSED("tvc_sim_flat", tvc_sim_flat(h, v, s, cx, cy, n, out, ints, nullptr, need, nullptr));
-        REFUSED("tvc_sim_flat", tvc_sim_flat(h, v, s, cx, cy, n, out, ints, ws, 0, nullptr));
+        REFUSED(tvc_sim_flat(h, v, s, cx, cy, n, out, ints, ws, need - 1, nullptr), TVC_E_INVALID, "tvc_sim_flat");      // too small a workspace
+        REFUSED(tvc_sim_flat(h, v, s, cx, cy, n, out, ints, ws + 4, need, nullptr), TVC_E_INVALID, "tvc_sim_flat");      // misaligned
+        REFUSED(tvc_sim_flat(h, v, s, cx, cy, n, out, ints, nullptr, need, nullptr), TVC_E_INVALID, "tvc_sim_flat");
+        REFUSED(tvc_sim_flat(h, v, s, cx, cy, n, out, ints, ws, 0, nullptr), TVC_E_INVALID, "tvc_sim_flat");
         (void)hipFree(v); (void)hipFree(s); (void)hipFree(cx); (void)hipFree(cy); (void)hipFree(nan); (void)hipFree(ws);
     }
     {
@@ -103,20 +81,20 @@ int main() {
         const uint64_t need = tvc_sim_flat_workspace(8);
         CHECK(tvc_sim_flat_rank(nullptr, v, v, 8, c, nullptr, nullptr) == TVC_E_INVALID);
         CHECK(tvc_sim_flat(nullptr, v, v, c, c, 8, out, ints, ws, need, nullptr) == TVC_E_INVALID);
-        REFUSED("tvc_sim_flat_rank", tvc_sim_flat_rank(h, v, v, 0, c, nullptr, nullptr));
-        REFUSED("tvc_sim_flat_rank", tvc_sim_flat_rank(h, v, v, -8, c, nullptr, nullptr));
-        REFUSED("tvc_sim_flat_rank", tvc_sim_flat_rank(h, v, v, (int64_t)TVC_SIM_MAX_N + 1, c, nullptr, nullptr));
-        REFUSED("tvc_sim_flat_rank", tvc_sim_flat_rank(h, nullptr, v, 8, c, nullptr, nullptr));
-        REFUSED("tvc_sim_flat_rank", tvc_sim_flat_rank(h, v, nullptr, 8, c, nullptr, nullptr));
-        REFUSED("tvc_sim_flat_rank", tvc_sim_flat_rank(h, v, v, 8, nullptr, nullptr, nullptr));
-        REFUSED("tvc_sim_flat", tvc_sim_flat(h, v, v, c, c, 0, out, ints, ws, need, nullptr));
-        REFUSED("tvc_sim_flat", tvc_sim_flat(h, v, v, c, c, (int64_t)TVC_SIM_MAX_N + 1, out, ints, ws, need, nullptr));
-        REFUSED("tvc_sim_flat", tvc_sim_flat(h, nullptr, v, c, c, 8, out, ints, ws, need, nullptr));
-        REFUSED("tvc_sim_flat", tvc_sim_flat(h, v, nullptr, c, c, 8, out, ints, ws, need, nullptr));
-        REFUSED("tvc_sim_flat", tvc_sim_flat(h, v, v, nullptr, c, 8, out, ints, ws, need, nullptr));
-        REFUSED("tvc_sim_flat", tvc_sim_flat(h, v, v, c, nullptr, 8, out, ints, ws, need, nullptr));
-        REFUSED("tvc_sim_flat", tvc_sim_flat(h, v, v, c, c, 8, nullptr, ints, ws, need, nullptr));
-        REFUSED("tvc_sim_flat", tvc_sim_flat(h, v, v, c, c, 8, out, nullptr, ws, need, nullptr));
+        REFUSED(tvc_sim_flat_rank(h, v, v, 0, c, nullptr, nullptr), TVC_E_INVALID, "tvc_sim_flat_rank");
+        REFUSED(tvc_sim_flat_rank(h, v, v, -8, c, nullptr, nullptr), TVC_E_INVALID, "tvc_sim_flat_rank");
+        REFUSED(tvc_sim_flat_rank(h, v, v, (int64_t)TVC_SIM_MAX_N + 1, c, nullptr, nullptr), TVC_E_INVALID, "tvc_sim_flat_rank");
+        REFUSED(tvc_sim_flat_rank(h, nullptr, v, 8, c, nullptr, nullptr), TVC_E_INVALID, "tvc_sim_flat_rank");
+        REFUSED(tvc_sim_flat_rank(h, v, nullptr, 8, c, nullptr, nullptr), TVC_E_INVALID, "tvc_sim_flat_rank");
+        REFUSED(tvc_sim_flat_rank(h, v, v, 8, nullptr, nullptr, nullptr), TVC_E_INVALID, "tvc_sim_flat_rank");
+        REFUSED(tvc_sim_flat(h, v, v, c, c, 0, out, ints, ws, need, nullptr), TVC_E_INVALID, "tvc_sim_flat");
+        REFUSED(tvc_sim_flat(h, v, v, c, c, (int64_t)TVC_SIM_MAX_N + 1, out, ints, ws, need, nullptr), TVC_E_INVALID, "tvc_sim_flat");
+        REFUSED(tvc_sim_flat(h, nullptr, v, c, c, 8, out, ints, ws, need, nullptr), TVC_E_INVALID, "tvc_sim_flat");
+        REFUSED(tvc_sim_flat(h, v, nullptr, c, c, 8, out, ints, ws, need, nullptr), TVC_E_INVALID, "tvc_sim_flat");
+        REFUSED(tvc_sim_flat(h, v, v, nullptr, c, 8, out, ints, ws, need, nullptr), TVC_E_INVALID, "tvc_sim_flat");
+        REFUSED(tvc_sim_flat(h, v, v, c, nullptr, 8, out, ints, ws, need, nullptr), TVC_E_INVALID, "tvc_sim_flat");
+        REFUSED(tvc_sim_flat(h, v, v, c, c, 8, nullptr, ints, ws, need, nullptr), TVC_E_INVALID, "tvc_sim_flat");
+        REFUSED(tvc_sim_flat(h, v, v, c, c, 8, out, nullptr, ws, need, nullptr), TVC_E_INVALID, "tvc_sim_flat");
     }
 
     // ---- tvc_topk_overlap
@@ -125,14 +103,14 @@ int main() {
     int32_t* b = (int32_t*)buf((size_t)M * Lb, 4);
     int32_t* count = (int32_t*)buf(M, 4);
     CHECK(tvc_topk_overlap(nullptr, a, b, M, La, Lb, 4, count, nullptr) == TVC_E_INVALID);
-    REFUSED("tvc_topk_overlap", tvc_topk_overlap(h, a, b, -1, La, Lb, 4, count, nullptr));
-    REFUSED("tvc_topk_overlap", tvc_topk_overlap(h, a, b, M, -1, Lb, 4, count, nullptr));
-    REFUSED("tvc_topk_overlap", tvc_topk_overlap(h, a, b, M, La, -1, 4, count, nullptr));
-    REFUSED("tvc_topk_overlap", tvc_topk_overlap(h, a, b, M, La, Lb, 0, count, nullptr));
-    REFUSED("tvc_topk_overlap", tvc_topk_overlap(h, a, b, M, La, Lb, TVC_TOPK_OVERLAP_MAX_K + 1, count, nullptr));
-    REFUSED("tvc_topk_overlap", tvc_topk_overlap(h, nullptr, b, M, La, Lb, 4, count, nullptr));
-    REFUSED("tvc_topk_overlap", tvc_topk_overlap(h, a, nullptr, M, La, Lb, 4, count, nullptr));
-    REFUSED("tvc_topk_overlap", tvc_topk_overlap(h, a, b, M, La, Lb, 4, nullptr, nullptr));
+    REFUSED(tvc_topk_overlap(h, a, b, -1, La, Lb, 4, count, nullptr), TVC_E_INVALID, "tvc_topk_overlap");
+    REFUSED(tvc_topk_overlap(h, a, b, M, -1, Lb, 4, count, nullptr), TVC_E_INVALID, "tvc_topk_overlap");
+    REFUSED(tvc_topk_overlap(h, a, b, M, La, -1, 4, count, nullptr), TVC_E_INVALID, "tvc_topk_overlap");
+    REFUSED(tvc_topk_overlap(h, a, b, M, La, Lb, 0, count, nullptr), TVC_E_INVALID, "tvc_topk_overlap");
+    REFUSED(tvc_topk_overlap(h, a, b, M, La, Lb, TVC_TOPK_OVERLAP_MAX_K + 1, count, nullptr), TVC_E_INVALID, "tvc_topk_overlap");
+    REFUSED(tvc_topk_overlap(h, nullptr, b, M, La, Lb, 4, count, nullptr), TVC_E_INVALID, "tvc_topk_overlap");
+    REFUSED(tvc_topk_overlap(h, a, nullptr, M, La, Lb, 4, count, nullptr), TVC_E_INVALID, "tvc_topk_overlap");
+    REFUSED(tvc_topk_overlap(h, a, b, M, La, Lb, 4, nullptr, nullptr), TVC_E_INVALID, "tvc_topk_overlap");
     for (int k : {1, 3, 4, 64, 65, 1000, TVC_TOPK_OVERLAP_MAX_K}) OK(tvc_topk_overlap(h, a, b, M, La, Lb, k, count, nullptr));
     OK(tvc_topk_overlap(h, nullptr, nullptr, 0, La, Lb, 4, nullptr, nullptr));                     // M == 0: legal, no buffers
 

@@ -184,39 +184,17 @@ def test_bench_gpus_8_shard_bank_dry_run():
     assert out["shard_rows"] == [1_250_000] * 8 and out["collectives_ok"] is True
 
 
-def test_host_code_under_address_and_ub_sanitizers(pkg, tmp_path):
-    """the host side of the C-ABI -- tvc_abi.cpp, tvc_precise.cpp, tvc_split.cpp, tvc_sd.cpp: descriptor
-    validation, workspace sizing, name -> tensor maps, the arena's dry / real passes, prefix-string dispatch, options,
-    chunking, error paths -- built with ``g++ -fsanitize=address,undefined`` against a host stand-in of the HIP runtime
+def test_host_code_under_address_and_ub_sanitizers(pkg, tmp_path, tmp_path_factory):
+    """the host side of the C-ABI -- descriptor validation, workspace sizing, name -> tensor maps, the arena's
+    dry / real passes, prefix-string dispatch, options, chunking, error paths -- built with the sanitizers (the build of
+    tests/host_san_build.py) against a host stand-in of the HIP runtime
     (tests/host_san/hip/hip_runtime.h: "device" blocks with known sizes; kernels are no-ops generated from csrc/kernels.hpp,
     the GEMM launcher checks every operand / output range against its block) and driven through every entry point by
     tests/host_san/driver.cpp.  Leak detection on: every handle-owned device block must be released by tvc_destroy."""
-    import os
-    import subprocess
-    import sys
-    import torch
-    import importlib
-    csrc = ROOT / "multimodal-detection-consistency_amd" / "csrc"
-    san = ROOT / "tests" / "host_san"
-    stubs = tmp_path / "stubs.cpp"
-    subprocess.run([sys.executable, str(san / "gen_stubs.py"), str(csrc / "kernels.hpp"), str(stubs)], check=True)
+    import host_san_build
     # the toy latent-diffusion geometry of driver.cpp, tensors as the product's own host code prepares them
-    sdm = importlib.import_module(pkg.__name__ + ".sd_model")
-    arch = pkg.SDArch(block_out_channels=(64, 128), down_block_attn=(True, False), layers_per_block=1, heads=8,
-                      cross_attention_dim=128, vae_block_out_channels=(64, 128), vae_layers_per_block=1, sample_size=16)
-    uw, vw = pkg.make_sd_weights(arch, seed=3)
-    with open(tmp_path / "names.txt", "w") as f:
-        for n, x in sorted(sdm.prepare_sd_tensors(uw, vw, torch.device("cpu")).items()):
-            f.write(f"{n} {x.shape[0]} {x.numel() // x.shape[0]} {x.element_size()}\n")
-    exe = tmp_path / "driver"
-    cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           f"-I{san}", f"-I{csrc}", "-x", "c++"] + [str(csrc / f) for f in ("tvc_abi.cpp", "tvc_precise.cpp", "tvc_split.cpp", "tvc_sd.cpp", "tvc_sd_op.cpp", "tvc_tower_op.cpp")] + \
-          [str(stubs), str(san / "driver.cpp"), "-o", str(exe)]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([str(exe), str(tmp_path / "names.txt")], capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0 and "HOST_SAN_OK" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])
+    names = host_san_build.write_sd_names(pkg, tmp_path / "names.txt")
+    host_san_build.run_driver("host_san", "HOST_SAN_OK", tmp_path_factory, args=[names])
 
 
 def test_oracle_empty_component_semantics():

@@ -1,15 +1,14 @@
 """CPU: the radius-graph / DBSCAN C-ABI surface -- tvc_radius_graph / tvc_dbscan_sweep / tvc_dbscan_finish are declared in
 include/tvc.h, bound in _lib.SIGNATURES and exported by the built library without an ABI version bump, and their host code
 (tvc_dbscan.cpp: every refusal, the workspaces, the plan of host_plan.hpp) runs clean under AddressSanitizer / UBSan with leak
-detection (tests/host_san_dbscan/driver.cpp on tests/host_san's HIP stand-in, the build of test_attack_host.py plus
-tvc_dbscan.cpp)."""
-import os
+detection (tests/host_san_dbscan/driver.cpp on tests/host_san's HIP stand-in, built and run by tests/host_san_build.py)."""
 import re
 import subprocess
-import sys
 from pathlib import Path
 
 import pytest
+
+import host_san_build
 
 ROOT = Path(__file__).resolve().parents[1]
 NEW = {"tvc_radius_graph", "tvc_dbscan_sweep", "tvc_dbscan_finish"}
@@ -52,21 +51,8 @@ def test_reference_bank_config_validates_the_dbscan_fields(pkg):
             pkg.ReferenceBankConfig(**bad)
 
 
-def test_dbscan_host_code_under_address_and_ub_sanitizers(tmp_path):
-    csrc = ROOT / "multimodal-detection-consistency_amd" / "csrc"
-    san = ROOT / "tests" / "host_san"
-    stubs = tmp_path / "stubs.cpp"
-    subprocess.run([sys.executable, str(san / "gen_stubs.py"), str(csrc / "kernels.hpp"), str(stubs)], check=True)
+def test_dbscan_host_code_under_address_and_ub_sanitizers(tmp_path_factory):
+    stubs = host_san_build.stubs_text(tmp_path_factory)
     for name in ("launch_radius_graph", "launch_dbscan_sweep", "launch_dbscan_finish", "launch_kmeans_rownorm"):
-        assert name in stubs.read_text()
-    exe = tmp_path / "driver_dbscan"
-    srcs = ("tvc_abi.cpp", "tvc_precise.cpp", "tvc_split.cpp", "tvc_sd.cpp", "tvc_sd_op.cpp", "tvc_tower_op.cpp", "tvc_kmeans.cpp",
-            "tvc_ivf.cpp", "tvc_attack.cpp", "tvc_dbscan.cpp")
-    cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           f"-I{san}", f"-I{csrc}", "-x", "c++"] + [str(csrc / f) for f in srcs] + \
-          [str(stubs), str(ROOT / "tests" / "host_san_dbscan" / "driver.cpp"), "-o", str(exe)]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0 and "HOST_SAN_DBSCAN_OK" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])
+        assert name in stubs
+    host_san_build.run_driver("host_san_dbscan", "HOST_SAN_DBSCAN_OK", tmp_path_factory)

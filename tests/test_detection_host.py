@@ -1,15 +1,15 @@
 """CPU: the host half of the detection evaluation -- the declarations of the three entry points and the constants the engine
 mirrors, ``bootstrap_metric`` with a callable against the reference's loop, the signatures of the new surface, and the host code
 of tvc_roc.cpp (checks, refusals, chunking, the workspace; the plan of host_plan.hpp) under AddressSanitizer / UBSan with leak
-detection as a stand-alone program (tests/host_san_roc/driver.cpp on tests/host_san's HIP stand-in)."""
+detection as a stand-alone program (tests/host_san_roc/driver.cpp on tests/host_san's HIP stand-in, built and run by
+tests/host_san_build.py)."""
 import inspect
-import os
 import re
-import subprocess
-import sys
 from pathlib import Path
 
 import numpy as np
+
+import host_san_build
 
 ROOT = Path(__file__).resolve().parents[1]
 CSRC = ROOT / "multimodal-detection-consistency_amd" / "csrc"
@@ -109,17 +109,5 @@ def test_bootstrap_metric_with_a_callable_is_the_reference_loop(pkg):
         pkg.bootstrap_metric("auroc", scores, labels)
 
 
-def test_roc_host_code_under_address_and_ub_sanitizers(tmp_path):
-    san = ROOT / "tests" / "host_san"
-    stubs = tmp_path / "stubs.cpp"
-    subprocess.run([sys.executable, str(san / "gen_stubs.py"), str(CSRC / "kernels.hpp"), str(stubs)], check=True)
-    exe = tmp_path / "driver_roc"
-    srcs = ("tvc_abi.cpp", "tvc_precise.cpp", "tvc_split.cpp", "tvc_sd.cpp", "tvc_sd_op.cpp", "tvc_tower_op.cpp", "tvc_roc.cpp")
-    cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           f"-I{san}", f"-I{CSRC}", "-x", "c++"] + [str(CSRC / f) for f in srcs] + \
-          [str(stubs), str(ROOT / "tests" / "host_san_roc" / "driver.cpp"), "-o", str(exe)]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0 and "HOST_SAN_ROC_OK" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])
+def test_roc_host_code_under_address_and_ub_sanitizers(tmp_path_factory):
+    host_san_build.run_driver("host_san_roc", "HOST_SAN_ROC_OK", tmp_path_factory)

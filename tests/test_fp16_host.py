@@ -1,12 +1,12 @@
 """CPU: the fp16 tower mode's C-ABI surface (TVC_OPT_TOWER_PRECISION = 3) -- the new entry points are declared in
 include/tvc.h, bound in _lib.SIGNATURES and exported by the built library, and the host code that drives the mode runs
 clean under AddressSanitizer / UBSan with every GEMM range checked (tests/host_san_f16/driver.cpp on tests/host_san's HIP
-stand-in, the same build as test_abi_and_host.py::test_host_code_under_address_and_ub_sanitizers)."""
-import os
+stand-in, built and run by tests/host_san_build.py)."""
 import re
 import subprocess
-import sys
 from pathlib import Path
+
+import host_san_build
 
 ROOT = Path(__file__).resolve().parents[1]
 NEW = {"tvc_set_weights_f16", "tvc_gemm_f16", "tvc_attention_f16", "tvc_layernorm_f16"}
@@ -26,17 +26,5 @@ def test_fp16_entry_points_declared_bound_and_exported(pkg):
     assert pkg.TVCEngine.PRECISIONS["fp16"] == 3
 
 
-def test_fp16_mode_host_code_under_address_and_ub_sanitizers(tmp_path):
-    csrc = ROOT / "multimodal-detection-consistency_amd" / "csrc"
-    san = ROOT / "tests" / "host_san"
-    stubs = tmp_path / "stubs.cpp"
-    subprocess.run([sys.executable, str(san / "gen_stubs.py"), str(csrc / "kernels.hpp"), str(stubs)], check=True)
-    exe = tmp_path / "driver_f16"
-    cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           f"-I{san}", f"-I{csrc}", "-x", "c++"] + [str(csrc / f) for f in ("tvc_abi.cpp", "tvc_precise.cpp", "tvc_split.cpp", "tvc_sd.cpp", "tvc_sd_op.cpp", "tvc_tower_op.cpp")] + \
-          [str(stubs), str(ROOT / "tests" / "host_san_f16" / "driver.cpp"), "-o", str(exe)]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0 and "HOST_SAN_F16_OK" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])
+def test_fp16_mode_host_code_under_address_and_ub_sanitizers(tmp_path_factory):
+    host_san_build.run_driver("host_san_f16", "HOST_SAN_F16_OK", tmp_path_factory)

@@ -1,13 +1,13 @@
 """CPU: the IVF C-ABI surface -- tvc_ivf_probe / tvc_ivf_scan are declared in include/tvc.h, bound in _lib.SIGNATURES and
 exported by the built library without an ABI version bump; host_plan.hpp's ivf_scan_plan holds its promises over a sweep of
 sizes under UBSan; and the host code (tvc_ivf.cpp: refusals, workspaces, chunking) runs clean under AddressSanitizer / UBSan
-with leak detection (tests/host_san_ivf/driver.cpp on tests/host_san's HIP stand-in, the build of test_kmeans_host.py plus
-tvc_ivf.cpp)."""
-import os
+with leak detection (tests/host_san_ivf/driver.cpp on tests/host_san's HIP stand-in, built and run by
+tests/host_san_build.py)."""
 import re
 import subprocess
-import sys
 from pathlib import Path
+
+import host_san_build
 
 ROOT = Path(__file__).resolve().parents[1]
 NEW = {"tvc_ivf_probe", "tvc_ivf_scan"}
@@ -104,18 +104,5 @@ def test_ivf_scan_plan_under_ubsan(tmp_path):
     assert r.returncode == 0 and "PLAN_OK" in r.stdout, (r.stdout, r.stderr)
 
 
-def test_ivf_host_code_under_address_and_ub_sanitizers(tmp_path):
-    csrc = ROOT / "multimodal-detection-consistency_amd" / "csrc"
-    san = ROOT / "tests" / "host_san"
-    stubs = tmp_path / "stubs.cpp"
-    subprocess.run([sys.executable, str(san / "gen_stubs.py"), str(csrc / "kernels.hpp"), str(stubs)], check=True)
-    exe = tmp_path / "driver_ivf"
-    srcs = ("tvc_abi.cpp", "tvc_precise.cpp", "tvc_split.cpp", "tvc_sd.cpp", "tvc_sd_op.cpp", "tvc_tower_op.cpp", "tvc_kmeans.cpp", "tvc_ivf.cpp")
-    cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           f"-I{san}", f"-I{csrc}", "-x", "c++"] + [str(csrc / f) for f in srcs] + \
-          [str(stubs), str(ROOT / "tests" / "host_san_ivf" / "driver.cpp"), "-o", str(exe)]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0 and "HOST_SAN_IVF_OK" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])
+def test_ivf_host_code_under_address_and_ub_sanitizers(tmp_path_factory):
+    host_san_build.run_driver("host_san_ivf", "HOST_SAN_IVF_OK", tmp_path_factory)

@@ -3,17 +3,17 @@
 methods and the batch forms), the five entry points are declared in include/tvc.h, bound in _lib.SIGNATURES and exported by the
 built library without an ABI version bump, no other source references their unit, and the host code (tvc_sim.cpp: every
 refusal, the empty calls, the workspace sizing of host_plan.hpp) runs clean under AddressSanitizer / UBSan with leak detection
-(tests/host_san_sim/driver.cpp, a stand-alone program on tests/host_san's HIP stand-in: the build of
-test_retrieval_host_san.py with tvc_sim.cpp in place of tvc_rank.cpp)."""
+(tests/host_san_sim/driver.cpp, a stand-alone program on tests/host_san's HIP stand-in, built and run by
+tests/host_san_build.py)."""
 import dataclasses
 import inspect
-import os
 import re
 import subprocess
-import sys
 from pathlib import Path
 
 import pytest
+
+import host_san_build
 
 ROOT = Path(__file__).resolve().parents[1]
 NEW = {"tvc_sim_rows", "tvc_sim_flat_workspace", "tvc_sim_flat_rank", "tvc_sim_flat", "tvc_topk_overlap"}
@@ -79,21 +79,8 @@ def test_no_existing_source_references_the_sim_unit():
                 assert name not in text, (p.name, name)
 
 
-def test_sim_host_code_under_address_and_ub_sanitizers(tmp_path):
-    csrc = ROOT / "multimodal-detection-consistency_amd" / "csrc"
-    san = ROOT / "tests" / "host_san"
-    stubs = tmp_path / "stubs.cpp"
-    subprocess.run([sys.executable, str(san / "gen_stubs.py"), str(csrc / "kernels.hpp"), str(stubs)], check=True)
-    text = stubs.read_text()
+def test_sim_host_code_under_address_and_ub_sanitizers(tmp_path_factory):
+    text = host_san_build.stubs_text(tmp_path_factory)
     for name in ("launch_sim_rows", "launch_sim_flat_rank", "launch_sim_flat", "launch_topk_overlap"):
         assert name in text, name
-    exe = tmp_path / "driver_sim"
-    srcs = ("tvc_abi.cpp", "tvc_precise.cpp", "tvc_split.cpp", "tvc_sd.cpp", "tvc_sd_op.cpp", "tvc_tower_op.cpp", "tvc_sim.cpp")
-    cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           f"-I{san}", f"-I{csrc}", "-x", "c++"] + [str(csrc / f) for f in srcs] + \
-          [str(stubs), str(ROOT / "tests" / "host_san_sim" / "driver.cpp"), "-o", str(exe)]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env=env)       # run directly: nothing is preloaded
-    assert r.returncode == 0 and "HOST_SAN_SIM_OK" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])
+    host_san_build.run_driver("host_san_sim", "HOST_SAN_SIM_OK", tmp_path_factory)              # run directly: nothing is preloaded

@@ -3,15 +3,15 @@ tvc_graph_pair_fill / tvc_pair_cosine are declared in include/tvc.h, bound in _l
 without an ABI version bump; the engine and package names exist; the configuration validates; no other translation unit
 references tvc_pairs.cpp; and its host code (every refusal, P == 0, the launch plan of host_plan.hpp) runs clean under
 AddressSanitizer / UBSan with leak detection in a stand-alone program (tests/host_san_pairs/driver.cpp on tests/host_san's HIP
-stand-in, the build of test_dbscan_host.py plus tvc_pairs.cpp, nothing preloaded)."""
+stand-in, built and run by tests/host_san_build.py, nothing preloaded)."""
 import json
-import os
 import re
 import subprocess
-import sys
 from pathlib import Path
 
 import pytest
+
+import host_san_build
 
 ROOT = Path(__file__).resolve().parents[1]
 NEW = {"tvc_graph_pair_count", "tvc_graph_pair_fill", "tvc_pair_cosine"}
@@ -114,22 +114,8 @@ def test_no_other_source_references_the_pairs_unit():
     assert " pairs.hip" in mk and " tvc_pairs.cpp" in mk
 
 
-def test_pairs_host_code_under_address_and_ub_sanitizers(tmp_path):
-    csrc = ROOT / "multimodal-detection-consistency_amd" / "csrc"
-    san = ROOT / "tests" / "host_san"
-    stubs = tmp_path / "stubs.cpp"
-    subprocess.run([sys.executable, str(san / "gen_stubs.py"), str(csrc / "kernels.hpp"), str(stubs), "--trace"], check=True)
+def test_pairs_host_code_under_address_and_ub_sanitizers(tmp_path, tmp_path_factory):
+    stubs = host_san_build.stubs_text(tmp_path_factory)
     for name in ("launch_graph_pair_count", "launch_graph_pair_fill", "launch_pair_cosine"):
-        assert name in stubs.read_text()
-    exe = tmp_path / "driver_pairs"
-    srcs = ("tvc_abi.cpp", "tvc_precise.cpp", "tvc_split.cpp", "tvc_sd.cpp", "tvc_sd_op.cpp", "tvc_tower_op.cpp", "tvc_kmeans.cpp",
-            "tvc_ivf.cpp", "tvc_attack.cpp", "tvc_dbscan.cpp", "tvc_pairs.cpp")
-    cmd = ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           f"-I{san}", f"-I{csrc}", "-x", "c++"] + [str(csrc / f) for f in srcs] + \
-          [str(stubs), str(ROOT / "tests" / "host_san_pairs" / "driver.cpp"), "-o", str(exe)]
-    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1",
-               HIP_STUB_TRACE=str(tmp_path / "trace.txt"))
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0 and "HOST_SAN_PAIRS_OK" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])
+        assert name in stubs
+    host_san_build.run_driver("host_san_pairs", "HOST_SAN_PAIRS_OK", tmp_path_factory, trace=tmp_path / "trace.txt")
